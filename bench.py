@@ -16,10 +16,15 @@ N>1: windows are sharded contiguously, no collective in the forward; the scoring
 sensor's order statistics over ALL ticks: one all-to-all by sensor + an all-gather of the [N,2]
 median/IQR table (gdn_amd/harness.distributed_anomaly).
 
-Prints ONE JSON line on rank 0.  Extra objects: `roofline` (the gather-aggregate kernel K8 the
-north star names, measured live with HIP events in a staged-pipeline leg of this same process),
-`roofline_fused` (the fused kernel that dominates the timed region), `cpu_baseline` (the oracle,
-op-faithful CPU port, on a bounded sample; N=1 only).
+Prints ONE JSON line on rank 0.  A plain run measures the headline only: set-up, --warmup steps, a pre-roll to
+steady clocks, EXACTLY --steps timed steps, the result line.  `--dump-outputs DIR` then also writes what the last
+timed step computed (`dump_outputs`).  `--full` adds everything else, measured in the same process:
+`roofline` (the gather-aggregate kernel K8 the north star names, measured live with HIP events in a
+staged-pipeline leg), `roofline_fused` (the fused kernel that dominates the timed region), their bf16 and
+launch-size sweeps, the bf16-storage / per-batch-launch / raw-series variants of the step, `train_step`,
+`streaming_copy` and `cpu_baseline` (the oracle, op-faithful CPU port, on a bounded sample; N=1 only).
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
 """
 import argparse
 import json
@@ -33,6 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT = 60 << 20          # --dump-outputs: array bytes over every rank (< 64 MB with the .npy headers)
 N_SENSORS, WINDOW, TOPK, DIM = 127, 15, 30, 64
 # --workload: the headline is BASELINE configs[2]; configs[4] (the WADI-shape stress case) is a second line
 WORKLOADS = {
@@ -297,6 +303,28 @@ def cpu_baseline(params, budget_s=12.0):
             "host_logical_cpus": os.cpu_count()}
 
 
+def dump_outputs(outdir, arrays, limit, suffix=""):
+    """Write each array of `arrays` (name -> float32 / float64 device tensor, in order of importance) as
+    `outdir/<name><suffix>.npy`.  An array that does not fit in what is left of `limit` bytes is replaced by
+    `<name>_sample<suffix>.npy`: a fixed, seeded choice of its rows (ascending), the same for every run of the
+    same shape, so two builds can still be compared row for row."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    left = limit
+    for name, a in arrays.items():
+        a = a.detach()
+        assert a.dtype in (torch.float32, torch.float64), (name, a.dtype)
+        if a.numel() * a.element_size() > left:
+            keep = left // (a[0].numel() * a.element_size())
+            if keep == 0:
+                continue
+            rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a, name = a[rows.to(a.device)], name + "_sample"
+        out = a.cpu().numpy()
+        np.save(os.path.join(outdir, name + suffix + ".npy"), out)
+        left -= out.nbytes
+
+
 def main():
     # stdout carries exactly one JSON line: RCCL prints a version banner to stdout when the first
     # communicator is created, so everything else goes to stderr until the result is ready
@@ -321,7 +349,7 @@ def run():
     ap.add_argument("--coalesce", type=int, default=64,
                     help="consecutive minibatches of the resident series sent as one launch (1 = per-batch launches)")
     ap.add_argument("--ticks", type=int, default=32768, help="windows per rank per step (SURVEY §8d)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of --steps steps each; the median is reported")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--streams", type=int, default=3,
                     help="side streams the forward launches of a step rotate over (matters with --coalesce 1: one launch "
@@ -332,13 +360,18 @@ def run():
     ap.add_argument("--exchange-chunk", type=int, default=32768,
                     help="N>1: ticks per async all-to-all of the scoring keys (overlaps the following forward chunks)")
     ap.add_argument("--sweep-max", type=int, default=262144,
-                    help="largest launch of the K8 roofline sweep (0 = stop at --ticks)")
-    ap.add_argument("--skip-cpu", action="store_true")
+                    help="--full: largest launch of the K8 roofline sweep (0 = stop at --ticks)")
+    ap.add_argument("--skip-cpu", action="store_true", help="--full: leave out cpu_baseline")
     ap.add_argument("--rehearse-dist", action="store_true",
                     help="1 rank, but run the N>1 step (RCCL process group, all-to-all scoring exchange)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="swat",
                     help="swat = BASELINE configs[2] (the headline); config4 = the 512-sensor stress shape")
     ap.add_argument("--dim", type=int, default=64, help="embedding / hidden width d (config4 is quoted at 64 and 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines and sweeps, the step's variants, train step, streaming copy, "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     args = ap.parse_args()
     global N_SENSORS, WINDOW, TOPK, DIM
     wl = WORKLOADS[args.workload]
@@ -371,6 +404,8 @@ def run():
     if world == 1 and not args.rehearse_dist:
         step = ev.step
         step_impl = "SeriesEvaluator: forward launches + device scoring, one HIP graph replay per step"
+        # what a caller of the step holds afterwards: the returned anomaly score, the predictions, the scoring table
+        outputs = lambda anomaly: {"anomaly": anomaly, "med_iqr": ev.med_iqr, "pred": ev.pred}
     else:
         # N>1: windows shard by rank with no collective in the forward; the scoring exchange (all-to-all of
         # the radix keys by sensor) is issued per chunk of ticks and overlaps the forward of the following
@@ -384,36 +419,39 @@ def run():
         step = sev.step
         step_impl = ("ShardedEvaluator: compute segments replayed from HIP graphs" if sev._graphs is not None else
                      "ShardedEvaluator: eager launches") + ", async all_to_all_single per chunk + one all_gather (eager RCCL)"
+        outputs = lambda anomaly: {"anomaly": anomaly, "pred": sev.pred}     # this rank's ticks
 
-    # Kernel-level legs first, on every rank (their results are only reported by rank 0): K8 and fused
-    # roofline with HIP events, each after its own ~60 ms of sustained launches.  Besides producing the
-    # roofline numbers this leaves the GPU at steady clocks when the W warm-up steps begin — it needs ~50 ms
-    # of load after an idle period to get there (tools/probe_ramp.py), and W steps alone are a few ms.
-    launches_for = lambda b: max(12, min(64, 65536 // b))
-    sizes = sorted({batch, min(4096, t), launch_batch, t})      # 4096: the launch size rounds 1-2 quoted
-    sweep = [k8_roofline(model, x, b, launches=launches_for(b)) for b in sizes]
-    if world == 1 and args.sweep_max > t and args.workload == "swat":   # the largest per-GPU launch
-        xbig = torch.rand((args.sweep_max, N_SENSORS, WINDOW), device=device)     # 2 GB; xlin + z: 17 GB
-        sweep.append(k8_roofline(model, xbig, args.sweep_max, launches=12))
-        del xbig
-        torch.cuda.empty_cache()
-    fused_leg = fused_roofline(model, x, ev.pred, launch_batch, launches=launches_for(launch_batch))
-    fused_sweep = [fused_leg if b == launch_batch else fused_roofline(model, x, ev.pred, b, launches=launches_for(b))
-                   for b in sizes]
-    # BASELINE configs[2] says bf16: the same kernels with x / xlin / z stored in bf16 (fp32 arithmetic)
-    sweep_bf16 = [r for r in (k8_roofline(model, x, b, launches=launches_for(b), storage="bf16") for b in sizes)
-                  if r is not None]
-    fused_leg_bf16 = fused_roofline(model, x, ev.pred, launch_batch, launches=launches_for(launch_batch), storage="bf16")
+    if args.full:
+        # Kernel-level legs first, on every rank (their results are only reported by rank 0): K8 and fused
+        # roofline with HIP events, each after its own ~60 ms of sustained launches.
+        launches_for = lambda b: max(12, min(64, 65536 // b))
+        sizes = sorted({batch, min(4096, t), launch_batch, t})      # 4096: the launch size rounds 1-2 quoted
+        sweep = [k8_roofline(model, x, b, launches=launches_for(b)) for b in sizes]
+        if world == 1 and args.sweep_max > t and args.workload == "swat":   # the largest per-GPU launch
+            xbig = torch.rand((args.sweep_max, N_SENSORS, WINDOW), device=device)     # 2 GB; xlin + z: 17 GB
+            sweep.append(k8_roofline(model, xbig, args.sweep_max, launches=12))
+            del xbig
+            torch.cuda.empty_cache()
+        fused_leg = fused_roofline(model, x, ev.pred, launch_batch, launches=launches_for(launch_batch))
+        fused_sweep = [fused_leg if b == launch_batch else fused_roofline(model, x, ev.pred, b, launches=launches_for(b))
+                       for b in sizes]
+        # BASELINE configs[2] says bf16: the same kernels with x / xlin / z stored in bf16 (fp32 arithmetic)
+        sweep_bf16 = [r for r in (k8_roofline(model, x, b, launches=launches_for(b), storage="bf16") for b in sizes)
+                      if r is not None]
+        fused_leg_bf16 = fused_roofline(model, x, ev.pred, launch_batch, launches=launches_for(launch_batch),
+                                        storage="bf16")
 
     def timed(fn, steps):
-        """`steps` steps bracketed by barrier + synchronize on both sides; max over ranks."""
+        """`steps` steps bracketed by barrier + synchronize on both sides; max over ranks.  Returns (seconds,
+        what the last step returned)."""
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        out = None
         for _ in range(steps):
-            fn()
+            out = fn()
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -423,25 +461,28 @@ def run():
             tmax = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        return dt
+        return dt, out
 
     def preroll(fn, ms=120.0):
         """>= `ms` of back-to-back steps right before a timed region (not part of --warmup): this GPU needs
         ~50 ms of sustained load after an idle period to reach its steady clocks (tools/probe_ramp.py), and a
         20-step region is 14 ms.  The step count is agreed across ranks (the N>1 step contains collectives)."""
-        per_step = timed(fn, 8) / 8
+        per_step = timed(fn, 8)[0] / 8
         for _ in range(int(ms * 1e-3 / max(per_step, 1e-6)) + 1):
             fn()
 
     for _ in range(args.warmup):
         step()
-    # the timed region: EXACTLY --steps steps, repeated (each repeat after its own pre-roll); the median
-    # repeat is the reported one, all of them are listed
+    # the timed region: EXACTLY --steps steps, after a pre-roll; with --repeats R > 1 it is repeated (each repeat
+    # after its own pre-roll), the median repeat is the reported one, all of them are listed
     repeats = []
     for _ in range(max(1, args.repeats)):
         preroll(step)
-        repeats.append(timed(step, args.steps))
+        dt, last = timed(step, args.steps)
+        repeats.append(dt)
     elapsed = sorted(repeats)[len(repeats) // 2]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs(last), DUMP_LIMIT // world, f"_rank{rank}" if world > 1 else "")
 
     result = None
     if rank == 0:
@@ -465,65 +506,66 @@ def run():
                        if world > 1 else "single GPU"},
         }
         result["timed_regions_ms_per_step"] = [round(1e3 * r / args.steps, 4) for r in repeats]
-    if rank == 0:
-        # the launch size the timed region uses
-        result["roofline"] = next(r for r in sweep if r["batch"] == launch_batch)
-        result["roofline_sweep"] = [{"batch": r["batch"], "achieved": r["achieved"], "frac": r["frac"],
-                                     "launch_us": r["launch_us"]} for r in sweep]
-        result["roofline_fused"] = fused_leg
-        result["roofline_fused_sweep"] = [{"batch": r["batch"], "launch_us": r["launch_us"], "windows_per_s": r["windows_per_s"]}
-                                          for r in fused_sweep]
-        if sweep_bf16:
-            result["roofline_bf16"] = next(r for r in sweep_bf16 if r["batch"] == launch_batch)
-            result["roofline_bf16_sweep"] = [{"batch": r["batch"], "achieved": r["achieved"], "frac": r["frac"],
-                                              "launch_us": r["launch_us"]} for r in sweep_bf16]
-        result["roofline_fused_bf16"] = fused_leg_bf16
-        if args.coalesce > 1 and world == 1 and not args.rehearse_dist:      # transparency: the same step with one launch per logical minibatch
-            ev1 = harness.SeriesEvaluator(model, x, y, batch=batch, use_graph=not args.no_graph, streams=args.streams)
-            for _ in range(args.warmup):
-                ev1.step()
-            preroll(ev1.step)
-            result["value_per_batch_launches"] = round(t * args.steps / timed(ev1.step, args.steps), 1)
-    if rank == 0 and world == 1 and not args.rehearse_dist:
-        # the same step on bf16-stored windows (BASELINE configs[2] wording; `value` stays the fp32 line)
-        evb = harness.SeriesEvaluator(model, x.bfloat16(), y, batch=batch, use_graph=not args.no_graph,
-                                      streams=args.streams, coalesce=args.coalesce)
-        for _ in range(args.warmup):
-            evb.step()
-        preroll(evb.step)
-        result["value_bf16_storage"] = round(t * args.steps / timed(evb.step, args.steps), 1)
-        del evb
-    if rank == 0 and world == 1 and not args.rehearse_dist:
-        # the same step with the windows built in-kernel from the raw [N, T+W] series
-        raw = torch.rand((N_SENSORS, t + WINDOW), generator=torch.Generator().manual_seed(7)).to(device)
-        ev2 = harness.SeriesEvaluator(model, None, raw[:, WINDOW:].t().contiguous(), batch=batch,
-                                      use_graph=not args.no_graph, streams=args.streams, coalesce=args.coalesce,
-                                      series=raw)
-        from gdn_amd._lib import GdnHipError
-        try:
-            for _ in range(args.warmup):
-                ev2.step()
-            preroll(ev2.step)
-            result["value_windows_from_raw_series"] = round(t * args.steps / timed(ev2.step, args.steps), 1)
-        except GdnHipError as exc:      # n > 127 with n * w beyond the row-gather kernel's in-kernel window addressing
-            result["value_windows_from_raw_series"] = None
-            result["value_windows_from_raw_series_note"] = f"not available at this shape: {exc}"
-        del ev2, raw
-    # training step (BASELINE configs[3] with several ranks): every rank takes part in the gradient all-reduce
-    if args.workload == "swat" or world == 1:
-        from gdn_amd import _lib
-        if _lib.load().gdn_train_supported(N_SENSORS, WINDOW, DIM, TOPK):
-            line = train_step_line(device, n=x.shape[1], w=x.shape[2], batch=args.batch, dist=dist,
-                                   split=world > 1 or args.rehearse_dist)
-        else:       # e.g. > ~600 sensors: not even a 64-column slice of the backward's [n+1, d] fp32 tile fits LDS
-            line = {"ms_per_step": None, "note": "gdn_train_supported() == 0 at this shape (the backward's tile slice "
-                                                  "exceeds the 160 KB of LDS)"}
+    if args.full:
         if rank == 0:
-            result["train_step"] = line
-    if rank == 0 and world == 1:
-        result["streaming_copy"] = streaming_copy_rate(device)
-        if not args.skip_cpu:
-            result["cpu_baseline"] = cpu_baseline(params)
+            # the launch size the timed region uses
+            result["roofline"] = next(r for r in sweep if r["batch"] == launch_batch)
+            result["roofline_sweep"] = [{"batch": r["batch"], "achieved": r["achieved"], "frac": r["frac"],
+                                         "launch_us": r["launch_us"]} for r in sweep]
+            result["roofline_fused"] = fused_leg
+            result["roofline_fused_sweep"] = [{"batch": r["batch"], "launch_us": r["launch_us"], "windows_per_s": r["windows_per_s"]}
+                                              for r in fused_sweep]
+            if sweep_bf16:
+                result["roofline_bf16"] = next(r for r in sweep_bf16 if r["batch"] == launch_batch)
+                result["roofline_bf16_sweep"] = [{"batch": r["batch"], "achieved": r["achieved"], "frac": r["frac"],
+                                                  "launch_us": r["launch_us"]} for r in sweep_bf16]
+            result["roofline_fused_bf16"] = fused_leg_bf16
+            if args.coalesce > 1 and world == 1 and not args.rehearse_dist:      # transparency: the same step with one launch per logical minibatch
+                ev1 = harness.SeriesEvaluator(model, x, y, batch=batch, use_graph=not args.no_graph, streams=args.streams)
+                for _ in range(args.warmup):
+                    ev1.step()
+                preroll(ev1.step)
+                result["value_per_batch_launches"] = round(t * args.steps / timed(ev1.step, args.steps)[0], 1)
+        if rank == 0 and world == 1 and not args.rehearse_dist:
+            # the same step on bf16-stored windows (BASELINE configs[2] wording; `value` stays the fp32 line)
+            evb = harness.SeriesEvaluator(model, x.bfloat16(), y, batch=batch, use_graph=not args.no_graph,
+                                          streams=args.streams, coalesce=args.coalesce)
+            for _ in range(args.warmup):
+                evb.step()
+            preroll(evb.step)
+            result["value_bf16_storage"] = round(t * args.steps / timed(evb.step, args.steps)[0], 1)
+            del evb
+        if rank == 0 and world == 1 and not args.rehearse_dist:
+            # the same step with the windows built in-kernel from the raw [N, T+W] series
+            raw = torch.rand((N_SENSORS, t + WINDOW), generator=torch.Generator().manual_seed(7)).to(device)
+            ev2 = harness.SeriesEvaluator(model, None, raw[:, WINDOW:].t().contiguous(), batch=batch,
+                                          use_graph=not args.no_graph, streams=args.streams, coalesce=args.coalesce,
+                                          series=raw)
+            from gdn_amd._lib import GdnHipError
+            try:
+                for _ in range(args.warmup):
+                    ev2.step()
+                preroll(ev2.step)
+                result["value_windows_from_raw_series"] = round(t * args.steps / timed(ev2.step, args.steps)[0], 1)
+            except GdnHipError as exc:      # n > 127 with n * w beyond the row-gather kernel's in-kernel window addressing
+                result["value_windows_from_raw_series"] = None
+                result["value_windows_from_raw_series_note"] = f"not available at this shape: {exc}"
+            del ev2, raw
+        # training step (BASELINE configs[3] with several ranks): every rank takes part in the gradient all-reduce
+        if args.workload == "swat" or world == 1:
+            from gdn_amd import _lib
+            if _lib.load().gdn_train_supported(N_SENSORS, WINDOW, DIM, TOPK):
+                line = train_step_line(device, n=x.shape[1], w=x.shape[2], batch=args.batch, dist=dist,
+                                       split=world > 1 or args.rehearse_dist)
+            else:       # e.g. > ~600 sensors: not even a 64-column slice of the backward's [n+1, d] fp32 tile fits LDS
+                line = {"ms_per_step": None, "note": "gdn_train_supported() == 0 at this shape (the backward's tile slice "
+                                                      "exceeds the 160 KB of LDS)"}
+            if rank == 0:
+                result["train_step"] = line
+        if rank == 0 and world == 1:
+            result["streaming_copy"] = streaming_copy_rate(device)
+            if not args.skip_cpu:
+                result["cpu_baseline"] = cpu_baseline(params)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

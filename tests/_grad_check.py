@@ -27,6 +27,7 @@ KINK_BAND = 1e-6        # a (Leaky)ReLU input closer to 0 than this can fall on 
                         # pre-activation behind a BatchNorm is ~3e-7; observed: flipped at 2.8e-7 and 8e-7, not at 1.8e-6)
 TOL_MAX = 2e-5          # max |d| <= TOL_MAX * max|g| per tensor
 TOL_ELEM = 1e-2         # |d| <= TOL_ELEM * max(|g|, 1e-3 max|g|) per element
+TOL_ZERO = 1e-6         # a zero gradient: max |g| < TOL_ZERO * (the step's largest float64 gradient)
 NOISE_FLOOR = 1e-12     # a parameter whose float64 gradient is below this everywhere has a true gradient of 0
 
 
@@ -153,11 +154,11 @@ def _group_of(name):
     return name.rsplit(".", 1)[0] + ".<weight|bias>" if name.endswith((".weight", ".bias")) else name
 
 
-def assert_grads_close(got, want, tol_max=TOL_MAX, tol_elem=TOL_ELEM, what=""):
+def assert_grads_close(got, want, tol_max=TOL_MAX, tol_elem=TOL_ELEM, what="", tol_zero=TOL_ZERO):
     """Every tensor of `got` (name -> fp32 gradient) against its float64 value, relative to the largest entry of
     its group (`_group_of`; same-shape members only) and, element by element, relative to the element.
-    Zero-gradient parameters (a bias in front of a train-mode BatchNorm) must come out as rounding noise.
-    Returns the worst ratios seen (for reports)."""
+    Zero-gradient parameters (a bias in front of a train-mode BatchNorm) must come out as rounding noise: below
+    `tol_zero` of the step's largest gradient.  Returns the worst ratios seen (for reports)."""
     tops = {}
     for name, w in want.items():
         key = (_group_of(name), tuple(w.shape))
@@ -167,7 +168,7 @@ def assert_grads_close(got, want, tol_max=TOL_MAX, tol_elem=TOL_ELEM, what=""):
     for name, w in want.items():
         g = got[name].detach().cpu().to(f64).reshape(w.shape)
         if float(w.abs().max()) < NOISE_FLOOR:
-            assert float(g.abs().max()) < 1e-6 * everything, (what, name, "expected rounding noise", float(g.abs().max()))
+            assert float(g.abs().max()) < tol_zero * everything, (what, name, "expected rounding noise", float(g.abs().max()))
             continue
         top = tops[(_group_of(name), tuple(w.shape))]
         diff = (g - w).abs()

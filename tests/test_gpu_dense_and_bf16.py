@@ -134,7 +134,7 @@ def test_planned_launch_equals_the_plain_entry_point(bf16, gpu_device):
     np.testing.assert_allclose(again.cpu().numpy(), plain2.cpu().numpy(), atol=2e-7, rtol=0)
 
 
-def test_valu_and_dense_fused_paths_agree(gpu_device):
+def test_valu_and_dense_fused_paths_agree(gpu_device, tmp_path):
     """The fp32 VALU row-gather kernel (GDN_FUSED_PATH=valu, also the path of every shape the dense kernels
     do not take) and the matrix-core kernel on the same inputs, in two processes (the choice is read once)."""
     import os
@@ -148,7 +148,7 @@ def test_valu_and_dense_fused_paths_agree(gpu_device):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for path in ("dense", "valu"):
-        f = f"/tmp/gdn_path_{path}.pt"
+        f = str(tmp_path / f"gdn_path_{path}.pt")
         subprocess.run([sys.executable, "-c", code % (root, root), f], check=True,
                        env=dict(os.environ, GDN_FUSED_PATH=path))
         outs.append(torch.load(f, weights_only=True))

@@ -456,8 +456,11 @@ def test_evaluator_and_training_on_raw_unit_series(gpu_device):
     assert abs(loss - ref_loss) <= 1e-5 * ref_loss
     assert all(bool(torch.isfinite(v).all()) for v in got.values())
     # (logits are O(1e5) here: the softmax is one-hot and its gradient is what survives cancellation, so fp32 —
-    # any fp32 — keeps 3 digits of the attention gradients, not 5: bounds widened accordingly)
-    assert_grads_close(got, want, tol_max=1e-3, tol_elem=0.5, what="raw-unit training step")
+    # any fp32 — keeps 3 digits of the attention gradients, not 5: bounds widened accordingly.  The same holds for
+    # d_att_i, exactly 0 in float64: a target whose logits are all negative gets d_s_i = -0.8 * sum(alpha * (d_pi -
+    # dot)), about one fp32 ulp of `dot` (gdn_backward.hip pass 1), and d_att_i multiplies it by the O(1e5) inputs.
+    # Measured: 0.476 = 4.7e-6 of the step's largest gradient, 6e-5 of d_att_j)
+    assert_grads_close(got, want, tol_max=1e-3, tol_elem=0.5, what="raw-unit training step", tol_zero=1e-5)
 
 
 def test_range_guard_inside_a_user_captured_graph(gpu_device):

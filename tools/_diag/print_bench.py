@@ -1,4 +1,4 @@
-"""stdin: one bench.py JSON line -> the few numbers an A/B run compares.  usage: python bench.py ... | python tools/_diag/print_bench.py [label]"""
+"""stdin: one bench.py JSON line -> the few numbers an A/B run compares.  usage: python bench.py --full ... | python tools/_diag/print_bench.py [label]"""
 import json
 import sys
 r = json.loads(sys.stdin.read())

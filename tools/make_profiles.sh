@@ -11,8 +11,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ $PART = all ] || [ $PART = bench ]; then
   # (a) kernel trace + stats of the bench command itself, then the un-profiled bench line
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $ROOT/bench.py --steps 20 --warmup 5 --skip-cpu > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
-  (cd $ROOT && python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err)
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $ROOT/bench.py --steps 20 --warmup 5 --full --skip-cpu > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+  (cd $ROOT && python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err)
 fi
 if [ $PART = all ] || [ $PART = kernels ]; then
   # (b) one launch size per file: fused / staged kernels, fp32 and bf16 storage
