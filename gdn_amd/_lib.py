@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GDN_HIP_LIB", os.path.join(_HERE, "libgdn_hip.so"))   # override: diagnostic builds
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _c_int, _c_float, _p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -23,6 +23,8 @@ SIGNATURES = {
     "gdn_node_terms": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p],
     "gdn_bn_fold": [_p, _p, _p, _p, _c_float, _c_int, _p, _p],
     "gdn_project_fwd": [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "gdn_project_fwd_series": [_p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "gdn_tile_fits": [_c_int] * 4,
     "gdn_attn_aggregate_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
     "gdn_head_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p],
     "gdn_head_train_fwd": [_p] * 10 + [_c_float] + [_c_int] * 3 + [_c_float] * 4 + [_p] * 9,

@@ -636,7 +636,9 @@ static int attn_aggregate_bwd_impl(const float* d_z, const float* xlin, const fl
     // whole or (d = 128) as two 64-column slices the workgroup walks one after the other
     glb = true;
     if (!bwd_plan(batch, n, d, k, false, &pl)) {
-      if (d != 128 || !bwd_plan(batch, n, d, k, false, &pl, 64)) return GDN_ERR_UNSUPPORTED;
+      if (d != 128 || !bwd_plan(batch, n, d, k, false, &pl, 64))   // beyond the tile: gdn_large.hip
+        return gdn_large_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj,
+                                  d_bias, workspace, bwd_bias_ws_floats(d), (hipStream_t)stream);
       sliced = true;
     }
   }

@@ -42,6 +42,16 @@ int gdn_dense_attn_bwd(const float* d_z, const float* xlin, const float* alpha, 
                        float* d_bias, float* bias_ws, hipStream_t stream);   // matrix-core backward of the gather-aggregate
 int gdn_dense_project(const void* x, int is_bf16, const float* lin_w, const float* node_terms, int batch, int n,
                       int w, int d, void* xlin, float* s_i, float* s_j, hipStream_t stream);
+// gdn_large.hip: the graph layer beyond the LDS tile (n up to 4096, xlin gathered from global memory); the staged
+// entry points call these where make_plan / bwd_plan refuse the shape.  x rows at xb + b*bstride + s*sstride.
+int gdn_large_project(const float* xb, long long bstride, long long sstride, const float* lin_w, const float* terms,
+                      int batch, int n, int w, int d, float* xlin, float* s_i, float* s_j, hipStream_t stream);
+int gdn_large_aggregate(const float* xlin, const float* s_i, const float* s_j, const uint16_t* nbr, const float* bias,
+                        int batch, int n, int d, int k, float* z, float* alpha, hipStream_t stream);
+int gdn_large_attn_bwd(const float* d_z, const float* xlin, const float* alpha, const float* s_i, const float* s_j,
+                       const uint16_t* nbr, const uint32_t* rent, const int32_t* rlen, int batch, int n, int d, int k,
+                       float* d_xlin, float* d_si, float* d_sj, float* d_bias, float* workspace,
+                       long long bias_ws_floats, hipStream_t stream);
 // run-time choice between the two fused forward implementations: GDN_FUSED_PATH=valu keeps the fp32 VALU
 // row-gather kernel for every shape (read once per process)
 static inline bool gdn_use_dense_path() {

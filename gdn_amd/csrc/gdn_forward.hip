@@ -1268,6 +1268,25 @@ int dispatch_window(const Plan& pl, const Args& a, int threads, hipStream_t stre
 
 }  // namespace
 
+// 1 when the one-launch fused forward (the window's tile in LDS) takes this shape
+extern "C" int gdn_tile_fits(int n, int w, int d, int k) {
+  if (n <= 0 || w <= 0 || d <= 0 || k <= 0) return 0;
+  Plan pl; int threads;
+  return make_plan(MODE_FUSED, 1, n, w, d, k, &pl, &threads) == GDN_OK;
+}
+
+// gdn_project_fwd on windows read straight from the raw series [n, series_len]: window b = series[:, first + b :
+// first + b + w].  The streaming row kernel at every shape (the same bits as gdn_project_fwd gives beyond the tile).
+extern "C" int gdn_project_fwd_series(const float* series, int series_len, int first, const float* lin_w,
+                                      const float* node_terms, int batch, int n, int w, int d, float* xlin,
+                                      float* s_i, float* s_j, void* stream) {
+  if (!series || !lin_w || !node_terms || !xlin || !s_i || !s_j || series_len <= 0 || first < 0 || w <= 0)
+    return GDN_ERR_ARG;
+  if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;   // last window must fit
+  return gdn_large_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
+                           (hipStream_t)stream);
+}
+
 // 1 when the staged forward (gdn_project_fwd + gdn_attn_aggregate_fwd) takes this shape
 int gdn_forward_staged_ok(int n, int w, int d, int k) {
   Plan pl; int threads;
@@ -1282,6 +1301,9 @@ static int project_fwd_impl(const float* x, const float* lin_w, const float* nod
     return gdn_dense_project(x, 0, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, (hipStream_t)stream);
   Plan pl; int threads;
   const int rc = make_plan(MODE_PROJECT, batch, n, w, d, 0, &pl, &threads);
+  if (rc == GDN_ERR_UNSUPPORTED)   // beyond the LDS tile: the streaming row kernel (gdn_large.hip)
+    return gdn_large_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
+                             (hipStream_t)stream);
   if (rc != GDN_OK) return rc;
   Args a = {};
   a.x = x; a.lin_w = lin_w; a.node_terms = node_terms;
@@ -1308,6 +1330,8 @@ static int attn_aggregate_fwd_impl(const float* xlin, const float* s_i, const fl
     return gdn_dense_attn_aggregate(xlin, 0, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
   Plan pl; int threads;
   const int rc = make_plan(MODE_ATTN, batch, n, 0, d, k, &pl, &threads);
+  if (rc == GDN_ERR_UNSUPPORTED)   // beyond the LDS tile: rows gathered from global memory (gdn_large.hip)
+    return gdn_large_aggregate(xlin, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
   if (rc != GDN_OK) return rc;
   Args a = {};
   a.xlin_in = xlin; a.si_in = s_i; a.sj_in = s_j; a.nbr = nbr; a.deg = deg; a.gnn_bias = bias;

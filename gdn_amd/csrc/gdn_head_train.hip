@@ -42,6 +42,7 @@ struct HG {
 #define GDN_FX_WORDS 6        // + one flag word (NaN / inf / beyond 2^130 seen: the total reads as NaN)
 #define GDN_FX_LSB 130
 #define GDN_HEAD_EMB_PARTS 64  // batch parts of the embedding-gradient pass, one [n,d] partial each
+#define GDN_FX_MAX_ADDS 2048   // addends per accumulator between two resets, summed over its replicas
 
 struct RunningStats {   // BatchNorm buffers updated by the forward (any pointer may be null)
   float *rm1, *rv1, *rm2, *rv2;
@@ -95,7 +96,10 @@ struct BnCols {
 
 // ---- exact accumulation across workgroups (see the header) --------------------------------------------------
 // An accumulator is GDN_FX_WORDS 64-bit words `stride` words apart (one per limb, then the flag).  Every limb
-// receives at most one addend below 2^52 per call: 2048 calls between two resets cannot overflow its 63 bits.
+// receives at most one addend below 2^52 per call, and fx_total adds the GDN_HEAD_REPL replicas' limbs as 64-bit
+// integers BEFORE it carries: the bound is on the total over the replicas — at most GDN_FX_MAX_ADDS calls
+// between two resets across all replicas, or the sum can leave its 63 bits.  A head pass makes one call per
+// workgroup (chunks x parts of them): head_parts keeps that product at or below the bound.
 __device__ __forceinline__ void fx_atomic_add(unsigned long long* p, int stride, double x) {
   const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
   const int ex = (int)((bits >> 52) & 0x7ffull);
@@ -597,6 +601,9 @@ int head_parts(int batch, int chunks, int mode) {
   const int by_rounds = (batch + GDN_HEAD_UNROLL - 1) / GDN_HEAD_UNROLL;   // at least one full round each
   if (parts > by_rounds) parts = by_rounds;
   if (mode == H_BWD1 && parts > GDN_HEAD_EMB_PARTS) parts = GDN_HEAD_EMB_PARTS;
+  // one exact-sum addend per workgroup and accumulator (fx_atomic_add): chunks x parts within GDN_FX_MAX_ADDS
+  // (chunks <= 512 at n <= 4096, so at least 4 parts remain)
+  if (parts > GDN_FX_MAX_ADDS / chunks) parts = GDN_FX_MAX_ADDS / chunks;
   return parts < 1 ? 1 : parts;
 }
 

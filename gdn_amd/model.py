@@ -22,6 +22,9 @@ forward on CPU tensors raises.
                              OutLayer MLP on the fp32 matrix cores (gdn_mlp_train_fwd/bwd, any hidden width
                              up to 512; beyond: torch ops)
                              (`loss.backward()` reaches every parameter exactly as in the reference)
+  graphs beyond the LDS tile (gdn_tile_fits == 0, up to 4096 sensors): eval runs the staged chain project ->
+                             gather-aggregate -> head with xlin / z in HBM (fp32 only), training the autograd path
+                             above — the staged entry points switch to their large-graph kernels by themselves
   harness.NativeTrainStep is the same arithmetic without autograd (flat buffers, in-kernel dropout, gdn_adam_step).
 """
 from __future__ import annotations
@@ -228,7 +231,7 @@ class OutLayer(nn.Module):
 
 class _EvalConstants:
     __slots__ = ("key", "graph", "terms", "bn1", "bn2", "fused_args", "plans", "mlp", "stream", "ready", "guards",
-                 "limits")
+                 "limits", "large", "bufs")
 
 
 class GDN(nn.Module):
@@ -318,6 +321,11 @@ class GDN(nn.Module):
         c.guards = {}                # stream -> int32[2] range guard of the eval fast path
         c.limits = {}                # bf16_storage -> the plan's x limit as a host float (read on first use)
         c.mlp = False                # eval-mode OutLayer MLP plan: False = not built yet, None = unsupported
+        d, w = gnn.lin.weight.shape
+        # beyond the LDS tile (include/gdn_hip.h "Supported shapes"): the eval forward is staged — project,
+        # gather-aggregate, head — with xlin and z in HBM, in buffers kept here per (stream, batch)
+        c.large = not _lib.load().gdn_tile_fits(emb.shape[0], w, d, c.graph.k)
+        c.bufs = {}
         if not self.training:
             c.bn1 = ops.bn_fold(self.gnn_layers[0].bn)
             c.bn2 = ops.bn_fold(self.bn_outlayer_in)
@@ -376,6 +384,10 @@ class GDN(nn.Module):
         if x.shape[1] != n or x.shape[2] != w:
             raise ValueError(f"expected data of shape [B, {n}, {w}], got {tuple(x.shape)}")
         bf16 = x.dtype == torch.bfloat16
+        if c.large:
+            if keys is not None:
+                raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
+            return self._forward_large(x, c, out, b)
         plan = None if (wide and not bf16) else self._plan(c, bf16)
         g = self._guard(c, torch.cuda.current_stream()) if (guard and plan is not None and not bf16) else None
         cur = self._wait_ready(c)
@@ -396,6 +408,50 @@ class GDN(nn.Module):
         else:
             _lib.call("gdn_forward_fused_bf16" if bf16 else "gdn_forward_fused", x.data_ptr(), *ptrs, b, n, w, d, k,
                       out.data_ptr(), st)
+        return out
+
+    def _large_buffers(self, c, batch: int):
+        """(xlin, s_i, s_j, z) of the staged eval forward beyond the tile, one set per (stream, batch): allocated
+        on first use (a warm-up before any capture), reused by every later launch on that stream."""
+        key = (torch.cuda.current_stream().cuda_stream, batch)
+        bufs = c.bufs.get(key)
+        if bufs is None:
+            n, d = self.embedding.weight.shape
+            dev = self.embedding.weight.device
+            rows = batch * n
+            bufs = (torch.empty((rows, d), dtype=torch.float32, device=dev),
+                    torch.empty((rows,), dtype=torch.float32, device=dev),
+                    torch.empty((rows,), dtype=torch.float32, device=dev),
+                    torch.empty((rows, d), dtype=torch.float32, device=dev))
+            c.bufs[key] = bufs
+        return bufs
+
+    def _forward_large(self, x, c, out, batch: int, series=None, first: int = 0):
+        """Eval forward (out_layer_num == 1) of a graph beyond the LDS tile: gdn_project_fwd (or its series form) ->
+        gdn_attn_aggregate_fwd -> gdn_head_fwd, fp32 row gathers from HBM (no range guard: there are no 16-bit
+        operands on this path).  `series` [n, T]: window b = series[:, first + b : first + b + w]."""
+        src = x if series is None else series
+        if src.dtype == torch.bfloat16:
+            raise _lib.GdnHipError(f"bf16 storage needs the LDS tile: {self.embedding.weight.shape[0]} sensors "
+                                   "do not fit it (graphs beyond the tile run in fp32 only)")
+        gnn = self.gnn_layers[0].gnn
+        lin = self.out_layer.mlp[0]
+        emb = self.embedding.weight
+        n, d = emb.shape
+        w = gnn.lin.weight.shape[1]
+        cur = self._wait_ready(c)
+        st = cur.cuda_stream
+        xlin, s_i, s_j, z = self._large_buffers(c, batch)
+        if series is None:
+            _lib.call("gdn_project_fwd", x.data_ptr(), gnn.lin.weight.data_ptr(), c.terms.data_ptr(), batch, n, w, d,
+                      xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
+        else:
+            _lib.call("gdn_project_fwd_series", series.data_ptr(), series.shape[1], first, gnn.lin.weight.data_ptr(),
+                      c.terms.data_ptr(), batch, n, w, d, xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
+        _lib.call("gdn_attn_aggregate_fwd", xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), c.graph.nbr.data_ptr(),
+                  c.graph.deg.data_ptr(), gnn.bias.data_ptr(), batch, n, d, c.graph.k, z.data_ptr(), None, st)
+        _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
+                  lin.weight.data_ptr(), lin.bias.data_ptr(), batch, n, d, out.data_ptr(), None, st)
         return out
 
     def operand_limit(self, bf16: bool = False) -> float:
@@ -468,6 +524,9 @@ class GDN(nn.Module):
         gnn = layer.gnn
         c = self._constants()
         self.learned_graph = c.graph.topk                                   # GDN.py:159
+        if bf16 and c.large:
+            raise _lib.GdnHipError(f"bf16 storage needs the LDS tile: {node_num} sensors do not fit it (graphs "
+                                   "beyond the tile run in fp32 only)")
         if batch == 0 and not self.training:
             # an empty minibatch: the reference's ops run on empty tensors and return [0, N]
             return torch.empty((0, node_num), dtype=torch.float32, device=x.device)
@@ -570,7 +629,10 @@ class GDN(nn.Module):
     def fused_keys_supported(self, bf16: bool = False) -> bool:
         """True when the eval forward of this model can leave the scoring keys itself (`keys=` of forward_into /
         forward_series): out_layer_num == 1 on the planned matrix-core path."""
-        return (not self.training) and self.out_layer_num == 1 and self._plan(self._constants(), bf16) is not None
+        if self.training or self.out_layer_num != 1:
+            return False
+        c = self._constants()
+        return not c.large and self._plan(c, bf16) is not None
 
     def forward_series(self, series, first: int, batch: int, out=None, keys=None, wide: bool = False):
         """Eval forward of `batch` consecutive stride-1 windows taken directly from the raw series
@@ -582,6 +644,13 @@ class GDN(nn.Module):
         gnn = self.gnn_layers[0].gnn
         lin = self.out_layer.mlp[0]
         self.learned_graph = c.graph.topk
+        if c.large:
+            if keys is not None:
+                raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
+            series = ops._chk(series, series.dtype, name="series")
+            if out is None:
+                out = torch.empty((batch, series.shape[0]), dtype=torch.float32, device=series.device)
+            return self._forward_large(None, c, out, batch, series=series, first=first)
         plan = None if wide else self._plan(c, False)
         st = self._wait_ready(c).cuda_stream
         series = ops._chk(series, name="series")

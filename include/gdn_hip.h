@@ -19,15 +19,19 @@
  *     window-major order (row = b*n + sensor), the layout of models/GDN.py:130;
  *   - re-entrant across distinct streams.
  *
- * Supported shapes: d in {16, 32, 64, 128}; 1 <= w <= 64; 1 <= k <= n with k+1 <= 1024,
- * and the window's working set must fit the 160 KB of LDS of one CU:
- *   forward (staged and fused): the xlin tile (n+1)*dc*4 bytes, dc = d (d = 128: 64, two
- *     column slices) — n up to ~600 at d = 64/128, ~1000 at d = 32, ~2000 at d = 16;
- *   backward (gdn_attn_aggregate_bwd): that tile at full d PLUS two [n, pitch] fp32 tables and the lists
- *     in LDS — n up to ~250 at d = 64 with k = 30 (127-sensor WADI, 51-sensor SWaT, the 25-55-sensor
- *     MSL/SMAP/PSM sets); beyond that the tables go through the caller's workspace in global memory and
- *     only the tile must fit (n <= ~600 at d = 64: the 512-sensor / k = 64 stress shape trains; d = 128 walks
- *     two 64-column slices when the full tile does not fit: n <= ~600 there too);
+ * Supported shapes: d in {16, 32, 64, 128}; 1 <= w <= 64; 1 <= k <= n <= 4096 with k+1 <= 1024.
+ * Two forms of the graph layer, chosen by the library per entry point, never by the caller:
+ *   TILE form — the window's working set in the 160 KB of LDS of one CU:
+ *     forward (staged and fused): the xlin tile (n+1)*dc*4 bytes, dc = d (d = 128: 64, two column slices) —
+ *       n up to ~610 at d = 64/128, ~1180 at d = 32, ~2200 at d = 16 (gdn_tile_fits: the fused forward);
+ *     backward (gdn_attn_aggregate_bwd): that tile at full d PLUS two [n, pitch] fp32 tables and the lists
+ *       in LDS — n up to ~250 at d = 64 with k = 30; beyond that the tables go through the caller's workspace
+ *       and only the tile must fit (d = 128 walks two 64-column slices when the full tile does not fit);
+ *   LARGE form — where the tile form refuses (n up to 4096), gdn_project_fwd, gdn_attn_aggregate_fwd and
+ *     gdn_attn_aggregate_bwd run streaming kernels that keep only the window's s_i / s_j and one list per wave
+ *     in LDS and gather the source rows of xlin (forward) / d_z (backward) from global memory; fp32 only,
+ *     bitwise reproducible.  The fused entry points (gdn_forward_fused*: no workspace), the bf16 ones and
+ *     gdn_train_supported (the native captured step) keep to the tile form;
  *   matrix-core ("dense") kernels — gdn_forward_fused, gdn_project_fwd, gdn_attn_aggregate_fwd pick them
  *     by themselves for n <= 127, d = 64, w <= 32, k <= 63 (gdn_forward_fused also at d = 128); the staged
  *     bf16-storage entry points exist only there;
@@ -47,7 +51,7 @@ extern "C" {
 #define GDN_ERR_LAUNCH (-2)       /* hipGetLastError() != hipSuccess after the launch      */
 #define GDN_ERR_UNSUPPORTED (-3)  /* shape outside the supported set above                 */
 
-#define GDN_ABI_VERSION 21
+#define GDN_ABI_VERSION 22
 int gdn_abi_version(void);
 
 /* Number of u16 slots per neighbour-list row for a given k: (k+1) rounded up to 16. */
@@ -101,6 +105,19 @@ int gdn_bn_fold(const float* weight, const float* bias, const float* running_mea
 int gdn_project_fwd(const float* x, const float* lin_w, const float* node_terms,
                     int batch, int n, int w, int d,
                     float* xlin, float* s_i, float* s_j, void* stream);
+
+/* gdn_project_fwd_series: gdn_project_fwd on windows read straight from the raw series[n, series_len] (the
+ * layout of gdn_forward_fused_series): window b = series[:, first+b : first+b+w]; requires first + batch - 1 + w
+ * <= series_len.  Runs the large-form streaming kernel at every shape (the same bits gdn_project_fwd gives
+ * on the same windows where the tile form refuses): the eval path of graphs beyond the tile without a
+ * [B, n, w] copy.                                                                                            */
+int gdn_project_fwd_series(const float* series, int series_len, int first, const float* lin_w,
+                           const float* node_terms, int batch, int n, int w, int d,
+                           float* xlin, float* s_i, float* s_j, void* stream);
+
+/* gdn_tile_fits: 1 when the tile form of the forward takes (n, w, d, k) — the one-launch gdn_forward_fused and
+ * its plans — 0 when only the staged entry points (large form beyond the tile) do.  Host only, no launch.      */
+int gdn_tile_fits(int n, int w, int d, int k);
 
 /* gdn_attn_aggregate_fwd: models/graph_layer.py:65-74,82-117 + PyG propagate / softmax:
  * LeakyReLU(0.2) logits, softmax over each target's incoming edges (max-subtract, exp,
@@ -479,8 +496,9 @@ int gdn_forward_fused_bf16(const uint16_t* x, const float* lin_w, const float* n
  *                 ticket, ZERO before the first call, left zero by every call][1024 x d floats: the d_bias
  *                 rows][batch*n*pitch floats of d_pi when the tile plus the two [n, pitch] tables exceed LDS
  *                 (n ~> 250 at d = 64, k = 30; the 512-sensor / k = 64 stress shape) — the tables then go
- *                 through global memory and only the tile must fit: (n+1)*d*4 bytes <= ~155 KB].  One
- *                 workspace per stream: two concurrent calls must not share one.                      */
+ *                 through global memory and only the tile must fit: (n+1)*d*4 bytes <= ~155 KB; beyond
+ *                 the tile (large form) the same d_pi table carries the softmax gradient from the per-target
+ *                 pass to the per-source pass].  One workspace per stream: two concurrent calls must not share one. */
 long long gdn_attn_aggregate_bwd_workspace_bytes(int batch, int n, int d, int k);
 int gdn_attn_aggregate_bwd(const float* d_z, const float* xlin, const float* alpha,
                            const float* s_i, const float* s_j,
