@@ -25,6 +25,7 @@ SIGNATURES = {
     "gdn_project_fwd": [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gdn_project_fwd_series": [_p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gdn_tile_fits": [_c_int] * 4,
+    "gdn_terms_pitch": [_c_int],
     "gdn_attn_aggregate_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
     "gdn_head_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p],
     "gdn_head_train_fwd": [_p] * 10 + [_c_float] + [_c_int] * 3 + [_c_float] * 4 + [_p] * 9,

@@ -714,6 +714,7 @@ extern "C" int gdn_train_supported(int n, int w, int d, int k) {
 
 extern "C" long long gdn_project_bwd_workspace_bytes(int n, int w, int d) {
   if (n <= 0 || w <= 0 || d <= 0) return 0;
+  if (w > GDN_MAX_W) return gdn_long_project_bwd_workspace_bytes(n, w, d);
   const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
   return (long long)GDN_PBWD_MAX_ROWS * (d * wp + 128 + 2 * n) * (long long)sizeof(float);
 }
@@ -724,7 +725,10 @@ extern "C" int gdn_project_bwd_partials(const float* x, const float* d_xlin, con
                                         void* stream) {
   if (!x || !d_xlin || !d_si || !d_sj || !workspace || !rows_out || batch <= 0 || n <= 0 || w <= 0) return GDN_ERR_ARG;
   if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
-  if (w > GDN_MAX_W || n > 4096) return GDN_ERR_UNSUPPORTED;
+  if (w > GDN_MAX_W)   // long windows: partial [d + 2, w] blocks (gdn_long_window.hip)
+    return gdn_long_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out,
+                                         (hipStream_t)stream);
+  if (n > 4096) return GDN_ERR_UNSUPPORTED;
   const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
   // rows per staged chunk: whole window when it fits ~96 KB (three workgroups per CU at the SWaT shape)
   int rc = (24576 - 2 * n) / (wp + d + 2);
@@ -754,6 +758,11 @@ extern "C" int gdn_project_bwd(const float* x, const float* d_xlin, const float*
                                int batch, int n, int w, int d, float* workspace, float* d_lin_w, float* d_a,
                                float* d_c, void* stream) {
   if (!d_lin_w || !d_a || !d_c) return GDN_ERR_ARG;
+  if (w > GDN_MAX_W) {
+    if (!x || !d_xlin || !d_si || !d_sj || !workspace || batch <= 0 || n <= 0) return GDN_ERR_ARG;
+    return gdn_long_project_bwd(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, d_lin_w, d_a, d_c,
+                                (hipStream_t)stream);
+  }
   int rows = 0;
   const int rc = gdn_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, &rows, stream);
   if (rc != GDN_OK) return rc;
@@ -772,7 +781,10 @@ extern "C" int gdn_terms_bwd_acc(const float* lin_w, const float* att_i, const f
   if (!lin_w || !att_i || !att_j || !att_em_i || !att_em_j || !emb || !d_a || !d_c || !d_lin_w || !d_att_i ||
       !d_att_j || !d_att_em_i || !d_att_em_j || !d_emb || n <= 0 || d <= 0 || w <= 0)
     return GDN_ERR_ARG;
-  if (w > GDN_MAX_W || d > 256 || (256 % d) != 0) return GDN_ERR_UNSUPPORTED;
+  if (w > GDN_MAX_W)   // long windows: d_a at pitch gdn_terms_pitch(w)
+    return gdn_long_terms_bwd(lin_w, att_i, att_j, att_em_i, att_em_j, emb, d_a, d_c, n, d, w, d_lin_w, d_att_i,
+                              d_att_j, d_att_em_i, d_att_em_j, d_emb, accumulate_emb, (hipStream_t)stream);
+  if (d > 256 || (256 % d) != 0) return GDN_ERR_UNSUPPORTED;
   int grid = (n * d + 1024 * 2 - 1) / (1024 * 2);
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(gdn_terms_bwd_kernel, dim3(grid), dim3(1024), 0, (hipStream_t)stream, lin_w, att_i, att_j,

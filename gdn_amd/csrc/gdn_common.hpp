@@ -9,7 +9,8 @@
 #define GDN_NEG_SLOPE 0.2f      // LeakyReLU slope, reference models/graph_layer.py:13
 #define GDN_SOFTMAX_EPS 1e-16f  // torch_geometric.utils.softmax 1.5.0 denominator epsilon
 #define GDN_MAX_W 64
-#define GDN_A_PITCH 64          // a_i / a_j are stored zero padded to 64 floats
+#define GDN_A_PITCH 64          // a_i / a_j are stored zero padded to 64 floats (w > 64: gdn_terms_pitch(w))
+#define GDN_LONG_MAX_W 1024     // longest window: gdn_long_window.hip
 
 static inline int gdn_launch_status() {
   return hipGetLastError() == hipSuccess ? GDN_OK : GDN_ERR_LAUNCH;
@@ -52,6 +53,22 @@ int gdn_large_attn_bwd(const float* d_z, const float* xlin, const float* alpha, 
                        const uint16_t* nbr, const uint32_t* rent, const int32_t* rlen, int batch, int n, int d, int k,
                        float* d_xlin, float* d_si, float* d_sj, float* d_bias, float* workspace,
                        long long bias_ws_floats, hipStream_t stream);
+// gdn_long_window.hip: windows longer than GDN_MAX_W (up to GDN_LONG_MAX_W); the entry points hand every w > 64
+// call to these before any other path.  Node terms at pitch gdn_terms_pitch(w); x rows as gdn_large_project's.
+int gdn_long_node_terms(const float* lin_w, const float* att_i, const float* att_j, const float* att_em_i,
+                        const float* att_em_j, const float* emb, int n, int d, int w, float* node_terms,
+                        hipStream_t stream);
+int gdn_long_project(const float* xb, long long bstride, long long sstride, const float* lin_w, const float* terms,
+                     int batch, int n, int w, int d, float* xlin, float* s_i, float* s_j, hipStream_t stream);
+long long gdn_long_project_bwd_workspace_bytes(int n, int w, int d);
+int gdn_long_project_bwd_partials(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch,
+                                  int n, int w, int d, float* workspace, int* parts_out, hipStream_t stream);
+int gdn_long_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch, int n,
+                         int w, int d, float* workspace, float* d_lin_w, float* d_a, float* d_c, hipStream_t stream);
+int gdn_long_terms_bwd(const float* lin_w, const float* att_i, const float* att_j, const float* att_em_i,
+                       const float* att_em_j, const float* emb, const float* d_a, const float* d_c, int n, int d, int w,
+                       float* d_lin_w, float* d_att_i, float* d_att_j, float* d_att_em_i, float* d_att_em_j,
+                       float* d_emb, int accumulate_emb, hipStream_t stream);
 // run-time choice between the two fused forward implementations: GDN_FUSED_PATH=valu keeps the fp32 VALU
 // row-gather kernel for every shape (read once per process)
 static inline bool gdn_use_dense_path() {

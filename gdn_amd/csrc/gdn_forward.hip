@@ -1283,6 +1283,9 @@ extern "C" int gdn_project_fwd_series(const float* series, int series_len, int f
   if (!series || !lin_w || !node_terms || !xlin || !s_i || !s_j || series_len <= 0 || first < 0 || w <= 0)
     return GDN_ERR_ARG;
   if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;   // last window must fit
+  if (w > GDN_MAX_W)   // long windows: the matrix-core projection of gdn_long_window.hip
+    return gdn_long_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
+                            (hipStream_t)stream);
   return gdn_large_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
                            (hipStream_t)stream);
 }
@@ -1297,6 +1300,9 @@ int gdn_forward_staged_ok(int n, int w, int d, int k) {
 static int project_fwd_impl(const float* x, const float* lin_w, const float* node_terms, int batch,
                             int n, int w, int d, float* xlin, float* s_i, float* s_j, void* stream, bool wide) {
   if (!x || !lin_w || !node_terms || !xlin || !s_i || !s_j) return GDN_ERR_ARG;
+  if (w > GDN_MAX_W)   // long windows (both forms: exact fp32, no 16-bit operands): gdn_long_window.hip
+    return gdn_long_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
+                            (hipStream_t)stream);
   if (!wide && batch > 0 && gdn_use_dense_path() && gdn_dense_supported(n, w, d, 1))
     return gdn_dense_project(x, 0, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, (hipStream_t)stream);
   Plan pl; int threads;

@@ -265,7 +265,8 @@ extern "C" int gdn_node_terms(const float* lin_w, const float* att_i, const floa
   if (!lin_w || !att_i || !att_j || !att_em_i || !att_em_j || !emb || !node_terms || n <= 0 ||
       d <= 0 || w <= 0)
     return GDN_ERR_ARG;
-  if (w > GDN_MAX_W) return GDN_ERR_UNSUPPORTED;
+  if (w > GDN_MAX_W)   // long windows: a_i / a_j at pitch gdn_terms_pitch(w) (gdn_long_window.hip)
+    return gdn_long_node_terms(lin_w, att_i, att_j, att_em_i, att_em_j, emb, n, d, w, node_terms, (hipStream_t)stream);
   const int total = 2 * GDN_A_PITCH + 2 * n;
   hipLaunchKernelGGL(gdn_node_terms_kernel, dim3((total + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, lin_w, att_i, att_j, att_em_i, att_em_j, emb, n, d, w,

@@ -926,6 +926,7 @@ extern "C" int gdn_train_finish(double* head_workspace, double* stats, int head_
       !proj_workspace || !d_proj_w || !d_a || !d_c || batch <= 0 || n <= 0 || w <= 0 || proj_rows <= 0)
     return GDN_ERR_ARG;
   if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
+  if (w > GDN_MAX_W) return GDN_ERR_UNSUPPORTED;   // (long windows' partial blocks: gdn_project_bwd reduces them)
   TailArgs t = {};
   const size_t sums_bytes = fx_block_words(6, d) * sizeof(double);
   const int chunks = (n + 256 / (d / 4) - 1) / (256 / (d / 4));

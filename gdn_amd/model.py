@@ -22,9 +22,10 @@ forward on CPU tensors raises.
                              OutLayer MLP on the fp32 matrix cores (gdn_mlp_train_fwd/bwd, any hidden width
                              up to 512; beyond: torch ops)
                              (`loss.backward()` reaches every parameter exactly as in the reference)
-  graphs beyond the LDS tile (gdn_tile_fits == 0, up to 4096 sensors): eval runs the staged chain project ->
-                             gather-aggregate -> head with xlin / z in HBM (fp32 only), training the autograd path
-                             above — the staged entry points switch to their large-graph kernels by themselves
+  graphs beyond the LDS tile (gdn_tile_fits == 0, up to 4096 sensors) and windows longer than 64 ticks (up to
+                             1024): eval runs the staged chain project -> aggregate -> head with xlin / z in HBM
+                             (fp32 only), training the autograd path above — the staged entry points switch to their
+                             large-graph / long-window kernels by themselves
   harness.NativeTrainStep is the same arithmetic without autograd (flat buffers, in-kernel dropout, gdn_adam_step).
 """
 from __future__ import annotations
@@ -387,7 +388,7 @@ class GDN(nn.Module):
         if c.large:
             if keys is not None:
                 raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
-            return self._forward_large(x, c, out, b)
+            return self._forward_large(x, c, out, b, wide=wide or (guard and self._large_guard_wide(x, c)))
         plan = None if (wide and not bf16) else self._plan(c, bf16)
         g = self._guard(c, torch.cuda.current_stream()) if (guard and plan is not None and not bf16) else None
         cur = self._wait_ready(c)
@@ -426,14 +427,37 @@ class GDN(nn.Module):
             c.bufs[key] = bufs
         return bufs
 
-    def _forward_large(self, x, c, out, batch: int, series=None, first: int = 0):
-        """Eval forward (out_layer_num == 1) of a graph beyond the LDS tile: gdn_project_fwd (or its series form) ->
-        gdn_attn_aggregate_fwd -> gdn_head_fwd, fp32 row gathers from HBM (no range guard: there are no 16-bit
-        operands on this path).  `series` [n, T]: window b = series[:, first + b : first + b + w]."""
+    def _bf16_refusal(self) -> _lib.GdnHipError:
+        """Why bf16 windows are refused where the tile form does not take the shape."""
+        w = self.gnn_layers[0].gnn.lin.weight.shape[1]
+        if w > 64:
+            return _lib.GdnHipError(f"bf16 storage needs the LDS tile: windows of {w} ticks do not fit it (windows "
+                                    "longer than 64 ticks run in fp32 only)")
+        return _lib.GdnHipError(f"bf16 storage needs the LDS tile: {self.embedding.weight.shape[0]} sensors do not "
+                                "fit it (graphs beyond the tile run in fp32 only)")
+
+    def _large_guard_wide(self, src, c) -> bool:
+        """Range check of the staged forward under operand_range='auto'.  The projection and the gather kernels
+        beyond the tile are fp32 throughout, but on a long-window model with a small graph (n <= 127, d = 64,
+        k <= 63) gdn_attn_aggregate_fwd picks the matrix-core aggregate, which carries xlin as two f16 terms: there
+        the inputs are compared with the limit on the host (inside a capture, where that cannot happen, the fp32
+        `_wide` aggregate runs)."""
+        n, d = self.embedding.weight.shape
+        if not (n <= 127 and d == 64 and 1 <= c.graph.k <= 63):
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            return True
+        return self.input_exceeds_limit(src)
+
+    def _forward_large(self, x, c, out, batch: int, series=None, first: int = 0, wide: bool = False):
+        """Eval forward (out_layer_num == 1) of a shape the LDS tile does not take (a graph beyond it, or windows
+        longer than 64 ticks): gdn_project_fwd (or its series form) -> gdn_attn_aggregate_fwd -> gdn_head_fwd with
+        xlin / z in HBM.  Beyond the tile every kernel is fp32 (no range guard needed); `wide` selects the fp32
+        aggregate where the matrix-core one would be picked (see _large_guard_wide).  `series` [n, T]: window b =
+        series[:, first + b : first + b + w]."""
         src = x if series is None else series
         if src.dtype == torch.bfloat16:
-            raise _lib.GdnHipError(f"bf16 storage needs the LDS tile: {self.embedding.weight.shape[0]} sensors "
-                                   "do not fit it (graphs beyond the tile run in fp32 only)")
+            raise self._bf16_refusal()
         gnn = self.gnn_layers[0].gnn
         lin = self.out_layer.mlp[0]
         emb = self.embedding.weight
@@ -448,8 +472,9 @@ class GDN(nn.Module):
         else:
             _lib.call("gdn_project_fwd_series", series.data_ptr(), series.shape[1], first, gnn.lin.weight.data_ptr(),
                       c.terms.data_ptr(), batch, n, w, d, xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
-        _lib.call("gdn_attn_aggregate_fwd", xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), c.graph.nbr.data_ptr(),
-                  c.graph.deg.data_ptr(), gnn.bias.data_ptr(), batch, n, d, c.graph.k, z.data_ptr(), None, st)
+        _lib.call("gdn_attn_aggregate_fwd_wide" if wide else "gdn_attn_aggregate_fwd", xlin.data_ptr(), s_i.data_ptr(),
+                  s_j.data_ptr(), c.graph.nbr.data_ptr(), c.graph.deg.data_ptr(), gnn.bias.data_ptr(), batch, n, d,
+                  c.graph.k, z.data_ptr(), None, st)
         _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
                   lin.weight.data_ptr(), lin.bias.data_ptr(), batch, n, d, out.data_ptr(), None, st)
         return out
@@ -525,8 +550,7 @@ class GDN(nn.Module):
         c = self._constants()
         self.learned_graph = c.graph.topk                                   # GDN.py:159
         if bf16 and c.large:
-            raise _lib.GdnHipError(f"bf16 storage needs the LDS tile: {node_num} sensors do not fit it (graphs "
-                                   "beyond the tile run in fp32 only)")
+            raise self._bf16_refusal()
         if batch == 0 and not self.training:
             # an empty minibatch: the reference's ops run on empty tensors and return [0, N]
             return torch.empty((0, node_num), dtype=torch.float32, device=x.device)
@@ -650,7 +674,7 @@ class GDN(nn.Module):
             series = ops._chk(series, series.dtype, name="series")
             if out is None:
                 out = torch.empty((batch, series.shape[0]), dtype=torch.float32, device=series.device)
-            return self._forward_large(None, c, out, batch, series=series, first=first)
+            return self._forward_large(None, c, out, batch, series=series, first=first, wide=wide)
         plan = None if wide else self._plan(c, False)
         st = self._wait_ready(c).cuda_stream
         series = ops._chk(series, name="series")

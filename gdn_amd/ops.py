@@ -94,13 +94,21 @@ def graph_from_topk(topk: torch.Tensor) -> SensorGraph:
     return SensorGraph(topk, nbr, deg)
 
 
+def terms_pitch(w: int) -> int:
+    """P of the node-terms layout [a_i(P) | a_j(P) | c_i(n) | c_j(n)]: 64 up to w = 64, round_up(w, 64) above."""
+    p = _lib.load().gdn_terms_pitch(w)
+    if p == 0:
+        raise _lib.GdnHipError(f"window length {w} is not supported (1 <= w <= 1024, include/gdn_hip.h)")
+    return p
+
+
 def node_terms(lin_w, att_i, att_j, att_em_i, att_em_j, emb) -> torch.Tensor:
     lin_w = _chk(lin_w.detach(), name="lin.weight")
     d, w = lin_w.shape
     emb = _chk(emb.detach(), name="embedding")
     n = emb.shape[0]
     vs = [_chk(v.detach().reshape(-1), name="att") for v in (att_i, att_j, att_em_i, att_em_j)]
-    out = torch.empty((128 + 2 * n,), dtype=torch.float32, device=emb.device)
+    out = torch.empty((2 * terms_pitch(w) + 2 * n,), dtype=torch.float32, device=emb.device)
     _lib.call("gdn_node_terms", _ptr(lin_w), *[_ptr(v) for v in vs], _ptr(emb), n, d, w, _ptr(out), _stream())
     return out
 
@@ -517,13 +525,15 @@ def attn_aggregate_bwd(d_z, xlin, alpha, s_i, s_j, graph: SensorGraph, batch: in
 
 
 def project_bwd(x, d_xlin, d_si, d_sj, d: int):
-    """Gradients of project_fwd: d_lin_w[d,w] (direct term), d_a[2,64], d_c[2,n]."""
+    """Gradients of project_fwd: d_lin_w[d,w] (direct term), d_a[2,P] (P = terms_pitch(w)), d_c[2,n]."""
     x = _chk(x, name="x")
     b, n, w = x.shape
     ws = torch.empty((_lib.load().gdn_project_bwd_workspace_bytes(n, w, d) // 4,), dtype=torch.float32,
                      device=x.device)
-    flat = torch.empty((d * w + 128 + 2 * n,), dtype=torch.float32, device=x.device)
-    d_lin_w, d_a, d_c = flat[:d * w].view(d, w), flat[d * w:d * w + 128].view(2, 64), flat[d * w + 128:].view(2, n)
+    ap = terms_pitch(w)
+    flat = torch.empty((d * w + 2 * ap + 2 * n,), dtype=torch.float32, device=x.device)
+    d_lin_w, d_a, d_c = (flat[:d * w].view(d, w), flat[d * w:d * w + 2 * ap].view(2, ap),
+                         flat[d * w + 2 * ap:].view(2, n))
     _lib.call("gdn_project_bwd", _ptr(x), _ptr(_chk(d_xlin)), _ptr(_chk(d_si)), _ptr(_chk(d_sj)),
               b, n, w, d, _ptr(ws), _ptr(d_lin_w), _ptr(d_a), _ptr(d_c), _stream())
     return d_lin_w, d_a, d_c

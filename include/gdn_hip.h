@@ -19,7 +19,11 @@
  *     window-major order (row = b*n + sensor), the layout of models/GDN.py:130;
  *   - re-entrant across distinct streams.
  *
- * Supported shapes: d in {16, 32, 64, 128}; 1 <= w <= 64; 1 <= k <= n <= 4096 with k+1 <= 1024.
+ * Supported shapes: d in {16, 32, 64, 128}; 1 <= w <= 1024; 1 <= k <= n <= 4096 with k+1 <= 1024.
+ * Windows longer than 64 ticks (LONG-WINDOW form, w = 65..1024) run the staged entry points only: gdn_node_terms,
+ *   gdn_project_fwd[_wide] / _series (fp32 matrix-core projection, exact fp32, no range limit), gdn_project_bwd[_partials],
+ *   gdn_terms_bwd[_acc]; everything after xlin depends on n, d, k only and takes the forms below.  gdn_tile_fits,
+ *   gdn_fused_plan_bytes and gdn_train_supported return 0, the fused / bf16 entry points GDN_ERR_UNSUPPORTED.
  * Two forms of the graph layer, chosen by the library per entry point, never by the caller:
  *   TILE form — the window's working set in the 160 KB of LDS of one CU:
  *     forward (staged and fused): the xlin tile (n+1)*dc*4 bytes, dc = d (d = 128: 64, two column slices) —
@@ -81,12 +85,17 @@ int gdn_graph_from_topk(const int64_t* topk_idx, int n, int k,
  *   pi(i<-j) = [xlin_i.att_i + v_i.att_em_i] + [xlin_j.att_j + v_j.att_em_j]
  * and xlin = x.lin^T, so each bracket is  x_row . a + c[sensor]  with
  *   a_i = lin^T att_i  [w],  c_i[s] = v_s . att_em_i  [n]   (same for _j).
- * node_terms receives [a_i(64) | a_j(64) | c_i(n) | c_j(n)] (a_* zero padded to 64).   */
+ * node_terms receives [a_i(P) | a_j(P) | c_i(n) | c_j(n)] (a_* zero padded to P = gdn_terms_pitch(w): 64 for
+ * w <= 64, round_up(w, 64) above).                                                                                */
 int gdn_node_terms(const float* lin_w, const float* att_i, const float* att_j,
                    const float* att_em_i, const float* att_em_j, const float* emb,
                    int n, int d, int w, float* node_terms, void* stream);
 
-/* gdn_topk_graph + gdn_node_terms as ONE launch (a training step rebuilds both from the parameters it is about
+/* gdn_terms_pitch: P of the node-terms layout above (64 for 1 <= w <= 64, round_up(w, 64) for w <= 1024), 0 for an
+ * unsupported w.  Host only, no launch.                                                                           */
+int gdn_terms_pitch(int w);
+
+/* gdn_topk_graph + gdn_node_terms as ONE launch (w <= 64) (a training step rebuilds both from the parameters it is about
  * to use; they are independent of each other): same outputs, no cos_out.                              */
 int gdn_topk_graph_terms(const float* emb, int n, int d, int k, int64_t* topk_idx, uint16_t* nbr,
                          int32_t* deg, const float* lin_w, const float* att_i, const float* att_j,
@@ -526,16 +535,17 @@ int gdn_graph_reverse(const uint16_t* nbr, const int32_t* deg, int n, int k,
 
 /* Backward of gdn_project_fwd, i.e. of `x = self.lin(x)` (models/graph_layer.py:56) and of the
  * folded logit scalars (graph_layer.py:94-104):
- * x[BN,w], d_xlin[BN,d], d_si/d_sj[BN] -> d_lin_w[d,w] (direct term), d_a[2,64]
- * (grads of a_i, a_j), d_c[2,n] (grads of c_i, c_j); outputs are written, not accumulated.
- * workspace: gdn_project_bwd_workspace_bytes(n, w, d) bytes (one partial row per workgroup). */
+ * x[BN,w], d_xlin[BN,d], d_si/d_sj[BN] -> d_lin_w[d,w] (direct term), d_a[2,P] (grads of a_i, a_j, P =
+ * gdn_terms_pitch(w), zero padded), d_c[2,n] (grads of c_i, c_j); outputs are written, not accumulated.
+ * workspace: gdn_project_bwd_workspace_bytes(n, w, d) bytes (one partial row per workgroup; w > 64: one partial
+ * [d+2, w] block per row range, which only gdn_project_bwd reduces — gdn_train_finish refuses w > 64).          */
 long long gdn_project_bwd_workspace_bytes(int n, int w, int d);
 int gdn_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj,
                     int batch, int n, int w, int d, float* workspace,
                     float* d_lin_w, float* d_a, float* d_c, void* stream);
 
 /* gdn_terms_bwd: chain rule through gdn_node_terms (a = lin^T att, c = emb . att_em — the
- * separable form of models/graph_layer.py:90-104): from gdn_project_bwd's d_a[2,64] / d_c[2,n]
+ * separable form of models/graph_layer.py:90-104): from gdn_project_bwd's d_a[2,P] / d_c[2,n]
  *   d_lin_w[d,w] += att_i (x) d_a[0] + att_j (x) d_a[1]      (in/out: holds the direct term)
  *   d_att_i/j[d]  = lin_w d_a[0/1]     d_att_em_i/j[d] = emb^T d_c[0/1]
  *   d_emb[n,d]    = d_c[0] (x) att_em_i + d_c[1] (x) att_em_j                               */
