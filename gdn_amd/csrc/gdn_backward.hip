@@ -596,6 +596,8 @@ extern "C" long long gdn_attn_aggregate_bwd_workspace_bytes(int batch, int n, in
   if (batch <= 0 || n <= 0 || k <= 0 || k > n || d <= 0) return 0;
   BwdPlan pl;
   long long floats = bwd_bias_ws_floats(d);
+  if (gdn_any_width(d))   // gdn_any_width.hip: the d_pi table always goes through the workspace
+    return (floats + (long long)batch * n * gdn_nbr_pitch(k)) * (long long)sizeof(float);
   if (!bwd_plan(batch, n, d, k, true, &pl) || (d == 128 && gdn_bwd_sliced_forced()))
     floats += (long long)batch * n * gdn_nbr_pitch(k);   // tables beyond LDS
   return floats * (long long)sizeof(float);
@@ -624,6 +626,9 @@ static int attn_aggregate_bwd_impl(const float* d_z, const float* xlin, const fl
       batch <= 0 || n <= 0 || k <= 0)
     return GDN_ERR_ARG;
   if ((!rent || !rlen) && !dense) return GDN_ERR_ARG;
+  if (gdn_any_width(d))   // embedding widths other than the four: gdn_any_width.hip
+    return gdn_any_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj, d_bias,
+                            workspace, bwd_bias_ws_floats(d), (hipStream_t)stream);
   if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
   if (k > n || n > 4096 || k + 1 > 1024) return GDN_ERR_UNSUPPORTED;
   BwdPlan pl;
@@ -714,6 +719,7 @@ extern "C" int gdn_train_supported(int n, int w, int d, int k) {
 
 extern "C" long long gdn_project_bwd_workspace_bytes(int n, int w, int d) {
   if (n <= 0 || w <= 0 || d <= 0) return 0;
+  if (gdn_any_width(d)) return gdn_any_project_bwd_workspace_bytes(n, w, d);
   if (w > GDN_MAX_W) return gdn_long_project_bwd_workspace_bytes(n, w, d);
   const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
   return (long long)GDN_PBWD_MAX_ROWS * (d * wp + 128 + 2 * n) * (long long)sizeof(float);
@@ -724,6 +730,9 @@ extern "C" int gdn_project_bwd_partials(const float* x, const float* d_xlin, con
                                         int batch, int n, int w, int d, float* workspace, int* rows_out,
                                         void* stream) {
   if (!x || !d_xlin || !d_si || !d_sj || !workspace || !rows_out || batch <= 0 || n <= 0 || w <= 0) return GDN_ERR_ARG;
+  if (gdn_any_width(d))   // embedding widths other than the four: partial [d + 2, w] blocks (gdn_any_width.hip)
+    return gdn_any_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out,
+                                        (hipStream_t)stream);
   if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
   if (w > GDN_MAX_W)   // long windows: partial [d + 2, w] blocks (gdn_long_window.hip)
     return gdn_long_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out,
@@ -758,6 +767,11 @@ extern "C" int gdn_project_bwd(const float* x, const float* d_xlin, const float*
                                int batch, int n, int w, int d, float* workspace, float* d_lin_w, float* d_a,
                                float* d_c, void* stream) {
   if (!d_lin_w || !d_a || !d_c) return GDN_ERR_ARG;
+  if (gdn_any_width(d)) {
+    if (!x || !d_xlin || !d_si || !d_sj || !workspace || batch <= 0 || n <= 0 || w <= 0) return GDN_ERR_ARG;
+    return gdn_any_project_bwd(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, d_lin_w, d_a, d_c,
+                               (hipStream_t)stream);
+  }
   if (w > GDN_MAX_W) {
     if (!x || !d_xlin || !d_si || !d_sj || !workspace || batch <= 0 || n <= 0) return GDN_ERR_ARG;
     return gdn_long_project_bwd(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, d_lin_w, d_a, d_c,
@@ -781,7 +795,7 @@ extern "C" int gdn_terms_bwd_acc(const float* lin_w, const float* att_i, const f
   if (!lin_w || !att_i || !att_j || !att_em_i || !att_em_j || !emb || !d_a || !d_c || !d_lin_w || !d_att_i ||
       !d_att_j || !d_att_em_i || !d_att_em_j || !d_emb || n <= 0 || d <= 0 || w <= 0)
     return GDN_ERR_ARG;
-  if (w > GDN_MAX_W)   // long windows: d_a at pitch gdn_terms_pitch(w)
+  if (w > GDN_MAX_W || gdn_any_width(d))   // long windows / other widths: d_a at pitch gdn_terms_pitch(w), run-time d
     return gdn_long_terms_bwd(lin_w, att_i, att_j, att_em_i, att_em_j, emb, d_a, d_c, n, d, w, d_lin_w, d_att_i,
                               d_att_j, d_att_em_i, d_att_em_j, d_emb, accumulate_emb, (hipStream_t)stream);
   if (d > 256 || (256 % d) != 0) return GDN_ERR_UNSUPPORTED;

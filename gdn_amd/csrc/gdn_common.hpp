@@ -69,6 +69,28 @@ int gdn_long_terms_bwd(const float* lin_w, const float* att_i, const float* att_
                        const float* att_em_j, const float* emb, const float* d_a, const float* d_c, int n, int d, int w,
                        float* d_lin_w, float* d_att_i, float* d_att_j, float* d_att_em_i, float* d_att_em_j,
                        float* d_emb, int accumulate_emb, hipStream_t stream);
+int gdn_long_project_reduce(const float* part, int parts, int batch, int n, int w, int d, const float* d_si,
+                            const float* d_sj, float* d_lin_w, float* d_a, float* d_c, hipStream_t stream);
+// gdn_any_width.hip: embedding widths other than 16 / 32 / 64 / 128 (1 <= d <= GDN_ANY_MAX_D); the staged entry points
+// hand every such d to these before any other path, at every n, w, k of the envelope.  Dense [B*n, d] rows.
+#define GDN_ANY_MAX_D 256
+bool gdn_any_width(int d);
+int gdn_any_project(const float* xb, long long bstride, long long sstride, const float* lin_w, const float* terms,
+                    int batch, int n, int w, int d, float* xlin, float* s_i, float* s_j, hipStream_t stream);
+int gdn_any_aggregate(const float* xlin, const float* s_i, const float* s_j, const uint16_t* nbr, const float* bias,
+                      int batch, int n, int d, int k, float* z, float* alpha, hipStream_t stream);
+int gdn_any_attn_bwd(const float* d_z, const float* xlin, const float* alpha, const float* s_i, const float* s_j,
+                     const uint16_t* nbr, const uint32_t* rent, const int32_t* rlen, int batch, int n, int d, int k,
+                     float* d_xlin, float* d_si, float* d_sj, float* d_bias, float* workspace,
+                     long long bias_ws_floats, hipStream_t stream);
+int gdn_any_head(const float* z, const float* emb, const float* bn1_affine, const float* bn2_affine,
+                 const float* out_w, const float* out_b, int batch, int n, int d, float* out, float* h2,
+                 hipStream_t stream);
+long long gdn_any_project_bwd_workspace_bytes(int n, int w, int d);
+int gdn_any_project_bwd_partials(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch,
+                                 int n, int w, int d, float* workspace, int* parts_out, hipStream_t stream);
+int gdn_any_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch, int n,
+                        int w, int d, float* workspace, float* d_lin_w, float* d_a, float* d_c, hipStream_t stream);
 // run-time choice between the two fused forward implementations: GDN_FUSED_PATH=valu keeps the fp32 VALU
 // row-gather kernel for every shape (read once per process)
 static inline bool gdn_use_dense_path() {

@@ -1283,6 +1283,9 @@ extern "C" int gdn_project_fwd_series(const float* series, int series_len, int f
   if (!series || !lin_w || !node_terms || !xlin || !s_i || !s_j || series_len <= 0 || first < 0 || w <= 0)
     return GDN_ERR_ARG;
   if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;   // last window must fit
+  if (gdn_any_width(d))   // embedding widths other than the four: gdn_any_width.hip
+    return gdn_any_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
+                           (hipStream_t)stream);
   if (w > GDN_MAX_W)   // long windows: the matrix-core projection of gdn_long_window.hip
     return gdn_long_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
                             (hipStream_t)stream);
@@ -1300,6 +1303,9 @@ int gdn_forward_staged_ok(int n, int w, int d, int k) {
 static int project_fwd_impl(const float* x, const float* lin_w, const float* node_terms, int batch,
                             int n, int w, int d, float* xlin, float* s_i, float* s_j, void* stream, bool wide) {
   if (!x || !lin_w || !node_terms || !xlin || !s_i || !s_j) return GDN_ERR_ARG;
+  if (gdn_any_width(d))   // embedding widths other than the four (both forms: exact fp32): gdn_any_width.hip
+    return gdn_any_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
+                           (hipStream_t)stream);
   if (w > GDN_MAX_W)   // long windows (both forms: exact fp32, no 16-bit operands): gdn_long_window.hip
     return gdn_long_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
                             (hipStream_t)stream);
@@ -1332,6 +1338,8 @@ static int attn_aggregate_fwd_impl(const float* xlin, const float* s_i, const fl
                                    int batch, int n, int d, int k, float* z, float* alpha,
                                    void* stream, bool wide) {
   if (!xlin || !s_i || !s_j || !nbr || !deg || !bias || !z) return GDN_ERR_ARG;
+  if (gdn_any_width(d))   // embedding widths other than the four (fp32 gathers, both forms): gdn_any_width.hip
+    return gdn_any_aggregate(xlin, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
   if (!wide && batch > 0 && gdn_use_dense_path() && gdn_dense_supported(n, 1, d, k))
     return gdn_dense_attn_aggregate(xlin, 0, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
   Plan pl; int threads;
@@ -1490,6 +1498,8 @@ static int head_launch(const ZT* z, const float* emb, const float* bn1_affine, c
 extern "C" int gdn_head_fwd(const float* z, const float* emb, const float* bn1_affine,
                             const float* bn2_affine, const float* out_w, const float* out_b, int batch,
                             int n, int d, float* out, float* h2, void* stream) {
+  if (gdn_any_width(d))   // embedding widths other than the four: gdn_any_width.hip
+    return gdn_any_head(z, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, d, out, h2, (hipStream_t)stream);
   return head_launch<float>(z, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, d, out, h2, stream);
 }
 

@@ -86,6 +86,7 @@ __device__ __forceinline__ void emit_list(const int* __restrict__ rank_of, int i
 
 // One workgroup per target sensor i: reference models/GDN.py:148-159 (cosine row, top-k),
 // then the list form of :161-163.
+template <bool V4 = true>
 __device__ __forceinline__ void graph_row(
     const float* __restrict__ emb, int n, int d, int k, int pitch, int64_t* __restrict__ topk_idx,
     uint16_t* __restrict__ nbr, int32_t* __restrict__ deg, float* __restrict__ cos_out, float* smem_graph) {
@@ -104,7 +105,15 @@ __device__ __forceinline__ void graph_row(
   for (int j = threadIdx.x; j < n; j += blockDim.x) {
     const float4* ej4 = reinterpret_cast<const float4*>(emb + (size_t)j * d);
     float dot = 0.f, nj2 = 0.f;
-    for (int t = 0; t < d / 4; ++t) {
+    if constexpr (!V4) {   // d % 4 != 0 (rows not 16-byte aligned): column by column, the same k-ordered chains
+      const float* ej = emb + (size_t)j * d;
+      for (int t = 0; t < d; ++t) {
+        const float b = ej[t];
+        dot = fmaf(ei[t], b, dot);
+        nj2 = fmaf(b, b, nj2);
+      }
+    }
+    for (int t = 0; t < (V4 ? d / 4 : 0); ++t) {
       const float4 a4 = ei4[t], b4 = ej4[t];
       dot = fmaf(a4.x, b4.x, dot); nj2 = fmaf(b4.x, b4.x, nj2);
       dot = fmaf(a4.y, b4.y, dot); nj2 = fmaf(b4.y, b4.y, nj2);
@@ -153,6 +162,14 @@ __global__ __launch_bounds__(256) void gdn_graph_kernel(
     uint16_t* __restrict__ nbr, int32_t* __restrict__ deg, float* __restrict__ cos_out) {
   extern __shared__ float smem_graph[];
   graph_row(emb, n, d, k, pitch, topk_idx, nbr, deg, cos_out, smem_graph);
+}
+
+// widths that are not a multiple of 4 (gdn_any_width.hip's range): scalar row reads
+__global__ __launch_bounds__(256) void gdn_graph_scalar_kernel(
+    const float* __restrict__ emb, int n, int d, int k, int pitch, int64_t* __restrict__ topk_idx,
+    uint16_t* __restrict__ nbr, int32_t* __restrict__ deg, float* __restrict__ cos_out) {
+  extern __shared__ float smem_graph[];
+  graph_row<false>(emb, n, d, k, pitch, topk_idx, nbr, deg, cos_out, smem_graph);
 }
 
 // Same list build from a given [n,k] top-k table.  The table is caller data: entries outside
@@ -242,8 +259,14 @@ __global__ void gdn_bn_fold_kernel(const float* __restrict__ weight, const float
 extern "C" int gdn_topk_graph(const float* emb, int n, int d, int k, int64_t* topk_idx, uint16_t* nbr,
                               int32_t* deg, float* cos_out, void* stream) {
   if (!emb || !topk_idx || !nbr || !deg || n <= 0 || d <= 0 || k <= 0) return GDN_ERR_ARG;
-  if (k > n || n > 4096 || k + 1 > 1024 || (d & 3)) return GDN_ERR_UNSUPPORTED;
+  if (k > n || n > 4096 || k + 1 > 1024) return GDN_ERR_UNSUPPORTED;
   const int pitch = gdn_nbr_pitch(k);
+  if (d & 3) {   // any width up to 256 (gdn_any_width.hip): rows read column by column
+    if (!gdn_any_width(d)) return GDN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(gdn_graph_scalar_kernel, dim3(n), dim3(256), 2 * n * sizeof(float), (hipStream_t)stream,
+                       emb, n, d, k, pitch, topk_idx, nbr, deg, cos_out);
+    return gdn_launch_status();
+  }
   hipLaunchKernelGGL(gdn_graph_kernel, dim3(n), dim3(256), 2 * n * sizeof(float), (hipStream_t)stream,
                      emb, n, d, k, pitch, topk_idx, nbr, deg, cos_out);
   return gdn_launch_status();

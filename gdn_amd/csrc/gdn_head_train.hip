@@ -192,6 +192,59 @@ __device__ __forceinline__ void col_reduce(const double (&v)[4], double* red, un
   }
 }
 
+// Row segments at a run-time width dd (ANY: gdn_any_width.hip's widths, the kernel instantiated on the padded width
+// D >= dd): columns >= dd read as 0 and are never stored; float4 where dd % 4 == 0, else column by column.
+template <bool ANY>
+__device__ __forceinline__ void hld(const float* p, int c0, int dd, float (&v)[4]) {
+  if constexpr (!ANY) {
+    ld4(p + c0, v);
+  } else if ((dd & 3) == 0) {
+    if (c0 < dd) ld4(p + c0, v);
+    else v[0] = v[1] = v[2] = v[3] = 0.f;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = c0 + q < dd ? p[c0 + q] : 0.f;
+  }
+}
+// the same from LDS (scalar reads at ANY widths: row starts k * dd are not 16-byte aligned)
+template <bool ANY>
+__device__ __forceinline__ void hldc(const float* p, int c0, int dd, float (&v)[4]) {
+  if constexpr (!ANY) {
+    ld4(p + c0, v);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = c0 + q < dd ? p[c0 + q] : 0.f;
+  }
+}
+template <bool ANY>
+__device__ __forceinline__ void hst(float* p, int c0, int dd, const float4& v) {
+  if constexpr (!ANY) {
+    *reinterpret_cast<float4*>(p + c0) = v;
+  } else if ((dd & 3) == 0) {
+    if (c0 < dd) *reinterpret_cast<float4*>(p + c0) = v;
+  } else {
+    const float t[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (c0 + q < dd) p[c0 + q] = t[q];
+  }
+}
+
+// col_reduce with the accumulator laid out at the run-time width dd (gdn_any_width.hip's widths)
+template <int D>
+__device__ __forceinline__ void col_reduce_rt(const double (&v)[4], double* red, unsigned long long* gdst, int tid,
+                                              int slot, int c0, int dd) {
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[slot * D + c0 + q] = v[q];
+  __syncthreads();
+  if (tid < dd) {
+    double s = 0.0;
+    for (int q = 0; q < HG<D>::SLOTS; ++q) s += red[q * D + tid];
+    fx_atomic_add(gdst + tid, dd, s);
+  }
+}
+
 enum { H_STAT1 = 0, H_STAT2 = 1, H_OUT = 2, H_BWD2 = 3, H_BWD1 = 4, H_DZ = 5 };
 
 #define GDN_HEAD_UNROLL 4   // windows in flight per thread: the passes are latency bound otherwise
@@ -531,6 +584,353 @@ __global__ __launch_bounds__(256) void gdn_head_train_kernel(const HeadArgs a) {
   }
 }
 
+// gdn_head_train_kernel's passes at a run-time width (ANY: d = dd_arg, 1..256, gdn_any_width.hip's widths) on the
+// padded width D: global rows, the accumulator blocks and the LDS column tables are laid out at dd, lane groups at D.
+// The four tile widths keep gdn_head_train_kernel above, source and all (its code and bits stay as they were).
+template <int D, int MODE, bool ANY>
+__device__ __forceinline__ void head_train_body(const HeadArgs& a, int dd_arg) {
+  using G = HG<D>;
+  const int dd = ANY ? dd_arg : D;
+  constexpr int U = GDN_HEAD_UNROLL;
+  __shared__ double red[1024];                                // [SLOTS][D]
+  const int tid = threadIdx.x, lr = tid % G::LPR, slot = tid / G::LPR, c0 = lr * 4;
+  const double rows = (double)a.batch * (double)a.n;
+  const int chunk = blockIdx.x % a.chunks, part = blockIdx.x / a.chunks;
+  const int n = chunk * G::SLOTS + slot;
+  const bool live = n < a.n;
+  const int b0 = (int)((long long)a.batch * part / a.parts);
+  const int b1 = (int)((long long)a.batch * (part + 1) / a.parts);
+
+  // (Measured, round 2: issuing the first round of row loads BEFORE the statistics prologue below, or 8 rows
+  // in flight instead of 4, made the backward passes 1-6 us slower — more live registers — and the forward
+  // ones ~1 us faster: a wash, not kept.)
+  unsigned rng_k0 = 0, rng_k1 = 0;
+  if (MODE >= H_OUT && a.rng) {
+    const unsigned long long seed = (unsigned long long)a.rng[0], step = (unsigned long long)a.rng[1];
+    rng_k0 = (unsigned)seed ^ (unsigned)(step * 0x9E3779B97F4A7C15ull >> 32);
+    rng_k1 = (unsigned)(seed >> 32) + (unsigned)step * 0x7F4A7C15u;
+  }
+  float e[4] = {0.f, 0.f, 0.f, 0.f};
+  if (MODE >= H_STAT2 && live) hld<ANY>(a.emb + (size_t)n * dd, c0, dd, e);
+  float zq[U][4], mq[U][4], goq[U], gaq[U][4];
+  auto load_round = [&](int bq) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {                     // all loads of the round first
+      const int b = min(bq + u, b1 - 1);
+      const size_t row = (size_t)b * a.n + n;
+      hld<ANY>(a.z + row * dd, c0, dd, zq[u]);
+      mq[u][0] = mq[u][1] = mq[u][2] = mq[u][3] = 1.f;
+      if (MODE >= H_OUT && a.mask) {
+        hld<ANY>(a.mask + row * dd, c0, dd, mq[u]);
+      } else if (ANY && MODE >= H_OUT && a.keep) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) mq[u][v] = c0 + v < dd ? a.keep[row * dd + c0 + v] * a.keep_scale : 0.f;
+      } else if (MODE >= H_OUT && a.keep) {           // one byte per element: a quarter of the mask traffic
+        const uchar4 kb = *reinterpret_cast<const uchar4*>(a.keep + row * D + c0);
+        mq[u][0] = kb.x * a.keep_scale; mq[u][1] = kb.y * a.keep_scale;
+        mq[u][2] = kb.z * a.keep_scale; mq[u][3] = kb.w * a.keep_scale;
+      } else if (MODE >= H_OUT && a.rng) {            // drawn in place: no mask traffic at all
+        const unsigned e0 = (unsigned)(row * dd + c0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) mq[u][v] = gdn_mix32(e0 + v, rng_k0, rng_k1) >= a.rng_threshold ? a.keep_scale : 0.f;
+      }
+      goq[u] = (MODE >= H_BWD2 && a.d_out) ? a.d_out[row] : 0.f;
+      gaq[u][0] = gaq[u][1] = gaq[u][2] = gaq[u][3] = 0.f;
+      if (MODE >= H_BWD2 && a.d_act) hld<ANY>(a.d_act + row * dd, c0, dd, gaq[u]);
+    }
+  };
+
+  // totals of the accumulators earlier passes left behind (summed over their replicas once per workgroup):
+  // rows 0-3 = column sums of z, z^2, h1, h1^2; rows 4-7 = sums of d_y2, d_y2*xhat2, d_y1, d_y1*xhat1
+  __shared__ double tot[8 * D];                               // [8][dd]
+  constexpr int NF = MODE >= H_OUT ? 4 : (MODE >= H_STAT2 ? 2 : 0);
+  constexpr int NB = MODE == H_DZ ? 4 : (MODE == H_BWD1 ? 2 : 0);
+  const unsigned long long* fwords = reinterpret_cast<const unsigned long long*>(a.fstats);
+  unsigned long long* awords = reinterpret_cast<unsigned long long*>(a.acc);
+  // A row of totals is converted from its limbs by the FIRST pass that consumes it (every workgroup of that pass
+  // does the same exact integer arithmetic); workgroup 0 leaves the fp64 value in the block's totals, where the
+  // later passes read it: 8 row conversions per step instead of 24 (each costs a pass ~1.5 us of prologue).
+  //   forward rows 0,1: fresh in H_STAT2; rows 2,3: fresh in H_OUT.  backward rows 0,1: fresh in H_BWD1; rows
+  //   2,3: fresh in H_DZ; rows 4,5 (d_lin_w, d_lin_b) are converted by the finish kernel.
+  for (int t = tid; t < NF * dd; t += 256) {
+    const int row = t / dd;
+    const bool fresh = (MODE == H_STAT2) || (MODE == H_OUT && row >= 2);
+    double v;
+    if (fresh) {
+      v = fx_total(fwords + fx_at(0, 4, row, dd, t % dd), dd, (size_t)4 * GDN_FX_WORDS * dd);
+      if (blockIdx.x == 0) const_cast<double*>(a.fstats)[t] = v;
+    } else {
+      v = a.fstats[t];
+    }
+    tot[t] = v;
+  }
+  for (int t = tid; t < NB * dd; t += 256) {
+    const int row = t / dd;
+    const bool fresh = (MODE == H_BWD1) || (MODE == H_DZ && row >= 2);
+    double v;
+    if (fresh) {
+      v = fx_total(awords + fx_at(0, 6, row, dd, t % dd), dd, (size_t)6 * GDN_FX_WORDS * dd);
+      if (blockIdx.x == 0) a.acc[t] = v;
+    } else {
+      v = a.acc[t];
+    }
+    tot[4 * dd + t] = v;
+  }
+  if constexpr (NF > 0) __syncthreads();
+
+  if constexpr (MODE == H_OUT) {
+    // running_mean / running_var / num_batches_tracked of both BatchNorms (torch: momentum update with
+    // the UNBIASED batch variance); done once, by workgroup 0 of the last forward pass
+    if (blockIdx.x == 0) {
+      for (int q = tid; q < 2 * dd; q += 256) {   // (one round below d = 256)
+        const int which = q / dd, t = q % dd;
+        float* rm = which ? a.run.rm2 : a.run.rm1;
+        float* rv = which ? a.run.rv2 : a.run.rv1;
+        const float mom = which ? a.run.mom2 : a.run.mom1;
+        if (rm && rv) {
+          const double m = tot[which * 2 * dd + t] / rows;
+          double var = tot[which * 2 * dd + dd + t] / rows - m * m;
+          if (var < 0.0) var = 0.0;
+          rm[t] = (1.f - mom) * rm[t] + mom * (float)m;
+          rv[t] = (1.f - mom) * rv[t] + mom * (float)(var * rows / (rows - 1.0));
+        }
+      }
+      if (tid == 0) {
+        if (a.run.nbt1) *a.run.nbt1 += 1;
+        if (a.run.nbt2) *a.run.nbt2 += 1;
+      }
+    }
+  }
+
+  // Per-column constants ONCE per workgroup (one thread per column and BatchNorm: the fp64 divisions and the
+  // square root), handed to the SLOTS lane groups through LDS — computed per thread they were the same ~20 fp64
+  // transcendental sequences 16 times over, a couple of microseconds of every latency-bound pass.
+  __shared__ float colc[12 * D];      // [12][dd]: [mu1 | is1 | sc1 | be1 | mu2 | is2 | sc2 | be2 | m2a | m2b | m1a | m1b]
+  if constexpr (MODE >= H_STAT2) {
+    constexpr int NBN = MODE >= H_OUT ? 2 : 1;
+    for (int t = tid; t < NBN * dd; t += 256) {
+      const int which = t / dd, c = t - which * dd;
+      const double* sum = tot + which * 2 * dd;
+      const double m = sum[c] / rows;
+      double var = sum[dd + c] / rows - m * m;
+      if (var < 0.0) var = 0.0;
+      const float is = (float)(1.0 / sqrt(var + (double)(which ? a.eps2 : a.eps1)));
+      float* dst = colc + which * 4 * dd;
+      dst[c] = (float)m;
+      dst[dd + c] = is;
+      dst[2 * dd + c] = (which ? a.g2 : a.g1)[c] * is;
+      dst[3 * dd + c] = (which ? a.b2 : a.b1)[c];
+    }
+    if constexpr (MODE >= H_BWD1) {
+      constexpr int NM = MODE == H_DZ ? 4 : 2;
+      for (int t = tid; t < NM * dd; t += 256) colc[8 * dd + t] = (float)(tot[4 * dd + t] / rows);   // means of d_y2, d_y2 xhat2, d_y1, d_y1 xhat1
+    }
+    __syncthreads();
+  }
+  BnCols bn1 = {}, bn2 = {};
+  if constexpr (MODE >= H_STAT2) {
+    hldc<ANY>(colc, c0, dd, bn1.mu); hldc<ANY>(colc + dd, c0, dd, bn1.is);
+    hldc<ANY>(colc + 2 * dd, c0, dd, bn1.sc); hldc<ANY>(colc + 3 * dd, c0, dd, bn1.be);
+  }
+  if constexpr (MODE >= H_OUT) {
+    hldc<ANY>(colc + 4 * dd, c0, dd, bn2.mu); hldc<ANY>(colc + 5 * dd, c0, dd, bn2.is);
+    hldc<ANY>(colc + 6 * dd, c0, dd, bn2.sc); hldc<ANY>(colc + 7 * dd, c0, dd, bn2.be);
+  }
+  float w4[4] = {0.f, 0.f, 0.f, 0.f};
+  if (MODE >= H_OUT && a.w) hld<ANY>(a.w, c0, dd, w4);
+  float m2a[4] = {}, m2b[4] = {}, m1a[4] = {}, m1b[4] = {};
+  if constexpr (MODE >= H_BWD1) {
+    hldc<ANY>(colc + 8 * dd, c0, dd, m2a);      // mean of d_y2
+    hldc<ANY>(colc + 9 * dd, c0, dd, m2b);      // mean of d_y2 * xhat2
+  }
+  if constexpr (MODE == H_DZ) {
+    hldc<ANY>(colc + 10 * dd, c0, dd, m1a);
+    hldc<ANY>(colc + 11 * dd, c0, dd, m1b);
+  }
+  double acc0[4] = {0.0, 0.0, 0.0, 0.0}, acc1[4] = {0.0, 0.0, 0.0, 0.0}, acc2[4] = {0.0, 0.0, 0.0, 0.0};
+  double acc_s = 0.0;
+  const float bias_o = (MODE == H_OUT && a.bo) ? a.bo[0] : 0.f;
+  const float mse_scale = (float)(2.0 / rows);
+  if (live) {
+    for (int bq = b0; bq < b1; bq += U) {
+      load_round(bq);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (bq + u >= b1) break;
+        const size_t row = (size_t)(bq + u) * a.n + n;
+        const float(&z)[4] = zq[u];
+        const float(&m)[4] = mq[u];
+        if constexpr (MODE == H_STAT1) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const double zd = (double)z[v];
+            acc0[v] += zd;
+            acc1[v] = fma(zd, zd, acc1[v]);
+          }
+          continue;
+        }
+        float y1[4], a1[4], h1[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          y1[v] = fmaf(z[v] - bn1.mu[v], bn1.sc[v], bn1.be[v]);
+          a1[v] = fmaxf(y1[v], 0.f);
+          h1[v] = a1[v] * e[v];
+        }
+        if constexpr (MODE == H_STAT2) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const double hd = (double)h1[v];
+            acc0[v] += hd;
+            acc1[v] = fma(hd, hd, acc1[v]);
+          }
+          continue;
+        }
+        float y2[4], a2[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          y2[v] = fmaf(h1[v] - bn2.mu[v], bn2.sc[v], bn2.be[v]);
+          a2[v] = fmaxf(y2[v], 0.f);
+        }
+        if constexpr (MODE == H_OUT) {
+          if (a.act) {   // MLP head: hand the dropped-out activation to the OutLayer (models/GDN.py:182-183)
+            hst<ANY>(a.act + row * dd, c0, dd, make_float4(a2[0] * m[0], a2[1] * m[1], a2[2] * m[2], a2[3] * m[3]));
+            continue;
+          }
+          float part_o = 0.f;
+#pragma unroll
+          for (int v = 0; v < 4; ++v) part_o = fmaf(a2[v] * m[v], w4[v], part_o);
+#pragma unroll
+          for (int s = 1; s < G::LPR; s <<= 1) part_o += __shfl_xor(part_o, s);   // lanes of one row
+          if (lr == 0) {
+            const float o = part_o + bias_o;
+            a.out[row] = o;
+            if (a.y) {
+              const float df = o - a.y[row];
+              acc_s = fma((double)df, (double)df, acc_s);
+              a.mse_d_out[row] = df * mse_scale;
+            }
+          }
+          continue;
+        }
+        const float go = goq[u];
+        float dy2[4], x2h[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const float gh = a.d_act ? gaq[u][v] : go * w4[v];   // gradient of the head's [BN, d] activation
+          dy2[v] = y2[v] > 0.f ? gh * m[v] : 0.f;
+          x2h[v] = (h1[v] - bn2.mu[v]) * bn2.is[v];
+        }
+        if constexpr (MODE == H_BWD2) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            acc0[v] += (double)dy2[v];
+            acc1[v] += (double)(dy2[v] * x2h[v]);
+            acc2[v] += (double)(go * a2[v] * m[v]);
+          }
+          if (lr == 0) acc_s += (double)go;
+          continue;
+        }
+        float dh1[4], dy1[4], x1h[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          dh1[v] = bn2.sc[v] * (dy2[v] - m2a[v] - x2h[v] * m2b[v]);
+          dy1[v] = y1[v] > 0.f ? dh1[v] * e[v] : 0.f;
+          x1h[v] = (z[v] - bn1.mu[v]) * bn1.is[v];
+        }
+        if constexpr (MODE == H_BWD1) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            acc0[v] += (double)dy1[v];
+            acc1[v] += (double)(dy1[v] * x1h[v]);
+            acc2[v] += (double)(dh1[v] * a1[v]);        // d_emb[n, column]: private to this thread
+          }
+          continue;
+        }
+        if constexpr (MODE == H_DZ) {
+          float4 o;
+          o.x = bn1.sc[0] * (dy1[0] - m1a[0] - x1h[0] * m1b[0]);
+          o.y = bn1.sc[1] * (dy1[1] - m1a[1] - x1h[1] * m1b[1]);
+          o.z = bn1.sc[2] * (dy1[2] - m1a[2] - x1h[2] * m1b[2]);
+          o.w = bn1.sc[3] * (dy1[3] - m1a[3] - x1h[3] * m1b[3]);
+          hst<ANY>(a.d_z + row * dd, c0, dd, o);
+        }
+      }
+    }
+  }
+
+  if constexpr (MODE == H_OUT) {
+    if (a.y) {                                    // loss = mean((out - y)^2): fixed-order reduction, last workgroup finishes
+      __shared__ bool last;
+      __syncthreads();
+      red[tid] = acc_s;
+      __syncthreads();
+      for (int q = 128; q > 0; q >>= 1) {
+        if (tid < q) red[tid] += red[tid + q];
+        __syncthreads();
+      }
+      unsigned long long* ticket = reinterpret_cast<unsigned long long*>(a.mse_ws);
+      if (tid == 0) {
+        // no release/acquire fence (each would write back this XCD's whole L2: ~20 us over 512 workgroups): the
+        // partial is an agent-scope atomic store, acknowledged (vmcnt) before the ticket is taken, and the last
+        // workgroup reads the partials back with agent-scope atomic loads
+        __hip_atomic_store(a.mse_ws + 1 + blockIdx.x, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long t = __hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = t == (unsigned long long)gridDim.x - 1ull;
+      }
+      __syncthreads();
+      if (last) {
+        double sum = 0.0;
+        for (int q = tid; q < (int)gridDim.x; q += 256)
+          sum += __hip_atomic_load(a.mse_ws + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        red[tid] = sum;
+        __syncthreads();
+        for (int q = 128; q > 0; q >>= 1) {
+          if (tid < q) red[tid] += red[tid + q];
+          __syncthreads();
+        }
+        if (tid == 0) {
+          a.loss[0] = (float)(red[0] / rows);
+          __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+  }
+  const int repl = blockIdx.x % GDN_HEAD_REPL;
+  if constexpr (MODE == H_STAT1 || MODE == H_STAT2) {
+    const int r0 = MODE == H_STAT1 ? 0 : 2;
+    col_reduce_rt<D>(acc0, red, awords + fx_at(repl, 4, r0, dd, 0), tid, slot, c0, dd);
+    col_reduce_rt<D>(acc1, red, awords + fx_at(repl, 4, r0 + 1, dd, 0), tid, slot, c0, dd);
+  }
+  if constexpr (MODE == H_BWD2) {
+    col_reduce_rt<D>(acc0, red, awords + fx_at(repl, 6, 0, dd, 0), tid, slot, c0, dd);
+    col_reduce_rt<D>(acc1, red, awords + fx_at(repl, 6, 1, dd, 0), tid, slot, c0, dd);
+    col_reduce_rt<D>(acc2, red, awords + fx_at(repl, 6, 4, dd, 0), tid, slot, c0, dd);
+    __syncthreads();
+    red[tid] = acc_s;
+    __syncthreads();
+    if (tid == 0) {
+      double s = 0.0;
+      for (int q = 0; q < 256; ++q) s += red[q];
+      fx_atomic_add(awords + fx_at(repl, 6, 5, dd, 0), dd, s);
+    }
+  }
+  if constexpr (MODE == H_BWD1) {
+    col_reduce_rt<D>(acc0, red, awords + fx_at(repl, 6, 2, dd, 0), tid, slot, c0, dd);
+    col_reduce_rt<D>(acc1, red, awords + fx_at(repl, 6, 3, dd, 0), tid, slot, c0, dd);
+    if (live)   // every (part, sensor, column) has exactly one owner: plain store, summed by the finish kernel
+      hst<ANY>(a.demb_part + ((size_t)part * a.n + n) * dd, c0, dd,
+               make_float4((float)acc2[0], (float)acc2[1], (float)acc2[2], (float)acc2[3]));
+  }
+}
+
+// gdn_any_width.hip's widths: d at run time on the padded width DP (16 .. 256)
+template <int DP, int MODE>
+__global__ __launch_bounds__(256) void gdn_any_head_train_kernel(const HeadArgs a, int d) {
+  head_train_body<DP, MODE, true>(a, d);
+}
+
+template <int MAXD>   // largest d: 128 for the tile widths, 256 at gdn_any_width.hip's
 __device__ __forceinline__ void head_finish_body(double* __restrict__ ws, const float* __restrict__ demb_part,
                                                  int parts, int n, int d, float* d_bn1_w, float* d_bn1_b, float* d_bn2_w,
                                                  float* d_bn2_b, float* d_lin_w, float* d_lin_b, float* d_emb,
@@ -539,7 +939,7 @@ __device__ __forceinline__ void head_finish_body(double* __restrict__ ws, const 
   if (block == 0) {
     // the six gradient rows of the head, then — every pass of this step is complete, this is the last reader —
     // both accumulator blocks are left zeroed for the next step, which then needs no memset launches
-    __shared__ float fin[6 * 128];
+    __shared__ float fin[6 * MAXD];
     unsigned long long* wsw = reinterpret_cast<unsigned long long*>(ws);
     for (int i = (int)threadIdx.x; i < 6 * d; i += (int)blockDim.x)     // rows 0-3: converted by H_BWD1 / H_DZ
       fin[i] = i < 4 * d ? (float)ws[i]
@@ -571,8 +971,16 @@ __global__ void gdn_head_finish_kernel(double* __restrict__ ws, const float* __r
                                        int parts, int n, int d, float* d_bn1_w, float* d_bn1_b, float* d_bn2_w,
                                        float* d_bn2_b, float* d_lin_w, float* d_lin_b, float* d_emb,
                                        double* zero_stats) {
-  head_finish_body(ws, demb_part, parts, n, d, d_bn1_w, d_bn1_b, d_bn2_w, d_bn2_b, d_lin_w, d_lin_b, d_emb, zero_stats,
-                   (int)blockIdx.x);
+  head_finish_body<128>(ws, demb_part, parts, n, d, d_bn1_w, d_bn1_b, d_bn2_w, d_bn2_b, d_lin_w, d_lin_b, d_emb,
+                        zero_stats, (int)blockIdx.x);
+}
+
+__global__ void gdn_any_head_finish_kernel(double* __restrict__ ws, const float* __restrict__ demb_part,
+                                           int parts, int n, int d, float* d_bn1_w, float* d_bn1_b, float* d_bn2_w,
+                                           float* d_bn2_b, float* d_lin_w, float* d_lin_b, float* d_emb,
+                                           double* zero_stats) {
+  head_finish_body<256>(ws, demb_part, parts, n, d, d_bn1_w, d_bn1_b, d_bn2_w, d_bn2_b, d_lin_w, d_lin_b, d_emb,
+                        zero_stats, (int)blockIdx.x);
 }
 
 // The training step's two small reductions in ONE launch (a launch costs ~5 us inside a replayed step whatever
@@ -588,7 +996,7 @@ struct TailArgs {
 };
 __global__ __launch_bounds__(256) void gdn_train_tail_kernel(const TailArgs t) {
   if ((int)blockIdx.x < t.g1)
-    head_finish_body(t.head_ws, t.demb_part, t.parts, t.n, t.d, t.d_bn1_w, t.d_bn1_b, t.d_bn2_w, t.d_bn2_b, t.d_lin_w,
+    head_finish_body<128>(t.head_ws, t.demb_part, t.parts, t.n, t.d, t.d_bn1_w, t.d_bn1_b, t.d_bn2_w, t.d_bn2_b, t.d_lin_w,
                      t.d_lin_b, t.d_emb, t.zero_stats, (int)blockIdx.x);
   else
     gdn_project_reduce_body(t.proj_part, t.rows, t.d, t.n, t.w, t.wp, t.d_proj_w, t.d_a, t.d_c, (int)blockIdx.x - t.g1);
@@ -612,6 +1020,40 @@ void launch_pass(HeadArgs a, hipStream_t st) {
   a.chunks = (a.n + HG<D>::SLOTS - 1) / HG<D>::SLOTS;
   a.parts = head_parts(a.batch, a.chunks, MODE);
   hipLaunchKernelGGL((gdn_head_train_kernel<D, MODE>), dim3(a.chunks * a.parts), dim3(256), 0, st, a);
+}
+
+template <int DP, int MODE>
+void launch_pass_any(HeadArgs a, int d, hipStream_t st) {
+  a.chunks = (a.n + HG<DP>::SLOTS - 1) / HG<DP>::SLOTS;
+  a.parts = head_parts(a.batch, a.chunks, MODE);
+  hipLaunchKernelGGL((gdn_any_head_train_kernel<DP, MODE>), dim3(a.chunks * a.parts), dim3(256), 0, st, a, d);
+}
+
+// the three forward (FWD) or backward passes at a gdn_any_width.hip width; returns the chunk count of the passes
+template <bool FWD>
+int head_passes_any(const HeadArgs& a, int d, hipStream_t st) {
+  const int dp = d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : d <= 128 ? 128 : 256;
+#define GDN_HEAD_ANY(DP)                                                                        \
+  case DP:                                                                                      \
+    if (FWD) {                                                                                  \
+      launch_pass_any<DP, H_STAT1>(a, d, st);                                                   \
+      launch_pass_any<DP, H_STAT2>(a, d, st);                                                   \
+      launch_pass_any<DP, H_OUT>(a, d, st);                                                     \
+    } else {                                                                                    \
+      launch_pass_any<DP, H_BWD2>(a, d, st);                                                    \
+      launch_pass_any<DP, H_BWD1>(a, d, st);                                                    \
+      launch_pass_any<DP, H_DZ>(a, d, st);                                                      \
+    }                                                                                           \
+    return (a.n + HG<DP>::SLOTS - 1) / HG<DP>::SLOTS;
+  switch (dp) {
+    GDN_HEAD_ANY(16)
+    GDN_HEAD_ANY(32)
+    GDN_HEAD_ANY(64)
+    GDN_HEAD_ANY(128)
+    GDN_HEAD_ANY(256)
+  }
+#undef GDN_HEAD_ANY
+  return 0;
 }
 
 // loss = mean((out - y)^2) and its gradient d_out = 2 (out - y) / count in one launch (train.py:20-23
@@ -731,7 +1173,8 @@ static int head_train_fwd_impl(const float* z, const float* emb, const float* bn
   if (!z || !emb || !bn1_w || !bn1_b || !bn2_w || !bn2_b || !stats) return GDN_ERR_ARG;
   if (act ? (lin_w || lin_b || out) : (!lin_w || !lin_b || !out)) return GDN_ERR_ARG;
   if (!head_shape_ok(batch, n, d)) return GDN_ERR_ARG;   // torch: "Expected more than 1 value per channel"
-  if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
+  const bool any = gdn_any_width(d);                      // other widths: run-time d (head_train_body<.., true>)
+  if (!any && d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   HeadArgs a = {};
   a.z = z; a.emb = emb; a.g1 = bn1_w; a.b1 = bn1_b; a.g2 = bn2_w; a.b2 = bn2_b; a.w = lin_w; a.bo = lin_b;
@@ -745,6 +1188,10 @@ static int head_train_fwd_impl(const float* z, const float* emb, const float* bn
   a.run = {running_mean1, running_var1, running_mean2, running_var2, batches1, batches2, momentum1, momentum2};
   if (!zeroed && hipMemsetAsync(stats, 0, fx_block_words(4, d) * sizeof(double), st) != hipSuccess)
     return GDN_ERR_LAUNCH;
+  if (any) {
+    head_passes_any<true>(a, d, st);
+    return gdn_launch_status();
+  }
 #define GDN_HEAD_F(DD)                 \
   case DD:                             \
     launch_pass<DD, H_STAT1>(a, st);   \
@@ -802,7 +1249,8 @@ static int head_train_bwd_impl(const float* d_out, const float* z, const float* 
     return GDN_ERR_ARG;
   if (d_act ? (d_out || lin_w || d_lin_w || d_lin_b) : (!d_out || !lin_w || !d_lin_w || !d_lin_b)) return GDN_ERR_ARG;
   if (!head_shape_ok(batch, n, d)) return GDN_ERR_ARG;
-  if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
+  const bool any = gdn_any_width(d);
+  if (!any && d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   HeadArgs a = {};
   a.z = z; a.emb = emb; a.g1 = bn1_w; a.b1 = bn1_b; a.g2 = bn2_w; a.b2 = bn2_b; a.w = lin_w; a.bo = nullptr;
@@ -815,6 +1263,15 @@ static int head_train_bwd_impl(const float* d_out, const float* z, const float* 
   const size_t sums_bytes = fx_block_words(6, d) * sizeof(double);
   a.demb_part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + sums_bytes);
   if (!zeroed && hipMemsetAsync(workspace, 0, sums_bytes, st) != hipSuccess) return GDN_ERR_LAUNCH;
+  if (any) {
+    const int chunks = head_passes_any<false>(a, d, st);
+    if (defer_finish) return gdn_launch_status();
+    const int total = n * d > d ? n * d : d;
+    hipLaunchKernelGGL(gdn_any_head_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, st, workspace,
+                       a.demb_part, head_parts(batch, chunks, H_BWD1), n, d, d_bn1_w, d_bn1_b, d_bn2_w, d_bn2_b,
+                       d_lin_w, d_lin_b, d_emb, zeroed ? const_cast<double*>(stats) : nullptr);
+    return gdn_launch_status();
+  }
 #define GDN_HEAD_B(DD)                \
   case DD:                            \
     launch_pass<DD, H_BWD2>(a, st);   \

@@ -391,9 +391,15 @@ int gdn_long_project_bwd(const float* x, const float* d_xlin, const float* d_si,
   int parts = 0;
   const int rc = gdn_long_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, &parts, st);
   if (rc != GDN_OK) return rc;
+  return gdn_long_project_reduce(workspace, parts, batch, n, w, d, d_si, d_sj, d_lin_w, d_a, d_c, st);
+}
+
+// the partial blocks added in range order (also the reduce of gdn_any_width.hip's projection backward, any w)
+int gdn_long_project_reduce(const float* part, int parts, int batch, int n, int w, int d, const float* d_si,
+                            const float* d_sj, float* d_lin_w, float* d_a, float* d_c, hipStream_t st) {
   const int ap = gdn_terms_pitch(w);
   const int total = (d + 2) * w + 2 * (ap - w) + 2 * n;
-  hipLaunchKernelGGL(gdn_long_project_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, workspace, parts, d,
+  hipLaunchKernelGGL(gdn_long_project_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, part, parts, d,
                      w, ap, n, batch, d_si, d_sj, d_lin_w, d_a, d_c);
   return gdn_launch_status();
 }
@@ -402,7 +408,8 @@ int gdn_long_terms_bwd(const float* lin_w, const float* att_i, const float* att_
                        const float* att_em_j, const float* emb, const float* d_a, const float* d_c, int n, int d, int w,
                        float* d_lin_w, float* d_att_i, float* d_att_j, float* d_att_em_i, float* d_att_em_j,
                        float* d_emb, int accumulate_emb, hipStream_t st) {
-  if (w > GDN_LONG_MAX_W || d > 256 || (256 % d) != 0) return GDN_ERR_UNSUPPORTED;
+  // any d <= 256: a workgroup's 1024 threads hold 1024 / d whole column groups (the rest idle)
+  if (w > GDN_LONG_MAX_W || d > 256 || (!gdn_any_width(d) && (256 % d) != 0)) return GDN_ERR_UNSUPPORTED;
   int grid = (n * d + 1024 * 2 - 1) / (1024 * 2);
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(gdn_long_terms_bwd_kernel, dim3(grid), dim3(1024), 0, st, lin_w, att_i, att_j, att_em_i,

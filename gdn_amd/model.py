@@ -22,10 +22,11 @@ forward on CPU tensors raises.
                              OutLayer MLP on the fp32 matrix cores (gdn_mlp_train_fwd/bwd, any hidden width
                              up to 512; beyond: torch ops)
                              (`loss.backward()` reaches every parameter exactly as in the reference)
-  graphs beyond the LDS tile (gdn_tile_fits == 0, up to 4096 sensors) and windows longer than 64 ticks (up to
-                             1024): eval runs the staged chain project -> aggregate -> head with xlin / z in HBM
-                             (fp32 only), training the autograd path above — the staged entry points switch to their
-                             large-graph / long-window kernels by themselves
+  graphs beyond the LDS tile (gdn_tile_fits == 0, up to 4096 sensors), windows longer than 64 ticks (up to
+                             1024) and embedding widths other than 16 / 32 / 64 / 128 (any d up to 256): eval runs
+                             the staged chain project -> aggregate -> head with xlin / z in HBM (fp32 only), training
+                             the autograd path above — the staged entry points switch to their large-graph /
+                             long-window / any-width kernels by themselves
   harness.NativeTrainStep is the same arithmetic without autograd (flat buffers, in-kernel dropout, gdn_adam_step).
 """
 from __future__ import annotations
@@ -311,6 +312,7 @@ class GDN(nn.Module):
         c = _EvalConstants()
         c.key = key
         emb = self.embedding.weight
+        ops.check_width(emb.shape[1])                  # before any launch: d > 256 has no kernel
         if self.injected_graph is not None:
             c.graph = ops.graph_from_topk(self.injected_graph.to(emb.device))
         else:
@@ -429,7 +431,10 @@ class GDN(nn.Module):
 
     def _bf16_refusal(self) -> _lib.GdnHipError:
         """Why bf16 windows are refused where the tile form does not take the shape."""
-        w = self.gnn_layers[0].gnn.lin.weight.shape[1]
+        d, w = self.gnn_layers[0].gnn.lin.weight.shape
+        if d not in (16, 32, 64, 128):
+            return _lib.GdnHipError(f"bf16 storage needs the LDS tile: embedding width {d} does not fit it (widths "
+                                    "other than 16, 32, 64 and 128 run in fp32 only)")
         if w > 64:
             return _lib.GdnHipError(f"bf16 storage needs the LDS tile: windows of {w} ticks do not fit it (windows "
                                     "longer than 64 ticks run in fp32 only)")

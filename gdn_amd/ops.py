@@ -102,6 +102,16 @@ def terms_pitch(w: int) -> int:
     return p
 
 
+MAX_WIDTH = 256     # largest embedding width d (include/gdn_hip.h "Supported shapes")
+
+
+def check_width(d: int) -> int:
+    """The embedding width d, or GdnHipError when no kernel takes it (1 <= d <= 256).  Host only, no launch."""
+    if not 1 <= d <= MAX_WIDTH:
+        raise _lib.GdnHipError(f"embedding width {d} is not supported (1 <= d <= {MAX_WIDTH}, include/gdn_hip.h)")
+    return d
+
+
 def node_terms(lin_w, att_i, att_j, att_em_i, att_em_j, emb) -> torch.Tensor:
     lin_w = _chk(lin_w.detach(), name="lin.weight")
     d, w = lin_w.shape

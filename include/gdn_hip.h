@@ -19,7 +19,14 @@
  *     window-major order (row = b*n + sensor), the layout of models/GDN.py:130;
  *   - re-entrant across distinct streams.
  *
- * Supported shapes: d in {16, 32, 64, 128}; 1 <= w <= 1024; 1 <= k <= n <= 4096 with k+1 <= 1024.
+ * Supported shapes: 1 <= d <= 256; 1 <= w <= 1024; 1 <= k <= n <= 4096 with k+1 <= 1024.
+ * Embedding widths other than 16, 32, 64 and 128 (ANY-WIDTH form, gdn_any_width.hip) run the staged fp32 entry points
+ *   only, at every n, w, k above: gdn_topk_graph (scalar row reads where d % 4 != 0), gdn_node_terms,
+ *   gdn_project_fwd[_wide] / _series, gdn_attn_aggregate_fwd[_wide], gdn_head_fwd, gdn_head_train_* (all four pairs),
+ *   gdn_attn_aggregate_bwd[_wide], gdn_project_bwd[_partials], gdn_terms_bwd[_acc] and their workspace queries.  Kernels
+ *   run on the padded width (16, 32, 64, 128 or 256) with columns >= d masked; xlin, z and their gradients stay dense
+ *   [BN, d].  gdn_tile_fits, gdn_fused_plan_bytes and gdn_train_supported return 0, the fused / bf16 entry points
+ *   and gdn_train_finish GDN_ERR_UNSUPPORTED; no projection, aggregate or head kernel takes d > 256.
  * Windows longer than 64 ticks (LONG-WINDOW form, w = 65..1024) run the staged entry points only: gdn_node_terms,
  *   gdn_project_fwd[_wide] / _series (fp32 matrix-core projection, exact fp32, no range limit), gdn_project_bwd[_partials],
  *   gdn_terms_bwd[_acc]; everything after xlin depends on n, d, k only and takes the forms below.  gdn_tile_fits,
