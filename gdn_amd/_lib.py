@@ -62,6 +62,7 @@ SIGNATURES = {
     "gdn_mlp_plan_layer": [_p] * 6 + [_c_float] + [_c_int] * 4 + [_p, _p],
     "gdn_mlp_plan_out": [_p, _p] + [_c_int] * 3 + [_p, _p],
     "gdn_mlp_fwd": [_p, _p] + [_c_int] * 4 + [_p, _p],
+    "gdn_head_mlp_fwd": [_p] * 5 + [_c_int] * 5 + [_p, _p],
     "gdn_fused_plan_bytes": [_c_int] * 5,
     "gdn_fused_plan_build": [_p] * 10 + [_c_int] * 5 + [_p, _p],
     "gdn_forward_fused_plan": [_p, _p] + [_c_int] * 6 + [_p, _p, _p],

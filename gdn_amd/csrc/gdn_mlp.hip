@@ -124,10 +124,23 @@ __global__ void mlp_plan_out_kernel(const float* __restrict__ w_out, const float
 }
 
 // ---- the chain -----------------------------------------------------------------------------------------
+// HEAD form (gdn_head_mlp_fwd): the rows come in as z[BN, d] and the eval head (gdn_head_kernel: BN+ReLU, x embedding,
+// BN+ReLU) runs in registers while the first layer's B operand is built — h2 never exists in memory.
+struct MlpHead {
+  const float* emb;      // [n, d]
+  const float* bn1;      // [scale(d) | shift(d)] of GNNLayer.bn
+  const float* bn2;      // [scale(d) | shift(d)] of bn_outlayer_in
+  int n;
+};
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {   // p 16-byte aligned
+  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
 // NT = Np / 32 output tiles per hidden layer; KS0 = k-steps of the first layer.
-template <int NT, int KS0>
+template <int NT, int KS0, bool HEAD>
 __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(const float* __restrict__ h2, const char* __restrict__ plan,
-                                                         MlpGeo g, int rows, float* __restrict__ out) {
+                                                         MlpGeo g, int rows, float* __restrict__ out, MlpHead hd) {
   constexpr int NP = 32 * NT, KSH = 2 * NT;
   constexpr int ROWB = 48;                       // LDS bytes per weight row of one plane (32 data + 16: conflict-free b128)
   constexpr int PLANE = NP * ROWB, SLAB_LDS = 2 * PLANE;
@@ -159,23 +172,64 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(const float* __restrict
     }
   };
   const int a_off = l32 * ROWB + h * 16;         // this lane's weight operand inside a tile of a plane
+  // HEAD: sc1 | sh1 | sc2 | sh2 once per workgroup in LDS.  Column k's constants are ONE address for the 32 lanes of
+  // a half wave: from global memory such a load is served lane by lane, from LDS it is a broadcast.
+  const float* bnl = nullptr;
+  if constexpr (HEAD) {
+    constexpr int D = 16 * KS0;                  // the supported widths are exactly 16 * KS0: every k is a column
+    __shared__ float bn_lds[4 * D];
+    for (int i = tid; i < 4 * D; i += 256) bn_lds[i] = i < 2 * D ? hd.bn1[i] : hd.bn2[i - 2 * D];
+    bnl = bn_lds;
+    __syncthreads();
+  }
 
   for (int blk = blockIdx.x; blk * 128 < rows; blk += gridDim.x) {
     const int m = blk * 128 + wv * 32 + l32;     // this lane's row (as an MFMA column)
     const bool live = m < rows;
     // ---- first layer's B operand: the row's features in natural order
     u32x4 bh[KSH > KS0 ? KSH : KS0], bl[KSH > KS0 ? KSH : KS0];
+    if constexpr (HEAD) {
+      // the head of row m on its way into the operand: the operation sequence of gdn_head_kernel's h2 output
+      // (fma, max, mul, fma, max), so the bits are those gdn_mlp_fwd reads back from memory
+      constexpr int D = 16 * KS0;
+      const float* zr = h2 + (live ? (size_t)m * D : 0);
+      const float* er = hd.emb + (live ? (size_t)(m % hd.n) * D : 0);
+      float zv[KS0][8], ev[KS0][8];
 #pragma unroll
-    for (int s = 0; s < KS0; ++s) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 16 * s + 8 * h + j;
-        const bool ok = live && k < g.d_in;
-        const float t = h2[ok ? (size_t)m * g.d_in + k : 0];
-        v[j] = ok ? t : 0.f;
+      for (int s = 0; s < KS0; ++s) {
+        load8(zr + 16 * s + 8 * h, zv[s]);
+        load8(er + 16 * s + 8 * h, ev[s]);
       }
-      split8_f16(v, bh[s], bl[s]);
+#pragma unroll
+      for (int s = 0; s < KS0; ++s) {
+        const int k0 = 16 * s + 8 * h;
+        float sc1[8], sh1[8], sc2[8], sh2[8], v[8];
+        load8(bnl + k0, sc1);
+        load8(bnl + D + k0, sh1);
+        load8(bnl + 2 * D + k0, sc2);
+        load8(bnl + 3 * D + k0, sh2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float t = fmaxf(fmaf(zv[s][j], sc1[j], sh1[j]), 0.f);
+          t *= ev[s][j];
+          t = fmaxf(fmaf(t, sc2[j], sh2[j]), 0.f);
+          v[j] = live ? t : 0.f;
+        }
+        split8_f16(v, bh[s], bl[s]);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < KS0; ++s) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = 16 * s + 8 * h + j;
+          const bool ok = live && k < g.d_in;
+          const float t = h2[ok ? (size_t)m * g.d_in + k : 0];
+          v[j] = ok ? t : 0.f;
+        }
+        split8_f16(v, bh[s], bl[s]);
+      }
     }
     f32x16 acc[NT];
     for (int layer = 0; layer < g.hidden_layers; ++layer) {
@@ -251,11 +305,12 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(const float* __restrict
   }
 }
 
-template <int NT>
-int mlp_launch_ks0(const float* h2, const char* plan, const MlpGeo& g, int rows, float* out, hipStream_t st) {
+template <int NT, bool HEAD>
+int mlp_launch_ks0(const float* h2, const char* plan, const MlpGeo& g, int rows, float* out, const MlpHead& hd,
+                   hipStream_t st) {
   const int grid = max(1, min((rows + 127) / 128, gdn_cu_count() * 2));
 #define GDN_MLP_CASE(K) \
-  case K: hipLaunchKernelGGL((mlp_fwd_kernel<NT, K>), dim3(grid), dim3(256), 0, st, h2, plan, g, rows, out); break;
+  case K: hipLaunchKernelGGL((mlp_fwd_kernel<NT, K, HEAD>), dim3(grid), dim3(256), 0, st, h2, plan, g, rows, out, hd); break;
   switch (g.ks0) {
     GDN_MLP_CASE(1) GDN_MLP_CASE(2) GDN_MLP_CASE(4) GDN_MLP_CASE(8)
     default: return GDN_ERR_UNSUPPORTED;
@@ -298,22 +353,38 @@ extern "C" int gdn_mlp_plan_out(const float* weight, const float* bias, int d_in
   return gdn_launch_status();
 }
 
+template <bool HEAD>
+int mlp_launch(const float* in, const char* p, const MlpGeo& g, int rows, float* out, const MlpHead& hd, hipStream_t st) {
+  switch (g.np / 32) {
+    case 1: return mlp_launch_ks0<1, HEAD>(in, p, g, rows, out, hd, st);
+    case 2: return mlp_launch_ks0<2, HEAD>(in, p, g, rows, out, hd, st);
+    case 3: return mlp_launch_ks0<3, HEAD>(in, p, g, rows, out, hd, st);
+    case 4: return mlp_launch_ks0<4, HEAD>(in, p, g, rows, out, hd, st);
+    case 5: return mlp_launch_ks0<5, HEAD>(in, p, g, rows, out, hd, st);
+    case 6: return mlp_launch_ks0<6, HEAD>(in, p, g, rows, out, hd, st);
+    case 7: return mlp_launch_ks0<7, HEAD>(in, p, g, rows, out, hd, st);
+    case 8: return mlp_launch_ks0<8, HEAD>(in, p, g, rows, out, hd, st);
+  }
+  return GDN_ERR_UNSUPPORTED;
+}
+
 extern "C" int gdn_mlp_fwd(const float* h2, const void* plan, int rows, int d_in, int hidden, int layers,
                            float* out, void* stream) {
   if (!h2 || !plan || !out || rows <= 0) return GDN_ERR_ARG;
   if (!mlp_supported(d_in, hidden, layers)) return GDN_ERR_UNSUPPORTED;
-  const MlpGeo g = mlp_geo(d_in, hidden, layers);
-  const char* p = reinterpret_cast<const char*>(plan);
-  hipStream_t st = (hipStream_t)stream;
-  switch (g.np / 32) {
-    case 1: return mlp_launch_ks0<1>(h2, p, g, rows, out, st);
-    case 2: return mlp_launch_ks0<2>(h2, p, g, rows, out, st);
-    case 3: return mlp_launch_ks0<3>(h2, p, g, rows, out, st);
-    case 4: return mlp_launch_ks0<4>(h2, p, g, rows, out, st);
-    case 5: return mlp_launch_ks0<5>(h2, p, g, rows, out, st);
-    case 6: return mlp_launch_ks0<6>(h2, p, g, rows, out, st);
-    case 7: return mlp_launch_ks0<7>(h2, p, g, rows, out, st);
-    case 8: return mlp_launch_ks0<8>(h2, p, g, rows, out, st);
-  }
-  return GDN_ERR_UNSUPPORTED;
+  return mlp_launch<false>(h2, reinterpret_cast<const char*>(plan), mlp_geo(d_in, hidden, layers), rows, out, MlpHead{},
+                           (hipStream_t)stream);
+}
+
+extern "C" int gdn_head_mlp_fwd(const float* z, const float* emb, const float* bn1_affine, const float* bn2_affine,
+                                const void* plan, int batch, int n, int d, int hidden, int layers, float* out,
+                                void* stream) {
+  if (!z || !emb || !bn1_affine || !bn2_affine || !plan || !out || batch <= 0 || n <= 0) return GDN_ERR_ARG;
+  if (!mlp_supported(d, hidden, layers)) return GDN_ERR_UNSUPPORTED;
+  if ((long long)batch * n > 0x7fffffffLL) return GDN_ERR_UNSUPPORTED;
+  // the operand build reads z, emb and the affine tables as 16-byte vectors (rows are d * 4 >= 64 bytes)
+  if ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(emb)) & 15) return GDN_ERR_ARG;
+  const MlpHead hd = {emb, bn1_affine, bn2_affine, n};
+  return mlp_launch<true>(z, reinterpret_cast<const char*>(plan), mlp_geo(d, hidden, layers), batch * n, out, hd,
+                          (hipStream_t)stream);
 }

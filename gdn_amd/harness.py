@@ -485,7 +485,7 @@ class SeriesEvaluator:
         # range of the matrix-core kernels the whole evaluator runs on the fp32 row-gather kernels
         src0 = series if series is not None else x_all
         self.wide = (model.operand_range == "wide" and src0.dtype != torch.bfloat16) or (
-            model.operand_range == "auto" and model.out_layer_num == 1 and model.input_exceeds_limit(src0))
+            model.operand_range == "auto" and model.input_exceeds_limit(src0))
         self.logical_batch, self.coalesce = batch, max(1, coalesce)
         self.t, self.n = y_all.shape
         dev = y_all.device
@@ -518,6 +518,8 @@ class SeriesEvaluator:
         if m.out_layer_num == 1 and not m.training and not self.wide:
             src = self.series if self.series is not None else self.x
             m._plan(m._constants(), src.dtype == torch.bfloat16)
+        elif m.out_layer_num > 1 and not m.training:     # the OutLayer MLP's plan, for the same reason
+            m._mlp_tail(m._constants())
         spans = [(s, min(self.t, s + self.batch)) for s in range(0, self.t, self.batch)]
         # scoring hand-off: the forward's epilogue writes the float64 radix keys |pred - y| of its windows into
         # their columns of the [n, t] key block at the head of the scoring workspace (no gdn_score_keys launch)
@@ -575,7 +577,7 @@ class SeriesEvaluator:
                 src0 = self.series if self.series is not None else self.x
                 m = self.model
                 self.wide = (m.operand_range == "wide" and src0.dtype != torch.bfloat16) or (
-                    m.operand_range == "auto" and m.out_layer_num == 1 and m.input_exceeds_limit(src0))
+                    m.operand_range == "auto" and m.input_exceeds_limit(src0))
             self._graph_key = key
 
     def _capture(self, fn):

@@ -170,16 +170,31 @@ class Main:
         # test.py's loop with the windows built in the kernel from the resident series (stride 1)
         w = self.train_config["slide_win"]
         n_test = self.test_series.shape[1] - w
-        pred = best_model.forward_series(self.test_series, 0, n_test,
-                                         wide=best_model.input_exceeds_limit(self.test_series)) \
-            if best_model.out_layer_num == 1 else \
-            torch.cat([best_model(x, None) for x, _y, _l, _e in IndexLoader(
-                self.test_dataset, torch.arange(n_test), self.train_config["batch"], False, None)])
+        if best_model.out_layer_num == 1:
+            pred = best_model.forward_series(self.test_series, 0, n_test,
+                                             wide=best_model.input_exceeds_limit(self.test_series))
+        else:
+            pred = self.predict_mlp_head(best_model, n_test)
         gt = self.test_series[:, w:].t().contiguous()
         labels = self.test_labels[w:]
         self.test_result = [pred, gt, labels.view(-1, 1).expand(-1, pred.shape[1])]
         _, self.val_result = harness.test(best_model, self.val_dataloader, self.device, as_tensors=True)
         return self.get_score(self.test_result, self.val_result)
+
+    def predict_mlp_head(self, model, n_test: int, span: int = 8192):
+        """Test predictions of an out_layer_num > 1 model: forward_series on the resident series, `span` windows per
+        call (the staged route keeps xlin and z of one call in HBM).  An OutLayer forward_series refuses (hidden
+        layers wider than 512 or of unequal widths) goes through the reference's loop: minibatches of materialised
+        windows through model(x)."""
+        if model.mlp_fast_path_supported():
+            pred = torch.empty((n_test, self.test_series.shape[0]), dtype=torch.float32, device=self.device)
+            wide = model.input_exceeds_limit(self.test_series)
+            for s in range(0, n_test, span):
+                e = min(n_test, s + span)
+                model.forward_series(self.test_series, s, e - s, out=pred[s:e], wide=wide)
+            return pred
+        return torch.cat([model(x, None) for x, _y, _l, _e in IndexLoader(
+            self.test_dataset, torch.arange(n_test), self.train_config["batch"], False, None)])
 
     def get_score(self, test_result, val_result):
         """main.py:150-174."""

@@ -233,7 +233,7 @@ class OutLayer(nn.Module):
 
 class _EvalConstants:
     __slots__ = ("key", "graph", "terms", "bn1", "bn2", "fused_args", "plans", "mlp", "stream", "ready", "guards",
-                 "limits", "large", "bufs")
+                 "limits", "large", "bufs", "tail")
 
 
 class GDN(nn.Module):
@@ -329,6 +329,7 @@ class GDN(nn.Module):
         # gather-aggregate, head — with xlin and z in HBM, in buffers kept here per (stream, batch)
         c.large = not _lib.load().gdn_tile_fits(emb.shape[0], w, d, c.graph.k)
         c.bufs = {}
+        c.tail = None                # out_layer_num > 1: the staged eval route's MLP tail, "plan" / "wide" (_mlp_tail)
         if not self.training:
             c.bn1 = ops.bn_fold(self.gnn_layers[0].bn)
             c.bn2 = ops.bn_fold(self.bn_outlayer_in)
@@ -413,9 +414,11 @@ class GDN(nn.Module):
                       out.data_ptr(), st)
         return out
 
-    def _large_buffers(self, c, batch: int):
-        """(xlin, s_i, s_j, z) of the staged eval forward beyond the tile, one set per (stream, batch): allocated
-        on first use (a warm-up before any capture), reused by every later launch on that stream."""
+    def _large_buffers(self, c, batch: int, tail=None):
+        """(xlin, s_i, s_j, z) of the staged eval forward, one set per (stream, batch): allocated on first use (a
+        warm-up before any capture), reused by every later launch on that stream.  With the "wide" MLP tail
+        (_mlp_tail) three more: h2 [rows, d], the workspace of gdn_mlp_eval_fwd, and d + 1 zeros standing in for the
+        Linear(d -> 1) the head kernel also evaluates."""
         key = (torch.cuda.current_stream().cuda_stream, batch)
         bufs = c.bufs.get(key)
         if bufs is None:
@@ -426,8 +429,38 @@ class GDN(nn.Module):
                     torch.empty((rows,), dtype=torch.float32, device=dev),
                     torch.empty((rows,), dtype=torch.float32, device=dev),
                     torch.empty((rows, d), dtype=torch.float32, device=dev))
+            if tail == "wide":
+                bufs += (torch.empty((rows, d), dtype=torch.float32, device=dev),
+                         ops.mlp_eval_wide_workspace(self.out_layer, rows, d, dev),
+                         torch.zeros((d + 1,), dtype=torch.float32, device=dev))
             c.bufs[key] = bufs
         return bufs
+
+    def _mlp_tail(self, c, refuse: bool = True):
+        """Which kernels end the staged eval route of an out_layer_num > 1 model: "plan" = gdn_head_mlp_fwd on the
+        OutLayer's plan (built here when missing, on the constants' stream like `_plan`), "wide" = gdn_head_fwd ->
+        h2 -> gdn_mlp_eval_fwd.  An OutLayer neither takes is refused here, before any buffer or launch
+        (`refuse=False`: None instead)."""
+        if c.tail is None:
+            d = self.embedding.weight.shape[1]
+            if c.mlp is False:
+                with torch.cuda.stream(c.stream) if c.stream is not None else contextlib.nullcontext():
+                    c.mlp = ops.mlp_plan(self.out_layer, d)
+                    if c.mlp is not None and c.ready is not None:
+                        c.ready = torch.cuda.Event()
+                        c.ready.record(c.stream)
+            if c.mlp is not None:
+                c.tail = "plan"
+            elif ops.mlp_eval_wide_supported(self.out_layer, d):
+                c.tail = "wide"
+            elif refuse:
+                widths = [m.out_features for m in self.out_layer.mlp if isinstance(m, nn.Linear)][:-1]
+                raise _lib.GdnHipError(
+                    "forward_into / forward_series have no kernel for this OutLayer (hidden width "
+                    f"{' / '.join(str(h) for h in dict.fromkeys(widths))}, input width {d}): gdn_head_mlp_fwd takes hidden "
+                    "<= 256 at widths 16, 32, 64 and 128, gdn_mlp_eval_fwd equal hidden widths up to 512 at a width that "
+                    "is a multiple of 4, both with tracked running statistics; GDN.forward evaluates this model")
+        return c.tail
 
     def _bf16_refusal(self) -> _lib.GdnHipError:
         """Why bf16 windows are refused where the tile form does not take the shape."""
@@ -455,24 +488,26 @@ class GDN(nn.Module):
         return self.input_exceeds_limit(src)
 
     def _forward_large(self, x, c, out, batch: int, series=None, first: int = 0, wide: bool = False):
-        """Eval forward (out_layer_num == 1) of a shape the LDS tile does not take (a graph beyond it, or windows
-        longer than 64 ticks): gdn_project_fwd (or its series form) -> gdn_attn_aggregate_fwd -> gdn_head_fwd with
-        xlin / z in HBM.  Beyond the tile every kernel is fp32 (no range guard needed); `wide` selects the fp32
-        aggregate where the matrix-core one would be picked (see _large_guard_wide).  `series` [n, T]: window b =
-        series[:, first + b : first + b + w]."""
+        """Staged eval forward: gdn_project_fwd (or its series form) -> gdn_attn_aggregate_fwd -> head, with xlin / z
+        in HBM, in buffers kept in the constants cache.  out_layer_num == 1: the shapes the LDS tile does not take (a
+        graph beyond it, windows longer than 64 ticks, other widths), ending in gdn_head_fwd.  out_layer_num > 1:
+        every shape, ending in the MLP tail of `_mlp_tail` — gdn_head_mlp_fwd (no h2), or gdn_head_fwd -> h2 ->
+        gdn_mlp_eval_fwd.  Beyond the tile every kernel is fp32 (no range guard needed); `wide` selects the fp32
+        projection / aggregate where the matrix-core ones would be picked (see _large_guard_wide).  `series`
+        [n, T]: window b = series[:, first + b : first + b + w] (the fp32 streaming projection at every shape)."""
         src = x if series is None else series
         if src.dtype == torch.bfloat16:
             raise self._bf16_refusal()
         gnn = self.gnn_layers[0].gnn
-        lin = self.out_layer.mlp[0]
         emb = self.embedding.weight
         n, d = emb.shape
         w = gnn.lin.weight.shape[1]
+        tail = None if self.out_layer_num == 1 else self._mlp_tail(c)       # (refuses before anything is launched)
         cur = self._wait_ready(c)
         st = cur.cuda_stream
-        xlin, s_i, s_j, z = self._large_buffers(c, batch)
+        xlin, s_i, s_j, z, *more = self._large_buffers(c, batch, tail)
         if series is None:
-            _lib.call("gdn_project_fwd", x.data_ptr(), gnn.lin.weight.data_ptr(), c.terms.data_ptr(), batch, n, w, d,
+            _lib.call("gdn_project_fwd_wide" if wide and not c.large else "gdn_project_fwd", x.data_ptr(), gnn.lin.weight.data_ptr(), c.terms.data_ptr(), batch, n, w, d,
                       xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
         else:
             _lib.call("gdn_project_fwd_series", series.data_ptr(), series.shape[1], first, gnn.lin.weight.data_ptr(),
@@ -480,9 +515,50 @@ class GDN(nn.Module):
         _lib.call("gdn_attn_aggregate_fwd_wide" if wide else "gdn_attn_aggregate_fwd", xlin.data_ptr(), s_i.data_ptr(),
                   s_j.data_ptr(), c.graph.nbr.data_ptr(), c.graph.deg.data_ptr(), gnn.bias.data_ptr(), batch, n, d,
                   c.graph.k, z.data_ptr(), None, st)
-        _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
-                  lin.weight.data_ptr(), lin.bias.data_ptr(), batch, n, d, out.data_ptr(), None, st)
+        if tail is None:
+            lin = self.out_layer.mlp[0]
+            _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
+                      lin.weight.data_ptr(), lin.bias.data_ptr(), batch, n, d, out.data_ptr(), None, st)
+        elif tail == "plan":
+            plan, hidden, layers = c.mlp
+            _lib.call("gdn_head_mlp_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
+                      plan.data_ptr(), batch, n, d, hidden, layers, out.data_ptr(), st)
+        else:
+            # (the head kernel's own Linear(d -> 1) runs on zeros into `out`, which the MLP then overwrites)
+            h2, ws, zeros = more
+            _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(), zeros.data_ptr(),
+                      zeros.data_ptr() + 4 * d, batch, n, d, out.data_ptr(), h2.data_ptr(), st)
+            ops.mlp_eval_wide(h2, self.out_layer, out=out.view(-1), ws=ws)
         return out
+
+    def mlp_fast_path_supported(self) -> bool:
+        """True when forward_into / forward_series take this out_layer_num > 1 model in eval mode (an OutLayer with a
+        plan, or one gdn_mlp_eval_fwd takes); False: only GDN.forward evaluates it."""
+        if self.training or self.out_layer_num == 1:
+            return False
+        return self._mlp_tail(self._constants(), refuse=False) is not None
+
+    def _forward_mlp(self, x, out, batch: int, keys, series=None, first: int = 0, wide: bool = False):
+        """forward_into / forward_series of an out_layer_num > 1 model: the staged route at every shape."""
+        c = self._constants()
+        self.learned_graph = c.graph.topk
+        src = x if series is None else series
+        if not src.is_cuda:
+            raise _lib.GdnHipError(f"input is on {src.device}: gdn_amd needs a HIP device (no CPU fallback)")
+        if keys is not None:
+            raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
+        if src.dtype == torch.bfloat16:
+            raise _lib.GdnHipError("bf16 storage is not available with an MLP head (out_layer_num > 1): the staged bf16 "
+                                   "kernels end at the matrix-core shapes and the OutLayer MLP reads fp32")
+        n, w = self.embedding.weight.shape[0], self.gnn_layers[0].gnn.lin.weight.shape[1]
+        if series is None:
+            if x.dim() != 3 or x.shape[1] != n or x.shape[2] != w:
+                raise ValueError(f"expected data of shape [B, {n}, {w}], got {tuple(x.shape)}")
+        elif series.dim() != 2 or series.shape[0] != n:
+            raise ValueError(f"expected a series of shape [{n}, T], got {tuple(series.shape)}")
+        if out is None:
+            out = torch.empty((batch, n), dtype=torch.float32, device=src.device)
+        return self._forward_large(x, c, out, batch, series=series, first=first, wide=wide)
 
     def operand_limit(self, bf16: bool = False) -> float:
         """Largest |x| the eval fast path's matrix-core kernel represents with the current parameters (inf: no
@@ -646,9 +722,15 @@ class GDN(nn.Module):
         """Eval fast path writing into a caller-owned [B, N] slice (no allocation, HIP-graph
         capturable once `_constants()` is warm): used by harness.SeriesEvaluator.  `keys`: see _launch_fused.
         The caller vouches for the range of `data` (`input_exceeds_limit`, asked once per resident tensor):
-        `wide=True` runs the fp32 row-gather kernel, False the matrix-core one WITHOUT the range guard."""
-        if self.training or self.out_layer_num != 1:
-            raise RuntimeError("forward_into is the eval / out_layer_num == 1 fast path")
+        `wide=True` runs the fp32 row-gather kernel, False the matrix-core one WITHOUT the range guard.
+        out_layer_num > 1 takes the staged route (project -> aggregate -> MLP tail, `_forward_large`) on buffers
+        cached per (stream, batch): fp32 windows only, no `keys`."""
+        if self.training:
+            raise RuntimeError("forward_into is the eval fast path (model.eval() first)")
+        if self.out_layer_num != 1:
+            if data.dtype not in (torch.float32, torch.bfloat16):
+                data = data.float()
+            return self._forward_mlp(data.contiguous(), out, data.shape[0], keys, wide=wide)
         c = self._constants()
         self.learned_graph = c.graph.topk
         if data.dtype not in (torch.float32, torch.bfloat16):
@@ -666,9 +748,13 @@ class GDN(nn.Module):
     def forward_series(self, series, first: int, batch: int, out=None, keys=None, wide: bool = False):
         """Eval forward of `batch` consecutive stride-1 windows taken directly from the raw series
         [node_num, T] (the layout `TimeDataset` slices, datasets/TimeDataset.py:42-49): window b is
-        series[:, first+b : first+b+W] and predicts column first+b+W.  No [T, N, W] tensor exists."""
-        if self.training or self.out_layer_num != 1:
-            raise RuntimeError("forward_series is the eval / out_layer_num == 1 fast path")
+        series[:, first+b : first+b+W] and predicts column first+b+W.  No [T, N, W] tensor exists.
+        out_layer_num > 1: the staged route, as forward_into."""
+        if self.training:
+            raise RuntimeError("forward_series is the eval fast path (model.eval() first)")
+        if self.out_layer_num != 1:
+            series = series if series.is_contiguous() else series.contiguous()
+            return self._forward_mlp(None, out, batch, keys, series=series, first=first, wide=wide)
         c = self._constants()
         gnn = self.gnn_layers[0].gnn
         lin = self.out_layer.mlp[0]

@@ -227,6 +227,19 @@ def mlp_fwd(h2, plan_info, out: torch.Tensor | None = None):
     return out
 
 
+def head_mlp_fwd(z, emb, bn1_affine, bn2_affine, plan_info, batch: int, out: torch.Tensor | None = None):
+    """z[batch * n, d] -> out[batch * n]: the eval head (models/GDN.py:77-79,175-180) and the OutLayer MLP
+    (:45-56) as one launch (gdn_head_mlp_fwd): the bits of mlp_fwd(head_fwd(z, ..., want_h2=True)[1]) without h2."""
+    plan, hidden, layers = plan_info
+    z = _chk(z, name="z")
+    rows, d = z.shape
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.float32, device=z.device)
+    _lib.call("gdn_head_mlp_fwd", _ptr(z), _ptr(_chk(emb.detach())), _ptr(bn1_affine), _ptr(bn2_affine), _ptr(plan),
+              batch, rows // batch, d, hidden, layers, _ptr(out), _stream())
+    return out
+
+
 def _bn_running(bn):
     """(momentum, running_mean, running_var, num_batches_tracked) pointers for the train-mode head."""
     if not bn.track_running_stats or bn.running_mean is None:
@@ -380,14 +393,23 @@ def mlp_eval_wide_supported(out_layer, d_in: int) -> bool:
     return _lib.load().gdn_mlp_eval_workspace_bytes(2, d_in, h, len(hidden) + 1) > 0
 
 
-def mlp_eval_wide(h2, out_layer, out: torch.Tensor | None = None):
+def mlp_eval_wide_workspace(out_layer, rows: int, d_in: int, device) -> torch.Tensor:
+    """Scratch of mlp_eval_wide for `rows` rows (gdn_mlp_eval_workspace_bytes): callers that run the same shape
+    again and again keep it and pass it as `ws=`."""
+    hidden, _last = mlp_train_layers(out_layer)
+    nbytes = _lib.load().gdn_mlp_eval_workspace_bytes(rows, d_in, hidden[0][0].out_features, len(hidden) + 1)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def mlp_eval_wide(h2, out_layer, out: torch.Tensor | None = None, ws: torch.Tensor | None = None):
     """h2[rows, d] -> out[rows]: OutLayer.forward (models/GDN.py:45-56) in eval mode on the fp32 matrix-core GEMM
-    kernels (gdn_mlp_eval_fwd)."""
+    kernels (gdn_mlp_eval_fwd).  `ws`: a workspace from mlp_eval_wide_workspace (allocated per call when None)."""
     h2 = _chk(h2, name="h2")
     rows, d_in = h2.shape
     hidden, last = mlp_train_layers(out_layer)
     h, layers = hidden[0][0].out_features, len(hidden) + 1
-    ws = torch.empty((_lib.load().gdn_mlp_eval_workspace_bytes(rows, d_in, h, layers),), dtype=torch.uint8, device=h2.device)
+    if ws is None:
+        ws = mlp_eval_wide_workspace(out_layer, rows, d_in, h2.device)
     if out is None:
         out = torch.empty((rows,), dtype=torch.float32, device=h2.device)
     params, running, eps = [], [], []

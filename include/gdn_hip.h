@@ -174,6 +174,17 @@ int gdn_mlp_plan_out(const float* weight, const float* bias, int d_in, int hidde
 int gdn_mlp_fwd(const float* h2, const void* plan, int rows, int d_in, int hidden, int layers,
                 float* out, void* stream);
 
+/* gdn_head_mlp_fwd: gdn_head_fwd (the h2 output) and gdn_mlp_fwd as ONE launch: z[BN, d] -> out[BN], BN = batch * n.
+ * The head (models/GDN.py:77-79,175-180: BN+ReLU, x embedding row BN % n, BN+ReLU) is computed in registers while
+ * the chain's first matrix operand is built, by the operation sequence gdn_head_fwd uses, so h2 never exists in
+ * memory and the result equals gdn_mlp_fwd(gdn_head_fwd(z).h2) bit for bit.  The two affine tables (gdn_bn_fold)
+ * are staged in LDS once per workgroup; the embedding rows are read per lane.  Same plan and same supported set
+ * as gdn_mlp_fwd (gdn_mlp_plan_bytes(d, hidden, layers) != 0), anything else GDN_ERR_UNSUPPORTED; z and emb
+ * 16-byte aligned (GDN_ERR_ARG otherwise, like a null pointer or a non-positive size), all before any launch.   */
+int gdn_head_mlp_fwd(const float* z, const float* emb, const float* bn1_affine, const float* bn2_affine,
+                     const void* plan, int batch, int n, int d, int hidden, int layers,
+                     float* out, void* stream);
+
 /* ---- train-mode head (out_layer_num == 1) -------------------------------------------
  * gdn_head_train_fwd: the same chain as gdn_head_fwd under model.train(): both BatchNorms
  * normalise by the statistics of this batch (models/GDN.py:77-79 GNNLayer.bn, :178-180
