@@ -30,6 +30,17 @@
 //
 // Two barriers per window; the next window's x values are loaded into registers before P and stored
 // to LDS after E.
+//
+// The FUSED kernel with fp32 storage runs P and M in the other order (DCfg::XAGG).  GraphLayer's lin has no
+// bias, so  z_i = sum_j alpha_ij (lin' x_j) + C = lin' (sum_j alpha_ij x_j) + C:  it aggregates the raw window
+// (16 WK columns: ONE 32-column block instead of d/32) and projects the 32 aggregated rows of each wave afterwards.
+//   X  the staging thread of (k-step s, lane half h, column w) holds the 8 sources of that operand slot, splits
+//      them once and writes them as a ready X^T fragment (besides the row-major tile the scalar tile reads);
+//   P0 only the scalar tile (s_i, s_j) is left of P;
+//   M  Zx^T[w, target] += X^T . A^T, one column block; the accumulator (target on the lane, w in the registers)
+//      IS the B operand of the projection in k order "element j of half h = w 16wk + 8(j>>2) + 4h + (j&3)";
+//   P1 out^T[c, target] = lin' . Zx + C (C-in from the table block), the layout E consumes.
+// With bf16 storage the projected tile must be rounded to bf16 as the staged path stores it: that order stays.
 #include "gdn_common.hpp"
 
 #include <stdlib.h>
@@ -53,6 +64,11 @@ enum { FMT_F16 = 0, FMT_BF16 = 1 };
 // unscaled by 2^-15 inside the epilogue constants.  |xlin'| must stay below 65504 / 8.
 #define GDN_F16_ALPHA_SCALE 4096.0f
 #define GDN_F16_X_SCALE 8.0f
+// The fused fp32-storage kernel aggregates the RAW window and projects afterwards (see its head): the x operand
+// of the aggregation carries 2^3, the aggregated row is brought from 2^15 back to 2^3 (x 2^-12, exact) before
+// it is split for the projection, whose lin' operand carries GDN_F16_X_SCALE: the result is unscaled by 2^-6.
+#define GDN_F16_XT_SCALE 8.0f
+#define GDN_F16_Z_SCALE 8.0f
 
 // ---- 16-bit term splitting ------------------------------------------------------------------------
 template <int FMT>
@@ -155,14 +171,16 @@ struct DCfg {
                                                        // lo term of alpha take turns in it (scatter hi, its
                                                        // products, scatter lo over the same positions, its
                                                        // product), which halves the image: 2 workgroups per CU
-  static constexpr int NPX = FMT == FMT_F16 ? 2 : 1;   // terms of the projected tile
+  static constexpr bool XAGG = FMT == FMT_F16;         // aggregate the raw window, project afterwards (file head)
+  static constexpr int MCB = XAGG ? 1 : DC;            // 32-column blocks of the aggregation product
+  static constexpr int NPX = FMT == FMT_F16 ? 2 : 1;   // terms of the aggregated tile (XAGG: of x^T)
   static constexpr int NTL = FMT == FMT_F16 ? 2 : 3;   // terms of lin.weight / a_i / a_j
   static constexpr int NTXIN = FMT == FMT_F16 ? 2 : 1; // terms of the x values (bf16 storage: exact)
   static constexpr int XP = 16 * WK + 4;               // x tile pitch in floats (odd number of 16-B slots)
   static constexpr int XU = 8 * WK;                    // x values per thread per window
   static constexpr int OFF_A = 0;
-  static constexpr int OFF_XF = NT * AWAVE;            // [KS][DC][NPX][64 lanes] x 16 B
-  static constexpr int OFF_XS = OFF_XF + KS * DC * NPX * 1024;
+  static constexpr int OFF_XF = NT * AWAVE;            // [KS][MCB][NPX][64 lanes] x 16 B
+  static constexpr int OFF_XS = OFF_XF + KS * MCB * NPX * 1024;
   static constexpr int OFF_SI = OFF_XS + ROWS * XP * 4;
   static constexpr int OFF_SJ = OFF_SI + ROWS * 4;
   static constexpr int OFF_EC = OFF_SJ + ROWS * 4;     // epilogue column constants: 4 tables of 32 DC floats
@@ -283,10 +301,9 @@ struct LaneConsts {
   using C = DCfg<NT, DC, WK, SL, FMT>;
   int sjoff[SL], scoff[SL];
   u32x4 bl[DC][WK][C::NTL], bs[WK][C::NTL];
-  float cin[DC];
   float e2[DC][16];
   float out_b;
-  static constexpr int WORDS = 2 * SL + 4 * (DC * WK * C::NTL + WK * C::NTL) + DC + 16 * DC + 1;
+  static constexpr int WORDS = 2 * SL + 4 * (DC * WK * C::NTL + WK * C::NTL) + 16 * DC + 1;
   static constexpr int TABLE_WORDS = 4 * 32 * DC + 3 * C::ROWS;     // [ec | cs] as they sit in LDS
   static constexpr size_t LIMIT_WORD = (size_t)TABLE_WORDS + (size_t)WORDS * C::THREADS;   // the x limit (float)
   static constexpr size_t PLAN_BYTES = (LIMIT_WORD + 1) * 4;
@@ -322,8 +339,6 @@ struct LaneConsts {
           bs[wk][t][e] = tmp;
         }
 #pragma unroll
-    for (int cb = 0; cb < DC; ++cb) f(i++, reinterpret_cast<unsigned&>(cin[cb]));
-#pragma unroll
     for (int cb = 0; cb < DC; ++cb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) f(i++, reinterpret_cast<unsigned&>(e2[cb][r]));
@@ -351,18 +366,19 @@ __device__ __forceinline__ void compute_lane_consts(const DArgs& a, LaneConsts<N
       k.scoff[q] = C::OFF_A + wv * C::AWAVE + (lane >> 1) * C::AROW + pos_of_source(j) * 2;
     }
   }
-  // P: B operand = lin'^T (k on the registers, output column on the lane), split once
+  // P: B operand = lin'^T (k on the registers, output column on the lane), split once.  XAGG: the same registers
+  // are the A operand of P1, whose k order is the row map of the aggregation accumulator (slot 8h + j = window
+  // column 16wk + 8(j>>2) + 4h + (j&3)); C-in is the sh1' row of the table block
 #pragma unroll
   for (int cb = 0; cb < DC; ++cb) {
     const int c = cb * 32 + l32;
     const float sc = FOLD ? a.bn1[c] * GDN_F16_X_SCALE : 1.f;
-    k.cin[cb] = FOLD ? fmaf(a.gnn_bias[c], a.bn1[c], a.bn1[d + c]) * GDN_F16_X_SCALE : 0.f;
 #pragma unroll
     for (int wk = 0; wk < WK; ++wk) {
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int kk = wk * 16 + 8 * h + j;
+        const int kk = wk * 16 + (C::XAGG ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j);
         v[j] = ld_or(a.lin_w, c * w + kk, kk < w) * sc;
       }
       split8<FMT, C::NTL>(v, k.bl[cb][wk]);
@@ -386,16 +402,17 @@ __device__ __forceinline__ void compute_lane_consts(const DArgs& a, LaneConsts<N
     for (int r = 0; r < 16; ++r) {
       const int c = cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
       k.e2[cb][r] = ld_or(a.emb, tgt * d + c, tgt < n) * a.bn2[c] *
-                    (FMT == FMT_F16 ? 1.f / (GDN_F16_ALPHA_SCALE * GDN_F16_X_SCALE) : 1.f);
+                    (FMT == FMT_F16 ? 1.f / (GDN_F16_Z_SCALE * GDN_F16_X_SCALE) : 1.f);
     }
   k.out_b = a.out_b[0];
 }
 
 // the two LDS tables, written to `dst` (LDS or the plan): epilogue column constants
-// [sh2 | out_w | sc1 | sh1'] (the last two are used without the BatchNorm fold), then the C-in of the
+// [sh2 | out_w | sc1 | sh1'] (sc1 is used without the BatchNorm fold; sh1' = bias * sc1 + sh1 is the epilogue's
+// shift there, and with the fold (fp32 storage) the C-in of P1, in the scale of its accumulator), then the C-in of the
 // scalar tile [c_i | c_j | zeros][ROWS] in the log2 domain (row n, the list sentinel, gets s_j = -inf;
 // the lanes of the 30 unused columns read the zero row)
-template <int NT, int DC>
+template <int NT, int DC, int FMT>
 __device__ __forceinline__ void compute_tables(const DArgs& a, float* dst) {
   constexpr int ROWS = 32 * NT, THREADS = 64 * NT, d = 32 * DC;
   const int tid = threadIdx.x, n = a.n;
@@ -403,7 +420,8 @@ __device__ __forceinline__ void compute_tables(const DArgs& a, float* dst) {
     dst[c] = a.bn2[d + c];
     dst[d + c] = a.out_w[c];
     dst[2 * d + c] = a.bn1[c];
-    dst[3 * d + c] = fmaf(a.gnn_bias[c], a.bn1[c], a.bn1[d + c]);
+    dst[3 * d + c] = fmaf(a.gnn_bias[c], a.bn1[c], a.bn1[d + c]) *
+                     (FMT == FMT_F16 ? GDN_F16_Z_SCALE * GDN_F16_X_SCALE : 1.f);
   }
   float* ct = dst + 4 * d;
   for (int t = tid; t < 3 * ROWS; t += THREADS) {
@@ -414,33 +432,41 @@ __device__ __forceinline__ void compute_tables(const DArgs& a, float* dst) {
   }
 }
 
-// Largest |x| the fp32-storage kernel represents (the "x limit" of a plan).  x itself becomes two f16 terms
-// (|x| < 65504), and so does the BatchNorm-folded projected tile times 2^3: |tile| <= max|x| * L1 + C with
-// L1 = max_c sum_w |lin'[c, w]| and C = max_c |C-in[c]| (both carry the 2^3).  limit = min(60000, (60000 - C) / L1);
-// 0 when C alone is out of range (every launch is then flagged).  bf16 storage: x is one exact bf16 term with
-// fp32's exponent range, the tile is rounded to bf16: no limit (+inf).
+// Largest |x| the fp32-storage kernel represents (the "x limit" of a plan).  With the aggregation in front of the
+// projection (DCfg::XAGG) the 16-bit operand chain of a window is
+//   x             two f16 terms, unscaled (scalar tile) and times 2^3 (X^T fragments):   8 |x| < 65504
+//   alpha * 2^12  two f16 terms, <= 4096 (1 + 2^-11)                                     whatever x
+//   Zx * 2^3      the aggregated row sum_j alpha_ij x_j, two f16 terms: a convex combination of the window's
+//                 values up to the rounding of alpha (sum_j alpha_hi <= 1 + 2^-11):      8 |Zx| <= 8 max|x| (1 + 2^-10)
+//   lin' * 2^3    two f16 terms, parameters only:                                        8 max|lin'[c, w]| < 65504
+// and everything behind them (products, C-in, the projected row) is fp32.  So limit = 60000 / 2^3 = 7500 (60000:
+// 9 % of head room for the roundings above), or 0 when a lin' entry (or C-in) is out of range or not finite: every
+// launch is then flagged.  The projected tile itself no longer exists in 16 bits, so neither its L1 bound
+// max|x| sum_w |lin'[c, w]| nor C-in enter.  bf16 storage: x is one exact bf16 term with fp32's exponent range,
+// the tile is rounded to bf16: no limit (+inf).
 template <int NT, int DC, int FMT>
 __device__ __forceinline__ float compute_xlimit(const DArgs& a) {
   if constexpr (FMT != FMT_F16) return INFINITY;
-  __shared__ unsigned m_l1, m_c;
+  __shared__ unsigned m_lin, m_c;
   const int tid = threadIdx.x, d = 32 * DC;
-  if (tid == 0) { m_l1 = 0u; m_c = 0u; }
+  if (tid == 0) { m_lin = 0u; m_c = 0u; }
   __syncthreads();
   for (int c = tid; c < d; c += 64 * NT) {
     const float sc = a.bn1[c] * GDN_F16_X_SCALE;
-    float l1 = 0.f;
-    for (int q = 0; q < a.w; ++q) l1 += fabsf(a.lin_w[c * a.w + q] * sc);
-    const float cin = fabsf(fmaf(a.gnn_bias[c], a.bn1[c], a.bn1[d + c]) * GDN_F16_X_SCALE);
+    float lmax = 0.f;
+    for (int q = 0; q < a.w; ++q) {
+      const float v = fabsf(a.lin_w[c * a.w + q] * sc);
+      lmax = v > lmax || v != v ? v : lmax;
+    }
+    const float cin = fabsf(fmaf(a.gnn_bias[c], a.bn1[c], a.bn1[d + c]));
     // non-negative floats order like their bits; NaN / inf parameters compare as huge: limit 0
-    atomicMax(&m_l1, __float_as_uint(l1));
+    atomicMax(&m_lin, __float_as_uint(lmax));
     atomicMax(&m_c, __float_as_uint(cin));
   }
   __syncthreads();
-  const float l1 = __uint_as_float(m_l1), cmax = __uint_as_float(m_c);
-  float lim = 60000.f;
-  if (!(cmax < 60000.f) || !(l1 < 3.0e38f)) lim = 0.f;
-  else if (l1 > 0.f) lim = fminf(lim, (60000.f - cmax) / l1);
-  return lim;
+  const float lmax = __uint_as_float(m_lin), cmax = __uint_as_float(m_c);
+  if (!(lmax < 60000.f) || !(cmax < 3.0e38f)) return 0.f;
+  return 60000.f / GDN_F16_XT_SCALE;
 }
 
 // The plan also ORDERS each lane's list slots.  A lane may visit its SL slots in any order (softmax and the
@@ -492,7 +518,7 @@ __global__ __launch_bounds__(64 * NT) void gdn_dense_plan_kernel(const DArgs a, 
     k.sjoff[q] = s_sj[tid][s_perm[tid][q]];
     k.scoff[q] = s_sc[tid][s_perm[tid][q]];
   }
-  compute_tables<NT, DC>(a, reinterpret_cast<float*>(plan));
+  compute_tables<NT, DC, FMT>(a, reinterpret_cast<float*>(plan));
   unsigned* lanes = plan + K::TABLE_WORDS;
   k.each_word([&](int i, unsigned& wd) { lanes[i * T + threadIdx.x] = wd; });
   const float xlim = compute_xlimit<NT, DC, FMT>(a);
@@ -577,6 +603,9 @@ __global__ __launch_bounds__(64 * NT) void gdn_bank_order_kernel(const uint16_t*
 #define GDN_PRIO_M 3
 #define GDN_PRIO_E 1
 #endif
+#ifndef GDN_PRIO_P1         // the projection behind the aggregation (fp32 storage): matrix-core work, like M
+#define GDN_PRIO_P1 3
+#endif
 template <int NT, int DC, int WK, int SL, int FMT>
 // two workgroups per CU (2 waves per SIMD, <= 256 registers) where the constants fit; the long-list /
 // long-window variants take the whole register file (accumulator registers as spill space) at one
@@ -596,6 +625,9 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
     reinterpret_cast<uint4*>(smem + C::OFF_A + wv * C::AWAVE)[t] = make_uint4(0, 0, 0, 0);
   {   // pad columns CW .. XP-1 of the x tile are never read; columns w .. CW-1 and rows >= n are stored as 0
   }
+  if constexpr (C::XAGG)   // X^T fragments: the lanes of rows 16 WK .. 31 are never written again
+    for (int t = tid; t < C::KS * C::NPX * 64; t += C::THREADS)
+      reinterpret_cast<uint4*>(smem + C::OFF_XF)[t] = make_uint4(0, 0, 0, 0);
   // per-launch constants: from the plan, or computed here (gdn_forward_fused without a plan)
   LaneConsts<NT, DC, WK, SL, FMT> k;
   float xlim = INFINITY;                       // range guard (fp32 storage): see compute_xlimit
@@ -608,29 +640,36 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
       if (a.range_flag) xlim = __uint_as_float(a.plan[LaneConsts<NT, DC, WK, SL, FMT>::LIMIT_WORD]);
   } else {
     compute_lane_consts(a, k);     // (no plan, no x limit: the range guard is a feature of planned launches)
-    compute_tables<NT, DC>(a, reinterpret_cast<float*>(smem + C::OFF_EC));
+    compute_tables<NT, DC, FMT>(a, reinterpret_cast<float*>(smem + C::OFF_EC));
   }
-  // out-of-range lanes, as a wave-uniform mask in scalar registers (the kernel sits AT its 256-VGPR budget: a
-  // per-lane flag cost 20 more spilled registers and 9 % of the launch)
+  // out-of-range lanes, as a wave-uniform mask in scalar registers (the bf16-storage and long-window variants sit
+  // AT their 256-VGPR budget: a per-lane flag cost 20 more spilled registers and 9 % of the launch)
   unsigned long long out_of_range = 0ull;
   const int si_off = C::OFF_SI + (32 * wv + (lane >> 1)) * 4;
   const int cs_off = C::OFF_CS + (min(l32, 2) * C::ROWS + 32 * wv + 4 * h) * 4;   // + 32 (r >> 2): 4 rows
   const int tgt = 32 * wv + l32;
 
-  // x staging: a thread owns column (tid % CW) of rows row0, row0 + RS, ...; global offsets are one VGPR
-  // plus a scalar step per row group (buffer loads: reads past the end of the input return 0), LDS
+  // x staging: a thread owns column (tid % CW) of rows row0 + xro(0), row0 + xro(1), ...; global offsets are one
+  // VGPR plus a scalar step per row (buffer loads: reads past the end of the input return 0), LDS
   // offsets one VGPR plus an immediate.  Pad rows / columns are stored as 0 every window.
+  //   row0 = tid / CW, xro(u) = u RS: the rows of a thread are RS apart; or,
+  //   XAGG: the thread's values 8q .. 8q+7 are one operand slot of X^T (k-step s, lane half hh) in the k order of
+  //   pos_of_source: slot 2s + hh = tid / CW + q RS, row0 = 16 s + 4 hh, xro(8q + j) = 16 NT q + 8 (j >> 2) + (j & 3).
   constexpr int CW = 16 * WK, RS = C::THREADS / CW;
   static_assert(C::XU * RS == C::ROWS, "x staging covers the tile");
+  static_assert(!C::XAGG || RS * WK == 2 * C::KS, "one operand slot per thread and pass");
   constexpr int ESZ = FMT == FMT_F16 ? 4 : 2;
-  const int xcol = tid & (CW - 1), xrow0 = tid / CW;
+  const int xcol = tid & (CW - 1), xsl = tid / CW;
+  const int xrow0 = C::XAGG ? 16 * (xsl >> 1) + 4 * (xsl & 1) : xsl;
+  auto xro = [](int u) constexpr { return C::XAGG ? 16 * NT * (u >> 3) + 8 * ((u & 7) >> 2) + (u & 3) : u * RS; };
   const int rstride = a.series_len > 0 ? a.series_len : w;
   const int xvoff = (min(xrow0, n - 1) * rstride + min(xcol, w - 1)) * ESZ;
-  const int xstep = RS * rstride * ESZ;
+  const int xstep = rstride * ESZ;
   const int xst_off = C::OFF_XS + (xrow0 * C::XP + xcol) * 4;
+  const int xf_st = C::OFF_XF + (((xsl >> 1) * C::NPX) << 10) + ((xsl & 1) * 32 + xcol) * 16;   // XAGG: + (q NT NPX + t) << 10
   bool xok[C::XU];
 #pragma unroll
-  for (int u = 0; u < C::XU; ++u) xok[u] = xcol < w && xrow0 + u * RS < n;
+  for (int u = 0; u < C::XU; ++u) xok[u] = xcol < w && xrow0 + xro(u) < n;
   const size_t win_stride = a.series_len > 0 ? 1 : (size_t)n * w;
   const size_t x0 = a.series_len > 0 ? (size_t)a.series_first : 0;
   const size_t x_total = (a.series_len > 0 ? (size_t)n * a.series_len : (size_t)a.batch * n * w) * ESZ;
@@ -644,9 +683,9 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
 #pragma unroll
     for (int u = 0; u < C::XU; ++u) {
       if constexpr (FMT == FMT_F16) {
-        xr[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, xvoff, u * xstep, 0));
+        xr[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, xvoff, xro(u) * xstep, 0));
       } else {
-        xr[u] = __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(rsrc, xvoff, u * xstep, 0) << 16);
+        xr[u] = __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(rsrc, xvoff, xro(u) * xstep, 0) << 16);
       }
     }
   };
@@ -663,24 +702,39 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
 #pragma unroll
     for (int u = 0; u < C::XU; ++u) {
       const float xv = xok[u] ? xr[u] : 0.f;
-      *reinterpret_cast<float*>(smem + xst_off + u * (RS * C::XP * 4)) = xv;
+      *reinterpret_cast<float*>(smem + xst_off + xro(u) * (C::XP * 4)) = xv;
 #ifndef GDN_NO_GUARD
       if constexpr (FMT == FMT_F16) out_of_range |= __builtin_amdgcn_ballot_w64(!(fabsf(xv) < xlim));   // (NaN too)
 #endif
     }
     if (b == (int)blockIdx.x) { GDN_STAMP(3) }
     __syncthreads();                                           // B1: x tile of window b visible
+    if constexpr (C::XAGG) {
+      // X^T operand fragments of window b (every wave is past M of window b - 1, the last reader of the area)
+#pragma unroll
+      for (int q = 0; q < WK; ++q) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (xok[8 * q + j] ? xr[8 * q + j] : 0.f) * GDN_F16_XT_SCALE;
+        u32x4 xf[C::NPX];
+        split8<FMT, C::NPX>(v, xf);
+#pragma unroll
+        for (int t = 0; t < C::NPX; ++t)
+          *reinterpret_cast<u32x4*>(smem + xf_st + ((q * NT * C::NPX + t) << 10)) = xf[t];
+      }
+    }
     load_window(min(b + (int)gridDim.x, a.batch - 1));         // lands under the math (last round: re-read)
     if (b == (int)blockIdx.x) { GDN_STAMP(4) }
 
     // ------------------------------------------------------------ P
     {
       __builtin_amdgcn_s_setprio(GDN_PRIO_P);
-      f32x16 acc1[DC], accs;
+      f32x16 acc1[C::XAGG ? 1 : DC], accs;      // (XAGG: no projected tile, P0 is the scalar tile alone)
+      if constexpr (!C::XAGG)
 #pragma unroll
-      for (int cb = 0; cb < DC; ++cb)
+        for (int cb = 0; cb < DC; ++cb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc1[cb][r] = k.cin[cb];
+          for (int r = 0; r < 16; ++r) acc1[cb][r] = 0.f;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 t = *reinterpret_cast<const float4*>(smem + cs_off + 32 * g);
@@ -700,8 +754,9 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
 #pragma unroll
           for (int tl = 0; tl < C::NTL; ++tl)
             if (tx + tl < (C::NTXIN > C::NTL ? C::NTXIN : C::NTL)) {
+              if constexpr (!C::XAGG)
 #pragma unroll
-              for (int cb = 0; cb < DC; ++cb) acc1[cb] = F::mfma(ax[tx], k.bl[cb][wk][tl], acc1[cb]);
+                for (int cb = 0; cb < DC; ++cb) acc1[cb] = F::mfma(ax[tx], k.bl[cb][wk][tl], acc1[cb]);
               accs = F::mfma(ax[tx], k.bs[wk][tl], accs);
             }
       }
@@ -712,6 +767,7 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
         for (int r = 0; r < 16; ++r) sdst[(r & 3) + 8 * (r >> 2)] = accs[r];
       }
       // the projected tile as operand fragments of the aggregation product: k-steps 2wv, 2wv+1
+      if constexpr (!C::XAGG)
 #pragma unroll
       for (int cb = 0; cb < DC; ++cb)
 #pragma unroll
@@ -745,25 +801,26 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
     // Operand reads run one k-step ahead of the products (two named fragment sets).
     float ygt = 0.f;                                  // issued here, consumed after the products
     if (a.keys && h == 0 && tgt < n) ygt = a.key_gt[(size_t)b * n + tgt];
-    f32x16 acc2[DC];
+    constexpr int MCB = C::MCB;                         // XAGG: one block, Zx^T[w, target]
+    f32x16 acc2[MCB];
 #pragma unroll
-    for (int cb = 0; cb < DC; ++cb)
+    for (int cb = 0; cb < MCB; ++cb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[cb][r] = 0.f;
-    constexpr int XF_KS = (DC * C::NPX) << 10;          // bytes of fragments per k-step
+    constexpr int XF_KS = (MCB * C::NPX) << 10;         // bytes of fragments per k-step
     const int xf_lane = C::OFF_XF + lane * 16;
-    u32x4 fa[2], fx[2][DC][C::NPX];
+    u32x4 fa[2], fx[2][MCB][C::NPX];
     auto fetch_hi = [&](int ks, int buf) {
       fa[buf] = lds_frag(smem, arow_off + ks * 32);
 #pragma unroll
-      for (int cb = 0; cb < DC; ++cb)
+      for (int cb = 0; cb < MCB; ++cb)
 #pragma unroll
         for (int t = 0; t < C::NPX; ++t) fx[buf][cb][t] = lds_frag(smem, xf_lane + ks * XF_KS + ((cb * C::NPX + t) << 10));
     };
     auto fetch_lo = [&](int ks, int buf) {
       fa[buf] = lds_frag(smem, arow_off + ks * 32);
 #pragma unroll
-      for (int cb = 0; cb < DC; ++cb) fx[buf][cb][0] = lds_frag(smem, xf_lane + ks * XF_KS + ((cb * C::NPX) << 10));
+      for (int cb = 0; cb < MCB; ++cb) fx[buf][cb][0] = lds_frag(smem, xf_lane + ks * XF_KS + ((cb * C::NPX) << 10));
     };
     if (b == (int)blockIdx.x) { GDN_STAMP(7) }
     __builtin_amdgcn_s_setprio(GDN_PRIO_M);      // see the note at the kernel's head
@@ -776,7 +833,7 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
       if (ks + 1 < C::KS) fetch_hi(ks + 1, (ks + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int cb = 0; cb < DC; ++cb)
+      for (int cb = 0; cb < MCB; ++cb)
 #pragma unroll
         for (int t = 0; t < C::NPX; ++t) acc2[cb] = F::mfma(fx[ks & 1][cb][t], fa[ks & 1], acc2[cb]);
       __builtin_amdgcn_sched_barrier(0);
@@ -790,12 +847,49 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
       if (ks + 1 < C::KS) fetch_lo(ks + 1, (ks + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int cb = 0; cb < DC; ++cb) acc2[cb] = F::mfma(fx[ks & 1][cb][0], fa[ks & 1], acc2[cb]);
+      for (int cb = 0; cb < MCB; ++cb) acc2[cb] = F::mfma(fx[ks & 1][cb][0], fa[ks & 1], acc2[cb]);
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if (b == (int)blockIdx.x) { GDN_STAMP(8) }
+    // ------------------------------------------------------------ P1 (XAGG)
+    // out^T[c, target] = lin' . Zx + C.  Registers 8wk .. 8wk+7 of the aggregation accumulator (target on the lane)
+    // are k slots 8h .. 8h+7 of the B operand as they stand (window column 16wk + 8(j>>2) + 4h + (j&3): the order
+    // k.bl was built in); they carry 2^12 (alpha) x 2^3 (x) and go back to 2^3, an exact power of two, before the
+    // split.  C-in is the accumulator's initial value: the sh1' row of the table block, column on the registers.
+    f32x16 acc3[DC];
+    if constexpr (C::XAGG) {
+      __builtin_amdgcn_s_setprio(GDN_PRIO_P1);
+#pragma unroll
+      for (int cb = 0; cb < DC; ++cb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4 t = *reinterpret_cast<const float4*>(smem + ec_off + 12 * d + 128 * cb + 32 * g);
+          acc3[cb][4 * g] = t.x; acc3[cb][4 * g + 1] = t.y; acc3[cb][4 * g + 2] = t.z; acc3[cb][4 * g + 3] = t.w;
+        }
+#pragma unroll
+      for (int wk = 0; wk < WK; ++wk) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          v[j] = acc2[0][8 * wk + j] * (GDN_F16_Z_SCALE / (GDN_F16_ALPHA_SCALE * GDN_F16_XT_SCALE));
+        u32x4 zf[2];
+        split8<FMT, 2>(v, zf);
+#pragma unroll
+        for (int tz = 0; tz < 2; ++tz)
+#pragma unroll
+          for (int tl = 0; tl < C::NTL; ++tl)
+            if (tz + tl < 2) {
+#pragma unroll
+              for (int cb = 0; cb < DC; ++cb) acc3[cb] = F::mfma(k.bl[cb][wk][tl], zf[tz], acc3[cb]);
+            }
+      }
+    } else {
+#pragma unroll
+      for (int cb = 0; cb < DC; ++cb) acc3[cb] = acc2[cb < MCB ? cb : 0];
     }
 
     __builtin_amdgcn_s_setprio(GDN_PRIO_E);
-    if (b == (int)blockIdx.x) { GDN_STAMP(8) }
+    if (b == (int)blockIdx.x) { GDN_STAMP(9) }
     // ------------------------------------------------------------ E  (models/GDN.py:77-79,175-184)
     float part = 0.f;
 #pragma unroll
@@ -814,7 +908,7 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          float v = acc2[cb][4 * g + i];
+          float v = acc3[cb][4 * g + i];
           if constexpr (!FOLD) v = fmaf(v, sc1a[i], sh1a[i]);
           v = fmaxf(v, 0.f);
           v = fmaxf(fmaf(v, k.e2[cb][4 * g + i], sh2a[i]), 0.f);
@@ -827,11 +921,11 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
       a.out[(size_t)b * n + tgt] = o;
       if (a.keys) a.keys[(size_t)tgt * a.key_pitch + b] = fabs((double)o - (double)ygt);
     }
-    if (b == (int)blockIdx.x) { GDN_STAMP(9) }
+    if (b == (int)blockIdx.x) { GDN_STAMP(10) }
   }
   if constexpr (FMT == FMT_F16)
     if (a.range_flag && out_of_range != 0ull && lane == 0) a.range_flag[0] = 1;     // (same value from every writer)
-  GDN_STAMP(10)
+  GDN_STAMP(11)
 }
 
 #ifndef GDN_DENSE_EXTRA_DC   // the d = 128 translation unit instantiates the fused family only

@@ -385,10 +385,12 @@ int gdn_graph_bank_order(const uint16_t* nbr, int n, int k, uint16_t* nbr_ordere
 /* ---- plans: the fused forward with its per-launch constants precomputed -------------
  * For shapes on the matrix-core path (n <= 127, d = 64 or 128, w <= 32, k <= 63) everything a
  * workgroup of gdn_forward_fused derives from the parameters and the sensor graph (list
- * offsets, split weight operands, folded BatchNorm / embedding factors) can be computed
+ * offsets, split weight operands in the k order of the product that consumes them, folded
+ * BatchNorm / embedding factors, the C-in table, the x limit) can be computed
  * once per parameter update into a caller-owned device buffer, the PLAN; launches that are
  * given it skip that prologue (~10 us per workgroup), which is most of the time of a
- * single-minibatch launch.  The plan is read-only for the launches and holds no pointers.
+ * single-minibatch launch.  The plan is read-only for the launches and holds no pointers;
+ * its layout is private to the library build that wrote it (size: gdn_fused_plan_bytes).
  *   gdn_fused_plan_bytes   size of the plan for this shape (0 = shape not on this path:
  *                          use gdn_forward_fused);
  *   gdn_fused_plan_build   same parameter arguments as gdn_forward_fused;
@@ -410,9 +412,11 @@ int gdn_forward_fused_series_plan(const float* series, int series_len, int first
 
 /* ---- range guard ---------------------------------------------------------------------
  * The reference computes in fp32 on whatever the caller feeds it (models/graph_layer.py:56).  The fp32-storage
- * matrix-core kernels carry x, and the BatchNorm-folded projected tile times 8, as two f16 terms each: values
- * of 65504 and beyond do not exist there.  Every plan therefore holds its X LIMIT, the largest |x| for which
- * both are representable whatever the window: min(60000, (60000 - max_c |C-in[c]|) / max_c sum_w |lin'[c,w]|)
+ * fused matrix-core kernel aggregates the raw window before it projects it: it carries x times 8, and the aggregated
+ * row sum_j alpha_ij x_j times 8 (a convex combination of the window's values), as two f16 terms each: values of
+ * 65504 and beyond do not exist there.  Every plan therefore holds its X LIMIT, the largest |x| for which both are
+ * representable whatever the window: 60000 / 8 = 7500, whatever lin' and C-in are (the projected tile and C-in
+ * exist in fp32 only) — or 0 when an entry of the BatchNorm-folded lin' times 8 is itself outside the f16 range
  * (a float at byte gdn_fused_plan_limit_offset(...) of the plan; +inf for bf16 storage, whose terms have
  * fp32's exponent range).  Normalised data (the reference's scripts/process_*.py: MinMax to [0, 1]) sits four
  * orders of magnitude below it; raw engineering units may not.  Two ways to stay exact for ANY input:

@@ -15,7 +15,7 @@ from test_gpu_forward_parity import random_params  # noqa: E402
 dev = torch.device("cuda:0")
 model = random_params(127, 15, 30, 64, seed=0).to(dev).eval()
 names = ["start", "consts loaded", "first x issued+barrier", "x stored", "B1 passed", "P done", "B2 passed",
-         "S done", "M done", "E done + store", "kernel end"]
+         "S done", "M done", "P1 done", "E done + store", "kernel end"]
 for b in (512, 4096, 32768):
     x = torch.rand((b, 127, 15), device=dev)
     with torch.no_grad():
@@ -26,7 +26,7 @@ for b in (512, 4096, 32768):
     lib = _lib.load()
     lib.gdn_debug_read_stamps.argtypes = [ctypes.c_void_p]
     assert lib.gdn_debug_read_stamps(buf) == 0
-    t = [buf[i] for i in range(11)]
+    t = [buf[i] for i in range(12)]
     print(f"batch {b}: (10 ns ticks since kernel start)")
-    for i in range(1, 11):
+    for i in range(1, 12):
         print(f"   {names[i]:28s} +{(t[i] - t[i - 1]) * 10:7d} ns   at {(t[i] - t[0]) * 10:7d} ns")
