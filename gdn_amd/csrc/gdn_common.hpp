@@ -114,6 +114,7 @@ __device__ __forceinline__ float dpp_f(float v) {
 }
 #define GDN_DPP_XOR1 0xB1          // quad_perm [1,0,3,2]
 #define GDN_DPP_XOR2 0x4E          // quad_perm [2,3,0,1]
+#define GDN_DPP_XOR3 0x1B          // quad_perm [3,2,1,0]
 #define GDN_DPP_HALF_MIRROR 0x141  // lane i <-> 7-i inside each 8
 #define GDN_DPP_MIRROR 0x140       // lane i <-> 15-i inside each 16
 #define GDN_DPP_ROR1 0x121         // rotate the 16-lane row by one lane

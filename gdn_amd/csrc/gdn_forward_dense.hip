@@ -178,14 +178,38 @@ struct DCfg {
   static constexpr int NTXIN = FMT == FMT_F16 ? 2 : 1; // terms of the x values (bf16 storage: exact)
   static constexpr int XP = 16 * WK + 4;               // x tile pitch in floats (odd number of 16-B slots)
   static constexpr int XU = 8 * WK;                    // x values per thread per window
+  // XAGG, WK = 1: rows 16 .. 31 of X^T do not exist and rows 16 .. 31 of the product Zx^T are never consumed (P1
+  // reads accumulator registers 0 .. 8 WK - 1), so a fragment holds the 16 lanes of each lane half that carry
+  // window columns and the lanes l32 >= 16 read their neighbour's slot: whatever they multiply lands in dead rows
+  static constexpr bool XHALF = XAGG && WK == 1;
+  static constexpr int XFL = XHALF ? 16 : 32;          // stored lanes per lane half of an X^T fragment
+  static constexpr int XFRAG = 2 * XFL * 16;           // bytes per (k-step, block, term)
   static constexpr int OFF_A = 0;
-  static constexpr int OFF_XF = NT * AWAVE;            // [KS][MCB][NPX][64 lanes] x 16 B
-  static constexpr int OFF_XS = OFF_XF + KS * MCB * NPX * 1024;
-  static constexpr int OFF_SI = OFF_XS + ROWS * XP * 4;
+  static constexpr int OFF_XF = NT * AWAVE;            // [KS][MCB][NPX][2 XFL lanes] x 16 B
+  static constexpr int OFF_XS = OFF_XF + KS * MCB * NPX * XFRAG;
+  static constexpr int OFF_SI = OFF_XS + (XAGG ? 0 : ROWS * XP * 4);   // (XAGG: no row-major x tile)
   static constexpr int OFF_SJ = OFF_SI + ROWS * 4;
   static constexpr int OFF_EC = OFF_SJ + ROWS * 4;     // epilogue column constants: 4 tables of 32 DC floats
   static constexpr int OFF_CS = OFF_EC + 4 * 32 * DC * 4;   // C-in of the scalar tile: [c_i | c_j | zeros][ROWS]
-  static constexpr int LDS = OFF_CS + 3 * ROWS * 4;
+  static constexpr int CS_WORDS = XAGG ? 0 : 3 * ROWS;      // (XAGG: no scalar tile, c_i / c_j are LaneConsts::sadd)
+  static constexpr int LDS = OFF_CS + CS_WORDS * 4;
+  // x staging (see the kernel): a thread owns column tid % CW of XU rows.  XAGG: its values 8q .. 8q+7 are one
+  // operand slot of X^T, slot tid / CW + q RS = 2 (k-step) + (lane half), in the k order of pos_of_source
+  static constexpr int CW = 16 * WK, RS = THREADS / CW;
+  static __host__ __device__ constexpr int xrow0(int xsl) { return XAGG ? 16 * (xsl >> 1) + 4 * (xsl & 1) : xsl; }
+  static __host__ __device__ constexpr int xro(int u) {
+    return XAGG ? 16 * NT * (u >> 3) + 8 * ((u & 7) >> 2) + (u & 3) : u * RS;
+  }
+  // Workgroups per CU the kernel is compiled for (__launch_bounds__: the register budget follows from it) and is
+  // launched at (fused_op refuses a launch whose occupancy query reports fewer).  Three with fp32 storage where a
+  // third of the CU's 160 KB of LDS, allocated in units of 1280 bytes, holds the workgroup (3 x NT waves on 4 SIMDs:
+  // <= 168 registers at NT = 4; the kernel takes 167 and no scratch); two (<= 256 registers) for bf16 storage, whose
+  // row-major tile and 175+ registers do not fit three; the long-list / long-window variants take the whole
+  // register file (accumulator registers as spill space) at one.
+  static constexpr int LDS_UNIT = 1280;
+  static constexpr int LDS_ALLOC = (LDS + LDS_UNIT - 1) / LDS_UNIT * LDS_UNIT;
+  static constexpr int WGS = !(DC == 2 && NT >= 3 && SL <= 16 && WK == 1) ? 1
+                             : XAGG && 3 * LDS_ALLOC <= 160 * 1024 ? 3 : 2;
 };
 
 struct DArgs {
@@ -271,6 +295,19 @@ __device__ __forceinline__ void scatter_terms(char* smem, const int (&scoff)[SL]
   }
 }
 
+// One step of the halving butterfly of the attention scalars (fused kernel, X): a lane carries 2M partial sums, keeps
+// M of them (the upper half where `upper`), hands the other M to its partner (DPP pattern CTRL, whose `upper` is the
+// opposite) and adds what the partner hands over: M sums over twice as many lanes.
+template <int M, int CTRL, int N>
+__device__ __forceinline__ void halve_sources(float (&r)[N], bool upper) {
+  static_assert(2 * M <= N, "");
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    const float keep = upper ? r[i + M] : r[i], give = upper ? r[i] : r[i + M];
+    r[i] = keep + dpp_f<CTRL>(give);
+  }
+}
+
 #ifdef GDN_STAMPS   // diagnostic build only: shader-clock stamps of workgroup 0 / wave 0 (tools/probe_stamps.py)
 __device__ unsigned long long g_dense_stamps[64];
 #define GDN_STAMP(i)                                                                      \
@@ -300,11 +337,16 @@ template <int NT, int DC, int WK, int SL, int FMT>
 struct LaneConsts {
   using C = DCfg<NT, DC, WK, SL, FMT>;
   int sjoff[SL], scoff[SL];
-  u32x4 bl[DC][WK][C::NTL], bs[WK][C::NTL];
+  u32x4 bl[DC][WK][C::NTL], bs[WK][C::NTL];            // bs: the scalar tile's B operand (not XAGG)
+  // XAGG: the attention scalars are fp32 dot products reduced over the CW lanes that hold a source's columns (see
+  // the kernel).  A lane ends with ONE scalar: kind (s_i / s_j) = bit CW/2 of its column, source = row
+  // xrow0 + xro(column % (CW/2)).  sk = folded a_kind'[own column], sp = a_kind'[column of the first exchange's
+  // partner], sadd = c_kind of that source (-inf at the list sentinel, 0 on pad rows): the values of compute_tables
+  float sk, sp, sadd;
   float e2[DC][16];
   float out_b;
-  static constexpr int WORDS = 2 * SL + 4 * (DC * WK * C::NTL + WK * C::NTL) + 16 * DC + 1;
-  static constexpr int TABLE_WORDS = 4 * 32 * DC + 3 * C::ROWS;     // [ec | cs] as they sit in LDS
+  static constexpr int WORDS = 2 * SL + 4 * DC * WK * C::NTL + (C::XAGG ? 3 : 4 * WK * C::NTL) + 16 * DC + 1;
+  static constexpr int TABLE_WORDS = 4 * 32 * DC + C::CS_WORDS;     // [ec | cs] as they sit in LDS
   static constexpr size_t LIMIT_WORD = (size_t)TABLE_WORDS + (size_t)WORDS * C::THREADS;   // the x limit (float)
   static constexpr size_t PLAN_BYTES = (LIMIT_WORD + 1) * 4;
 
@@ -328,16 +370,22 @@ struct LaneConsts {
             f(i++, tmp);
             bl[cb][wk][t][e] = tmp;
           }
+    if constexpr (C::XAGG) {
+      f(i++, reinterpret_cast<unsigned&>(sk));
+      f(i++, reinterpret_cast<unsigned&>(sp));
+      f(i++, reinterpret_cast<unsigned&>(sadd));
+    } else {
 #pragma unroll
-    for (int wk = 0; wk < WK; ++wk)
+      for (int wk = 0; wk < WK; ++wk)
 #pragma unroll
-      for (int t = 0; t < C::NTL; ++t)
+        for (int t = 0; t < C::NTL; ++t)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          unsigned tmp = bs[wk][t][e];
-          f(i++, tmp);
-          bs[wk][t][e] = tmp;
-        }
+          for (int e = 0; e < 4; ++e) {
+            unsigned tmp = bs[wk][t][e];
+            f(i++, tmp);
+            bs[wk][t][e] = tmp;
+          }
+    }
 #pragma unroll
     for (int cb = 0; cb < DC; ++cb)
 #pragma unroll
@@ -384,15 +432,27 @@ __device__ __forceinline__ void compute_lane_consts(const DArgs& a, LaneConsts<N
       split8<FMT, C::NTL>(v, k.bl[cb][wk]);
     }
   }
+  if constexpr (C::XAGG) {
+    // a_i / a_j are stored zero padded to 64; the first exchange of the reduction pairs column c with c ^ (CW - 1)
+    // (WK = 1: row mirror) or c ^ 16 (WK = 2: the other DPP row)
+    const int xcol = tid & (C::CW - 1), kind = xcol / (C::CW / 2);
+    const int pcol = WK == 1 ? xcol ^ 15 : xcol ^ 16;
+    const int row = C::xrow0(tid / C::CW) + C::xro(xcol & (C::CW / 2 - 1));
+    k.sk = ld_or(a.node_terms, kind * GDN_A_PITCH + xcol, xcol < w) * GDN_LOG2E;
+    k.sp = ld_or(a.node_terms, kind * GDN_A_PITCH + pcol, pcol < w) * GDN_LOG2E;
+    k.sadd = ld_or(a.node_terms, 2 * GDN_A_PITCH + kind * n + row, row < n) * GDN_LOG2E;
+    if (kind == 1 && row == n) k.sadd = -INFINITY;
+  } else {
 #pragma unroll
-  for (int wk = 0; wk < WK; ++wk) {
-    float v[8];
+    for (int wk = 0; wk < WK; ++wk) {
+      float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int kk = wk * 16 + 8 * h + j;   // a_i / a_j are stored zero padded to 64
-      v[j] = ld_or(a.node_terms, l32 * GDN_A_PITCH + kk, l32 < 2) * GDN_LOG2E;
+      for (int j = 0; j < 8; ++j) {
+        const int kk = wk * 16 + 8 * h + j;   // a_i / a_j are stored zero padded to 64
+        v[j] = ld_or(a.node_terms, l32 * GDN_A_PITCH + kk, l32 < 2) * GDN_LOG2E;
+      }
+      split8<FMT, C::NTL>(v, k.bs[wk]);
     }
-    split8<FMT, C::NTL>(v, k.bs[wk]);
   }
   // E: embedding x BatchNorm scale of this lane's target, per (column block, register)
   const int tgt = 32 * wv + l32;
@@ -423,6 +483,7 @@ __device__ __forceinline__ void compute_tables(const DArgs& a, float* dst) {
     dst[3 * d + c] = fmaf(a.gnn_bias[c], a.bn1[c], a.bn1[d + c]) *
                      (FMT == FMT_F16 ? GDN_F16_Z_SCALE * GDN_F16_X_SCALE : 1.f);
   }
+  if constexpr (FMT == FMT_F16) return;     // (DCfg::XAGG: no scalar tile)
   float* ct = dst + 4 * d;
   for (int t = tid; t < 3 * ROWS; t += THREADS) {
     const int which = t / ROWS, row = t - which * ROWS;
@@ -607,9 +668,8 @@ __global__ __launch_bounds__(64 * NT) void gdn_bank_order_kernel(const uint16_t*
 #define GDN_PRIO_P1 3
 #endif
 template <int NT, int DC, int WK, int SL, int FMT>
-// two workgroups per CU (2 waves per SIMD, <= 256 registers) where the constants fit; the long-list /
-// long-window variants take the whole register file (accumulator registers as spill space) at one
-__global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1) ? 2 : 1) GDN_FUSED_ATTR void gdn_dense_fused_kernel(const DArgs a) {
+// DCfg::WGS workgroups per CU
+__global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSED_ATTR void gdn_dense_fused_kernel(const DArgs a) {
   using C = DCfg<NT, DC, WK, SL, FMT>;
   using F = Fmt<FMT>;
   extern __shared__ uint4 smem_u4[];
@@ -625,9 +685,7 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
     reinterpret_cast<uint4*>(smem + C::OFF_A + wv * C::AWAVE)[t] = make_uint4(0, 0, 0, 0);
   {   // pad columns CW .. XP-1 of the x tile are never read; columns w .. CW-1 and rows >= n are stored as 0
   }
-  if constexpr (C::XAGG)   // X^T fragments: the lanes of rows 16 WK .. 31 are never written again
-    for (int t = tid; t < C::KS * C::NPX * 64; t += C::THREADS)
-      reinterpret_cast<uint4*>(smem + C::OFF_XF)[t] = make_uint4(0, 0, 0, 0);
+  // (XAGG: every window rewrites the whole X^T fragment area, pad rows and columns as 0)
   // per-launch constants: from the plan, or computed here (gdn_forward_fused without a plan)
   LaneConsts<NT, DC, WK, SL, FMT> k;
   float xlim = INFINITY;                       // range guard (fp32 storage): see compute_xlimit
@@ -646,7 +704,7 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
   // AT their 256-VGPR budget: a per-lane flag cost 20 more spilled registers and 9 % of the launch)
   unsigned long long out_of_range = 0ull;
   const int si_off = C::OFF_SI + (32 * wv + (lane >> 1)) * 4;
-  const int cs_off = C::OFF_CS + (min(l32, 2) * C::ROWS + 32 * wv + 4 * h) * 4;   // + 32 (r >> 2): 4 rows
+  const int cs_off = C::OFF_CS + (min(l32, 2) * C::ROWS + 32 * wv + 4 * h) * 4;   // + 32 (r >> 2): 4 rows (not XAGG)
   const int tgt = 32 * wv + l32;
 
   // x staging: a thread owns column (tid % CW) of rows row0 + xro(0), row0 + xro(1), ...; global offsets are one
@@ -655,18 +713,20 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
   //   row0 = tid / CW, xro(u) = u RS: the rows of a thread are RS apart; or,
   //   XAGG: the thread's values 8q .. 8q+7 are one operand slot of X^T (k-step s, lane half hh) in the k order of
   //   pos_of_source: slot 2s + hh = tid / CW + q RS, row0 = 16 s + 4 hh, xro(8q + j) = 16 NT q + 8 (j >> 2) + (j & 3).
-  constexpr int CW = 16 * WK, RS = C::THREADS / CW;
+  constexpr int CW = C::CW, RS = C::RS;
   static_assert(C::XU * RS == C::ROWS, "x staging covers the tile");
   static_assert(!C::XAGG || RS * WK == 2 * C::KS, "one operand slot per thread and pass");
   constexpr int ESZ = FMT == FMT_F16 ? 4 : 2;
   const int xcol = tid & (CW - 1), xsl = tid / CW;
-  const int xrow0 = C::XAGG ? 16 * (xsl >> 1) + 4 * (xsl & 1) : xsl;
-  auto xro = [](int u) constexpr { return C::XAGG ? 16 * NT * (u >> 3) + 8 * ((u & 7) >> 2) + (u & 3) : u * RS; };
+  const int xrow0 = C::xrow0(xsl);
+  auto xro = [](int u) constexpr { return C::xro(u); };
   const int rstride = a.series_len > 0 ? a.series_len : w;
   const int xvoff = (min(xrow0, n - 1) * rstride + min(xcol, w - 1)) * ESZ;
   const int xstep = rstride * ESZ;
-  const int xst_off = C::OFF_XS + (xrow0 * C::XP + xcol) * 4;
-  const int xf_st = C::OFF_XF + (((xsl >> 1) * C::NPX) << 10) + ((xsl & 1) * 32 + xcol) * 16;   // XAGG: + (q NT NPX + t) << 10
+  const int xst_off = C::OFF_XS + (xrow0 * C::XP + xcol) * 4;                      // x tile (not XAGG)
+  const int xf_st = C::OFF_XF + (xsl >> 1) * C::NPX * C::XFRAG + ((xsl & 1) * C::XFL + xcol) * 16;   // XAGG: + (q NT NPX + t) XFRAG
+  // XAGG: where this lane's attention scalar goes (LaneConsts::sk): s_i / s_j of one source
+  const int xs_dst = (xcol / (CW / 2) ? C::OFF_SJ : C::OFF_SI) + (xrow0 + C::xro(xcol & (CW / 2 - 1))) * 4;
   bool xok[C::XU];
 #pragma unroll
   for (int u = 0; u < C::XU; ++u) xok[u] = xcol < w && xrow0 + xro(u) < n;
@@ -695,96 +755,124 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
   GDN_STAMP(2)
 
   const int arow_off = C::OFF_A + wv * C::AWAVE + l32 * C::AROW + h * 16;   // alpha operand of this lane
-  const int xrow_off = C::OFF_XS + ((32 * wv + l32) * C::XP + 8 * h) * 4;  // x operand of this lane
+  const int xrow_off = C::OFF_XS + ((32 * wv + l32) * C::XP + 8 * h) * 4;  // x operand of this lane (not XAGG)
   const int ec_off = C::OFF_EC + 16 * h;                                   // + 32 (r >> 2) + 128 cb: 4 columns
 
   for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
-#pragma unroll
-    for (int u = 0; u < C::XU; ++u) {
-      const float xv = xok[u] ? xr[u] : 0.f;
-      *reinterpret_cast<float*>(smem + xst_off + xro(u) * (C::XP * 4)) = xv;
-#ifndef GDN_NO_GUARD
-      if constexpr (FMT == FMT_F16) out_of_range |= __builtin_amdgcn_ballot_w64(!(fabsf(xv) < xlim));   // (NaN too)
-#endif
-    }
-    if (b == (int)blockIdx.x) { GDN_STAMP(3) }
-    __syncthreads();                                           // B1: x tile of window b visible
     if constexpr (C::XAGG) {
-      // X^T operand fragments of window b (every wave is past M of window b - 1, the last reader of the area)
+      // ---------------------------------------------------------- X  (fp32 storage: no x tile, no P0)
+      __builtin_amdgcn_s_setprio(GDN_PRIO_P);
+      if (b == (int)blockIdx.x) { GDN_STAMP(3) }
+      __syncthreads();     // B1: every wave is past S and M of window b - 1, the last readers of s_i / s_j and of
+                           // the fragment area (the alpha image is wave private)
+      float xv[C::XU];
+#pragma unroll
+      for (int u = 0; u < C::XU; ++u) {
+        xv[u] = xok[u] ? xr[u] : 0.f;
+#ifndef GDN_NO_GUARD
+        out_of_range |= __builtin_amdgcn_ballot_w64(!(fabsf(xv[u]) < xlim));   // (NaN too)
+#endif
+      }
+      // X^T operand fragments of window b
 #pragma unroll
       for (int q = 0; q < WK; ++q) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (xok[8 * q + j] ? xr[8 * q + j] : 0.f) * GDN_F16_XT_SCALE;
+        for (int j = 0; j < 8; ++j) v[j] = xv[8 * q + j] * GDN_F16_XT_SCALE;
         u32x4 xf[C::NPX];
         split8<FMT, C::NPX>(v, xf);
 #pragma unroll
         for (int t = 0; t < C::NPX; ++t)
-          *reinterpret_cast<u32x4*>(smem + xf_st + ((q * NT * C::NPX + t) << 10)) = xf[t];
+          *reinterpret_cast<u32x4*>(smem + xf_st + (q * NT * C::NPX + t) * C::XFRAG) = xf[t];
       }
-    }
-    load_window(min(b + (int)gridDim.x, a.batch - 1));         // lands under the math (last round: re-read)
-    if (b == (int)blockIdx.x) { GDN_STAMP(4) }
+      // Attention scalars s_i / s_j of every source (graph_layer.py:94-104), log2 domain: fp32 dot products of
+      // length w over the CW lanes that hold a source's columns, all 2 XU of a thread reduced together by a halving
+      // butterfly: the first exchange decides the kind (lanes with bit CW/2 of the column clear keep s_i, the others
+      // s_j, so the coefficient of either side is a per-lane constant: no select), every later one halves the
+      // sources a lane carries (keep one half, hand the other to the partner), until lane c holds the whole sum of
+      // one (kind, source): 2 XU - 1 exchanges instead of 2 XU x log2(CW).
+      float sr[C::XU];
+#pragma unroll
+      for (int u = 0; u < C::XU; ++u) {
+        const float other = WK == 1 ? dpp_f<GDN_DPP_MIRROR>(xv[u]) : __shfl_xor(xv[u], 16);
+        sr[u] = fmaf(other, k.sp, xv[u] * k.sk);
+      }
+      if constexpr (WK == 2) halve_sources<8, GDN_DPP_MIRROR>(sr, (xcol & 8) != 0);
+      halve_sources<4, GDN_DPP_HALF_MIRROR>(sr, (xcol & 4) != 0);
+      halve_sources<2, GDN_DPP_XOR3>(sr, (xcol & 2) != 0);
+      halve_sources<1, GDN_DPP_XOR1>(sr, (xcol & 1) != 0);
+      *reinterpret_cast<float*>(smem + xs_dst) = sr[0] + k.sadd;
+      load_window(min(b + (int)gridDim.x, a.batch - 1));         // lands under the math (last round: re-read)
+      if (b == (int)blockIdx.x) { GDN_STAMP(4) }
+    } else {
+      // ---------------------------------------------------------- bf16 storage: x tile, then P
+#pragma unroll
+      for (int u = 0; u < C::XU; ++u) {
+        const float xv = xok[u] ? xr[u] : 0.f;
+        *reinterpret_cast<float*>(smem + xst_off + xro(u) * (C::XP * 4)) = xv;
+      }
+      if (b == (int)blockIdx.x) { GDN_STAMP(3) }
+      __syncthreads();                                           // B1: x tile of window b visible
+      load_window(min(b + (int)gridDim.x, a.batch - 1));         // lands under the math (last round: re-read)
+      if (b == (int)blockIdx.x) { GDN_STAMP(4) }
 
-    // ------------------------------------------------------------ P
-    {
-      __builtin_amdgcn_s_setprio(GDN_PRIO_P);
-      f32x16 acc1[C::XAGG ? 1 : DC], accs;      // (XAGG: no projected tile, P0 is the scalar tile alone)
-      if constexpr (!C::XAGG)
+      // ------------------------------------------------------------ P
+      {
+        __builtin_amdgcn_s_setprio(GDN_PRIO_P);
+        f32x16 acc1[DC], accs;
 #pragma unroll
         for (int cb = 0; cb < DC; ++cb)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc1[cb][r] = 0.f;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 t = *reinterpret_cast<const float4*>(smem + cs_off + 32 * g);
-        accs[4 * g] = t.x; accs[4 * g + 1] = t.y; accs[4 * g + 2] = t.z; accs[4 * g + 3] = t.w;
-      }
+        for (int g = 0; g < 4; ++g) {
+          const float4 t = *reinterpret_cast<const float4*>(smem + cs_off + 32 * g);
+          accs[4 * g] = t.x; accs[4 * g + 1] = t.y; accs[4 * g + 2] = t.z; accs[4 * g + 3] = t.w;
+        }
 #pragma unroll
-      for (int wk = 0; wk < WK; ++wk) {
-        float v[8];
-        const float4 v0 = *reinterpret_cast<const float4*>(smem + xrow_off + wk * 64);
-        const float4 v1 = *reinterpret_cast<const float4*>(smem + xrow_off + wk * 64 + 16);
-        v[0] = v0.x; v[1] = v0.y; v[2] = v0.z; v[3] = v0.w;
-        v[4] = v1.x; v[5] = v1.y; v[6] = v1.z; v[7] = v1.w;
-        u32x4 ax[C::NTXIN];
-        split8<FMT, C::NTXIN>(v, ax);
+        for (int wk = 0; wk < WK; ++wk) {
+          float v[8];
+          const float4 v0 = *reinterpret_cast<const float4*>(smem + xrow_off + wk * 64);
+          const float4 v1 = *reinterpret_cast<const float4*>(smem + xrow_off + wk * 64 + 16);
+          v[0] = v0.x; v[1] = v0.y; v[2] = v0.z; v[3] = v0.w;
+          v[4] = v1.x; v[5] = v1.y; v[6] = v1.z; v[7] = v1.w;
+          u32x4 ax[C::NTXIN];
+          split8<FMT, C::NTXIN>(v, ax);
 #pragma unroll
-        for (int tx = 0; tx < C::NTXIN; ++tx)
+          for (int tx = 0; tx < C::NTXIN; ++tx)
 #pragma unroll
-          for (int tl = 0; tl < C::NTL; ++tl)
-            if (tx + tl < (C::NTXIN > C::NTL ? C::NTXIN : C::NTL)) {
-              if constexpr (!C::XAGG)
+            for (int tl = 0; tl < C::NTL; ++tl)
+              if (tx + tl < (C::NTXIN > C::NTL ? C::NTXIN : C::NTL)) {
 #pragma unroll
                 for (int cb = 0; cb < DC; ++cb) acc1[cb] = F::mfma(ax[tx], k.bl[cb][wk][tl], acc1[cb]);
-              accs = F::mfma(ax[tx], k.bs[wk][tl], accs);
-            }
-      }
-      // attention scalars: columns 0 / 1 of the scalar tile
-      if (l32 < 2) {
-        float* sdst = reinterpret_cast<float*>(smem + (l32 == 0 ? C::OFF_SI : C::OFF_SJ)) + 32 * wv + 4 * h;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sdst[(r & 3) + 8 * (r >> 2)] = accs[r];
-      }
-      // the projected tile as operand fragments of the aggregation product: k-steps 2wv, 2wv+1
-      if constexpr (!C::XAGG)
-#pragma unroll
-      for (int cb = 0; cb < DC; ++cb)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          float v[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = acc1[cb][8 * s + j];
-          u32x4 xf[C::NPX];
-          split8<FMT, C::NPX>(v, xf);
-#pragma unroll
-          for (int t = 0; t < C::NPX; ++t)
-            *reinterpret_cast<u32x4*>(smem + C::OFF_XF + ((((2 * wv + s) * DC + cb) * C::NPX + t) << 10) + lane * 16) = xf[t];
+                accs = F::mfma(ax[tx], k.bs[wk][tl], accs);
+              }
         }
-    }
+        // attention scalars: columns 0 / 1 of the scalar tile
+        if (l32 < 2) {
+          float* sdst = reinterpret_cast<float*>(smem + (l32 == 0 ? C::OFF_SI : C::OFF_SJ)) + 32 * wv + 4 * h;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sdst[(r & 3) + 8 * (r >> 2)] = accs[r];
+        }
+        // the projected tile as operand fragments of the aggregation product: k-steps 2wv, 2wv+1
+#pragma unroll
+        for (int cb = 0; cb < DC; ++cb)
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = acc1[cb][8 * s + j];
+            u32x4 xf[C::NPX];
+            split8<FMT, C::NPX>(v, xf);
+#pragma unroll
+            for (int t = 0; t < C::NPX; ++t)
+              *reinterpret_cast<u32x4*>(smem + C::OFF_XF + ((((2 * wv + s) * DC + cb) * C::NPX + t) << 10) + lane * 16) = xf[t];
+          }
+      }
+    }   // bf16 storage (not XAGG)
     __builtin_amdgcn_s_setprio(GDN_PRIO_S);
     if (b == (int)blockIdx.x) { GDN_STAMP(5) }
-    __syncthreads();                                           // B2: tile fragments + scalars visible
+    __syncthreads();                                           // B2: operand fragments + scalars visible
     if (b == (int)blockIdx.x) { GDN_STAMP(6) }
 
     // ------------------------------------------------------------ S
@@ -807,20 +895,20 @@ __global__ __launch_bounds__(64 * NT, (DC == 2 && NT >= 3 && SL <= 16 && WK == 1
     for (int cb = 0; cb < MCB; ++cb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[cb][r] = 0.f;
-    constexpr int XF_KS = (MCB * C::NPX) << 10;         // bytes of fragments per k-step
-    const int xf_lane = C::OFF_XF + lane * 16;
+    constexpr int XF_KS = MCB * C::NPX * C::XFRAG;      // bytes of fragments per k-step
+    const int xf_lane = C::OFF_XF + (C::XHALF ? h * 16 + (l32 & 15) : lane) * 16;   // (XHALF: see DCfg)
     u32x4 fa[2], fx[2][MCB][C::NPX];
     auto fetch_hi = [&](int ks, int buf) {
       fa[buf] = lds_frag(smem, arow_off + ks * 32);
 #pragma unroll
       for (int cb = 0; cb < MCB; ++cb)
 #pragma unroll
-        for (int t = 0; t < C::NPX; ++t) fx[buf][cb][t] = lds_frag(smem, xf_lane + ks * XF_KS + ((cb * C::NPX + t) << 10));
+        for (int t = 0; t < C::NPX; ++t) fx[buf][cb][t] = lds_frag(smem, xf_lane + ks * XF_KS + (cb * C::NPX + t) * C::XFRAG);
     };
     auto fetch_lo = [&](int ks, int buf) {
       fa[buf] = lds_frag(smem, arow_off + ks * 32);
 #pragma unroll
-      for (int cb = 0; cb < MCB; ++cb) fx[buf][cb][0] = lds_frag(smem, xf_lane + ks * XF_KS + ((cb * C::NPX) << 10));
+      for (int cb = 0; cb < MCB; ++cb) fx[buf][cb][0] = lds_frag(smem, xf_lane + ks * XF_KS + cb * C::NPX * C::XFRAG);
     };
     if (b == (int)blockIdx.x) { GDN_STAMP(7) }
     __builtin_amdgcn_s_setprio(GDN_PRIO_M);      // see the note at the kernel's head
@@ -1729,12 +1817,18 @@ int fused_op(int op, const DArgs& a, unsigned* plan_out, long long* bytes, hipSt
   }
   auto kern = gdn_dense_fused_kernel<NT, DC, WK, SL, FMT>;
   const int occ = blocks_per_cu(reinterpret_cast<const void*>(kern), C::THREADS, C::LDS);
+  // the kernel is compiled for C::WGS resident workgroups per CU (registers by its launch bound, LDS by DCfg): a
+  // device that holds fewer is not the one this build is for, and running thinner in silence would hide it.
+  // GDN_DENSE_MAX_OCC caps the grid at that many workgroups per CU instead (A/B runs; read once per process).
+  if (occ < C::WGS) return GDN_ERR_LAUNCH;
+  const int occ_cap = GDN_ENV_INT_ONCE("GDN_DENSE_MAX_OCC", 0);
+  const int occ_used = occ_cap > 0 ? min(occ, occ_cap) : occ;
   // A launch that cannot fill the machine twice over (one minibatch of 512 windows on 256 CUs) gets TWO windows
-  // per workgroup instead of one: every workgroup pays the prologue (~3 us: 90 plan words per lane, the zero
-  // fill), and the CU slots the thinner grid leaves free are what a concurrent launch on another stream runs
+  // per workgroup instead of one: every workgroup pays the prologue (~3 us: 84-101 plan words per lane, the zero
+  // fill of the alpha image), and the CU slots the thinner grid leaves free are what a concurrent launch on another stream runs
   // in.  Measured at 512-window launches (bench.py --coalesce 1): one stream 46.6 -> 45.1 M windows/s, two
   // streams 60.0 -> 71.3 M.  GDN_DENSE_MIN_WPW overrides (A/B runs; read once per process).
-  const int slots = cu_count() * occ;
+  const int slots = cu_count() * occ_used;
   int wpw = GDN_ENV_INT_ONCE("GDN_DENSE_MIN_WPW", 0);
   if (wpw <= 0) wpw = (a.batch > cu_count() && a.batch <= slots) ? 2 : 1;
   const int grid = max(1, min((a.batch + wpw - 1) / wpw, slots));

@@ -14,7 +14,10 @@ from test_gpu_forward_parity import random_params  # noqa: E402
 
 dev = torch.device("cuda:0")
 model = random_params(127, 15, 30, 64, seed=0).to(dev).eval()
-names = ["start", "consts loaded", "first x issued+barrier", "x stored", "B1 passed", "P done", "B2 passed",
+# The model below runs fp32 storage, whose phase list the names follow (phase X): 3 = reached B1, 4 = B1 passed +
+# fragments and attention scalars written + prefetch issued, 5 = priority dropped, reached B2.  With bf16 storage (or
+# a library older than phase X) stamps 3-5 keep their earlier meaning: 3 = x tile stored, 4 = B1 passed, 5 = P done.
+names = ["start", "consts loaded", "first x issued+barrier", "reached B1", "B1 + X done", "reached B2", "B2 passed",
          "S done", "M done", "P1 done", "E done + store", "kernel end"]
 for b in (512, 4096, 32768):
     x = torch.rand((b, 127, 15), device=dev)
