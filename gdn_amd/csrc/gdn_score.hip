@@ -772,6 +772,109 @@ __global__ __launch_bounds__(256) void score_smooth_max_kernel(
   }
 }
 
+// Normalise, smooth, top m.  The same sweep as score_smooth_max_kernel (same loads, same float64 operations in the
+// same order), but a tick keeps its m largest smoothed scores WITH their sensors instead of the maximum alone: the
+// lane's two values of the sweep and the list carried over from earlier sweeps (entry r in lane r) are the
+// candidates; m rounds of "wave maximum of (score, sensor), the owner masks it out" leave the new list, again entry
+// r in lane r.  Order: larger score first, equal scores by the lower sensor (sensors are unique among the
+// candidates, so every round has one owner).  The [n, t] table is never written.
+constexpr int TOPM_MAX = 8;
+
+__global__ __launch_bounds__(256) void score_smooth_topm_kernel(
+    const float* __restrict__ pred, const float* __restrict__ gt, const double* __restrict__ med_iqr,
+    int t, int n, int first_tick, const float* __restrict__ halo_pred, const float* __restrict__ halo_gt,
+    int m, double* __restrict__ top_scores, int* __restrict__ top_sensors) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  const int nruns = (t + RUN - 1) / RUN;
+  constexpr int NONE = 0x7fffffff;               // sensor of a masked / missing candidate (score -inf)
+  for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb) {
+    const int t0 = run * RUN, t1 = min(t, t0 + RUN);
+    double cs[RUN];                               // the carried list: entry `lane` of every tick of the run
+    int ci[RUN];
+#pragma unroll
+    for (int u = 0; u < RUN; ++u) {
+      cs[u] = -INFINITY;
+      ci[u] = NONE;
+    }
+    for (int s0 = 0; s0 < n; s0 += 128) {
+      const int sa_ = s0 + lane, sb_ = s0 + 64 + lane;
+      const bool la = sa_ < n, lb = sb_ < n;
+      const int ca = la ? sa_ : n - 1, cb = lb ? sb_ : n - 1;
+      const double meda = med_iqr[2 * ca], dena = 1.0 / (fabs(med_iqr[2 * ca + 1]) + 1e-2);
+      const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
+      const int g0 = first_tick + t0;
+      float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
+#pragma unroll
+      for (int u = 0; u < RUN + 3; ++u) {
+        const int tt = t0 - 3 + u;
+        const bool halo = tt < 0;
+        const int row = halo ? (first_tick > 0 ? 3 + tt : 0) : min(tt, t - 1);
+        const float* pp = (halo && first_tick > 0 ? halo_pred : pred) + (size_t)row * n;
+        const float* gg = (halo && first_tick > 0 ? halo_gt : gt) + (size_t)row * n;
+        pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
+      }
+      auto norm = [&](float pv, float gv, double med, double inv_den) -> double {
+        return (fabs((double)pv - (double)gv) - med) * inv_den;
+      };
+      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena) : 0.0;
+      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena) : 0.0;
+      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena) : 0.0;
+      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb) : 0.0;
+      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb) : 0.0;
+      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb) : 0.0;
+#pragma unroll
+      for (int u = 0; u < RUN; ++u) {
+        const int tick = t0 + u;
+        if (tick >= t1) continue;                  // (wave uniform)
+        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena);
+        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb);
+        double sma = 0.0, smb = 0.0;
+        if (first_tick + tick >= 3) {
+          sma = (((a3 + a2) + a1) + a0) / 4.0;
+          smb = (((b3 + b2) + b1) + b0) / 4.0;
+        }
+        a3 = a2; a2 = a1; a1 = a0;
+        b3 = b2; b2 = b1; b1 = b0;
+        // this lane's three candidates
+        double v0 = la ? sma : -INFINITY, v1 = lb ? smb : -INFINITY, v2 = cs[u];
+        int i0 = la ? sa_ : NONE, i1 = lb ? sb_ : NONE, i2 = ci[u];
+        double ns = -INFINITY;
+        int ni = NONE;
+        for (int r = 0; r < m; ++r) {              // (m is wave uniform)
+          double bs = v0;
+          int bi = i0;
+          if (v1 > bs || (v1 == bs && i1 < bi)) { bs = v1; bi = i1; }
+          if (v2 > bs || (v2 == bs && i2 < bi)) { bs = v2; bi = i2; }
+#pragma unroll
+          for (int d = 32; d >= 1; d >>= 1) {
+            const double os = __shfl_xor(bs, d);
+            const int oi = __shfl_xor(bi, d);
+            if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
+          }
+          if (bi != NONE) {                        // the owner masks its candidate out
+            if (i0 == bi) { v0 = -INFINITY; i0 = NONE; }
+            if (i1 == bi) { v1 = -INFINITY; i1 = NONE; }
+            if (i2 == bi) { v2 = -INFINITY; i2 = NONE; }
+          }
+          if (lane == r) { ns = bs; ni = bi; }
+        }
+        cs[u] = ns;
+        ci[u] = ni;
+      }
+    }
+    if (lane < m) {
+#pragma unroll
+      for (int u = 0; u < RUN; ++u) {
+        if (t0 + u < t1) {
+          top_scores[(size_t)(t0 + u) * m + lane] = cs[u];
+          top_sensors[(size_t)(t0 + u) * m + lane] = ci[u];
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -885,5 +988,22 @@ extern "C" int gdn_score_smooth_max(const float* pred, const float* gt, const do
   const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
   hipLaunchKernelGGL(score_smooth_max_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt,
                      med_iqr, t, n, first_tick, halo_pred, halo_gt, scores, anomaly);
+  return gdn_launch_status();
+}
+
+// gdn_score_smooth_max with the m largest scores of every tick and their sensors instead of the maximum alone
+// (1 <= m <= 8, m <= n): top_scores[t, m] descending, top_sensors[t, m]; equal scores by the lower sensor.  Same
+// arithmetic, first_tick and halo as gdn_score_smooth_max: with m = 1, top_scores[:, 0] is its anomaly bit for bit.
+extern "C" int gdn_score_smooth_topm(const float* pred, const float* gt, const double* med_iqr, int t, int n,
+                                     int first_tick, const float* halo_pred, const float* halo_gt, int m,
+                                     double* top_scores, int32_t* top_sensors, void* stream) {
+  if (!pred || !gt || !med_iqr || !top_scores || !top_sensors || t <= 0 || n <= 0 || first_tick < 0)
+    return GDN_ERR_ARG;
+  if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  const int runs = (t + RUN - 1) / RUN;
+  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
+  hipLaunchKernelGGL(score_smooth_topm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, med_iqr,
+                     t, n, first_tick, halo_pred, halo_gt, m, top_scores, top_sensors);
   return gdn_launch_status();
 }

@@ -18,6 +18,7 @@ import contextlib
 import ctypes
 import gc
 import os
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -471,10 +472,13 @@ class SeriesEvaluator:
 
     def __init__(self, model, x_all: torch.Tensor | None, y_all: torch.Tensor, batch: int, use_graph: bool = True,
                  want_scores: bool = False, streams: int = 3, coalesce: int = 1,
-                 series: torch.Tensor | None = None):
+                 series: torch.Tensor | None = None, top_m: int = 0):
         """`batch` = the logical minibatch of the reference's loader; `coalesce` consecutive batches
         (contiguous in the resident series) go out as ONE launch — eval results do not depend on the
-        minibatch size, and launches of a few thousand windows amortise the per-workgroup prologue."""
+        minibatch size, and launches of a few thousand windows amortise the per-workgroup prologue.
+        `top_m` >= 1 (up to 8): the score launch is gdn_score_smooth_topm — `top_scores` [T, m] float64 and
+        `top_sensors` [T, m] int32 hold every tick's m largest sensor scores and their sensors, `anomaly` is column 0
+        of `top_scores` (see `localise`).  0: exactly the launches of a plain step."""
         # `series` [N, T_raw] (datasets/TimeDataset.py:42 layout) replaces x_all: window t is
         # series[:, t : t+W], built inside the kernel — no [T, N, W] tensor (SURVEY §8f-1)
         assert (x_all is None) != (series is None), "give either the window tensor or the raw series"
@@ -494,6 +498,16 @@ class SeriesEvaluator:
         self.med_iqr = torch.empty((self.n, 2), dtype=torch.float64, device=dev)
         self.anomaly = torch.empty((self.t,), dtype=torch.float64, device=dev)
         self.scores = torch.empty((self.n, self.t), dtype=torch.float64, device=dev) if want_scores else None
+        self.top_m = int(top_m)
+        self.top_scores = self.top_sensors = None
+        if self.top_m:
+            if want_scores:
+                raise ValueError("top_m replaces the [N, T] score table: ask for one of want_scores and top_m")
+            if not 1 <= self.top_m <= min(8, self.n):
+                raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {self.n}")
+            self.top_scores = torch.empty((self.t, self.top_m), dtype=torch.float64, device=dev)
+            self.top_sensors = torch.empty((self.t, self.top_m), dtype=torch.int32, device=dev)
+            self.anomaly = self.top_scores[:, 0]
         self.graph = None
         self.fgraph = None
         self.use_graph = use_graph
@@ -557,6 +571,11 @@ class SeriesEvaluator:
         else:
             _lib.call("gdn_score_quantiles", self.pred.data_ptr(), self.y.data_ptr(), self.t, self.n,
                       self.ws.data_ptr(), self.med_iqr.data_ptr(), st)
+        if self.top_m:
+            _lib.call("gdn_score_smooth_topm", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
+                      self.t, self.n, 0, None, None, self.top_m, self.top_scores.data_ptr(),
+                      self.top_sensors.data_ptr(), st)
+            return
         _lib.call("gdn_score_smooth_max", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
                   self.t, self.n, 0, None, None,
                   None if self.scores is None else self.scores.data_ptr(), self.anomaly.data_ptr(), st)
@@ -609,6 +628,46 @@ class SeriesEvaluator:
             self.graph = self._capture(self._launch_all)
         self.graph.replay()
         return self.anomaly
+
+
+# --------------------------------------------------------------------------- localisation
+class Localisation(NamedTuple):
+    """What `localise` returns, one row per tick: the m most deviating sensors, their smoothed scores, predicted
+    and observed values, and for each of them the sensors it was reading (-1 = padding) with their attention."""
+    ticks: torch.Tensor          # [Q] int64
+    sensors: torch.Tensor        # [Q, m] int64
+    scores: torch.Tensor         # [Q, m] float64
+    predicted: torch.Tensor      # [Q, m] fp32
+    observed: torch.Tensor       # [Q, m] fp32
+    neighbours: torch.Tensor     # [Q, m, K+1] int64
+    attention: torch.Tensor      # [Q, m, K+1] fp32
+
+    def numpy(self) -> dict:
+        return {name: getattr(self, name).cpu().numpy() for name in self._fields}
+
+
+def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localisation:
+    """Which sensors deviate at `ticks` (rows of the evaluator's prediction table) and which neighbours they were
+    reading: the top-m table of the evaluator's last step (SeriesEvaluator(top_m >= 1), step() first) plus one
+    gdn_attention_at launch on its resident data.  `m` defaults to the evaluator's top_m."""
+    ev = evaluator
+    if not ev.top_m:
+        raise ValueError("localise needs an evaluator built with top_m >= 1")
+    m = ev.top_m if m is None else int(m)
+    if not 1 <= m <= ev.top_m:
+        raise ValueError(f"m = {m}: the evaluator keeps {ev.top_m} sensors per tick")
+    dev = ev.pred.device
+    ticks = torch.as_tensor(ticks, device=dev).to(torch.int64).reshape(-1)
+    if ticks.numel() and (int(ticks.min()) < 0 or int(ticks.max()) >= ev.t):
+        raise ValueError(f"ticks outside [0, {ev.t})")
+    sensors = ev.top_sensors[ticks, :m].long()
+    rows = ticks.view(-1, 1).expand(-1, m)
+    src = ev.series if ev.series is not None else ev.x
+    model = ev.model
+    nb = model.attention_neighbours()
+    att = model.attention_at(src, rows.reshape(-1), sensors.reshape(-1))
+    return Localisation(ticks, sensors, ev.top_scores[ticks, :m], ev.pred[rows, sensors], ev.y[rows, sensors],
+                        nb[sensors], att.reshape(ticks.numel(), m, nb.shape[1]))
 
 
 # --------------------------------------------------------------------------- graphed train step

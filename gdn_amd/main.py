@@ -179,7 +179,20 @@ class Main:
         labels = self.test_labels[w:]
         self.test_result = [pred, gt, labels.view(-1, 1).expand(-1, pred.shape[1])]
         _, self.val_result = harness.test(best_model, self.val_dataloader, self.device, as_tensors=True)
-        return self.get_score(self.test_result, self.val_result)
+        info = self.get_score(self.test_result, self.val_result)
+        if self.env_config.get("localise"):
+            self.save_localisation(best_model, gt, float(info[4]), self.env_config["localise"])
+        return info
+
+    def save_localisation(self, model, gt, threshold: float, path: str, m: int = 3):
+        """-localise PATH: for every test tick whose anomaly score exceeds the report's threshold, the m most
+        deviating sensors with their scores, predicted / observed values, the sensors they were reading and the
+        attention on them (harness.localise), saved as one .npz (numpy appends the suffix when PATH lacks it)."""
+        ev = harness.SeriesEvaluator(model, None, gt, batch=8192, use_graph=False, series=self.test_series,
+                                     top_m=min(m, gt.shape[1]))
+        anomaly = ev.step()
+        self.localisation = harness.localise(ev, torch.nonzero(anomaly > threshold).view(-1))
+        np.savez(path, threshold=np.float64(threshold), **self.localisation.numpy())
 
     def predict_mlp_head(self, model, n_test: int, span: int = 8192):
         """Test predictions of an out_layer_num > 1 model: forward_series on the resident series, `span` windows per
@@ -244,6 +257,8 @@ def build_parser():
     parser.add_argument("-load_model_path", help="trained model path", type=str, default="")
     parser.add_argument("-data_root", help="directory holding <dataset>/train.csv, test.csv, list.txt", type=str, default="./data")
     parser.add_argument("-no_hip_graph", help="launch every training step eagerly", action="store_true")
+    parser.add_argument("-localise", help="save the deviating sensors and their attention at the ticks above the "
+                        "report's threshold to this .npz", type=str, default="")
     return parser
 
 
@@ -261,7 +276,8 @@ def main(argv=None):
                     "decay": args.decay, "val_ratio": args.val_ratio, "topk": args.topk,
                     "hip_graph": not args.no_hip_graph}
     env_config = {"save_path": args.save_path_pattern, "dataset": args.dataset, "report": args.report,
-                  "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root}
+                  "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
+                  "localise": args.localise}
     return Main(train_config, env_config, debug=False).run()
 
 

@@ -800,3 +800,50 @@ class GDN(nn.Module):
         xlin, s_i, s_j = ops.project_fwd(x, gnn.lin.weight, c.terms, wide=wide)
         _, alpha = ops.attn_aggregate_fwd(xlin, s_i, s_j, c.graph, gnn.bias, batch, want_alpha=True, wide=wide)
         return alpha, c.graph, batch
+
+    # ------------------------------------------------------------------ attention from raw data (localisation)
+    def _attention_constants(self, what: str):
+        if self.training:
+            raise RuntimeError(f"{what} is an eval-mode query (model.eval() first)")
+        c = self._constants()
+        self._wait_ready(c)
+        self.learned_graph = c.graph.topk
+        return c, self.gnn_layers[0].gnn.lin.weight.shape[1]
+
+    def attention_neighbours(self) -> torch.Tensor:
+        """[N, K+1] int64: the source sensor of every attention slot of a target — its top-k ranks without itself,
+        then itself (the edge order of `edge_index_1`); -1 where a target has fewer than K+1 sources."""
+        c, _ = self._attention_constants("attention_neighbours")
+        g = c.graph
+        nb = getattr(g, "_neighbours", None)
+        if nb is None:
+            nb = (g.nbr.view(torch.int16).to(torch.int64) & 0xFFFF)[:, :g.k + 1]
+            slots = torch.arange(g.k + 1, device=nb.device).view(1, -1)
+            nb = torch.where(slots < g.deg.long().view(-1, 1), nb, torch.full_like(nb, -1))
+            g._neighbours = nb
+        return nb
+
+    def attention_series(self, series, first: int, batch: int, weights=None):
+        """The attention graph averaged over windows first .. first+batch-1 of the raw series [N, T] (window b =
+        series[:, first+b : first+b+W]), optionally weighted (weights [batch], e.g. a 0/1 mask of a span): returns
+        (mean [N, K+1] fp32, neighbours [N, K+1] int64, -1 = padding).  Needs the raw data, the node terms and the
+        neighbour lists only: every supported n, w, d and any OutLayer.  Eval only; fp32 data on the device."""
+        c, w = self._attention_constants("attention_series")
+        mean = ops.attention_mean(series, c.terms, c.graph, w, first=first, batch=batch, weights=weights)
+        return mean[:, :c.graph.k + 1], self.attention_neighbours()
+
+    def attention_windows(self, x, weights=None):
+        """attention_series on materialised windows x[B, N, W]: the same bits on the same windows."""
+        c, w = self._attention_constants("attention_windows")
+        if x.dim() != 3:
+            raise ValueError(f"expected windows [B, N, W], got {tuple(x.shape)}")
+        mean = ops.attention_mean(x, c.terms, c.graph, w, weights=weights)
+        return mean[:, :c.graph.k + 1], self.attention_neighbours()
+
+    def attention_at(self, series_or_windows, windows, sensors):
+        """Attention rows [Q, K+1] of the pairs (windows[q], sensors[q]): which neighbours sensor sensors[q] was
+        reading in window windows[q] (slot order: attention_neighbours()).  `series_or_windows`: the raw series
+        [N, T] (window index = its first column) or windows [B, N, W].  Eval only; fp32 data on the device."""
+        c, w = self._attention_constants("attention_at")
+        alpha = ops.attention_at(series_or_windows, windows, sensors, c.terms, c.graph, w)
+        return alpha[:, :c.graph.k + 1]

@@ -663,3 +663,120 @@ def score_smooth_max(pred, gt, med_iqr, want_scores: bool = True, first_tick: in
     _lib.call("gdn_score_smooth_max", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n,
               first_tick, _ptr(hp), _ptr(hg), _ptr(scores), _ptr(anomaly), _stream())
     return scores, anomaly
+
+
+def score_smooth_topm(pred, gt, med_iqr, m: int, first_tick: int = 0, halo_pred=None, halo_gt=None,
+                      top_scores: torch.Tensor | None = None, top_sensors: torch.Tensor | None = None):
+    """score_smooth_max that keeps the `m` largest smoothed scores of every tick and their sensors (1 <= m <= 8,
+    m <= n) instead of the maximum alone; the [n, t] table is never written.  Returns (top_scores[t, m] float64
+    descending, top_sensors[t, m] int32; equal scores in ascending sensor order); both may be preallocated."""
+    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    t, n = pred.shape
+    if top_scores is None:
+        top_scores = torch.empty((t, m), dtype=torch.float64, device=pred.device)
+    if top_sensors is None:
+        top_sensors = torch.empty((t, m), dtype=torch.int32, device=pred.device)
+    if (top_scores.shape != (t, m) or top_scores.dtype != torch.float64 or not top_scores.is_contiguous()
+            or top_sensors.shape != (t, m) or top_sensors.dtype != torch.int32 or not top_sensors.is_contiguous()):
+        raise ValueError("top_scores / top_sensors must be contiguous [t, m] float64 / int32 tensors")
+    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
+    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
+    _lib.call("gdn_score_smooth_topm", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n, first_tick,
+              _ptr(hp), _ptr(hg), m, _ptr(top_scores), _ptr(top_sensors), _stream())
+    return top_scores, top_sensors
+
+
+def _attention_source(src: torch.Tensor, name: str) -> torch.Tensor:
+    """The raw data of the attention entry points: fp32 on a HIP device.  They are fp32 throughout, so bf16 storage is
+    refused by name (as CPU tensors are) instead of being converted behind the caller's back."""
+    if not src.is_cuda:
+        raise _lib.GdnHipError(f"{name} is on {src.device}: attention from raw data needs a HIP device (no CPU fallback)")
+    if src.dtype == torch.bfloat16:
+        raise _lib.GdnHipError(f"{name} is bfloat16: attention from raw data runs on fp32 storage only (bf16 storage "
+                               "is not supported by gdn_attention_mean / gdn_attention_at)")
+    if src.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {src.dtype}")
+    if src.dim() not in (2, 3):
+        raise ValueError(f"{name}: expected the raw series [n, T] or windows [B, n, w], got {tuple(src.shape)}")
+    return src if src.is_contiguous() else src.contiguous()
+
+
+_attention_ws: dict = {}      # (device, stream) -> workspace of attention_mean, grown on demand
+
+
+def _attention_workspace(nbytes: int, device) -> torch.Tensor:
+    key = (device, _stream())
+    ws = _attention_ws.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+        _attention_ws[key] = ws
+    return ws
+
+
+def attention_mean(src, terms, graph: SensorGraph, w: int, first: int = 0, batch: int | None = None, weights=None,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """Weighted mean of the attention rows over a run of windows, from raw data (include/gdn_hip.h "attention from
+    raw data"): `src` is the raw series [n, T] (windows first .. first+batch-1, window b = columns first+b ..
+    first+b+w-1) or windows [B, n, w].  weights [batch] fp32 or None (plain mean).  Returns mean[n, pitch] fp32 in
+    the slot order of graph.nbr, padding 0; a weight sum that is not positive gives zeros.  Bitwise reproducible."""
+    src = _attention_source(src, "series" if src.dim() == 2 else "x")
+    if src.dim() == 2:
+        n, t_raw = src.shape
+        if batch is None:
+            batch = t_raw - w + 1 - first
+    else:
+        if first != 0 or (batch is not None and batch != src.shape[0]):
+            raise ValueError("windows [B, n, w] are averaged whole: first = 0, batch = B")
+        batch, n, t_raw = src.shape[0], src.shape[1], 0
+        if src.shape[2] != w:
+            raise ValueError(f"windows of {src.shape[2]} ticks given to a model of window length {w}")
+    if n != graph.n:
+        raise ValueError(f"{n} sensors given to a graph of {graph.n}")
+    if weights is not None:
+        weights = _chk(weights, name="weights").reshape(-1)
+        if weights.numel() != batch:
+            raise ValueError(f"{weights.numel()} weights for {batch} windows")
+    nbytes = _lib.load().gdn_attention_workspace_bytes(batch, n, w, graph.k)
+    ws = _attention_workspace(max(nbytes, 8), src.device)
+    if out is None:
+        out = torch.empty((n, graph.pitch), dtype=torch.float32, device=src.device)
+    _lib.call("gdn_attention_mean", _ptr(src), t_raw, first, _ptr(weights), _ptr(terms), _ptr(graph.nbr),
+              _ptr(graph.deg), batch, n, w, graph.k, _ptr(ws), _ptr(out), _stream())
+    return out
+
+
+def attention_at(src, windows, sensors, terms, graph: SensorGraph, w: int, out: torch.Tensor | None = None,
+                 check: bool = True) -> torch.Tensor:
+    """One attention row per (window, sensor) pair from raw data: `src` as attention_mean's, windows [Q] = window
+    indices (series: the window's first column), sensors [Q].  Returns alpha[Q, pitch] fp32.  `check`: compare the
+    pairs with the data's extent on the host first (one synchronisation; the kernel itself writes zeros for a pair
+    outside the data)."""
+    src = _attention_source(src, "series" if src.dim() == 2 else "x")
+    dev = src.device
+    windows = torch.as_tensor(windows, device=dev).to(torch.int64).reshape(-1).contiguous()
+    sensors = torch.as_tensor(sensors, device=dev).to(torch.int32).reshape(-1).contiguous()
+    q = windows.numel()
+    if sensors.numel() != q:
+        raise ValueError(f"{q} windows but {sensors.numel()} sensors")
+    if src.dim() == 2:
+        n, t_raw = src.shape
+        last = t_raw - w
+    else:
+        n, t_raw = src.shape[1], 0
+        last = src.shape[0] - 1
+        if src.shape[2] != w:
+            raise ValueError(f"windows of {src.shape[2]} ticks given to a model of window length {w}")
+    if n != graph.n:
+        raise ValueError(f"{n} sensors given to a graph of {graph.n}")
+    if out is None:
+        out = torch.empty((q, graph.pitch), dtype=torch.float32, device=dev)
+    if q == 0:
+        return out
+    if check:
+        if int(windows.min()) < 0 or int(windows.max()) > last:
+            raise ValueError(f"window indices outside [0, {last}]")
+        if int(sensors.min()) < 0 or int(sensors.max()) >= n:
+            raise ValueError(f"sensor indices outside [0, {n})")
+    _lib.call("gdn_attention_at", _ptr(src), t_raw, _ptr(windows), _ptr(sensors), q, _ptr(terms), _ptr(graph.nbr),
+              _ptr(graph.deg), n, w, graph.k, _ptr(out), _stream())
+    return out

@@ -606,6 +606,42 @@ int gdn_score_smooth_max(const float* pred, const float* gt, const double* med_i
                          int t, int n, int first_tick, const float* halo_pred,
                          const float* halo_gt, double* scores, double* anomaly, void* stream);
 
+/* gdn_score_smooth_topm: gdn_score_smooth_max that keeps, per tick, the m largest smoothed scores and their sensors
+ * (which sensor deviates) instead of the maximum alone: top_scores[t, m] float64 descending, top_sensors[t, m] int32;
+ * equal scores come in ascending sensor order (the first 3 ticks of the series, all 0: sensors 0 .. m-1).  Same
+ * float64 arithmetic in the same order, same first_tick / halo meaning; with m = 1, top_scores[:, 0] equals the
+ * anomaly of gdn_score_smooth_max bit for bit.  The [n, t] table is never written.  1 <= m <= 8 and m <= n, else
+ * GDN_ERR_UNSUPPORTED.                                                                                          */
+int gdn_score_smooth_topm(const float* pred, const float* gt, const double* med_iqr,
+                          int t, int n, int first_tick, const float* halo_pred,
+                          const float* halo_gt, int m, double* top_scores, int32_t* top_sensors, void* stream);
+
+/* ---- attention from raw data -----------------------------------------------------------
+ * The attention weights of models/graph_layer.py:91-110 (att_weight_1) without the projection: the logit is
+ * separable ("per-forward constants" above), so alpha depends on the raw window, node_terms and the neighbour lists
+ * only — not on d, xlin or the head.  fp32 VALU throughout: fp32's own range, no guard.  Arithmetic: s_i / s_j =
+ * fp32 dot product of the window row with a_i / a_j, + c_i / c_j; LeakyReLU(0.2); max-subtract, exp, / (sum + 1e-16)
+ * over the target's valid slots.  Rows have pitch = gdn_nbr_pitch(k) slots in the order of `nbr` (the top-k ranks
+ * without self, then self); padding slots are written as 0.
+ * Addressing of x: t_raw > 0: the raw series [n, t_raw], window b = columns first+b .. first+b+w-1 (gdn_attention_at:
+ * windows[q] .. windows[q]+w-1); t_raw == 0: windows [batch, n, w] (first must be 0; gdn_attention_at: window index
+ * windows[q]).  Both give the same bits on the same windows.
+ *   gdn_attention_mean  mean[n, pitch] = sum_b weights[b] alpha_b / sum_b weights[b] over `batch` windows (weights ==
+ *                       NULL: the plain mean; a weight sum that is not positive: zeros).  Per-workgroup float64
+ *                       partial blocks in `workspace` (gdn_attention_workspace_bytes, no initialisation needed) are
+ *                       added in block order by a second launch: no floating-point atomics, bitwise reproducible.
+ *   gdn_attention_at    alpha[q, pitch]: one row per pair (windows[q], sensors[q]); a pair outside the data (negative
+ *                       window, window past the series, sensor outside [0, n)) gets a row of zeros.
+ * 1 <= w <= 1024, 1 <= k <= n <= 4096, k + 1 <= 1024, else GDN_ERR_UNSUPPORTED (workspace bytes: 0); windows that
+ * do not fit the series, or first != 0 with t_raw == 0: GDN_ERR_ARG.  All decided before any launch.           */
+long long gdn_attention_workspace_bytes(int batch, int n, int w, int k);
+int gdn_attention_mean(const float* x, long long t_raw, long long first, const float* weights,
+                       const float* node_terms, const uint16_t* nbr, const int32_t* deg,
+                       int batch, int n, int w, int k, void* workspace, float* mean, void* stream);
+int gdn_attention_at(const float* x, long long t_raw, const int64_t* windows, const int32_t* sensors, int q,
+                     const float* node_terms, const uint16_t* nbr, const int32_t* deg,
+                     int n, int w, int k, float* alpha, void* stream);
+
 /* gdn_terms_bwd with accumulate_emb != 0: d_emb += (instead of =) — the head's share of the embedding
  * gradient already sits in d_emb (gdn_head_train_bwd), so both land in one gradient slot without an add
  * kernel.                                                                                              */
