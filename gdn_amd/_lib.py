@@ -96,6 +96,10 @@ SIGNATURES = {
     "gdn_attention_workspace_bytes": [_c_int] * 4,
     "gdn_attention_mean": [_p, ctypes.c_longlong, ctypes.c_longlong] + [_p] * 4 + [_c_int] * 4 + [_p, _p, _p],
     "gdn_attention_at": [_p, ctypes.c_longlong, _p, _p, _c_int, _p, _p, _p] + [_c_int] * 3 + [_p, _p],
+    "gdn_windows_gather": [_p, _c_int, ctypes.c_longlong, _p, ctypes.c_longlong, _p, ctypes.c_longlong, _c_int, _c_int,
+                           _p, _p, _p],
+    "gdn_epoch_advance": [_p, _p, _p, ctypes.c_longlong, _p],
+    "gdn_mse_batch_means": [_p, _p, ctypes.c_longlong, _c_int, ctypes.c_longlong, _p, _p, _p, _p],
 }
 
 ERRORS = {-1: "GDN_ERR_ARG (null pointer or non-positive dimension)",

@@ -687,11 +687,12 @@ class AutogradTrainStep:
     tail of the first graph, averaging + unpacking the head of the second).
 
     `x` / `y` are the static input buffers: copy each minibatch into them, call `step()`, read
-    `loss` (a device scalar) whenever convenient."""
+    `loss` (a device scalar) whenever convenient.  `pre` / `post`: see NativeTrainStep."""
 
     def __init__(self, model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
-                 split: bool | None = None, wide: bool = False):
+                 split: bool | None = None, wide: bool = False, pre=None, post=None):
         self.wide = bool(wide)
+        self.pre, self.post = pre, post
         p0 = next(model.parameters())
         if not p0.is_cuda:
             raise RuntimeError("GraphedTrainStep needs the model on a HIP device")
@@ -714,6 +715,17 @@ class AutogradTrainStep:
         import os
         self._torch_mse = bool(os.environ.get("GDN_TORCH_MSE"))
         self._dbg = None                                 # diagnostic snapshot buffers (tools/probe_mse_replay.py)
+
+    # the two halves of a step with the caller's hooks: what an eager step issues and what the graphs hold
+    def _first(self):
+        if self.pre is not None:
+            self.pre()
+        self._forward_backward()
+
+    def _second(self):
+        self._update()
+        if self.post is not None:
+            self.post()
 
     # the two halves of a step; `loss` is written in place so it survives replays
     def _forward_backward(self):
@@ -765,15 +777,15 @@ class AutogradTrainStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(3):
-                self._forward_backward()
+                self._first()
                 self._all_reduce()
-                self._update()
+                self._second()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
         graphs = []
         if self._split:
-            for fn in (self._forward_backward, self._update):
+            for fn in (self._first, self._second):
                 g = torch.cuda.CUDAGraph()
                 with capture(g, pool=pool):
                     fn()
@@ -781,8 +793,8 @@ class AutogradTrainStep:
         else:
             g = torch.cuda.CUDAGraph()
             with capture(g, pool=pool):
-                self._forward_backward()
-                self._update()
+                self._first()
+                self._second()
             graphs.append(g)
         with torch.no_grad():
             for t, s in zip(tensors, saved):
@@ -793,15 +805,20 @@ class AutogradTrainStep:
                         v.zero_()
         self._graphs = graphs
 
+    def prepare(self):
+        """Capture now (the first `step()` otherwise does): a caller whose hooks keep state of their own
+        (harness.SeriesTrainer's cursor) resets it after the warm-up steps of the capture have moved it."""
+        if self.use_graph and self._graphs is None:
+            self._capture()
+
     def step(self):
         if not self.use_graph:
-            self._forward_backward()
+            self._first()
             if self._split:
                 self._all_reduce()
-            self._update()
+            self._second()
             return self.loss
-        if self._graphs is None:
-            self._capture()
+        self.prepare()
         self._graphs[0].replay()
         if self._split:
             self._all_reduce()                           # the only eager op of a multi-rank step
@@ -875,7 +892,12 @@ class NativeTrainStep:
 
     The launches of a step are captured once in a HIP graph (two graphs around the all-reduce with >1 rank).
     `x` / `y` are the static input buffers; `loss` a device scalar.  BatchNorm uses per-rank batch
-    statistics (standard DDP)."""
+    statistics (standard DDP).
+
+    `pre` / `post`: optional callables that issue launches on the current stream immediately before the step's first
+    launch and immediately after the optimizer's — in eager mode, in the warm-up steps of the capture and INSIDE the
+    captured graph (with two graphs: `pre` in the first, `post` in the second).  harness.SeriesTrainer hangs the
+    window gather and the cursor / loss bookkeeping of an epoch there.  None: exactly the launches of a plain step."""
 
     BETAS, EPS = (0.9, 0.999), 1e-8
 
@@ -894,9 +916,10 @@ class NativeTrainStep:
         return model.out_layer_num == 1 or ops.mlp_train_supported(model.out_layer, model.embedding.weight.shape[1], 2)
 
     def __init__(self, model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
-                 split: bool | None = None, seed: int | None = None, wide: bool = False):
+                 split: bool | None = None, seed: int | None = None, wide: bool = False, pre=None, post=None):
         from . import _lib
         self._lib = _lib
+        self.pre, self.post = pre, post
         # inputs beyond the 16-bit operand range of the matrix-core kernels: the `_wide` (fp32 row-gather) entry
         # points throughout, decided by the caller from its data (harness.train: first batch / config["wide"])
         self.wide = bool(wide)
@@ -994,6 +1017,16 @@ class NativeTrainStep:
         return float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
 
     # the two halves of a step ---------------------------------------------------------------------------------
+    def _first(self):
+        if self.pre is not None:
+            self.pre()
+        self._forward_backward()
+
+    def _second(self):
+        self._adam()
+        if self.post is not None:
+            self.post()
+
     def _forward_backward(self):
         call, ws, m = self._lib.call, self.ws, self.model
         st = torch.cuda.current_stream().cuda_stream
@@ -1109,9 +1142,9 @@ class NativeTrainStep:
         tensors = [self.flat_p, self.exp_avg, self.exp_avg_sq, self.state] + list(self.model.buffers())
         saved = [t.detach().clone() for t in tensors]
         for _ in range(2):
-            self._forward_backward()
+            self._first()
             self._all_reduce()
-            self._adam()
+            self._second()
         torch.cuda.synchronize()
         with torch.no_grad():
             for t, s_ in zip(tensors, saved):
@@ -1120,7 +1153,7 @@ class NativeTrainStep:
         torch.cuda.synchronize()
         graphs = []
         if self._split:
-            for fn in (self._forward_backward, self._adam):
+            for fn in (self._first, self._second):
                 g_ = torch.cuda.CUDAGraph()
                 with capture(g_):
                     fn()
@@ -1128,20 +1161,24 @@ class NativeTrainStep:
         else:
             g_ = torch.cuda.CUDAGraph()
             with capture(g_):
-                self._forward_backward()
-                self._adam()
+                self._first()
+                self._second()
             graphs.append(g_)
         self._graphs = graphs
 
+    def prepare(self):
+        """Capture now (the first `step()` otherwise does); see AutogradTrainStep.prepare."""
+        if self.use_graph and self._graphs is None:
+            self._capture()
+
     def step(self):
         if not self.use_graph:
-            self._forward_backward()
+            self._first()
             if self._split:
                 self._all_reduce()
-            self._adam()
+            self._second()
         else:
-            if self._graphs is None:
-                self._capture()
+            self.prepare()
             self._graphs[0].replay()
             if self._split:
                 self._all_reduce()
@@ -1151,16 +1188,232 @@ class NativeTrainStep:
 
 
 def GraphedTrainStep(model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
-                     split: bool | None = None, native: bool | None = None, wide: bool | None = None):
+                     split: bool | None = None, native: bool | None = None, wide: bool | None = None, pre=None,
+                     post=None):
     """The captured training step: `NativeTrainStep` when the model and its shape allow it (plain nn.Dropout, an
     OutLayer and a sensor count the training kernels take), else `AutogradTrainStep`.  `native=False` forces the
-    autograd form.  `wide`: the inputs exceed the 16-bit operand range (None: model.operand_range == "wide")."""
+    autograd form.  `wide`: the inputs exceed the 16-bit operand range (None: model.operand_range == "wide").
+    `pre` / `post`: launches issued (and captured) right before and right after the step, see NativeTrainStep."""
     if native is None:
         native = NativeTrainStep.applicable(model)
     if wide is None:
         wide = getattr(model, "operand_range", "auto") == "wide"
     if native:
         return NativeTrainStep(model, batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph, split=split,
-                               wide=wide)
+                               wide=wide, pre=pre, post=post)
     return AutogradTrainStep(model, batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph, split=split,
-                             wide=wide)
+                             wide=wide, pre=pre, post=post)
+
+
+# --------------------------------------------------------------------------- epochs from the resident series
+def epoch_order(loader) -> torch.Tensor:
+    """The dataset positions one epoch of `loader` (a torch DataLoader, num_workers = 0) would yield, as ONE int64
+    tensor, drawing from torch's generators exactly what iterating the loader draws: the iterator's base seed
+    (torch/utils/data/dataloader.py, _BaseDataLoaderIter.__init__) and then whatever the batch sampler draws (a
+    RandomSampler: the seed of its permutation) — so a run that asks for the order sees the same shuffles, and leaves
+    the generator in the same state, as a run that iterates.  Milliseconds per epoch instead of per batch: no
+    collate of `batch` zero-dimensional tensors."""
+    torch.empty((), dtype=torch.int64).random_(generator=loader.generator)
+    order = [i for b in loader.batch_sampler for i in b]
+    return torch.tensor(order, dtype=torch.int64)
+
+
+def _window_ticks(source):
+    """(target ticks int64 [T], DataLoader or None) of what `train_series` / `Main` hand over: an index loader
+    (`main.IndexLoader`: `.loader` over a TensorDataset of window indices, `.windows.starts` their ticks) or a plain
+    tensor / sequence of target ticks (trained or scored in the given order, nothing drawn)."""
+    if source is None:
+        return None, None
+    if hasattr(source, "loader") and hasattr(source, "windows"):
+        idx = source.loader.dataset.tensors[0]
+        starts = source.windows.starts
+        return starts[idx.to(starts.device)], source.loader
+    return torch.as_tensor(source).to(torch.int64).reshape(-1), None
+
+
+_VALIDATE_CHUNK_BYTES = 256 << 20       # window buffer of validate_series: a few thousand windows at the usual shapes
+_validate_x: dict = {}                  # (device, floats) -> gathered-window buffer, reused across calls
+
+
+def validate_series(model, series, starts, batch: int, wide=None):
+    """harness.test's loss and outputs for the windows of target ticks `starts` of a series [n, T] resident on the
+    device, with nothing but launches per chunk: (val_loss, pred [Tv, n], gt [Tv, n]).
+
+    A chunk (a multiple of `batch`, a few thousand windows — eval results do not depend on the minibatch) is cut by
+    ONE gdn_windows_gather into a cached buffer, its targets straight into their rows of `gt`, and goes through
+    `model.forward_into` into its rows of `pred`; ONE gdn_mse_batch_means then forms F.mse_loss of every logical
+    minibatch and test.py's sum(losses) / len(losses), and one float64 comes back to the host.  An OutLayer the fast
+    path refuses (GDN.mlp_fast_path_supported) goes through `model(x)` on the gathered chunk."""
+    model.eval()
+    series = ops._chk(series, name="series")
+    n, series_len = series.shape
+    w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+    dev = series.device
+    starts = ops.check_window_table(starts, w, series_len).to(dev).contiguous()
+    tv = int(starts.numel())
+    pred = torch.empty((tv, n), dtype=torch.float32, device=dev)
+    gt = torch.empty((tv, n), dtype=torch.float32, device=dev)
+    if tv == 0:
+        return 0.0, pred, gt
+    if wide is None:
+        wide = model.operand_range == "wide" or (model.operand_range == "auto" and model.input_exceeds_limit(series))
+    fast = model.out_layer_num == 1 or model.mlp_fast_path_supported()
+    per_window = n * w * 4
+    chunk = max(1, min(4096, _VALIDATE_CHUNK_BYTES // per_window) // batch) * batch
+    chunk = min(chunk, (tv + batch - 1) // batch * batch)
+    key = (dev, chunk * n * w)
+    xbuf = _validate_x.get(key)
+    if xbuf is None:
+        xbuf = _validate_x[key] = torch.empty((chunk * n * w,), dtype=torch.float32, device=dev)
+    before = model.operand_range
+    for s in range(0, tv, chunk):
+        rows = min(chunk, tv - s)
+        x = xbuf[: rows * n * w].view(rows, n, w)
+        ops.windows_gather(series, starts, rows, w, x, gt[s:s + rows], first=s)
+        if fast:
+            model.forward_into(x, pred[s:s + rows], wide=wide)
+        else:
+            model.operand_range = "wide" if wide else "narrow"
+            try:
+                with torch.no_grad():
+                    pred[s:s + rows].copy_(model(x, None))
+            finally:
+                model.operand_range = before
+    _means, mean = ops.mse_batch_means(pred, gt, batch)
+    return float(mean.item()), pred, gt
+
+
+class SeriesTrainer:
+    """An epoch of harness.train as `len(order) // batch` graph replays with no host work between them.
+
+    Owns a `GraphedTrainStep` whose `pre` hook is ONE gdn_windows_gather launch — it reads the cursor and cuts the
+    step's windows from the resident series straight into the step's static `x` / `y` — and whose `post` hook is
+    gdn_epoch_advance (the step's loss into its row of the loss table, the cursor on); the device copy of the epoch's
+    table of target ticks (capacity fixed here, so the pointers a captured graph holds stay valid); the cursor; the
+    loss table.  `train_starts`: the target tick of every training window (SeriesWindows.starts[train indices])."""
+
+    def __init__(self, model, series, w: int, train_starts, batch: int, lr: float = 1e-3, weight_decay: float = 0.0,
+                 wide: bool = False, use_graph: bool = True, native: bool | None = None):
+        self.series = ops._chk(series, name="series")
+        dev = self.series.device
+        self.model, self.w, self.batch, self.wide = model, int(w), int(batch), bool(wide)
+        self.train_starts = ops.check_window_table(train_starts, self.w, self.series.shape[1]).to(dev)
+        cap = int(self.train_starts.numel())
+        self.full_steps = cap // self.batch
+        self.table = torch.zeros((max(1, cap),), dtype=torch.int64, device=dev)
+        self.cursor = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.loss_table = torch.zeros((self.full_steps + 1,), dtype=torch.float32, device=dev)
+        self._tail = None                                # (x, y) of the ragged last batch, by its size
+        self.step = GraphedTrainStep(model, self.batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph,
+                                     native=native, wide=self.wide, pre=self._gather, post=self._advance)
+        self.optimizer = self.step.optimizer
+
+    # the hooks: static arguments only (they are captured with the step)
+    def _gather(self):
+        # (count = the table's capacity: a captured launch cannot learn an epoch's length, and epoch() replays exactly
+        # len(order) // batch times, so no replay reaches an entry beyond the epoch)
+        ops.windows_gather(self.series, self.table, self.batch, self.w, self.step.x, self.step.y, cursor=self.cursor)
+
+    def _advance(self):
+        ops.epoch_advance(self.step.loss, self.cursor, self.loss_table)
+
+    def epoch(self, order) -> list:
+        """Train on windows train_starts[order] in that order; returns the step losses (ONE device-to-host read)."""
+        order = torch.as_tensor(order).to(torch.int64).reshape(-1)
+        total = int(order.numel())
+        if total > self.table.numel():
+            raise ValueError(f"an epoch of {total} windows on a trainer built for {self.table.numel()}")
+        if total and (int(order.min()) < 0 or int(order.max()) >= self.train_starts.numel()):
+            raise ValueError(f"window positions outside [0, {self.train_starts.numel()})")
+        dev = self.series.device
+        self.table[:total].copy_(self.train_starts[order.to(dev)])
+        full, rest = divmod(total, self.batch)
+        self.model.train()
+        # the warm-up steps of the capture run on this epoch's first windows and move the cursor: capture first, then
+        # put the cursor at the epoch's start
+        if full:
+            self.step.prepare()
+        self.cursor.zero_()
+        for _ in range(full):
+            self.step.step()
+        steps = full
+        if rest:
+            # the ragged last batch: today's eager branch of harness.train on windows the same kernel gathered
+            if self._tail is None or self._tail[0].shape[0] != rest:
+                n = self.series.shape[0]
+                self._tail = (torch.empty((rest, n, self.w), dtype=torch.float32, device=dev),
+                              torch.empty((rest, n), dtype=torch.float32, device=dev))
+            x, y = self._tail
+            ops.windows_gather(self.series, self.table, rest, self.w, x, y, first=full * self.batch, count=total)
+            before = self.model.operand_range
+            self.model.operand_range = "wide" if self.wide else "narrow"
+            try:
+                self.optimizer.zero_grad()
+                out = self.model(x, None)
+                loss = F.mse_loss(out, y, reduction="mean")
+                loss.backward()
+                sync_gradients(self.model)
+                self.optimizer.step()
+            finally:
+                self.model.operand_range = before
+            self.loss_table[full].copy_(loss.detach())
+            steps += 1
+        return self.loss_table[:steps].tolist() if steps else []
+
+
+def train_series(model=None, save_path="", config=None, series=None, w: int | None = None, train_loader_or_indices=None,
+                 val_starts=None, use_graph: bool | None = None):
+    """harness.train's loop (same optimizer, loss, `wide` decision, checkpoint rule, 15-epoch early stop, returned
+    list of step losses) for a series [n, T] resident on the device: every epoch is one upload of the window table and
+    a run of graph replays (SeriesTrainer), every validation pass `validate_series`.
+
+    `train_loader_or_indices` / `val_starts`: an index loader (`main.IndexLoader`) — its DataLoader is asked for the
+    epoch's order (`epoch_order`: the shuffles and the generator's state are those of a run that iterates it, the
+    validation loader's per-epoch draw included) — or a tensor of target ticks, taken in the given order.
+    `use_graph` None: config["hip_graph"], default True.  One process only."""
+    from ._lib import GdnHipError
+    if world()[1] > 1:
+        raise GdnHipError("train_series runs in one process: sharding an epoch of the resident series across ranks is "
+                          "not implemented (harness.train with per-rank loaders does data-parallel training)")
+    config = config or {}
+    if use_graph is None:
+        use_graph = bool(config.get("hip_graph", True))
+    w = int(w if w is not None else model.gnn_layers[0].gnn.lin.weight.shape[1])
+    train_starts, train_loader = _window_ticks(train_loader_or_indices)
+    val_ticks, val_loader = _window_ticks(val_starts)
+    batch = int(train_loader.batch_size if train_loader is not None else config.get("batch", 128))
+    val_batch = int(val_loader.batch_size if val_loader is not None else batch)
+    range_before = getattr(model, "operand_range", "auto")
+    wide = config.get("wide", None)
+    if range_before != "auto":
+        wide = range_before == "wide"
+    elif wide is None:
+        # the resident series is there to be looked at: all of it, not the first batch (the weights move: margin)
+        wide = model.train().input_exceeds_limit(series, margin=16.0)
+    trainer = None
+    losses, min_loss, stale = [], 1e8, 0
+    for _epoch in range(config.get("epoch", 1)):
+        order = epoch_order(train_loader) if train_loader is not None else torch.arange(train_starts.numel())
+        if trainer is None:
+            trainer = SeriesTrainer(model, series, w, train_starts, min(batch, max(1, int(train_starts.numel()))),
+                                    lr=0.001, weight_decay=config.get("decay", 0), wide=wide, use_graph=use_graph)
+        step_losses = trainer.epoch(order)
+        losses.extend(step_losses)
+        acc = float(sum(step_losses))
+        if val_ticks is not None:
+            if val_loader is not None:
+                epoch_order(val_loader)                  # what iterating the validation loader draws
+            val_loss, _pred, _gt = validate_series(model, series, val_ticks, val_batch)
+            if val_loss < min_loss:
+                if save_path:
+                    torch.save(model.state_dict(), save_path)
+                min_loss, stale = val_loss, 0
+            else:
+                stale += 1
+            if stale >= 15:
+                break
+        elif acc < min_loss:
+            if save_path:
+                torch.save(model.state_dict(), save_path)
+            min_loss = acc
+    return losses

@@ -11,9 +11,10 @@ and prints `F1 score / precision / recall`.
 What is different is WHERE the data lives: the two series stay in HBM as [N, T]
 tensors and every window is cut from them on the device —
   * training batches: the DataLoader of main.py:128-148 is kept for what it decides (the random
-    contiguous validation block, the shuffled order: same RNG draws as the reference), but it yields
-    window INDICES; the [batch, N, W] block is gathered from the resident series (stride
-    `slide_stride`, datasets/TimeDataset.py:44-58) by one device op;
+    contiguous validation block, the shuffled order: same RNG draws as the reference), but it is only
+    asked for an epoch's ORDER (harness.epoch_order); the [batch, N, W] block of every step is cut
+    from the resident series (stride `slide_stride`, datasets/TimeDataset.py:44-58) by a kernel
+    inside the captured step (harness.train_series), and the validation loss is formed on the device;
   * evaluation: `GDN.forward_series` builds the stride-1 windows inside the kernel; predictions, the
     anomaly scores and the threshold sweep never leave the device (gdn_amd/evaluate.py).
 The reference's `TimeDataset` would materialise a W-fold copy of both series on the host."""
@@ -162,9 +163,17 @@ class Main:
             # the resident training series is looked at once and the step runs on the fp32 row-gather kernels when
             # it exceeds the 16-bit operand range of the matrix-core ones (include/gdn_hip.h "range guard")
             self.train_config.setdefault("wide", self.model.train().input_exceeds_limit(self.train_series, margin=16.0))
-            self.train_log = harness.train(self.model, model_save_path, config=self.train_config,
-                                           train_dataloader=self.train_dataloader, val_dataloader=self.val_dataloader,
-                                           use_graph=bool(self.train_config.get("hip_graph", True)))
+            if self.train_config.get("hip_graph", True):
+                # epochs on the device (harness.train_series): the loaders decide the order (same draws), the windows
+                # are cut inside the captured step, the validation loss is formed on the device
+                self.train_log = harness.train_series(self.model, model_save_path, config=self.train_config,
+                                                      series=self.train_series, w=self.train_config["slide_win"],
+                                                      train_loader_or_indices=self.train_dataloader,
+                                                      val_starts=self.val_dataloader)
+            else:       # -no_hip_graph: the eager loop over the loaders, as before
+                self.train_log = harness.train(self.model, model_save_path, config=self.train_config,
+                                               train_dataloader=self.train_dataloader,
+                                               val_dataloader=self.val_dataloader, use_graph=False)
         self.model.load_state_dict(torch.load(model_save_path, weights_only=True))
         best_model = self.model.to(self.device).eval()
         # test.py's loop with the windows built in the kernel from the resident series (stride 1)
@@ -178,7 +187,11 @@ class Main:
         gt = self.test_series[:, w:].t().contiguous()
         labels = self.test_labels[w:]
         self.test_result = [pred, gt, labels.view(-1, 1).expand(-1, pred.shape[1])]
-        _, self.val_result = harness.test(best_model, self.val_dataloader, self.device, as_tensors=True)
+        val_ticks = self.train_dataset.starts[self.val_dataloader.loader.dataset.tensors[0].to(self.device)]
+        harness.epoch_order(self.val_dataloader.loader)     # (the draw of iterating the loader, as test() did)
+        _, val_pred, val_gt = harness.validate_series(best_model, self.train_series, val_ticks,
+                                                      self.train_config["batch"])
+        self.val_result = [val_pred, val_gt, self.train_dataset.labels[val_ticks].view(-1, 1).expand(-1, val_pred.shape[1])]
         info = self.get_score(self.test_result, self.val_result)
         if self.env_config.get("localise"):
             self.save_localisation(best_model, gt, float(info[4]), self.env_config["localise"])

@@ -780,3 +780,55 @@ def attention_at(src, windows, sensors, terms, graph: SensorGraph, w: int, out: 
     _lib.call("gdn_attention_at", _ptr(src), t_raw, _ptr(windows), _ptr(sensors), q, _ptr(terms), _ptr(graph.nbr),
               _ptr(graph.deg), n, w, graph.k, _ptr(out), _stream())
     return out
+
+
+# --------------------------------------------------------------------------- epochs from the resident series
+def check_window_table(starts: torch.Tensor, w: int, series_len: int) -> torch.Tensor:
+    """A table of target ticks for windows_gather: int64, flat, every tick inside [w, series_len).  Looked at ONCE, when
+    the table is uploaded (one synchronisation for a device tensor); the kernel itself writes zeros for a tick outside
+    the data."""
+    starts = torch.as_tensor(starts).to(torch.int64).reshape(-1)
+    if starts.numel() and (int(starts.min()) < w or int(starts.max()) >= series_len):
+        raise ValueError(f"target ticks outside [{w}, {series_len})")
+    return starts
+
+
+def windows_gather(series, starts, batch: int, w: int, x_out, y_out, first: int = 0, cursor=None, count: int | None = None):
+    """x_out[b, i, :] = series[i, t-w : t], y_out[b, i] = series[i, t] with t = starts[first + cursor[0] * batch + b]
+    (cursor None: starts[first + b]) for b < batch: datasets/TimeDataset.py's windows of a series [n, T] resident on the
+    device.  `starts` int64 on the device (check_window_table), `count` = its valid entries (default: all); entries
+    beyond it give windows of zeros.  x_out / y_out: contiguous fp32 with room for [batch, n, w] / [batch, n]."""
+    series = _chk(series, name="series")
+    if series.dim() != 2:
+        raise ValueError(f"expected the raw series [n, T], got {tuple(series.shape)}")
+    n, series_len = series.shape
+    starts = _chk(starts, torch.int64, name="starts")
+    if cursor is not None:
+        cursor = _chk(cursor, torch.int64, name="cursor")
+    for t, need, name in ((x_out, batch * n * w, "x_out"), (y_out, batch * n, "y_out")):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need:
+            raise ValueError(f"{name}: a contiguous fp32 device tensor of at least {need} elements is needed")
+    _lib.call("gdn_windows_gather", _ptr(series), n, series_len, _ptr(starts), starts.numel() if count is None else count,
+              _ptr(cursor), first, batch, w, _ptr(x_out), _ptr(y_out), _stream())
+    return x_out, y_out
+
+
+def epoch_advance(loss, cursor, loss_table):
+    """loss_table[cursor[0]] = loss (when the row exists); cursor[0] += 1.  One launch, stream-ordered after the step."""
+    _lib.call("gdn_epoch_advance", _ptr(_chk(loss, name="loss")), _ptr(_chk(cursor, torch.int64, name="cursor")),
+              _ptr(_chk(loss_table, name="loss_table")), loss_table.numel(), _stream())
+
+
+def mse_batch_means(pred, y, batch: int, batch_means=None, mean=None):
+    """(batch_means [ceil(rows / batch)], mean []) float64: F.mse_loss of every logical minibatch of `batch` rows of
+    pred / y [rows, n] (the last one ragged) and test.py's sum(losses) / len(losses).  Bitwise reproducible."""
+    pred, y = _chk(pred, name="pred"), _chk(y, name="y")
+    if pred.shape != y.shape or pred.dim() != 2:
+        raise ValueError(f"expected pred and y of one shape [rows, n], got {tuple(pred.shape)} and {tuple(y.shape)}")
+    rows, n = pred.shape
+    if batch_means is None:
+        batch_means = torch.empty(((rows + batch - 1) // batch,), dtype=torch.float64, device=pred.device)
+    if mean is None:
+        mean = torch.empty((), dtype=torch.float64, device=pred.device)
+    _lib.call("gdn_mse_batch_means", _ptr(pred), _ptr(y), rows, n, batch, _ptr(batch_means), _ptr(mean), None, _stream())
+    return batch_means, mean

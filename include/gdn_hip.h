@@ -651,6 +651,31 @@ int gdn_terms_bwd_acc(const float* lin_w, const float* att_i, const float* att_j
                       float* d_att_i, float* d_att_j, float* d_att_em_i, float* d_att_em_j,
                       float* d_emb, int accumulate_emb, void* stream);
 
+/* ---- epochs from the resident series ------------------------------------------------------
+ * Training and validation windows cut on the device from the raw series [n, series_len] (datasets/TimeDataset.py:
+ * window of target tick t = columns t-w .. t-1, target = column t), so that an epoch is a run of graph replays with
+ * no host work between them.  Additive entry points: the ABI version does not move.
+ *   gdn_windows_gather   table entry e = first + (cursor ? cursor[0] * batch : 0) + b names tick t = starts[e];
+ *                        x_out[b, i, :] = series[i, t-w : t], y_out[b, i] = series[i, t] for b < batch.  An entry with
+ *                        e >= count, or a tick outside [w, series_len), gets a window of zeros and reads nothing.
+ *                        `cursor` (device, may be NULL) is only read: advancing it is gdn_epoch_advance's launch.
+ *                        1 <= w <= 1024, 1 <= n <= 4096 (else GDN_ERR_UNSUPPORTED), any alignment of t; offsets
+ *                        into the series are 64-bit.
+ *   gdn_epoch_advance    one thread: r = cursor[0]; if (r < table_len) loss_table[r] = loss[0]; cursor[0] = r + 1.
+ *                        Stream-ordered after the step whose gather read the cursor.
+ *   gdn_mse_batch_means  batch_means[q] = mean((pred - y)^2) over rows [q*batch, min(rows, (q+1)*batch)) of
+ *                        pred / y [rows, n] (difference in fp32, accumulation in float64 in a fixed order), for
+ *                        q < ceil(rows / batch); mean[0] = their plain average, added in batch order (test.py:
+ *                        sum(losses) / len(losses)).  No atomics: bitwise reproducible.  `workspace` is not used
+ *                        (may be NULL).
+ * Null required pointers, batch < 1, count < 1, rows < 1, table_len < 1: GDN_ERR_ARG; all decided before any launch. */
+int gdn_windows_gather(const float* series, int n, long long series_len, const int64_t* starts, long long count,
+                       const int64_t* cursor, long long first, int batch, int w, float* x_out, float* y_out,
+                       void* stream);
+int gdn_epoch_advance(const float* loss, int64_t* cursor, float* loss_table, long long table_len, void* stream);
+int gdn_mse_batch_means(const float* pred, const float* y, long long rows, int n, long long batch,
+                        double* batch_means, double* mean, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
