@@ -371,9 +371,7 @@ class ShardedEvaluator:
 
     def _hip_forward(self, start, stop):
         if self._wide is None:      # range of the resident shard, looked at once
-            m = self.model
-            self._wide = (m.operand_range == "wide" and self.x.dtype != torch.bfloat16) or (
-                m.operand_range == "auto" and m.input_exceeds_limit(self.x))
+            self._wide = self.model.wide_for(self.x)
         self.model.forward_into(self.x[start:stop], self.pred[start:stop], wide=self._wide)
 
     # A step = nchunks x [forward + keys of the chunk | async all-to-all of its key rows] -> [select of my sensors'
@@ -482,14 +480,12 @@ class SeriesEvaluator:
         # `series` [N, T_raw] (datasets/TimeDataset.py:42 layout) replaces x_all: window t is
         # series[:, t : t+W], built inside the kernel — no [T, N, W] tensor
         assert (x_all is None) != (series is None), "give either the window tensor or the raw series"
-        assert y_all.is_cuda and (x_all if x_all is not None else series).is_cuda
         self.series = series
         self.model, self.x, self.y, self.batch = model.eval(), x_all, y_all, batch * max(1, coalesce)
+        assert y_all.is_cuda and self.src.is_cuda
         # range of the resident data, looked at ONCE (include/gdn_hip.h "range guard"): beyond the 16-bit operand
         # range of the matrix-core kernels the whole evaluator runs on the fp32 row-gather kernels
-        src0 = series if series is not None else x_all
-        self.wide = (model.operand_range == "wide" and src0.dtype != torch.bfloat16) or (
-            model.operand_range == "auto" and model.input_exceeds_limit(src0))
+        self.wide = model.wide_for(self.src)
         self.logical_batch, self.coalesce = batch, max(1, coalesce)
         self.t, self.n = y_all.shape
         dev = y_all.device
@@ -524,14 +520,18 @@ class SeriesEvaluator:
         n_launch = (self.t + self.batch - 1) // self.batch
         self.side = [torch.cuda.Stream(device=dev) for _ in range(min(streams, n_launch))] if streams > 1 else []
 
+    @property
+    def src(self) -> torch.Tensor:
+        """The resident data: the raw series when there is one, else the window tensor."""
+        return self.series if self.series is not None else self.x
+
     def _launch_forward(self, with_keys: bool = False):
         m = self.model
         # constants and the plan are built (when stale) HERE, on the caller's stream, before the fork: built
         # lazily inside the first side-stream launch, the launches on the other side streams would read them
         # unordered (first eager step after a parameter update: garbage in some windows)
         if m.out_layer_num == 1 and not m.training and not self.wide:
-            src = self.series if self.series is not None else self.x
-            m._plan(m._constants(), src.dtype == torch.bfloat16)
+            m._plan(m._constants(), self.src.dtype == torch.bfloat16)
         elif m.out_layer_num > 1 and not m.training:     # the OutLayer MLP's plan, for the same reason
             m._mlp_tail(m._constants())
         spans = [(s, min(self.t, s + self.batch)) for s in range(0, self.t, self.batch)]
@@ -581,8 +581,7 @@ class SeriesEvaluator:
                   None if self.scores is None else self.scores.data_ptr(), self.anomaly.data_ptr(), st)
 
     def _launch_all(self):
-        src = self.series if self.series is not None else self.x
-        fuse = self.fuse_keys and not self.wide and self.model.fused_keys_supported(src.dtype == torch.bfloat16)
+        fuse = self.fuse_keys and not self.wide and self.model.fused_keys_supported(self.src.dtype == torch.bfloat16)
         self._launch_forward(with_keys=fuse)
         self._launch_score(have_keys=fuse)
 
@@ -593,10 +592,7 @@ class SeriesEvaluator:
         if key != getattr(self, "_graph_key", None):
             self.graph = self.fgraph = None
             if getattr(self, "_graph_key", None) is not None:      # the x limit follows the parameters: look again
-                src0 = self.series if self.series is not None else self.x
-                m = self.model
-                self.wide = (m.operand_range == "wide" and src0.dtype != torch.bfloat16) or (
-                    m.operand_range == "auto" and m.input_exceeds_limit(src0))
+                self.wide = self.model.wide_for(self.src)
             self._graph_key = key
 
     def _capture(self, fn):
@@ -662,10 +658,9 @@ def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localis
         raise ValueError(f"ticks outside [0, {ev.t})")
     sensors = ev.top_sensors[ticks, :m].long()
     rows = ticks.view(-1, 1).expand(-1, m)
-    src = ev.series if ev.series is not None else ev.x
     model = ev.model
     nb = model.attention_neighbours()
-    att = model.attention_at(src, rows.reshape(-1), sensors.reshape(-1))
+    att = model.attention_at(ev.src, rows.reshape(-1), sensors.reshape(-1))
     return Localisation(ticks, sensors, ev.top_scores[ticks, :m], ev.pred[rows, sensors], ev.y[rows, sensors],
                         nb[sensors], att.reshape(ticks.numel(), m, nb.shape[1]))
 
@@ -1256,7 +1251,7 @@ def validate_series(model, series, starts, batch: int, wide=None):
     if tv == 0:
         return 0.0, pred, gt
     if wide is None:
-        wide = model.operand_range == "wide" or (model.operand_range == "auto" and model.input_exceeds_limit(series))
+        wide = model.wide_for(series)
     fast = model.out_layer_num == 1 or model.mlp_fast_path_supported()
     per_window = n * w * 4
     chunk = max(1, min(4096, _VALIDATE_CHUNK_BYTES // per_window) // batch) * batch

@@ -233,7 +233,62 @@ class OutLayer(nn.Module):
 
 class _EvalConstants:
     __slots__ = ("key", "graph", "terms", "bn1", "bn2", "fused_args", "plans", "mlp", "stream", "ready", "guards",
-                 "limits", "large", "bufs", "tail")
+                 "limits", "large", "bufs", "tail", "dims")
+
+
+WINDOWS, SERIES = 0, 1       # source kinds of the eval fast path (index into the symbol pairs below)
+
+
+class _Source:
+    """What an eval forward reads: windows x[B, n, w], or `batch` stride-1 windows of series[n, T] from column `first`."""
+    __slots__ = ("kind", "data", "batch", "lead")
+
+    def __init__(self, data, first=None, batch=None):
+        self.data = data
+        if first is None:
+            self.kind, self.batch, self.lead = WINDOWS, len(data) if data.dim() else 0, (data.data_ptr(),)
+        else:       # the leading arguments of a C entry point are all its windows and series forms differ in
+            self.kind, self.batch, self.lead = SERIES, batch, (data.data_ptr(), data.shape[-1], first)
+
+
+def eval_route(kind, bf16: bool, mlp: bool, large: bool, planned: bool, wide: bool, guard: bool, keys: bool, tail):
+    """Which launches an eval forward is: a key of _ROUTES, or a "refuse_..." name (DESIGN.md "Eval routes" has the
+    table and what the facts mean).  Plain facts in, a name out; no tensor is touched."""
+    if mlp or large:                            # staged: project -> aggregate -> head / MLP tail, fp32 only
+        if keys:
+            return "refuse_keys"
+        if bf16:
+            return "refuse_bf16_mlp" if mlp else "refuse_bf16_shape"
+        if mlp and tail is None:
+            return "refuse_outlayer"
+        return "staged" if not wide else "staged_wide" if large or kind == SERIES else "staged_wide_project"
+    if bf16 and kind == SERIES:
+        return "refuse_series_dtype"
+    if wide and not bf16:                       # (bf16 storage has no operand limit)
+        return "refuse_keys" if keys else "gated"
+    if not planned:
+        return "refuse_keys" if keys else "tile_bf16" if bf16 else "tile"
+    if keys:
+        return "plan_keys"
+    return "plan_guarded" if guard and not bf16 else "plan"
+
+
+_ROUTES = {     # route -> launch steps: one fused step (two with the guard), or projection + aggregate of the staged chain
+    "plan": ("plan",), "plan_guarded": ("plan", "gated"), "plan_keys": ("keys",), "gated": ("gated",),
+    "staged": ("project", "aggregate"), "staged_wide": ("project", "aggregate_wide"),
+    "tile": ("tile",), "tile_bf16": ("tile_bf16",), "staged_wide_project": ("project_wide", "aggregate_wide"),
+}
+_SYMBOLS = {    # launch step -> C entry point for (WINDOWS, SERIES); None: no such launch from here
+    "plan": ("gdn_forward_fused_plan", "gdn_forward_fused_series_plan"),
+    "keys": ("gdn_forward_fused_plan_keys", "gdn_forward_fused_series_plan_keys"),
+    "gated": ("gdn_forward_fused_gated", "gdn_forward_fused_series_gated"),
+    "tile": ("gdn_forward_fused", None),                    # (series: ops.forward_fused_series)
+    "tile_bf16": ("gdn_forward_fused_bf16", None),
+    "project": ("gdn_project_fwd", "gdn_project_fwd_series"),
+    "project_wide": ("gdn_project_fwd_wide", None),         # (the series projection is the fp32 streaming one anyway)
+    "aggregate": ("gdn_attn_aggregate_fwd",) * 2,
+    "aggregate_wide": ("gdn_attn_aggregate_fwd_wide",) * 2,
+}
 
 
 class GDN(nn.Module):
@@ -325,6 +380,7 @@ class GDN(nn.Module):
         c.limits = {}                # bf16_storage -> the plan's x limit as a host float (read on first use)
         c.mlp = False                # eval-mode OutLayer MLP plan: False = not built yet, None = unsupported
         d, w = gnn.lin.weight.shape
+        c.dims = (emb.shape[0], w)   # (n, w) every eval forward checks its input against
         # beyond the LDS tile (include/gdn_hip.h "Supported shapes"): the eval forward is staged — project,
         # gather-aggregate, head — with xlin and z in HBM, in buffers kept here per (stream, batch)
         c.large = not _lib.load().gdn_tile_fits(emb.shape[0], w, d, c.graph.k)
@@ -358,60 +414,114 @@ class GDN(nn.Module):
             cur.wait_event(c.ready)
         return cur
 
+    @contextlib.contextmanager
+    def _on_constants_stream(self, c):
+        """Build something that belongs to the constants: on `c.stream`, with `c.ready` recorded again behind it
+        (launches on other streams order themselves behind that event, `_wait_ready`)."""
+        with torch.cuda.stream(c.stream) if c.stream is not None else contextlib.nullcontext():
+            yield
+            if c.ready is not None:
+                c.ready = torch.cuda.Event()
+                c.ready.record(c.stream)
+
     def _guard(self, c, stream):
         """The int32[2] range guard of this stream (zero: the gated launch leaves it zeroed)."""
         g = c.guards.get(stream.cuda_stream)
-        if g is None and torch.cuda.is_current_stream_capturing():
+        if g is None:
             # first use inside somebody's capture: no stream switch, no event — the zero fill becomes a node of that
             # graph (every replay starts from a lowered guard, which is what the gated launch leaves anyway)
-            g = torch.zeros((2,), dtype=torch.int32, device=self.embedding.weight.device)
-            c.guards[stream.cuda_stream] = g
-        if g is None:
-            with torch.cuda.stream(c.stream) if c.stream is not None else contextlib.nullcontext():
+            with contextlib.nullcontext() if torch.cuda.is_current_stream_capturing() else self._on_constants_stream(c):
                 g = torch.zeros((2,), dtype=torch.int32, device=self.embedding.weight.device)
-                if c.ready is not None:
-                    c.ready = torch.cuda.Event()
-                    c.ready.record(c.stream)
             c.guards[stream.cuda_stream] = g
         return g
 
-    def _launch_fused(self, x, c, out, keys=None, guard: bool = False, wide: bool = False):
-        """One ctypes call (two with the range guard); every argument except x / out comes from the constants
-        cache.  `keys` = (gt[B, n] fp32, device pointer of the float64 key rows, row pitch): the launch also
-        leaves the scoring keys |out - gt| (planned matrix-core path only).  `wide`: the inputs are known to
-        exceed the 16-bit operand range — fp32 row-gather kernel.  `guard`: they are not known — the planned
-        launch flags out-of-range windows and a gated row-gather launch on the same stream redoes them."""
-        if not x.is_cuda:
-            raise _lib.GdnHipError(f"input is on {x.device}: gdn_amd needs a HIP device (no CPU fallback)")
+    def _eval_forward(self, src, out, *, keys=None, guard: bool = False, wide: bool = False, c=None):
+        """THE eval fast path (forward with out_layer_num == 1, forward_into, forward_series): checks and refusals,
+        then `eval_route` names the launches and one of the two launchers issues them.  `keys` = (gt[B, n] fp32,
+        device pointer of the float64 key rows, row pitch): the launch also leaves the scoring keys |out - gt|.
+        `wide`: the inputs are known to exceed the 16-bit operand range — fp32 kernels.  `guard`: they are not known —
+        the planned launch flags out-of-range windows and a gated row-gather launch on the same stream redoes them."""
+        if c is None:
+            c = self._constants()
+        if self.learned_graph is not c.graph.topk:      # (nn.Module.__setattr__ costs a microsecond: once per constants)
+            self.learned_graph = c.graph.topk
+        data = src.data
+        if not data.is_cuda:
+            raise _lib.GdnHipError(f"input is on {data.device}: gdn_amd needs a HIP device (no CPU fallback)")
+        n, w = c.dims
+        if src.kind == WINDOWS:
+            if data.dim() != 3 or data.shape[1] != n or data.shape[2] != w:
+                raise ValueError(f"expected data of shape [B, {n}, {w}], got {tuple(data.shape)}")
+        elif data.dim() != 2 or data.shape[0] != n:
+            raise ValueError(f"expected a series of shape [{n}, T], got {tuple(data.shape)}")
+        bf16 = data.dtype == torch.bfloat16
+        if data.dtype != torch.float32 and not bf16:
+            raise self._refusal("refuse_series_dtype", data)     # (forward / forward_into convert their windows)
+        mlp = self.out_layer_num > 1
+        fused = not (mlp or c.large)
+        planned = fused and (bf16 or not wide) and not (bf16 and src.kind == SERIES) and self._plan(c, bf16) is not None
+        # (neither plan is built where the route cannot use it: a refusal allocates and launches nothing)
+        tail = self._mlp_tail(c) if mlp and keys is None and not bf16 else None
+        route = eval_route(src.kind, bf16, mlp, c.large, planned, wide, guard, keys is not None, tail)
+        if route not in _ROUTES:
+            raise self._refusal(route, data)
+        if out is None:
+            out = torch.empty((src.batch, n), dtype=torch.float32, device=data.device)
+        if fused:
+            return self._launch_fused(src, c, out, route, keys)
+        if guard and route == "staged":     # (guard comes with out_layer_num == 1 only: staged means beyond the tile)
+            route = "staged_wide" if self._large_guard_wide(data, c) else route
+        return self._forward_large(src, c, out, route)
+
+    def _refusal(self, why: str, data=None) -> Exception:
+        """The exception behind a "refuse_..." answer of eval_route."""
+        d, w = self.gnn_layers[0].gnn.lin.weight.shape
+        if why == "refuse_keys":
+            return _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
+        if why == "refuse_series_dtype":
+            return TypeError(f"series: expected {torch.float32}, got {data.dtype}")
+        if why == "refuse_bf16_mlp":
+            return _lib.GdnHipError("bf16 storage is not available with an MLP head (out_layer_num > 1): the staged bf16 "
+                                    "kernels end at the matrix-core shapes and the OutLayer MLP reads fp32")
+        if why == "refuse_outlayer":
+            widths = [m.out_features for m in self.out_layer.mlp if isinstance(m, nn.Linear)][:-1]
+            return _lib.GdnHipError(
+                "forward_into / forward_series have no kernel for this OutLayer (hidden width "
+                f"{' / '.join(str(h) for h in dict.fromkeys(widths))}, input width {d}): gdn_head_mlp_fwd takes hidden "
+                "<= 256 at widths 16, 32, 64 and 128, gdn_mlp_eval_fwd equal hidden widths up to 512 at a width that "
+                "is a multiple of 4, both with tracked running statistics; GDN.forward evaluates this model")
+        # refuse_bf16_shape: bf16 windows where the tile form does not take the shape — by width, window, sensor count
+        what = (f"embedding width {d} does not fit it (widths other than 16, 32, 64 and 128" if d not in (16, 32, 64, 128)
+                else f"windows of {w} ticks do not fit it (windows longer than 64 ticks" if w > 64
+                else f"{self.embedding.weight.shape[0]} sensors do not fit it (graphs beyond the tile")
+        return _lib.GdnHipError(f"bf16 storage needs the LDS tile: {what} run in fp32 only)")
+
+    def _launch_fused(self, src, c, out, route: str, keys=None):
+        """The fused launcher: one ctypes call (two with the range guard); every argument except the source and
+        `out` comes from the constants cache."""
         ptrs, n, w, d, k = c.fused_args
-        b = x.shape[0]
-        if x.shape[1] != n or x.shape[2] != w:
-            raise ValueError(f"expected data of shape [B, {n}, {w}], got {tuple(x.shape)}")
-        bf16 = x.dtype == torch.bfloat16
-        if c.large:
-            if keys is not None:
-                raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
-            return self._forward_large(x, c, out, b, wide=wide or (guard and self._large_guard_wide(x, c)))
-        plan = None if (wide and not bf16) else self._plan(c, bf16)
-        g = self._guard(c, torch.cuda.current_stream()) if (guard and plan is not None and not bf16) else None
-        cur = self._wait_ready(c)
-        st = cur.cuda_stream
-        if keys is not None:
-            if plan is None:
-                raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
-            gt, key_ptr, key_pitch = keys
-            _lib.call("gdn_forward_fused_plan_keys", x.data_ptr(), plan.data_ptr(), ops._chk(gt, name="gt").data_ptr(),
-                      key_ptr, key_pitch, b, n, w, d, k, int(bf16), out.data_ptr(), st)
-        elif plan is not None:
-            _lib.call("gdn_forward_fused_plan", x.data_ptr(), plan.data_ptr(), b, n, w, d, k, int(bf16),
-                      out.data_ptr(), None if g is None else g.data_ptr(), st)
-            if g is not None:       # no-op unless the launch above met a value outside the operand range
-                _lib.call("gdn_forward_fused_gated", g.data_ptr(), x.data_ptr(), *ptrs, b, n, w, d, k, out.data_ptr(), st)
-        elif wide and not bf16:
-            _lib.call("gdn_forward_fused_gated", None, x.data_ptr(), *ptrs, b, n, w, d, k, out.data_ptr(), st)
-        else:
-            _lib.call("gdn_forward_fused_bf16" if bf16 else "gdn_forward_fused", x.data_ptr(), *ptrs, b, n, w, d, k,
-                      out.data_ptr(), st)
+        bf16 = src.data.dtype == torch.bfloat16
+        plan = c.plans.get(bf16)                                # (built by _eval_forward where the route uses it)
+        g = self._guard(c, torch.cuda.current_stream()) if route == "plan_guarded" else None
+        st = self._wait_ready(c).cuda_stream
+        dims, o = (src.batch, n, w, d, k), out.data_ptr()
+        flag = (int(bf16),) if src.kind == WINDOWS else ()      # (the planned windows entry points take the storage)
+        for step in _ROUTES[route]:
+            symbol = _SYMBOLS[step][src.kind]
+            if step == "plan":
+                _lib.call(symbol, *src.lead, plan.data_ptr(), *dims, *flag, o, None if g is None else g.data_ptr(), st)
+            elif step == "keys":
+                gt, key_ptr, key_pitch = keys
+                _lib.call(symbol, *src.lead, plan.data_ptr(), ops._chk(gt, name="gt").data_ptr(), key_ptr, key_pitch,
+                          *dims, *flag, o, st)
+            elif step == "gated":       # behind a guarded plan launch: no-op unless that met a value out of range
+                _lib.call(symbol, None if g is None else g.data_ptr(), *src.lead, *ptrs, *dims, o, st)
+            elif symbol is not None:
+                _lib.call(symbol, *src.lead, *ptrs, *dims, o, st)
+            else:
+                gnn, lin = self.gnn_layers[0].gnn, self.out_layer.mlp[0]
+                ops.forward_fused_series(src.data, src.lead[2], src.batch, w, gnn.lin.weight, c.terms, c.graph, gnn.bias,
+                                         self.embedding.weight, c.bn1, c.bn2, lin.weight, lin.bias, out=out)
         return out
 
     def _large_buffers(self, c, batch: int, tail=None):
@@ -425,54 +535,27 @@ class GDN(nn.Module):
             n, d = self.embedding.weight.shape
             dev = self.embedding.weight.device
             rows = batch * n
-            bufs = (torch.empty((rows, d), dtype=torch.float32, device=dev),
-                    torch.empty((rows,), dtype=torch.float32, device=dev),
-                    torch.empty((rows,), dtype=torch.float32, device=dev),
-                    torch.empty((rows, d), dtype=torch.float32, device=dev))
+
+            def empty(*shape):
+                return torch.empty(shape, dtype=torch.float32, device=dev)
+            bufs = (empty(rows, d), empty(rows), empty(rows), empty(rows, d))
             if tail == "wide":
-                bufs += (torch.empty((rows, d), dtype=torch.float32, device=dev),
-                         ops.mlp_eval_wide_workspace(self.out_layer, rows, d, dev),
+                bufs += (empty(rows, d), ops.mlp_eval_wide_workspace(self.out_layer, rows, d, dev),
                          torch.zeros((d + 1,), dtype=torch.float32, device=dev))
             c.bufs[key] = bufs
         return bufs
 
-    def _mlp_tail(self, c, refuse: bool = True):
+    def _mlp_tail(self, c):
         """Which kernels end the staged eval route of an out_layer_num > 1 model: "plan" = gdn_head_mlp_fwd on the
         OutLayer's plan (built here when missing, on the constants' stream like `_plan`), "wide" = gdn_head_fwd ->
-        h2 -> gdn_mlp_eval_fwd.  An OutLayer neither takes is refused here, before any buffer or launch
-        (`refuse=False`: None instead)."""
+        h2 -> gdn_mlp_eval_fwd, None = an OutLayer neither takes (eval_route refuses it)."""
         if c.tail is None:
             d = self.embedding.weight.shape[1]
             if c.mlp is False:
-                with torch.cuda.stream(c.stream) if c.stream is not None else contextlib.nullcontext():
+                with self._on_constants_stream(c):
                     c.mlp = ops.mlp_plan(self.out_layer, d)
-                    if c.mlp is not None and c.ready is not None:
-                        c.ready = torch.cuda.Event()
-                        c.ready.record(c.stream)
-            if c.mlp is not None:
-                c.tail = "plan"
-            elif ops.mlp_eval_wide_supported(self.out_layer, d):
-                c.tail = "wide"
-            elif refuse:
-                widths = [m.out_features for m in self.out_layer.mlp if isinstance(m, nn.Linear)][:-1]
-                raise _lib.GdnHipError(
-                    "forward_into / forward_series have no kernel for this OutLayer (hidden width "
-                    f"{' / '.join(str(h) for h in dict.fromkeys(widths))}, input width {d}): gdn_head_mlp_fwd takes hidden "
-                    "<= 256 at widths 16, 32, 64 and 128, gdn_mlp_eval_fwd equal hidden widths up to 512 at a width that "
-                    "is a multiple of 4, both with tracked running statistics; GDN.forward evaluates this model")
+            c.tail = "plan" if c.mlp is not None else "wide" if ops.mlp_eval_wide_supported(self.out_layer, d) else None
         return c.tail
-
-    def _bf16_refusal(self) -> _lib.GdnHipError:
-        """Why bf16 windows are refused where the tile form does not take the shape."""
-        d, w = self.gnn_layers[0].gnn.lin.weight.shape
-        if d not in (16, 32, 64, 128):
-            return _lib.GdnHipError(f"bf16 storage needs the LDS tile: embedding width {d} does not fit it (widths "
-                                    "other than 16, 32, 64 and 128 run in fp32 only)")
-        if w > 64:
-            return _lib.GdnHipError(f"bf16 storage needs the LDS tile: windows of {w} ticks do not fit it (windows "
-                                    "longer than 64 ticks run in fp32 only)")
-        return _lib.GdnHipError(f"bf16 storage needs the LDS tile: {self.embedding.weight.shape[0]} sensors do not "
-                                "fit it (graphs beyond the tile run in fp32 only)")
 
     def _large_guard_wide(self, src, c) -> bool:
         """Range check of the staged forward under operand_range='auto'.  The projection and the gather kernels
@@ -487,47 +570,38 @@ class GDN(nn.Module):
             return True
         return self.input_exceeds_limit(src)
 
-    def _forward_large(self, x, c, out, batch: int, series=None, first: int = 0, wide: bool = False):
-        """Staged eval forward: gdn_project_fwd (or its series form) -> gdn_attn_aggregate_fwd -> head, with xlin / z
-        in HBM, in buffers kept in the constants cache.  out_layer_num == 1: the shapes the LDS tile does not take (a
-        graph beyond it, windows longer than 64 ticks, other widths), ending in gdn_head_fwd.  out_layer_num > 1:
-        every shape, ending in the MLP tail of `_mlp_tail` — gdn_head_mlp_fwd (no h2), or gdn_head_fwd -> h2 ->
-        gdn_mlp_eval_fwd.  Beyond the tile every kernel is fp32 (no range guard needed); `wide` selects the fp32
-        projection / aggregate where the matrix-core ones would be picked (see _large_guard_wide).  `series`
-        [n, T]: window b = series[:, first + b : first + b + w] (the fp32 streaming projection at every shape)."""
-        src = x if series is None else series
-        if src.dtype == torch.bfloat16:
-            raise self._bf16_refusal()
+    def _forward_large(self, src, c, out, route: str):
+        """The staged launcher: projection -> aggregate -> head, with xlin / z in HBM, in buffers kept in the constants
+        cache.  out_layer_num == 1: the shapes the LDS tile does not take (a graph beyond it, windows longer than 64
+        ticks, other widths).  out_layer_num > 1: every shape, ending in the MLP tail of `_mlp_tail`.  Beyond the tile
+        every kernel is fp32; the `_wide` routes select the fp32 projection / aggregate where the matrix-core ones
+        would be picked (_large_guard_wide).  A series is projected by the fp32 streaming kernel at every shape."""
         gnn = self.gnn_layers[0].gnn
         emb = self.embedding.weight
         n, d = emb.shape
         w = gnn.lin.weight.shape[1]
-        tail = None if self.out_layer_num == 1 else self._mlp_tail(c)       # (refuses before anything is launched)
-        cur = self._wait_ready(c)
-        st = cur.cuda_stream
+        batch, tail = src.batch, c.tail
+        st = self._wait_ready(c).cuda_stream
         xlin, s_i, s_j, z, *more = self._large_buffers(c, batch, tail)
-        if series is None:
-            _lib.call("gdn_project_fwd_wide" if wide and not c.large else "gdn_project_fwd", x.data_ptr(), gnn.lin.weight.data_ptr(), c.terms.data_ptr(), batch, n, w, d,
-                      xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
-        else:
-            _lib.call("gdn_project_fwd_series", series.data_ptr(), series.shape[1], first, gnn.lin.weight.data_ptr(),
-                      c.terms.data_ptr(), batch, n, w, d, xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
-        _lib.call("gdn_attn_aggregate_fwd_wide" if wide else "gdn_attn_aggregate_fwd", xlin.data_ptr(), s_i.data_ptr(),
-                  s_j.data_ptr(), c.graph.nbr.data_ptr(), c.graph.deg.data_ptr(), gnn.bias.data_ptr(), batch, n, d,
-                  c.graph.k, z.data_ptr(), None, st)
-        if tail is None:
-            lin = self.out_layer.mlp[0]
-            _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
-                      lin.weight.data_ptr(), lin.bias.data_ptr(), batch, n, d, out.data_ptr(), None, st)
-        elif tail == "plan":
+        project, aggregate = _ROUTES[route]
+        _lib.call(_SYMBOLS[project][src.kind], *src.lead, gnn.lin.weight.data_ptr(), c.terms.data_ptr(), batch, n, w, d,
+                  xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), st)
+        _lib.call(_SYMBOLS[aggregate][src.kind], xlin.data_ptr(), s_i.data_ptr(), s_j.data_ptr(), c.graph.nbr.data_ptr(),
+                  c.graph.deg.data_ptr(), gnn.bias.data_ptr(), batch, n, d, c.graph.k, z.data_ptr(), None, st)
+        if tail == "plan":
             plan, hidden, layers = c.mlp
             _lib.call("gdn_head_mlp_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(),
                       plan.data_ptr(), batch, n, d, hidden, layers, out.data_ptr(), st)
-        else:
-            # (the head kernel's own Linear(d -> 1) runs on zeros into `out`, which the MLP then overwrites)
+            return out
+        if tail is None:
+            lin = self.out_layer.mlp[0]
+            lin_w, lin_b, h2_ptr = lin.weight.data_ptr(), lin.bias.data_ptr(), None
+        else:       # the head kernel's own Linear(d -> 1) runs on zeros into `out`, which the MLP then overwrites
             h2, ws, zeros = more
-            _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(), zeros.data_ptr(),
-                      zeros.data_ptr() + 4 * d, batch, n, d, out.data_ptr(), h2.data_ptr(), st)
+            lin_w, lin_b, h2_ptr = zeros.data_ptr(), zeros.data_ptr() + 4 * d, h2.data_ptr()
+        _lib.call("gdn_head_fwd", z.data_ptr(), emb.data_ptr(), c.bn1.data_ptr(), c.bn2.data_ptr(), lin_w, lin_b,
+                  batch, n, d, out.data_ptr(), h2_ptr, st)
+        if tail is not None:
             ops.mlp_eval_wide(h2, self.out_layer, out=out.view(-1), ws=ws)
         return out
 
@@ -536,29 +610,7 @@ class GDN(nn.Module):
         plan, or one gdn_mlp_eval_fwd takes); False: only GDN.forward evaluates it."""
         if self.training or self.out_layer_num == 1:
             return False
-        return self._mlp_tail(self._constants(), refuse=False) is not None
-
-    def _forward_mlp(self, x, out, batch: int, keys, series=None, first: int = 0, wide: bool = False):
-        """forward_into / forward_series of an out_layer_num > 1 model: the staged route at every shape."""
-        c = self._constants()
-        self.learned_graph = c.graph.topk
-        src = x if series is None else series
-        if not src.is_cuda:
-            raise _lib.GdnHipError(f"input is on {src.device}: gdn_amd needs a HIP device (no CPU fallback)")
-        if keys is not None:
-            raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
-        if src.dtype == torch.bfloat16:
-            raise _lib.GdnHipError("bf16 storage is not available with an MLP head (out_layer_num > 1): the staged bf16 "
-                                   "kernels end at the matrix-core shapes and the OutLayer MLP reads fp32")
-        n, w = self.embedding.weight.shape[0], self.gnn_layers[0].gnn.lin.weight.shape[1]
-        if series is None:
-            if x.dim() != 3 or x.shape[1] != n or x.shape[2] != w:
-                raise ValueError(f"expected data of shape [B, {n}, {w}], got {tuple(x.shape)}")
-        elif series.dim() != 2 or series.shape[0] != n:
-            raise ValueError(f"expected a series of shape [{n}, T], got {tuple(series.shape)}")
-        if out is None:
-            out = torch.empty((batch, n), dtype=torch.float32, device=src.device)
-        return self._forward_large(x, c, out, batch, series=series, first=first, wide=wide)
+        return self._mlp_tail(self._constants()) is not None
 
     def operand_limit(self, bf16: bool = False) -> float:
         """Largest |x| the eval fast path's matrix-core kernel represents with the current parameters (inf: no
@@ -596,7 +648,9 @@ class GDN(nn.Module):
                 limit = torch.minimum(limit, ops.fused_plan_limit(plan, n, w, d, k, False))
         return not bool(data.detach().abs().amax() * margin < limit)            # (NaN compares false: wide)
 
-    def _wide_for(self, x) -> bool:
+    def wide_for(self, x) -> bool:
+        """THE range decision for `x` (windows or a series on the device) under `operand_range`: True = run the fp32
+        kernels.  "auto" looks at the data (input_exceeds_limit: one synchronisation — ask once per resident tensor)."""
         if self.operand_range == "wide":
             return x.dtype != torch.bfloat16
         if self.operand_range == "narrow":
@@ -609,12 +663,9 @@ class GDN(nn.Module):
         if bf16 not in c.plans:
             gnn = self.gnn_layers[0].gnn
             lin = self.out_layer.mlp[0]
-            with torch.cuda.stream(c.stream) if c.stream is not None else contextlib.nullcontext():
+            with self._on_constants_stream(c):
                 c.plans[bf16] = ops.fused_plan(gnn.lin.weight, c.terms, c.graph, gnn.bias, self.embedding.weight,
                                                c.bn1, c.bn2, lin.weight, lin.bias, bf16_storage=bf16)
-                if c.ready is not None:
-                    c.ready = torch.cuda.Event()
-                    c.ready.record(c.stream)
         return c.plans[bf16]
 
     # ------------------------------------------------------------------ forward
@@ -631,7 +682,7 @@ class GDN(nn.Module):
         c = self._constants()
         self.learned_graph = c.graph.topk                                   # GDN.py:159
         if bf16 and c.large:
-            raise self._bf16_refusal()
+            raise self._refusal("refuse_bf16_shape")
         if batch == 0 and not self.training:
             # an empty minibatch: the reference's ops run on empty tensors and return [0, N]
             return torch.empty((0, node_num), dtype=torch.float32, device=x.device)
@@ -639,12 +690,11 @@ class GDN(nn.Module):
 
         if not self.training:
             if self.out_layer_num == 1:
-                out = torch.empty((batch, node_num), dtype=torch.float32, device=x.device)
                 mode = self.operand_range
-                self._launch_fused(x, c, out, guard=mode == "auto", wide=mode == "wide")
+                out = self._eval_forward(_Source(x), None, guard=mode == "auto", wide=mode == "wide", c=c)
                 layer._set_dense(lambda: self._dense_attention(x, c, batch))
                 return out
-            wide = self._wide_for(x)
+            wide = self.wide_for(x)
             xlin, s_i, s_j = ops.project_fwd(x, gnn.lin.weight, c.terms, wide=wide)
             # (alpha only on request — att_weight_1 — like the fused path: the launch then reads the bank-ordered lists)
             z, _ = ops.attn_aggregate_fwd(xlin, s_i, s_j, c.graph, gnn.bias, batch, want_alpha=False, wide=wide)
@@ -666,7 +716,7 @@ class GDN(nn.Module):
 
         # ---- training: HIP forward/backward for the graph layer and (out_layer_num == 1) the head
         z, alpha = _GraphAttentionFn.apply(x, gnn.lin.weight, gnn.att_i, gnn.att_j, gnn.att_em_i,
-                                           gnn.att_em_j, emb, gnn.bias, c.graph, batch, c.terms, self._wide_for(x))
+                                           gnn.att_em_j, emb, gnn.bias, c.graph, batch, c.terms, self.wide_for(x))
         layer._set_dense((alpha, c.graph, batch))
         if self.out_layer_num == 1 and self._hip_train_head_ok():
             lin = self.out_layer.mlp[0]
@@ -719,23 +769,16 @@ class GDN(nn.Module):
         return dp(ones).reshape(batch * node_num, d), 1.0
 
     def forward_into(self, data, out, keys=None, wide: bool = False):
-        """Eval fast path writing into a caller-owned [B, N] slice (no allocation, HIP-graph
-        capturable once `_constants()` is warm): used by harness.SeriesEvaluator.  `keys`: see _launch_fused.
-        The caller vouches for the range of `data` (`input_exceeds_limit`, asked once per resident tensor):
-        `wide=True` runs the fp32 row-gather kernel, False the matrix-core one WITHOUT the range guard.
-        out_layer_num > 1 takes the staged route (project -> aggregate -> MLP tail, `_forward_large`) on buffers
-        cached per (stream, batch): fp32 windows only, no `keys`."""
+        """Eval fast path writing into a caller-owned [B, N] slice (no allocation, HIP-graph capturable once
+        `_constants()` is warm): used by harness.SeriesEvaluator.  `keys`: see _eval_forward.  The caller vouches for
+        the range of `data` (`wide_for`, asked once per resident tensor): `wide=True` runs the fp32 row-gather kernel,
+        False the matrix-core one WITHOUT the range guard.  out_layer_num > 1 takes the staged route (`_forward_large`)
+        on buffers cached per (stream, batch): fp32 windows only, no `keys`."""
         if self.training:
             raise RuntimeError("forward_into is the eval fast path (model.eval() first)")
-        if self.out_layer_num != 1:
-            if data.dtype not in (torch.float32, torch.bfloat16):
-                data = data.float()
-            return self._forward_mlp(data.contiguous(), out, data.shape[0], keys, wide=wide)
-        c = self._constants()
-        self.learned_graph = c.graph.topk
         if data.dtype not in (torch.float32, torch.bfloat16):
             data = data.float()
-        return self._launch_fused(data.contiguous(), c, out, keys, wide=wide)
+        return self._eval_forward(_Source(data.contiguous()), out, keys=keys, wide=wide)
 
     def fused_keys_supported(self, bf16: bool = False) -> bool:
         """True when the eval forward of this model can leave the scoring keys itself (`keys=` of forward_into /
@@ -752,51 +795,12 @@ class GDN(nn.Module):
         out_layer_num > 1: the staged route, as forward_into."""
         if self.training:
             raise RuntimeError("forward_series is the eval fast path (model.eval() first)")
-        if self.out_layer_num != 1:
-            series = series if series.is_contiguous() else series.contiguous()
-            return self._forward_mlp(None, out, batch, keys, series=series, first=first, wide=wide)
-        c = self._constants()
-        gnn = self.gnn_layers[0].gnn
-        lin = self.out_layer.mlp[0]
-        self.learned_graph = c.graph.topk
-        if c.large:
-            if keys is not None:
-                raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
-            series = ops._chk(series, series.dtype, name="series")
-            if out is None:
-                out = torch.empty((batch, series.shape[0]), dtype=torch.float32, device=series.device)
-            return self._forward_large(None, c, out, batch, series=series, first=first, wide=wide)
-        plan = None if wide else self._plan(c, False)
-        st = self._wait_ready(c).cuda_stream
-        series = ops._chk(series, name="series")
-        n, t_len = series.shape
-        d, w = gnn.lin.weight.shape
-        if out is None:
-            out = torch.empty((batch, n), dtype=torch.float32, device=series.device)
-        if plan is not None:
-            if keys is not None:
-                gt, key_ptr, key_pitch = keys
-                _lib.call("gdn_forward_fused_series_plan_keys", series.data_ptr(), t_len, first, plan.data_ptr(),
-                          ops._chk(gt, name="gt").data_ptr(), key_ptr, key_pitch, batch, n, w, d, c.graph.k,
-                          out.data_ptr(), st)
-                return out
-            _lib.call("gdn_forward_fused_series_plan", series.data_ptr(), t_len, first, plan.data_ptr(), batch, n, w, d,
-                      c.graph.k, out.data_ptr(), None, st)
-            return out
-        if keys is not None:
-            raise _lib.GdnHipError("scoring keys from the forward launch need the planned matrix-core path")
-        if wide:     # the fp32 row-gather kernel on the raw series (inputs beyond the 16-bit operand range)
-            ptrs = c.fused_args[0]
-            _lib.call("gdn_forward_fused_series_gated", None, series.data_ptr(), t_len, first, *ptrs, batch, n, w, d,
-                      c.graph.k, out.data_ptr(), st)
-            return out
-        return ops.forward_fused_series(series, first, batch, w, gnn.lin.weight, c.terms,
-                                        c.graph, gnn.bias, self.embedding.weight, c.bn1, c.bn2, lin.weight,
-                                        lin.bias, out=out)
+        series = series if series.is_contiguous() else series.contiguous()
+        return self._eval_forward(_Source(series, first, batch), out, keys=keys, wide=wide)
 
     def _dense_attention(self, x, c, batch):
         gnn = self.gnn_layers[0].gnn
-        wide = self._wide_for(x)
+        wide = self.wide_for(x)
         xlin, s_i, s_j = ops.project_fwd(x, gnn.lin.weight, c.terms, wide=wide)
         _, alpha = ops.attn_aggregate_fwd(xlin, s_i, s_j, c.graph, gnn.bias, batch, want_alpha=True, wide=wide)
         return alpha, c.graph, batch
