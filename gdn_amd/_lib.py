@@ -100,6 +100,11 @@ SIGNATURES = {
                            _p, _p, _p],
     "gdn_epoch_advance": [_p, _p, _p, ctypes.c_longlong, _p],
     "gdn_mse_batch_means": [_p, _p, ctypes.c_longlong, _c_int, ctypes.c_longlong, _p, _p, _p, _p],
+    "gdn_stream_state_bytes": [_c_int, _c_int],
+    "gdn_stream_init": [_p, _p, ctypes.c_longlong, _c_int, _c_int, _p],
+    "gdn_stream_windows": [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p],
+    "gdn_stream_score": [_p] * 5 + [_c_int] * 4 + [_p] * 4,
+    "gdn_stream_advance": [_p] * 6 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p],
 }
 
 ERRORS = {-1: "GDN_ERR_ARG (null pointer or non-positive dimension)",

@@ -1,0 +1,321 @@
+// The streaming detector (include/gdn_hip.h "streaming detector"): one device allocation holds the stream's state —
+// tick / alarm / log counters, the float64 smoothing carry and the last w ticks of every sensor — and four launches
+// make a push of 1 .. c ticks: cut the windows, (the model's forward,) score with the carried smoothing state,
+// advance the state.  Only gdn_stream_advance writes the state; the other two read it, and stream order makes a push
+// race-free.  Plain copy, sweep and scan kernels: no inline assembly, no floating-point atomics.
+#include "gdn_common.hpp"
+
+// The float64 scoring here must round where gdn_score.hip's sweep rounds (the stream is compared with it bit for bit):
+// every product and sum is an operation of its own — no contraction of a normalised error's multiply into the 4-tap sum.
+#pragma clang fp contract(off)
+
+namespace {
+
+#define GDN_STREAM_HEADER 4          // int64 words ahead of the carry: ticks, alarms, logged, (reserved)
+#define GDN_STREAM_THREADS 256
+#define GDN_STREAM_PER_THREAD 4      // flat elements per thread, GDN_STREAM_THREADS apart (gdn_windows_gather's shape)
+#define GDN_STREAM_SPAN (GDN_STREAM_THREADS * GDN_STREAM_PER_THREAD)
+
+__host__ __device__ inline const double* stream_carry(const void* state) {
+  return reinterpret_cast<const double*>(state) + GDN_STREAM_HEADER;
+}
+__host__ __device__ inline double* stream_carry(void* state) {
+  return reinterpret_cast<double*>(state) + GDN_STREAM_HEADER;
+}
+__host__ __device__ inline const float* stream_hist(const void* state, int n) {
+  return reinterpret_cast<const float*>(stream_carry(state) + 3 * (size_t)n);
+}
+__host__ __device__ inline float* stream_hist(void* state, int n) {
+  return reinterpret_cast<float*>(stream_carry(state) + 3 * (size_t)n);
+}
+
+// hist = the last w columns of history[n, h]; counters and carry zero.  Lanes along the flat [i, w] index.
+__global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_init_kernel(
+    void* __restrict__ state, const float* __restrict__ history, long long h, int n, int w) {
+  const unsigned nw = (unsigned)n * (unsigned)w;
+  const unsigned f0 = blockIdx.x * GDN_STREAM_SPAN + threadIdx.x;
+  float* __restrict__ hist = stream_hist(state, n);
+#pragma unroll
+  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+    const unsigned f = f0 + j * GDN_STREAM_THREADS;
+    if (f >= nw) break;
+    const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
+    hist[f] = history[(long long)i * h + (h - w) + c];
+  }
+  if (blockIdx.x == 0) {
+    long long* __restrict__ head = reinterpret_cast<long long*>(state);
+    double* __restrict__ carry = stream_carry(state);
+    if (threadIdx.x < GDN_STREAM_HEADER) head[threadIdx.x] = 0;
+    for (int f = threadIdx.x; f < 3 * n; f += GDN_STREAM_THREADS) carry[f] = 0.0;
+  }
+}
+
+// Workgroup (b, span): elements [span * SPAN, (span + 1) * SPAN) of window b's flat [i, c] index: the w values of
+// sensor i before tick b of the chunk.  Position b - w + c of the stream relative to the chunk's first tick: negative
+// = column w + (b - w + c) = b + c of hist, else that row of the (time-major) chunk.
+__global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_windows_kernel(
+    const void* __restrict__ state, const float* __restrict__ chunk, int n, int w, float* __restrict__ x_out) {
+  const int b = blockIdx.x;
+  const unsigned nw = (unsigned)n * (unsigned)w;     // <= 4096 * 1024
+  const float* __restrict__ hist = stream_hist(state, n);
+  float* __restrict__ xb = x_out + (size_t)b * nw;
+  const unsigned f0 = blockIdx.y * GDN_STREAM_SPAN + threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+    const unsigned f = f0 + j * GDN_STREAM_THREADS;
+    if (f >= nw) break;
+    const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
+    const int pos = b - w + (int)c;
+    xb[f] = pos < 0 ? hist[(size_t)i * w + (unsigned)(b + (int)c)] : chunk[(size_t)pos * n + i];
+  }
+}
+
+// Normalise, smooth, top m, flag: the sweep of score_smooth_topm_kernel (gdn_score.hip) — the same loads, the same
+// float64 operations in the same order, the same m rounds of "wave maximum of (score, sensor)" — with the series
+// position of the chunk's first tick read from the state and the three normalised errors before the chunk taken from
+// the carry (rows 0, 1, 2 = three, two, one tick before; zeros where the series has no such tick).  One wave owns a run
+// of 8 consecutive ticks of the chunk; only the run at tick 0 reaches back into the carry.
+constexpr int RUN = 8;
+constexpr int TOPM_MAX = 8;
+
+__global__ __launch_bounds__(256) void gdn_stream_score_kernel(
+    const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ gt,
+    const double* __restrict__ med_iqr, const double* __restrict__ threshold, int t, int n, int m,
+    double* __restrict__ top_scores, int* __restrict__ top_sensors, int* __restrict__ alarm) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  const int nruns = (t + RUN - 1) / RUN;
+  constexpr int NONE = 0x7fffffff;               // sensor of a masked / missing candidate (score -inf)
+  const long long first_tick = reinterpret_cast<const long long*>(state)[0];
+  const double* __restrict__ carry = stream_carry(state);
+  const double thr = threshold[0];
+  for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb) {
+    const int t0 = run * RUN, t1 = min(t, t0 + RUN);
+    double cs[RUN];                               // the carried list: entry `lane` of every tick of the run
+    int ci[RUN];
+#pragma unroll
+    for (int u = 0; u < RUN; ++u) {
+      cs[u] = -INFINITY;
+      ci[u] = NONE;
+    }
+    for (int s0 = 0; s0 < n; s0 += 128) {
+      const int sa_ = s0 + lane, sb_ = s0 + 64 + lane;
+      const bool la = sa_ < n, lb = sb_ < n;
+      const int ca = la ? sa_ : n - 1, cb = lb ? sb_ : n - 1;
+      const double meda = med_iqr[2 * ca], dena = 1.0 / (fabs(med_iqr[2 * ca + 1]) + 1e-2);
+      const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
+      float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
+#pragma unroll
+      for (int u = 0; u < RUN + 3; ++u) {
+        const int tt = t0 - 3 + u;                 // < 0 (run 0 only): the value comes from the carry, row 0 is a stand-in
+        const int row = tt < 0 ? 0 : min(tt, t - 1);
+        const float* pp = pred + (size_t)row * n;
+        const float* gg = gt + (size_t)row * n;
+        pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
+      }
+      auto norm = [&](float pv, float gv, double med, double inv_den) -> double {
+        return (fabs((double)pv - (double)gv) - med) * inv_den;
+      };
+      double a3, a2, a1, b3, b2, b1;
+      if (t0 == 0) {                               // (wave uniform)
+        a3 = carry[ca]; a2 = carry[(size_t)n + ca]; a1 = carry[2 * (size_t)n + ca];
+        b3 = carry[cb]; b2 = carry[(size_t)n + cb]; b1 = carry[2 * (size_t)n + cb];
+      } else {
+        a3 = norm(pa[0], ga[0], meda, dena); a2 = norm(pa[1], ga[1], meda, dena); a1 = norm(pa[2], ga[2], meda, dena);
+        b3 = norm(pb[0], gb[0], medb, denb); b2 = norm(pb[1], gb[1], medb, denb); b1 = norm(pb[2], gb[2], medb, denb);
+      }
+#pragma unroll
+      for (int u = 0; u < RUN; ++u) {
+        const int tick = t0 + u;
+        if (tick >= t1) continue;                  // (wave uniform)
+        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena);
+        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb);
+        double sma = 0.0, smb = 0.0;
+        if (first_tick + tick >= 3) {               // numpy sums the 4 values left to right
+          sma = (((a3 + a2) + a1) + a0) / 4.0;
+          smb = (((b3 + b2) + b1) + b0) / 4.0;
+        }
+        a3 = a2; a2 = a1; a1 = a0;
+        b3 = b2; b2 = b1; b1 = b0;
+        // this lane's three candidates
+        double v0 = la ? sma : -INFINITY, v1 = lb ? smb : -INFINITY, v2 = cs[u];
+        int i0 = la ? sa_ : NONE, i1 = lb ? sb_ : NONE, i2 = ci[u];
+        double ns = -INFINITY;
+        int ni = NONE;
+        for (int r = 0; r < m; ++r) {              // (m is wave uniform)
+          double bs = v0;
+          int bi = i0;
+          if (v1 > bs || (v1 == bs && i1 < bi)) { bs = v1; bi = i1; }
+          if (v2 > bs || (v2 == bs && i2 < bi)) { bs = v2; bi = i2; }
+#pragma unroll
+          for (int d = 32; d >= 1; d >>= 1) {
+            const double os = __shfl_xor(bs, d);
+            const int oi = __shfl_xor(bi, d);
+            if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
+          }
+          if (bi != NONE) {                        // the owner masks its candidate out
+            if (i0 == bi) { v0 = -INFINITY; i0 = NONE; }
+            if (i1 == bi) { v1 = -INFINITY; i1 = NONE; }
+            if (i2 == bi) { v2 = -INFINITY; i2 = NONE; }
+          }
+          if (lane == r) { ns = bs; ni = bi; }
+        }
+        cs[u] = ns;
+        ci[u] = ni;
+      }
+    }
+    if (lane < m) {
+#pragma unroll
+      for (int u = 0; u < RUN; ++u) {
+        if (t0 + u < t1) {
+          top_scores[(size_t)(t0 + u) * m + lane] = cs[u];
+          top_sensors[(size_t)(t0 + u) * m + lane] = ci[u];
+          if (lane == 0) alarm[t0 + u] = cs[u] > thr ? 1 : 0;      // strict; a NaN score compares false
+        }
+      }
+    }
+  }
+}
+
+// The one launch that writes the state.  Workgroup i < n rolls row i of hist: every thread loads its (up to 4)
+// columns of the NEW row — from the old row where the column survives, else from the chunk — then a barrier, then the
+// stores: no column is read after it has been overwritten, whatever count is.  Workgroup n: the carry (one thread per
+// sensor: its three old entries are read before any is written), the alarm log (an ordered compaction: ballot and
+// popcount inside a wave, four wave totals through LDS, 256 flags a round in tick order) and, last, the counters.
+__global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
+    void* __restrict__ state, const float* __restrict__ chunk, const float* __restrict__ pred,
+    const double* __restrict__ med_iqr, const int* __restrict__ alarm, const int* __restrict__ top_sensors, int count,
+    int n, int w, int m, long long* __restrict__ log_ticks, int* __restrict__ log_sensors, long long log_len) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < n) {
+    const int i = blockIdx.x;
+    float* __restrict__ row = stream_hist(state, n) + (size_t)i * w;
+    float v[GDN_STREAM_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+      const int c = tid + j * GDN_STREAM_THREADS;             // w <= 1024 = PER_THREAD * THREADS
+      v[j] = 0.f;
+      if (c < w) {
+        const long long src = (long long)c + count;           // column of [hist | chunk^T]
+        v[j] = src < w ? row[src] : chunk[(size_t)(src - w) * n + i];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+      const int c = tid + j * GDN_STREAM_THREADS;
+      if (c < w) row[c] = v[j];
+    }
+    return;
+  }
+  __shared__ int wave_total[GDN_STREAM_THREADS / 64];
+  long long* __restrict__ head = reinterpret_cast<long long*>(state);
+  double* __restrict__ carry = stream_carry(state);
+  // carry: the last three of [carry0, carry1, carry2, a(chunk row 0), .., a(chunk row count - 1)]
+  for (int s = tid; s < n; s += GDN_STREAM_THREADS) {
+    const double med = med_iqr[2 * s], inv_den = 1.0 / (fabs(med_iqr[2 * s + 1]) + 1e-2);
+    double next[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int q = count + j;                                 // position in the 3 + count values above
+      if (q < 3) {
+        next[j] = carry[(size_t)q * n + s];
+      } else {
+        const size_t at = (size_t)(q - 3) * n + s;
+        next[j] = (fabs((double)pred[at] - (double)chunk[at]) - med) * inv_den;     // gdn_stream_score's `norm`
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) carry[(size_t)j * n + s] = next[j];
+  }
+  // alarm log
+  const long long ticks = head[0], logged = head[2];
+  const int lane = tid & 63, wv = tid >> 6;
+  long long raised = 0;                                        // flags in the rounds before this one
+  for (int base = 0; base < count; base += GDN_STREAM_THREADS) {
+    const int b = base + tid;
+    const bool flag = b < count && alarm[b] != 0;
+    const unsigned long long mask = __ballot(flag);
+    if (lane == 0) wave_total[wv] = __popcll(mask);
+    __syncthreads();
+    int before = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+    for (int v = 0; v < GDN_STREAM_THREADS / 64; ++v) {
+      if (v < wv) before += wave_total[v];
+      total += wave_total[v];
+    }
+    __syncthreads();                                           // wave_total is rewritten next round
+    const long long slot = logged + raised + before;
+    if (flag && slot < log_len) {
+      log_ticks[slot] = ticks + b;
+      for (int r = 0; r < m; ++r) log_sensors[slot * m + r] = top_sensors[(size_t)b * m + r];
+    }
+    raised += total;
+  }
+  if (tid == 0) {
+    head[0] = ticks + count;
+    head[1] += raised;
+    const long long want = logged + raised, room = log_len > logged ? log_len : logged;
+    head[2] = want < room ? want : room;                       // a full log drops entries; `alarms` keeps counting
+  }
+}
+
+bool stream_shape_ok(int n, int w) { return w >= 1 && w <= GDN_LONG_MAX_W && n >= 1 && n <= 4096; }
+
+}  // namespace
+
+extern "C" long long gdn_stream_state_bytes(int n, int w) {
+  if (!stream_shape_ok(n, w)) return 0;
+  const long long bytes = 8ll * GDN_STREAM_HEADER + 8ll * 3 * n + 4ll * n * w;
+  return (bytes + 7) & ~7ll;
+}
+
+extern "C" int gdn_stream_init(void* state, const float* history, long long h, int n, int w, void* stream) {
+  if (!state || !history) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  if (h < w) return GDN_ERR_ARG;                   // a cold start: the caller buffers w ticks first
+  const unsigned nw = (unsigned)n * (unsigned)w;
+  hipLaunchKernelGGL(gdn_stream_init_kernel, dim3((nw + GDN_STREAM_SPAN - 1) / GDN_STREAM_SPAN),
+                     dim3(GDN_STREAM_THREADS), 0, (hipStream_t)stream, state, history, h, n, w);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_stream_windows(const void* state, const float* chunk, int c, int count, int n, int w, float* x_out,
+                                  void* stream) {
+  if (!state || !chunk || !x_out) return GDN_ERR_ARG;
+  if (count < 1 || count > c) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  const unsigned nw = (unsigned)n * (unsigned)w;
+  const dim3 grid((unsigned)count, (nw + GDN_STREAM_SPAN - 1) / GDN_STREAM_SPAN);
+  hipLaunchKernelGGL(gdn_stream_windows_kernel, grid, dim3(GDN_STREAM_THREADS), 0, (hipStream_t)stream, state, chunk, n,
+                     w, x_out);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_stream_score(const void* state, const float* pred, const float* chunk, const double* med_iqr,
+                                const double* threshold, int c, int count, int n, int m, double* top_scores,
+                                int32_t* top_sensors, int32_t* alarm, void* stream) {
+  if (!state || !pred || !chunk || !med_iqr || !threshold || !top_scores || !top_sensors || !alarm) return GDN_ERR_ARG;
+  if (count < 1 || count > c) return GDN_ERR_ARG;
+  if (n < 1 || n > 4096) return GDN_ERR_UNSUPPORTED;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  const int runs = (count + RUN - 1) / RUN;
+  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
+  hipLaunchKernelGGL(gdn_stream_score_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
+                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_stream_advance(void* state, const float* chunk, const float* pred, const double* med_iqr,
+                                  const int32_t* alarm, const int32_t* top_sensors, int c, int count, int n, int w,
+                                  int m, int64_t* log_ticks, int32_t* log_sensors, long long log_len, void* stream) {
+  if (!state || !chunk || !pred || !med_iqr || !alarm || !top_sensors) return GDN_ERR_ARG;
+  if (count < 1 || count > c || log_len < 0) return GDN_ERR_ARG;
+  if (log_len > 0 && (!log_ticks || !log_sensors)) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(gdn_stream_advance_kernel, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0, (hipStream_t)stream,
+                     state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
+                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len);
+  return gdn_launch_status();
+}

@@ -1412,3 +1412,169 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
                 torch.save(model.state_dict(), save_path)
             min_loss = acc
     return losses
+
+
+# --------------------------------------------------------------------------- streaming detector
+_STREAM_MAX_CHUNK = 4096                # ticks per push: validate_series' cap on windows per launch
+
+
+class StreamDetector:
+    """Scores ticks as they arrive against a frozen calibration, with nothing but launches per push.
+
+    The stream's state lives on the device (include/gdn_hip.h "streaming detector"): the last w ticks of every sensor,
+    the float64 smoothing carry, the tick / alarm counters and the alarm log.  A push of `chunk` ticks is ONE copy
+    into the static chunk buffer and ONE replay of a graph captured once: gdn_stream_windows (the chunk's windows cut
+    from history + chunk) -> model.forward_into -> gdn_stream_score (gdn_score_smooth_topm's arithmetic at the
+    stream's position, flags against the threshold) -> gdn_stream_advance (the only writer of the state).  A shorter
+    push issues the same launches eagerly with count = its ticks; a longer one is split.  No host synchronisation.
+
+    The stream equals harness.SeriesEvaluator(top_m=...) with this `med_iqr` on [history[:, -w:] | stream]: the same
+    windows, the same forward, the same float64 scoring bit for bit.
+
+    `med_iqr` [n, 2] float64 and `threshold` (a number or a device float64 scalar) come from a period known to be
+    normal (`from_calibration`); `history` [n, h >= w] fp32 holds the ticks before the stream (a cold start is
+    refused).  `top_m` sensors per tick are kept (1 .. 8); `log` alarm entries are kept (0: no log).  `wide`: None asks
+    model.wide_for(history) once, True / False is the caller's word; under operand_range == "auto" on the planned
+    matrix-core route the forward is the guarded launch, which redoes an out-of-range push in fp32 on the device."""
+
+    def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
+                 use_graph: bool = True, wide: bool | None = None):
+        self.model = model.eval()
+        w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+        n = model.embedding.weight.shape[0]
+        self.n, self.w, self.chunk, self.top_m, self.use_graph = n, w, int(chunk), int(top_m), bool(use_graph)
+        if not 1 <= self.chunk <= _STREAM_MAX_CHUNK:
+            raise ValueError(f"chunk = {chunk}: a push scores 1 to {_STREAM_MAX_CHUNK} ticks (longer pushes are split)")
+        if self.chunk * n * w * 4 > _VALIDATE_CHUNK_BYTES:
+            raise ValueError(f"chunk = {chunk}: the window buffer [{chunk}, {n}, {w}] fp32 exceeds "
+                             f"{_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
+        if not 1 <= self.top_m <= min(8, n):
+            raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {n}")
+        if int(log) < 0:
+            raise ValueError(f"log = {log}: the alarm log holds 0 or more entries")
+        if model.out_layer_num > 1 and not ops.mlp_fast_tail_supported(model.out_layer, model.embedding.weight.shape[1]):
+            raise model._refusal("refuse_outlayer")        # (GDN.mlp_fast_path_supported's answer, from host facts)
+        history = ops._chk(history, name="history")
+        if history.dim() != 2 or history.shape[0] != n:
+            raise ValueError(f"expected a history of shape [{n}, h], got {tuple(history.shape)}")
+        dev = history.device
+        med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr")
+        if med_iqr.shape != (n, 2):
+            raise ValueError(f"expected med_iqr of shape [{n}, 2], got {tuple(med_iqr.shape)}")
+        self.med_iqr = med_iqr.clone()
+        self.threshold = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev).clone()
+        self.state = ops.stream_state(history, w)
+        self.wide = model.wide_for(history[:, -w:]) if wide is None else bool(wide)
+        c, m = self.chunk, self.top_m
+        self.chunk_buf = torch.zeros((c, n), dtype=torch.float32, device=dev)
+        self.x = torch.zeros((c, n, w), dtype=torch.float32, device=dev)
+        self.pred = torch.zeros((c, n), dtype=torch.float32, device=dev)
+        self.top_scores = torch.zeros((c, m), dtype=torch.float64, device=dev)
+        self.top_sensors = torch.zeros((c, m), dtype=torch.int32, device=dev)
+        self.alarm = torch.zeros((c,), dtype=torch.int32, device=dev)
+        self.log_ticks = torch.zeros((int(log),), dtype=torch.int64, device=dev) if log else None
+        self.log_sensors = torch.zeros((int(log), m), dtype=torch.int32, device=dev) if log else None
+        self.graph = None
+        self._graph_key = None
+        self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
+
+    @classmethod
+    def from_calibration(cls, model, series, chunk: int, batch: int = 8192, **kw):
+        """A detector calibrated on `series` [n, T] fp32 on the device, a period known to be normal: ONE
+        SeriesEvaluator step over it gives `med_iqr`; threshold = the largest anomaly score of that period (the rule
+        of `-report val`); history = its last w ticks unless `history=` names the ticks the stream really follows."""
+        series = ops._chk(series, name="series")
+        w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+        if series.dim() != 2 or series.shape[1] <= w:
+            raise ValueError(f"calibration needs a series [n, T] with T > {w}, got {tuple(series.shape)}")
+        gt = series[:, w:].t().contiguous()
+        ev = SeriesEvaluator(model, None, gt, batch=batch, use_graph=False, series=series)
+        anomaly = ev.step()
+        kw.setdefault("history", series[:, -w:])
+        history = kw.pop("history")
+        return cls(model, ev.med_iqr, anomaly.max(), history, chunk, **kw)
+
+    # the launches of a push: static arguments only (they are captured)
+    def _guarded(self) -> bool:
+        m = self.model
+        if self.wide or m.operand_range != "auto" or m.out_layer_num != 1:
+            return False
+        c = m._constants()
+        return not c.large and m._plan(c, False) is not None
+
+    def _launch(self, count: int, guard: bool):
+        ops.stream_windows(self.state, self.chunk_buf, self.w, self.x, count=count)
+        x = self.x if count == self.chunk else self.x[:count]
+        self.model.forward_into(x, self.pred[:count], wide=self.wide, guard=guard)
+        ops.stream_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.top_m,
+                         self.top_scores, self.top_sensors, self.alarm, count=count)
+        ops.stream_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors, self.w,
+                           self.top_m, self.log_ticks, self.log_sensors, count=count)
+
+    def _fresh(self):
+        """A captured graph bakes in the pointers of the model's folded constants: drop it when a parameter changed."""
+        key = self.model._constants().key
+        if key != self._graph_key:
+            self.graph = None
+            self._graph_key = key
+
+    def _push(self, ticks):
+        r = ticks.shape[0]
+        self.chunk_buf[:r].copy_(ticks)
+        self._last = r
+        if r != self.chunk or not self.use_graph:
+            return self._launch(r, self._guarded())
+        self._fresh()
+        if self.graph is not None:
+            return self.graph.replay()
+        # the first full push (or the first after a parameter change) goes out eagerly and is the warm-up of the
+        # capture (occupancy queries, the staged route's buffers, the range guard); a capture launches nothing, so the
+        # state moves once
+        guard = self._guarded()
+        self._launch(r, guard)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with capture(self.graph):
+            self._launch(r, guard)
+
+    def push(self, ticks):
+        """Score `ticks` [r, n] fp32 (device or host), oldest first.  Returns views (top_scores [r', m] float64,
+        top_sensors [r', m] int32, alarm [r'] int32) of the static buffers, valid until the next push; r' = r when
+        r <= chunk, else the ticks of the last of the pushes it was split into (the counters and the log hold all)."""
+        if ticks.dim() != 2 or ticks.shape[1] != self.n:
+            raise ValueError(f"expected ticks of shape [r, {self.n}], got {tuple(ticks.shape)}")
+        if ticks.dtype != torch.float32:
+            raise TypeError(f"ticks: expected {torch.float32}, got {ticks.dtype}")
+        if ticks.shape[0] < 1:
+            raise ValueError("a push needs at least one tick")
+        for s in range(0, ticks.shape[0], self.chunk):
+            self._push(ticks[s:s + self.chunk])
+        r = self._last
+        return self.top_scores[:r], self.top_sensors[:r], self.alarm[:r]
+
+    def status(self):
+        """(ticks, alarms, log_ticks[:logged], log_sensors[:logged]): ONE read of the counters (a synchronisation)."""
+        ticks, alarms, logged = (int(v) for v in self.state[:3].tolist())
+        if self.log_ticks is None:
+            dev = self.state.device
+            return (ticks, alarms, torch.empty((0,), dtype=torch.int64, device=dev),
+                    torch.empty((0, self.top_m), dtype=torch.int32, device=dev))
+        return ticks, alarms, self.log_ticks[:logged], self.log_sensors[:logged]
+
+    def localise(self, rows=None) -> Localisation:
+        """harness.localise for the last push: which sensors deviate at its alarm rows (`rows=None`; or the given
+        rows of the push) and which neighbours they were reading — ONE model.attention_at on the static window
+        buffer.  `ticks` are global stream ticks; the other fields mean what they mean for `localise`."""
+        r, m = self._last, self.top_m
+        if rows is None:
+            rows = torch.nonzero(self.alarm[:r]).view(-1)
+        rows = torch.as_tensor(rows, device=self.state.device).to(torch.int64).reshape(-1)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= r):
+            raise ValueError(f"rows outside [0, {r}) of the last push")
+        sensors = self.top_sensors[rows].long()
+        at = rows.view(-1, 1).expand(-1, m)
+        nb = self.model.attention_neighbours()
+        att = self.model.attention_at(self.x, at.reshape(-1), sensors.reshape(-1))
+        first = self.state[0] - r                       # (advance has run: ticks counts the push already)
+        return Localisation(first + rows, sensors, self.top_scores[rows], self.pred[at, sensors],
+                            self.chunk_buf[at, sensors], nb[sensors], att.reshape(rows.numel(), m, nb.shape[1]))

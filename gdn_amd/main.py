@@ -195,7 +195,32 @@ class Main:
         info = self.get_score(self.test_result, self.val_result)
         if self.env_config.get("localise"):
             self.save_localisation(best_model, gt, float(info[4]), self.env_config["localise"])
+        if self.env_config.get("stream"):
+            self.stream_test_series(best_model, val_ticks, int(self.env_config["stream"]))
         return info
+
+    def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10):
+        """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
+        of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
+        threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
+        counters and the alarm log are read ONCE at the end and kept as `stream_result`."""
+        w = self.train_config["slide_win"]
+        lo, hi = int(val_ticks.min()), int(val_ticks.max())
+        normal = self.train_series[:, lo - w:hi + 1].contiguous()
+        det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
+                                                      top_m=min(3, normal.shape[0]))
+        ticks = self.test_series[:, w:].t().contiguous()
+        for s in range(0, ticks.shape[0], chunk):
+            det.push(ticks[s:s + chunk])
+        scored, alarms, log_ticks, log_sensors = det.status()
+        self.stream_result = {"chunk": chunk, "threshold": float(det.threshold.item()), "ticks": scored,
+                              "alarms": alarms, "log_ticks": log_ticks.cpu().numpy(),
+                              "log_sensors": log_sensors.cpu().numpy()}
+        first = ", ".join(str(int(t) + w) for t in self.stream_result["log_ticks"][:show])
+        print(f"stream: {scored} ticks in pushes of {chunk}, threshold {self.stream_result['threshold']:.6g} from "
+              f"{normal.shape[1] - w} validation ticks: {alarms} alarm ticks"
+              + (f"; first at test ticks {first}" if alarms else "") + "\n")
+        return self.stream_result
 
     def save_localisation(self, model, gt, threshold: float, path: str, m: int = 3):
         """-localise PATH: for every test tick whose anomaly score exceeds the report's threshold, the m most
@@ -249,7 +274,8 @@ class Main:
 
 
 def build_parser():
-    """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph."""
+    """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
+    -localise / -stream."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -272,6 +298,8 @@ def build_parser():
     parser.add_argument("-no_hip_graph", help="launch every training step eagerly", action="store_true")
     parser.add_argument("-localise", help="save the deviating sensors and their attention at the ticks above the "
                         "report's threshold to this .npz", type=str, default="")
+    parser.add_argument("-stream", help="after the report, replay the test series through a streaming detector in "
+                        "pushes of this many ticks (calibrated on the validation block)", type=int, default=0)
     return parser
 
 
@@ -290,7 +318,7 @@ def main(argv=None):
                     "hip_graph": not args.no_hip_graph}
     env_config = {"save_path": args.save_path_pattern, "dataset": args.dataset, "report": args.report,
                   "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
-                  "localise": args.localise}
+                  "localise": args.localise, "stream": args.stream}
     return Main(train_config, env_config, debug=False).run()
 
 

@@ -768,17 +768,18 @@ class GDN(nn.Module):
             self._ones = None if getattr(dp, "inplace", False) else ones
         return dp(ones).reshape(batch * node_num, d), 1.0
 
-    def forward_into(self, data, out, keys=None, wide: bool = False):
+    def forward_into(self, data, out, keys=None, wide: bool = False, guard: bool = False):
         """Eval fast path writing into a caller-owned [B, N] slice (no allocation, HIP-graph capturable once
         `_constants()` is warm): used by harness.SeriesEvaluator.  `keys`: see _eval_forward.  The caller vouches for
         the range of `data` (`wide_for`, asked once per resident tensor): `wide=True` runs the fp32 row-gather kernel,
-        False the matrix-core one WITHOUT the range guard.  out_layer_num > 1 takes the staged route (`_forward_large`)
-        on buffers cached per (stream, batch): fp32 windows only, no `keys`."""
+        False the matrix-core one WITHOUT the range guard — unless `guard=True` (harness.StreamDetector: data that is
+        still to come), which hands the decision to the device as _eval_forward describes.  out_layer_num > 1 takes
+        the staged route (`_forward_large`) on buffers cached per (stream, batch): fp32 windows only, no `keys`."""
         if self.training:
             raise RuntimeError("forward_into is the eval fast path (model.eval() first)")
         if data.dtype not in (torch.float32, torch.bfloat16):
             data = data.float()
-        return self._eval_forward(_Source(data.contiguous()), out, keys=keys, wide=wide)
+        return self._eval_forward(_Source(data.contiguous()), out, keys=keys, guard=guard, wide=wide)
 
     def fused_keys_supported(self, bf16: bool = False) -> bool:
         """True when the eval forward of this model can leave the scoring keys itself (`keys=` of forward_into /

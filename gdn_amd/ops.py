@@ -393,6 +393,16 @@ def mlp_eval_wide_supported(out_layer, d_in: int) -> bool:
     return _lib.load().gdn_mlp_eval_workspace_bytes(2, d_in, h, len(hidden) + 1) > 0
 
 
+def mlp_fast_tail_supported(out_layer, d_in: int) -> bool:
+    """True when one of the two eval tails takes this OutLayer (mlp_plan or mlp_eval_wide_supported), decided from the
+    module's configuration and the library's size queries alone: no tensor is touched, no device is needed."""
+    linears = [m for m in out_layer.mlp if isinstance(m, torch.nn.Linear)]
+    bns = [m for m in out_layer.mlp if isinstance(m, torch.nn.BatchNorm1d)]
+    planned = (len(linears) >= 2 and all(b.track_running_stats and b.affine for b in bns)
+               and _lib.load().gdn_mlp_plan_bytes(d_in, linears[0].out_features, len(linears)) != 0)
+    return planned or mlp_eval_wide_supported(out_layer, d_in)
+
+
 def mlp_eval_wide_workspace(out_layer, rows: int, d_in: int, device) -> torch.Tensor:
     """Scratch of mlp_eval_wide for `rows` rows (gdn_mlp_eval_workspace_bytes): callers that run the same shape
     again and again keep it and pass it as `ws=`."""
@@ -832,3 +842,91 @@ def mse_batch_means(pred, y, batch: int, batch_means=None, mean=None):
         mean = torch.empty((), dtype=torch.float64, device=pred.device)
     _lib.call("gdn_mse_batch_means", _ptr(pred), _ptr(y), rows, n, batch, _ptr(batch_means), _ptr(mean), None, _stream())
     return batch_means, mean
+
+
+# --------------------------------------------------------------------------- streaming detector
+def _stream_buf(t, dtype, need: int, name: str):
+    if not t.is_cuda:
+        raise _lib.GdnHipError(f"{name} is on {t.device}: gdn_amd ops need a HIP device (no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < need:
+        raise ValueError(f"{name}: a contiguous {dtype} device tensor of at least {need} elements is needed")
+    return t
+
+
+def stream_state(history, w: int) -> torch.Tensor:
+    """The device state of a stream (include/gdn_hip.h "streaming detector") that starts after `history` [n, h >= w]:
+    an int64 tensor of gdn_stream_state_bytes(n, w) / 8 words, counters and carry zero, hist = history[:, -w:]."""
+    history = _chk(history, name="history")
+    if history.dim() != 2:
+        raise ValueError(f"expected the history [n, h], got {tuple(history.shape)}")
+    n, h = history.shape
+    if h < w:
+        raise ValueError(f"a history of {h} ticks is shorter than the window of {w}: buffer {w} ticks before streaming")
+    nbytes = _lib.load().gdn_stream_state_bytes(n, w)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"stream state: no kernel for n = {n}, w = {w} (1 <= n <= 4096, 1 <= w <= 1024)")
+    state = torch.zeros((nbytes // 8,), dtype=torch.int64, device=history.device)       # (padding bytes compare equal)
+    _lib.call("gdn_stream_init", _ptr(state), _ptr(history), h, n, w, _stream())
+    return state
+
+
+def stream_state_views(state, n: int, w: int):
+    """(counters int64[3] = ticks, alarms, logged; carry float64 [3, n]; hist fp32 [n, w]): views of a stream state."""
+    carry = state[4:4 + 3 * n].view(torch.float64).view(3, n)
+    hist = state[4 + 3 * n:].view(torch.float32)[: n * w].view(n, w)
+    return state[:3], carry, hist
+
+
+def _stream_dims(state, chunk, count, w: int):
+    chunk = _chk(chunk, name="chunk")
+    if chunk.dim() != 2:
+        raise ValueError(f"expected the chunk [c, n] (one row per tick), got {tuple(chunk.shape)}")
+    c, n = chunk.shape
+    count = c if count is None else int(count)
+    _stream_buf(state, torch.int64, max(1, _lib.load().gdn_stream_state_bytes(n, w) // 8), "state")
+    return chunk, c, n, count
+
+
+def stream_windows(state, chunk, w: int, x_out, count: int | None = None):
+    """x_out[b, i, :] = the w values of sensor i before tick b of `chunk` [c, n] (time-major), for b < count
+    (default: all c rows): the head of a window from the state's hist, the rest from the chunk's earlier rows."""
+    chunk, c, n, count = _stream_dims(state, chunk, count, w)
+    _stream_buf(x_out, torch.float32, c * n * w, "x_out")
+    _lib.call("gdn_stream_windows", _ptr(state), _ptr(chunk), c, count, n, w, _ptr(x_out), _stream())
+    return x_out
+
+
+def stream_score(state, pred, chunk, med_iqr, threshold, m: int, top_scores, top_sensors, alarm, count: int | None = None):
+    """gdn_score_smooth_topm over `count` rows of pred / chunk [c, n] at the stream's position: first tick and the three
+    values before the chunk come from the state.  alarm[b] = top_scores[b, 0] > threshold[0] (a float64 device scalar)."""
+    chunk, c, n, count = _stream_dims(state, chunk, count, 1)
+    pred = _stream_buf(pred, torch.float32, c * n, "pred")
+    _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
+    _stream_buf(threshold, torch.float64, 1, "threshold")
+    _stream_buf(top_scores, torch.float64, c * m, "top_scores")
+    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
+    _stream_buf(alarm, torch.int32, c, "alarm")
+    _lib.call("gdn_stream_score", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(med_iqr), _ptr(threshold), c, count, n, m,
+              _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
+    return top_scores, top_sensors, alarm
+
+
+def stream_advance(state, chunk, pred, med_iqr, alarm, top_sensors, w: int, m: int, log_ticks=None, log_sensors=None,
+                   count: int | None = None):
+    """The one launch that writes the stream state: hist and carry rolled by `count` ticks, the counters on, every
+    alarm appended to log_ticks [L] int64 / log_sensors [L, m] int32 in tick order (both None: no log)."""
+    chunk, c, n, count = _stream_dims(state, chunk, count, w)
+    _stream_buf(pred, torch.float32, c * n, "pred")
+    _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
+    _stream_buf(alarm, torch.int32, c, "alarm")
+    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
+    if (log_ticks is None) != (log_sensors is None):
+        raise ValueError("give both log_ticks and log_sensors, or neither")
+    log_len = 0
+    if log_ticks is not None:
+        log_len = log_ticks.numel()
+        _stream_buf(log_ticks, torch.int64, log_len, "log_ticks")
+        _stream_buf(log_sensors, torch.int32, log_len * m, "log_sensors")
+    _lib.call("gdn_stream_advance", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors),
+              c, count, n, w, m, _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len,
+              _stream())

@@ -676,6 +676,49 @@ int gdn_epoch_advance(const float* loss, int64_t* cursor, float* loss_table, lon
 int gdn_mse_batch_means(const float* pred, const float* y, long long rows, int n, long long batch,
                         double* batch_means, double* mean, void* workspace, void* stream);
 
+/* ---- streaming detector --------------------------------------------------------------------
+ * Scoring ticks as they arrive, 1 .. c at a time, against a frozen calibration (median / IQR per sensor and one
+ * threshold, both from a period known to be normal), with every piece of stream state on the device so that a push is
+ * a fixed run of launches (capturable in a HIP graph).  Additive entry points: the ABI version does not move.
+ * State: ONE allocation of gdn_stream_state_bytes(n, w) bytes (8-byte aligned; 0 for an unsupported shape):
+ *   int64  ticks      ticks scored so far            (byte 0)
+ *   int64  alarms     alarm ticks so far             (byte 8)
+ *   int64  logged     log entries written so far     (byte 16)
+ *   int64  reserved                                  (byte 24)
+ *   double carry[3, n]   normalised errors (|pred - gt| - median) * (1 / (|iqr| + 1e-2)) of the last three scored
+ *                        ticks, oldest first; zeros where the stream has no such tick      (byte 32)
+ *   float  hist[n, w]    the last w ticks of every sensor, oldest first                    (byte 32 + 24 n)
+ * Only gdn_stream_advance writes the state after gdn_stream_init; the other two read it.  A push is, in stream order:
+ * gdn_stream_windows, the model's forward on x_out, gdn_stream_score, gdn_stream_advance.  `chunk` [c, n] fp32 is
+ * time-major (one row per tick, the layout of pred / gt everywhere else): it is the gt of the score launch itself.
+ *   gdn_stream_init     hist = the last w columns of history[n, h]; counters and carry 0 (so the 4-tap mean of the
+ *                       first three scored ticks is 0, as at the start of a series).  h < w: GDN_ERR_ARG.
+ *   gdn_stream_windows  x_out[b, i, :] for b < count = the w values of sensor i before tick b of the chunk: the first
+ *                       max(0, w - b) from hist[i, b:], the rest from chunk[b-w .. b-1, i].  Rows b >= count are not
+ *                       written.
+ *   gdn_stream_score    gdn_score_smooth_topm over the chunk's `count` rows with first_tick = ticks read from the
+ *                       state and the three values before the chunk from carry: the same float64 operations in the
+ *                       same order, the same top-m order.  alarm[b] = top_scores[b, 0] > threshold[0] (threshold: one
+ *                       float64 on the device; strict, a NaN score never alarms).
+ *   gdn_stream_advance  hist = the last w columns of [hist | chunk^T] (a row is loaded whole before any of it is
+ *                       stored: count < w is safe); carry = the last three of [carry | the chunk's normalised errors];
+ *                       ticks += count; alarms += raised flags; every alarm appended to the log in tick order (ordered
+ *                       compaction in one workgroup, no atomics) as log_ticks[e] = its global tick, log_sensors[e, :] =
+ *                       its row of top_sensors, while e < log_len; a full log drops entries, alarms keeps counting.
+ *                       log_len may be 0 with NULL log pointers.
+ * 1 <= w <= 1024, 1 <= n <= 4096, 1 <= m <= 8, m <= n: else GDN_ERR_UNSUPPORTED.  Null required pointers, count < 1,
+ * count > c, log_len < 0, log_len > 0 with a NULL log pointer: GDN_ERR_ARG.  All decided before any launch.          */
+long long gdn_stream_state_bytes(int n, int w);
+int gdn_stream_init(void* state, const float* history, long long h, int n, int w, void* stream);
+int gdn_stream_windows(const void* state, const float* chunk, int c, int count, int n, int w, float* x_out,
+                       void* stream);
+int gdn_stream_score(const void* state, const float* pred, const float* chunk, const double* med_iqr,
+                     const double* threshold, int c, int count, int n, int m, double* top_scores,
+                     int32_t* top_sensors, int32_t* alarm, void* stream);
+int gdn_stream_advance(void* state, const float* chunk, const float* pred, const double* med_iqr,
+                       const int32_t* alarm, const int32_t* top_sensors, int c, int count, int n, int w, int m,
+                       int64_t* log_ticks, int32_t* log_sensors, long long log_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
