@@ -18,13 +18,15 @@ import contextlib
 import ctypes
 import gc
 import os
+import warnings
 from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
+import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 
 
 # --------------------------------------------------------------------------- eval loop
@@ -85,57 +87,78 @@ def train(model=None, save_path="", config=None, train_dataloader=None, val_data
     graphed = None
     if not use_graph:
         optimizer = torch.optim.Adam(model.parameters(), lr=0.001, weight_decay=config.get("decay", 0))
-    losses, min_loss, stale = [], 1e8, 0
+    losses, best = [], _BestSoFar()
     # Range of the training inputs (include/gdn_hip.h "range guard"): decided ONCE — config["wide"] when the caller
     # knows (python -m gdn_amd.main looks at its resident series), else from the first batch — and pinned on the
-    # model for the whole run: no per-step host check, and the captured step needs the answer before the capture
-    range_before = getattr(model, "operand_range", "auto")
+    # model for every training step of the run: no per-step host check, and the captured step needs the answer before
+    # the capture.  A range the caller has set is left alone; validation data gets its own range (eval guard)
+    auto = getattr(model, "operand_range", "auto") == "auto"
     wide = config.get("wide", None)
     for _epoch in range(config.get("epoch", 1)):
         model.train()
         epoch_losses = []
         for x, labels, _attack, edge_index in train_dataloader:
             x, labels = x.float().to(device), labels.float().to(device)
-            if wide is None and range_before == "auto":
+            if wide is None and auto:
                 wide = model.input_exceeds_limit(x, margin=16.0)      # (the weights move during training)
-            if range_before == "auto":
-                model.operand_range = "wide" if wide else "narrow"
-            if use_graph and graphed is None:
-                graphed = GraphedTrainStep(model, x.shape[0], lr=0.001, weight_decay=config.get("decay", 0),
-                                           wide=model.operand_range == "wide")
-                optimizer = graphed.optimizer
-            if graphed is not None and x.shape[0] == graphed.x.shape[0]:
-                graphed.x.copy_(x)
-                graphed.y.copy_(labels)
-                epoch_losses.append(graphed.step().clone())
-                continue
-            optimizer.zero_grad()
-            out = model(x, edge_index)
-            loss = F.mse_loss(out, labels, reduction="mean")
-            loss.backward()
-            sync_gradients(model)
-            optimizer.step()
-            epoch_losses.append(loss.detach())
+            with pinned_range(model, wide) if auto else contextlib.nullcontext():
+                if use_graph and graphed is None:
+                    graphed = GraphedTrainStep(model, x.shape[0], lr=0.001, weight_decay=config.get("decay", 0),
+                                               wide=model.operand_range == "wide")
+                    optimizer = graphed.optimizer
+                if graphed is not None and x.shape[0] == graphed.x.shape[0]:
+                    graphed.x.copy_(x)
+                    graphed.y.copy_(labels)
+                    epoch_losses.append(graphed.step().clone())
+                else:
+                    epoch_losses.append(_eager_step(model, optimizer, x, labels, edge_index))
         step_losses = torch.stack(epoch_losses).tolist() if epoch_losses else []
         losses.extend(step_losses)
-        acc = float(sum(step_losses))
-        if val_dataloader is not None:
-            model.operand_range = range_before          # validation data: its own range (eval guard)
-            val_loss, _ = test(model, val_dataloader, device)
-            if val_loss < min_loss:
-                if save_path:
-                    torch.save(model.state_dict(), save_path)
-                min_loss, stale = val_loss, 0
-            else:
-                stale += 1
-            if stale >= 15:
-                break
-        elif acc < min_loss:
+        val_loss = test(model, val_dataloader, device)[0] if val_dataloader is not None else None
+        if best.update(val_loss, float(sum(step_losses)), model, save_path):
+            break
+    return losses
+
+
+@contextlib.contextmanager
+def pinned_range(model, wide):
+    """`model.operand_range` set to "wide" / "narrow" for the block — the caller has looked at its data, so nothing
+    inside (a captured step above all) runs a host check — and back to what it was afterwards, exceptions included."""
+    before = getattr(model, "operand_range", "auto")
+    model.operand_range = "wide" if wide else "narrow"
+    try:
+        yield
+    finally:
+        model.operand_range = before
+
+
+def _eager_step(model, optimizer, x, y, edge_index=None):
+    """One optimisation step of the reference's train() (train.py:52-66) through autograd; returns the detached loss."""
+    optimizer.zero_grad()
+    loss = F.mse_loss(model(x, edge_index), y, reduction="mean")
+    loss.backward()
+    sync_gradients(model)
+    optimizer.step()
+    return loss.detach()
+
+
+class _BestSoFar:
+    """The reference's checkpoint and early-stop rule (train.py:89-108), one epoch per `update`.  With a validation
+    loss: save on a strictly better one, stop after 15 epochs without.  Without: save on a better summed training
+    loss, never stop."""
+
+    def __init__(self):
+        self.min_loss, self.stale = 1e8, 0
+
+    def update(self, val_loss, summed_loss, model, save_path) -> bool:
+        loss = summed_loss if val_loss is None else val_loss
+        if loss < self.min_loss:
             if save_path:
                 torch.save(model.state_dict(), save_path)
-            min_loss = acc
-    model.operand_range = range_before
-    return losses
+            self.min_loss, self.stale = loss, 0
+        elif val_loss is not None:
+            self.stale += 1
+        return self.stale >= 15
 
 
 # --------------------------------------------------------------------------- sharding / DDP
@@ -426,7 +449,6 @@ class ShardedEvaluator:
             self._graphs, self._result = graphs, out
             return True
         except Exception as exc:     # noqa: BLE001 — a capture that fails must not take the evaluator down with it
-            import warnings
             warnings.warn(f"ShardedEvaluator: HIP-graph capture of the compute segments failed ({exc!r}); running eagerly")
             self._graphs = None
             torch.cuda.synchronize()
@@ -563,7 +585,6 @@ class SeriesEvaluator:
             main.wait_event(join)
 
     def _launch_score(self, have_keys: bool = False):
-        from . import _lib
         st = torch.cuda.current_stream().cuda_stream
         if have_keys:       # keys [n, t] already sit at the head of the workspace (same layout gdn_score_quantiles uses)
             _lib.call("gdn_score_select", self.ws.data_ptr(), 1, self.n, self.t, self.t,
@@ -666,28 +687,112 @@ def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localis
 
 
 # --------------------------------------------------------------------------- graphed train step
-class AutogradTrainStep:
-    """One optimisation step of the reference's train() (train.py:52-66: zero_grad, forward, MSE,
-    backward, Adam) captured once in a HIP graph and replayed per minibatch — the form that goes through
-    torch autograd and torch.optim.Adam(fused=True): used when `NativeTrainStep` does not apply
-    (a custom `model.dp` module, an injected graph, an OutLayer or a shape the training kernels do not take).
+class _CapturedStep:
+    """One optimisation step of the reference's train() (train.py:52-79) issued as two halves: `_first` (the caller's
+    `pre` hook, then forward, loss and backward) and `_second` (the optimizer, then the `post` hook).  With more than
+    one rank (or `split=True`, the rehearsal of it) ONE eager op sits between the halves, the all-reduce of a flat
+    gradient bucket.
 
-    At the reference's batch sizes a step is ~30 launches of a few microseconds each, so issuing
-    them from Python costs more than running them; a replayed graph removes that.  The graph
-    covers the per-step rebuild of the sensor graph and the folded attention terms (they depend
-    on the parameters Adam has just changed), the HIP forward/backward of the graph layer and of
-    the train-mode head, the fused MSE loss + gradient kernel, torch's dropout draw and a fused,
-    capturable Adam.  With more than one rank the step is
-    two graphs around ONE eager op, the all-reduce of the flat gradient bucket (packing is the
-    tail of the first graph, averaging + unpacking the head of the second).
+    At the reference's batch sizes a step is a few dozen launches of a few microseconds each, so issuing them from
+    Python costs more than running them.  With `use_graph` the halves are captured once — one HIP graph, or two around
+    the all-reduce — and a step is one or two replays.  `_capture`: snapshot `_saved()`; `WARMUP` eager steps (lazy
+    attribute / occupancy queries, allocations); restore the snapshot, then `_after_restore()` — capturing must not
+    train the model; capture (which executes nothing) through `capture()` into one shared pool.
 
-    `x` / `y` are the static input buffers: copy each minibatch into them, call `step()`, read
-    `loss` (a device scalar) whenever convenient.  `pre` / `post`: see NativeTrainStep."""
+    `x` / `y` are the static input buffers: copy each minibatch into them, call `step()`, read `loss` (a device scalar)
+    whenever convenient.
+
+    `pre` / `post`: optional callables that issue launches on the current stream immediately before the step's first
+    launch and immediately after the optimizer's — in eager mode, in the warm-up steps of the capture and INSIDE the
+    captured graph (with two graphs: `pre` in the first, `post` in the second).  harness.SeriesTrainer hangs the
+    window gather and the cursor / loss bookkeeping of an epoch there.  None: exactly the launches of a plain step.
+
+    A subclass sets `model`, `x`, `y`, `loss` and `optimizer` and provides `_forward_backward()`, `_update()`,
+    `_all_reduce()`, `_saved()` (the tensors whose values the warm-up must not change) and `_after_restore()`."""
+
+    WARMUP = 2
+
+    def __init__(self, use_graph: bool, split: bool | None, pre, post):
+        self.pre, self.post = pre, post
+        self.use_graph, self._graphs = use_graph, None
+        # two graphs around the (eager) gradient all-reduce; forced on by `split=True` for rehearsal
+        self._split = world()[1] > 1 if split is None else bool(split)
+
+    def _first(self):
+        if self.pre is not None:
+            self.pre()
+        self._forward_backward()
+
+    def _second(self):
+        self._update()
+        if self.post is not None:
+            self.post()
+
+    def _warm_up(self):
+        for _ in range(self.WARMUP):
+            self._first()
+            self._all_reduce()
+            self._second()
+
+    def _capture(self):
+        saved = [(t, t.detach().clone()) for t in self._saved()]
+        self._warm_up()
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for t, s in saved:
+                t.copy_(s)
+            self._after_restore()
+        torch.cuda.synchronize()
+        pool = torch.cuda.graph_pool_handle()
+        graphs = []
+        for half in ((self._first,), (self._second,)) if self._split else ((self._first, self._second),):
+            g = torch.cuda.CUDAGraph()
+            with capture(g, pool=pool):
+                for fn in half:
+                    fn()
+            graphs.append(g)
+        self._graphs = graphs
+
+    def prepare(self):
+        """Capture now (the first `step()` otherwise does): a caller whose hooks keep state of their own
+        (harness.SeriesTrainer's cursor) resets it after the warm-up steps of the capture have moved it."""
+        if self.use_graph and self._graphs is None:
+            self._capture()
+
+    def step(self):
+        if self.use_graph:
+            self.prepare()
+            self._graphs[0].replay()
+            if self._split:
+                self._all_reduce()                       # the only eager op of a multi-rank step
+                self._graphs[1].replay()
+        else:
+            self._first()
+            if self._split:
+                self._all_reduce()
+            self._second()
+        # a replay writes parameters and BatchNorm statistics through raw pointers: no Python forward runs and no
+        # version counter moves, so the model's cached eval constants (sensor graph, attention terms, BatchNorm
+        # folds) must be dropped here or eval after training serves stale ones
+        self.model.invalidate_constants()
+        return self.loss
+
+
+class AutogradTrainStep(_CapturedStep):
+    """The step through torch autograd and torch.optim.Adam(fused=True, capturable=True): used when `NativeTrainStep`
+    does not apply (a custom `model.dp` module, an injected graph, an OutLayer or a shape the training kernels do not
+    take).  The halves hold the per-step rebuild of the sensor graph and the folded attention terms, the HIP
+    forward/backward of the graph layer and of the train-mode head, the fused MSE loss + gradient kernel, torch's
+    dropout draw and the fused Adam.  Split: packing the gradient bucket is the tail of the first half, averaging +
+    unpacking the head of the second.  The warm-up runs on a side stream, as torch asks of autograd work that precedes
+    a capture."""
+
+    WARMUP = 3
 
     def __init__(self, model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
                  split: bool | None = None, wide: bool = False, pre=None, post=None):
+        super().__init__(use_graph, split, pre, post)
         self.wide = bool(wide)
-        self.pre, self.post = pre, post
         p0 = next(model.parameters())
         if not p0.is_cuda:
             raise RuntimeError("GraphedTrainStep needs the model on a HIP device")
@@ -702,35 +807,15 @@ class AutogradTrainStep:
         # fused: one multi-tensor launch for all 13 parameters instead of ~40 small ones
         self.optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=True,
                                           fused=True)
-        self.use_graph = use_graph
-        self._graphs = None
-        # two graphs around the (eager) gradient all-reduce; forced on by `split=True` for rehearsal
-        self._split = world()[1] > 1 if split is None else bool(split)
         self._flat = None                                # static gradient bucket (split mode)
-        import os
         self._torch_mse = bool(os.environ.get("GDN_TORCH_MSE"))
         self._dbg = None                                 # diagnostic snapshot buffers (tools/probe_mse_replay.py)
 
-    # the two halves of a step with the caller's hooks: what an eager step issues and what the graphs hold
-    def _first(self):
-        if self.pre is not None:
-            self.pre()
-        self._forward_backward()
-
-    def _second(self):
-        self._update()
-        if self.post is not None:
-            self.post()
-
-    # the two halves of a step; `loss` is written in place so it survives replays
+    # `loss` is written in place so it survives replays
     def _forward_backward(self):
         self.optimizer.zero_grad(set_to_none=True)      # backward then writes fresh gradients: no fill, no add
-        before = self.model.operand_range
-        self.model.operand_range = "wide" if self.wide else "narrow"      # no host check inside a captured step
-        try:
+        with pinned_range(self.model, self.wide):       # no host check inside a captured step
             out = self.model(self.x, None)
-        finally:
-            self.model.operand_range = before
         if self._torch_mse:     # diagnostic (tools/probe_mse_replay.py): the round-1 form with torch's reduction
             loss = F.mse_loss(out, self.y, reduction="mean")
             loss.backward()
@@ -760,69 +845,21 @@ class AutogradTrainStep:
         if world()[1] > 1:
             dist.all_reduce(self._flat, op=dist.ReduceOp.SUM)
 
-    def _snapshot(self):
-        tensors = list(self.model.parameters()) + list(self.model.buffers())
-        return tensors, [t.detach().clone() for t in tensors]
+    def _saved(self):
+        return list(self.model.parameters()) + list(self.model.buffers())
 
-    def _capture(self):
-        """Warm up on a side stream, capture, then put parameters, BN statistics and the Adam
-        state back to what they were: capturing must not train the model."""
-        tensors, saved = self._snapshot()
+    def _after_restore(self):
+        for state in self.optimizer.state.values():
+            for v in state.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+
+    def _warm_up(self):
         side = torch.cuda.Stream(device=self.x.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(3):
-                self._first()
-                self._all_reduce()
-                self._second()
+            super()._warm_up()
         torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        pool = torch.cuda.graph_pool_handle()
-        graphs = []
-        if self._split:
-            for fn in (self._first, self._second):
-                g = torch.cuda.CUDAGraph()
-                with capture(g, pool=pool):
-                    fn()
-                graphs.append(g)
-        else:
-            g = torch.cuda.CUDAGraph()
-            with capture(g, pool=pool):
-                self._first()
-                self._second()
-            graphs.append(g)
-        with torch.no_grad():
-            for t, s in zip(tensors, saved):
-                t.copy_(s)
-            for state in self.optimizer.state.values():
-                for v in state.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-        self._graphs = graphs
-
-    def prepare(self):
-        """Capture now (the first `step()` otherwise does): a caller whose hooks keep state of their own
-        (harness.SeriesTrainer's cursor) resets it after the warm-up steps of the capture have moved it."""
-        if self.use_graph and self._graphs is None:
-            self._capture()
-
-    def step(self):
-        if not self.use_graph:
-            self._first()
-            if self._split:
-                self._all_reduce()
-            self._second()
-            return self.loss
-        self.prepare()
-        self._graphs[0].replay()
-        if self._split:
-            self._all_reduce()                           # the only eager op of a multi-rank step
-            self._graphs[1].replay()
-        # a replay writes parameters and BatchNorm statistics through raw pointers: no Python forward
-        # runs and no version counter moves, so the model's cached eval constants (sensor graph,
-        # attention terms, BatchNorm folds) must be dropped here or eval after training serves stale ones
-        self.model.invalidate_constants()
-        return self.loss
 
 
 def flat_layout(params):
@@ -869,9 +906,17 @@ class _FlatAdam:
         o.model.invalidate_constants()
 
 
-class NativeTrainStep:
-    """the training step of train.py:63-79 with nothing but this library's kernels between the
-    input batch and the updated parameters — no autograd graph, no torch optimizer, no mask tensor.
+def _ptr_array(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _float_array(values):
+    return (ctypes.c_float * len(values))(*values)
+
+
+class NativeTrainStep(_CapturedStep):
+    """the step with nothing but this library's kernels between the input batch and the updated
+    parameters — no autograd graph, no torch optimizer, no mask tensor.
 
       * every parameter is a VIEW into one flat fp32 buffer; gradients, Adam's exp_avg / exp_avg_sq are flat
         buffers of the same layout;
@@ -885,26 +930,19 @@ class NativeTrainStep:
         folded into the optimizer kernel);
       * gdn_adam_step: one launch over the flat buffers, torch.optim.Adam's update.
 
-    The launches of a step are captured once in a HIP graph (two graphs around the all-reduce with >1 rank).
-    `x` / `y` are the static input buffers; `loss` a device scalar.  BatchNorm uses per-rank batch
-    statistics (standard DDP).
-
-    `pre` / `post`: optional callables that issue launches on the current stream immediately before the step's first
-    launch and immediately after the optimizer's — in eager mode, in the warm-up steps of the capture and INSIDE the
-    captured graph (with two graphs: `pre` in the first, `post` in the second).  harness.SeriesTrainer hangs the
-    window gather and the cursor / loss bookkeeping of an epoch there.  None: exactly the launches of a plain step."""
+    Every address a launch takes — workspace, parameter and gradient slots — is fixed in the constructor and looked up
+    there once; a launch reads only VALUES (dropout rate, BatchNorm momentum / eps / running statistics, the current
+    stream) when it is issued.  BatchNorm uses per-rank batch statistics (standard DDP)."""
 
     BETAS, EPS = (0.9, 0.999), 1e-8
 
     @staticmethod
     def applicable(model) -> bool:
-        import torch.nn as nn
         if not (type(model.dp) is nn.Dropout and model._hip_train_head_ok() and model.injected_graph is None
                 and next(model.parameters()).is_cuda):
             return False
         n, d = model.embedding.weight.shape
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
-        from . import _lib
         if not _lib.load().gdn_train_supported(n, w, d, model.topk):     # shape outside the training kernels
             return False
         # out_layer_num > 1: the OutLayer MLP must be one gdn_mlp_train_fwd takes (any row count > 1)
@@ -912,9 +950,8 @@ class NativeTrainStep:
 
     def __init__(self, model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
                  split: bool | None = None, seed: int | None = None, wide: bool = False, pre=None, post=None):
-        from . import _lib
+        super().__init__(use_graph, split, pre, post)
         self._lib = _lib
-        self.pre, self.post = pre, post
         # inputs beyond the 16-bit operand range of the matrix-core kernels: the `_wide` (fp32 row-gather) entry
         # points throughout, decided by the caller from its data (harness.train: first batch / config["wide"])
         self.wide = bool(wide)
@@ -943,9 +980,8 @@ class NativeTrainStep:
         self.state = torch.tensor([seed, 0], dtype=torch.int64, device=dev)     # {dropout seed, steps taken}
         self.optimizer = _FlatAdam(self)
 
-        gnn, layer = model.gnn_layers[0].gnn, model.gnn_layers[0]
         n, d = model.embedding.weight.shape
-        w, k = gnn.lin.weight.shape[1], model.topk
+        w, k = model.gnn_layers[0].gnn.lin.weight.shape[1], model.topk
         self.n, self.d, self.w, self.k, self.batch = n, d, w, k, batch
         lib = _lib.load()
         pitch = ops.nbr_pitch(k)
@@ -992,133 +1028,153 @@ class NativeTrainStep:
         # the gdn_mse_loss_grad launch — measured SLOWER (0.198 vs 0.193 ms: 512 workgroups each pay the block
         # reductions and the ticket), so off by default
         self._fuse_mse = os.environ.get("GDN_FUSE_MSE", "0") == "1"
-        self.use_graph = use_graph
-        self._graphs = None
-        self._split = world()[1] > 1 if split is None else bool(split)
+
+        # the address tables of the launches: workspace and static buffers by name, parameter (P) and gradient (G)
+        # slots by parameter name, and the groups the launches take together
+        self._pt = {key: t.data_ptr() for key, t in self.ws.items()}
+        self._pt.update(x=self.x.data_ptr(), y=self.y.data_ptr(), loss=self.loss.data_ptr(), rng=self.state.data_ptr())
         name_of = {id(p): name for name, p in model.named_parameters()}
-        self._off = {name_of[id(p)]: off for p, (off, _c) in zip(self.params, self.slices)}
-        self._layer, self._gnn = layer, gnn
-
-    # pointers -------------------------------------------------------------------------------------------------
-    def _pp(self, name):
-        return self.flat_p.data_ptr() + 4 * self._off[name]
-
-    def _gp(self, name):
-        return self.flat_g.data_ptr() + 4 * self._off[name]
+        names = [name_of[id(p)] for p in self.params]
+        P = self._P = {name: self.flat_p.data_ptr() + 4 * off for name, (off, _c) in zip(names, self.slices)}
+        G = self._G = {name: self.flat_g.data_ptr() + 4 * off for name, (off, _c) in zip(names, self.slices)}
+        att = ["gnn_layers.0.gnn." + leaf for leaf in ("lin.weight", "att_i", "att_j", "att_em_i", "att_em_j")]
+        bn = ["gnn_layers.0.bn.weight", "gnn_layers.0.bn.bias", "bn_outlayer_in.weight", "bn_outlayer_in.bias"]
+        last = 0 if self._mlp is None else 3 * (self._mlp[1] - 1)      # the OutLayer's closing Linear
+        last = [f"out_layer.mlp.{last}.weight", f"out_layer.mlp.{last}.bias"]
+        self._att_p, self._att_g = [P[nm] for nm in att], [G[nm] for nm in att]
+        self._bn_p, self._bn_g = [P[nm] for nm in bn], [G[nm] for nm in bn]
+        self._last_p, self._last_g = [P[nm] for nm in last], [G[nm] for nm in last]
+        if self._mlp is not None:       # the hidden layers' {Linear weight, bias, BatchNorm weight, bias}, as the kernels take them
+            hidden = [f"out_layer.mlp.{3 * l + j}.{kind}" for l in range(self._mlp[1] - 1) for j, kind in
+                      ((0, "weight"), (0, "bias"), (1, "weight"), (1, "bias"))]
+            self._mlp_p, self._mlp_g = _ptr_array([P[nm] for nm in hidden]), _ptr_array([G[nm] for nm in hidden])
 
     def _bn_run(self, bn):
         if not bn.track_running_stats or bn.running_mean is None:
             return 0.0, None, None, None
         return float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
 
-    # the two halves of a step ---------------------------------------------------------------------------------
-    def _first(self):
-        if self.pre is not None:
-            self.pre()
-        self._forward_backward()
-
-    def _second(self):
-        self._adam()
-        if self.post is not None:
-            self.post()
-
+    # the first half of a step, stage by stage ------------------------------------------------------------------
     def _forward_backward(self):
-        call, ws, m = self._lib.call, self.ws, self.model
-        st = torch.cuda.current_stream().cuda_stream
-        n, d, w, k, b = self.n, self.d, self.w, self.k, self.batch
-        P, G = self._pp, self._gp
-        g = "gnn_layers.0.gnn."
-        bn1, bn2 = self._layer.bn, m.bn_outlayer_in
+        m = self.model
+        main = torch.cuda.current_stream()
+        st = main.cuda_stream
         p_drop = float(m.dp.p) if m.dp.training else 0.0
-        rng = self.state.data_ptr()
-        pt = {key: t.data_ptr() for key, t in ws.items()}
-        # graph + folded attention terms of THIS step's parameters (models/GDN.py:145-165, graph_layer.py:94-104).
+        bn1, bn2 = m.gnn_layers[0].bn, m.bn_outlayer_in
+        m1, rm1, rv1, nb1 = self._bn_run(bn1)
+        m2, rm2, rv2, nb2 = self._bn_run(bn2)
+        eps = (float(bn1.eps), float(bn2.eps))
+        run = (m1, m2, rm1, rv1, nb1, rm2, rv2, nb2)
+        reverse_on = self._graph_terms_project(main, st)
+        self._aggregate(st)
+        self._head_forward(p_drop, eps, run, st)
+        if self._mlp is not None or not self._fuse_mse:
+            self._loss(st)
+        # backward: gradients land in their slots of flat_g
+        self._head_backward(p_drop, eps, st)
+        main.wait_stream(reverse_on)                 # reverse lists
+        self._aggregate_backward(st)
+        self._project_backward_finish(st)
+        self._terms_backward(st)
+
+    def _graph_terms_project(self, main, st):
+        """Graph + folded attention terms of THIS step's parameters (models/GDN.py:145-165, graph_layer.py:94-104),
+        then the projection.  Returns the stream the reverse lists are written on."""
+        call, pt, emb = self._lib.call, self._pt, self._P["embedding.weight"]
+        n, d, w, k, b = self.n, self.d, self.w, self.k, self.batch
+        if not self._fork:
+            # graph rows and folded terms in one launch (independent work, one launch less on the critical path)
+            call("gdn_topk_graph_terms", emb, n, d, k, pt["topk"], pt["nbr"], pt["deg"], *self._att_p, w, pt["terms"], st)
+            if self._need_reverse:       # only the row-gather backward reads the reverse lists
+                call("gdn_graph_reverse", pt["nbr"], pt["deg"], n, k, pt["rent"], pt["rlen"], st)
+            call("gdn_project_fwd" + self._sfx, pt["x"], self._att_p[0], pt["terms"], b, n, w, d, pt["xlin"],
+                 pt["s_i"], pt["s_j"], st)
+            return main
         # GDN_TRAIN_FORK=1: three independent chains forked onto side streams (parallel branches of the captured
         # graph): [top-k graph] | [folded terms -> projection] | [reverse lists, needed by the backward only] —
         # measured SLOWER than the serial chain inside a HIP graph (0.235 vs 0.218 ms), so off by default
-        main = torch.cuda.current_stream()
-        if self._fork:
-            side, side2 = self._side
-            side.wait_stream(main)
-            s2 = side.cuda_stream
-            call("gdn_node_terms", P(g + "lin.weight"), P(g + "att_i"), P(g + "att_j"), P(g + "att_em_i"), P(g + "att_em_j"),
-                 P("embedding.weight"), n, d, w, pt["terms"], s2)
-            call("gdn_project_fwd" + self._sfx, self.x.data_ptr(), P(g + "lin.weight"), pt["terms"], b, n, w, d, pt["xlin"],
-                 pt["s_i"], pt["s_j"], s2)
-            call("gdn_topk_graph", P("embedding.weight"), n, d, k, pt["topk"], pt["nbr"], pt["deg"], None, st)
-            side2.wait_stream(main)
-            call("gdn_graph_reverse", pt["nbr"], pt["deg"], n, k, pt["rent"], pt["rlen"], side2.cuda_stream)
-            main.wait_stream(side)
-        else:
-            side2 = main
-            # graph rows and folded terms in one launch (independent work, one launch less on the critical path)
-            call("gdn_topk_graph_terms", P("embedding.weight"), n, d, k, pt["topk"], pt["nbr"], pt["deg"], P(g + "lin.weight"),
-                 P(g + "att_i"), P(g + "att_j"), P(g + "att_em_i"), P(g + "att_em_j"), w, pt["terms"], st)
-            if self._need_reverse:       # only the row-gather backward reads the reverse lists
-                call("gdn_graph_reverse", pt["nbr"], pt["deg"], n, k, pt["rent"], pt["rlen"], st)
-            call("gdn_project_fwd" + self._sfx, self.x.data_ptr(), P(g + "lin.weight"), pt["terms"], b, n, w, d, pt["xlin"],
-                 pt["s_i"], pt["s_j"], st)
-        call("gdn_attn_aggregate_fwd" + self._sfx, pt["xlin"], pt["s_i"], pt["s_j"], pt["nbr"], pt["deg"], P(g + "bias"), b, n, d, k,
-             pt["z"], pt["alpha"], st)
-        m1, rm1, rv1, nb1 = self._bn_run(bn1)
-        m2, rm2, rv2, nb2 = self._bn_run(bn2)
-        bnp = (P("gnn_layers.0.bn.weight"), P("gnn_layers.0.bn.bias"), P("bn_outlayer_in.weight"), P("bn_outlayer_in.bias"))
-        bng = (G("gnn_layers.0.bn.weight"), G("gnn_layers.0.bn.bias"), G("bn_outlayer_in.weight"), G("bn_outlayer_in.bias"))
-        eps = (float(bn1.eps), float(bn2.eps))
-        run = (m1, m2, rm1, rv1, nb1, rm2, rv2, nb2)
-        if self._mlp is None:
-            lw, lb = "out_layer.mlp.0.weight", "out_layer.mlp.0.bias"
-            if self._fuse_mse:   # the loss and its gradient come out of the head's last forward pass
-                call("gdn_head_train_fwd_rng_mse", pt["z"], P("embedding.weight"), *bnp, P(lw), P(lb), rng, p_drop, b, n, d,
-                     *eps, *run, pt["stats"], pt["out"], self.y.data_ptr(), pt["head_mse_ws"], self.loss.data_ptr(),
-                     pt["d_out"], 1, st)
-            else:
-                call("gdn_head_train_fwd_rng", pt["z"], P("embedding.weight"), *bnp, P(lw), P(lb), rng, p_drop, b, n, d,
-                     *eps, *run, pt["stats"], pt["out"], 1, st)
+        side, side2 = self._side
+        side.wait_stream(main)
+        s2 = side.cuda_stream
+        call("gdn_node_terms", *self._att_p, emb, n, d, w, pt["terms"], s2)
+        call("gdn_project_fwd" + self._sfx, pt["x"], self._att_p[0], pt["terms"], b, n, w, d, pt["xlin"],
+             pt["s_i"], pt["s_j"], s2)
+        call("gdn_topk_graph", emb, n, d, k, pt["topk"], pt["nbr"], pt["deg"], None, st)
+        side2.wait_stream(main)
+        call("gdn_graph_reverse", pt["nbr"], pt["deg"], n, k, pt["rent"], pt["rlen"], side2.cuda_stream)
+        main.wait_stream(side)
+        return side2
+
+    def _aggregate(self, st):
+        pt = self._pt
+        self._lib.call("gdn_attn_aggregate_fwd" + self._sfx, pt["xlin"], pt["s_i"], pt["s_j"], pt["nbr"], pt["deg"],
+                       self._P["gnn_layers.0.gnn.bias"], self.batch, self.n, self.d, self.k, pt["z"], pt["alpha"], st)
+
+    def _head_forward(self, p_drop, eps, run, st):
+        call, pt, emb = self._lib.call, self._pt, self._P["embedding.weight"]
+        b, n, d = self.batch, self.n, self.d
+        if self._mlp is None and self._fuse_mse:     # the loss and its gradient come out of the head's last forward pass
+            call("gdn_head_train_fwd_rng_mse", pt["z"], emb, *self._bn_p, *self._last_p, pt["rng"], p_drop, b, n, d,
+                 *eps, *run, pt["stats"], pt["out"], pt["y"], pt["head_mse_ws"], pt["loss"], pt["d_out"], 1, st)
+        elif self._mlp is None:
+            call("gdn_head_train_fwd_rng", pt["z"], emb, *self._bn_p, *self._last_p, pt["rng"], p_drop, b, n, d,
+                 *eps, *run, pt["stats"], pt["out"], 1, st)
         else:
             # out_layer_num > 1: head passes up to the dropped-out activation, then the MLP on the matrix cores
             h, layers, bns = self._mlp
-            arr = lambda ptrs: (ctypes.c_void_p * len(ptrs))(*ptrs)
-            names = [f"out_layer.mlp.{3 * l + j}.{kind}" for l in range(layers - 1) for j, kind in
-                     ((0, "weight"), (0, "bias"), (1, "weight"), (1, "bias"))]
-            lw, lb = f"out_layer.mlp.{3 * (layers - 1)}.weight", f"out_layer.mlp.{3 * (layers - 1)}.bias"
             runs = [self._bn_run(bn) for bn in bns]
-            call("gdn_head_train_fwd_act", pt["z"], P("embedding.weight"), *bnp, None, None, 1.0, rng, p_drop, b, n, d,
+            call("gdn_head_train_fwd_act", pt["z"], emb, *self._bn_p, None, None, 1.0, pt["rng"], p_drop, b, n, d,
                  *eps, *run, pt["stats"], pt["act"], 1, st)
-            call("gdn_mlp_train_fwd", pt["act"], arr([P(nm) for nm in names]),
-                 arr([q for r in runs for q in (r[1], r[2])]), arr([r[3] for r in runs]),
-                 (ctypes.c_float * len(bns))(*[float(bn.eps) for bn in bns]),
-                 (ctypes.c_float * len(bns))(*[r[0] for r in runs]), P(lw), P(lb), b * n, d, h, layers,
+            call("gdn_mlp_train_fwd", pt["act"], self._mlp_p, _ptr_array([q for r in runs for q in (r[1], r[2])]),
+                 _ptr_array([r[3] for r in runs]), _float_array([float(bn.eps) for bn in bns]),
+                 _float_array([r[0] for r in runs]), *self._last_p, b * n, d, h, layers,
                  pt["mlp_saved"], pt["mlp_ws"], pt["out"], st)
-        if self._mlp is not None or not self._fuse_mse:
-            call("gdn_mse_loss_grad", pt["out"], self.y.data_ptr(), b * n, pt["mse_ws"], self.loss.data_ptr(), pt["d_out"], st)
-        # backward: gradients land in their slots of flat_g
+
+    def _loss(self, st):
+        pt = self._pt
+        self._lib.call("gdn_mse_loss_grad", pt["out"], pt["y"], self.batch * self.n, pt["mse_ws"], pt["loss"],
+                       pt["d_out"], st)
+
+    def _head_backward(self, p_drop, eps, st):
+        call, pt, emb, d_emb = self._lib.call, self._pt, self._P["embedding.weight"], self._G["embedding.weight"]
+        b, n, d = self.batch, self.n, self.d
         if self._mlp is None:
             # (buffers_zeroed | 2: the head's small finishing reduction runs in the combined tail launch below)
-            call("gdn_head_train_bwd_rng", pt["d_out"], pt["z"], P("embedding.weight"), *bnp, P(lw), rng, p_drop,
-                 pt["stats"], b, n, d, *eps, pt["head_ws"], pt["d_z"], G("embedding.weight"), *bng, G(lw), G(lb), 3, st)
+            call("gdn_head_train_bwd_rng", pt["d_out"], pt["z"], emb, *self._bn_p, self._last_p[0], pt["rng"], p_drop,
+                 pt["stats"], b, n, d, *eps, pt["head_ws"], pt["d_z"], d_emb, *self._bn_g, *self._last_g, 3, st)
         else:
-            call("gdn_mlp_train_bwd", pt["d_out"], pt["act"], arr([P(nm) for nm in names]), P(lw), b * n, d, h, layers,
-                 pt["mlp_saved"], pt["mlp_ws"], arr([G(nm) for nm in names]), G(lw), G(lb), pt["d_act"], st)
-            call("gdn_head_train_bwd_act", pt["d_act"], pt["z"], P("embedding.weight"), *bnp, None, None, 1.0, rng,
-                 p_drop, pt["stats"], b, n, d, *eps, pt["head_ws"], pt["d_z"], G("embedding.weight"), *bng, 1, st)
-        main.wait_stream(side2)                      # reverse lists
-        call("gdn_attn_aggregate_bwd" + self._sfx, pt["d_z"], pt["xlin"], pt["alpha"], pt["s_i"], pt["s_j"], pt["nbr"], pt["rent"],
-             pt["rlen"], b, n, d, k, pt["d_xlin"], pt["d_si"], pt["d_sj"], G(g + "bias"), pt["bwd_ws"], st)
+            h, layers, _bns = self._mlp
+            call("gdn_mlp_train_bwd", pt["d_out"], pt["act"], self._mlp_p, self._last_p[0], b * n, d, h, layers,
+                 pt["mlp_saved"], pt["mlp_ws"], self._mlp_g, *self._last_g, pt["d_act"], st)
+            call("gdn_head_train_bwd_act", pt["d_act"], pt["z"], emb, *self._bn_p, None, None, 1.0, pt["rng"],
+                 p_drop, pt["stats"], b, n, d, *eps, pt["head_ws"], pt["d_z"], d_emb, *self._bn_g, 1, st)
+
+    def _aggregate_backward(self, st):
+        pt = self._pt
+        self._lib.call("gdn_attn_aggregate_bwd" + self._sfx, pt["d_z"], pt["xlin"], pt["alpha"], pt["s_i"], pt["s_j"],
+                       pt["nbr"], pt["rent"], pt["rlen"], self.batch, self.n, self.d, self.k, pt["d_xlin"], pt["d_si"],
+                       pt["d_sj"], self._G["gnn_layers.0.gnn.bias"], pt["bwd_ws"], st)
+
+    def _project_backward_finish(self, st):
+        call, pt, d_lin = self._lib.call, self._pt, self._att_g[0]
+        b, n, w, d = self.batch, self.n, self.w, self.d
         if self._mlp is None:
             # partial rows only; their reduction and the head's finishing reduction share ONE launch
             rows = ctypes.c_int(0)
-            call("gdn_project_bwd_partials", self.x.data_ptr(), pt["d_xlin"], pt["d_si"], pt["d_sj"], b, n, w, d,
+            call("gdn_project_bwd_partials", pt["x"], pt["d_xlin"], pt["d_si"], pt["d_sj"], b, n, w, d,
                  pt["proj_ws"], ctypes.byref(rows), st)
-            call("gdn_train_finish", pt["head_ws"], pt["stats"], 1, b, n, d, G("embedding.weight"), *bng, G(lw), G(lb),
-                 pt["proj_ws"], rows.value, w, G(g + "lin.weight"), pt["d_a"], pt["d_c"], st)
+            call("gdn_train_finish", pt["head_ws"], pt["stats"], 1, b, n, d, self._G["embedding.weight"], *self._bn_g,
+                 *self._last_g, pt["proj_ws"], rows.value, w, d_lin, pt["d_a"], pt["d_c"], st)
         else:
-            call("gdn_project_bwd", self.x.data_ptr(), pt["d_xlin"], pt["d_si"], pt["d_sj"], b, n, w, d, pt["proj_ws"],
-                 G(g + "lin.weight"), pt["d_a"], pt["d_c"], st)
-        call("gdn_terms_bwd_acc", P(g + "lin.weight"), P(g + "att_i"), P(g + "att_j"), P(g + "att_em_i"), P(g + "att_em_j"),
-             P("embedding.weight"), pt["d_a"], pt["d_c"], n, d, w, G(g + "lin.weight"), G(g + "att_i"), G(g + "att_j"),
-             G(g + "att_em_i"), G(g + "att_em_j"), G("embedding.weight"), 1, st)
+            call("gdn_project_bwd", pt["x"], pt["d_xlin"], pt["d_si"], pt["d_sj"], b, n, w, d, pt["proj_ws"],
+                 d_lin, pt["d_a"], pt["d_c"], st)
 
+    def _terms_backward(self, st):
+        pt = self._pt
+        self._lib.call("gdn_terms_bwd_acc", *self._att_p, self._P["embedding.weight"], pt["d_a"], pt["d_c"], self.n,
+                       self.d, self.w, *self._att_g, self._G["embedding.weight"], 1, st)
+
+    # the second half, and what the scaffold asks ---------------------------------------------------------------
     def _all_reduce(self):
         all_reduce_flat(self.flat_g)
 
@@ -1131,55 +1187,14 @@ class NativeTrainStep:
                        self.BETAS[1], self.EPS, self.wd, float(grad_scale), 0, 0,
                        torch.cuda.current_stream().cuda_stream)
 
-    def _capture(self):
-        """Warm up (lazy attribute / occupancy queries) and capture; the warm-up steps are undone: capturing must
-        not train the model."""
-        tensors = [self.flat_p, self.exp_avg, self.exp_avg_sq, self.state] + list(self.model.buffers())
-        saved = [t.detach().clone() for t in tensors]
-        for _ in range(2):
-            self._first()
-            self._all_reduce()
-            self._second()
-        torch.cuda.synchronize()
-        with torch.no_grad():
-            for t, s_ in zip(tensors, saved):
-                t.copy_(s_)
-            self.flat_g.zero_()
-        torch.cuda.synchronize()
-        graphs = []
-        if self._split:
-            for fn in (self._first, self._second):
-                g_ = torch.cuda.CUDAGraph()
-                with capture(g_):
-                    fn()
-                graphs.append(g_)
-        else:
-            g_ = torch.cuda.CUDAGraph()
-            with capture(g_):
-                self._first()
-                self._second()
-            graphs.append(g_)
-        self._graphs = graphs
+    def _update(self):
+        self._adam()
 
-    def prepare(self):
-        """Capture now (the first `step()` otherwise does); see AutogradTrainStep.prepare."""
-        if self.use_graph and self._graphs is None:
-            self._capture()
+    def _saved(self):
+        return [self.flat_p, self.exp_avg, self.exp_avg_sq, self.state] + list(self.model.buffers())
 
-    def step(self):
-        if not self.use_graph:
-            self._first()
-            if self._split:
-                self._all_reduce()
-            self._second()
-        else:
-            self.prepare()
-            self._graphs[0].replay()
-            if self._split:
-                self._all_reduce()
-                self._graphs[1].replay()
-        self.model.invalidate_constants()       # parameters moved under the model's cached eval constants
-        return self.loss
+    def _after_restore(self):
+        self.flat_g.zero_()
 
 
 def GraphedTrainStep(model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
@@ -1188,16 +1203,14 @@ def GraphedTrainStep(model, batch: int, lr: float = 1e-3, weight_decay: float = 
     """The captured training step: `NativeTrainStep` when the model and its shape allow it (plain nn.Dropout, an
     OutLayer and a sensor count the training kernels take), else `AutogradTrainStep`.  `native=False` forces the
     autograd form.  `wide`: the inputs exceed the 16-bit operand range (None: model.operand_range == "wide").
-    `pre` / `post`: launches issued (and captured) right before and right after the step, see NativeTrainStep."""
+    `pre` / `post`: launches issued (and captured) right before and right after the step, see _CapturedStep."""
     if native is None:
         native = NativeTrainStep.applicable(model)
     if wide is None:
         wide = getattr(model, "operand_range", "auto") == "wide"
-    if native:
-        return NativeTrainStep(model, batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph, split=split,
-                               wide=wide, pre=pre, post=post)
-    return AutogradTrainStep(model, batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph, split=split,
-                             wide=wide, pre=pre, post=post)
+    cls = NativeTrainStep if native else AutogradTrainStep
+    return cls(model, batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph, split=split, wide=wide, pre=pre,
+               post=post)
 
 
 # --------------------------------------------------------------------------- epochs from the resident series
@@ -1260,7 +1273,6 @@ def validate_series(model, series, starts, batch: int, wide=None):
     xbuf = _validate_x.get(key)
     if xbuf is None:
         xbuf = _validate_x[key] = torch.empty((chunk * n * w,), dtype=torch.float32, device=dev)
-    before = model.operand_range
     for s in range(0, tv, chunk):
         rows = min(chunk, tv - s)
         x = xbuf[: rows * n * w].view(rows, n, w)
@@ -1268,12 +1280,8 @@ def validate_series(model, series, starts, batch: int, wide=None):
         if fast:
             model.forward_into(x, pred[s:s + rows], wide=wide)
         else:
-            model.operand_range = "wide" if wide else "narrow"
-            try:
-                with torch.no_grad():
-                    pred[s:s + rows].copy_(model(x, None))
-            finally:
-                model.operand_range = before
+            with pinned_range(model, wide), torch.no_grad():
+                pred[s:s + rows].copy_(model(x, None))
     _means, mean = ops.mse_batch_means(pred, gt, batch)
     return float(mean.item()), pred, gt
 
@@ -1340,18 +1348,8 @@ class SeriesTrainer:
                               torch.empty((rest, n), dtype=torch.float32, device=dev))
             x, y = self._tail
             ops.windows_gather(self.series, self.table, rest, self.w, x, y, first=full * self.batch, count=total)
-            before = self.model.operand_range
-            self.model.operand_range = "wide" if self.wide else "narrow"
-            try:
-                self.optimizer.zero_grad()
-                out = self.model(x, None)
-                loss = F.mse_loss(out, y, reduction="mean")
-                loss.backward()
-                sync_gradients(self.model)
-                self.optimizer.step()
-            finally:
-                self.model.operand_range = before
-            self.loss_table[full].copy_(loss.detach())
+            with pinned_range(self.model, self.wide):
+                self.loss_table[full].copy_(_eager_step(self.model, self.optimizer, x, y))
             steps += 1
         return self.loss_table[:steps].tolist() if steps else []
 
@@ -1366,9 +1364,8 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
     epoch's order (`epoch_order`: the shuffles and the generator's state are those of a run that iterates it, the
     validation loader's per-epoch draw included) — or a tensor of target ticks, taken in the given order.
     `use_graph` None: config["hip_graph"], default True.  One process only."""
-    from ._lib import GdnHipError
     if world()[1] > 1:
-        raise GdnHipError("train_series runs in one process: sharding an epoch of the resident series across ranks is "
+        raise _lib.GdnHipError("train_series runs in one process: sharding an epoch of the resident series across ranks is "
                           "not implemented (harness.train with per-rank loaders does data-parallel training)")
     config = config or {}
     if use_graph is None:
@@ -1386,7 +1383,7 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
         # the resident series is there to be looked at: all of it, not the first batch (the weights move: margin)
         wide = model.train().input_exceeds_limit(series, margin=16.0)
     trainer = None
-    losses, min_loss, stale = [], 1e8, 0
+    losses, best = [], _BestSoFar()
     for _epoch in range(config.get("epoch", 1)):
         order = epoch_order(train_loader) if train_loader is not None else torch.arange(train_starts.numel())
         if trainer is None:
@@ -1394,23 +1391,13 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
                                     lr=0.001, weight_decay=config.get("decay", 0), wide=wide, use_graph=use_graph)
         step_losses = trainer.epoch(order)
         losses.extend(step_losses)
-        acc = float(sum(step_losses))
+        val_loss = None
         if val_ticks is not None:
             if val_loader is not None:
                 epoch_order(val_loader)                  # what iterating the validation loader draws
-            val_loss, _pred, _gt = validate_series(model, series, val_ticks, val_batch)
-            if val_loss < min_loss:
-                if save_path:
-                    torch.save(model.state_dict(), save_path)
-                min_loss, stale = val_loss, 0
-            else:
-                stale += 1
-            if stale >= 15:
-                break
-        elif acc < min_loss:
-            if save_path:
-                torch.save(model.state_dict(), save_path)
-            min_loss = acc
+            val_loss = validate_series(model, series, val_ticks, val_batch)[0]
+        if best.update(val_loss, float(sum(step_losses)), model, save_path):
+            break
     return losses
 
 

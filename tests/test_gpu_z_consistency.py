@@ -64,6 +64,53 @@ def test_graphed_train_step_equals_eager_steps(split, gpu_device):
     assert min(finals[1][0]) < finals[1][0][0]          # it trains
 
 
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("native", [True, False])
+def test_hooks_run_once_per_step_in_one_graph_and_in_two(native, split, gpu_device):
+    """`pre` / `post` of both step forms, in one graph and in two around the all-reduce: each hook runs exactly once
+    per step, eager or replayed, and once per warm-up step of the capture (2 native, 3 autograd), which leaves the
+    parameters where they were; a replayed run equals the eager one bit for bit; hooks that touch nothing of the
+    step change nothing (native: the run without hooks is the same run)."""
+    from gdn_amd import harness
+    from test_gpu_forward_parity import random_params
+    b = 64
+    g = torch.Generator().manual_seed(5)
+    xs = torch.rand((4, b, 27, 10), generator=g).to(gpu_device)
+    ys = torch.rand((4, b, 27), generator=g).to(gpu_device)
+
+    def run(use_graph, hooks):
+        model = random_params(27, 10, 8, 64, seed=3).to(gpu_device)
+        model.dp.p = 0.0
+        pre_n = torch.zeros((), dtype=torch.int64, device=gpu_device)
+        post_n = torch.zeros((), dtype=torch.int64, device=gpu_device)
+        step = harness.GraphedTrainStep(model, b, use_graph=use_graph, split=split, native=native,
+                                        pre=(lambda: pre_n.add_(1)) if hooks else None,
+                                        post=(lambda: post_n.add_(1)) if hooks else None)
+        assert isinstance(step, harness.NativeTrainStep) == native
+        if use_graph:
+            before = [p.detach().clone() for p in model.parameters()]
+            step._capture()
+            for p, q in zip(model.parameters(), before):
+                assert torch.equal(p, q)
+        start = (int(pre_n), int(post_n))
+        if use_graph:
+            assert start == (((2, 2) if native else (3, 3)) if hooks else (0, 0))
+        losses = []
+        for i in range(4):
+            step.x.copy_(xs[i]); step.y.copy_(ys[i])
+            losses.append(step.step().clone())
+        assert (int(pre_n) - start[0], int(post_n) - start[1]) == ((4, 4) if hooks else (0, 0))
+        return [torch.stack(losses)] + [t.detach().clone() for t in list(model.parameters()) + list(model.buffers())]
+
+    eager, graphed = run(False, True), run(True, True)
+    assert len(eager) == len(graphed)
+    for i, (a, c) in enumerate(zip(eager, graphed)):
+        assert torch.equal(a, c), (i, float((a.double() - c.double()).abs().max()))
+    if native:
+        for i, (a, c) in enumerate(zip(run(True, False), graphed)):
+            assert torch.equal(a, c), i
+
+
 def test_harness_train_graph_mode_matches_eager(gpu_device, tmp_path):
     """train(use_graph=True): full minibatches replay the captured step, the ragged last batch runs
     eagerly with the same optimizer; same losses, same checkpoint as the eager loop."""
