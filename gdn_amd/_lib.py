@@ -6,11 +6,12 @@ a HIP device, every op raises.  Build with `python -c "import __graft_entry__ as
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GDN_HIP_LIB", os.path.join(_HERE, "libgdn_hip.so"))   # override: diagnostic builds
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _c_int, _c_float, _p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -25,6 +26,7 @@ SIGNATURES = {
     "gdn_project_fwd": [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gdn_project_fwd_series": [_p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gdn_tile_fits": [_c_int] * 4,
+    "gdn_kernel_family": [_c_int] * 6,
     "gdn_terms_pitch": [_c_int],
     "gdn_attn_aggregate_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
     "gdn_head_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p],
@@ -106,6 +108,18 @@ SIGNATURES = {
     "gdn_stream_score": [_p] * 5 + [_c_int] * 4 + [_p] * 4,
     "gdn_stream_advance": [_p] * 6 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p],
 }
+
+# gdn_kernel_family's enums (include/gdn_hip.h "route table")
+FAMILY_NONE, FAMILY_DENSE, FAMILY_TILE, FAMILY_LARGE, FAMILY_LONG, FAMILY_ANY = range(6)
+STAGE_PROJECT, STAGE_AGGREGATE, STAGE_ATTN_BWD, STAGE_PROJECT_BWD, STAGE_TERMS, STAGE_HEAD, STAGE_FUSED = range(7)
+ROUTE_WIDE, ROUTE_BF16, ROUTE_SERIES = 1, 2, 4
+
+
+@functools.lru_cache(maxsize=None)      # a constant of the process per shape: eager callers ask on every launch
+def family(stage: int, n: int, w: int, d: int, k: int, flags: int = 0) -> int:
+    """The kernel family the library runs `stage` with at this shape (gdn_kernel_family, host only)."""
+    return load().gdn_kernel_family(stage, n, w, d, k, flags) & 0xff
+
 
 ERRORS = {-1: "GDN_ERR_ARG (null pointer or non-positive dimension)",
           -2: "GDN_ERR_LAUNCH (HIP launch failed)",

@@ -586,94 +586,74 @@ static bool bwd_plan(int batch, int n, int d, int k, bool with_tables, BwdPlan* 
   return pl->lds_bytes <= 160 * 1024;
 }
 
-// GDN_BWD_SLICED=1 (read once per process): d = 128 always walks two 64-column slices (A/B against the whole tile)
-static bool gdn_bwd_sliced_forced() { return GDN_ENV_INT_ONCE("GDN_BWD_SLICED", 0) != 0; }
+// bwd_plan's ladder, asked by gdn_route: the sub-form of the TILE backward — tables in LDS, tables through the
+// workspace, two 64-column slices (d = 128; `force_sliced`: always) — or -1 where not even the sliced tile fits
+int gdn_tile_attn_bwd_form(int n, int d, int k, bool force_sliced) {
+  BwdPlan pl;
+  if (!(force_sliced && d == 128)) {
+    if (bwd_plan(1, n, d, k, true, &pl)) return GDN_BWD_TABLES_LDS;
+    if (bwd_plan(1, n, d, k, false, &pl)) return GDN_BWD_TABLES_GLOBAL;
+  }
+  return d == 128 && bwd_plan(1, n, d, k, false, &pl, 64) ? GDN_BWD_SLICED : -1;
+}
 
 // workspace = [ticket + GDN_COLSUM_MAX_ROWS partial rows of d_bias][d_pi tables when they do not fit LDS]
 static long long bwd_bias_ws_floats(int d) { return GDN_COLSUM_WS_HEAD + (long long)GDN_COLSUM_MAX_ROWS * d; }
 
 extern "C" long long gdn_attn_aggregate_bwd_workspace_bytes(int batch, int n, int d, int k) {
   if (batch <= 0 || n <= 0 || k <= 0 || k > n || d <= 0) return 0;
-  BwdPlan pl;
+  int form = -1;
+  const int fam = gdn_route(GDN_STAGE_ATTN_BWD, n, 1, d, k, GDN_ROUTE_WIDE, &form);
   long long floats = bwd_bias_ws_floats(d);
-  if (gdn_any_width(d))   // gdn_any_width.hip: the d_pi table always goes through the workspace
-    return (floats + (long long)batch * n * gdn_nbr_pitch(k)) * (long long)sizeof(float);
-  if (!bwd_plan(batch, n, d, k, true, &pl) || (d == 128 && gdn_bwd_sliced_forced()))
-    floats += (long long)batch * n * gdn_nbr_pitch(k);   // tables beyond LDS
+  if (fam != GDN_FAMILY_TILE || form != GDN_BWD_TABLES_LDS)   // the d_pi table [batch*n, pitch] beyond LDS
+    floats += (long long)batch * n * gdn_nbr_pitch(k);
   return floats * (long long)sizeof(float);
 }
 
-// GDN_BWD_PATH=valu (read once per process) keeps the row-gather backward at every shape (A/B runs)
-static bool gdn_bwd_valu_forced() {
-  static const bool valu_bwd = [] { const char* e = getenv("GDN_BWD_PATH"); return e && e[0] == 'v'; }();
-  return valu_bwd;
-}
-
-// 1 when gdn_attn_aggregate_bwd reads the reverse lists (gdn_graph_reverse) at this shape, 0 when it runs
-// the matrix-core backward, which does not (rent / rlen may then be null and the launch can be skipped)
-extern "C" int gdn_attn_aggregate_bwd_uses_reverse(int n, int d, int k) {
-  if (n <= 0 || k <= 0 || k > n) return 1;
-  return (d == 64 && !gdn_bwd_valu_forced() && gdn_use_dense_path() && gdn_dense_supported(n, 1, d, k)) ? 0 : 1;
-}
-
-static int attn_aggregate_bwd_impl(const float* d_z, const float* xlin, const float* alpha,
-                                   const float* s_i, const float* s_j, const uint16_t* nbr,
-                                   const uint32_t* rent, const int32_t* rlen, int batch, int n, int d,
-                                   int k, float* d_xlin, float* d_si, float* d_sj, float* d_bias,
-                                   float* workspace, void* stream, bool wide) {
-  const bool dense = !wide && !gdn_attn_aggregate_bwd_uses_reverse(n, d, k);
+static int attn_aggregate_bwd_impl(const float* d_z, const float* xlin, const float* alpha, const float* s_i,
+                                   const float* s_j, const uint16_t* nbr, const uint32_t* rent, const int32_t* rlen,
+                                   int batch, int n, int d, int k, float* d_xlin, float* d_si, float* d_sj,
+                                   float* d_bias, float* workspace, void* stream, int flags) {
+  int form = -1;
+  const int fam = gdn_route(GDN_STAGE_ATTN_BWD, n, 1, d, k, flags, &form);
   if (!d_z || !xlin || !alpha || !s_i || !s_j || !nbr || !d_xlin || !d_si || !d_sj || !d_bias || !workspace ||
       batch <= 0 || n <= 0 || k <= 0)
     return GDN_ERR_ARG;
-  if ((!rent || !rlen) && !dense) return GDN_ERR_ARG;
-  if (gdn_any_width(d))   // embedding widths other than the four: gdn_any_width.hip
-    return gdn_any_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj, d_bias,
-                            workspace, bwd_bias_ws_floats(d), (hipStream_t)stream);
-  if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
-  if (k > n || n > 4096 || k + 1 > 1024) return GDN_ERR_UNSUPPORTED;
-  BwdPlan pl;
-  bool glb = false, sliced = false;
-  if (gdn_bwd_sliced_forced() && d == 128) {
-    if (!bwd_plan(batch, n, d, k, false, &pl, 64)) return GDN_ERR_UNSUPPORTED;
-    glb = sliced = true;
-  } else if (!bwd_plan(batch, n, d, k, true, &pl)) {
-    // tables through global memory (the workspace behind the d_bias rows); the tile alone must still fit,
-    // whole or (d = 128) as two 64-column slices the workgroup walks one after the other
-    glb = true;
-    if (!bwd_plan(batch, n, d, k, false, &pl)) {
-      if (d != 128 || !bwd_plan(batch, n, d, k, false, &pl, 64))   // beyond the tile: gdn_large.hip
-        return gdn_large_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj,
-                                  d_bias, workspace, bwd_bias_ws_floats(d), (hipStream_t)stream);
-      sliced = true;
-    }
-  }
+  if ((!rent || !rlen) && fam != GDN_FAMILY_DENSE) return GDN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  switch (fam) {
+    case GDN_FAMILY_ANY:
+      return gdn_any_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj, d_bias,
+                              workspace, bwd_bias_ws_floats(d), st);
+    case GDN_FAMILY_LARGE:
+      return gdn_large_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj,
+                                d_bias, workspace, bwd_bias_ws_floats(d), st);
+    case GDN_FAMILY_DENSE:   // both halves of the backward as dense products (gdn_forward_dense.hip)
+      return gdn_dense_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, batch, n, k, d_xlin, d_si, d_sj, d_bias, workspace, st);
+    case GDN_FAMILY_TILE: break;
+    default: return GDN_ERR_UNSUPPORTED;
+  }
+  // tables in LDS, or in global memory (the workspace behind the d_bias rows) where only the tile fits, whole or sliced
+  const bool glb = form != GDN_BWD_TABLES_LDS, sliced = form == GDN_BWD_SLICED;
+  BwdPlan pl;
+  bwd_plan(batch, n, d, k, !glb, &pl, sliced ? 64 : 0);
   float* dpi_ws = workspace + bwd_bias_ws_floats(d);
   const bool many_rows = n * (d / 64 > 0 ? d / 64 : 1) > 64;   // enough rows for 32 lane groups
-  // matrix-core shapes: both halves of the backward as dense products (gdn_forward_dense.hip)
-  if (dense)
-    return gdn_dense_attn_bwd(d_z, xlin, alpha, s_i, s_j, nbr, batch, n, k, d_xlin, d_si, d_sj, d_bias, workspace, st);
-#define GDN_BWD_NT(DD, NT, GL)                                                                        \
+#define GDN_BWD_NT(NT, ...)   /* __VA_ARGS__: the kernel's template arguments */                    \
   {                                                                                                   \
-    const int grid = min(occupancy_grid(gdn_attn_bwd_kernel<DD, NT, GL>, NT, pl.lds_bytes, batch),    \
+    const int grid = min(occupancy_grid(gdn_attn_bwd_kernel<__VA_ARGS__>, NT, pl.lds_bytes, batch),   \
                          GDN_COLSUM_MAX_ROWS);                                                        \
-    hipLaunchKernelGGL((gdn_attn_bwd_kernel<DD, NT, GL>), dim3(grid), dim3(NT), pl.lds_bytes, st, pl, d_z, xlin, \
+    hipLaunchKernelGGL((gdn_attn_bwd_kernel<__VA_ARGS__>), dim3(grid), dim3(NT), pl.lds_bytes, st, pl, d_z, xlin, \
                        alpha, s_i, s_j, nbr, rent, rlen, d_xlin, d_si, d_sj, d_bias, dpi_ws, workspace); \
   }
 #define GDN_BWD(DD)                                                   \
   case DD:                                                            \
-    if (glb) GDN_BWD_NT(DD, 512, true)                                \
-    else if (many_rows) GDN_BWD_NT(DD, 512, false)                         \
-    else GDN_BWD_NT(DD, 256, false)                                   \
+    if (glb) GDN_BWD_NT(512, DD, 512, true)                           \
+    else if (many_rows) GDN_BWD_NT(512, DD, 512, false)               \
+    else GDN_BWD_NT(256, DD, 256, false)                              \
     break;
-  if (sliced) {
-    const int grid = min(occupancy_grid(gdn_attn_bwd_kernel<64, 512, true, true, 2>, 512, pl.lds_bytes, batch),
-                         GDN_COLSUM_MAX_ROWS);
-    hipLaunchKernelGGL((gdn_attn_bwd_kernel<64, 512, true, true, 2>), dim3(grid), dim3(512), pl.lds_bytes, st, pl,
-                       d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, d_xlin, d_si, d_sj, d_bias, dpi_ws, workspace);
-    return gdn_launch_status();
-  }
-  switch (d) {
+  if (sliced) GDN_BWD_NT(512, 64, 512, true, true, 2)
+  else switch (d) {
     GDN_BWD(16)
     GDN_BWD(32)
     GDN_BWD(64)
@@ -684,45 +664,35 @@ static int attn_aggregate_bwd_impl(const float* d_z, const float* xlin, const fl
   return gdn_launch_status();
 }
 
-extern "C" int gdn_attn_aggregate_bwd(const float* d_z, const float* xlin, const float* alpha,
-                                      const float* s_i, const float* s_j, const uint16_t* nbr,
-                                      const uint32_t* rent, const int32_t* rlen, int batch, int n, int d,
-                                      int k, float* d_xlin, float* d_si, float* d_sj, float* d_bias,
-                                      float* workspace, void* stream) {
+extern "C" int gdn_attn_aggregate_bwd(const float* d_z, const float* xlin, const float* alpha, const float* s_i,
+                                      const float* s_j, const uint16_t* nbr, const uint32_t* rent, const int32_t* rlen,
+                                      int batch, int n, int d, int k, float* d_xlin, float* d_si, float* d_sj,
+                                      float* d_bias, float* workspace, void* stream) {
   return attn_aggregate_bwd_impl(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj,
-                                 d_bias, workspace, stream, false);
+                                 d_bias, workspace, stream, 0);
 }
 // `_wide`: the row-gather backward at every shape (reverse lists required)
-extern "C" int gdn_attn_aggregate_bwd_wide(const float* d_z, const float* xlin, const float* alpha,
-                                           const float* s_i, const float* s_j, const uint16_t* nbr,
-                                           const uint32_t* rent, const int32_t* rlen, int batch, int n, int d,
-                                           int k, float* d_xlin, float* d_si, float* d_sj, float* d_bias,
-                                           float* workspace, void* stream) {
+extern "C" int gdn_attn_aggregate_bwd_wide(const float* d_z, const float* xlin, const float* alpha, const float* s_i,
+                                           const float* s_j, const uint16_t* nbr, const uint32_t* rent,
+                                           const int32_t* rlen, int batch, int n, int d, int k, float* d_xlin,
+                                           float* d_si, float* d_sj, float* d_bias, float* workspace, void* stream) {
   return attn_aggregate_bwd_impl(d_z, xlin, alpha, s_i, s_j, nbr, rent, rlen, batch, n, d, k, d_xlin, d_si, d_sj,
-                                 d_bias, workspace, stream, true);
+                                 d_bias, workspace, stream, GDN_ROUTE_WIDE);
 }
 
-// 1 when every kernel of a training step (staged forward, this file's backward) takes the shape: what
-// harness.NativeTrainStep.applicable() asks before it commits to the captured step
-extern "C" int gdn_train_supported(int n, int w, int d, int k) {
-  if (n <= 0 || w <= 0 || k <= 0 || k > n || n > 4096 || k + 1 > 1024 || w > GDN_MAX_W) return 0;
-  if (d != 16 && d != 32 && d != 64 && d != 128) return 0;
-  BwdPlan pl;
-  if (!bwd_plan(1, n, d, k, true, &pl) && !bwd_plan(1, n, d, k, false, &pl) &&
-      !(d == 128 && bwd_plan(1, n, d, k, false, &pl, 64)))
-    return 0;
-  const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
-  int rc = (24576 - 2 * n) / (wp + d + 2);                  // gdn_project_bwd's staging chunk
-  if (rc < 1) return 0;
-  return gdn_forward_staged_ok(n, w, d, k);
-}
+// gdn_project_bwd's padded window, and its rows per staged chunk: the whole window when it fits ~96 KB (three
+// workgroups per CU at the SWaT shape); < 1: the tile kernel does not take the shape
+static int pbwd_wp(int w) { return w <= 8 ? 8 : ((w + 15) & ~15); }
+static int pbwd_chunk_rows(int n, int w, int d) { return min(n, (24576 - 2 * n) / (pbwd_wp(w) + d + 2)); }
+bool gdn_tile_project_bwd_ok(int n, int w, int d) { return pbwd_chunk_rows(n, w, d) >= 1; }   // (asked by gdn_route)
 
 extern "C" long long gdn_project_bwd_workspace_bytes(int n, int w, int d) {
-  if (n <= 0 || w <= 0 || d <= 0) return 0;
-  if (gdn_any_width(d)) return gdn_any_project_bwd_workspace_bytes(n, w, d);
-  if (w > GDN_MAX_W) return gdn_long_project_bwd_workspace_bytes(n, w, d);
-  const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
-  return (long long)GDN_PBWD_MAX_ROWS * (d * wp + 128 + 2 * n) * (long long)sizeof(float);
+  switch (gdn_route(GDN_STAGE_PROJECT_BWD, n, w, d, 0, 0)) {
+    case GDN_FAMILY_ANY: return gdn_any_project_bwd_workspace_bytes(n, w, d);
+    case GDN_FAMILY_LONG: return gdn_long_project_bwd_workspace_bytes(n, w, d);
+    case GDN_FAMILY_TILE: return (long long)GDN_PBWD_MAX_ROWS * (d * pbwd_wp(w) + 128 + 2 * n) * (long long)sizeof(float);
+  }
+  return 0;
 }
 
 // first half of gdn_project_bwd: the per-workgroup partial rows; *rows_out = how many there are
@@ -730,21 +700,15 @@ extern "C" int gdn_project_bwd_partials(const float* x, const float* d_xlin, con
                                         int batch, int n, int w, int d, float* workspace, int* rows_out,
                                         void* stream) {
   if (!x || !d_xlin || !d_si || !d_sj || !workspace || !rows_out || batch <= 0 || n <= 0 || w <= 0) return GDN_ERR_ARG;
-  if (gdn_any_width(d))   // embedding widths other than the four: partial [d + 2, w] blocks (gdn_any_width.hip)
-    return gdn_any_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out,
-                                        (hipStream_t)stream);
-  if (d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
-  if (w > GDN_MAX_W)   // long windows: partial [d + 2, w] blocks (gdn_long_window.hip)
-    return gdn_long_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out,
-                                         (hipStream_t)stream);
-  if (n > 4096) return GDN_ERR_UNSUPPORTED;
-  const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
-  // rows per staged chunk: whole window when it fits ~96 KB (three workgroups per CU at the SWaT shape)
-  int rc = (24576 - 2 * n) / (wp + d + 2);
-  if (rc > n) rc = n;
-  if (rc < 1) return GDN_ERR_UNSUPPORTED;
-  const int lds = (max(rc * (wp + d + 2), 16 * 256) + 2 * n) * 4;
   hipStream_t st = (hipStream_t)stream;
+  switch (gdn_route(GDN_STAGE_PROJECT_BWD, n, w, d, 0, 0)) {   // ANY / LONG: partial [d + 2, w] blocks
+    case GDN_FAMILY_ANY: return gdn_any_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out, st);
+    case GDN_FAMILY_LONG: return gdn_long_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, rows_out, st);
+    case GDN_FAMILY_TILE: break;
+    default: return GDN_ERR_UNSUPPORTED;
+  }
+  const int wp = pbwd_wp(w), rc = pbwd_chunk_rows(n, w, d);
+  const int lds = (max(rc * (wp + d + 2), 16 * 256) + 2 * n) * 4;
   int grid = 1;
 #define GDN_PB(DD)                                                                                  \
   case DD: {                                                                                        \
@@ -766,21 +730,14 @@ extern "C" int gdn_project_bwd_partials(const float* x, const float* d_xlin, con
 extern "C" int gdn_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj,
                                int batch, int n, int w, int d, float* workspace, float* d_lin_w, float* d_a,
                                float* d_c, void* stream) {
-  if (!d_lin_w || !d_a || !d_c) return GDN_ERR_ARG;
-  if (gdn_any_width(d)) {
-    if (!x || !d_xlin || !d_si || !d_sj || !workspace || batch <= 0 || n <= 0 || w <= 0) return GDN_ERR_ARG;
-    return gdn_any_project_bwd(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, d_lin_w, d_a, d_c,
-                               (hipStream_t)stream);
-  }
-  if (w > GDN_MAX_W) {
-    if (!x || !d_xlin || !d_si || !d_sj || !workspace || batch <= 0 || n <= 0) return GDN_ERR_ARG;
-    return gdn_long_project_bwd(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, d_lin_w, d_a, d_c,
-                                (hipStream_t)stream);
-  }
+  if (!x || !d_xlin || !d_si || !d_sj || !workspace || !d_lin_w || !d_a || !d_c || batch <= 0 || n <= 0 || w <= 0)
+    return GDN_ERR_ARG;
   int rows = 0;
   const int rc = gdn_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, &rows, stream);
   if (rc != GDN_OK) return rc;
-  const int wp = w <= 8 ? 8 : ((w + 15) & ~15);
+  if (gdn_route(GDN_STAGE_PROJECT_BWD, n, w, d, 0, 0) != GDN_FAMILY_TILE)   // ANY / LONG: blocks, added in range order
+    return gdn_long_project_reduce(workspace, rows, batch, n, w, d, d_si, d_sj, d_lin_w, d_a, d_c, (hipStream_t)stream);
+  const int wp = pbwd_wp(w);
   const int len = d * wp + 128 + 2 * n;
   hipLaunchKernelGGL(gdn_project_reduce_kernel, dim3((len + 15) / 16), dim3(256), 0, (hipStream_t)stream, workspace,
                      rows, d, n, w, wp, d_lin_w, d_a, d_c);
@@ -795,10 +752,14 @@ extern "C" int gdn_terms_bwd_acc(const float* lin_w, const float* att_i, const f
   if (!lin_w || !att_i || !att_j || !att_em_i || !att_em_j || !emb || !d_a || !d_c || !d_lin_w || !d_att_i ||
       !d_att_j || !d_att_em_i || !d_att_em_j || !d_emb || n <= 0 || d <= 0 || w <= 0)
     return GDN_ERR_ARG;
-  if (w > GDN_MAX_W || gdn_any_width(d))   // long windows / other widths: d_a at pitch gdn_terms_pitch(w), run-time d
-    return gdn_long_terms_bwd(lin_w, att_i, att_j, att_em_i, att_em_j, emb, d_a, d_c, n, d, w, d_lin_w, d_att_i,
-                              d_att_j, d_att_em_i, d_att_em_j, d_emb, accumulate_emb, (hipStream_t)stream);
-  if (d > 256 || (256 % d) != 0) return GDN_ERR_UNSUPPORTED;
+  switch (gdn_route(GDN_STAGE_TERMS, n, w, d, 0, 0)) {
+    case GDN_FAMILY_LONG:
+    case GDN_FAMILY_ANY:   // long windows / other widths: d_a at pitch gdn_terms_pitch(w), run-time d
+      return gdn_long_terms_bwd(lin_w, att_i, att_j, att_em_i, att_em_j, emb, d_a, d_c, n, d, w, d_lin_w, d_att_i,
+                                d_att_j, d_att_em_i, d_att_em_j, d_emb, accumulate_emb, (hipStream_t)stream);
+    case GDN_FAMILY_TILE: break;
+    default: return GDN_ERR_UNSUPPORTED;
+  }
   int grid = (n * d + 1024 * 2 - 1) / (1024 * 2);
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(gdn_terms_bwd_kernel, dim3(grid), dim3(1024), 0, (hipStream_t)stream, lin_w, att_i, att_j,

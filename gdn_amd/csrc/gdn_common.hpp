@@ -26,7 +26,16 @@ int gdn_blocks_per_cu(const void* fn, int threads, int lds);
 #define GDN_ENV_INT_ONCE(NAME, FALLBACK) \
   ([]() -> int { static const int v = [] { const char* e = getenv(NAME); return e ? atoi(e) : (FALLBACK); }(); return v; }())
 
-int gdn_forward_staged_ok(int n, int w, int d, int k);        // gdn_forward.hip: the staged forward takes the shape
+// gdn_route.hip: THE kernel-family decision of the staged graph layer (include/gdn_hip.h "route table"): GDN_FAMILY_* of
+// `stage` at (n, w, d, k) under GDN_ROUTE_* flags; dimensions a stage does not depend on are ignored.  Pure host
+// arithmetic.  *bwd_form (ATTN_BWD, family TILE): GDN_BWD_* below, the sub-form that decides the workspace layout.
+int gdn_route(int stage, int n, int w, int d, int k, int flags, int* bwd_form = nullptr);
+int gdn_forward_staged_ok(int n, int w, int d, int k);        // the tile kernels take both stages of the staged forward
+// the LDS budgets of the tile kernels, asked by gdn_route: make_plan (gdn_forward.hip), bwd_plan and the projection
+// backward's staging chunk (gdn_backward.hip)
+bool gdn_tile_forward_ok(int stage, int n, int w, int d, int k, bool series);
+int gdn_tile_attn_bwd_form(int n, int d, int k, bool force_sliced);   // GDN_BWD_*, or -1 beyond the tile
+bool gdn_tile_project_bwd_ok(int n, int w, int d);
 // gdn_forward_dense.hip: the matrix-core aggregation path (n <= 127, d = 64); x is fp32 or bf16 bits
 bool gdn_dense_supported(int n, int w, int d, int k);         // staged kernels: d = 64
 bool gdn_dense_fused_supported(int n, int w, int d, int k);   // fused kernel: d = 64 or 128
@@ -43,8 +52,8 @@ int gdn_dense_attn_bwd(const float* d_z, const float* xlin, const float* alpha, 
                        float* d_bias, float* bias_ws, hipStream_t stream);   // matrix-core backward of the gather-aggregate
 int gdn_dense_project(const void* x, int is_bf16, const float* lin_w, const float* node_terms, int batch, int n,
                       int w, int d, void* xlin, float* s_i, float* s_j, hipStream_t stream);
-// gdn_large.hip: the graph layer beyond the LDS tile (n up to 4096, xlin gathered from global memory); the staged
-// entry points call these where make_plan / bwd_plan refuse the shape.  x rows at xb + b*bstride + s*sstride.
+// gdn_large.hip: the graph layer beyond the LDS tile (n up to 4096, xlin gathered from global memory): family LARGE,
+// where make_plan / bwd_plan refuse the shape.  x rows at xb + b*bstride + s*sstride.
 int gdn_large_project(const float* xb, long long bstride, long long sstride, const float* lin_w, const float* terms,
                       int batch, int n, int w, int d, float* xlin, float* s_i, float* s_j, hipStream_t stream);
 int gdn_large_aggregate(const float* xlin, const float* s_i, const float* s_j, const uint16_t* nbr, const float* bias,
@@ -53,8 +62,8 @@ int gdn_large_attn_bwd(const float* d_z, const float* xlin, const float* alpha, 
                        const uint16_t* nbr, const uint32_t* rent, const int32_t* rlen, int batch, int n, int d, int k,
                        float* d_xlin, float* d_si, float* d_sj, float* d_bias, float* workspace,
                        long long bias_ws_floats, hipStream_t stream);
-// gdn_long_window.hip: windows longer than GDN_MAX_W (up to GDN_LONG_MAX_W); the entry points hand every w > 64
-// call to these before any other path.  Node terms at pitch gdn_terms_pitch(w); x rows as gdn_large_project's.
+// gdn_long_window.hip: windows longer than GDN_MAX_W (up to GDN_LONG_MAX_W): family LONG.  Node terms at pitch
+// gdn_terms_pitch(w); x rows as gdn_large_project's.
 int gdn_long_node_terms(const float* lin_w, const float* att_i, const float* att_j, const float* att_em_i,
                         const float* att_em_j, const float* emb, int n, int d, int w, float* node_terms,
                         hipStream_t stream);
@@ -63,16 +72,14 @@ int gdn_long_project(const float* xb, long long bstride, long long sstride, cons
 long long gdn_long_project_bwd_workspace_bytes(int n, int w, int d);
 int gdn_long_project_bwd_partials(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch,
                                   int n, int w, int d, float* workspace, int* parts_out, hipStream_t stream);
-int gdn_long_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch, int n,
-                         int w, int d, float* workspace, float* d_lin_w, float* d_a, float* d_c, hipStream_t stream);
 int gdn_long_terms_bwd(const float* lin_w, const float* att_i, const float* att_j, const float* att_em_i,
                        const float* att_em_j, const float* emb, const float* d_a, const float* d_c, int n, int d, int w,
                        float* d_lin_w, float* d_att_i, float* d_att_j, float* d_att_em_i, float* d_att_em_j,
                        float* d_emb, int accumulate_emb, hipStream_t stream);
 int gdn_long_project_reduce(const float* part, int parts, int batch, int n, int w, int d, const float* d_si,
                             const float* d_sj, float* d_lin_w, float* d_a, float* d_c, hipStream_t stream);
-// gdn_any_width.hip: embedding widths other than 16 / 32 / 64 / 128 (1 <= d <= GDN_ANY_MAX_D); the staged entry points
-// hand every such d to these before any other path, at every n, w, k of the envelope.  Dense [B*n, d] rows.
+// gdn_any_width.hip: embedding widths other than 16 / 32 / 64 / 128 (1 <= d <= GDN_ANY_MAX_D): family ANY, at every
+// n, w, k of the envelope.  Dense [B*n, d] rows.
 #define GDN_ANY_MAX_D 256
 bool gdn_any_width(int d);
 int gdn_any_project(const float* xb, long long bstride, long long sstride, const float* lin_w, const float* terms,
@@ -89,18 +96,6 @@ int gdn_any_head(const float* z, const float* emb, const float* bn1_affine, cons
 long long gdn_any_project_bwd_workspace_bytes(int n, int w, int d);
 int gdn_any_project_bwd_partials(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch,
                                  int n, int w, int d, float* workspace, int* parts_out, hipStream_t stream);
-int gdn_any_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch, int n,
-                        int w, int d, float* workspace, float* d_lin_w, float* d_a, float* d_c, hipStream_t stream);
-// run-time choice between the two fused forward implementations: GDN_FUSED_PATH=valu keeps the fp32 VALU
-// row-gather kernel for every shape (read once per process)
-static inline bool gdn_use_dense_path() {
-  static const int use = [] {
-    const char* e = getenv("GDN_FUSED_PATH");
-    return (e && e[0] == 'v') ? 0 : 1;
-  }();
-  return use != 0;
-}
-
 // ---- DPP within a 16-lane row ------------------------------------------------------
 // dpp_ctrl encodings (gfx9): quad_perm 0x00-0xFF, row_ror:n 0x120+n, row_mirror 0x140,
 // row_half_mirror 0x141.

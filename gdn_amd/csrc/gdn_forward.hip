@@ -1268,117 +1268,106 @@ int dispatch_window(const Plan& pl, const Args& a, int threads, hipStream_t stre
 
 }  // namespace
 
-// 1 when the one-launch fused forward (the window's tile in LDS) takes this shape
-extern "C" int gdn_tile_fits(int n, int w, int d, int k) {
-  if (n <= 0 || w <= 0 || d <= 0 || k <= 0) return 0;
+// make_plan's LDS budget, asked by gdn_route (`series`: windows read from the raw series: the MFMA-projection variants)
+bool gdn_tile_forward_ok(int stage, int n, int w, int d, int k, bool series) {
   Plan pl; int threads;
-  return make_plan(MODE_FUSED, 1, n, w, d, k, &pl, &threads) == GDN_OK;
+  const int mode = stage == GDN_STAGE_PROJECT ? MODE_PROJECT : stage == GDN_STAGE_AGGREGATE ? MODE_ATTN : MODE_FUSED;
+  return make_plan(mode, 1, n, w, d, k, &pl, &threads) == GDN_OK && (!series || pl.mfma);
 }
 
-// gdn_project_fwd on windows read straight from the raw series [n, series_len]: window b = series[:, first + b :
-// first + b + w].  The streaming row kernel at every shape (the same bits as gdn_project_fwd gives beyond the tile).
-extern "C" int gdn_project_fwd_series(const float* series, int series_len, int first, const float* lin_w,
-                                      const float* node_terms, int batch, int n, int w, int d, float* xlin,
-                                      float* s_i, float* s_j, void* stream) {
-  if (!series || !lin_w || !node_terms || !xlin || !s_i || !s_j || series_len <= 0 || first < 0 || w <= 0)
+// x rows at xb + b*bstride + s*sstride: [B, n, w] windows (n*w, w) or the raw series (1, series_len)
+static int project_fwd_impl(const float* xb, long long bstride, long long sstride, const float* lin_w,
+                            const float* node_terms, int batch, int n, int w, int d, float* xlin, float* s_i,
+                            float* s_j, void* stream, int flags) {
+  if (!xb || !lin_w || !node_terms || !xlin || !s_i || !s_j || batch <= 0 || n <= 0 || w <= 0 || d <= 0)
     return GDN_ERR_ARG;
-  if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;   // last window must fit
-  if (gdn_any_width(d))   // embedding widths other than the four: gdn_any_width.hip
-    return gdn_any_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
-                           (hipStream_t)stream);
-  if (w > GDN_MAX_W)   // long windows: the matrix-core projection of gdn_long_window.hip
-    return gdn_long_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
-                            (hipStream_t)stream);
-  return gdn_large_project(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
-                           (hipStream_t)stream);
-}
-
-// 1 when the staged forward (gdn_project_fwd + gdn_attn_aggregate_fwd) takes this shape
-int gdn_forward_staged_ok(int n, int w, int d, int k) {
-  Plan pl; int threads;
-  return make_plan(MODE_PROJECT, 1, n, w, d, 0, &pl, &threads) == GDN_OK &&
-         make_plan(MODE_ATTN, 1, n, 0, d, k, &pl, &threads) == GDN_OK;
-}
-
-static int project_fwd_impl(const float* x, const float* lin_w, const float* node_terms, int batch,
-                            int n, int w, int d, float* xlin, float* s_i, float* s_j, void* stream, bool wide) {
-  if (!x || !lin_w || !node_terms || !xlin || !s_i || !s_j) return GDN_ERR_ARG;
-  if (gdn_any_width(d))   // embedding widths other than the four (both forms: exact fp32): gdn_any_width.hip
-    return gdn_any_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
-                           (hipStream_t)stream);
-  if (w > GDN_MAX_W)   // long windows (both forms: exact fp32, no 16-bit operands): gdn_long_window.hip
-    return gdn_long_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
-                            (hipStream_t)stream);
-  if (!wide && batch > 0 && gdn_use_dense_path() && gdn_dense_supported(n, w, d, 1))
-    return gdn_dense_project(x, 0, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  switch (gdn_route(GDN_STAGE_PROJECT, n, w, d, 0, flags)) {
+    case GDN_FAMILY_ANY: return gdn_any_project(xb, bstride, sstride, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, st);
+    case GDN_FAMILY_LONG: return gdn_long_project(xb, bstride, sstride, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, st);
+    case GDN_FAMILY_LARGE: return gdn_large_project(xb, bstride, sstride, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, st);
+    case GDN_FAMILY_DENSE: return gdn_dense_project(xb, 0, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, st);
+    case GDN_FAMILY_TILE: break;
+    default: return GDN_ERR_UNSUPPORTED;
+  }
   Plan pl; int threads;
   const int rc = make_plan(MODE_PROJECT, batch, n, w, d, 0, &pl, &threads);
-  if (rc == GDN_ERR_UNSUPPORTED)   // beyond the LDS tile: the streaming row kernel (gdn_large.hip)
-    return gdn_large_project(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j,
-                             (hipStream_t)stream);
   if (rc != GDN_OK) return rc;
   Args a = {};
-  a.x = x; a.lin_w = lin_w; a.node_terms = node_terms;
+  a.x = xb; a.lin_w = lin_w; a.node_terms = node_terms;
   a.xlin_out = xlin; a.si_out = s_i; a.sj_out = s_j;
-  return dispatch_window<MODE_PROJECT>(pl, a, threads, (hipStream_t)stream);
+  return dispatch_window<MODE_PROJECT>(pl, a, threads, st);
 }
 
 extern "C" int gdn_project_fwd(const float* x, const float* lin_w, const float* node_terms, int batch,
                                int n, int w, int d, float* xlin, float* s_i, float* s_j, void* stream) {
-  return project_fwd_impl(x, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, stream, false);
+  return project_fwd_impl(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, stream, 0);
 }
 // `_wide`: the fp32 row-gather kernels at every shape — inputs beyond the range of the 16-bit operand terms
 extern "C" int gdn_project_fwd_wide(const float* x, const float* lin_w, const float* node_terms, int batch,
                                     int n, int w, int d, float* xlin, float* s_i, float* s_j, void* stream) {
-  return project_fwd_impl(x, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, stream, true);
+  return project_fwd_impl(x, (long long)n * w, w, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, stream,
+                          GDN_ROUTE_WIDE);
+}
+// gdn_project_fwd on windows read straight from the raw series [n, series_len]: window b = series[:, first + b :
+// first + b + w].  A streaming row kernel at every shape (the same bits as gdn_project_fwd gives beyond the tile).
+extern "C" int gdn_project_fwd_series(const float* series, int series_len, int first, const float* lin_w,
+                                      const float* node_terms, int batch, int n, int w, int d, float* xlin, float* s_i,
+                                      float* s_j, void* stream) {
+  if (!series || series_len <= 0 || first < 0 || w <= 0) return GDN_ERR_ARG;
+  if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;   // last window must fit
+  return project_fwd_impl(series + first, 1, series_len, lin_w, node_terms, batch, n, w, d, xlin, s_i, s_j, stream,
+                          GDN_ROUTE_SERIES);
 }
 
-static int attn_aggregate_fwd_impl(const float* xlin, const float* s_i, const float* s_j,
-                                   const uint16_t* nbr, const int32_t* deg, const float* bias,
-                                   int batch, int n, int d, int k, float* z, float* alpha,
-                                   void* stream, bool wide) {
-  if (!xlin || !s_i || !s_j || !nbr || !deg || !bias || !z) return GDN_ERR_ARG;
-  if (gdn_any_width(d))   // embedding widths other than the four (fp32 gathers, both forms): gdn_any_width.hip
-    return gdn_any_aggregate(xlin, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
-  if (!wide && batch > 0 && gdn_use_dense_path() && gdn_dense_supported(n, 1, d, k))
-    return gdn_dense_attn_aggregate(xlin, 0, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
+static int attn_aggregate_fwd_impl(const float* xlin, const float* s_i, const float* s_j, const uint16_t* nbr,
+                                   const int32_t* deg, const float* bias, int batch, int n, int d, int k, float* z,
+                                   float* alpha, void* stream, int flags) {
+  if (!xlin || !s_i || !s_j || !nbr || !deg || !bias || !z || batch <= 0 || n <= 0 || d <= 0 || k <= 0)
+    return GDN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  switch (gdn_route(GDN_STAGE_AGGREGATE, n, 1, d, k, flags)) {
+    case GDN_FAMILY_ANY: return gdn_any_aggregate(xlin, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, st);
+    case GDN_FAMILY_DENSE: return gdn_dense_attn_aggregate(xlin, 0, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, st);
+    case GDN_FAMILY_LARGE: return gdn_large_aggregate(xlin, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, st);
+    case GDN_FAMILY_TILE: break;
+    default: return GDN_ERR_UNSUPPORTED;
+  }
   Plan pl; int threads;
   const int rc = make_plan(MODE_ATTN, batch, n, 0, d, k, &pl, &threads);
-  if (rc == GDN_ERR_UNSUPPORTED)   // beyond the LDS tile: rows gathered from global memory (gdn_large.hip)
-    return gdn_large_aggregate(xlin, s_i, s_j, nbr, bias, batch, n, d, k, z, alpha, (hipStream_t)stream);
   if (rc != GDN_OK) return rc;
   Args a = {};
   a.xlin_in = xlin; a.si_in = s_i; a.sj_in = s_j; a.nbr = nbr; a.deg = deg; a.gnn_bias = bias;
   a.z = z; a.alpha = alpha;
-  return dispatch_window<MODE_ATTN>(pl, a, threads, (hipStream_t)stream);
+  return dispatch_window<MODE_ATTN>(pl, a, threads, st);
 }
 
-extern "C" int gdn_attn_aggregate_fwd(const float* xlin, const float* s_i, const float* s_j,
-                                      const uint16_t* nbr, const int32_t* deg, const float* bias,
-                                      int batch, int n, int d, int k, float* z, float* alpha,
-                                      void* stream) {
-  return attn_aggregate_fwd_impl(xlin, s_i, s_j, nbr, deg, bias, batch, n, d, k, z, alpha, stream, false);
+extern "C" int gdn_attn_aggregate_fwd(const float* xlin, const float* s_i, const float* s_j, const uint16_t* nbr,
+                                      const int32_t* deg, const float* bias, int batch, int n, int d, int k,
+                                      float* z, float* alpha, void* stream) {
+  return attn_aggregate_fwd_impl(xlin, s_i, s_j, nbr, deg, bias, batch, n, d, k, z, alpha, stream, 0);
 }
-extern "C" int gdn_attn_aggregate_fwd_wide(const float* xlin, const float* s_i, const float* s_j,
-                                           const uint16_t* nbr, const int32_t* deg, const float* bias,
-                                           int batch, int n, int d, int k, float* z, float* alpha,
-                                           void* stream) {
-  return attn_aggregate_fwd_impl(xlin, s_i, s_j, nbr, deg, bias, batch, n, d, k, z, alpha, stream, true);
+extern "C" int gdn_attn_aggregate_fwd_wide(const float* xlin, const float* s_i, const float* s_j, const uint16_t* nbr,
+                                           const int32_t* deg, const float* bias, int batch, int n, int d, int k,
+                                           float* z, float* alpha, void* stream) {
+  return attn_aggregate_fwd_impl(xlin, s_i, s_j, nbr, deg, bias, batch, n, d, k, z, alpha, stream, GDN_ROUTE_WIDE);
 }
 
 namespace {
-// sparse-gather kernel for the shapes the dense kernels do not cover (x_bf16: bf16 storage of x and xlin)
-int fused_gather(const void* x, int x_bf16, const float* lin_w, const float* node_terms, const uint16_t* nbr,
-                 const int32_t* deg, const float* gnn_bias, const float* emb, const float* bn1_affine,
-                 const float* bn2_affine, const float* out_w, const float* out_b, int batch, int n, int w,
-                 int d, int k, float* out, void* stream, int* gate = nullptr) {
+// sparse-gather kernel for the shapes the dense kernels do not cover (x_bf16: bf16 storage of x and xlin;
+// series_len > 0: x is the raw series [n, series_len], window b starts at tick first + b)
+int fused_gather(const void* x, int x_bf16, int series_len, int first, const float* lin_w, const float* node_terms,
+                 const uint16_t* nbr, const int32_t* deg, const float* gnn_bias, const float* emb,
+                 const float* bn1_affine, const float* bn2_affine, const float* out_w, const float* out_b, int batch,
+                 int n, int w, int d, int k, float* out, void* stream, int* gate = nullptr) {
   Plan pl; int threads;
   const int rc = make_plan(MODE_FUSED, batch, n, w, d, k, &pl, &threads);
   if (rc != GDN_OK) return rc;
+  if (series_len && !pl.mfma) return GDN_ERR_UNSUPPORTED;   // series addressing lives in the MFMA-projection variants
   if (gate && pl.nslices > 1) return GDN_ERR_UNSUPPORTED;   // (the sliced form clears `out` first: not gateable)
   Args a = {};
   a.gate = gate;
-  a.x = static_cast<const float*>(x); a.x_bf16 = x_bf16; a.lin_w = lin_w; a.node_terms = node_terms; a.nbr = nbr; a.deg = deg;
+  a.x = static_cast<const float*>(x); a.x_bf16 = x_bf16; a.series_len = series_len; a.series_first = first; a.lin_w = lin_w; a.node_terms = node_terms; a.nbr = nbr; a.deg = deg;
   a.gnn_bias = gnn_bias; a.emb = emb; a.bn1 = bn1_affine; a.bn2 = bn2_affine;
   a.out_w = out_w; a.out_b = out_b; a.out = out;
   if (pl.nslices > 1 &&   // the slices add their partial head outputs into `out`
@@ -1388,41 +1377,43 @@ int fused_gather(const void* x, int x_bf16, const float* lin_w, const float* nod
 }
 }  // namespace
 
-extern "C" int gdn_forward_fused(const float* x, const float* lin_w, const float* node_terms,
-                                 const uint16_t* nbr, const int32_t* deg, const float* gnn_bias,
-                                 const float* emb, const float* bn1_affine, const float* bn2_affine,
-                                 const float* out_w, const float* out_b, int batch, int n, int w, int d,
-                                 int k, float* out, void* stream) {
-  if (!x || !lin_w || !node_terms || !nbr || !deg || !gnn_bias || !emb || !bn1_affine ||
-      !bn2_affine || !out_w || !out_b || !out)
+// The fused entry points: the matrix-core kernel where the route says DENSE (the `_gated` forms: never), else row gather
+static int fused_impl(int flags, int* guard, const void* x, int series_len, int first, const float* lin_w,
+                      const float* node_terms, const uint16_t* nbr, const int32_t* deg, const float* gnn_bias,
+                      const float* emb, const float* bn1_affine, const float* bn2_affine, const float* out_w,
+                      const float* out_b, int batch, int n, int w, int d, int k, float* out, void* stream) {
+  if (!x || !lin_w || !node_terms || !nbr || !deg || !gnn_bias || !emb || !bn1_affine || !bn2_affine || !out_w ||
+      !out_b || !out || batch <= 0)
     return GDN_ERR_ARG;
-  if (batch > 0 && gdn_use_dense_path() && gdn_dense_fused_supported(n, w, d, k))
-    return gdn_dense_forward_fused(x, 0, 0, 0, lin_w, node_terms, nbr, gnn_bias, emb, bn1_affine, bn2_affine,
-                                   out_w, out_b, batch, n, w, d, k, out, (hipStream_t)stream);
-  return fused_gather(x, 0, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine, out_w, out_b,
-                      batch, n, w, d, k, out, stream);
+  if ((flags & GDN_ROUTE_SERIES) && (series_len <= 0 || first < 0 || (long long)first + batch - 1 + w > series_len))
+    return GDN_ERR_ARG;
+  const int bf16 = (flags & GDN_ROUTE_BF16) != 0;
+  if (gdn_route(GDN_STAGE_FUSED, n, w, d, k, flags) == GDN_FAMILY_DENSE)
+    return gdn_dense_forward_fused(x, bf16, series_len, first, lin_w, node_terms, nbr, gnn_bias, emb, bn1_affine,
+                                   bn2_affine, out_w, out_b, batch, n, w, d, k, out, (hipStream_t)stream);
+  return fused_gather(x, bf16, series_len, first, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine,
+                      out_w, out_b, batch, n, w, d, k, out, stream, guard);
+}
+
+extern "C" int gdn_forward_fused(const float* x, const float* lin_w, const float* node_terms, const uint16_t* nbr,
+                                 const int32_t* deg, const float* gnn_bias, const float* emb, const float* bn1_affine,
+                                 const float* bn2_affine, const float* out_w, const float* out_b, int batch, int n,
+                                 int w, int d, int k, float* out, void* stream) {
+  return fused_impl(0, nullptr, x, 0, 0, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine, out_w,
+                    out_b, batch, n, w, d, k, out, stream);
 }
 
 // The row-gather (fp32 VALU) fused forward, optionally GATED on a range guard (include/gdn_hip.h "range guard"):
 // guard == null runs it unconditionally (inputs known to exceed the 16-bit operand range); otherwise the launch
 // does nothing unless guard[0] != 0, recomputes every window in fp32 when it is, and leaves guard[0..1] = 0.
 extern "C" int gdn_forward_fused_gated(int* guard, const float* x, const float* lin_w, const float* node_terms,
-                                       const uint16_t* nbr, const int32_t* deg, const float* gnn_bias,
-                                       const float* emb, const float* bn1_affine, const float* bn2_affine,
-                                       const float* out_w, const float* out_b, int batch, int n, int w, int d,
-                                       int k, float* out, void* stream) {
-  if (!x || !lin_w || !node_terms || !nbr || !deg || !gnn_bias || !emb || !bn1_affine ||
-      !bn2_affine || !out_w || !out_b || !out)
-    return GDN_ERR_ARG;
-  return fused_gather(x, 0, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine, out_w, out_b,
-                      batch, n, w, d, k, out, stream, guard);
+                                       const uint16_t* nbr, const int32_t* deg, const float* gnn_bias, const float* emb,
+                                       const float* bn1_affine, const float* bn2_affine, const float* out_w,
+                                       const float* out_b, int batch, int n, int w, int d, int k, float* out,
+                                       void* stream) {
+  return fused_impl(GDN_ROUTE_WIDE, guard, x, 0, 0, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine,
+                    out_w, out_b, batch, n, w, d, k, out, stream);
 }
-
-static int fused_gather_series(const float* series, int series_len, int first, const float* lin_w,
-                               const float* node_terms, const uint16_t* nbr, const int32_t* deg,
-                               const float* gnn_bias, const float* emb, const float* bn1_affine,
-                               const float* bn2_affine, const float* out_w, const float* out_b,
-                               int batch, int n, int w, int d, int k, float* out, void* stream, int* gate);
 
 extern "C" int gdn_forward_fused_series_gated(int* guard, const float* series, int series_len, int first,
                                               const float* lin_w, const float* node_terms, const uint16_t* nbr,
@@ -1430,50 +1421,17 @@ extern "C" int gdn_forward_fused_series_gated(int* guard, const float* series, i
                                               const float* bn1_affine, const float* bn2_affine, const float* out_w,
                                               const float* out_b, int batch, int n, int w, int d, int k, float* out,
                                               void* stream) {
-  if (!series || !lin_w || !node_terms || !nbr || !deg || !gnn_bias || !emb || !bn1_affine ||
-      !bn2_affine || !out_w || !out_b || !out || series_len <= 0 || first < 0)
-    return GDN_ERR_ARG;
-  if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;
-  return fused_gather_series(series, series_len, first, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine,
-                             bn2_affine, out_w, out_b, batch, n, w, d, k, out, stream, guard);
+  return fused_impl(GDN_ROUTE_WIDE | GDN_ROUTE_SERIES, guard, series, series_len, first, lin_w, node_terms, nbr, deg,
+                    gnn_bias, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, w, d, k, out, stream);
 }
 
 extern "C" int gdn_forward_fused_series(const float* series, int series_len, int first, const float* lin_w,
                                         const float* node_terms, const uint16_t* nbr, const int32_t* deg,
                                         const float* gnn_bias, const float* emb, const float* bn1_affine,
-                                        const float* bn2_affine, const float* out_w, const float* out_b,
-                                        int batch, int n, int w, int d, int k, float* out, void* stream) {
-  if (!series || !lin_w || !node_terms || !nbr || !deg || !gnn_bias || !emb || !bn1_affine ||
-      !bn2_affine || !out_w || !out_b || !out || series_len <= 0 || first < 0)
-    return GDN_ERR_ARG;
-  if ((long long)first + batch - 1 + w > series_len) return GDN_ERR_ARG;   // last window must fit
-  if (batch > 0 && gdn_use_dense_path() && gdn_dense_fused_supported(n, w, d, k))
-    return gdn_dense_forward_fused(series, 0, series_len, first, lin_w, node_terms, nbr, gnn_bias, emb, bn1_affine,
-                                   bn2_affine, out_w, out_b, batch, n, w, d, k, out, (hipStream_t)stream);
-  return fused_gather_series(series, series_len, first, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine,
-                             bn2_affine, out_w, out_b, batch, n, w, d, k, out, stream, nullptr);
-}
-
-static int fused_gather_series(const float* series, int series_len, int first, const float* lin_w,
-                               const float* node_terms, const uint16_t* nbr, const int32_t* deg,
-                               const float* gnn_bias, const float* emb, const float* bn1_affine,
-                               const float* bn2_affine, const float* out_w, const float* out_b,
-                               int batch, int n, int w, int d, int k, float* out, void* stream, int* gate) {
-  Plan pl; int threads;
-  const int rc = make_plan(MODE_FUSED, batch, n, w, d, k, &pl, &threads);
-  if (rc != GDN_OK) return rc;
-  if (!pl.mfma) return GDN_ERR_UNSUPPORTED;   // series addressing lives in the MFMA-projection variants
-  if (gate && pl.nslices > 1) return GDN_ERR_UNSUPPORTED;
-  Args a = {};
-  a.gate = gate;
-  a.x = series; a.series_len = series_len; a.series_first = first;
-  a.lin_w = lin_w; a.node_terms = node_terms; a.nbr = nbr; a.deg = deg;
-  a.gnn_bias = gnn_bias; a.emb = emb; a.bn1 = bn1_affine; a.bn2 = bn2_affine;
-  a.out_w = out_w; a.out_b = out_b; a.out = out;
-  if (pl.nslices > 1 &&
-      hipMemsetAsync(out, 0, (size_t)batch * n * sizeof(float), (hipStream_t)stream) != hipSuccess)
-    return GDN_ERR_LAUNCH;
-  return dispatch_window<MODE_FUSED>(pl, a, threads, (hipStream_t)stream);
+                                        const float* bn2_affine, const float* out_w, const float* out_b, int batch,
+                                        int n, int w, int d, int k, float* out, void* stream) {
+  return fused_impl(GDN_ROUTE_SERIES, nullptr, series, series_len, first, lin_w, node_terms, nbr, deg, gnn_bias, emb,
+                    bn1_affine, bn2_affine, out_w, out_b, batch, n, w, d, k, out, stream);
 }
 
 template <typename ZT>
@@ -1498,9 +1456,13 @@ static int head_launch(const ZT* z, const float* emb, const float* bn1_affine, c
 extern "C" int gdn_head_fwd(const float* z, const float* emb, const float* bn1_affine,
                             const float* bn2_affine, const float* out_w, const float* out_b, int batch,
                             int n, int d, float* out, float* h2, void* stream) {
-  if (gdn_any_width(d))   // embedding widths other than the four: gdn_any_width.hip
-    return gdn_any_head(z, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, d, out, h2, (hipStream_t)stream);
-  return head_launch<float>(z, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, d, out, h2, stream);
+  if (!z || !emb || !bn1_affine || !bn2_affine || !out_w || !out_b || !out || batch <= 0 || n <= 0) return GDN_ERR_ARG;
+  switch (gdn_route(GDN_STAGE_HEAD, n, 1, d, 1, 0)) {
+    case GDN_FAMILY_ANY:
+      return gdn_any_head(z, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, d, out, h2, (hipStream_t)stream);
+    case GDN_FAMILY_TILE: return head_launch<float>(z, emb, bn1_affine, bn2_affine, out_w, out_b, batch, n, d, out, h2, stream);
+  }
+  return GDN_ERR_UNSUPPORTED;
 }
 
 extern "C" int gdn_head_fwd_bf16(const uint16_t* z, const float* emb, const float* bn1_affine,
@@ -1526,16 +1488,10 @@ extern "C" int gdn_attn_aggregate_fwd_bf16(const uint16_t* xlin, const float* s_
 }
 
 extern "C" int gdn_forward_fused_bf16(const uint16_t* x, const float* lin_w, const float* node_terms,
-                                      const uint16_t* nbr, const int32_t* deg, const float* gnn_bias,
-                                      const float* emb, const float* bn1_affine, const float* bn2_affine,
-                                      const float* out_w, const float* out_b, int batch, int n, int w, int d,
-                                      int k, float* out, void* stream) {
-  if (!x || !lin_w || !node_terms || !nbr || !deg || !gnn_bias || !emb || !bn1_affine || !bn2_affine ||
-      !out_w || !out_b || !out || batch <= 0)
-    return GDN_ERR_ARG;
-  if (gdn_use_dense_path() && gdn_dense_fused_supported(n, w, d, k))
-    return gdn_dense_forward_fused(x, 1, 0, 0, lin_w, node_terms, nbr, gnn_bias, emb, bn1_affine, bn2_affine,
-                                   out_w, out_b, batch, n, w, d, k, out, (hipStream_t)stream);
-  return fused_gather(x, 1, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine, out_w, out_b,
-                      batch, n, w, d, k, out, stream);
+                                      const uint16_t* nbr, const int32_t* deg, const float* gnn_bias, const float* emb,
+                                      const float* bn1_affine, const float* bn2_affine, const float* out_w,
+                                      const float* out_b, int batch, int n, int w, int d, int k, float* out,
+                                      void* stream) {
+  return fused_impl(GDN_ROUTE_BF16, nullptr, x, 0, 0, lin_w, node_terms, nbr, deg, gnn_bias, emb, bn1_affine, bn2_affine,
+                    out_w, out_b, batch, n, w, d, k, out, stream);
 }

@@ -262,7 +262,7 @@ extern "C" int gdn_topk_graph(const float* emb, int n, int d, int k, int64_t* to
   if (k > n || n > 4096 || k + 1 > 1024) return GDN_ERR_UNSUPPORTED;
   const int pitch = gdn_nbr_pitch(k);
   if (d & 3) {   // any width up to 256 (gdn_any_width.hip): rows read column by column
-    if (!gdn_any_width(d)) return GDN_ERR_UNSUPPORTED;
+    if (d > GDN_ANY_MAX_D) return GDN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(gdn_graph_scalar_kernel, dim3(n), dim3(256), 2 * n * sizeof(float), (hipStream_t)stream,
                        emb, n, d, k, pitch, topk_idx, nbr, deg, cos_out);
     return gdn_launch_status();
@@ -288,8 +288,11 @@ extern "C" int gdn_node_terms(const float* lin_w, const float* att_i, const floa
   if (!lin_w || !att_i || !att_j || !att_em_i || !att_em_j || !emb || !node_terms || n <= 0 ||
       d <= 0 || w <= 0)
     return GDN_ERR_ARG;
-  if (w > GDN_MAX_W)   // long windows: a_i / a_j at pitch gdn_terms_pitch(w) (gdn_long_window.hip)
-    return gdn_long_node_terms(lin_w, att_i, att_j, att_em_i, att_em_j, emb, n, d, w, node_terms, (hipStream_t)stream);
+  switch (gdn_route(GDN_STAGE_TERMS, n, w, d, 0, 0)) {
+    case GDN_FAMILY_NONE: return GDN_ERR_UNSUPPORTED;
+    case GDN_FAMILY_LONG:   // a_i / a_j at pitch gdn_terms_pitch(w) (gdn_long_window.hip)
+      return gdn_long_node_terms(lin_w, att_i, att_j, att_em_i, att_em_j, emb, n, d, w, node_terms, (hipStream_t)stream);
+  }
   const int total = 2 * GDN_A_PITCH + 2 * n;
   hipLaunchKernelGGL(gdn_node_terms_kernel, dim3((total + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, lin_w, att_i, att_j, att_em_i, att_em_j, emb, n, d, w,

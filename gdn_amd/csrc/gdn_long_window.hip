@@ -386,14 +386,6 @@ int gdn_long_project_bwd_partials(const float* x, const float* d_xlin, const flo
   return gdn_launch_status();
 }
 
-int gdn_long_project_bwd(const float* x, const float* d_xlin, const float* d_si, const float* d_sj, int batch, int n,
-                         int w, int d, float* workspace, float* d_lin_w, float* d_a, float* d_c, hipStream_t st) {
-  int parts = 0;
-  const int rc = gdn_long_project_bwd_partials(x, d_xlin, d_si, d_sj, batch, n, w, d, workspace, &parts, st);
-  if (rc != GDN_OK) return rc;
-  return gdn_long_project_reduce(workspace, parts, batch, n, w, d, d_si, d_sj, d_lin_w, d_a, d_c, st);
-}
-
 // the partial blocks added in range order (also the reduce of gdn_any_width.hip's projection backward, any w)
 int gdn_long_project_reduce(const float* part, int parts, int batch, int n, int w, int d, const float* d_si,
                             const float* d_sj, float* d_lin_w, float* d_a, float* d_c, hipStream_t st) {

@@ -560,11 +560,11 @@ class GDN(nn.Module):
     def _large_guard_wide(self, src, c) -> bool:
         """Range check of the staged forward under operand_range='auto'.  The projection and the gather kernels
         beyond the tile are fp32 throughout, but on a long-window model with a small graph (n <= 127, d = 64,
-        k <= 63) gdn_attn_aggregate_fwd picks the matrix-core aggregate, which carries xlin as two f16 terms: there
-        the inputs are compared with the limit on the host (inside a capture, where that cannot happen, the fp32
-        `_wide` aggregate runs)."""
+        k <= 63) gdn_attn_aggregate_fwd routes to the matrix-core aggregate (gdn_kernel_family), which carries xlin as
+        two f16 terms: there the inputs are compared with the limit on the host (inside a capture, where that cannot
+        happen, the fp32 `_wide` aggregate runs)."""
         n, d = self.embedding.weight.shape
-        if not (n <= 127 and d == 64 and 1 <= c.graph.k <= 63):
+        if _lib.family(_lib.STAGE_AGGREGATE, n, 1, d, c.graph.k) != _lib.FAMILY_DENSE:
             return False
         if torch.cuda.is_current_stream_capturing():
             return True

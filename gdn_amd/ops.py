@@ -5,8 +5,6 @@ device — there is no CPU path.
 """
 from __future__ import annotations
 
-import os
-
 import ctypes
 
 import torch
@@ -47,11 +45,11 @@ class SensorGraph:
 
     def nbr_ordered(self):
         """The neighbour lists with every row permuted inside its two halves for LDS bank spread
-        (gdn_graph_bank_order), or `nbr` itself for shapes the matrix-core kernels do not take.  For launches
+        (gdn_graph_bank_order), or `nbr` itself where the aggregate does not route to the matrix-core kernels.  For launches
         that do not hand alpha out in rank order.  Built on first use, once per graph."""
         if self._ordered is False:
             self._ordered = None
-            if self.n <= 127 and nbr_pitch(self.k) <= 64:
+            if _lib.family(_lib.STAGE_AGGREGATE, self.n, 1, 64, self.k) == _lib.FAMILY_DENSE:
                 out = torch.empty_like(self.nbr)
                 out.copy_(self.nbr)                         # (padding rows / slots as in the original)
                 _lib.call("gdn_graph_bank_order", _ptr(self.nbr), self.n, self.k, _ptr(out), _stream())
@@ -171,7 +169,9 @@ def attn_aggregate_fwd(xlin, s_i, s_j, graph: SensorGraph, bias, batch: int, wan
     n = bn // batch
     z = torch.empty_like(xlin)
     alpha = torch.empty((bn, graph.pitch), dtype=torch.float32, device=xlin.device) if want_alpha else None
-    nbr = graph.nbr if (want_alpha or wide or d != 64) else graph.nbr_ordered()
+    flags = _lib.ROUTE_BF16 if sfx == "_bf16" else _lib.ROUTE_WIDE if wide else 0
+    dense = _lib.family(_lib.STAGE_AGGREGATE, n, 1, d, graph.k, flags) == _lib.FAMILY_DENSE
+    nbr = graph.nbr_ordered() if dense and not want_alpha else graph.nbr
     _lib.call("gdn_attn_aggregate_fwd" + sfx, _ptr(xlin), _ptr(_chk(s_i)), _ptr(_chk(s_j)), _ptr(nbr),
               _ptr(graph.deg), _ptr(_chk(bias.detach())), batch, n, d, graph.k, _ptr(z), _ptr(alpha), _stream())
     return z, alpha
@@ -503,13 +503,11 @@ def fused_plan(lin_w, terms, graph: SensorGraph, gnn_bias, emb, bn1_affine, bn2_
                bf16_storage: bool = False):
     """Per-launch constants of the fused forward, precomputed (include/gdn_hip.h "plans"); None when the
     shape is not on the matrix-core path.  Rebuild after every parameter update."""
-    if os.environ.get("GDN_FUSED_PATH", "").startswith("v"):      # diagnostic: keep the fp32 VALU kernels
-        return None
     lin_w = _chk(lin_w.detach(), name="lin.weight")
     d, w = lin_w.shape
     n = emb.shape[0]
     nbytes = _lib.load().gdn_fused_plan_bytes(n, w, d, graph.k, int(bf16_storage))
-    if nbytes == 0:
+    if nbytes == 0 or _lib.family(_lib.STAGE_FUSED, n, w, d, graph.k) != _lib.FAMILY_DENSE:   # (GDN_FUSED_PATH=valu)
         return None
     plan = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=emb.device)
     _lib.call("gdn_fused_plan_build", _ptr(lin_w), _ptr(terms), _ptr(graph.nbr), _ptr(graph.deg),

@@ -31,21 +31,41 @@
  *   gdn_project_fwd[_wide] / _series (fp32 matrix-core projection, exact fp32, no range limit), gdn_project_bwd[_partials],
  *   gdn_terms_bwd[_acc]; everything after xlin depends on n, d, k only and takes the forms below.  gdn_tile_fits,
  *   gdn_fused_plan_bytes and gdn_train_supported return 0, the fused / bf16 entry points GDN_ERR_UNSUPPORTED.
- * Two forms of the graph layer, chosen by the library per entry point, never by the caller:
- *   TILE form — the window's working set in the 160 KB of LDS of one CU:
+ * Route table — the kernel FAMILY of every stage of the graph layer, chosen by the library, never by the caller.
+ *   gdn_route.hip is the one place that decides it and gdn_kernel_family the query; rules apply in the order written,
+ *   inside the supported shapes above (outside them: NONE, and the entry point returns GDN_ERR_UNSUPPORTED).
+ *   "dense shape" = n <= 127, d = 64, w <= 32, k <= 63.  Dimensions a stage does not depend on are ignored.
+ *     PROJECT (n, w, d)       gdn_project_fwd[_wide|_series|_bf16]:
+ *                             BF16: DENSE at a dense shape, else NONE; ANY at d not 16/32/64/128; LONG at w > 64;
+ *                             SERIES: LARGE; DENSE at a dense shape unless WIDE; TILE where the xlin tile fits; LARGE.
+ *     AGGREGATE (n, d, k)     gdn_attn_aggregate_fwd[_wide|_bf16]: as PROJECT without the LONG and SERIES rules.
+ *     ATTN_BWD (n, d, k)      gdn_attn_aggregate_bwd[_wide]: ANY; DENSE at a dense shape unless WIDE; TILE in one of
+ *                             three sub-forms (below); LARGE.
+ *     PROJECT_BWD (n, w, d)   gdn_project_bwd[_partials]: ANY; LONG; TILE.
+ *     TERMS (w, d)            gdn_node_terms, gdn_terms_bwd[_acc]: LONG at w > 64; ANY; TILE (gdn_node_terms runs one
+ *                             kernel for ANY and TILE, gdn_terms_bwd one for LONG and ANY).
+ *     HEAD (d)                gdn_head_fwd: ANY; TILE.
+ *     FUSED (n, w, d, k)      gdn_forward_fused[_series|_bf16|_gated]: NONE at d not 16/32/64/128 or w > 64; DENSE at a
+ *                             dense shape (also d = 128) unless WIDE (the _gated forms); TILE where the tile fits
+ *                             (SERIES: and the projection runs on the matrix cores); NONE — one launch, no workspace.
+ *   The families:
+ *   TILE — the window's working set in the 160 KB of LDS of one CU:
  *     forward (staged and fused): the xlin tile (n+1)*dc*4 bytes, dc = d (d = 128: 64, two column slices) —
  *       n up to ~610 at d = 64/128, ~1180 at d = 32, ~2200 at d = 16 (gdn_tile_fits: the fused forward);
- *     backward (gdn_attn_aggregate_bwd): that tile at full d PLUS two [n, pitch] fp32 tables and the lists
- *       in LDS — n up to ~250 at d = 64 with k = 30; beyond that the tables go through the caller's workspace
- *       and only the tile must fit (d = 128 walks two 64-column slices when the full tile does not fit);
- *   LARGE form — where the tile form refuses (n up to 4096), gdn_project_fwd, gdn_attn_aggregate_fwd and
- *     gdn_attn_aggregate_bwd run streaming kernels that keep only the window's s_i / s_j and one list per wave
- *     in LDS and gather the source rows of xlin (forward) / d_z (backward) from global memory; fp32 only,
- *     bitwise reproducible.  The fused entry points (gdn_forward_fused*: no workspace), the bf16 ones and
- *     gdn_train_supported (the native captured step) keep to the tile form;
- *   matrix-core ("dense") kernels — gdn_forward_fused, gdn_project_fwd, gdn_attn_aggregate_fwd pick them
- *     by themselves for n <= 127, d = 64, w <= 32, k <= 63 (gdn_forward_fused also at d = 128); the staged
+ *     backward (gdn_attn_aggregate_bwd), three sub-forms: that tile at full d PLUS two [n, pitch] fp32 tables and the
+ *       lists in LDS (GDN_BWD_TABLES_LDS) — n up to ~250 at d = 64 with k = 30; beyond that the tables go through the
+ *       caller's workspace and only the tile must fit (GDN_BWD_TABLES_GLOBAL); d = 128 walks two 64-column slices
+ *       when the full tile does not fit (GDN_BWD_SLICED);
+ *   LARGE — where the tile refuses (n up to 4096): streaming kernels that keep only the window's s_i / s_j and one
+ *     list per wave in LDS and gather the source rows of xlin (forward) / d_z (backward) from global memory; fp32 only,
+ *     bitwise reproducible;
+ *   DENSE — the matrix-core kernels (every factor as two 16-bit terms: the range guard below); the staged
  *     bf16-storage entry points exist only there;
+ *   LONG, ANY — the long-window and any-width forms above.
+ *   gdn_tile_fits, gdn_train_supported (the tile kernels take every stage of a training step),
+ *   gdn_attn_aggregate_bwd_uses_reverse and the two backward workspace queries are reads of this table.
+ *   Diagnostic A/B overrides, read once per process: GDN_FUSED_PATH=valu (no DENSE at any stage, bf16 storage aside),
+ *   GDN_BWD_PATH=valu (no DENSE at ATTN_BWD), GDN_BWD_SLICED=1 (ATTN_BWD at d = 128: GDN_BWD_SLICED or NONE).
  * anything else returns GDN_ERR_UNSUPPORTED (never a silent fallback).
  */
 #ifndef GDN_HIP_H
@@ -62,7 +82,7 @@ extern "C" {
 #define GDN_ERR_LAUNCH (-2)       /* hipGetLastError() != hipSuccess after the launch      */
 #define GDN_ERR_UNSUPPORTED (-3)  /* shape outside the supported set above                 */
 
-#define GDN_ABI_VERSION 22
+#define GDN_ABI_VERSION 23
 int gdn_abi_version(void);
 
 /* Number of u16 slots per neighbour-list row for a given k: (k+1) rounded up to 16. */
@@ -134,6 +154,30 @@ int gdn_project_fwd_series(const float* series, int series_len, int first, const
 /* gdn_tile_fits: 1 when the tile form of the forward takes (n, w, d, k) — the one-launch gdn_forward_fused and
  * its plans — 0 when only the staged entry points (large form beyond the tile) do.  Host only, no launch.      */
 int gdn_tile_fits(int n, int w, int d, int k);
+
+/* gdn_kernel_family: the route table above as a query (host only, no launch) — the GDN_FAMILY_* that the entry
+ * points of `stage` run at (n, w, d, k) under `flags`, in the low 8 bits; for GDN_STAGE_ATTN_BWD with family TILE the
+ * GDN_BWD_* sub-form in bits 8 and up (it decides the layout gdn_attn_aggregate_bwd_workspace_bytes sizes).          */
+#define GDN_FAMILY_NONE 0
+#define GDN_FAMILY_DENSE 1
+#define GDN_FAMILY_TILE 2
+#define GDN_FAMILY_LARGE 3
+#define GDN_FAMILY_LONG 4
+#define GDN_FAMILY_ANY 5
+#define GDN_STAGE_PROJECT 0
+#define GDN_STAGE_AGGREGATE 1
+#define GDN_STAGE_ATTN_BWD 2
+#define GDN_STAGE_PROJECT_BWD 3
+#define GDN_STAGE_TERMS 4
+#define GDN_STAGE_HEAD 5
+#define GDN_STAGE_FUSED 6
+#define GDN_ROUTE_WIDE 1     /* the `_wide` / `_gated` entry points: never DENSE                          */
+#define GDN_ROUTE_BF16 2     /* the `_bf16` entry points: x / xlin / z stored as bf16                     */
+#define GDN_ROUTE_SERIES 4   /* the `_series` entry points: windows read from the raw series (PROJECT, FUSED) */
+#define GDN_BWD_TABLES_LDS 0
+#define GDN_BWD_TABLES_GLOBAL 1
+#define GDN_BWD_SLICED 2
+int gdn_kernel_family(int stage, int n, int w, int d, int k, int flags);
 
 /* gdn_attn_aggregate_fwd: models/graph_layer.py:65-74,82-117 + PyG propagate / softmax:
  * LeakyReLU(0.2) logits, softmax over each target's incoming edges (max-subtract, exp,

@@ -13,7 +13,7 @@ def test_header_documents_any_width_and_the_abi_stays():
     from gdn_amd import _lib
     header = open(os.path.join(ROOT, "include", "gdn_hip.h")).read()
     assert "1 <= d <= 256" in header
-    assert "#define GDN_ABI_VERSION 22" in header and _lib.ABI_VERSION == 22
+    assert "#define GDN_ABI_VERSION 23" in header and _lib.ABI_VERSION == 23
 
 
 def test_new_widths_stay_off_the_tile_the_plans_and_the_native_step():

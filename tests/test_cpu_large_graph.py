@@ -12,7 +12,7 @@ def test_large_graph_symbols_declared_and_exported():
         assert re.search(r"\bint " + name + r"\(", header), name
         assert name in _lib.SIGNATURES
         assert hasattr(_lib.load(), name)
-    assert "#define GDN_ABI_VERSION 22" in header and _lib.ABI_VERSION == 22
+    assert "#define GDN_ABI_VERSION 23" in header and _lib.ABI_VERSION == 23
 
 
 def test_tile_predicate_follows_the_lds_budget():

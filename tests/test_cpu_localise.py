@@ -29,7 +29,7 @@ def test_header_signatures_and_exports_agree_and_the_abi_stays():
         assert fn.restype is (ctypes.c_longlong if declared[name] == "long long" else ctypes.c_int)
     assert declared["gdn_attention_workspace_bytes"] == "long long"
     assert [declared[n] for n in NEW if n != "gdn_attention_workspace_bytes"] == ["int"] * 3
-    assert "#define GDN_ABI_VERSION 22" in header and _lib.ABI_VERSION == 22 and lib.gdn_abi_version() == 22
+    assert "#define GDN_ABI_VERSION 23" in header and _lib.ABI_VERSION == 23 and lib.gdn_abi_version() == 23
     p, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     assert _lib.SIGNATURES["gdn_score_smooth_topm"] == [p, p, p, i, i, i, p, p, i, p, p, p]
     assert _lib.SIGNATURES["gdn_attention_mean"] == [p, ll, ll, p, p, p, p, i, i, i, i, p, p, p]

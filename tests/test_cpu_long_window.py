@@ -11,7 +11,7 @@ def test_terms_pitch_declared_and_exported():
     assert re.search(r"\bint gdn_terms_pitch\(", header)
     assert "gdn_terms_pitch" in _lib.SIGNATURES
     assert hasattr(_lib.load(), "gdn_terms_pitch")
-    assert "#define GDN_ABI_VERSION 22" in header and _lib.ABI_VERSION == 22
+    assert "#define GDN_ABI_VERSION 23" in header and _lib.ABI_VERSION == 23
     assert "1 <= w <= 1024" in header
 
 

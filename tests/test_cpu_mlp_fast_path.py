@@ -16,13 +16,13 @@ def test_header_declares_the_entry_point_and_the_abi_stays():
     from gdn_amd import _lib
     header = open(os.path.join(ROOT, "include", "gdn_hip.h")).read()
     assert re.search(r"\bint gdn_head_mlp_fwd\(const float\* z, const float\* emb,", header)
-    assert "#define GDN_ABI_VERSION 22" in header and _lib.ABI_VERSION == 22
+    assert "#define GDN_ABI_VERSION 23" in header and _lib.ABI_VERSION == 23
 
 
 def test_library_exports_and_binding():
     from gdn_amd import _lib, ops
     lib = _lib.load()
-    assert lib.gdn_abi_version() == 22
+    assert lib.gdn_abi_version() == 23
     fn = lib.gdn_head_mlp_fwd                    # AttributeError: the symbol is missing
     # z, emb, bn1, bn2, plan | batch, n, d, hidden, layers | out, stream
     assert _lib.SIGNATURES["gdn_head_mlp_fwd"] == [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2

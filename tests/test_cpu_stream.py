@@ -34,7 +34,7 @@ def test_header_signatures_and_exports_agree_and_the_abi_stays():
         assert fn.restype is (ctypes.c_longlong if declared[name] == "long long" else ctypes.c_int)
     assert declared["gdn_stream_state_bytes"] == "long long"
     assert [declared[n] for n in NEW[1:]] == ["int"] * 4
-    assert "#define GDN_ABI_VERSION 22" in header and binding.ABI_VERSION == 22 and lib.gdn_abi_version() == 22
+    assert "#define GDN_ABI_VERSION 23" in header and binding.ABI_VERSION == 23 and lib.gdn_abi_version() == 23
     p, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     assert binding.SIGNATURES["gdn_stream_state_bytes"] == [i, i]
     assert binding.SIGNATURES["gdn_stream_init"] == [p, p, ll, i, i, p]

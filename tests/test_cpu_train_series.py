@@ -28,7 +28,7 @@ def test_header_signatures_and_exports_agree_and_the_abi_stays():
         assert declared.get(name) == "int" and name in _lib.SIGNATURES
         fn = getattr(lib, name)                      # AttributeError: the symbol is missing
         assert fn.argtypes == _lib.SIGNATURES[name] and fn.restype is ctypes.c_int
-    assert "#define GDN_ABI_VERSION 22" in header and _lib.ABI_VERSION == 22 and lib.gdn_abi_version() == 22
+    assert "#define GDN_ABI_VERSION 23" in header and _lib.ABI_VERSION == 23 and lib.gdn_abi_version() == 23
     p, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     assert _lib.SIGNATURES["gdn_windows_gather"] == [p, i, ll, p, ll, p, ll, i, i, p, p, p]
     assert _lib.SIGNATURES["gdn_epoch_advance"] == [p, p, p, ll, p]

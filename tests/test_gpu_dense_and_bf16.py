@@ -156,6 +156,34 @@ def test_valu_and_dense_fused_paths_agree(gpu_device, tmp_path):
     np.testing.assert_allclose(outs[0].numpy(), outs[1].numpy(), atol=4e-6, rtol=0)
 
 
+def test_valu_staged_aggregate_gets_rank_ordered_lists(gpu_device, tmp_path):
+    """Under GDN_FUSED_PATH=valu the staged aggregate routes to the row-gather kernel, which walks ceil(deg / 16)
+    rounds of a RANK-ordered list: ops.attn_aggregate_fwd asks the library's route (gdn_kernel_family) and must not
+    hand it the bank-ordered copy.  n = 40, k = 32 with every sensor in its own top-k: pitch 48, deg 32 — the smallest
+    shape where the bank permutation moves a valid entry past round 2.  z without alpha must equal, bit for bit, z of
+    the want_alpha call (always rank-ordered) in the same process."""
+    import os
+    import subprocess
+    import sys
+    code = ("import sys, torch; sys.path.insert(0, %r);"
+            "from gdn_amd import ops;"
+            "g = torch.Generator().manual_seed(5); n, w, d, k, b = 40, 8, 64, 32, 3;"
+            "r = lambda *s: (torch.rand(s, generator=g) * 2 - 1).to('cuda:0');"
+            "emb, lin_w, bias, x = r(n, d), r(d, w) * 0.3, r(d) * 0.1, r(b, n, w);"
+            "graph = ops.topk_graph(emb, k);"
+            "terms = ops.node_terms(lin_w, r(d) * 0.3, r(d) * 0.3, r(d) * 0.3, r(d) * 0.3, emb);"
+            "xlin, s_i, s_j = ops.project_fwd(x, lin_w, terms);"
+            "za, _ = ops.attn_aggregate_fwd(xlin, s_i, s_j, graph, bias, b, want_alpha=True);"
+            "zb, _ = ops.attn_aggregate_fwd(xlin, s_i, s_j, graph, bias, b, want_alpha=False);"
+            "torch.save((za.cpu(), zb.cpu(), graph.deg.cpu(), graph.pitch), sys.argv[1])")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    f = str(tmp_path / "valu_aggregate.pt")
+    subprocess.run([sys.executable, "-c", code % root, f], check=True, env=dict(os.environ, GDN_FUSED_PATH="valu"))
+    za, zb, deg, pitch = torch.load(f, weights_only=True)
+    assert pitch == 48 and bool((deg == 32).all())
+    assert bool(za.abs().sum() > 0) and torch.equal(za, zb)
+
+
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_bf16_storage_fused_forward(shape, gpu_device):
     """GDN.forward on bfloat16 windows (bf16 storage of x and of the LDS-resident projected tile)."""
