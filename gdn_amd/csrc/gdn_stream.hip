@@ -3,6 +3,10 @@
 // make a push of 1 .. c ticks: cut the windows, (the model's forward,) score with the carried smoothing state,
 // advance the state.  Only gdn_stream_advance writes the state; the other two read it, and stream order makes a push
 // race-free.  Plain copy, sweep and scan kernels: no inline assembly, no floating-point atomics.
+// Missing readings (opt-in, include/gdn_hip.h "Missing readings"): gdn_stream_fill leads the push and holds every
+// non-finite reading at its sensor's latest real one; the score and advance kernels have a GAPS instantiation each that
+// reads the validity plane and takes the normalised error of a missing reading as 0.0.  The plain instantiations are
+// the kernels they were: the extra parameters trail the argument list and are never read.
 #include "gdn_common.hpp"
 
 // The float64 scoring here must round where gdn_score.hip's sweep rounds (the stream is compared with it bit for bit):
@@ -70,18 +74,98 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_windows_kernel(
   }
 }
 
+// Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it
+// does not depend on how floating-point comparisons with NaN are compiled.
+#define GDN_FILL_WAVES 16            // waves of a workgroup: each owns a contiguous segment of the chunk's rows
+#define GDN_FILL_DEPTH 8             // row loads in flight per lane
+__device__ inline bool stream_missing(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// Workgroup g: sensors [64 g, 64 g + 64), one per lane (a row of the time-major chunk is contiguous along sensors:
+// coalesced).  Wave v walks rows [v * seg, (v + 1) * seg) ^ [0, count), DEPTH loads at a time, and reduces them to
+// (latest real reading, found one, missing readings, missing readings after the latest real one = the whole segment
+// when there is none).  "The right-most real reading wins" is associative: the segments meet in LDS, every wave takes
+// the latest real reading before its segment (hist[i, w - 1] when no earlier segment has one) and walks its rows a
+// second time, writing.  Wave 0 folds the counts.  Reads the state, writes none of it; no workgroup waits on another.
+__global__ __launch_bounds__(GDN_FILL_WAVES * 64) void gdn_stream_fill_kernel(
+    const void* __restrict__ state, const float* __restrict__ raw, int count, int n, int w,
+    float* __restrict__ filled, unsigned char* __restrict__ valid, int* __restrict__ gap_chunk) {
+  __shared__ float seg_last[GDN_FILL_WAVES][64];
+  __shared__ int seg_found[GDN_FILL_WAVES][64];
+  __shared__ int seg_missing[GDN_FILL_WAVES][64];
+  __shared__ int seg_trail[GDN_FILL_WAVES][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + lane;
+  const bool live = i < n;
+  const int ic = live ? i : n - 1;                                   // a dead lane reads sensor n - 1, writes nothing
+  const int seg = (count + GDN_FILL_WAVES - 1) / GDN_FILL_WAVES;
+  const int r0 = min(count, wv * seg), r1 = min(count, r0 + seg);
+  float last = 0.f;
+  int found = 0, missing = 0, trail = 0;
+  for (int b = r0; b < r1; b += GDN_FILL_DEPTH) {
+    float v[GDN_FILL_DEPTH];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) v[u] = raw[(size_t)min(b + u, r1 - 1) * n + ic];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) {
+      if (b + u < r1) {                                              // (wave uniform)
+        if (stream_missing(v[u])) { ++missing; ++trail; }
+        else { last = v[u]; found = 1; trail = 0; }
+      }
+    }
+  }
+  seg_last[wv][lane] = last;
+  seg_found[wv][lane] = found;
+  seg_missing[wv][lane] = missing;
+  seg_trail[wv][lane] = trail;
+  __syncthreads();
+  float hold = stream_hist(state, n)[(size_t)ic * w + (w - 1)];
+  for (int v = 0; v < wv; ++v)
+    if (seg_found[v][lane]) hold = seg_last[v][lane];
+  for (int b = r0; b < r1; b += GDN_FILL_DEPTH) {
+    float v[GDN_FILL_DEPTH];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) v[u] = raw[(size_t)min(b + u, r1 - 1) * n + ic];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) {
+      if (b + u < r1) {
+        const bool gone = stream_missing(v[u]);
+        if (!gone) hold = v[u];
+        if (live) {
+          filled[(size_t)(b + u) * n + i] = hold;
+          valid[(size_t)(b + u) * n + i] = gone ? 0 : 1;
+        }
+      }
+    }
+  }
+  if (wv == 0 && live) {
+    int total = 0, run = 0;
+    for (int v = 0; v < GDN_FILL_WAVES; ++v) total += seg_missing[v][lane];
+    for (int v = GDN_FILL_WAVES - 1; v >= 0; --v) {                  // from the last row back to the latest real reading
+      run += seg_trail[v][lane];
+      if (seg_found[v][lane]) break;
+    }
+    gap_chunk[i] = total;
+    gap_chunk[n + i] = run;
+  }
+}
+
 // Normalise, smooth, top m, flag: the sweep of score_smooth_topm_kernel (gdn_score.hip) — the same loads, the same
 // float64 operations in the same order, the same m rounds of "wave maximum of (score, sensor)" — with the series
 // position of the chunk's first tick read from the state and the three normalised errors before the chunk taken from
 // the carry (rows 0, 1, 2 = three, two, one tick before; zeros where the series has no such tick).  One wave owns a run
 // of 8 consecutive ticks of the chunk; only the run at tick 0 reaches back into the carry.
+// GAPS: `valid` [t, n] (1 = a real reading) travels as one bit per loaded row and the normalised error of a missing
+// reading is 0.0 — in its own tick's mean, as a predecessor inside the chunk, and (through gdn_stream_advance's carry)
+// as a predecessor of the next push.  Without GAPS `valid` is not read and the kernel is the one it was.
 constexpr int RUN = 8;
 constexpr int TOPM_MAX = 8;
 
+template <bool GAPS>
 __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
     const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ gt,
     const double* __restrict__ med_iqr, const double* __restrict__ threshold, int t, int n, int m,
-    double* __restrict__ top_scores, int* __restrict__ top_sensors, int* __restrict__ alarm) {
+    double* __restrict__ top_scores, int* __restrict__ top_sensors, int* __restrict__ alarm,
+    const unsigned char* __restrict__ valid) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int nruns = (t + RUN - 1) / RUN;
@@ -105,6 +189,7 @@ __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
       const double meda = med_iqr[2 * ca], dena = 1.0 / (fabs(med_iqr[2 * ca + 1]) + 1e-2);
       const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
       float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
+      unsigned oka = 0u, okb = 0u;                 // GAPS: bit u = the reading of row u is real
 #pragma unroll
       for (int u = 0; u < RUN + 3; ++u) {
         const int tt = t0 - 3 + u;                 // < 0 (run 0 only): the value comes from the carry, row 0 is a stand-in
@@ -112,24 +197,33 @@ __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
         const float* pp = pred + (size_t)row * n;
         const float* gg = gt + (size_t)row * n;
         pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
+        if constexpr (GAPS) {
+          const unsigned char* vv = valid + (size_t)row * n;
+          oka |= (vv[ca] ? 1u : 0u) << u;
+          okb |= (vv[cb] ? 1u : 0u) << u;
+        }
       }
-      auto norm = [&](float pv, float gv, double med, double inv_den) -> double {
-        return (fabs((double)pv - (double)gv) - med) * inv_den;
+      auto norm = [&](float pv, float gv, double med, double inv_den, unsigned ok, int u) -> double {
+        const double a = (fabs((double)pv - (double)gv) - med) * inv_den;
+        if constexpr (GAPS) return ((ok >> u) & 1u) ? a : 0.0;
+        return a;
       };
       double a3, a2, a1, b3, b2, b1;
       if (t0 == 0) {                               // (wave uniform)
         a3 = carry[ca]; a2 = carry[(size_t)n + ca]; a1 = carry[2 * (size_t)n + ca];
         b3 = carry[cb]; b2 = carry[(size_t)n + cb]; b1 = carry[2 * (size_t)n + cb];
       } else {
-        a3 = norm(pa[0], ga[0], meda, dena); a2 = norm(pa[1], ga[1], meda, dena); a1 = norm(pa[2], ga[2], meda, dena);
-        b3 = norm(pb[0], gb[0], medb, denb); b2 = norm(pb[1], gb[1], medb, denb); b1 = norm(pb[2], gb[2], medb, denb);
+        a3 = norm(pa[0], ga[0], meda, dena, oka, 0); a2 = norm(pa[1], ga[1], meda, dena, oka, 1);
+        a1 = norm(pa[2], ga[2], meda, dena, oka, 2);
+        b3 = norm(pb[0], gb[0], medb, denb, okb, 0); b2 = norm(pb[1], gb[1], medb, denb, okb, 1);
+        b1 = norm(pb[2], gb[2], medb, denb, okb, 2);
       }
 #pragma unroll
       for (int u = 0; u < RUN; ++u) {
         const int tick = t0 + u;
         if (tick >= t1) continue;                  // (wave uniform)
-        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena);
-        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb);
+        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena, oka, 3 + u);
+        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb, okb, 3 + u);
         double sma = 0.0, smb = 0.0;
         if (first_tick + tick >= 3) {               // numpy sums the 4 values left to right
           sma = (((a3 + a2) + a1) + a0) / 4.0;
@@ -182,10 +276,15 @@ __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
 // stores: no column is read after it has been overwritten, whatever count is.  Workgroup n: the carry (one thread per
 // sensor: its three old entries are read before any is written), the alarm log (an ordered compaction: ballot and
 // popcount inside a wave, four wave totals through LDS, 256 flags a round in tick order) and, last, the counters.
+// GAPS: `chunk` is the filled chunk; a carry entry taken from the chunk is 0.0 where valid says the reading was
+// missing, and the carry thread of sensor s folds the push's gap_chunk [2, n] into gaps [2, n] (missing_total,
+// missing_run): this launch is the only writer of both.  Without GAPS the three trailing parameters are not read.
+template <bool GAPS>
 __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
     void* __restrict__ state, const float* __restrict__ chunk, const float* __restrict__ pred,
     const double* __restrict__ med_iqr, const int* __restrict__ alarm, const int* __restrict__ top_sensors, int count,
-    int n, int w, int m, long long* __restrict__ log_ticks, int* __restrict__ log_sensors, long long log_len) {
+    int n, int w, int m, long long* __restrict__ log_ticks, int* __restrict__ log_sensors, long long log_len,
+    const unsigned char* __restrict__ valid, const int* __restrict__ gap_chunk, long long* __restrict__ gaps) {
   const int tid = threadIdx.x;
   if ((int)blockIdx.x < n) {
     const int i = blockIdx.x;
@@ -223,10 +322,18 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
       } else {
         const size_t at = (size_t)(q - 3) * n + s;
         next[j] = (fabs((double)pred[at] - (double)chunk[at]) - med) * inv_den;     // gdn_stream_score's `norm`
+        if constexpr (GAPS) {
+          if (!valid[at]) next[j] = 0.0;
+        }
       }
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) carry[(size_t)j * n + s] = next[j];
+    if constexpr (GAPS) {
+      const int trail = gap_chunk[n + s];
+      gaps[s] += gap_chunk[s];
+      gaps[(size_t)n + s] = trail == count ? gaps[(size_t)n + s] + count : trail;
+    }
   }
   // alarm log
   const long long ticks = head[0], logged = head[2];
@@ -301,8 +408,9 @@ extern "C" int gdn_stream_score(const void* state, const float* pred, const floa
   if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
   const int runs = (count + RUN - 1) / RUN;
   const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(gdn_stream_score_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
-                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm);
+  hipLaunchKernelGGL(gdn_stream_score_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
+                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm,
+                     static_cast<const unsigned char*>(nullptr));
   return gdn_launch_status();
 }
 
@@ -314,8 +422,53 @@ extern "C" int gdn_stream_advance(void* state, const float* chunk, const float* 
   if (log_len > 0 && (!log_ticks || !log_sensors)) return GDN_ERR_ARG;
   if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
   if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(gdn_stream_advance_kernel, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0, (hipStream_t)stream,
-                     state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
-                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len);
+  hipLaunchKernelGGL(gdn_stream_advance_kernel<false>, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0,
+                     (hipStream_t)stream, state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
+                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len,
+                     static_cast<const unsigned char*>(nullptr), static_cast<const int*>(nullptr),
+                     static_cast<long long*>(nullptr));
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_stream_fill(const void* state, const float* raw_chunk, int c, int count, int n, int w,
+                               float* filled_chunk, uint8_t* valid, int32_t* gap_chunk, void* stream) {
+  if (!state || !raw_chunk || !filled_chunk || !valid || !gap_chunk) return GDN_ERR_ARG;
+  if (count < 1 || count > c) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(gdn_stream_fill_kernel, dim3(((unsigned)n + 63) / 64), dim3(GDN_FILL_WAVES * 64), 0,
+                     (hipStream_t)stream, state, raw_chunk, count, n, w, filled_chunk, valid, gap_chunk);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_stream_score_gaps(const void* state, const float* pred, const float* chunk, const uint8_t* valid,
+                                     const double* med_iqr, const double* threshold, int c, int count, int n, int m,
+                                     double* top_scores, int32_t* top_sensors, int32_t* alarm, void* stream) {
+  if (!state || !pred || !chunk || !valid || !med_iqr || !threshold || !top_scores || !top_sensors || !alarm)
+    return GDN_ERR_ARG;
+  if (count < 1 || count > c) return GDN_ERR_ARG;
+  if (n < 1 || n > 4096) return GDN_ERR_UNSUPPORTED;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  const int runs = (count + RUN - 1) / RUN;
+  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
+  hipLaunchKernelGGL(gdn_stream_score_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
+                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm, valid);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_stream_advance_gaps(void* state, const float* chunk, const float* pred, const uint8_t* valid,
+                                       const int32_t* gap_chunk, const double* med_iqr, const int32_t* alarm,
+                                       const int32_t* top_sensors, int c, int count, int n, int w, int m,
+                                       int64_t* log_ticks, int32_t* log_sensors, long long log_len, int64_t* gaps,
+                                       void* stream) {
+  if (!state || !chunk || !pred || !valid || !gap_chunk || !med_iqr || !alarm || !top_sensors || !gaps)
+    return GDN_ERR_ARG;
+  if (count < 1 || count > c || log_len < 0) return GDN_ERR_ARG;
+  if (log_len > 0 && (!log_ticks || !log_sensors)) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(gdn_stream_advance_kernel<true>, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0,
+                     (hipStream_t)stream, state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
+                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len, valid, gap_chunk,
+                     reinterpret_cast<long long*>(gaps));
   return gdn_launch_status();
 }

@@ -1422,10 +1422,19 @@ class StreamDetector:
     normal (`from_calibration`); `history` [n, h >= w] fp32 holds the ticks before the stream (a cold start is
     refused).  `top_m` sensors per tick are kept (1 .. 8); `log` alarm entries are kept (0: no log).  `wide`: None asks
     model.wide_for(history) once, True / False is the caller's word; under operand_range == "auto" on the planned
-    matrix-core route the forward is the guarded launch, which redoes an out-of-range push in fp32 on the device."""
+    matrix-core route the forward is the guarded launch, which redoes an out-of-range push in fp32 on the device.
+
+    `gaps=True` gives the detector a notion of a missing reading: a pushed value that is not finite
+    (NaN, +inf, -inf).  The push lands in `raw_buf` and gdn_stream_fill leads the launches: it holds every missing
+    reading at its sensor's latest real one (`chunk_buf` is then the FILLED chunk, which windows, forward, score, hist
+    and localise() read) and writes the validity plane `valid` [chunk, n] uint8 (`valid[:r]` describes the last
+    push).  The score and advance launches are their `_gaps` variants: the normalised error of a missing reading is
+    exactly 0.0, so a dropped reading neither raises nor blinds the four ticks its error would sit in.
+    `status_gaps()` reads the per-sensor counters.  `history[:, -w:]` must be finite.  With no missing reading the
+    detector writes the bits a gaps=False detector writes; gaps=False issues exactly the launches it always did."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
-                 use_graph: bool = True, wide: bool | None = None):
+                 use_graph: bool = True, wide: bool | None = None, gaps: bool = False):
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -1450,6 +1459,10 @@ class StreamDetector:
             raise ValueError(f"expected med_iqr of shape [{n}, 2], got {tuple(med_iqr.shape)}")
         self.med_iqr = med_iqr.clone()
         self.threshold = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev).clone()
+        self.with_gaps = bool(gaps)
+        if self.with_gaps and history.shape[1] >= w and not bool(torch.isfinite(history[:, -w:]).all()):
+            raise ValueError(f"history: its last {w} ticks hold a value that is not finite; with gaps=True every "
+                             "missing reading is held at an earlier real one, so the stream must begin on real readings")
         self.state = ops.stream_state(history, w)
         self.wide = model.wide_for(history[:, -w:]) if wide is None else bool(wide)
         c, m = self.chunk, self.top_m
@@ -1461,6 +1474,12 @@ class StreamDetector:
         self.alarm = torch.zeros((c,), dtype=torch.int32, device=dev)
         self.log_ticks = torch.zeros((int(log),), dtype=torch.int64, device=dev) if log else None
         self.log_sensors = torch.zeros((int(log), m), dtype=torch.int32, device=dev) if log else None
+        self.raw_buf = self.valid = self.gap_chunk = self.gaps = None
+        if self.with_gaps:
+            self.raw_buf = torch.zeros((c, n), dtype=torch.float32, device=dev)
+            self.valid = torch.zeros((c, n), dtype=torch.uint8, device=dev)
+            self.gap_chunk = torch.zeros((2, n), dtype=torch.int32, device=dev)
+            self.gaps = torch.zeros((2, n), dtype=torch.int64, device=dev)      # missing_total, missing_run
         self.graph = None
         self._graph_key = None
         self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
@@ -1469,8 +1488,13 @@ class StreamDetector:
     def from_calibration(cls, model, series, chunk: int, batch: int = 8192, **kw):
         """A detector calibrated on `series` [n, T] fp32 on the device, a period known to be normal: ONE
         SeriesEvaluator step over it gives `med_iqr`; threshold = the largest anomaly score of that period (the rule
-        of `-report val`); history = its last w ticks unless `history=` names the ticks the stream really follows."""
+        of `-report val`); history = its last w ticks unless `history=` names the ticks the stream really follows.
+        `gaps=True` passes through; the calibration itself knows no missing reading, so a series that is not finite
+        is then refused."""
         series = ops._chk(series, name="series")
+        if kw.get("gaps") and not bool(torch.isfinite(series).all()):
+            raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
+                             "stream, not the calibration (fill or cut the period first)")
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         if series.dim() != 2 or series.shape[1] <= w:
             raise ValueError(f"calibration needs a series [n, T] with T > {w}, got {tuple(series.shape)}")
@@ -1490,9 +1514,18 @@ class StreamDetector:
         return not c.large and m._plan(c, False) is not None
 
     def _launch(self, count: int, guard: bool):
+        if self.with_gaps:
+            ops.stream_fill(self.state, self.raw_buf, self.w, self.chunk_buf, self.valid, self.gap_chunk, count=count)
         ops.stream_windows(self.state, self.chunk_buf, self.w, self.x, count=count)
         x = self.x if count == self.chunk else self.x[:count]
         self.model.forward_into(x, self.pred[:count], wide=self.wide, guard=guard)
+        if self.with_gaps:
+            ops.stream_score_gaps(self.state, self.pred, self.chunk_buf, self.valid, self.med_iqr, self.threshold,
+                                  self.top_m, self.top_scores, self.top_sensors, self.alarm, count=count)
+            ops.stream_advance_gaps(self.state, self.chunk_buf, self.pred, self.valid, self.gap_chunk, self.med_iqr,
+                                    self.alarm, self.top_sensors, self.w, self.top_m, self.gaps, self.log_ticks,
+                                    self.log_sensors, count=count)
+            return
         ops.stream_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.top_m,
                          self.top_scores, self.top_sensors, self.alarm, count=count)
         ops.stream_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors, self.w,
@@ -1507,7 +1540,7 @@ class StreamDetector:
 
     def _push(self, ticks):
         r = ticks.shape[0]
-        self.chunk_buf[:r].copy_(ticks)
+        (self.raw_buf if self.with_gaps else self.chunk_buf)[:r].copy_(ticks)
         self._last = r
         if r != self.chunk or not self.use_graph:
             return self._launch(r, self._guarded())
@@ -1548,10 +1581,20 @@ class StreamDetector:
                     torch.empty((0, self.top_m), dtype=torch.int32, device=dev))
         return ticks, alarms, self.log_ticks[:logged], self.log_sensors[:logged]
 
+    def status_gaps(self):
+        """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: the missing readings of every
+        sensor since the stream began, and the run of missing readings that ends at the last scored tick (0 after a
+        real reading; >= w: the sensor's whole window is held values).  ONE read (a synchronisation)."""
+        if not self.with_gaps:
+            raise ValueError("status_gaps(): the detector was built with gaps=False and counts no missing readings")
+        both = self.gaps.cpu()
+        return both[0], both[1]
+
     def localise(self, rows=None) -> Localisation:
         """harness.localise for the last push: which sensors deviate at its alarm rows (`rows=None`; or the given
         rows of the push) and which neighbours they were reading — ONE model.attention_at on the static window
-        buffer.  `ticks` are global stream ticks; the other fields mean what they mean for `localise`."""
+        buffer.  `ticks` are global stream ticks; the other fields mean what they mean for `localise`; under gaps=True
+        `observed` is the FILLED reading (the held value where the reading was missing: see `valid`)."""
         r, m = self._last, self.top_m
         if rows is None:
             rows = torch.nonzero(self.alarm[:r]).view(-1)

@@ -196,19 +196,22 @@ class Main:
         if self.env_config.get("localise"):
             self.save_localisation(best_model, gt, float(info[4]), self.env_config["localise"])
         if self.env_config.get("stream"):
-            self.stream_test_series(best_model, val_ticks, int(self.env_config["stream"]))
+            self.stream_test_series(best_model, val_ticks, int(self.env_config["stream"]),
+                                    gaps=bool(self.env_config.get("stream_gaps")))
         return info
 
-    def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10):
+    def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
-        counters and the alarm log are read ONCE at the end and kept as `stream_result`."""
+        counters and the alarm log are read ONCE at the end and kept as `stream_result`.  -stream_gaps: the detector
+        holds missing (non-finite) readings of the replayed ticks and keeps them out of the scores; the number of
+        sensors that had any and the missing readings in all join the printed line and `stream_result`."""
         w = self.train_config["slide_win"]
         lo, hi = int(val_ticks.min()), int(val_ticks.max())
         normal = self.train_series[:, lo - w:hi + 1].contiguous()
         det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
-                                                      top_m=min(3, normal.shape[0]))
+                                                      top_m=min(3, normal.shape[0]), gaps=gaps)
         ticks = self.test_series[:, w:].t().contiguous()
         for s in range(0, ticks.shape[0], chunk):
             det.push(ticks[s:s + chunk])
@@ -216,9 +219,16 @@ class Main:
         self.stream_result = {"chunk": chunk, "threshold": float(det.threshold.item()), "ticks": scored,
                               "alarms": alarms, "log_ticks": log_ticks.cpu().numpy(),
                               "log_sensors": log_sensors.cpu().numpy()}
+        held = ""
+        if gaps:
+            missing_total, _run = det.status_gaps()
+            self.stream_result["gap_sensors"] = int((missing_total > 0).sum())
+            self.stream_result["missing"] = int(missing_total.sum())
+            held = (f"; {self.stream_result['missing']} missing readings held on "
+                    f"{self.stream_result['gap_sensors']} sensors")
         first = ", ".join(str(int(t) + w) for t in self.stream_result["log_ticks"][:show])
         print(f"stream: {scored} ticks in pushes of {chunk}, threshold {self.stream_result['threshold']:.6g} from "
-              f"{normal.shape[1] - w} validation ticks: {alarms} alarm ticks"
+              f"{normal.shape[1] - w} validation ticks: {alarms} alarm ticks" + held
               + (f"; first at test ticks {first}" if alarms else "") + "\n")
         return self.stream_result
 
@@ -275,7 +285,7 @@ class Main:
 
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
-    -localise / -stream."""
+    -localise / -stream / -stream_gaps."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -300,6 +310,8 @@ def build_parser():
                         "report's threshold to this .npz", type=str, default="")
     parser.add_argument("-stream", help="after the report, replay the test series through a streaming detector in "
                         "pushes of this many ticks (calibrated on the validation block)", type=int, default=0)
+    parser.add_argument("-stream_gaps", help="with -stream: hold missing (non-finite) readings at the sensor's last "
+                        "real one and keep them out of the scores", action="store_true")
     return parser
 
 
@@ -318,7 +330,8 @@ def main(argv=None):
                     "hip_graph": not args.no_hip_graph}
     env_config = {"save_path": args.save_path_pattern, "dataset": args.dataset, "report": args.report,
                   "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
-                  "localise": args.localise, "stream": args.stream}
+                  "localise": args.localise, "stream": args.stream,
+                  "stream_gaps": args.stream_gaps}
     return Main(train_config, env_config, debug=False).run()
 
 

@@ -928,3 +928,61 @@ def stream_advance(state, chunk, pred, med_iqr, alarm, top_sensors, w: int, m: i
     _lib.call("gdn_stream_advance", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors),
               c, count, n, w, m, _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len,
               _stream())
+
+
+def stream_fill(state, raw_chunk, w: int, filled_chunk, valid, gap_chunk, count: int | None = None):
+    """Hold missing readings (not finite: NaN, +inf, -inf) of `raw_chunk` [c, n] at each sensor's latest real reading —
+    an earlier row of the chunk, else the state's hist[:, w - 1] — into `filled_chunk` [c, n]; valid [c, n] uint8 = 1
+    for a real reading; gap_chunk [2, n] int32 = the push's missing readings and its trailing run of them per sensor.
+    Rows >= count are not written."""
+    raw_chunk, c, n, count = _stream_dims(state, raw_chunk, count, w)
+    _stream_buf(filled_chunk, torch.float32, c * n, "filled_chunk")
+    _stream_buf(valid, torch.uint8, c * n, "valid")
+    _stream_buf(gap_chunk, torch.int32, 2 * n, "gap_chunk")
+    if filled_chunk.data_ptr() == raw_chunk.data_ptr():
+        raise ValueError("filled_chunk must not alias raw_chunk")
+    _lib.call("gdn_stream_fill", _ptr(state), _ptr(raw_chunk), c, count, n, w, _ptr(filled_chunk), _ptr(valid),
+              _ptr(gap_chunk), _stream())
+    return filled_chunk, valid, gap_chunk
+
+
+def stream_score_gaps(state, pred, chunk, valid, med_iqr, threshold, m: int, top_scores, top_sensors, alarm,
+                      count: int | None = None):
+    """stream_score on the filled `chunk` with the validity plane of stream_fill: the normalised error of a missing
+    reading is exactly 0.0 wherever it is used."""
+    chunk, c, n, count = _stream_dims(state, chunk, count, 1)
+    pred = _stream_buf(pred, torch.float32, c * n, "pred")
+    _stream_buf(valid, torch.uint8, c * n, "valid")
+    _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
+    _stream_buf(threshold, torch.float64, 1, "threshold")
+    _stream_buf(top_scores, torch.float64, c * m, "top_scores")
+    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
+    _stream_buf(alarm, torch.int32, c, "alarm")
+    _lib.call("gdn_stream_score_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(valid), _ptr(med_iqr), _ptr(threshold),
+              c, count, n, m, _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
+    return top_scores, top_sensors, alarm
+
+
+def stream_advance_gaps(state, chunk, pred, valid, gap_chunk, med_iqr, alarm, top_sensors, w: int, m: int, gaps,
+                        log_ticks=None, log_sensors=None, count: int | None = None):
+    """stream_advance on the filled `chunk`: carry entries of missing readings are 0.0, and the gap counters `gaps`
+    [2, n] int64 (missing_total, missing_run) take the push's gap_chunk.  The one launch that writes state and gaps."""
+    chunk, c, n, count = _stream_dims(state, chunk, count, w)
+    _stream_buf(pred, torch.float32, c * n, "pred")
+    _stream_buf(valid, torch.uint8, c * n, "valid")
+    _stream_buf(gap_chunk, torch.int32, 2 * n, "gap_chunk")
+    _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
+    _stream_buf(alarm, torch.int32, c, "alarm")
+    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
+    _stream_buf(gaps, torch.int64, 2 * n, "gaps")
+    if (log_ticks is None) != (log_sensors is None):
+        raise ValueError("give both log_ticks and log_sensors, or neither")
+    log_len = 0
+    if log_ticks is not None:
+        log_len = log_ticks.numel()
+        _stream_buf(log_ticks, torch.int64, log_len, "log_ticks")
+        _stream_buf(log_sensors, torch.int32, log_len * m, "log_sensors")
+    _lib.call("gdn_stream_advance_gaps", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(valid), _ptr(gap_chunk),
+              _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors), c, count, n, w, m,
+              _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len, _ptr(gaps),
+              _stream())

@@ -762,6 +762,36 @@ int gdn_stream_score(const void* state, const float* pred, const float* chunk, c
 int gdn_stream_advance(void* state, const float* chunk, const float* pred, const double* med_iqr,
                        const int32_t* alarm, const int32_t* top_sensors, int c, int count, int n, int w, int m,
                        int64_t* log_ticks, int32_t* log_sensors, long long log_len, void* stream);
+/* Missing readings (opt-in; additive entry points, the ABI version does not move).  A reading of the pushed chunk is
+ * MISSING when it is not finite (NaN, +inf, -inf: exponent field all ones).  A push is then, in stream order:
+ * gdn_stream_fill, gdn_stream_windows on the filled chunk, the forward, gdn_stream_score_gaps, gdn_stream_advance_gaps.
+ *   gdn_stream_fill          filled_chunk[b, i] for b < count = raw_chunk[b, i] when it is not missing, else the latest
+ *                            earlier reading of sensor i that was not missing: the closest earlier row of the chunk,
+ *                            else hist[i, w - 1] (finite by induction when the history the stream began on was finite:
+ *                            the caller's duty).  valid[b, i] = 1 for a real reading, 0 for a missing one.
+ *                            gap_chunk[0, i] = the missing readings of sensor i in this push, gap_chunk[1, i] = the run
+ *                            of missing readings that ends at row count - 1 (= count when every row was missing).
+ *                            Rows >= count of filled_chunk and valid are not written.  Reads the state, writes none of
+ *                            it.  One launch, no atomics.  filled_chunk must not alias raw_chunk.
+ *   gdn_stream_score_gaps    gdn_stream_score with `chunk` = the filled chunk and the validity plane: the normalised
+ *                            error of a missing reading is exactly 0.0 (the calibration median) in its own 4-tap mean
+ *                            and in those of the next three ticks; nothing else changes.  With every reading valid it
+ *                            writes the bits gdn_stream_score writes.
+ *   gdn_stream_advance_gaps  gdn_stream_advance with `chunk` = the filled chunk (hist rolls from it): the carry entries
+ *                            taken from the chunk are 0.0 where the reading was missing, and the gap counters
+ *                            gaps[2, n] int64 (row 0 missing_total, row 1 missing_run; zeroed by the caller before the
+ *                            first push) are folded: total += gap_chunk[0], run = gap_chunk[1] == count ? run + count
+ *                            : gap_chunk[1].  The only writer of the state and of `gaps`.
+ * Shapes and refusals as above (gdn_stream_score_gaps, like gdn_stream_score, has no w); all decided before any launch. */
+int gdn_stream_fill(const void* state, const float* raw_chunk, int c, int count, int n, int w, float* filled_chunk,
+                    uint8_t* valid, int32_t* gap_chunk, void* stream);
+int gdn_stream_score_gaps(const void* state, const float* pred, const float* chunk, const uint8_t* valid,
+                          const double* med_iqr, const double* threshold, int c, int count, int n, int m,
+                          double* top_scores, int32_t* top_sensors, int32_t* alarm, void* stream);
+int gdn_stream_advance_gaps(void* state, const float* chunk, const float* pred, const uint8_t* valid,
+                            const int32_t* gap_chunk, const double* med_iqr, const int32_t* alarm,
+                            const int32_t* top_sensors, int c, int count, int n, int w, int m, int64_t* log_ticks,
+                            int32_t* log_sensors, long long log_len, int64_t* gaps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@ and 512 ticks, a few thousand pushes after warm-up, HIP-event timed, every leg i
 
     python3 tools/probe_stream.py [--pushes 3000] [--runs 3]
 
+  --gaps: what missing readings cost instead of the legs above, same protocol —
+  (g0) the push of (a), gaps=False   (g1) gaps=True on clean ticks   (g2) gaps=True with about 1 % of the readings NaN
+
 Raw RESULT lines are what profiles/r07_stream_push.txt keeps."""
 import json
 import os
@@ -34,6 +37,26 @@ ARGV = sys.argv[1:]
 CHILD = _opt(ARGV, "--child", "")
 PUSHES = _opt(ARGV, "--pushes", 3000, int)
 RUNS = _opt(ARGV, "--runs", 3, int)
+GAPS = "--gaps" in ARGV
+
+if not CHILD and GAPS:
+    rows = {"g0": [], "g1": [], "g2": []}
+    for _ in range(RUNS):                       # alternate the legs; this process never opens the GPU
+        for leg in rows:
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", leg, "--pushes", str(PUSHES)]
+            run = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            lines = [ln for ln in run.stdout.splitlines() if ln.startswith("RESULT ")]
+            if run.returncode != 0 or not lines:
+                sys.exit(f"child ({leg}) failed (rc {run.returncode}):\n{run.stdout[-2000:]}\n{run.stderr[-2000:]}")
+            for ln in lines:
+                print(ln, flush=True)
+            rows[leg] += [json.loads(ln[len("RESULT "):]) for ln in lines]
+    for c in CHUNKS:
+        g0, g1, g2 = ([r["push_us"] for r in rows[leg] if r["chunk"] == c] for leg in rows)
+        fmt = lambda v: " ".join(f"{x:8.1f}" for x in v)
+        print(f"[stream gaps] chunk {c:3d}: gaps=False {fmt(g0)} us | gaps=True clean {fmt(g1)} us | gaps=True 1 % "
+              f"missing {fmt(g2)} us | fastest gaps=True clean / fastest gaps=False {min(g1) / min(g0):.3f}")
+    sys.exit(0)
 
 if not CHILD:
     rows = {"a": [], "b": [], "n": []}
@@ -87,8 +110,13 @@ def timed(push, pushes, warm=200):
 for c in CHUNKS:
     pushes = max(200, PUSHES // (1 if c < 512 else 4))
     ticks = torch.rand((64, c, N), generator=torch.Generator().manual_seed(2)).to(dev)      # 64 different chunks, cycled
-    if CHILD == "a":
+    if CHILD in ("a", "g0"):
         det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3)
+        us = timed(lambda i: det.push(ticks[i & 63]), pushes)
+    elif CHILD in ("g1", "g2"):
+        if CHILD == "g2":
+            ticks[torch.rand(ticks.shape, generator=torch.Generator().manual_seed(3)).to(dev) < 0.01] = float("nan")
+        det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3, gaps=True)
         us = timed(lambda i: det.push(ticks[i & 63]), pushes)
     elif CHILD == "n":
         det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3, use_graph=False)
