@@ -110,6 +110,9 @@ SIGNATURES = {
     "gdn_stream_fill": [_p, _p] + [_c_int] * 4 + [_p] * 4,
     "gdn_stream_score_gaps": [_p] * 6 + [_c_int] * 4 + [_p] * 4,
     "gdn_stream_advance_gaps": [_p] * 8 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p, _p],
+    "gdn_stream_calib_bytes": [_c_int, _c_int],
+    "gdn_stream_calib_write": [_p] * 4 + [_c_int] * 5 + [_p] * 3,
+    "gdn_stream_calib_write_gaps": [_p] * 5 + [_c_int] * 5 + [_p] * 3,
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

@@ -1431,10 +1431,22 @@ class StreamDetector:
     push).  The score and advance launches are their `_gaps` variants: the normalised error of a missing reading is
     exactly 0.0, so a dropped reading neither raises nor blinds the four ticks its error would sit in.
     `status_gaps()` reads the per-sensor counters.  `history[:, -w:]` must be finite.  With no missing reading the
-    detector writes the bits a gaps=False detector writes; gaps=False issues exactly the launches it always did."""
+    detector writes the bits a gaps=False detector writes; gaps=False issues exactly the launches it always did.
+
+    `recal=R` gives the detector a calibration ring on the device: `ring_keys` [n, R] float64 holds the
+    scoring keys |pred - gt| of the last R stream ticks (tick t in slot t mod R), `ring_keep` [R] uint8 which of them
+    count.  gdn_stream_calib_write sits between the score and the advance launch (captured with them): a tick is kept
+    unless it alarmed (`exclude_alarms`, default True) or — gaps=True — a reading of it was missing.  `recalibrate()`
+    overwrites `med_iqr` IN PLACE with the median / IQR of the kept ticks (one gdn_score_select straight from the
+    ring; the captured graph reads the table through the same pointer and stays) once `recal_min` ticks are kept
+    (default max(64, R // 4)); `threshold` (IQR-normalised units) and the carry are not touched.  `recal_every=E`:
+    `push` calls `recalibrate()` after every sub-push that crosses a multiple of E handed ticks.  `from_calibration`
+    seeds the ring with the last min(R, T - w) calibration ticks.  The ring writer only reads the stream: a recal=R
+    detector that never recalibrates writes the bits of a recal=0 one; recal=0 issues exactly the launches it did."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
-                 use_graph: bool = True, wide: bool | None = None, gaps: bool = False):
+                 use_graph: bool = True, wide: bool | None = None, gaps: bool = False, recal: int = 0,
+                 exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None):
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -1448,6 +1460,23 @@ class StreamDetector:
             raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {n}")
         if int(log) < 0:
             raise ValueError(f"log = {log}: the alarm log holds 0 or more entries")
+        self.recal, self.exclude_alarms, self.recal_every = int(recal), bool(exclude_alarms), int(recal_every)
+        self.recal_min = 0
+        if self.recal_every < 0 or (self.recal_every and not self.recal):
+            raise ValueError(f"recal_every = {recal_every}: recalibrating every so many ticks needs a calibration ring "
+                             "(recal=R) and a positive number of ticks")
+        if self.recal:                                     # host facts only: before any device work
+            if self.recal < self.chunk:
+                raise ValueError(f"recal = {recal}: the calibration ring must hold at least one push of chunk = "
+                                 f"{self.chunk} ticks (no two rows of a push may share a slot)")
+            if _lib.load().gdn_stream_calib_bytes(n, self.recal) <= 0:
+                raise ValueError(f"recal = {recal}: no calibration ring for n = {n}, R = {recal} (1 <= n <= 4096, "
+                                 "64 <= R <= 2^20, 8 n R <= 2 GiB)")
+            self.recal_min = max(64, self.recal // 4) if recal_min is None else int(recal_min)
+            if not 1 <= self.recal_min <= self.recal:
+                raise ValueError(f"recal_min = {recal_min}: between 1 and recal = {self.recal} kept ticks")
+        elif recal_min is not None:
+            raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
         if model.out_layer_num > 1 and not ops.mlp_fast_tail_supported(model.out_layer, model.embedding.weight.shape[1]):
             raise model._refusal("refuse_outlayer")        # (GDN.mlp_fast_path_supported's answer, from host facts)
         history = ops._chk(history, name="history")
@@ -1480,6 +1509,13 @@ class StreamDetector:
             self.valid = torch.zeros((c, n), dtype=torch.uint8, device=dev)
             self.gap_chunk = torch.zeros((2, n), dtype=torch.int32, device=dev)
             self.gaps = torch.zeros((2, n), dtype=torch.int64, device=dev)      # missing_total, missing_run
+        self.ring_keys = self.ring_keep = self._recal_ws = None
+        if self.recal:
+            self.ring_keys, self.ring_keep = ops.stream_calib_ring(n, self.recal, dev)
+            self._recal_ws = ops.score_select_workspace(1, n, self.recal, dev)
+        self.recals = 0                     # tables written by recalibrate()
+        self.recal_kept = 0                 # ... and the kept ticks behind the last one
+        self._handed = 0                    # ticks handed to push(): recal_every's clock
         self.graph = None
         self._graph_key = None
         self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
@@ -1503,7 +1539,19 @@ class StreamDetector:
         anomaly = ev.step()
         kw.setdefault("history", series[:, -w:])
         history = kw.pop("history")
-        return cls(model, ev.med_iqr, anomaly.max(), history, chunk, **kw)
+        det = cls(model, ev.med_iqr, anomaly.max(), history, chunk, **kw)
+        if det.recal:
+            det._seed(ev.pred, gt)
+        return det
+
+    def _seed(self, pred, gt):
+        """The keys of the last s = min(R, t) rows of a period normal by declaration, oldest first, into slots R - s ..
+        R - 1 with keep = 1 (no alarm is excluded): the stream starts at slot 0, so it overwrites the empty slots first
+        and the oldest seeded tick last."""
+        s = min(self.recal, pred.shape[0])
+        keys = ops.score_keys(pred[-s:], gt[-s:], s)
+        self.ring_keys[:, self.recal - s:].copy_(keys)
+        self.ring_keep[self.recal - s:].fill_(1)
 
     # the launches of a push: static arguments only (they are captured)
     def _guarded(self) -> bool:
@@ -1522,12 +1570,18 @@ class StreamDetector:
         if self.with_gaps:
             ops.stream_score_gaps(self.state, self.pred, self.chunk_buf, self.valid, self.med_iqr, self.threshold,
                                   self.top_m, self.top_scores, self.top_sensors, self.alarm, count=count)
+            if self.recal:
+                ops.stream_calib_write_gaps(self.state, self.pred, self.chunk_buf, self.alarm, self.valid,
+                                            self.ring_keys, self.ring_keep, self.exclude_alarms, count=count)
             ops.stream_advance_gaps(self.state, self.chunk_buf, self.pred, self.valid, self.gap_chunk, self.med_iqr,
                                     self.alarm, self.top_sensors, self.w, self.top_m, self.gaps, self.log_ticks,
                                     self.log_sensors, count=count)
             return
         ops.stream_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.top_m,
                          self.top_scores, self.top_sensors, self.alarm, count=count)
+        if self.recal:
+            ops.stream_calib_write(self.state, self.pred, self.chunk_buf, self.alarm, self.ring_keys, self.ring_keep,
+                                   self.exclude_alarms, count=count)
         ops.stream_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors, self.w,
                            self.top_m, self.log_ticks, self.log_sensors, count=count)
 
@@ -1569,8 +1623,32 @@ class StreamDetector:
             raise ValueError("a push needs at least one tick")
         for s in range(0, ticks.shape[0], self.chunk):
             self._push(ticks[s:s + self.chunk])
+            before, self._handed = self._handed, self._handed + self._last
+            if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
+                self.recalibrate()
         r = self._last
         return self.top_scores[:r], self.top_sensors[:r], self.alarm[:r]
+
+    def recalibrate(self) -> int:
+        """Overwrite `med_iqr` in place with the median / IQR per sensor of the kept ticks in the calibration ring
+        (np.median and numpy's 'linear' 25th / 75th percentiles: gdn_score_quantiles' arithmetic, ONE gdn_score_select
+        straight from the ring) and return how many ticks that was; with fewer than `recal_min` kept, write nothing
+        and return 0.  Eager, ONE host read (a synchronisation).  `threshold`, the carry and the captured graph stay:
+        the three normalised errors before the switch keep the table they were computed with."""
+        if not self.recal:
+            raise ValueError("recalibrate(): the detector was built with recal=0 and keeps no calibration ring")
+        total = int(self.ring_keep.sum())
+        if total < self.recal_min:
+            return 0
+        ops.score_select(self.ring_keys, 1, self.n, self.recal, total, self._recal_ws, out=self.med_iqr)
+        self.recals += 1
+        self.recal_kept = total
+        return total
+
+    def calibration(self):
+        """(a copy of the table in force [n, 2] float64, the kept ticks the last recalibrate() computed it from: 0 while
+        it is still the constructor's table)."""
+        return self.med_iqr.clone(), self.recal_kept
 
     def status(self):
         """(ticks, alarms, log_ticks[:logged], log_sensors[:logged]): ONE read of the counters (a synchronisation)."""

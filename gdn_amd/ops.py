@@ -986,3 +986,51 @@ def stream_advance_gaps(state, chunk, pred, valid, gap_chunk, med_iqr, alarm, to
               _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors), c, count, n, w, m,
               _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len, _ptr(gaps),
               _stream())
+
+
+def stream_calib_ring(n: int, R: int, device):
+    """An EMPTY calibration ring (include/gdn_hip.h "Rolling calibration") in one allocation of
+    gdn_stream_calib_bytes(n, R): (ring_keys [n, R] float64, every key the filler pattern; ring_keep [R] uint8, zero)."""
+    nbytes = _lib.load().gdn_stream_calib_bytes(n, R)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"calibration ring: no kernel for n = {n}, R = {R} (1 <= n <= 4096, 64 <= R <= 2^20, "
+                               "8 n R <= 2 GiB)")
+    ring = torch.full((nbytes // 8,), -1, dtype=torch.int64, device=device)            # all ones: the filler
+    ring_keys = ring[: n * R].view(torch.float64).view(n, R)
+    ring_keep = ring[n * R:].view(torch.uint8)[:R]
+    ring_keep.zero_()
+    return ring_keys, ring_keep
+
+
+def _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count):
+    chunk, c, n, count = _stream_dims(state, chunk, count, 1)
+    _stream_buf(pred, torch.float32, c * n, "pred")
+    _stream_buf(alarm, torch.int32, c, "alarm")
+    if ring_keys.dim() != 2 or ring_keys.shape[0] != n:
+        raise ValueError(f"ring_keys: expected [{n}, R], got {tuple(ring_keys.shape)}")
+    R = ring_keys.shape[1]
+    _stream_buf(ring_keys, torch.float64, n * R, "ring_keys")
+    _stream_buf(ring_keep, torch.uint8, R, "ring_keep")
+    return chunk, c, n, count, R
+
+
+def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_alarms: bool = True,
+                       count: int | None = None):
+    """Row b < count of the push -> slot (state.ticks + b) mod R of the calibration ring: its keys |pred - chunk| and
+    keep = 1, or the filler and keep = 0 when `exclude_alarms` and alarm[b] != 0.  After stream_score, before
+    stream_advance.  Writes the ring only."""
+    chunk, c, n, count, R = _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count)
+    _lib.call("gdn_stream_calib_write", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), c, count, n, R,
+              int(bool(exclude_alarms)), _ptr(ring_keys), _ptr(ring_keep), _stream())
+    return ring_keys, ring_keep
+
+
+def stream_calib_write_gaps(state, pred, chunk, alarm, valid, ring_keys, ring_keep, exclude_alarms: bool = True,
+                            count: int | None = None):
+    """stream_calib_write on the filled `chunk` with the validity plane of stream_fill: a tick with a missing reading in
+    any sensor is not kept either."""
+    chunk, c, n, count, R = _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count)
+    _stream_buf(valid, torch.uint8, c * n, "valid")
+    _lib.call("gdn_stream_calib_write_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), c, count, n,
+              R, int(bool(exclude_alarms)), _ptr(ring_keys), _ptr(ring_keep), _stream())
+    return ring_keys, ring_keep

@@ -792,6 +792,37 @@ int gdn_stream_advance_gaps(void* state, const float* chunk, const float* pred, 
                             const int32_t* gap_chunk, const double* med_iqr, const int32_t* alarm,
                             const int32_t* top_sensors, int c, int count, int n, int w, int m, int64_t* log_ticks,
                             int32_t* log_sensors, long long log_len, int64_t* gaps, void* stream);
+/* Rolling calibration (opt-in; additive entry points, the ABI version does not move).  A calibration ring keeps the
+ * scoring keys |pred - gt| of the last R stream ticks on the device, in the layout gdn_score_select reads as it stands
+ * (keys[1, n, pitch = R] holding `total` real keys, the filler in any slot), so that the median / IQR table the score
+ * launch reads through a fixed pointer can be recomputed in place from recent ticks, without a recapture.
+ * Ring: ONE allocation of gdn_stream_calib_bytes(n, R) = 8 n R + R bytes (rounded up to 8; 0 for an unsupported shape):
+ *   double  ring_keys[n, R]   slot j of sensor i: fabs((double)pred - (double)gt) as gdn_score_keys computes it, or
+ *                             the filler pattern (all ones)                                  (byte 0)
+ *   uint8   ring_keep[R]      1 where slot j holds a kept tick                               (byte 8 n R)
+ * An empty ring (the caller's duty before the first push): every key the filler, every keep flag 0.
+ *   gdn_stream_calib_write       row b < count of the push is stream tick ticks + b (ticks read from the state) and owns
+ *                                slot (ticks + b) mod R, whatever the alarms or the push sizes: the ring holds the last
+ *                                R stream ticks.  The tick is KEPT unless exclude_alarms != 0 and alarm[b] != 0; a kept
+ *                                tick writes its n keys and keep = 1, a tick that is not kept the filler into all n
+ *                                keys and keep = 0 (no older tick survives in its slot).  Rows >= count touch nothing.
+ *                                In stream order AFTER the score launch of the push (it wrote `alarm`) and BEFORE the
+ *                                advance launch (ticks is still the push's first tick).  Reads the state, pred, chunk
+ *                                and alarm; writes the ring only.  One launch, no atomics.
+ *   gdn_stream_calib_write_gaps  the same on the filled chunk with the validity plane of gdn_stream_fill: a tick with a
+ *                                missing reading in any sensor is not kept either (kept ticks are complete: filled =
+ *                                raw there).
+ * The table: gdn_score_select(ring_keys, 1, n, R, total = the sum of ring_keep, workspace, med_iqr) — every sensor has
+ * the same `total` because keeping is decided per tick.
+ * 1 <= n <= 4096, 64 <= R <= 2^20, 8 n R <= 2 GiB: else GDN_ERR_UNSUPPORTED.  Null pointers, count < 1, count > c,
+ * c > R (two rows of a push would share a slot): GDN_ERR_ARG.  All decided before any launch.                        */
+long long gdn_stream_calib_bytes(int n, int R);
+int gdn_stream_calib_write(const void* state, const float* pred, const float* chunk, const int32_t* alarm, int c,
+                           int count, int n, int R, int exclude_alarms, double* ring_keys, uint8_t* ring_keep,
+                           void* stream);
+int gdn_stream_calib_write_gaps(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                                const uint8_t* valid, int c, int count, int n, int R, int exclude_alarms,
+                                double* ring_keys, uint8_t* ring_keep, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,10 @@ and 512 ticks, a few thousand pushes after warm-up, HIP-event timed, every leg i
   --gaps: what missing readings cost instead of the legs above, same protocol —
   (g0) the push of (a), gaps=False   (g1) gaps=True on clean ticks   (g2) gaps=True with about 1 % of the readings NaN
 
+  --recal R: what the calibration ring costs instead of the legs above, same protocol —
+  (r0) the push of (a), recal=0   (r1) recal=R: the ring writer rides in the replay; after the timed pushes a second
+  recalibrate() is timed on the host clock (the read of ring_keep, the select, a synchronisation)
+
 Raw RESULT lines are what profiles/r07_stream_push.txt keeps."""
 import json
 import os
@@ -38,6 +42,27 @@ CHILD = _opt(ARGV, "--child", "")
 PUSHES = _opt(ARGV, "--pushes", 3000, int)
 RUNS = _opt(ARGV, "--runs", 3, int)
 GAPS = "--gaps" in ARGV
+RECAL = _opt(ARGV, "--recal", 0, int)
+
+if not CHILD and RECAL:
+    rows = {"r0": [], "r1": []}
+    for _ in range(RUNS):                       # alternate the legs; this process never opens the GPU
+        for leg in rows:
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", leg, "--pushes", str(PUSHES), "--recal", str(RECAL)]
+            run = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            lines = [ln for ln in run.stdout.splitlines() if ln.startswith("RESULT ")]
+            if run.returncode != 0 or not lines:
+                sys.exit(f"child ({leg}) failed (rc {run.returncode}):\n{run.stdout[-2000:]}\n{run.stderr[-2000:]}")
+            for ln in lines:
+                print(ln, flush=True)
+            rows[leg] += [json.loads(ln[len("RESULT "):]) for ln in lines]
+    for c in CHUNKS:
+        r0, r1 = ([r["push_us"] for r in rows[leg] if r["chunk"] == c] for leg in rows)
+        once = [r["recal_us"] for r in rows["r1"] if r["chunk"] == c]
+        fmt = lambda v: " ".join(f"{x:8.1f}" for x in v)
+        print(f"[stream recal] chunk {c:3d}: recal=0 {fmt(r0)} us | recal={RECAL} {fmt(r1)} us | fastest recal={RECAL} / "
+              f"fastest recal=0 {min(r1) / min(r0):.3f} | one recalibrate() {fmt(once)} us")
+    sys.exit(0)
 
 if not CHILD and GAPS:
     rows = {"g0": [], "g1": [], "g2": []}
@@ -110,7 +135,8 @@ def timed(push, pushes, warm=200):
 for c in CHUNKS:
     pushes = max(200, PUSHES // (1 if c < 512 else 4))
     ticks = torch.rand((64, c, N), generator=torch.Generator().manual_seed(2)).to(dev)      # 64 different chunks, cycled
-    if CHILD in ("a", "g0"):
+    extra = {}
+    if CHILD in ("a", "g0", "r0"):
         det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3)
         us = timed(lambda i: det.push(ticks[i & 63]), pushes)
     elif CHILD in ("g1", "g2"):
@@ -118,6 +144,18 @@ for c in CHUNKS:
             ticks[torch.rand(ticks.shape, generator=torch.Generator().manual_seed(3)).to(dev) < 0.01] = float("nan")
         det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3, gaps=True)
         us = timed(lambda i: det.push(ticks[i & 63]), pushes)
+    elif CHILD == "r1":
+        # exclude_alarms=False: the untrained model alarms at most ticks under this table; the writer's work is the same
+        det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3, recal=RECAL, recal_min=64,
+                                     exclude_alarms=False)
+        us = timed(lambda i: det.push(ticks[i & 63]), pushes)
+        import time
+        det.recalibrate()                                           # (the first call loads the select's kernels)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        kept = det.recalibrate()
+        torch.cuda.synchronize()
+        extra = {"recal": RECAL, "kept": kept, "recal_us": (time.perf_counter() - t0) * 1e6}
     elif CHILD == "n":
         det = harness.StreamDetector(model, med_iqr, 5.0, history, c, top_m=3, use_graph=False)
         det.push(ticks[0])
@@ -159,4 +197,4 @@ for c in CHUNKS:
                 halo_g.copy_(torch.cat([halo_g[c:], gt]))
             pos["tick"] = t + c
         us = timed(old, pushes)
-    print("RESULT " + json.dumps({"leg": CHILD, "chunk": c, "pushes": pushes, "push_us": us}), flush=True)
+    print("RESULT " + json.dumps({"leg": CHILD, "chunk": c, "pushes": pushes, "push_us": us, **extra}), flush=True)
