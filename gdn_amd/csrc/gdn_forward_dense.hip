@@ -39,6 +39,9 @@
 //   P0 only the scalar tile (s_i, s_j) is left of P;
 //   M  Zx^T[w, target] += X^T . A^T, one column block; the accumulator (target on the lane, w in the registers)
 //      IS the B operand of the projection in k order "element j of half h = w 16wk + 8(j>>2) + 4h + (j&3)";
+//      w <= 16 (DCfg::XHALF): 2 passes (ahi, alo) x 8 k-steps = 16 products instead of 24, 4 ds_read_b128 less per
+//      pass pair and k-step: product rows 16 .. 31, which no window column fills, carry the lo term of X^T and are
+//      added to rows 0 .. 15 (accumulator registers 8 + j to j) in front of P1;
 //   P1 out^T[c, target] = lin' . Zx + C (C-in from the table block), the layout E consumes.
 // With bf16 storage the projected tile must be rounded to bf16 as the staged path stores it: that order stays.
 #include "gdn_common.hpp"
@@ -178,9 +181,10 @@ struct DCfg {
   static constexpr int NTXIN = FMT == FMT_F16 ? 2 : 1; // terms of the x values (bf16 storage: exact)
   static constexpr int XP = 16 * WK + 4;               // x tile pitch in floats (odd number of 16-B slots)
   static constexpr int XU = 8 * WK;                    // x values per thread per window
-  // XAGG, WK = 1: rows 16 .. 31 of X^T do not exist and rows 16 .. 31 of the product Zx^T are never consumed (P1
-  // reads accumulator registers 0 .. 8 WK - 1), so a fragment holds the 16 lanes of each lane half that carry
-  // window columns and the lanes l32 >= 16 read their neighbour's slot: whatever they multiply lands in dead rows
+  // XAGG, WK = 1: rows 16 .. 31 of X^T do not exist, so a fragment holds the 16 lanes of each lane half that carry
+  // window columns, and the lanes l32 >= 16 read the LO term of their neighbour's slot where the lanes l32 < 16 read
+  // the hi term: rows 16 .. 31 of the product Zx^T are the lo-term contribution to rows 0 .. 15 (accumulator
+  // registers 8 + j and j of one lane), which P1 adds before it splits the aggregated row (see M in the kernel)
   static constexpr bool XHALF = XAGG && WK == 1;
   static constexpr int XFL = XHALF ? 16 : 32;          // stored lanes per lane half of an X^T fragment
   static constexpr int XFRAG = 2 * XFL * 16;           // bytes per (k-step, block, term)
@@ -757,6 +761,9 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
   const int arow_off = C::OFF_A + wv * C::AWAVE + l32 * C::AROW + h * 16;   // alpha operand of this lane
   const int xrow_off = C::OFF_XS + ((32 * wv + l32) * C::XP + 8 * h) * 4;  // x operand of this lane (not XAGG)
   const int ec_off = C::OFF_EC + 16 * h;                                   // + 32 (r >> 2) + 128 cb: 4 columns
+  // XHALF: the X^T operand of this lane in M, + k-step: product rows l32 < 16 take the hi term of window column l32,
+  // rows l32 >= 16 (which no window column has) the lo term of column l32 - 16, one term (XFRAG bytes) further on
+  const int xf_half = C::OFF_XF + (h * 16 + (l32 & 15)) * 16 + (l32 >> 4) * C::XFRAG;
 
   for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
     if constexpr (C::XAGG) {
@@ -896,7 +903,38 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[cb][r] = 0.f;
     constexpr int XF_KS = MCB * C::NPX * C::XFRAG;      // bytes of fragments per k-step
-    const int xf_lane = C::OFF_XF + (C::XHALF ? h * 16 + (l32 & 15) : lane) * 16;   // (XHALF: see DCfg)
+    if (b == (int)blockIdx.x) { GDN_STAMP(7) }
+    __builtin_amdgcn_s_setprio(GDN_PRIO_M);      // see the note at the kernel's head
+    if constexpr (C::XHALF) {
+      // ONE X fragment per lane and k-step for both passes (xf_half): rows 0 .. 15 of the product multiply the hi
+      // term of X^T, rows 16 .. 31 its lo term.  Summation order per (w, target), fp32:
+      //   registers 0 .. 7   (rows r):       sum_ks Xhi.ahi, then + sum_ks Xhi.alo   (16 products, one chain)
+      //   registers 8 .. 15  (rows 16 + r):  sum_ks Xlo.ahi, then + sum_ks Xlo.alo   (16 products, one chain)
+      // and P1 adds register 8 + j to register j once.  The lo pass keeps the SAME addressing rather than the
+      // neighbour's hi fragment (which would put a second Xhi.alo into the rows that are folded) or a fold between
+      // the passes (VALU work inside the accumulator chain): no register, no instruction, and Xlo.alo is the fourth
+      // term of (Xhi + Xlo)(ahi + alo), 2^-22 of the product, which the three-product form left out.
+      u32x4 fa[2], fx[2];
+      auto fetch = [&](int ks, int buf) {
+        fa[buf] = lds_frag(smem, arow_off + ks * 32);
+        fx[buf] = lds_frag(smem, xf_half + ks * XF_KS);
+      };
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+        scatter_terms<SL>(smem, k.scoff, pass == 0 ? ph : pl);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) {
+          if (ks + 1 < C::KS) fetch(ks + 1, (ks + 1) & 1);
+          __builtin_amdgcn_sched_barrier(0);
+          acc2[0] = F::mfma(fx[ks & 1], fa[ks & 1], acc2[0]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    } else {
+    const int xf_lane = C::OFF_XF + lane * 16;
     u32x4 fa[2], fx[2][MCB][C::NPX];
     auto fetch_hi = [&](int ks, int buf) {
       fa[buf] = lds_frag(smem, arow_off + ks * 32);
@@ -910,8 +948,6 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
 #pragma unroll
       for (int cb = 0; cb < MCB; ++cb) fx[buf][cb][0] = lds_frag(smem, xf_lane + ks * XF_KS + cb * C::NPX * C::XFRAG);
     };
-    if (b == (int)blockIdx.x) { GDN_STAMP(7) }
-    __builtin_amdgcn_s_setprio(GDN_PRIO_M);      // see the note at the kernel's head
     scatter_terms<SL>(smem, k.scoff, ph);
     __builtin_amdgcn_sched_barrier(0);
     fetch_hi(0, 0);
@@ -938,6 +974,7 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
       for (int cb = 0; cb < MCB; ++cb) acc2[cb] = F::mfma(fx[ks & 1][cb][0], fa[ks & 1], acc2[cb]);
       __builtin_amdgcn_sched_barrier(0);
     }
+    }   // not XHALF
     if (b == (int)blockIdx.x) { GDN_STAMP(8) }
     // ------------------------------------------------------------ P1 (XAGG)
     // out^T[c, target] = lin' . Zx + C.  Registers 8wk .. 8wk+7 of the aggregation accumulator (target on the lane)
@@ -958,8 +995,11 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
       for (int wk = 0; wk < WK; ++wk) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          v[j] = acc2[0][8 * wk + j] * (GDN_F16_Z_SCALE / (GDN_F16_ALPHA_SCALE * GDN_F16_XT_SCALE));
+        for (int j = 0; j < 8; ++j) {
+          // XHALF: row 16 + r of the accumulator is register 8 + j of the same lane: the lo term of X^T (see M)
+          const float z = C::XHALF ? acc2[0][j] + acc2[0][8 + j] : acc2[0][8 * wk + j];
+          v[j] = z * (GDN_F16_Z_SCALE / (GDN_F16_ALPHA_SCALE * GDN_F16_XT_SCALE));
+        }
         u32x4 zf[2];
         split8<FMT, 2>(v, zf);
 #pragma unroll
