@@ -114,7 +114,10 @@ struct BwdPlan {
 // workgroup walks NSL column slices of D one after the other, in both passes.  Pass 1 keeps the partial
 // d_alpha of the earlier slices in the d_pi workspace and finishes the softmax on the last slice (each
 // element is written and read back by the same lane); the sum of two slices is the sum the unsliced kernel
-// forms with its two lane groups, so both give the same bits.
+// forms with its two lane groups, so both give the same bits.  d_bias too: the sliced kernel sums a slice's columns
+// of d_z from the pass-2 tile with the unsliced 512-thread launch's assignment of rows to lane groups (it used to sum
+// them per target in pass 1, 32 groups against 16: another order, other bits) — the same bits as long as both forms
+// give every workgroup the same windows (grid = batch; tests/test_gpu_backward_stages.py).
 template <int D, int NT, bool GLB, bool DX = true, int NSL = 1>
 __global__ __launch_bounds__(NT) void gdn_attn_bwd_kernel(
     const BwdPlan pl, const float* __restrict__ d_z, const float* __restrict__ xlin,
@@ -216,8 +219,10 @@ __global__ __launch_bounds__(NT) void gdn_attn_bwd_kernel(
         const int i = ib + q * tpp;
         if (i >= pl.n) break;
         const PackB<G::VEC>& g = gq[q];
+        if constexpr (NSL == 1) {   // (column slices: summed in pass 2, in the unsliced kernel's order)
 #pragma unroll
-        for (int v = 0; v < G::VEC; ++v) bias_acc[cs].v[v] += g.v[v];
+          for (int v = 0; v < G::VEC; ++v) bias_acc[cs].v[v] += g.v[v];
+        }
         const float sti = si[i];
         float dot = 0.f;
         for (int r = 0; r < rounds; ++r) {
@@ -259,6 +264,16 @@ __global__ __launch_bounds__(NT) void gdn_attn_bwd_kernel(
     if constexpr (DX) {   // the tile now holds (this column slice of) d_z of this window (row n stays 0)
       stage_tile(d_z + row0 * DF, cs * D);
       __syncthreads();
+      if constexpr (NSL > 1) {
+        // d_bias of this slice, summed as the unsliced kernel sums it: tpp / NSL lane groups (its two groups per
+        // target share one slot), group s the rows s, s + tpp / NSL, ... in ascending order — the same bits
+        if (slot < tpp / NSL)
+          for (int i = slot; i < pl.n; i += tpp / NSL) {
+            const PackB<G::VEC> g = ldp<G::VEC>(tile + i * D + d0);
+#pragma unroll
+            for (int v = 0; v < G::VEC; ++v) bias_acc[cs].v[v] += g.v[v];
+          }
+      }
     }
 
     // ---- pass 2: per source, over its reverse list; the first two rounds of BL sources are fetched together
@@ -307,12 +322,15 @@ __global__ __launch_bounds__(NT) void gdn_attn_bwd_kernel(
   // d_bias = column sums of d_z: the lane groups' sums meet in LDS in a fixed order (the tile is free by now),
   // the workgroups' rows in gdn_colsum_ticket — no floating-point atomics, bitwise reproducible
   float* gsum = smem + pl.off_red;                      // [tpp][DF] then nth floats (the tile itself when it is large enough)
+  const int brows = tpp / NSL;                          // lane groups that hold column sums (slices: see pass 2)
+  if (slot < brows) {
 #pragma unroll
-  for (int s = 0; s < NSL; ++s) stp<G::VEC>(gsum + slot * DF + s * D + d0, bias_acc[s]);
+    for (int s = 0; s < NSL; ++s) stp<G::VEC>(gsum + slot * DF + s * D + d0, bias_acc[s]);
+  }
   __syncthreads();
   for (int t = tid; t < DF; t += nth) {
     float s = 0.f;
-    for (int q = 0; q < tpp; ++q) s += gsum[q * DF + t];
+    for (int q = 0; q < brows; ++q) s += gsum[q * DF + t];
     dbias[t] = s;
   }
   __syncthreads();

@@ -516,6 +516,7 @@ def test_matrix_core_backward_of_the_aggregate_over_random_shapes(gpu_device):
     products, d_z scaled per window) against float64 autograd of the same layer (graph_layer.py:106-117 in list
     form), over a seeded sweep of shapes and with the gradient magnitude varying by 12 orders of magnitude
     BETWEEN the windows of one launch (the per-window power-of-two scaling)."""
+    from _graph_layer_bwd_ref import aggregate_ref
     from gdn_amd import _lib, ops
     rng = np.random.default_rng(7)
     shapes = [(127, 30), (127, 63), (2, 1), (31, 15), (32, 16), (33, 31), (64, 47), (65, 48), (96, 5), (97, 32)]
@@ -536,26 +537,17 @@ def test_matrix_core_backward_of_the_aggregate_over_random_shapes(gpu_device):
         dev = lambda t: t.to(gpu_device)
         z, alpha = ops.attn_aggregate_fwd(dev(xlin), dev(s_i), dev(s_j), graph, dev(bias), b, want_alpha=True)
         d_xlin, d_si, d_sj, d_bias = ops.attn_aggregate_bwd(dev(d_z), dev(xlin), alpha, dev(s_i), dev(s_j), graph, b)
-        # float64 autograd of the layer in list form
-        nbr = graph.nbr.cpu().long()                                       # [n, pitch], padding = n
-        x64 = xlin.double().view(b, n, d).requires_grad_(True)
-        si64 = s_i.double().view(b, n).requires_grad_(True)
-        sj64 = s_j.double().view(b, n).requires_grad_(True)
-        b64 = bias.double().requires_grad_(True)
-        xpad = torch.cat((x64, torch.zeros((b, 1, d), dtype=torch.float64)), 1)
-        sjpad = torch.cat((sj64, torch.full((b, 1), -float("inf"), dtype=torch.float64)), 1)
-        e = torch.nn.functional.leaky_relu(si64.unsqueeze(-1) + sjpad[:, nbr], 0.2)
-        a64 = torch.softmax(e, dim=-1)
-        z64 = (a64.unsqueeze(-1) * xpad[:, nbr]).sum(2) + b64
-        np.testing.assert_allclose(z.cpu().double().numpy(), z64.detach().reshape(b * n, d).numpy(), atol=3e-6, rtol=1e-5)
-        z64.backward(d_z.double().view(b, n, d))
+        # float64 autograd of the layer in list form (tests/_graph_layer_bwd_ref.py; nbr: [n, pitch], padding = n)
+        z64, _a64, dx64, dsi64, dsj64, db64 = aggregate_ref(xlin.view(b, n, d), s_i.view(b, n), s_j.view(b, n), bias,
+                                                            graph.nbr.cpu().long(), d_z.view(b, n, d))
+        np.testing.assert_allclose(z.cpu().double().numpy(), z64.reshape(b * n, d).numpy(), atol=3e-6, rtol=1e-5)
         scale = mags.double().view(b, 1, 1)                                 # compare per window, relative to its scale
-        for name, got, want in (("d_xlin", d_xlin.view(b, n, d), x64.grad), ("d_si", d_si.view(b, n, 1), si64.grad.unsqueeze(-1)),
-                                ("d_sj", d_sj.view(b, n, 1), sj64.grad.unsqueeze(-1))):
+        for name, got, want in (("d_xlin", d_xlin.view(b, n, d), dx64), ("d_si", d_si.view(b, n, 1), dsi64.unsqueeze(-1)),
+                                ("d_sj", d_sj.view(b, n, 1), dsj64.unsqueeze(-1))):
             err = ((got.cpu().double() - want) / scale).abs().max()
             ref = (want / scale).abs().max().clamp_min(1.0)
             assert float(err / ref) < 3e-6, (n, k, b, name, float(err / ref))
-        np.testing.assert_allclose(d_bias.cpu().double().numpy(), b64.grad.numpy(), rtol=2e-5,
+        np.testing.assert_allclose(d_bias.cpu().double().numpy(), db64.numpy(), rtol=2e-5,
                                    atol=2e-6 * float(mags.max()) * (b * n) ** 0.5)
 
 
