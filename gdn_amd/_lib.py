@@ -92,6 +92,7 @@ SIGNATURES = {
     "gdn_score_select_workspace_bytes": [_c_int, _c_int, _c_int],
     "gdn_score_keys": [_p, _p, _c_int, _c_int, _c_int, _p, _p],
     "gdn_score_select": [_p, _c_int, _c_int, _c_int, ctypes.c_longlong, _p, _p, _p],
+    "gdn_score_select_paths": [_p, _c_int, _c_int, _c_int, ctypes.c_longlong, _p, _p, _p, _p],
     "gdn_score_quantiles": [_p, _p, _c_int, _c_int, _p, _p, _p],
     "gdn_score_smooth_max": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p],
     "gdn_score_smooth_topm": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p],

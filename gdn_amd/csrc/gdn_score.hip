@@ -14,6 +14,8 @@ struct SelectArgs {
   int rank[NQ];      // 0-based ranks in the ascending order of |pred-gt|
   double gamma[2];   // interpolation weights of the 25th / 75th percentile (numpy 'linear')
   int median_pair;   // 1: t even, median = mean of two middle values
+  int total;         // real keys per sensor
+  int bracket;       // 1: the one-workgroup flat select first tries the sample brackets (select_onewg_kernel)
 };
 
 // keys[s][tick] = |pred[tick][s] - gt[tick][s]| in float64 (bit pattern = radix key), transposed
@@ -116,6 +118,38 @@ __device__ __forceinline__ void locate_bin(const unsigned int* h, int left0, uns
       }
     }
     *npf = pf | ((unsigned long long)(4 * lane + bin) << shift);
+    *nrem = left;
+  }
+}
+
+// the same over 512 bins (8 per lane) for the bracket path of select_onewg_kernel: a wave finds the bin that holds
+// position left0 and writes code0 + bin and the position inside the bin; NOTHING is written when left0 lies outside
+// [0, sum of h): that is how a rank outside its bracket shows
+__device__ __forceinline__ void locate_bin512(const unsigned int* h, int left0, unsigned int code0, int lane,
+                                              unsigned int* code, int* nrem) {
+  const uint4 a = *reinterpret_cast<const uint4*>(h + 8 * lane);
+  const uint4 b = *reinterpret_cast<const uint4*>(h + 8 * lane + 4);
+  const int c[8] = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, (int)b.z, (int)b.w};
+  int mine = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) mine += c[j];
+  int incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(incl, d);
+    if (lane >= d) incl += up;
+  }
+  const int excl = incl - mine;
+  if (left0 >= excl && left0 < incl) {
+    int left = left0 - excl, bin = 0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      if (bin == j && left >= c[j]) {
+        left -= c[j];
+        bin = j + 1;
+      }
+    }
+    *code = code0 + (unsigned int)(8 * lane + bin);
     *nrem = left;
   }
 }
@@ -377,10 +411,35 @@ constexpr int ONE_FK = 32;
 constexpr int ONE_CAP = 8192;   // 16-bit-prefix survivors kept in LDS (64 KB)
 constexpr int ONE_CAP2 = 1024;  // 24-bit-prefix survivors finished by counting
 
+//
+// BRACKET PATH (flat rows with >= 4 * BR_S real keys; every test below is uniform over the workgroup and a failed one
+// runs the digit passes above unchanged, in the same launch):
+//   sample    BR_S hi words at the fixed stride slots / BR_S (slot floor(j * slots / BR_S)), loaded BEFORE the row so
+//             that their bitonic sort (in-wave exchanges by lane shuffles, the ten cross-wave stages through LDS) runs
+//             while the row's 32 loads per thread are in flight; the filler sorts last, m = real samples.
+//   brackets  per rank pair (q25, median, q75) the sample order statistics d positions below the pair's scaled
+//             position r * m / total and d above it.  For i.i.d. keys the number X of sample keys <= the rank's key
+//             is hypergeometric, no wider than Binomial(m, p): sigma <= sqrt(m) / 2.  A side misses when X deviates by
+//             d; with d = 5.24 sigma = BR_C * sqrt(m), BR_C = 2.62, the normal tail is 8e-8 per side and 12 sides
+//             (6 ranks x 2) stay below 1e-6 per sensor.  Brackets are hi-word ranges (the enclosing hi-word values),
+//             overlapping ones are merged: at most three disjoint intervals, ~17 % of the row each at m = 1024.
+//   one pass  over the hi words in registers: per interval the keys strictly below it (register adds, wave
+//             reduction, one LDS atomic per wave and counter) and a 512-bin histogram of the keys inside it (bin =
+//             (hi - lo) >> shift: monotone in the key) -- the brackets of a 1024-key sample are thousands of keys wide,
+//             far too many to finish by counting, so each rank is first located in a bin of ~15 keys.
+//   finish    a rank outside [below, below + inside) of its interval -> fallback.  The keys of the ranks' bins
+//             (~50-100) are staged as slot numbers, re-read in full (> ONE_CAP2 of them -> fallback) and every rank
+//             is finished by the counting finisher: full 64-bit keys, the same bits as the digit passes give.
+constexpr int BR_S = ONE_NT;      // sample size: one key per thread
+constexpr float BR_C = 2.62f;     // margin in units of sqrt(m) sample positions (see above)
+constexpr unsigned int BR_NONE = 0xffffu;   // bin code of a key outside every interval
+
 template <bool FLAT>
 __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl, const SelectArgs sa,
-                                                              double* __restrict__ med_iqr) {
+                                                              double* __restrict__ med_iqr, int* __restrict__ path) {
   __shared__ unsigned int hist[NQ][256];
+  __shared__ unsigned int sbuf[2 * BR_S];    // bracket path: the sample (two exchange buffers of the sort)
+  __shared__ unsigned int br_below[3], br_code[NQ], br_m;
   __shared__ unsigned long long prefix[NQ];
   __shared__ unsigned long long stage[ONE_CAP];
   __shared__ unsigned long long stage2[ONE_CAP2];
@@ -423,30 +482,254 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
       return kl.keys[((size_t)blk * kl.n + s) * kl.pitch + off];
     }
   };
+  const bool try_bracket = flat && sa.bracket != 0 && sa.total >= 4 * BR_S;    // uniform
+  unsigned int smp = 0xffffffffu;
+  if constexpr (flat) {
+    if (try_bracket) smp = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (((unsigned int)tid * slots) / BR_S) * 8 + 4, 0, 0);
+  }
   unsigned int khi[ONE_FK];
 #pragma unroll
   for (int u = 0; u < ONE_FK; ++u) {
     unsigned int hi;
     if constexpr (flat) hi = __builtin_amdgcn_raw_buffer_load_b32(rsrc, tid * 8 + 4, u * (ONE_NT * 8), 0);
     else hi = tid + u * ONE_NT < slots ? (unsigned int)(key_full(u) >> 32) : 0u;
-    khi[u] = tid + u * ONE_NT < slots ? hi : 0xffffffffu;   // filler: never a real key
+    if constexpr (flat) khi[u] = hi;                         // (slots past the row: below, after the sample's sort)
+    else khi[u] = tid + u * ONE_NT < slots ? hi : 0xffffffffu;   // filler: never a real key
   }
-  if (tid < NQ) {
-    prefix[tid] = 0ull;
-    rem[tid] = sa.rank[tid];
-  }
-  if (tid == 0) {
-    n_stage = 0u;
-    n_stage2 = 0u;
-  }
-  __syncthreads();
+  // survivors (bit u of keep: my key u) first as SLOT NUMBERS in sidx, to be re-read in full by all threads at once
+  // (a load inside the per-slot branch would pay one L2 round trip per survivor, serially); one LDS atomic per
+  // WAVE: lanes scan their survivor counts, the last lane reserves the range.  Returns the survivors' number.
+  auto stage_slots = [&](unsigned int keep) -> unsigned int {
+    const int mine = __popc(keep);
+    int incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    unsigned int base = 0u;
+    if (lane == 63) base = atomicAdd(&n_stage, (unsigned int)incl);
+    base = __shfl(base, 63);
+    unsigned int pos = base + (unsigned int)(incl - mine);
+    unsigned int t1 = tid;
+    asm volatile("" : "+v"(t1));     // keeps the 32 slot numbers from being precomputed outside the pass loop
+#pragma unroll
+    for (int u = 0; u < ONE_FK; ++u) {
+      if ((keep >> u) & 1u) {
+        if (pos < (unsigned int)ONE_CAP) sidx[pos] = (unsigned short)(t1 + u * ONE_NT);   // slots <= 32768
+        ++pos;
+      }
+    }
+    __syncthreads();
+    return n_stage;
+  };
+  // every rank finished by COUNTING: a thread per candidate counts the smaller / equal candidates of its bucket
+  // (bucket_of(j): candidate j's bucket, rank_bucket(q): the bucket that holds rank q at position rem[q])
+  auto finish_by_counting = [&](const unsigned long long* cand, unsigned int n, auto bucket_of, auto rank_bucket) {
+    if ((unsigned int)tid < n) {
+      const unsigned long long k = cand[tid];
+      const auto mine = bucket_of((unsigned int)tid);
+      bool wanted = false;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) wanted |= rank_bucket(q) == mine;
+      if (wanted) {
+        int less = 0, equal = 0;
+        for (unsigned int j = 0; j < n; ++j) {
+          const unsigned long long o = cand[j];
+          if (bucket_of(j) != mine) continue;
+          less += o < k ? 1 : 0;
+          equal += o == k ? 1 : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const int want = rem[q];                    // 0-based position inside the bucket
+          if (rank_bucket(q) == mine && less <= want && want < less + equal) prefix[q] = k;   // equal keys write the same value
+        }
+      }
+    }
+    __syncthreads();
+  };
 #ifdef GDN_SELECT_TIMING
-  long long tick[12];
-  int nt = 0;
+  long long tick[12], btick[8];
+  int nt = 0, nbt = 0;
+  unsigned int br_n = 0u;
+#endif
+  bool bracketed = false;
+  if constexpr (flat) {
+    if (try_bracket) {
+      unsigned int* hflat = &hist[0][0];     // three intervals x 512 bins
+      for (int i = tid; i < 3 * 512; i += ONE_NT) hflat[i] = 0u;
+      if (tid < 3) br_below[tid] = 0u;
+      if (tid < NQ) br_code[tid] = ~0u;
+      if (tid == 0) {
+        br_m = 0u;
+        n_stage = 0u;
+      }
+      // bitonic sort of the sample, one key per thread; buffers alternate, so one barrier per cross-wave stage
+      unsigned int v = smp;
+      int pp = 0;
+#pragma unroll
+      for (int k = 2; k <= BR_S; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          unsigned int o;
+          if (j >= 64) {
+            sbuf[pp * BR_S + tid] = v;
+            __syncthreads();
+            o = sbuf[pp * BR_S + (tid ^ j)];
+            pp ^= 1;
+          } else {
+            o = (unsigned int)__shfl_xor((int)v, j);
+          }
+          const bool take_min = ((tid & j) == 0) == ((tid & k) == 0);
+          v = take_min ? min(v, o) : max(v, o);
+        }
+      }
+      static_assert(BR_S == 1024, "the sorted sample ends in the first exchange buffer after ten cross-wave stages");
+      sbuf[tid] = v;
+      __syncthreads();
+      if (v != 0xffffffffu && (tid == BR_S - 1 || sbuf[tid + 1] == 0xffffffffu)) br_m = (unsigned int)(tid + 1);
+      __syncthreads();
+#ifdef GDN_SELECT_TIMING
+      btick[nbt++] = wall_clock64();
+#endif
+    }
+  }
+  // the row's hi words are first needed here: the sort above ran while their loads were in flight
+  if constexpr (flat) {
+#pragma unroll
+    for (int u = 0; u < ONE_FK; ++u) khi[u] = tid + u * ONE_NT < slots ? khi[u] : 0xffffffffu;   // filler: never a real key
+  }
+  if constexpr (flat) {
+    if (try_bracket) {
+      unsigned int* hflat = &hist[0][0];
+      const unsigned int* sorted = sbuf;
+      const int m = (int)br_m;                 // real keys in the sample (the filler sorted last)
+      if (m >= BR_S / 2) {
+        const float fm = (float)m, ft = (float)sa.total;
+        const int margin = (int)(BR_C * sqrtf(fm)) + 2;
+        unsigned int lo[3], hi[3];             // q25, median, q75: ascending
+        const int first[3] = {2, 0, 4};
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+          const int li = (int)((float)sa.rank[first[g]] * fm / ft) - margin;
+          const int ui = (int)((float)sa.rank[first[g] + 1] * fm / ft) + 1 + margin;
+          lo[g] = li < 0 ? 0u : sorted[li];
+          hi[g] = ui >= m ? 0x7fffffffu : sorted[ui];
+        }
+        // merge overlapping brackets into disjoint intervals [L, L + W]; an unused one matches no key (no key has
+        // the hi word 0x80000000: keys are non-negative, the filler is all ones)
+        unsigned int L0 = lo[0], H0 = hi[0], L1 = 0x80000000u, H1 = 0x80000000u, L2 = 0x80000000u, H2 = 0x80000000u;
+        int iv_med, iv_q75;
+        if (lo[1] <= H0) { H0 = hi[1]; iv_med = 0; } else { L1 = lo[1]; H1 = hi[1]; iv_med = 1; }
+        if (iv_med == 0) {
+          if (lo[2] <= H0) { H0 = hi[2]; iv_q75 = 0; } else { L1 = lo[2]; H1 = hi[2]; iv_q75 = 1; }
+        } else {
+          if (lo[2] <= H1) { H1 = hi[2]; iv_q75 = 1; } else { L2 = lo[2]; H2 = hi[2]; iv_q75 = 2; }
+        }
+        L0 = __builtin_amdgcn_readfirstlane(L0);
+        L1 = __builtin_amdgcn_readfirstlane(L1);
+        L2 = __builtin_amdgcn_readfirstlane(L2);
+        const unsigned int W0 = __builtin_amdgcn_readfirstlane(H0 - L0), W1 = __builtin_amdgcn_readfirstlane(H1 - L1),
+                           W2 = __builtin_amdgcn_readfirstlane(H2 - L2);
+        const unsigned int S0 = W0 < 512u ? 0u : 23u - (unsigned int)__clz((int)W0),   // (hi - L) >> S < 512
+                           S1 = W1 < 512u ? 0u : 23u - (unsigned int)__clz((int)W1),
+                           S2 = W2 < 512u ? 0u : 23u - (unsigned int)__clz((int)W2);
+        // interval * 512 + bin of a hi word, BR_NONE outside every interval (the filler and unused intervals included)
+        auto code_of = [&](unsigned int h) -> unsigned int {
+          const unsigned int d0 = h - L0, d1 = h - L1, d2 = h - L2;
+          unsigned int c = BR_NONE;
+          if (d2 <= W2) c = 1024u + (d2 >> S2);
+          if (d1 <= W1) c = 512u + (d1 >> S1);
+          if (d0 <= W0) c = d0 >> S0;
+          return c;
+        };
+        unsigned int b01 = 0u, b2 = 0u;        // keys below interval 0 | below interval 1 << 16, below interval 2
+#pragma unroll
+        for (int u = 0; u < ONE_FK; ++u) {
+          const unsigned int h = khi[u];       // the filler (all ones) is below nothing and inside nothing
+          b01 += (h < L0 ? 1u : 0u) + (h < L1 ? 0x10000u : 0u);
+          b2 += h < L2 ? 1u : 0u;
+          const unsigned int c = code_of(h);
+          if (c != BR_NONE) atomicAdd(&hflat[c], 1u);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {    // <= 2048 per wave and counter: the packed halves do not carry
+          b01 += __shfl_xor(b01, d);
+          b2 += __shfl_xor(b2, d);
+        }
+        if (lane == 0) {
+          atomicAdd(&br_below[0], b01 & 0xffffu);
+          atomicAdd(&br_below[1], b01 >> 16);
+          atomicAdd(&br_below[2], b2);
+        }
+        __syncthreads();
+#ifdef GDN_SELECT_TIMING
+        btick[nbt++] = wall_clock64();
+#endif
+        if (wv < NQ) {                         // wave q: rank q's bin inside its interval
+          const int iv = wv < 2 ? iv_med : (wv < 4 ? 0 : iv_q75);
+          locate_bin512(hflat + 512 * iv, sa.rank[wv] - (int)br_below[iv], 512u * (unsigned int)iv, lane,
+                        &br_code[wv], &rem[wv]);
+        }
+        __syncthreads();
+        unsigned int code[NQ];
+        bool inside = true;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          code[q] = __builtin_amdgcn_readfirstlane(br_code[q]);
+          inside = inside && code[q] != ~0u;   // nothing written: the rank is outside its bracket
+        }
+        if (inside) {
+          unsigned int keep = 0u;
+#pragma unroll
+          for (int u = 0; u < ONE_FK; ++u) {
+            const unsigned int c = code_of(khi[u]);
+            bool any = false;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) any |= c == code[q];
+            keep |= any ? (1u << u) : 0u;
+          }
+          const unsigned int n_cand = stage_slots(keep);
+#ifdef GDN_SELECT_TIMING
+          btick[nbt++] = wall_clock64();
+          br_n = n_cand;
+#endif
+          if (n_cand <= (unsigned int)ONE_CAP2) {
+            if ((unsigned int)tid < n_cand) {
+              const unsigned long long k = key_slot(sidx[tid]);
+              stage2[tid] = k;
+              sidx[tid] = (unsigned short)code_of((unsigned int)(k >> 32));   // the slot number is consumed
+            }
+            __syncthreads();
+            finish_by_counting(stage2, n_cand, [&](unsigned int j) { return (unsigned int)sidx[j]; },
+                               [&](int q) { return code[q]; });
+            bracketed = true;
+          }
+        }
+      }
+      if (!bracketed) __syncthreads();         // the counters read above are reset below
+#ifdef GDN_SELECT_TIMING
+      btick[nbt++] = wall_clock64();
+#endif
+    }
+  }
+  if (!bracketed) {
+    if (tid < NQ) {
+      prefix[tid] = 0ull;
+      rem[tid] = sa.rank[tid];
+    }
+    if (tid == 0) {
+      n_stage = 0u;
+      n_stage2 = 0u;
+    }
+    __syncthreads();
+  }
+#ifdef GDN_SELECT_TIMING
   tick[nt++] = wall_clock64();
 #endif
   bool in_lds = false;       // digits >= 2 read the compacted survivors
-  bool done = false;
+  bool done = bracketed;     // the digit passes run only when the brackets did not settle the ranks
   unsigned int n_keep = 0u;
   for (int pass = 0; pass < 8 && !done; ++pass) {
     const int shift = 56 - 8 * pass;
@@ -580,31 +863,7 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
         for (int q = 0; q < NQ; ++q) any |= h16 == p16[q];
         keep |= any ? (1u << u) : 0u;
       }
-      // one LDS atomic per WAVE: lanes scan their survivor counts, the last lane reserves the range
-      const int mine = __popc(keep);
-      int incl = mine;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-      }
-      unsigned int base = 0u;
-      if (lane == 63) base = atomicAdd(&n_stage, (unsigned int)incl);
-      base = __shfl(base, 63);
-      unsigned int pos = base + (unsigned int)(incl - mine);
-      // survivors first as SLOT NUMBERS, then re-read in full by all threads at once (a load inside the
-      // per-slot branch would pay one L2 round trip per survivor, serially)
-      unsigned int t1 = tid;
-      asm volatile("" : "+v"(t1));     // keeps the 32 slot numbers from being precomputed outside the pass loop
-#pragma unroll
-      for (int u = 0; u < ONE_FK; ++u) {
-        if ((keep >> u) & 1u) {
-          if (pos < (unsigned int)ONE_CAP) sidx[pos] = (unsigned short)(t1 + u * ONE_NT);   // slots <= 32768
-          ++pos;
-        }
-      }
-      __syncthreads();
-      n_keep = n_stage;
+      n_keep = stage_slots(keep);
       in_lds = n_keep <= (unsigned int)ONE_CAP;
       if (in_lds) {
         for (unsigned int i = tid; i < n_keep; i += ONE_NT) stage[i] = key_slot(sidx[i]);
@@ -626,24 +885,9 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
       __syncthreads();
       const unsigned int n2 = n_stage2;
       if (n2 <= (unsigned int)ONE_CAP2) {
-        if ((unsigned int)tid < n2) {
-          const unsigned long long k = stage2[tid];
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) {
-            const unsigned long long pq = prefix[q];
-            if (((k ^ pq) >> 40) != 0ull) continue;
-            int less = 0, equal = 0;
-            for (unsigned int j = 0; j < n2; ++j) {
-              const unsigned long long o = stage2[j];
-              if (((o ^ pq) >> 40) != 0ull) continue;
-              less += o < k ? 1 : 0;
-              equal += o == k ? 1 : 0;
-            }
-            const int want = rem[q];                    // 0-based position inside the bucket
-            if (less <= want && want < less + equal) prefix[q] = k;   // equal keys write the same value
-          }
-        }
-        __syncthreads();
+        // (a finished rank's prefix becomes a key of its own bucket: the 24-bit bucket it names does not change)
+        finish_by_counting(stage2, n2, [&](unsigned int j) { return stage2[j] >> 40; },
+                           [&](int q) { return prefix[q] >> 40; });
         done = true;
       }
     }
@@ -652,11 +896,18 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
 #endif
   }
 #ifdef GDN_SELECT_TIMING
-  if (tid == 0 && s == 1)
+  if (tid == 0 && s == 1 && bracketed)
+    printf("onewg bracket ticks(10ns): sample sort (under the row load) %lld count+histogram %lld locate+stage %lld "
+           "re-read+finish %lld candidates %u\n",
+           btick[0] - tick_start, btick[1] - btick[0], btick[2] - btick[1], btick[3] - btick[2], br_n);
+  else if (tid == 0 && s == 1)
     printf("onewg ticks(10ns): load %lld p0 %lld p1+compact %lld p2+finish %lld (passes run %d) survivors %u / %u\n",
            tick[0] - tick_start, tick[1] - tick[0], tick[2] - tick[1], tick[3] - tick[2], nt - 1, n_keep, n_stage2);
 #endif
-  if (tid == 0) write_result(prefix, sa, s, med_iqr);
+  if (tid == 0) {
+    write_result(prefix, sa, s, med_iqr);
+    if (path) path[s] = bracketed ? 0 : 1;
+  }
 }
 
 // Normalise, smooth, max.  One wave owns a run of consecutive ticks; lane l owns sensors l, l+64, ...
@@ -879,6 +1130,16 @@ __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
 
 namespace {
 
+// diagnostic knob: GDN_SELECT_BRACKET=0 keeps the one-workgroup select on its digit passes (comparisons)
+bool bracket_enabled() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("GDN_SELECT_BRACKET");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v == 1;
+}
+
 SelectArgs make_select_args(long long t) {
   SelectArgs sa;
   // np.median: middle value, or the mean of the two middle values when t is even
@@ -898,6 +1159,8 @@ SelectArgs make_select_args(long long t) {
     sa.rank[3 + 2 * h] = (int)ihi;
     sa.gamma[h] = vi - lo;
   }
+  sa.total = (int)t;
+  sa.bracket = bracket_enabled() ? 1 : 0;
   return sa;
 }
 
@@ -911,8 +1174,15 @@ bool force_multi_block() {
   return v == 1;
 }
 
+__global__ void select_path_fill_kernel(int* __restrict__ path, int n, int value) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) path[i] = value;
+}
+
+// path (optional, [n] int32 on the device): 0 where a sensor's ranks were settled by the sample brackets of
+// select_onewg_kernel, 1 where the digit passes ran (every sensor on the other routes)
 int run_select(const double* keys, int blocks, int n, int pitch, long long total, double* workspace,
-               double* med_iqr, hipStream_t st) {
+               double* med_iqr, int* path, hipStream_t st) {
   const long long slots = (long long)blocks * pitch;
   KeyLayout kl;
   kl.keys = reinterpret_cast<const unsigned long long*>(keys);
@@ -923,10 +1193,11 @@ int run_select(const double* keys, int blocks, int n, int pitch, long long total
   const int slices = (int)((slots + SLICE - 1) / SLICE);
   if (slices > 1 && slots <= (long long)ONE_NT * ONE_FK && !force_multi_block()) {
     // the whole sensor fits one workgroup's registers: one launch, no global state
-    if (kl.blocks == 1) hipLaunchKernelGGL(select_onewg_kernel<true>, dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr);
-    else hipLaunchKernelGGL(select_onewg_kernel<false>, dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr);
+    if (kl.blocks == 1) hipLaunchKernelGGL(select_onewg_kernel<true>, dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr, path);
+    else hipLaunchKernelGGL(select_onewg_kernel<false>, dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr, path);
     return gdn_launch_status();
   }
+  if (path) hipLaunchKernelGGL(select_path_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, path, n, 1);
   hipLaunchKernelGGL(select_init_kernel, dim3(n), dim3(256), 0, st, state, sa);
   if (slices == 1) {   // tiny input: everything in the finisher, straight from the input
     hipLaunchKernelGGL(select_finish_kernel<false>, dim3(n), dim3(FIN_NT), 0, st, kl, state, 0, sa, med_iqr);
@@ -967,7 +1238,16 @@ extern "C" int gdn_score_select(const double* keys, int blocks, int n, int pitch
   if (!keys || !workspace || !med_iqr || blocks <= 0 || n <= 0 || pitch <= 0 || total <= 0) return GDN_ERR_ARG;
   if (total > (long long)blocks * pitch || (long long)blocks * pitch > 0x7fffffffll) return GDN_ERR_ARG;
   if (blocks > 1 && pitch % SLICE != 0) return GDN_ERR_UNSUPPORTED;   // slices must not straddle blocks
-  return run_select(keys, blocks, n, pitch, total, workspace, med_iqr, (hipStream_t)stream);
+  return run_select(keys, blocks, n, pitch, total, workspace, med_iqr, nullptr, (hipStream_t)stream);
+}
+
+// gdn_score_select that also records, per sensor, which path settled its ranks (see run_select)
+extern "C" int gdn_score_select_paths(const double* keys, int blocks, int n, int pitch, long long total,
+                                      double* workspace, double* med_iqr, int* path, void* stream) {
+  if (!keys || !workspace || !med_iqr || !path || blocks <= 0 || n <= 0 || pitch <= 0 || total <= 0) return GDN_ERR_ARG;
+  if (total > (long long)blocks * pitch || (long long)blocks * pitch > 0x7fffffffll) return GDN_ERR_ARG;
+  if (blocks > 1 && pitch % SLICE != 0) return GDN_ERR_UNSUPPORTED;
+  return run_select(keys, blocks, n, pitch, total, workspace, med_iqr, path, (hipStream_t)stream);
 }
 
 extern "C" int gdn_score_quantiles(const float* pred, const float* gt, int t, int n, double* workspace,
@@ -976,7 +1256,7 @@ extern "C" int gdn_score_quantiles(const float* pred, const float* gt, int t, in
   double* keys = workspace;
   const int rc = gdn_score_keys(pred, gt, t, n, t, keys, stream);
   if (rc != GDN_OK) return rc;
-  return run_select(keys, 1, n, t, t, workspace + (size_t)t * n, med_iqr, (hipStream_t)stream);
+  return run_select(keys, 1, n, t, t, workspace + (size_t)t * n, med_iqr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int gdn_score_smooth_max(const float* pred, const float* gt, const double* med_iqr, int t, int n,

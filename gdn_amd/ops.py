@@ -646,6 +646,17 @@ def score_select(keys, blocks: int, n: int, pitch: int, total: int, ws: torch.Te
     return out
 
 
+def score_select_paths(keys, blocks: int, n: int, pitch: int, total: int):
+    """score_select plus, per sensor, the path that settled its ranks: 0 = sample brackets of the one-workgroup
+    select, 1 = digit passes (gdn_score_select_paths).  Returns (med_iqr[n, 2], path[n] int32)."""
+    keys = _chk(keys, torch.float64, "keys")
+    ws = score_select_workspace(blocks, n, pitch, keys.device)
+    out = torch.empty((n, 2), dtype=torch.float64, device=keys.device)
+    path = torch.full((n,), -1, dtype=torch.int32, device=keys.device)
+    _lib.call("gdn_score_select_paths", _ptr(keys), blocks, n, pitch, total, _ptr(ws), _ptr(out), _ptr(path), _stream())
+    return out, path
+
+
 def score_quantiles(pred, gt):
     """Per-sensor median and IQR of |pred-gt| over all ticks (util/data.py:75-82), float64.
     pred, gt: fp32 [t, n].  Returns med_iqr[n, 2]."""

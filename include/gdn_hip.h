@@ -644,6 +644,11 @@ long long gdn_score_select_workspace_bytes(int blocks, int n, int pitch);
 int gdn_score_keys(const float* pred, const float* gt, int t, int n, int pitch, double* keys, void* stream);
 int gdn_score_select(const double* keys, int blocks, int n, int pitch, long long total,
                      double* workspace, double* med_iqr, void* stream);
+/* gdn_score_select plus a diagnostic (additive entry point, the ABI version does not move): path[n] int32 on the
+ * device receives, per sensor, 0 where the one-workgroup select (one block, 2048 < pitch <= 32768) settled the
+ * ranks from its sample brackets and 1 where the digit passes ran (always 1 on the other routes).  Same result. */
+int gdn_score_select_paths(const double* keys, int blocks, int n, int pitch, long long total,
+                           double* workspace, double* med_iqr, int* path, void* stream);
 int gdn_score_quantiles(const float* pred, const float* gt, int t, int n,
                         double* workspace, double* med_iqr, void* stream);
 int gdn_score_smooth_max(const float* pred, const float* gt, const double* med_iqr,
