@@ -541,8 +541,10 @@ __global__ __launch_bounds__(256) void gdn_head_train_kernel(const HeadArgs a) {
       __syncthreads();
       if (last) {
         double sum = 0.0;
-        for (int q = tid; q < (int)gridDim.x; q += 256)
-          sum += __hip_atomic_load(a.mse_ws + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int q = tid; q < (int)gridDim.x; q += 256) {   // the partials go back zeroed, like the ticket: the
+          sum += __hip_atomic_load(a.mse_ws + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // workspace is all 0 between calls
+          __hip_atomic_store(a.mse_ws + 1 + q, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         red[tid] = sum;
         __syncthreads();
         for (int q = 128; q > 0; q >>= 1) {
@@ -881,8 +883,10 @@ __device__ __forceinline__ void head_train_body(const HeadArgs& a, int dd_arg) {
       __syncthreads();
       if (last) {
         double sum = 0.0;
-        for (int q = tid; q < (int)gridDim.x; q += 256)
-          sum += __hip_atomic_load(a.mse_ws + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int q = tid; q < (int)gridDim.x; q += 256) {   // the partials go back zeroed, like the ticket: the
+          sum += __hip_atomic_load(a.mse_ws + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // workspace is all 0 between calls
+          __hip_atomic_store(a.mse_ws + 1 + q, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         red[tid] = sum;
         __syncthreads();
         for (int q = 128; q > 0; q >>= 1) {
@@ -1308,7 +1312,7 @@ extern "C" int gdn_head_train_bwd(const float* d_out, const float* z, const floa
 
 // gdn_head_train_fwd_rng + gdn_mse_loss_grad in the same launches: the last forward pass also writes
 // d_out = 2 (out - y) / (batch n) and loss[0] = mean((out - y)^2).  mse_workspace: gdn_head_mse_workspace_bytes(),
-// zero-filled once (the ticket is handed back at 0).
+// zero-filled once (the ticket and the partials are handed back at 0).
 extern "C" long long gdn_head_mse_workspace_bytes(void) { return (4096 + 1) * (long long)sizeof(double); }
 
 extern "C" int gdn_head_train_fwd_rng_mse(const float* z, const float* emb, const float* bn1_w, const float* bn1_b,

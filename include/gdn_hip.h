@@ -295,7 +295,7 @@ int gdn_head_train_bwd_rng(const float* d_out, const float* z, const float* emb,
 /* gdn_head_train_fwd_rng with the loss folded in (train.py:20-23,70-72: F.mse_loss + the first step of
  * loss.backward()): the last forward pass also writes d_out = 2 (out - y) / (batch n) and loss[0] =
  * mean((out - y)^2) — per-workgroup fp64 partials added in a fixed order by the last workgroup to finish, as
- * gdn_mse_loss_grad does, without its launch.  mse_workspace: gdn_head_mse_workspace_bytes(), zero-filled once.
+ * gdn_mse_loss_grad does, without its launch.  mse_workspace: gdn_head_mse_workspace_bytes(), zero-filled once; every call leaves all of it zero.
  * (Measured on MI355X at 512 windows: 5 us slower than the separate launch — every one of the 512 workgroups
  * pays the block reduction and the ticket; harness.NativeTrainStep uses it only with GDN_FUSE_MSE=1.)        */
 long long gdn_head_mse_workspace_bytes(void);

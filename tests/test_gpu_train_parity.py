@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _head_train_ref import mix32_keep as _mix32_mask   # the in-kernel dropout draw: (seed, step, count, p, device)
 from conftest import MODEL_CASES, load_golden, meta
 from test_gpu_forward_parity import build_model
 
@@ -331,21 +332,6 @@ def test_adam_kernel_matches_torch_adam(gpu_device):
                                    atol=2e-7 * float(m.abs().max()))
         np.testing.assert_allclose(v.cpu().numpy(), opt.state[ref_p]["exp_avg_sq"].cpu().numpy(), rtol=2e-6, atol=1e-30)
         # (1 - beta2 is formed in double like torch's Python-float arithmetic: 1 - 0.999f would be 4.7e-5 off)
-
-
-def _mix32_mask(seed, step, count, p_drop, device):
-    """torch restatement of the in-kernel dropout draw (gdn_head_train.hip: gdn_mix32)."""
-    M = 0xFFFFFFFF
-    k0 = (seed & M) ^ (((step * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF) >> 32)
-    k1 = ((seed >> 32) + ((step * 0x7F4A7C15) & M)) & M
-    x = (torch.arange(count, dtype=torch.int64, device=device) * 0x9E3779B1 + k0) & M
-    x = x ^ (x >> 16)
-    x = (x * 0x85EBCA6B) & M
-    x = x ^ (x >> 13)
-    x = (x + k1) & M
-    x = (x * 0xC2B2AE35) & M
-    x = x ^ (x >> 16)
-    return x >= int(p_drop * 4294967296.0)
 
 
 def test_native_step_state_follows_checkpoint_round_trip(gpu_device):

@@ -20,7 +20,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_train_parity import FixedMaskDropout, _mix32_mask
+from _head_train_ref import mix32_keep as _mix32_mask
+from test_gpu_train_parity import FixedMaskDropout
 
 pytestmark = pytest.mark.gpu
 
