@@ -96,6 +96,11 @@ SIGNATURES = {
     "gdn_score_quantiles": [_p, _p, _c_int, _c_int, _p, _p, _p],
     "gdn_score_smooth_max": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p],
     "gdn_score_smooth_topm": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p],
+    "gdn_series_fill_workspace_bytes": [_c_int, _c_int],
+    "gdn_series_fill": [_p] + [_c_int] * 3 + [_p] * 7,
+    "gdn_score_keys_keep": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p],
+    "gdn_score_smooth_max_gaps": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p, _p],
+    "gdn_score_smooth_topm_gaps": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p, _p],
     "gdn_attention_workspace_bytes": [_c_int] * 4,
     "gdn_attention_mean": [_p, ctypes.c_longlong, ctypes.c_longlong] + [_p] * 4 + [_c_int] * 4 + [_p, _p, _p],
     "gdn_attention_at": [_p, ctypes.c_longlong, _p, _p, _c_int, _p, _p, _p] + [_c_int] * 3 + [_p, _p],

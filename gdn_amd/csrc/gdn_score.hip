@@ -915,12 +915,18 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
 // its float64 division — is computed once.  smoothed = mean of the value at the tick and its 3
 // predecessors (0 for the first 3 ticks of the SERIES), anomaly = max over sensors (wave reduction).
 // Rows before this shard's first tick come from the halo [3][n].
-constexpr int RUN = 8;        // ticks per wave (short runs: thousands of waves keep loads in flight)
+// GAPS (gdn_score_smooth_max_gaps / _topm_gaps; the same switch as gdn_stream_score_kernel's): `valid` [t, n] (1 = a
+// real reading; `halo_valid` [3, n] for the halo rows) travels as one bit per loaded row and the normalised error of a
+// missing reading is 0.0 in its own tick's mean and in the next three.  Without GAPS the two trailing parameters are
+// not read and the kernels are the ones they were (DESIGN §3.5d has the resource table of both instantiations).
+constexpr int RUN = 8;       // ticks per wave (short runs: thousands of waves keep loads in flight)
 
+template <bool GAPS>
 __global__ __launch_bounds__(256) void score_smooth_max_kernel(
     const float* __restrict__ pred, const float* __restrict__ gt, const double* __restrict__ med_iqr,
     int t, int n, int first_tick, const float* __restrict__ halo_pred, const float* __restrict__ halo_gt,
-    double* __restrict__ scores, double* __restrict__ anomaly) {
+    double* __restrict__ scores, double* __restrict__ anomaly, const unsigned char* __restrict__ valid,
+    const unsigned char* __restrict__ halo_valid) {
   __shared__ double best[4][RUN];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
@@ -942,6 +948,7 @@ __global__ __launch_bounds__(256) void score_smooth_max_kernel(
       // chain of dependent round trips and the kernel ran at 2.2 TB/s
       const int g0 = first_tick + t0;
       float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
+      unsigned oka = 0u, okb = 0u;                 // GAPS: bit u = the reading of row u is real
 #pragma unroll
       for (int u = 0; u < RUN + 3; ++u) {
         const int tt = t0 - 3 + u;                 // < 0: halo row 3 + tt (rows before this shard's first tick)
@@ -950,26 +957,33 @@ __global__ __launch_bounds__(256) void score_smooth_max_kernel(
         const float* pp = (halo && first_tick > 0 ? halo_pred : pred) + (size_t)row * n;
         const float* gg = (halo && first_tick > 0 ? halo_gt : gt) + (size_t)row * n;
         pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
+        if constexpr (GAPS) {
+          const unsigned char* vv = (halo && first_tick > 0 ? halo_valid : valid) + (size_t)row * n;
+          oka |= (vv[ca] ? 1u : 0u) << u;
+          okb |= (vv[cb] ? 1u : 0u) << u;
+        }
       }
-      auto norm = [&](float pv, float gv, double med, double inv_den) -> double {
-        return (fabs((double)pv - (double)gv) - med) * inv_den;
+      auto norm = [&](float pv, float gv, double med, double inv_den, unsigned ok, int u) -> double {
+        const double a = (fabs((double)pv - (double)gv) - med) * inv_den;
+        if constexpr (GAPS) return ((ok >> u) & 1u) ? a : 0.0;
+        return a;
       };
       // the 3 predecessors of t0 that exist in the series (a missing one only feeds ticks whose
       // series index is < 3, which are forced to 0)
-      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena) : 0.0;
-      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena) : 0.0;
-      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena) : 0.0;
-      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb) : 0.0;
-      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb) : 0.0;
-      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb) : 0.0;
+      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena, oka, 0) : 0.0;
+      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena, oka, 1) : 0.0;
+      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena, oka, 2) : 0.0;
+      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb, okb, 0) : 0.0;
+      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb, okb, 1) : 0.0;
+      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb, okb, 2) : 0.0;
       double mt[RUN];                             // this lane's max over its sensors, per tick of the run
 #pragma unroll
       for (int u = 0; u < RUN; ++u) {
         const int tick = t0 + u;
         mt[u] = -INFINITY;
         if (tick < t1) {                           // (wave uniform)
-          const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena);
-          const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb);
+          const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena, oka, 3 + u);
+          const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb, okb, 3 + u);
           double sma = 0.0, smb = 0.0;
           if (first_tick + tick >= 3) {               // numpy sums the 4 values left to right
             sma = (((a3 + a2) + a1) + a0) / 4.0;
@@ -1031,10 +1045,12 @@ __global__ __launch_bounds__(256) void score_smooth_max_kernel(
 // candidates, so every round has one owner).  The [n, t] table is never written.
 constexpr int TOPM_MAX = 8;
 
+template <bool GAPS>
 __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
     const float* __restrict__ pred, const float* __restrict__ gt, const double* __restrict__ med_iqr,
     int t, int n, int first_tick, const float* __restrict__ halo_pred, const float* __restrict__ halo_gt,
-    int m, double* __restrict__ top_scores, int* __restrict__ top_sensors) {
+    int m, double* __restrict__ top_scores, int* __restrict__ top_sensors, const unsigned char* __restrict__ valid,
+    const unsigned char* __restrict__ halo_valid) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int nruns = (t + RUN - 1) / RUN;
@@ -1056,6 +1072,7 @@ __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
       const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
       const int g0 = first_tick + t0;
       float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
+      unsigned oka = 0u, okb = 0u;                 // GAPS: bit u = the reading of row u is real
 #pragma unroll
       for (int u = 0; u < RUN + 3; ++u) {
         const int tt = t0 - 3 + u;
@@ -1064,22 +1081,29 @@ __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
         const float* pp = (halo && first_tick > 0 ? halo_pred : pred) + (size_t)row * n;
         const float* gg = (halo && first_tick > 0 ? halo_gt : gt) + (size_t)row * n;
         pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
+        if constexpr (GAPS) {
+          const unsigned char* vv = (halo && first_tick > 0 ? halo_valid : valid) + (size_t)row * n;
+          oka |= (vv[ca] ? 1u : 0u) << u;
+          okb |= (vv[cb] ? 1u : 0u) << u;
+        }
       }
-      auto norm = [&](float pv, float gv, double med, double inv_den) -> double {
-        return (fabs((double)pv - (double)gv) - med) * inv_den;
+      auto norm = [&](float pv, float gv, double med, double inv_den, unsigned ok, int u) -> double {
+        const double a = (fabs((double)pv - (double)gv) - med) * inv_den;
+        if constexpr (GAPS) return ((ok >> u) & 1u) ? a : 0.0;
+        return a;
       };
-      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena) : 0.0;
-      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena) : 0.0;
-      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena) : 0.0;
-      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb) : 0.0;
-      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb) : 0.0;
-      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb) : 0.0;
+      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena, oka, 0) : 0.0;
+      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena, oka, 1) : 0.0;
+      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena, oka, 2) : 0.0;
+      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb, okb, 0) : 0.0;
+      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb, okb, 1) : 0.0;
+      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb, okb, 2) : 0.0;
 #pragma unroll
       for (int u = 0; u < RUN; ++u) {
         const int tick = t0 + u;
         if (tick >= t1) continue;                  // (wave uniform)
-        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena);
-        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb);
+        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena, oka, 3 + u);
+        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb, okb, 3 + u);
         double sma = 0.0, smb = 0.0;
         if (first_tick + tick >= 3) {
           sma = (((a3 + a2) + a1) + a0) / 4.0;
@@ -1259,16 +1283,45 @@ extern "C" int gdn_score_quantiles(const float* pred, const float* gt, int t, in
   return run_select(keys, 1, n, t, t, workspace + (size_t)t * n, med_iqr, nullptr, (hipStream_t)stream);
 }
 
+namespace {
+
+template <bool GAPS>
+int smooth_max(const float* pred, const float* gt, const double* med_iqr, int t, int n, int first_tick,
+               const float* halo_pred, const float* halo_gt, double* scores, double* anomaly, const uint8_t* valid,
+               const uint8_t* halo_valid, void* stream) {
+  if (!pred || !gt || !med_iqr || !anomaly || t <= 0 || n <= 0 || first_tick < 0) return GDN_ERR_ARG;
+  if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
+  if (GAPS && (!valid || (first_tick > 0 && !halo_valid))) return GDN_ERR_ARG;
+  const int runs = (t + RUN - 1) / RUN;
+  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
+  hipLaunchKernelGGL(score_smooth_max_kernel<GAPS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt,
+                     med_iqr, t, n, first_tick, halo_pred, halo_gt, scores, anomaly, valid, halo_valid);
+  return gdn_launch_status();
+}
+
+template <bool GAPS>
+int smooth_topm(const float* pred, const float* gt, const double* med_iqr, int t, int n, int first_tick,
+                const float* halo_pred, const float* halo_gt, int m, double* top_scores, int32_t* top_sensors,
+                const uint8_t* valid, const uint8_t* halo_valid, void* stream) {
+  if (!pred || !gt || !med_iqr || !top_scores || !top_sensors || t <= 0 || n <= 0 || first_tick < 0)
+    return GDN_ERR_ARG;
+  if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
+  if (GAPS && (!valid || (first_tick > 0 && !halo_valid))) return GDN_ERR_ARG;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  const int runs = (t + RUN - 1) / RUN;
+  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
+  hipLaunchKernelGGL(score_smooth_topm_kernel<GAPS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, med_iqr,
+                     t, n, first_tick, halo_pred, halo_gt, m, top_scores, top_sensors, valid, halo_valid);
+  return gdn_launch_status();
+}
+
+}  // namespace
+
 extern "C" int gdn_score_smooth_max(const float* pred, const float* gt, const double* med_iqr, int t, int n,
                                     int first_tick, const float* halo_pred, const float* halo_gt,
                                     double* scores, double* anomaly, void* stream) {
-  if (!pred || !gt || !med_iqr || !anomaly || t <= 0 || n <= 0 || first_tick < 0) return GDN_ERR_ARG;
-  if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
-  const int runs = (t + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(score_smooth_max_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt,
-                     med_iqr, t, n, first_tick, halo_pred, halo_gt, scores, anomaly);
-  return gdn_launch_status();
+  return smooth_max<false>(pred, gt, med_iqr, t, n, first_tick, halo_pred, halo_gt, scores, anomaly, nullptr, nullptr,
+                           stream);
 }
 
 // gdn_score_smooth_max with the m largest scores of every tick and their sensors instead of the maximum alone
@@ -1277,13 +1330,25 @@ extern "C" int gdn_score_smooth_max(const float* pred, const float* gt, const do
 extern "C" int gdn_score_smooth_topm(const float* pred, const float* gt, const double* med_iqr, int t, int n,
                                      int first_tick, const float* halo_pred, const float* halo_gt, int m,
                                      double* top_scores, int32_t* top_sensors, void* stream) {
-  if (!pred || !gt || !med_iqr || !top_scores || !top_sensors || t <= 0 || n <= 0 || first_tick < 0)
-    return GDN_ERR_ARG;
-  if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
-  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  const int runs = (t + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(score_smooth_topm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, med_iqr,
-                     t, n, first_tick, halo_pred, halo_gt, m, top_scores, top_sensors);
-  return gdn_launch_status();
+  return smooth_topm<false>(pred, gt, med_iqr, t, n, first_tick, halo_pred, halo_gt, m, top_scores, top_sensors,
+                            nullptr, nullptr, stream);
+}
+
+// The two sweeps with a validity plane (include/gdn_hip.h "Resident series with missing readings"): the normalised
+// error of a missing (tick, sensor) is exactly 0.0 wherever it is used; with every reading valid they write the bits
+// of the plain entry points.
+extern "C" int gdn_score_smooth_max_gaps(const float* pred, const float* gt, const double* med_iqr, int t, int n,
+                                         int first_tick, const float* halo_pred, const float* halo_gt,
+                                         double* scores, double* anomaly, const uint8_t* valid,
+                                         const uint8_t* halo_valid, void* stream) {
+  return smooth_max<true>(pred, gt, med_iqr, t, n, first_tick, halo_pred, halo_gt, scores, anomaly, valid, halo_valid,
+                          stream);
+}
+
+extern "C" int gdn_score_smooth_topm_gaps(const float* pred, const float* gt, const double* med_iqr, int t, int n,
+                                          int first_tick, const float* halo_pred, const float* halo_gt, int m,
+                                          double* top_scores, int32_t* top_sensors, const uint8_t* valid,
+                                          const uint8_t* halo_valid, void* stream) {
+  return smooth_topm<true>(pred, gt, med_iqr, t, n, first_tick, halo_pred, halo_gt, m, top_scores, top_sensors, valid,
+                           halo_valid, stream);
 }

@@ -490,15 +490,29 @@ class SeriesEvaluator:
     :131-139), with nothing leaving the device.  With `use_graph=True` the launches of a step
     are captured once in a HIP graph and replayed."""
 
-    def __init__(self, model, x_all: torch.Tensor | None, y_all: torch.Tensor, batch: int, use_graph: bool = True,
-                 want_scores: bool = False, streams: int = 3, coalesce: int = 1,
-                 series: torch.Tensor | None = None, top_m: int = 0):
+    def __init__(self, model, x_all: torch.Tensor | None, y_all: torch.Tensor | None, batch: int,
+                 use_graph: bool = True, want_scores: bool = False, streams: int = 3, coalesce: int = 1,
+                 series: torch.Tensor | None = None, top_m: int = 0, gaps: bool = False, min_kept: int = 64):
         """`batch` = the logical minibatch of the reference's loader; `coalesce` consecutive batches
         (contiguous in the resident series) go out as ONE launch — eval results do not depend on the
         minibatch size, and launches of a few thousand windows amortise the per-workgroup prologue.
         `top_m` >= 1 (up to 8): the score launch is gdn_score_smooth_topm — `top_scores` [T, m] float64 and
         `top_sensors` [T, m] int32 hold every tick's m largest sensor scores and their sensors, `anomaly` is column 0
-        of `top_scores` (see `localise`).  0: exactly the launches of a plain step."""
+        of `top_scores` (see `localise`).  0: exactly the launches of a plain step.
+        `gaps=True` (needs `series=` in fp32, x_all = y_all = None) gives the evaluator the streaming
+        detector's notion of a missing reading: a value of the series that is not finite.  The constructor runs
+        gdn_series_fill ONCE: `series` becomes the FILLED series (every missing reading held at its sensor's latest
+        earlier real one; what the forward, `y` and `localise` read), `raw_series` keeps the caller's, `valid` [t, n] /
+        `keep` [t] uint8 say which readings are real and which ticks are complete, `kept` counts the latter (the ONE
+        host read gaps adds) and fewer than `min_kept` of them are refused.  A step is then forward ->
+        gdn_score_keys_keep -> gdn_score_select over the kept ticks -> the `_gaps` smooth launch: the table is
+        calibrated on complete ticks and a missing reading's normalised error is exactly 0.0.  series[:, :w] must be
+        finite.  On a finite series the step writes the bits of gaps=False; gaps=False issues the launches it did."""
+        self.with_gaps = bool(gaps)
+        self.raw_series = self.valid = self.keep = self._gap_counters = None
+        self.kept = None
+        if self.with_gaps:
+            series, y_all = self._fill(model, x_all, y_all, series, int(min_kept))
         # `series` [N, T_raw] (datasets/TimeDataset.py:42 layout) replaces x_all: window t is
         # series[:, t : t+W], built inside the kernel — no [T, N, W] tensor (SURVEY §8f-1)
         assert (x_all is None) != (series is None), "give either the window tensor or the raw series"
@@ -508,6 +522,11 @@ class SeriesEvaluator:
         # range of the resident data, looked at ONCE (include/gdn_hip.h "range guard"): beyond the 16-bit operand
         # range of the matrix-core kernels the whole evaluator runs on the fp32 row-gather kernels
         self.wide = model.wide_for(self.src)
+        # gaps=True at a shape without a series kernel (the fp32 tile form below d = 32 reads windows only): the windows
+        # of the filled series are cut ONCE, here, and the forward reads them — the streaming detector's route
+        self._windows = None
+        if self.with_gaps and not self._has_series_kernel():
+            self._windows = self._cut_windows()
         self.logical_batch, self.coalesce = batch, max(1, coalesce)
         self.t, self.n = y_all.shape
         dev = y_all.device
@@ -533,7 +552,7 @@ class SeriesEvaluator:
         # the gdn_score_keys launch disappears.  Measured SLOWER and therefore off by default: the 127 scattered
         # 8-byte stores per window (row pitch 256 KB) cost the forward ~40 us per 32768 windows, the transposing
         # keys kernel 14 us (step 0.379 vs 0.352 ms).
-        self.fuse_keys = os.environ.get("GDN_FUSE_KEYS", "0") == "1"
+        self.fuse_keys = os.environ.get("GDN_FUSE_KEYS", "0") == "1" and not self.with_gaps   # (the keys need `keep`)
         # independent batches are launched round-robin on side streams (fork/join around the
         # forward), so consecutive launches overlap each other's ramp-up and tail.  Round 1, 4096-window launches:
         # two streams 0.634 ms/step vs 0.697 with one and 0.676 with four.  Round 3, 512-window launches of two
@@ -542,10 +561,70 @@ class SeriesEvaluator:
         n_launch = (self.t + self.batch - 1) // self.batch
         self.side = [torch.cuda.Stream(device=dev) for _ in range(min(streams, n_launch))] if streams > 1 else []
 
+    def _fill(self, model, x_all, y_all, series, min_kept: int):
+        """gaps=True: refuse what has no meaning with missing readings, fill the series once, count the complete
+        ticks.  Returns (the filled series, the derived gt [t, n]); everything here precedes any forward."""
+        if x_all is not None or series is None:
+            raise ValueError("gaps=True: missing readings are held in the resident series; give series= and no window "
+                             "tensor")
+        if y_all is not None:
+            raise ValueError("gaps=True: y_all is derived from the filled series; pass y_all=None")
+        if series.dtype != torch.float32:
+            raise ValueError(f"gaps=True: the series must be fp32, got {series.dtype} (a bf16 series cannot be filled)")
+        if min_kept < 1:
+            raise ValueError(f"min_kept = {min_kept}: the calibration needs at least one complete tick")
+        w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+        self.raw_series = ops._chk(series, name="series")
+        filled, gt, self.valid, self.keep, self._gap_counters = ops.series_fill(self.raw_series, w)
+        head_real, kept = torch.stack([torch.isfinite(self.raw_series[:, :w]).all().long(),
+                                       self.keep.sum()]).tolist()            # ONE host read
+        if not head_real:
+            raise ValueError(f"series: its first {w} ticks hold a value that is not finite; with gaps=True every "
+                             "missing reading is held at an earlier real one, so the series must begin on real readings")
+        self.kept = int(kept)
+        if self.kept < min_kept:
+            raise ValueError(f"min_kept = {min_kept}: only kept = {self.kept} of the {gt.shape[0]} scored ticks have "
+                             "all their readings; too few for a median / IQR table")
+        return filled, gt
+
+    def _has_series_kernel(self) -> bool:
+        """Whether forward_series takes this model's shape: asked with ONE window (every refusal of the library is
+        decided before its launch; an accepted window is the warm-up that builds the plan)."""
+        try:
+            self.model.forward_series(self.series, 0, 1, wide=self.wide)
+        except _lib.GdnHipError:
+            return False
+        return True
+
+    def _cut_windows(self) -> torch.Tensor:
+        """[t, n, w] windows of the filled series, by gdn_windows_gather in launches of up to 4096 windows."""
+        n, t_raw = self.series.shape
+        t = self.y.shape[0]
+        w = t_raw - t
+        if t * n * w * 4 > 8 * _VALIDATE_CHUNK_BYTES:
+            raise ValueError(f"gaps=True: the model has no series kernel at this shape and the window tensor "
+                             f"[{t}, {n}, {w}] fp32 exceeds {8 * _VALIDATE_CHUNK_BYTES >> 20} MB; score a shorter series")
+        dev = self.series.device
+        starts = torch.arange(w, t_raw, dtype=torch.int64, device=dev)
+        x = torch.empty((t, n, w), dtype=torch.float32, device=dev)
+        y = torch.empty((min(t, 4096), n), dtype=torch.float32, device=dev)
+        for s in range(0, t, 4096):
+            ops.windows_gather(self.series, starts, min(4096, t - s), w, x[s:], y, first=s)
+        return x
+
     @property
     def src(self) -> torch.Tensor:
-        """The resident data: the raw series when there is one, else the window tensor."""
+        """The resident data: the raw series when there is one (gaps=True: the filled one), else the window tensor."""
         return self.series if self.series is not None else self.x
+
+    def status_gaps(self):
+        """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: every sensor's missing readings
+        among the scored ticks and the run of them that ends at the last tick (StreamDetector.status_gaps' counters
+        after the same ticks).  ONE read (a synchronisation)."""
+        if not self.with_gaps:
+            raise ValueError("status_gaps(): the evaluator was built with gaps=False and counts no missing readings")
+        both = self._gap_counters.cpu()
+        return both[0], both[1]
 
     def _launch_forward(self, with_keys: bool = False):
         m = self.model
@@ -561,12 +640,14 @@ class SeriesEvaluator:
         # their columns of the [n, t] key block at the head of the scoring workspace (no gdn_score_keys launch)
         def keys(s, e):
             return (self.y[s:e], self.ws.data_ptr() + 8 * s, self.t) if with_keys else None
-        if self.series is not None:
+        if self.series is not None and self._windows is None:
             def launch(s, e):
                 m.forward_series(self.series, s, e - s, out=self.pred[s:e], keys=keys(s, e), wide=self.wide)
         else:
+            x = self.x if self._windows is None else self._windows
+
             def launch(s, e):
-                m.forward_into(self.x[s:e], self.pred[s:e], keys=keys(s, e), wide=self.wide)
+                m.forward_into(x[s:e], self.pred[s:e], keys=keys(s, e), wide=self.wide)
         if len(self.side) < 2:
             for s, e in spans:
                 launch(s, e)
@@ -586,6 +667,8 @@ class SeriesEvaluator:
 
     def _launch_score(self, have_keys: bool = False):
         st = torch.cuda.current_stream().cuda_stream
+        if self.with_gaps:
+            return self._launch_score_gaps(st)
         if have_keys:       # keys [n, t] already sit at the head of the workspace (same layout gdn_score_quantiles uses)
             _lib.call("gdn_score_select", self.ws.data_ptr(), 1, self.n, self.t, self.t,
                       self.ws.data_ptr() + 8 * self.t * self.n, self.med_iqr.data_ptr(), st)
@@ -600,6 +683,22 @@ class SeriesEvaluator:
         _lib.call("gdn_score_smooth_max", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
                   self.t, self.n, 0, None, None,
                   None if self.scores is None else self.scores.data_ptr(), self.anomaly.data_ptr(), st)
+
+    def _launch_score_gaps(self, st):
+        """The scoring launches under gaps=True: the keys of complete ticks (the filler elsewhere) at the head of the
+        workspace, the select over `kept` of them (a host constant of the data: the step stays capturable), and the
+        sweep with the validity plane."""
+        keys, t, n = self.ws.data_ptr(), self.t, self.n
+        _lib.call("gdn_score_keys_keep", self.pred.data_ptr(), self.y.data_ptr(), self.keep.data_ptr(), t, n, t, keys, st)
+        _lib.call("gdn_score_select", keys, 1, n, t, self.kept, keys + 8 * t * n, self.med_iqr.data_ptr(), st)
+        if self.top_m:
+            _lib.call("gdn_score_smooth_topm_gaps", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
+                      t, n, 0, None, None, self.top_m, self.top_scores.data_ptr(), self.top_sensors.data_ptr(),
+                      self.valid.data_ptr(), None, st)
+            return
+        _lib.call("gdn_score_smooth_max_gaps", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
+                  t, n, 0, None, None, None if self.scores is None else self.scores.data_ptr(),
+                  self.anomaly.data_ptr(), self.valid.data_ptr(), None, st)
 
     def _launch_all(self):
         fuse = self.fuse_keys and not self.wide and self.model.fused_keys_supported(self.src.dtype == torch.bfloat16)
@@ -1519,39 +1618,56 @@ class StreamDetector:
         self.graph = None
         self._graph_key = None
         self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
+        self.calib_kept = None              # from_calibration(calib_gaps=True): the complete ticks behind the table
 
     @classmethod
-    def from_calibration(cls, model, series, chunk: int, batch: int = 8192, **kw):
+    def from_calibration(cls, model, series, chunk: int, batch: int = 8192, calib_gaps: bool = False,
+                         min_kept: int = 64, **kw):
         """A detector calibrated on `series` [n, T] fp32 on the device, a period known to be normal: ONE
         SeriesEvaluator step over it gives `med_iqr`; threshold = the largest anomaly score of that period (the rule
         of `-report val`); history = its last w ticks unless `history=` names the ticks the stream really follows.
         `gaps=True` passes through; the calibration itself knows no missing reading, so a series that is not finite
-        is then refused."""
+        is then refused — unless `calib_gaps=True` (needs gaps=True): the period is then scored by
+        SeriesEvaluator(gaps=True, min_kept=...), i.e. under the detector's own rules — missing readings held, the
+        table from the complete ticks, a missing reading's error neutral — the default history is the FILLED period's
+        last w ticks, and the ring is seeded with the period's own keep flags.  `calib_kept` is the number of complete
+        ticks behind the table (None without calib_gaps).  The stream's own counters start at zero."""
         series = ops._chk(series, name="series")
-        if kw.get("gaps") and not bool(torch.isfinite(series).all()):
+        if calib_gaps and not kw.get("gaps"):
+            raise ValueError("calib_gaps=True calibrates under the rules of a gaps=True detector: pass gaps=True too")
+        if kw.get("gaps") and not calib_gaps and not bool(torch.isfinite(series).all()):
             raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
                              "stream, not the calibration (fill or cut the period first)")
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         if series.dim() != 2 or series.shape[1] <= w:
             raise ValueError(f"calibration needs a series [n, T] with T > {w}, got {tuple(series.shape)}")
-        gt = series[:, w:].t().contiguous()
-        ev = SeriesEvaluator(model, None, gt, batch=batch, use_graph=False, series=series)
+        if calib_gaps:
+            ev = SeriesEvaluator(model, None, None, batch=batch, use_graph=False, series=series, gaps=True,
+                                 min_kept=min_kept)
+        else:
+            ev = SeriesEvaluator(model, None, series[:, w:].t().contiguous(), batch=batch, use_graph=False, series=series)
         anomaly = ev.step()
-        kw.setdefault("history", series[:, -w:])
+        kw.setdefault("history", ev.series[:, -w:])
         history = kw.pop("history")
         det = cls(model, ev.med_iqr, anomaly.max(), history, chunk, **kw)
+        det.calib_kept = ev.kept
         if det.recal:
-            det._seed(ev.pred, gt)
+            det._seed(ev.pred, ev.y, ev.keep)
         return det
 
-    def _seed(self, pred, gt):
+    def _seed(self, pred, gt, keep=None):
         """The keys of the last s = min(R, t) rows of a period normal by declaration, oldest first, into slots R - s ..
         R - 1 with keep = 1 (no alarm is excluded): the stream starts at slot 0, so it overwrites the empty slots first
-        and the oldest seeded tick last."""
+        and the oldest seeded tick last.  `keep` [t] uint8 (a calibration with missing readings): a tick that is not
+        complete gets the filler and keep = 0, as gdn_stream_calib_write_gaps would have left it."""
         s = min(self.recal, pred.shape[0])
-        keys = ops.score_keys(pred[-s:], gt[-s:], s)
+        if keep is None:
+            keys = ops.score_keys(pred[-s:], gt[-s:], s)
+            self.ring_keep[self.recal - s:].fill_(1)
+        else:
+            keys = ops.score_keys_keep(pred[-s:], gt[-s:], keep[-s:], s)
+            self.ring_keep[self.recal - s:].copy_(keep[-s:])
         self.ring_keys[:, self.recal - s:].copy_(keys)
-        self.ring_keep[self.recal - s:].fill_(1)
 
     # the launches of a push: static arguments only (they are captured)
     def _guarded(self) -> bool:

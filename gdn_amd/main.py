@@ -198,12 +198,13 @@ class Main:
         if self.env_config.get("stream"):
             self.stream_test_series(best_model, val_ticks, int(self.env_config["stream"]),
                                     gaps=bool(self.env_config.get("stream_gaps")),
+                                    calib_gaps=bool(self.env_config.get("stream_calib_gaps")),
                                     recal=int(self.env_config.get("stream_recal") or 0),
                                     recal_every=int(self.env_config.get("stream_recal_every") or 0))
         return info
 
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
-                           recal_every: int = 0):
+                           recal_every: int = 0, calib_gaps: bool = False):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
@@ -212,13 +213,20 @@ class Main:
         sensors that had any and the missing readings in all join the printed line and `stream_result`.
         -stream_recal R: the detector keeps a calibration ring of the last R ticks (seeded from the validation block)
         and, with -stream_recal_every E, rewrites its median / IQR table from it every E replayed ticks; the number
-        of recalibrations and the ticks kept at the last one join the line and `stream_result`."""
+        of recalibrations and the ticks kept at the last one join the line and `stream_result`.
+        -stream_calib_gaps (with -stream_gaps): the validation block may hold missing readings too; it is scored under
+        the detector's rules (from_calibration(calib_gaps=True)) and the complete ticks the table was computed from
+        join the line and `stream_result` ("calib_kept")."""
         w = self.train_config["slide_win"]
         lo, hi = int(val_ticks.min()), int(val_ticks.max())
         normal = self.train_series[:, lo - w:hi + 1].contiguous()
         if recal_every and not recal:
             raise ValueError("-stream_recal_every needs -stream_recal R (the calibration ring it recalibrates from)")
         rolling = {"recal": recal, "recal_every": recal_every} if recal else {}
+        if calib_gaps:
+            if not gaps:
+                raise ValueError("-stream_calib_gaps needs -stream_gaps (the detector whose rules the calibration follows)")
+            rolling["calib_gaps"] = True
         det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
                                                       top_m=min(3, normal.shape[0]), gaps=gaps, **rolling)
         ticks = self.test_series[:, w:].t().contiguous()
@@ -235,6 +243,9 @@ class Main:
             self.stream_result["missing"] = int(missing_total.sum())
             held = (f"; {self.stream_result['missing']} missing readings held on "
                     f"{self.stream_result['gap_sensors']} sensors")
+        if calib_gaps:
+            self.stream_result["calib_kept"] = det.calib_kept
+            held += f"; calibrated on {det.calib_kept} complete validation ticks"
         if recal:
             self.stream_result["recal"] = recal
             self.stream_result["recalibrations"] = det.recals
@@ -300,7 +311,7 @@ class Main:
 
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
-    -localise / -stream / -stream_gaps / -stream_recal / -stream_recal_every."""
+    -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -327,6 +338,8 @@ def build_parser():
                         "pushes of this many ticks (calibrated on the validation block)", type=int, default=0)
     parser.add_argument("-stream_gaps", help="with -stream: hold missing (non-finite) readings at the sensor's last "
                         "real one and keep them out of the scores", action="store_true")
+    parser.add_argument("-stream_calib_gaps", help="with -stream -stream_gaps: calibrate on a validation block that has "
+                        "missing readings itself, under the detector's rules", action="store_true")
     parser.add_argument("-stream_recal", help="with -stream: keep the scoring keys of the last R ticks in a calibration "
                         "ring on the device (R >= 64 and >= the push size; seeded from the validation block)", type=int,
                         default=0)
@@ -351,7 +364,7 @@ def main(argv=None):
     env_config = {"save_path": args.save_path_pattern, "dataset": args.dataset, "report": args.report,
                   "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
                   "localise": args.localise, "stream": args.stream,
-                  "stream_gaps": args.stream_gaps, "stream_recal": args.stream_recal,
+                  "stream_gaps": args.stream_gaps, "stream_calib_gaps": args.stream_calib_gaps, "stream_recal": args.stream_recal,
                   "stream_recal_every": args.stream_recal_every}
     return Main(train_config, env_config, debug=False).run()
 

@@ -705,6 +705,93 @@ def score_smooth_topm(pred, gt, med_iqr, m: int, first_tick: int = 0, halo_pred=
     return top_scores, top_sensors
 
 
+# --------------------------------------------------------------------------- resident series with missing readings
+def series_fill(raw, w: int):
+    """Hold the missing readings (not finite: NaN, +inf, -inf) of `raw` [n, t_raw] fp32 at each sensor's latest earlier
+    real one (gdn_series_fill; `raw` is not written, raw[:, :w] finite is the caller's duty).  Returns (filled
+    [n, t_raw], gt [t, n] = filled[:, w:] time-major, valid [t, n] uint8, keep [t] uint8 = 1 where a tick is complete,
+    counters [2, n] int64 = missing_total, missing_run over the t = t_raw - w scored ticks)."""
+    raw = _chk(raw, name="series")
+    if raw.dim() != 2:
+        raise ValueError(f"expected the series [n, t_raw], got {tuple(raw.shape)}")
+    n, t_raw = raw.shape
+    nbytes = _lib.load().gdn_series_fill_workspace_bytes(n, t_raw)
+    if nbytes <= 0 or w < 1 or t_raw <= w:
+        raise _lib.GdnHipError(f"series fill: no kernel for n = {n}, t_raw = {t_raw}, w = {w} "
+                               "(1 <= n <= 4096, w >= 1, t_raw > w)")
+    dev, t = raw.device, t_raw - w
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    filled = torch.empty_like(raw)
+    gt = torch.empty((t, n), dtype=torch.float32, device=dev)
+    valid = torch.empty((t, n), dtype=torch.uint8, device=dev)
+    keep = torch.empty((t,), dtype=torch.uint8, device=dev)
+    counters = torch.empty((2, n), dtype=torch.int64, device=dev)
+    _lib.call("gdn_series_fill", _ptr(raw), n, t_raw, w, _ptr(filled), _ptr(gt), _ptr(valid), _ptr(keep),
+              _ptr(counters), _ptr(ws), _stream())
+    return filled, gt, valid, keep, counters
+
+
+def score_keys_keep(pred, gt, keep, pitch: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """score_keys with the filler in all n keys of every tick whose `keep` [t] uint8 flag is 0."""
+    pred, gt, keep = _chk(pred, name="pred"), _chk(gt, name="gt"), _chk(keep, torch.uint8, "keep")
+    t, n = pred.shape
+    if keep.numel() != t:
+        raise ValueError(f"keep: one flag per tick is needed ({t}), got {keep.numel()}")
+    keys = out if out is not None else torch.empty((n, pitch), dtype=torch.float64, device=pred.device)
+    if keys.shape != (n, pitch) or keys.dtype != torch.float64 or not keys.is_contiguous():
+        raise ValueError("keys buffer must be a contiguous float64 [n, pitch] tensor")
+    _lib.call("gdn_score_keys_keep", _ptr(pred), _ptr(gt), _ptr(keep), t, n, pitch, _ptr(keys), _stream())
+    return keys
+
+
+def _valid_plane(valid, shape, name: str):
+    valid = _chk(valid, torch.uint8, name)
+    if tuple(valid.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a uint8 plane of shape {tuple(shape)}, got {tuple(valid.shape)}")
+    return valid
+
+
+def score_smooth_max_gaps(pred, gt, valid, med_iqr, want_scores: bool = True, first_tick: int = 0,
+                          halo_pred=None, halo_gt=None, halo_valid=None, anomaly: torch.Tensor | None = None):
+    """score_smooth_max on the filled `gt` with the validity plane `valid` [t, n] uint8 (`halo_valid` [3, n] beside the
+    halo): the normalised error of a missing reading is exactly 0.0 wherever it is used."""
+    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    t, n = pred.shape
+    valid = _valid_plane(valid, (t, n), "valid")
+    scores = torch.empty((n, t), dtype=torch.float64, device=pred.device) if want_scores else None
+    if anomaly is None:
+        anomaly = torch.empty((t,), dtype=torch.float64, device=pred.device)
+    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
+    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
+    hv = None if halo_valid is None else _valid_plane(halo_valid, (3, n), "halo_valid")
+    _lib.call("gdn_score_smooth_max_gaps", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n,
+              first_tick, _ptr(hp), _ptr(hg), _ptr(scores), _ptr(anomaly), _ptr(valid), _ptr(hv), _stream())
+    return scores, anomaly
+
+
+def score_smooth_topm_gaps(pred, gt, valid, med_iqr, m: int, first_tick: int = 0, halo_pred=None, halo_gt=None,
+                           halo_valid=None, top_scores: torch.Tensor | None = None,
+                           top_sensors: torch.Tensor | None = None):
+    """score_smooth_topm on the filled `gt` with the validity plane (see score_smooth_max_gaps)."""
+    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    t, n = pred.shape
+    valid = _valid_plane(valid, (t, n), "valid")
+    if top_scores is None:
+        top_scores = torch.empty((t, m), dtype=torch.float64, device=pred.device)
+    if top_sensors is None:
+        top_sensors = torch.empty((t, m), dtype=torch.int32, device=pred.device)
+    if (top_scores.shape != (t, m) or top_scores.dtype != torch.float64 or not top_scores.is_contiguous()
+            or top_sensors.shape != (t, m) or top_sensors.dtype != torch.int32 or not top_sensors.is_contiguous()):
+        raise ValueError("top_scores / top_sensors must be contiguous [t, m] float64 / int32 tensors")
+    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
+    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
+    hv = None if halo_valid is None else _valid_plane(halo_valid, (3, n), "halo_valid")
+    _lib.call("gdn_score_smooth_topm_gaps", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n,
+              first_tick, _ptr(hp), _ptr(hg), m, _ptr(top_scores), _ptr(top_sensors), _ptr(valid), _ptr(hv),
+              _stream())
+    return top_scores, top_sensors
+
+
 def _attention_source(src: torch.Tensor, name: str) -> torch.Tensor:
     """The raw data of the attention entry points: fp32 on a HIP device.  They are fp32 throughout, so bf16 storage is
     refused by name (as CPU tensors are) instead of being converted behind the caller's back."""

@@ -665,6 +665,46 @@ int gdn_score_smooth_topm(const float* pred, const float* gt, const double* med_
                           int t, int n, int first_tick, const float* halo_pred,
                           const float* halo_gt, int m, double* top_scores, int32_t* top_sensors, void* stream);
 
+/* Resident series with missing readings (opt-in; additive entry points, the ABI version does not move).  The offline
+ * counterpart of the streaming detector's "Missing readings" below, under the same three rules: a reading of
+ * raw [n, t_raw] is MISSING when its exponent field is all ones (NaN, +inf, -inf); a missing reading is HELD at its
+ * sensor's latest earlier real one; its normalised error is exactly 0.0 wherever it is used.  t = t_raw - w ticks are
+ * scored, tick j = column w + j; a tick is KEPT for the calibration when all n readings of it are real.
+ *   gdn_series_fill      ONCE per series, before any step (two launches, no atomics, no workgroup waits on another):
+ *                          filled [n, t_raw]   raw with every missing reading held; a sensor without any earlier real
+ *                                              reading gets 0 (raw[:, :w] finite is the caller's duty)
+ *                          gt [t, n]           filled[:, w:] time-major: what the forward is scored against
+ *                          valid [t, n] uint8  1 for a real reading
+ *                          keep [t] uint8      1 where all n readings of the tick are real
+ *                          counters [2, n] int64   row 0 missing_total, row 1 missing_run (the run of missing readings
+ *                                              that ends at the last tick), both over the t scored ticks
+ *                        workspace: gdn_series_fill_workspace_bytes(n, t_raw) bytes, 8-byte aligned (0 for an
+ *                        unsupported shape).  filled must not alias raw.  1 <= n <= 4096, w >= 1, t_raw > w: else
+ *                        GDN_ERR_UNSUPPORTED; null pointers: GDN_ERR_ARG.  All decided before any launch.
+ *   gdn_score_keys_keep  gdn_score_keys that writes the filler into all n keys of a tick whose keep flag is 0 (and into
+ *                        slots t .. pitch - 1): gdn_score_select(keys, 1, n, pitch, total = the kept ticks, ...) is then
+ *                        the median / IQR table over complete ticks — every sensor has the same `total`.
+ *   gdn_score_smooth_max_gaps / gdn_score_smooth_topm_gaps
+ *                        gdn_score_smooth_max / _topm with gt = the filled readings and the validity plane valid [t, n]
+ *                        (halo_valid [3, n] beside halo_pred / halo_gt when first_tick > 0): the normalised error of a
+ *                        missing (tick, sensor) is 0.0 in its own 4-tap mean and in those of the next three ticks;
+ *                        operation order, the zero scores of ticks 0-2, the top-m order and the tie rule stay.  With
+ *                        every reading valid they write the bits of the plain entry points.  valid == NULL (halo_valid
+ *                        == NULL with first_tick > 0): GDN_ERR_ARG.                                                    */
+long long gdn_series_fill_workspace_bytes(int n, int t_raw);
+int gdn_series_fill(const float* raw, int n, int t_raw, int w, float* filled, float* gt, uint8_t* valid,
+                    uint8_t* keep, int64_t* counters, void* workspace, void* stream);
+int gdn_score_keys_keep(const float* pred, const float* gt, const uint8_t* keep, int t, int n, int pitch,
+                        double* keys, void* stream);
+int gdn_score_smooth_max_gaps(const float* pred, const float* gt, const double* med_iqr,
+                              int t, int n, int first_tick, const float* halo_pred, const float* halo_gt,
+                              double* scores, double* anomaly, const uint8_t* valid, const uint8_t* halo_valid,
+                              void* stream);
+int gdn_score_smooth_topm_gaps(const float* pred, const float* gt, const double* med_iqr,
+                               int t, int n, int first_tick, const float* halo_pred, const float* halo_gt, int m,
+                               double* top_scores, int32_t* top_sensors, const uint8_t* valid,
+                               const uint8_t* halo_valid, void* stream);
+
 /* ---- attention from raw data -----------------------------------------------------------
  * The attention weights of models/graph_layer.py:91-110 (att_weight_1) without the projection: the logit is
  * separable ("per-forward constants" above), so alpha depends on the raw window, node_terms and the neighbour lists
