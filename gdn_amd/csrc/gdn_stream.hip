@@ -458,6 +458,38 @@ int calib_write(const void* state, const float* pred, const float* chunk, const 
   return gdn_launch_status();
 }
 
+template <bool GAPS>
+int stream_score(const void* state, const float* pred, const float* chunk, const uint8_t* valid, const double* med_iqr,
+                 const double* threshold, int c, int count, int n, int m, double* top_scores, int32_t* top_sensors,
+                 int32_t* alarm, void* stream) {
+  if (!state || !pred || !chunk || (GAPS && !valid) || !med_iqr || !threshold || !top_scores || !top_sensors || !alarm ||
+      count < 1 || count > c) return GDN_ERR_ARG;
+  if (n < 1 || n > 4096) return GDN_ERR_UNSUPPORTED;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  const int runs = (count + RUN - 1) / RUN;
+  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
+  hipLaunchKernelGGL(gdn_stream_score_kernel<GAPS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
+                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm, valid);
+  return gdn_launch_status();
+}
+
+template <bool GAPS>
+int stream_advance(void* state, const float* chunk, const float* pred, const uint8_t* valid, const int32_t* gap_chunk,
+                   const double* med_iqr, const int32_t* alarm, const int32_t* top_sensors, int c, int count, int n,
+                   int w, int m, int64_t* log_ticks, int32_t* log_sensors, long long log_len, int64_t* gaps,
+                   void* stream) {
+  if (!state || !chunk || !pred || !med_iqr || !alarm || !top_sensors || (GAPS && (!valid || !gap_chunk || !gaps)))
+    return GDN_ERR_ARG;
+  if (count < 1 || count > c || log_len < 0 || (log_len > 0 && (!log_ticks || !log_sensors))) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(gdn_stream_advance_kernel<GAPS>, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0,
+                     (hipStream_t)stream, state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
+                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len, valid, gap_chunk,
+                     reinterpret_cast<long long*>(gaps));
+  return gdn_launch_status();
+}
+
 }  // namespace
 
 extern "C" long long gdn_stream_calib_bytes(int n, int R) {
@@ -510,32 +542,15 @@ extern "C" int gdn_stream_windows(const void* state, const float* chunk, int c, 
 extern "C" int gdn_stream_score(const void* state, const float* pred, const float* chunk, const double* med_iqr,
                                 const double* threshold, int c, int count, int n, int m, double* top_scores,
                                 int32_t* top_sensors, int32_t* alarm, void* stream) {
-  if (!state || !pred || !chunk || !med_iqr || !threshold || !top_scores || !top_sensors || !alarm) return GDN_ERR_ARG;
-  if (count < 1 || count > c) return GDN_ERR_ARG;
-  if (n < 1 || n > 4096) return GDN_ERR_UNSUPPORTED;
-  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  const int runs = (count + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(gdn_stream_score_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
-                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm,
-                     static_cast<const unsigned char*>(nullptr));
-  return gdn_launch_status();
+  return stream_score<false>(state, pred, chunk, nullptr, med_iqr, threshold, c, count, n, m, top_scores, top_sensors,
+                             alarm, stream);
 }
 
 extern "C" int gdn_stream_advance(void* state, const float* chunk, const float* pred, const double* med_iqr,
                                   const int32_t* alarm, const int32_t* top_sensors, int c, int count, int n, int w,
                                   int m, int64_t* log_ticks, int32_t* log_sensors, long long log_len, void* stream) {
-  if (!state || !chunk || !pred || !med_iqr || !alarm || !top_sensors) return GDN_ERR_ARG;
-  if (count < 1 || count > c || log_len < 0) return GDN_ERR_ARG;
-  if (log_len > 0 && (!log_ticks || !log_sensors)) return GDN_ERR_ARG;
-  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
-  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(gdn_stream_advance_kernel<false>, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0,
-                     (hipStream_t)stream, state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
-                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len,
-                     static_cast<const unsigned char*>(nullptr), static_cast<const int*>(nullptr),
-                     static_cast<long long*>(nullptr));
-  return gdn_launch_status();
+  return stream_advance<false>(state, chunk, pred, nullptr, nullptr, med_iqr, alarm, top_sensors, c, count, n, w, m,
+                               log_ticks, log_sensors, log_len, nullptr, stream);
 }
 
 extern "C" int gdn_stream_fill(const void* state, const float* raw_chunk, int c, int count, int n, int w,
@@ -551,16 +566,8 @@ extern "C" int gdn_stream_fill(const void* state, const float* raw_chunk, int c,
 extern "C" int gdn_stream_score_gaps(const void* state, const float* pred, const float* chunk, const uint8_t* valid,
                                      const double* med_iqr, const double* threshold, int c, int count, int n, int m,
                                      double* top_scores, int32_t* top_sensors, int32_t* alarm, void* stream) {
-  if (!state || !pred || !chunk || !valid || !med_iqr || !threshold || !top_scores || !top_sensors || !alarm)
-    return GDN_ERR_ARG;
-  if (count < 1 || count > c) return GDN_ERR_ARG;
-  if (n < 1 || n > 4096) return GDN_ERR_UNSUPPORTED;
-  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  const int runs = (count + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(gdn_stream_score_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
-                     med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm, valid);
-  return gdn_launch_status();
+  return stream_score<true>(state, pred, chunk, valid, med_iqr, threshold, c, count, n, m, top_scores, top_sensors,
+                            alarm, stream);
 }
 
 extern "C" int gdn_stream_advance_gaps(void* state, const float* chunk, const float* pred, const uint8_t* valid,
@@ -568,15 +575,6 @@ extern "C" int gdn_stream_advance_gaps(void* state, const float* chunk, const fl
                                        const int32_t* top_sensors, int c, int count, int n, int w, int m,
                                        int64_t* log_ticks, int32_t* log_sensors, long long log_len, int64_t* gaps,
                                        void* stream) {
-  if (!state || !chunk || !pred || !valid || !gap_chunk || !med_iqr || !alarm || !top_sensors || !gaps)
-    return GDN_ERR_ARG;
-  if (count < 1 || count > c || log_len < 0) return GDN_ERR_ARG;
-  if (log_len > 0 && (!log_ticks || !log_sensors)) return GDN_ERR_ARG;
-  if (!stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
-  if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(gdn_stream_advance_kernel<true>, dim3((unsigned)n + 1), dim3(GDN_STREAM_THREADS), 0,
-                     (hipStream_t)stream, state, chunk, pred, med_iqr, alarm, top_sensors, count, n, w, m,
-                     reinterpret_cast<long long*>(log_ticks), log_sensors, log_len, valid, gap_chunk,
-                     reinterpret_cast<long long*>(gaps));
-  return gdn_launch_status();
+  return stream_advance<true>(state, chunk, pred, valid, gap_chunk, med_iqr, alarm, top_sensors, c, count, n, w, m,
+                              log_ticks, log_sensors, log_len, gaps, stream);
 }

@@ -666,39 +666,26 @@ class SeriesEvaluator:
             main.wait_event(join)
 
     def _launch_score(self, have_keys: bool = False):
+        """The table, then the sweep.  Under gaps=True the table is the select over `kept` (a host constant of the data:
+        the step stays capturable) of the keys of complete ticks, the filler elsewhere, and the sweep takes the validity
+        plane."""
         st = torch.cuda.current_stream().cuda_stream
-        if self.with_gaps:
-            return self._launch_score_gaps(st)
+        pred, y, med, keys, t, n = (self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(), self.ws.data_ptr(),
+                                    self.t, self.n)
         if have_keys:       # keys [n, t] already sit at the head of the workspace (same layout gdn_score_quantiles uses)
-            _lib.call("gdn_score_select", self.ws.data_ptr(), 1, self.n, self.t, self.t,
-                      self.ws.data_ptr() + 8 * self.t * self.n, self.med_iqr.data_ptr(), st)
+            _lib.call("gdn_score_select", keys, 1, n, t, t, keys + 8 * t * n, med, st)
+        elif self.with_gaps:
+            _lib.call("gdn_score_keys_keep", pred, y, self.keep.data_ptr(), t, n, t, keys, st)
+            _lib.call("gdn_score_select", keys, 1, n, t, self.kept, keys + 8 * t * n, med, st)
         else:
-            _lib.call("gdn_score_quantiles", self.pred.data_ptr(), self.y.data_ptr(), self.t, self.n,
-                      self.ws.data_ptr(), self.med_iqr.data_ptr(), st)
+            _lib.call("gdn_score_quantiles", pred, y, t, n, keys, med, st)
         if self.top_m:
-            _lib.call("gdn_score_smooth_topm", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
-                      self.t, self.n, 0, None, None, self.top_m, self.top_scores.data_ptr(),
-                      self.top_sensors.data_ptr(), st)
-            return
-        _lib.call("gdn_score_smooth_max", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
-                  self.t, self.n, 0, None, None,
-                  None if self.scores is None else self.scores.data_ptr(), self.anomaly.data_ptr(), st)
-
-    def _launch_score_gaps(self, st):
-        """The scoring launches under gaps=True: the keys of complete ticks (the filler elsewhere) at the head of the
-        workspace, the select over `kept` of them (a host constant of the data: the step stays capturable), and the
-        sweep with the validity plane."""
-        keys, t, n = self.ws.data_ptr(), self.t, self.n
-        _lib.call("gdn_score_keys_keep", self.pred.data_ptr(), self.y.data_ptr(), self.keep.data_ptr(), t, n, t, keys, st)
-        _lib.call("gdn_score_select", keys, 1, n, t, self.kept, keys + 8 * t * n, self.med_iqr.data_ptr(), st)
-        if self.top_m:
-            _lib.call("gdn_score_smooth_topm_gaps", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
-                      t, n, 0, None, None, self.top_m, self.top_scores.data_ptr(), self.top_sensors.data_ptr(),
-                      self.valid.data_ptr(), None, st)
-            return
-        _lib.call("gdn_score_smooth_max_gaps", self.pred.data_ptr(), self.y.data_ptr(), self.med_iqr.data_ptr(),
-                  t, n, 0, None, None, None if self.scores is None else self.scores.data_ptr(),
-                  self.anomaly.data_ptr(), self.valid.data_ptr(), None, st)
+            name, out = "gdn_score_smooth_topm", (self.top_m, self.top_scores.data_ptr(), self.top_sensors.data_ptr())
+        else:
+            name = "gdn_score_smooth_max"
+            out = (None if self.scores is None else self.scores.data_ptr(), self.anomaly.data_ptr())
+        gaps = (self.valid.data_ptr(), None) if self.with_gaps else ()
+        _lib.call(name + "_gaps" if self.with_gaps else name, pred, y, med, t, n, 0, None, None, *out, *gaps, st)
 
     def _launch_all(self):
         fuse = self.fuse_keys and not self.wide and self.model.fused_keys_supported(self.src.dtype == torch.bfloat16)
@@ -762,6 +749,24 @@ class Localisation(NamedTuple):
         return {name: getattr(self, name).cpu().numpy() for name in self._fields}
 
 
+def _row_indices(rows, device, limit: int, error: str) -> torch.Tensor:
+    rows = torch.as_tensor(rows, device=device).to(torch.int64).reshape(-1)
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= limit):
+        raise ValueError(error)
+    return rows
+
+
+def _localisation(model, src, ticks, rows, sensors, top_scores, pred, observed) -> Localisation:
+    """The Localisation of `ticks` [Q] from row `rows` [Q] of the tables pred / observed [T, n] and of the windows in
+    `src`, for the sensors [Q, m] int64 with the scores top_scores [Q, m]: ONE model.attention_at."""
+    m = sensors.shape[1]
+    at = rows.view(-1, 1).expand(-1, m)
+    nb = model.attention_neighbours()
+    att = model.attention_at(src, at.reshape(-1), sensors.reshape(-1))
+    return Localisation(ticks, sensors, top_scores, pred[at, sensors], observed[at, sensors], nb[sensors],
+                        att.reshape(rows.numel(), m, nb.shape[1]))
+
+
 def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localisation:
     """Which sensors deviate at `ticks` (rows of the evaluator's prediction table) and which neighbours they were
     reading: the top-m table of the evaluator's last step (SeriesEvaluator(top_m >= 1), step() first) plus one
@@ -772,17 +777,9 @@ def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localis
     m = ev.top_m if m is None else int(m)
     if not 1 <= m <= ev.top_m:
         raise ValueError(f"m = {m}: the evaluator keeps {ev.top_m} sensors per tick")
-    dev = ev.pred.device
-    ticks = torch.as_tensor(ticks, device=dev).to(torch.int64).reshape(-1)
-    if ticks.numel() and (int(ticks.min()) < 0 or int(ticks.max()) >= ev.t):
-        raise ValueError(f"ticks outside [0, {ev.t})")
-    sensors = ev.top_sensors[ticks, :m].long()
-    rows = ticks.view(-1, 1).expand(-1, m)
-    model = ev.model
-    nb = model.attention_neighbours()
-    att = model.attention_at(ev.src, rows.reshape(-1), sensors.reshape(-1))
-    return Localisation(ticks, sensors, ev.top_scores[ticks, :m], ev.pred[rows, sensors], ev.y[rows, sensors],
-                        nb[sensors], att.reshape(ticks.numel(), m, nb.shape[1]))
+    ticks = _row_indices(ticks, ev.pred.device, ev.t, f"ticks outside [0, {ev.t})")
+    return _localisation(ev.model, ev.src, ticks, ticks, ev.top_sensors[ticks, :m].long(), ev.top_scores[ticks, :m],
+                         ev.pred, ev.y)
 
 
 # --------------------------------------------------------------------------- graphed train step
@@ -1661,11 +1658,10 @@ class StreamDetector:
         and the oldest seeded tick last.  `keep` [t] uint8 (a calibration with missing readings): a tick that is not
         complete gets the filler and keep = 0, as gdn_stream_calib_write_gaps would have left it."""
         s = min(self.recal, pred.shape[0])
+        keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
         if keep is None:
-            keys = ops.score_keys(pred[-s:], gt[-s:], s)
             self.ring_keep[self.recal - s:].fill_(1)
         else:
-            keys = ops.score_keys_keep(pred[-s:], gt[-s:], keep[-s:], s)
             self.ring_keep[self.recal - s:].copy_(keep[-s:])
         self.ring_keys[:, self.recal - s:].copy_(keys)
 
@@ -1683,23 +1679,15 @@ class StreamDetector:
         ops.stream_windows(self.state, self.chunk_buf, self.w, self.x, count=count)
         x = self.x if count == self.chunk else self.x[:count]
         self.model.forward_into(x, self.pred[:count], wide=self.wide, guard=guard)
-        if self.with_gaps:
-            ops.stream_score_gaps(self.state, self.pred, self.chunk_buf, self.valid, self.med_iqr, self.threshold,
-                                  self.top_m, self.top_scores, self.top_sensors, self.alarm, count=count)
-            if self.recal:
-                ops.stream_calib_write_gaps(self.state, self.pred, self.chunk_buf, self.alarm, self.valid,
-                                            self.ring_keys, self.ring_keep, self.exclude_alarms, count=count)
-            ops.stream_advance_gaps(self.state, self.chunk_buf, self.pred, self.valid, self.gap_chunk, self.med_iqr,
-                                    self.alarm, self.top_sensors, self.w, self.top_m, self.gaps, self.log_ticks,
-                                    self.log_sensors, count=count)
-            return
+        # valid, gap_chunk and gaps are None on a plain detector: the wrappers then call the plain symbols
         ops.stream_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.top_m,
-                         self.top_scores, self.top_sensors, self.alarm, count=count)
+                         self.top_scores, self.top_sensors, self.alarm, count=count, valid=self.valid)
         if self.recal:
             ops.stream_calib_write(self.state, self.pred, self.chunk_buf, self.alarm, self.ring_keys, self.ring_keep,
-                                   self.exclude_alarms, count=count)
+                                   self.exclude_alarms, count=count, valid=self.valid)
         ops.stream_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors, self.w,
-                           self.top_m, self.log_ticks, self.log_sensors, count=count)
+                           self.top_m, self.log_ticks, self.log_sensors, count=count, valid=self.valid,
+                           gap_chunk=self.gap_chunk, gaps=self.gaps)
 
     def _fresh(self):
         """A captured graph bakes in the pointers of the model's folded constants: drop it when a parameter changed."""
@@ -1789,16 +1777,10 @@ class StreamDetector:
         rows of the push) and which neighbours they were reading — ONE model.attention_at on the static window
         buffer.  `ticks` are global stream ticks; the other fields mean what they mean for `localise`; under gaps=True
         `observed` is the FILLED reading (the held value where the reading was missing: see `valid`)."""
-        r, m = self._last, self.top_m
+        r = self._last
         if rows is None:
             rows = torch.nonzero(self.alarm[:r]).view(-1)
-        rows = torch.as_tensor(rows, device=self.state.device).to(torch.int64).reshape(-1)
-        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= r):
-            raise ValueError(f"rows outside [0, {r}) of the last push")
-        sensors = self.top_sensors[rows].long()
-        at = rows.view(-1, 1).expand(-1, m)
-        nb = self.model.attention_neighbours()
-        att = self.model.attention_at(self.x, at.reshape(-1), sensors.reshape(-1))
+        rows = _row_indices(rows, self.state.device, r, f"rows outside [0, {r}) of the last push")
         first = self.state[0] - r                       # (advance has run: ticks counts the push already)
-        return Localisation(first + rows, sensors, self.top_scores[rows], self.pred[at, sensors],
-                            self.chunk_buf[at, sensors], nb[sensors], att.reshape(rows.numel(), m, nb.shape[1]))
+        return _localisation(self.model, self.x, first + rows, rows, self.top_sensors[rows].long(), self.top_scores[rows],
+                             self.pred, self.chunk_buf)

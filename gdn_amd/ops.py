@@ -617,14 +617,22 @@ def score_workspace(t: int, n: int, device) -> torch.Tensor:
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
 
 
-def score_keys(pred, gt, pitch: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    """keys[n, pitch] float64 = |pred-gt| transposed (radix keys); slots t..pitch-1 = filler."""
+def score_keys(pred, gt, pitch: int, out: torch.Tensor | None = None, keep=None) -> torch.Tensor:
+    """keys[n, pitch] float64 = |pred-gt| transposed (radix keys); slots t..pitch-1 = filler.  With `keep` [t] uint8
+    (gdn_score_keys_keep) the filler is also in all n keys of every tick whose flag is 0."""
     pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
     t, n = pred.shape
+    if keep is not None:
+        keep = _chk(keep, torch.uint8, "keep")
+        if keep.numel() != t:
+            raise ValueError(f"keep: one flag per tick is needed ({t}), got {keep.numel()}")
     keys = out if out is not None else torch.empty((n, pitch), dtype=torch.float64, device=pred.device)
     if keys.shape != (n, pitch) or keys.dtype != torch.float64 or not keys.is_contiguous():
         raise ValueError("keys buffer must be a contiguous float64 [n, pitch] tensor")
-    _lib.call("gdn_score_keys", _ptr(pred), _ptr(gt), t, n, pitch, _ptr(keys), _stream())
+    if keep is None:
+        _lib.call("gdn_score_keys", _ptr(pred), _ptr(gt), t, n, pitch, _ptr(keys), _stream())
+    else:
+        _lib.call("gdn_score_keys_keep", _ptr(pred), _ptr(gt), _ptr(keep), t, n, pitch, _ptr(keys), _stream())
     return keys
 
 
@@ -668,28 +676,60 @@ def score_quantiles(pred, gt):
     return out
 
 
-def score_smooth_max(pred, gt, med_iqr, want_scores: bool = True, first_tick: int = 0,
-                     halo_pred=None, halo_gt=None, anomaly: torch.Tensor | None = None):
-    """evaluate.py:54-68 + the max over sensors of :131-139.  Returns (scores[n,t] | None, anomaly[t]);
-    `anomaly` may be a preallocated float64 [t] buffer."""
+def _valid_plane(valid, shape, name: str):
+    valid = _chk(valid, torch.uint8, name)
+    if tuple(valid.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a uint8 plane of shape {tuple(shape)}, got {tuple(valid.shape)}")
+    return valid
+
+
+def _smooth_planes(pred, gt, valid, halo_valid):
+    """pred, gt [t, n] fp32 and the optional validity plane `valid` [t, n] uint8 of the smooth launches, checked."""
     pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    if valid is not None:
+        valid = _valid_plane(valid, pred.shape, "valid")
+    elif halo_valid is not None:
+        raise ValueError("halo_valid is the halo of the validity plane: give valid as well")
+    return pred, gt, valid
+
+
+def _smooth_call(name: str, pred, gt, med_iqr, first_tick: int, halo_pred, halo_gt, outputs, valid, halo_valid):
+    """gdn_score_<name>, or gdn_score_<name>_gaps with (valid, halo_valid) behind the outputs when `valid` is given;
+    the halos ([3, n], the three ticks before first_tick) are checked here."""
+    t, n = pred.shape
+    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
+    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
+    hv = None if halo_valid is None else _valid_plane(halo_valid, (3, n), "halo_valid")
+    head = (_ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n, first_tick, _ptr(hp), _ptr(hg), *outputs)
+    if valid is None:
+        _lib.call(f"gdn_score_{name}", *head, _stream())
+    else:
+        _lib.call(f"gdn_score_{name}_gaps", *head, _ptr(valid), _ptr(hv), _stream())
+
+
+def score_smooth_max(pred, gt, med_iqr, want_scores: bool = True, first_tick: int = 0, halo_pred=None, halo_gt=None,
+                     anomaly: torch.Tensor | None = None, valid=None, halo_valid=None):
+    """evaluate.py:54-68 + the max over sensors of :131-139.  Returns (scores[n,t] | None, anomaly[t]);
+    `anomaly` may be a preallocated float64 [t] buffer.  With the validity plane `valid` [t, n] uint8 of a filled `gt`
+    (`halo_valid` [3, n] beside the halo) the normalised error of a missing reading is exactly 0.0 wherever it is used."""
+    pred, gt, valid = _smooth_planes(pred, gt, valid, halo_valid)
     t, n = pred.shape
     scores = torch.empty((n, t), dtype=torch.float64, device=pred.device) if want_scores else None
     if anomaly is None:
         anomaly = torch.empty((t,), dtype=torch.float64, device=pred.device)
-    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
-    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
-    _lib.call("gdn_score_smooth_max", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n,
-              first_tick, _ptr(hp), _ptr(hg), _ptr(scores), _ptr(anomaly), _stream())
+    _smooth_call("smooth_max", pred, gt, med_iqr, first_tick, halo_pred, halo_gt, (_ptr(scores), _ptr(anomaly)),
+                 valid, halo_valid)
     return scores, anomaly
 
 
 def score_smooth_topm(pred, gt, med_iqr, m: int, first_tick: int = 0, halo_pred=None, halo_gt=None,
-                      top_scores: torch.Tensor | None = None, top_sensors: torch.Tensor | None = None):
+                      top_scores: torch.Tensor | None = None, top_sensors: torch.Tensor | None = None,
+                      valid=None, halo_valid=None):
     """score_smooth_max that keeps the `m` largest smoothed scores of every tick and their sensors (1 <= m <= 8,
     m <= n) instead of the maximum alone; the [n, t] table is never written.  Returns (top_scores[t, m] float64
-    descending, top_sensors[t, m] int32; equal scores in ascending sensor order); both may be preallocated."""
-    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    descending, top_sensors[t, m] int32; equal scores in ascending sensor order); both may be preallocated.
+    `valid` / `halo_valid` as in score_smooth_max."""
+    pred, gt, valid = _smooth_planes(pred, gt, valid, halo_valid)
     t, n = pred.shape
     if top_scores is None:
         top_scores = torch.empty((t, m), dtype=torch.float64, device=pred.device)
@@ -698,10 +738,8 @@ def score_smooth_topm(pred, gt, med_iqr, m: int, first_tick: int = 0, halo_pred=
     if (top_scores.shape != (t, m) or top_scores.dtype != torch.float64 or not top_scores.is_contiguous()
             or top_sensors.shape != (t, m) or top_sensors.dtype != torch.int32 or not top_sensors.is_contiguous()):
         raise ValueError("top_scores / top_sensors must be contiguous [t, m] float64 / int32 tensors")
-    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
-    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
-    _lib.call("gdn_score_smooth_topm", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n, first_tick,
-              _ptr(hp), _ptr(hg), m, _ptr(top_scores), _ptr(top_sensors), _stream())
+    _smooth_call("smooth_topm", pred, gt, med_iqr, first_tick, halo_pred, halo_gt,
+                 (m, _ptr(top_scores), _ptr(top_sensors)), valid, halo_valid)
     return top_scores, top_sensors
 
 
@@ -729,67 +767,6 @@ def series_fill(raw, w: int):
     _lib.call("gdn_series_fill", _ptr(raw), n, t_raw, w, _ptr(filled), _ptr(gt), _ptr(valid), _ptr(keep),
               _ptr(counters), _ptr(ws), _stream())
     return filled, gt, valid, keep, counters
-
-
-def score_keys_keep(pred, gt, keep, pitch: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    """score_keys with the filler in all n keys of every tick whose `keep` [t] uint8 flag is 0."""
-    pred, gt, keep = _chk(pred, name="pred"), _chk(gt, name="gt"), _chk(keep, torch.uint8, "keep")
-    t, n = pred.shape
-    if keep.numel() != t:
-        raise ValueError(f"keep: one flag per tick is needed ({t}), got {keep.numel()}")
-    keys = out if out is not None else torch.empty((n, pitch), dtype=torch.float64, device=pred.device)
-    if keys.shape != (n, pitch) or keys.dtype != torch.float64 or not keys.is_contiguous():
-        raise ValueError("keys buffer must be a contiguous float64 [n, pitch] tensor")
-    _lib.call("gdn_score_keys_keep", _ptr(pred), _ptr(gt), _ptr(keep), t, n, pitch, _ptr(keys), _stream())
-    return keys
-
-
-def _valid_plane(valid, shape, name: str):
-    valid = _chk(valid, torch.uint8, name)
-    if tuple(valid.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected a uint8 plane of shape {tuple(shape)}, got {tuple(valid.shape)}")
-    return valid
-
-
-def score_smooth_max_gaps(pred, gt, valid, med_iqr, want_scores: bool = True, first_tick: int = 0,
-                          halo_pred=None, halo_gt=None, halo_valid=None, anomaly: torch.Tensor | None = None):
-    """score_smooth_max on the filled `gt` with the validity plane `valid` [t, n] uint8 (`halo_valid` [3, n] beside the
-    halo): the normalised error of a missing reading is exactly 0.0 wherever it is used."""
-    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
-    t, n = pred.shape
-    valid = _valid_plane(valid, (t, n), "valid")
-    scores = torch.empty((n, t), dtype=torch.float64, device=pred.device) if want_scores else None
-    if anomaly is None:
-        anomaly = torch.empty((t,), dtype=torch.float64, device=pred.device)
-    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
-    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
-    hv = None if halo_valid is None else _valid_plane(halo_valid, (3, n), "halo_valid")
-    _lib.call("gdn_score_smooth_max_gaps", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n,
-              first_tick, _ptr(hp), _ptr(hg), _ptr(scores), _ptr(anomaly), _ptr(valid), _ptr(hv), _stream())
-    return scores, anomaly
-
-
-def score_smooth_topm_gaps(pred, gt, valid, med_iqr, m: int, first_tick: int = 0, halo_pred=None, halo_gt=None,
-                           halo_valid=None, top_scores: torch.Tensor | None = None,
-                           top_sensors: torch.Tensor | None = None):
-    """score_smooth_topm on the filled `gt` with the validity plane (see score_smooth_max_gaps)."""
-    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
-    t, n = pred.shape
-    valid = _valid_plane(valid, (t, n), "valid")
-    if top_scores is None:
-        top_scores = torch.empty((t, m), dtype=torch.float64, device=pred.device)
-    if top_sensors is None:
-        top_sensors = torch.empty((t, m), dtype=torch.int32, device=pred.device)
-    if (top_scores.shape != (t, m) or top_scores.dtype != torch.float64 or not top_scores.is_contiguous()
-            or top_sensors.shape != (t, m) or top_sensors.dtype != torch.int32 or not top_sensors.is_contiguous()):
-        raise ValueError("top_scores / top_sensors must be contiguous [t, m] float64 / int32 tensors")
-    hp = None if halo_pred is None else _chk(halo_pred, name="halo_pred")
-    hg = None if halo_gt is None else _chk(halo_gt, name="halo_gt")
-    hv = None if halo_valid is None else _valid_plane(halo_valid, (3, n), "halo_valid")
-    _lib.call("gdn_score_smooth_topm_gaps", _ptr(pred), _ptr(gt), _ptr(_chk(med_iqr, torch.float64)), t, n,
-              first_tick, _ptr(hp), _ptr(hg), m, _ptr(top_scores), _ptr(top_sensors), _ptr(valid), _ptr(hv),
-              _stream())
-    return top_scores, top_sensors
 
 
 def _attention_source(src: torch.Tensor, name: str) -> torch.Tensor:
@@ -992,30 +969,48 @@ def stream_windows(state, chunk, w: int, x_out, count: int | None = None):
     return x_out
 
 
-def stream_score(state, pred, chunk, med_iqr, threshold, m: int, top_scores, top_sensors, alarm, count: int | None = None):
+def stream_score(state, pred, chunk, med_iqr, threshold, m: int, top_scores, top_sensors, alarm, count: int | None = None,
+                 valid=None):
     """gdn_score_smooth_topm over `count` rows of pred / chunk [c, n] at the stream's position: first tick and the three
-    values before the chunk come from the state.  alarm[b] = top_scores[b, 0] > threshold[0] (a float64 device scalar)."""
+    values before the chunk come from the state.  alarm[b] = top_scores[b, 0] > threshold[0] (a float64 device scalar).
+    With `valid` (stream_fill's plane of the filled `chunk`; gdn_stream_score_gaps) the normalised error of a missing
+    reading is exactly 0.0 wherever it is used."""
     chunk, c, n, count = _stream_dims(state, chunk, count, 1)
     pred = _stream_buf(pred, torch.float32, c * n, "pred")
+    if valid is not None:
+        _stream_buf(valid, torch.uint8, c * n, "valid")
     _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
     _stream_buf(threshold, torch.float64, 1, "threshold")
     _stream_buf(top_scores, torch.float64, c * m, "top_scores")
     _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
     _stream_buf(alarm, torch.int32, c, "alarm")
-    _lib.call("gdn_stream_score", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(med_iqr), _ptr(threshold), c, count, n, m,
-              _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
+    tail = (_ptr(med_iqr), _ptr(threshold), c, count, n, m, _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
+    if valid is None:
+        _lib.call("gdn_stream_score", _ptr(state), _ptr(pred), _ptr(chunk), *tail)
+    else:
+        _lib.call("gdn_stream_score_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(valid), *tail)
     return top_scores, top_sensors, alarm
 
 
 def stream_advance(state, chunk, pred, med_iqr, alarm, top_sensors, w: int, m: int, log_ticks=None, log_sensors=None,
-                   count: int | None = None):
+                   count: int | None = None, valid=None, gap_chunk=None, gaps=None):
     """The one launch that writes the stream state: hist and carry rolled by `count` ticks, the counters on, every
-    alarm appended to log_ticks [L] int64 / log_sensors [L, m] int32 in tick order (both None: no log)."""
+    alarm appended to log_ticks [L] int64 / log_sensors [L, m] int32 in tick order (both None: no log).  With `valid`,
+    `gap_chunk` (stream_fill's, of the filled `chunk`) and `gaps` [2, n] int64 (missing_total, missing_run), all three
+    or none (gdn_stream_advance_gaps): carry entries of missing readings are 0.0 and `gaps` takes the push's gap_chunk."""
+    with_gaps = valid is not None
+    if (gap_chunk is not None) != with_gaps or (gaps is not None) != with_gaps:
+        raise ValueError("give all of valid, gap_chunk and gaps, or none of them")
     chunk, c, n, count = _stream_dims(state, chunk, count, w)
     _stream_buf(pred, torch.float32, c * n, "pred")
+    if with_gaps:
+        _stream_buf(valid, torch.uint8, c * n, "valid")
+        _stream_buf(gap_chunk, torch.int32, 2 * n, "gap_chunk")
     _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
     _stream_buf(alarm, torch.int32, c, "alarm")
     _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
+    if with_gaps:
+        _stream_buf(gaps, torch.int64, 2 * n, "gaps")
     if (log_ticks is None) != (log_sensors is None):
         raise ValueError("give both log_ticks and log_sensors, or neither")
     log_len = 0
@@ -1023,9 +1018,13 @@ def stream_advance(state, chunk, pred, med_iqr, alarm, top_sensors, w: int, m: i
         log_len = log_ticks.numel()
         _stream_buf(log_ticks, torch.int64, log_len, "log_ticks")
         _stream_buf(log_sensors, torch.int32, log_len * m, "log_sensors")
-    _lib.call("gdn_stream_advance", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors),
-              c, count, n, w, m, _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len,
-              _stream())
+    tail = (_ptr(med_iqr), _ptr(alarm), _ptr(top_sensors), c, count, n, w, m, _ptr(log_ticks) if log_len else None,
+            _ptr(log_sensors) if log_len else None, log_len)
+    if with_gaps:
+        _lib.call("gdn_stream_advance_gaps", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(valid), _ptr(gap_chunk), *tail,
+                  _ptr(gaps), _stream())
+    else:
+        _lib.call("gdn_stream_advance", _ptr(state), _ptr(chunk), _ptr(pred), *tail, _stream())
 
 
 def stream_fill(state, raw_chunk, w: int, filled_chunk, valid, gap_chunk, count: int | None = None):
@@ -1044,48 +1043,6 @@ def stream_fill(state, raw_chunk, w: int, filled_chunk, valid, gap_chunk, count:
     return filled_chunk, valid, gap_chunk
 
 
-def stream_score_gaps(state, pred, chunk, valid, med_iqr, threshold, m: int, top_scores, top_sensors, alarm,
-                      count: int | None = None):
-    """stream_score on the filled `chunk` with the validity plane of stream_fill: the normalised error of a missing
-    reading is exactly 0.0 wherever it is used."""
-    chunk, c, n, count = _stream_dims(state, chunk, count, 1)
-    pred = _stream_buf(pred, torch.float32, c * n, "pred")
-    _stream_buf(valid, torch.uint8, c * n, "valid")
-    _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
-    _stream_buf(threshold, torch.float64, 1, "threshold")
-    _stream_buf(top_scores, torch.float64, c * m, "top_scores")
-    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
-    _stream_buf(alarm, torch.int32, c, "alarm")
-    _lib.call("gdn_stream_score_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(valid), _ptr(med_iqr), _ptr(threshold),
-              c, count, n, m, _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
-    return top_scores, top_sensors, alarm
-
-
-def stream_advance_gaps(state, chunk, pred, valid, gap_chunk, med_iqr, alarm, top_sensors, w: int, m: int, gaps,
-                        log_ticks=None, log_sensors=None, count: int | None = None):
-    """stream_advance on the filled `chunk`: carry entries of missing readings are 0.0, and the gap counters `gaps`
-    [2, n] int64 (missing_total, missing_run) take the push's gap_chunk.  The one launch that writes state and gaps."""
-    chunk, c, n, count = _stream_dims(state, chunk, count, w)
-    _stream_buf(pred, torch.float32, c * n, "pred")
-    _stream_buf(valid, torch.uint8, c * n, "valid")
-    _stream_buf(gap_chunk, torch.int32, 2 * n, "gap_chunk")
-    _stream_buf(med_iqr, torch.float64, 2 * n, "med_iqr")
-    _stream_buf(alarm, torch.int32, c, "alarm")
-    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
-    _stream_buf(gaps, torch.int64, 2 * n, "gaps")
-    if (log_ticks is None) != (log_sensors is None):
-        raise ValueError("give both log_ticks and log_sensors, or neither")
-    log_len = 0
-    if log_ticks is not None:
-        log_len = log_ticks.numel()
-        _stream_buf(log_ticks, torch.int64, log_len, "log_ticks")
-        _stream_buf(log_sensors, torch.int32, log_len * m, "log_sensors")
-    _lib.call("gdn_stream_advance_gaps", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(valid), _ptr(gap_chunk),
-              _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors), c, count, n, w, m,
-              _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len, _ptr(gaps),
-              _stream())
-
-
 def stream_calib_ring(n: int, R: int, device):
     """An EMPTY calibration ring (include/gdn_hip.h "Rolling calibration") in one allocation of
     gdn_stream_calib_bytes(n, R): (ring_keys [n, R] float64, every key the filler pattern; ring_keep [R] uint8, zero)."""
@@ -1100,7 +1057,12 @@ def stream_calib_ring(n: int, R: int, device):
     return ring_keys, ring_keep
 
 
-def _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count):
+def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_alarms: bool = True,
+                       count: int | None = None, valid=None):
+    """Row b < count of the push -> slot (state.ticks + b) mod R of the calibration ring: its keys |pred - chunk| and
+    keep = 1, or the filler and keep = 0 when `exclude_alarms` and alarm[b] != 0.  After stream_score, before
+    stream_advance.  Writes the ring only.  With `valid` (stream_fill's plane of the filled `chunk`;
+    gdn_stream_calib_write_gaps) a tick with a missing reading in any sensor is not kept either."""
     chunk, c, n, count = _stream_dims(state, chunk, count, 1)
     _stream_buf(pred, torch.float32, c * n, "pred")
     _stream_buf(alarm, torch.int32, c, "alarm")
@@ -1109,26 +1071,10 @@ def _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count):
     R = ring_keys.shape[1]
     _stream_buf(ring_keys, torch.float64, n * R, "ring_keys")
     _stream_buf(ring_keep, torch.uint8, R, "ring_keep")
-    return chunk, c, n, count, R
-
-
-def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_alarms: bool = True,
-                       count: int | None = None):
-    """Row b < count of the push -> slot (state.ticks + b) mod R of the calibration ring: its keys |pred - chunk| and
-    keep = 1, or the filler and keep = 0 when `exclude_alarms` and alarm[b] != 0.  After stream_score, before
-    stream_advance.  Writes the ring only."""
-    chunk, c, n, count, R = _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count)
-    _lib.call("gdn_stream_calib_write", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), c, count, n, R,
-              int(bool(exclude_alarms)), _ptr(ring_keys), _ptr(ring_keep), _stream())
-    return ring_keys, ring_keep
-
-
-def stream_calib_write_gaps(state, pred, chunk, alarm, valid, ring_keys, ring_keep, exclude_alarms: bool = True,
-                            count: int | None = None):
-    """stream_calib_write on the filled `chunk` with the validity plane of stream_fill: a tick with a missing reading in
-    any sensor is not kept either."""
-    chunk, c, n, count, R = _stream_calib(state, pred, chunk, alarm, ring_keys, ring_keep, count)
-    _stream_buf(valid, torch.uint8, c * n, "valid")
-    _lib.call("gdn_stream_calib_write_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), c, count, n,
-              R, int(bool(exclude_alarms)), _ptr(ring_keys), _ptr(ring_keep), _stream())
+    tail = (c, count, n, R, int(bool(exclude_alarms)), _ptr(ring_keys), _ptr(ring_keep), _stream())
+    if valid is None:
+        _lib.call("gdn_stream_calib_write", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), *tail)
+    else:
+        _stream_buf(valid, torch.uint8, c * n, "valid")
+        _lib.call("gdn_stream_calib_write_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), *tail)
     return ring_keys, ring_keep

@@ -46,8 +46,11 @@ def test_the_symbols_are_declared_bound_and_exported_and_the_abi_stays():
     assert binding.SIGNATURES["gdn_score_smooth_max"] == [p, p, p, i, i, i, p, p, p, p, p]
     assert binding.SIGNATURES["gdn_score_smooth_topm"] == [p, p, p, i, i, i, p, p, i, p, p, p]
     from gdn_amd import ops
-    assert all(callable(getattr(ops, f)) for f in ("series_fill", "score_keys_keep", "score_smooth_max_gaps",
-                                                   "score_smooth_topm_gaps"))
+    assert callable(ops.series_fill)
+    assert "keep" in inspect.signature(ops.score_keys).parameters
+    for f in ("score_smooth_max", "score_smooth_topm"):
+        assert {"valid", "halo_valid"} <= set(inspect.signature(getattr(ops, f)).parameters)
+    assert not any(hasattr(ops, f) for f in ("score_keys_keep", "score_smooth_max_gaps", "score_smooth_topm_gaps"))
 
 
 def test_evaluator_and_from_calibration_accept_the_new_arguments():

@@ -48,7 +48,10 @@ def test_the_three_symbols_are_declared_bound_and_exported_and_the_abi_stays():
     assert binding.SIGNATURES["gdn_stream_advance"] == [p, p, p, p, p, p, i, i, i, i, i, p, p, ll, p]
     import inspect
     from gdn_amd import harness, ops
-    assert all(callable(getattr(ops, f)) for f in ("stream_fill", "stream_score_gaps", "stream_advance_gaps"))
+    assert callable(ops.stream_fill)
+    assert "valid" in inspect.signature(ops.stream_score).parameters
+    assert {"valid", "gap_chunk", "gaps"} <= set(inspect.signature(ops.stream_advance).parameters)
+    assert not hasattr(ops, "stream_score_gaps") and not hasattr(ops, "stream_advance_gaps")
     assert inspect.signature(harness.StreamDetector.__init__).parameters["gaps"].default is False
     assert callable(harness.StreamDetector.status_gaps)
 

@@ -166,7 +166,9 @@ def test_the_three_symbols_are_declared_bound_and_exported_and_the_abi_stays():
     # ... with `valid` after the alarm flags
     assert binding.SIGNATURES["gdn_stream_calib_write_gaps"] == [p, p, p, p, p, i, i, i, i, i, p, p, p]
     from gdn_amd import harness, ops
-    assert all(callable(getattr(ops, f)) for f in ("stream_calib_ring", "stream_calib_write", "stream_calib_write_gaps"))
+    assert callable(ops.stream_calib_ring)
+    assert "valid" in inspect.signature(ops.stream_calib_write).parameters
+    assert not hasattr(ops, "stream_calib_write_gaps")
     prm = inspect.signature(harness.StreamDetector.__init__).parameters
     assert (prm["recal"].default, prm["exclude_alarms"].default, prm["recal_every"].default, prm["recal_min"].default) \
         == (0, True, 0, None)

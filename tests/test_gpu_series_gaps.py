@@ -237,7 +237,7 @@ def test_the_one_workgroup_select_takes_the_filler_of_incomplete_ticks(gpu_devic
     assert ev.kept == int(keep.sum()) and not torch.isnan(anomaly).any()
     rows = torch.from_numpy(np.nonzero(keep)[0]).to(dev)
     assert torch.equal(ev.med_iqr, ops.score_quantiles(ev.pred[rows].contiguous(), ev.y[rows].contiguous()))
-    keys = ops.score_keys_keep(ev.pred, ev.y, ev.keep, t)
+    keys = ops.score_keys(ev.pred, ev.y, t, keep=ev.keep)
     _table, path = ops.score_select_paths(keys, 1, n, t, ev.kept)
     assert torch.equal(_table, ev.med_iqr) and set(path.tolist()) <= {0, 1}      # (the one-workgroup route reports 0 / 1)
     assert bool((keys[:, torch.from_numpy(~keep).to(dev)].view(torch.int64) == -1).all())
@@ -265,7 +265,7 @@ def test_from_calibration_with_gaps_in_the_period(gpu_device):
     assert not det.gaps.any()                                        # the stream's own counters start at zero
     # the ring: the period's t ticks in the last t slots, with their own keep flags; the filler where one is 0
     assert torch.equal(det.ring_keep[R - t:], ev.keep) and not det.ring_keep[:R - t].any()
-    want = ops.score_keys_keep(ev.pred, ev.y, ev.keep, t)
+    want = ops.score_keys(ev.pred, ev.y, t, keep=ev.keep)
     assert torch.equal(_bits(det.ring_keys[:, R - t:]), _bits(want))
     dropped = det.ring_keys[:, R - t:][:, ev.keep == 0].view(torch.int64)
     assert dropped.numel() > 0 and bool((dropped == -1).all())

@@ -105,9 +105,9 @@ def _push_ops(history, raw, pred, med_iqr, chunk, m, thr, dev):
         raw_buf[:r].copy_(raw[t0:t0 + r])
         pbuf[:r].copy_(pred[t0:t0 + r])
         ops.stream_fill(state, raw_buf, w, chunk_buf, valid, gap_chunk, count=r)
-        ops.stream_score_gaps(state, pbuf, chunk_buf, valid, med_iqr, threshold, m, ts, ti, al, count=r)
-        ops.stream_advance_gaps(state, chunk_buf, pbuf, valid, gap_chunk, med_iqr, al, ti, w, m, gaps, log_t, log_s,
-                                count=r)
+        ops.stream_score(state, pbuf, chunk_buf, med_iqr, threshold, m, ts, ti, al, count=r, valid=valid)
+        ops.stream_advance(state, chunk_buf, pbuf, med_iqr, al, ti, w, m, log_t, log_s, count=r, valid=valid,
+                           gap_chunk=gap_chunk, gaps=gaps)
         outs.append((chunk_buf[:r].clone(), valid[:r].clone(), ts[:r].clone(), ti[:r].clone(), al[:r].clone()))
     cat = tuple(torch.cat([o[j] for o in outs]) for j in range(5))
     return cat, state, gaps, log_t, log_s
