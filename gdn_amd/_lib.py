@@ -108,6 +108,10 @@ SIGNATURES = {
                            _p, _p, _p],
     "gdn_epoch_advance": [_p, _p, _p, ctypes.c_longlong, _p],
     "gdn_mse_batch_means": [_p, _p, ctypes.c_longlong, _c_int, ctypes.c_longlong, _p, _p, _p, _p],
+    "gdn_windows_gather_gaps": [_p, _c_int, ctypes.c_longlong, _p, ctypes.c_longlong, _p, ctypes.c_longlong, _c_int,
+                                _c_int, _p, _p, _p, _p, _p, _p],
+    "gdn_mse_batch_means_masked": [_p, _p, _p, ctypes.c_longlong, _c_int, ctypes.c_longlong, _p, _p, _p, _p, _p],
+    "gdn_mse_loss_grad_masked": [_p, _p, _p, _p, _c_int, _c_int, _p, _p, _p, _p, _p],
     "gdn_stream_state_bytes": [_c_int, _c_int],
     "gdn_stream_init": [_p, _p, ctypes.c_longlong, _c_int, _c_int, _p],
     "gdn_stream_windows": [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p],

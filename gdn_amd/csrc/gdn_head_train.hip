@@ -1106,6 +1106,68 @@ __global__ __launch_bounds__(256) void gdn_mse_kernel(const float* __restrict__ 
   }
 }
 
+// gdn_mse_kernel over the real targets only: valid[batch, n] says which targets were observed,
+// row_valid[batch] how many per window.  Every workgroup first adds the per-window counts itself (a few KB; integer, so
+// the same m everywhere: no atomic, no launch and no counter to reset), then runs gdn_mse_kernel's loop — same grid,
+// same per-thread chains, same fixed-order finish, same (float)(2.0 / (double)m) — with a SELECT on the validity byte:
+// a masked slot adds nothing and its d_out is exactly 0.0 whatever out / y hold there.  m == count: gdn_mse_kernel's bits.
+__global__ __launch_bounds__(256) void gdn_mse_masked_kernel(const float* __restrict__ out, const float* __restrict__ y,
+                                                             const unsigned char* __restrict__ valid,
+                                                             const int* __restrict__ row_valid, int batch,
+                                                             long long count, float* __restrict__ d_out,
+                                                             double* __restrict__ ws, float* __restrict__ loss,
+                                                             long long* __restrict__ m_out) {
+  __shared__ double red[256];
+  __shared__ long long cnt[256];
+  __shared__ bool last;
+  const int tid = threadIdx.x;
+  long long c = 0;
+  for (int b = tid; b < batch; b += 256) c += row_valid[b];
+  cnt[tid] = c;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) cnt[tid] += cnt[tid + s];
+    __syncthreads();
+  }
+  const long long m = cnt[0];
+  const float scale = (float)(2.0 / (double)m);       // (m == 0: every slot is masked and scale is never used)
+  double acc = 0.0;
+  for (long long i = (long long)blockIdx.x * 256 + tid; i < count; i += (long long)gridDim.x * 256) {
+    const bool v = valid[i] != 0;
+    const float df = out[i] - y[i];
+    acc = v ? fma((double)df, (double)df, acc) : acc;
+    d_out[i] = v ? df * scale : 0.f;
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ws);
+  if (tid == 0) {
+    __hip_atomic_store(ws + 1 + blockIdx.x, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long t = __hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    last = t == (unsigned long long)gridDim.x - 1ull;
+  }
+  __syncthreads();
+  if (!last) return;
+  double s = 0.0;
+  for (int b = tid; b < (int)gridDim.x; b += 256)
+    s += __hip_atomic_load(ws + 1 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  red[tid] = s;
+  __syncthreads();
+  for (int q = 128; q > 0; q >>= 1) {
+    if (tid < q) red[tid] += red[tid + q];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    loss[0] = m > 0 ? (float)(red[0] / (double)m) : 0.f;
+    if (m_out) m_out[0] = m;
+    __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // gdn_exact_sum: the accumulator above on its own (tests pin it against an exactly rounded CPU sum)
 __global__ void gdn_exact_sum_kernel(const double* __restrict__ x, int count, unsigned long long* __restrict__ ws) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1145,6 +1207,18 @@ extern "C" int gdn_mse_loss_grad(const float* out, const float* y, long long cou
   if (grid > GDN_MSE_MAX_GRID) grid = GDN_MSE_MAX_GRID;
   hipLaunchKernelGGL(gdn_mse_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, out, y, count, d_out,
                      workspace, loss);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_mse_loss_grad_masked(const float* out, const float* y, const uint8_t* valid, const int* row_valid,
+                                        int batch, int n, double* workspace, float* loss, float* d_out, int64_t* m_out,
+                                        void* stream) {
+  if (!out || !y || !valid || !row_valid || !workspace || !loss || !d_out || batch < 1 || n < 1) return GDN_ERR_ARG;
+  const long long count = (long long)batch * n;
+  long long grid = (count + 1023) / 1024;
+  if (grid > GDN_MSE_MAX_GRID) grid = GDN_MSE_MAX_GRID;
+  hipLaunchKernelGGL(gdn_mse_masked_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, out, y, valid, row_valid,
+                     batch, count, d_out, workspace, loss, reinterpret_cast<long long*>(m_out));
   return gdn_launch_status();
 }
 

@@ -814,6 +814,20 @@ class _CapturedStep:
         # two graphs around the (eager) gradient all-reduce; forced on by `split=True` for rehearsal
         self._split = world()[1] > 1 if split is None else bool(split)
 
+    def _own_validity(self, gaps: bool, batch: int, n: int, dev):
+        """`gaps=True`: the step owns static `valid` [batch, n] uint8 and `row_valid` [batch] int32 beside
+        `x` / `y` — which targets were observed and how many per window, all of them until a gather says otherwise —
+        and its loss is the masked launch.  One rank only: per-rank masked means are not the global masked mean."""
+        self.gaps = bool(gaps)
+        self.valid = self.row_valid = None
+        if not self.gaps:
+            return
+        if world()[1] > 1:
+            raise _lib.GdnHipError("gaps=True runs in one process: every rank would divide by its own number of observed "
+                                   "targets, and the average of per-rank masked means is not the global masked mean")
+        self.valid = torch.ones((batch, n), dtype=torch.uint8, device=dev)
+        self.row_valid = torch.full((batch,), n, dtype=torch.int32, device=dev)
+
     def _first(self):
         if self.pre is not None:
             self.pre()
@@ -886,7 +900,7 @@ class AutogradTrainStep(_CapturedStep):
     WARMUP = 3
 
     def __init__(self, model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
-                 split: bool | None = None, wide: bool = False, pre=None, post=None):
+                 split: bool | None = None, wide: bool = False, pre=None, post=None, gaps: bool = False):
         super().__init__(use_graph, split, pre, post)
         self.wide = bool(wide)
         p0 = next(model.parameters())
@@ -904,7 +918,8 @@ class AutogradTrainStep(_CapturedStep):
         self.optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=True,
                                           fused=True)
         self._flat = None                                # static gradient bucket (split mode)
-        self._torch_mse = bool(os.environ.get("GDN_TORCH_MSE"))
+        self._own_validity(gaps, batch, n, dev)
+        self._torch_mse = bool(os.environ.get("GDN_TORCH_MSE")) and not self.gaps     # (torch's loss knows no mask)
         self._dbg = None                                 # diagnostic snapshot buffers (tools/probe_mse_replay.py)
 
     # `loss` is written in place so it survives replays
@@ -921,7 +936,8 @@ class AutogradTrainStep(_CapturedStep):
                 self._dbg["loss_raw"].copy_(loss.detach())
         else:
             # loss + its gradient in one launch (train.py:20-23, :72); autograd starts from d_out
-            ops.mse_loss_grad(out.detach(), self.y, self._mse_ws, loss=self.loss, d_out=self._d_out)
+            ops.mse_loss_grad(out.detach(), self.y, self._mse_ws, loss=self.loss, d_out=self._d_out, valid=self.valid,
+                              row_valid=self.row_valid)
             out.backward(self._d_out)
         if self._dbg is not None:
             for name, prm in self.model.named_parameters():
@@ -1045,7 +1061,8 @@ class NativeTrainStep(_CapturedStep):
         return model.out_layer_num == 1 or ops.mlp_train_supported(model.out_layer, model.embedding.weight.shape[1], 2)
 
     def __init__(self, model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
-                 split: bool | None = None, seed: int | None = None, wide: bool = False, pre=None, post=None):
+                 split: bool | None = None, seed: int | None = None, wide: bool = False, pre=None, post=None,
+                 gaps: bool = False):
         super().__init__(use_graph, split, pre, post)
         self._lib = _lib
         # inputs beyond the 16-bit operand range of the matrix-core kernels: the `_wide` (fp32 row-gather) entry
@@ -1123,12 +1140,15 @@ class NativeTrainStep(_CapturedStep):
         # GDN_FUSE_MSE=1: loss + d_out from the head's last forward pass (gdn_head_train_fwd_rng_mse) instead of
         # the gdn_mse_loss_grad launch — measured SLOWER (0.198 vs 0.193 ms: 512 workgroups each pay the block
         # reductions and the ticket), so off by default
-        self._fuse_mse = os.environ.get("GDN_FUSE_MSE", "0") == "1"
+        self._own_validity(gaps, batch, n, dev)
+        self._fuse_mse = os.environ.get("GDN_FUSE_MSE", "0") == "1" and not self.gaps    # (the head's loss knows no mask)
 
         # the address tables of the launches: workspace and static buffers by name, parameter (P) and gradient (G)
         # slots by parameter name, and the groups the launches take together
         self._pt = {key: t.data_ptr() for key, t in self.ws.items()}
         self._pt.update(x=self.x.data_ptr(), y=self.y.data_ptr(), loss=self.loss.data_ptr(), rng=self.state.data_ptr())
+        if self.gaps:
+            self._pt.update(valid=self.valid.data_ptr(), row_valid=self.row_valid.data_ptr())
         name_of = {id(p): name for name, p in model.named_parameters()}
         names = [name_of[id(p)] for p in self.params]
         P = self._P = {name: self.flat_p.data_ptr() + 4 * off for name, (off, _c) in zip(names, self.slices)}
@@ -1228,6 +1248,10 @@ class NativeTrainStep(_CapturedStep):
 
     def _loss(self, st):
         pt = self._pt
+        if self.gaps:
+            self._lib.call("gdn_mse_loss_grad_masked", pt["out"], pt["y"], pt["valid"], pt["row_valid"], self.batch,
+                           self.n, pt["mse_ws"], pt["loss"], pt["d_out"], None, st)
+            return
         self._lib.call("gdn_mse_loss_grad", pt["out"], pt["y"], self.batch * self.n, pt["mse_ws"], pt["loss"],
                        pt["d_out"], st)
 
@@ -1295,18 +1319,22 @@ class NativeTrainStep(_CapturedStep):
 
 def GraphedTrainStep(model, batch: int, lr: float = 1e-3, weight_decay: float = 0.0, use_graph: bool = True,
                      split: bool | None = None, native: bool | None = None, wide: bool | None = None, pre=None,
-                     post=None):
+                     post=None, gaps: bool = False):
     """The captured training step: `NativeTrainStep` when the model and its shape allow it (plain nn.Dropout, an
     OutLayer and a sensor count the training kernels take), else `AutogradTrainStep`.  `native=False` forces the
     autograd form.  `wide`: the inputs exceed the 16-bit operand range (None: model.operand_range == "wide").
-    `pre` / `post`: launches issued (and captured) right before and right after the step, see _CapturedStep."""
+    `pre` / `post`: launches issued (and captured) right before and right after the step, see _CapturedStep.
+    `gaps=True`: the step also owns `valid` [batch, n] uint8 / `row_valid` [batch] int32 and its loss is
+    the mean over the observed targets (gdn_mse_loss_grad_masked; GDN_FUSE_MSE / GDN_TORCH_MSE are ignored); one rank
+    only.  False: exactly the launches of a plain step."""
     if native is None:
         native = NativeTrainStep.applicable(model)
     if wide is None:
         wide = getattr(model, "operand_range", "auto") == "wide"
     cls = NativeTrainStep if native else AutogradTrainStep
+    extra = {"gaps": True} if gaps else {}
     return cls(model, batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph, split=split, wide=wide, pre=pre,
-               post=post)
+               post=post, **extra)
 
 
 # --------------------------------------------------------------------------- epochs from the resident series
@@ -1339,7 +1367,36 @@ _VALIDATE_CHUNK_BYTES = 256 << 20       # window buffer of validate_series: a fe
 _validate_x: dict = {}                  # (device, floats) -> gathered-window buffer, reused across calls
 
 
-def validate_series(model, series, starts, batch: int, wide=None):
+class SeriesFill(NamedTuple):
+    """A series with missing readings, held once (`fill_series`): what training and validation share."""
+    series: torch.Tensor        # [n, T] fp32, every missing reading at its sensor's latest earlier real one
+    raw: torch.Tensor           # [n, T] fp32, the caller's
+    valid: torch.Tensor         # [T - w, n] uint8, time-major: row t - w says which readings of tick t are real
+    counters: torch.Tensor      # [2, n] int64: missing_total, missing_run over ticks w .. T - 1
+
+
+def fill_series(raw, w: int) -> SeriesFill:
+    """gdn_series_fill ONCE for a training series, after ONE host read: raw[:, :w] must be finite, since
+    a missing reading is held at an earlier real one."""
+    if raw.dim() != 2 or raw.dtype != torch.float32:
+        raise ValueError(f"gaps=True: expected the series [n, T] in fp32, got {tuple(raw.shape)} {raw.dtype}")
+    if not bool(torch.isfinite(raw[:, :w]).all()):
+        raise ValueError(f"series: its first {w} ticks hold a value that is not finite; with gaps=True every missing "
+                         "reading is held at an earlier real one, so the series must begin on real readings")
+    raw = ops._chk(raw, name="series")
+    filled, _gt, valid, _keep, counters = ops.series_fill(raw, w)
+    return SeriesFill(filled, raw, valid, counters)
+
+
+def masked_share(valid, starts, w: int) -> float:
+    """The share of the targets of the windows `starts` (target ticks) that are missing: ONE host read."""
+    starts = torch.as_tensor(starts).to(torch.int64).reshape(-1).to(valid.device)
+    if starts.numel() == 0:
+        return 0.0
+    return 1.0 - float(valid[starts - w].float().mean())
+
+
+def validate_series(model, series, starts, batch: int, wide=None, valid=None):
     """harness.test's loss and outputs for the windows of target ticks `starts` of a series [n, T] resident on the
     device, with nothing but launches per chunk: (val_loss, pred [Tv, n], gt [Tv, n]).
 
@@ -1347,7 +1404,12 @@ def validate_series(model, series, starts, batch: int, wide=None):
     ONE gdn_windows_gather into a cached buffer, its targets straight into their rows of `gt`, and goes through
     `model.forward_into` into its rows of `pred`; ONE gdn_mse_batch_means then forms F.mse_loss of every logical
     minibatch and test.py's sum(losses) / len(losses), and one float64 comes back to the host.  An OutLayer the fast
-    path refuses (GDN.mlp_fast_path_supported) goes through `model(x)` on the gathered chunk."""
+    path refuses (GDN.mlp_fast_path_supported) goes through `model(x)` on the gathered chunk.
+
+    `valid`: the validity plane [T - w, n] uint8 of `series`, which is then the FILLED series
+    (`fill_series`).  Each chunk's gather also cuts its validity rows and gdn_mse_batch_means_masked closes the pass:
+    a minibatch's loss is the mean over its observed targets, a minibatch without one is left out of the average, and
+    the result is 0.0 when none has one.  `pred` / `gt` are what the call without `valid` returns."""
     model.eval()
     series = ops._chk(series, name="series")
     n, series_len = series.shape
@@ -1369,16 +1431,26 @@ def validate_series(model, series, starts, batch: int, wide=None):
     xbuf = _validate_x.get(key)
     if xbuf is None:
         xbuf = _validate_x[key] = torch.empty((chunk * n * w,), dtype=torch.float32, device=dev)
+    if valid is not None:
+        vrows = torch.empty((tv, n), dtype=torch.uint8, device=dev)
+        row_valid = torch.empty((chunk,), dtype=torch.int32, device=dev)
     for s in range(0, tv, chunk):
         rows = min(chunk, tv - s)
         x = xbuf[: rows * n * w].view(rows, n, w)
-        ops.windows_gather(series, starts, rows, w, x, gt[s:s + rows], first=s)
+        if valid is None:
+            ops.windows_gather(series, starts, rows, w, x, gt[s:s + rows], first=s)
+        else:
+            ops.windows_gather(series, starts, rows, w, x, gt[s:s + rows], first=s, valid=valid,
+                               valid_out=vrows[s:s + rows], row_valid=row_valid)
         if fast:
             model.forward_into(x, pred[s:s + rows], wide=wide)
         else:
             with pinned_range(model, wide), torch.no_grad():
                 pred[s:s + rows].copy_(model(x, None))
-    _means, mean = ops.mse_batch_means(pred, gt, batch)
+    if valid is not None:
+        mean = ops.mse_batch_means(pred, gt, batch, valid=vrows)[1]
+    else:
+        _means, mean = ops.mse_batch_means(pred, gt, batch)
     return float(mean.item()), pred, gt
 
 
@@ -1389,10 +1461,25 @@ class SeriesTrainer:
     step's windows from the resident series straight into the step's static `x` / `y` — and whose `post` hook is
     gdn_epoch_advance (the step's loss into its row of the loss table, the cursor on); the device copy of the epoch's
     table of target ticks (capacity fixed here, so the pointers a captured graph holds stay valid); the cursor; the
-    loss table.  `train_starts`: the target tick of every training window (SeriesWindows.starts[train indices])."""
+    loss table.  `train_starts`: the target tick of every training window (SeriesWindows.starts[train indices]).
+
+    `gaps=True`: `series` is the RAW series and may hold missing readings (values that are not finite)
+    after its first `w` ticks.  The constructor holds them once (`fill_series`; `fill=` hands over a fill already
+    done): `.series` is the filled series every window and target is cut from, `.raw_series` the caller's, `.valid`
+    the validity plane, `.status_gaps()` the counters.  The gather hook also cuts the validity bytes of the step's
+    targets into the step's `valid` / `row_valid`, and the step's loss is the mean over the observed targets.  On a
+    finite series an epoch writes the bits of gaps=False; gaps=False issues the launches it did."""
 
     def __init__(self, model, series, w: int, train_starts, batch: int, lr: float = 1e-3, weight_decay: float = 0.0,
-                 wide: bool = False, use_graph: bool = True, native: bool | None = None):
+                 wide: bool = False, use_graph: bool = True, native: bool | None = None, gaps: bool = False,
+                 fill: SeriesFill | None = None):
+        self.gaps = bool(gaps)
+        self.raw_series = self.valid = self._gap_counters = None
+        if self.gaps:
+            fill = fill_series(series, int(w)) if fill is None else fill
+            series, self.raw_series, self.valid, self._gap_counters = fill
+        elif fill is not None:
+            raise ValueError("fill= is the held series of gaps=True")
         self.series = ops._chk(series, name="series")
         dev = self.series.device
         self.model, self.w, self.batch, self.wide = model, int(w), int(batch), bool(wide)
@@ -1404,17 +1491,41 @@ class SeriesTrainer:
         self.loss_table = torch.zeros((self.full_steps + 1,), dtype=torch.float32, device=dev)
         self._tail = None                                # (x, y) of the ragged last batch, by its size
         self.step = GraphedTrainStep(model, self.batch, lr=lr, weight_decay=weight_decay, use_graph=use_graph,
-                                     native=native, wide=self.wide, pre=self._gather, post=self._advance)
+                                     native=native, wide=self.wide, pre=self._gather, post=self._advance, gaps=self.gaps)
         self.optimizer = self.step.optimizer
+        self._mse_ws = ops.mse_workspace(dev) if self.gaps else None     # the ragged tail's masked launch
 
     # the hooks: static arguments only (they are captured with the step)
     def _gather(self):
         # (count = the table's capacity: a captured launch cannot learn an epoch's length, and epoch() replays exactly
         # len(order) // batch times, so no replay reaches an entry beyond the epoch)
+        if self.gaps:
+            ops.windows_gather(self.series, self.table, self.batch, self.w, self.step.x, self.step.y, cursor=self.cursor,
+                               valid=self.valid, valid_out=self.step.valid, row_valid=self.step.row_valid)
+            return
         ops.windows_gather(self.series, self.table, self.batch, self.w, self.step.x, self.step.y, cursor=self.cursor)
 
     def _advance(self):
         ops.epoch_advance(self.step.loss, self.cursor, self.loss_table)
+
+    def status_gaps(self):
+        """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: every sensor's missing readings
+        among ticks w .. T - 1 of the series and the run of them that ends at the last tick.  ONE read."""
+        if not self.gaps:
+            raise ValueError("status_gaps(): the trainer was built with gaps=False and counts no missing readings")
+        both = self._gap_counters.cpu()
+        return both[0], both[1]
+
+    def _masked_tail_step(self, x, y, valid, row_valid):
+        """The ragged last batch under gaps=True: `_eager_step` with the masked launch in F.mse_loss's place — autograd
+        starts from d_out — and the same sync_gradients / optimizer calls.  Returns the loss (a device scalar)."""
+        self.optimizer.zero_grad()
+        out = self.model(x, None)
+        loss, d_out = ops.mse_loss_grad(out.detach(), y, self._mse_ws, valid=valid, row_valid=row_valid)
+        out.backward(d_out)
+        sync_gradients(self.model)
+        self.optimizer.step()
+        return loss
 
     def epoch(self, order) -> list:
         """Train on windows train_starts[order] in that order; returns the step losses (ONE device-to-host read)."""
@@ -1442,16 +1553,26 @@ class SeriesTrainer:
                 n = self.series.shape[0]
                 self._tail = (torch.empty((rest, n, self.w), dtype=torch.float32, device=dev),
                               torch.empty((rest, n), dtype=torch.float32, device=dev))
-            x, y = self._tail
-            ops.windows_gather(self.series, self.table, rest, self.w, x, y, first=full * self.batch, count=total)
-            with pinned_range(self.model, self.wide):
-                self.loss_table[full].copy_(_eager_step(self.model, self.optimizer, x, y))
+                if self.gaps:
+                    self._tail += (torch.empty((rest, n), dtype=torch.uint8, device=dev),
+                                   torch.empty((rest,), dtype=torch.int32, device=dev))
+            x, y = self._tail[:2]
+            if self.gaps:
+                ops.windows_gather(self.series, self.table, rest, self.w, x, y, first=full * self.batch, count=total,
+                                   valid=self.valid, valid_out=self._tail[2], row_valid=self._tail[3])
+                with pinned_range(self.model, self.wide):
+                    self.loss_table[full].copy_(self._masked_tail_step(*self._tail))
+            else:
+                ops.windows_gather(self.series, self.table, rest, self.w, x, y, first=full * self.batch, count=total)
+                with pinned_range(self.model, self.wide):
+                    self.loss_table[full].copy_(_eager_step(self.model, self.optimizer, x, y))
             steps += 1
         return self.loss_table[:steps].tolist() if steps else []
 
 
 def train_series(model=None, save_path="", config=None, series=None, w: int | None = None, train_loader_or_indices=None,
-                 val_starts=None, use_graph: bool | None = None):
+                 val_starts=None, use_graph: bool | None = None, gaps: bool | None = None,
+                 fill: SeriesFill | None = None):
     """harness.train's loop (same optimizer, loss, `wide` decision, checkpoint rule, 15-epoch early stop, returned
     list of step losses) for a series [n, T] resident on the device: every epoch is one upload of the window table and
     a run of graph replays (SeriesTrainer), every validation pass `validate_series`.
@@ -1459,7 +1580,12 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
     `train_loader_or_indices` / `val_starts`: an index loader (`main.IndexLoader`) — its DataLoader is asked for the
     epoch's order (`epoch_order`: the shuffles and the generator's state are those of a run that iterates it, the
     validation loader's per-epoch draw included) — or a tensor of target ticks, taken in the given order.
-    `use_graph` None: config["hip_graph"], default True.  One process only."""
+    `use_graph` None: config["hip_graph"], default True.  One process only.
+
+    `gaps` (None: config["train_gaps"], default False): `series` may hold missing readings (values that
+    are not finite) after its first `w` ticks.  They are held ONCE (`fill_series`, or the `fill=` of a caller that has
+    done it); the `wide` decision looks at the filled series; the trainer and every validation pass cut windows,
+    targets and validity bytes from that one fill, and every loss is the mean over the observed targets."""
     if world()[1] > 1:
         raise _lib.GdnHipError("train_series runs in one process: sharding an epoch of the resident series across ranks is "
                           "not implemented (harness.train with per-rank loaders does data-parallel training)")
@@ -1467,6 +1593,14 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
     if use_graph is None:
         use_graph = bool(config.get("hip_graph", True))
     w = int(w if w is not None else model.gnn_layers[0].gnn.lin.weight.shape[1])
+    if gaps is None:
+        gaps = bool(config.get("train_gaps", False))
+    raw, plane = series, None
+    if gaps:
+        fill = fill_series(raw, w) if fill is None else fill
+        series, plane = fill.series, fill.valid
+    elif fill is not None:
+        raise ValueError("fill= is the held series of gaps=True")
     train_starts, train_loader = _window_ticks(train_loader_or_indices)
     val_ticks, val_loader = _window_ticks(val_starts)
     batch = int(train_loader.batch_size if train_loader is not None else config.get("batch", 128))
@@ -1483,15 +1617,17 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
     for _epoch in range(config.get("epoch", 1)):
         order = epoch_order(train_loader) if train_loader is not None else torch.arange(train_starts.numel())
         if trainer is None:
-            trainer = SeriesTrainer(model, series, w, train_starts, min(batch, max(1, int(train_starts.numel()))),
-                                    lr=0.001, weight_decay=config.get("decay", 0), wide=wide, use_graph=use_graph)
+            extra = {"gaps": True, "fill": fill} if gaps else {}
+            trainer = SeriesTrainer(model, raw, w, train_starts, min(batch, max(1, int(train_starts.numel()))),
+                                    lr=0.001, weight_decay=config.get("decay", 0), wide=wide, use_graph=use_graph, **extra)
         step_losses = trainer.epoch(order)
         losses.extend(step_losses)
         val_loss = None
         if val_ticks is not None:
             if val_loader is not None:
                 epoch_order(val_loader)                  # what iterating the validation loader draws
-            val_loss = validate_series(model, series, val_ticks, val_batch)[0]
+            val_loss = (validate_series(model, series, val_ticks, val_batch, valid=plane)[0] if gaps else
+                        validate_series(model, series, val_ticks, val_batch)[0])
         if best.update(val_loss, float(sum(step_losses)), model, save_path):
             break
     return losses

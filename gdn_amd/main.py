@@ -155,6 +155,12 @@ class Main:
 
     # ------------------------------------------------------------------------------------------------
     def run(self):
+        # -train_gaps: train.csv may hold missing readings (NaN / inf).  They are held once, here; training, every
+        # validation pass and the validation block of the report cut windows, targets and validity bytes from this fill
+        train_gaps = bool(self.train_config.get("train_gaps"))
+        check_train_gaps(train_gaps, bool(self.train_config.get("hip_graph", True)))
+        fill = harness.fill_series(self.train_series, self.train_config["slide_win"]) if train_gaps else None
+        looked_at = fill.series if train_gaps else self.train_series
         if len(self.env_config["load_model_path"]) > 0:
             model_save_path = self.env_config["load_model_path"]
         else:
@@ -162,8 +168,19 @@ class Main:
             # raw engineering units (the reference's main.py normalises nothing; scripts/process_*.py do, offline):
             # the resident training series is looked at once and the step runs on the fp32 row-gather kernels when
             # it exceeds the 16-bit operand range of the matrix-core ones (include/gdn_hip.h "range guard")
-            self.train_config.setdefault("wide", self.model.train().input_exceeds_limit(self.train_series, margin=16.0))
-            if self.train_config.get("hip_graph", True):
+            self.train_config.setdefault("wide", self.model.train().input_exceeds_limit(looked_at, margin=16.0))
+            if train_gaps:
+                w = self.train_config["slide_win"]
+                ticks = self.train_dataset.starts
+                share = [harness.masked_share(fill.valid, ticks[ld.loader.dataset.tensors[0].to(ticks.device)], w)
+                         for ld in (self.train_dataloader, self.val_dataloader)]
+                print(f"train_gaps: {100 * share[0]:.3f} % of the training targets and {100 * share[1]:.3f} % of the "
+                      "validation targets are missing and left out of the losses")
+                self.train_log = harness.train_series(self.model, model_save_path, config=self.train_config,
+                                                      series=self.train_series, w=w,
+                                                      train_loader_or_indices=self.train_dataloader,
+                                                      val_starts=self.val_dataloader, gaps=True, fill=fill)
+            elif self.train_config.get("hip_graph", True):
                 # epochs on the device (harness.train_series): the loaders decide the order (same draws), the windows
                 # are cut inside the captured step, the validation loss is formed on the device
                 self.train_log = harness.train_series(self.model, model_save_path, config=self.train_config,
@@ -189,8 +206,12 @@ class Main:
         self.test_result = [pred, gt, labels.view(-1, 1).expand(-1, pred.shape[1])]
         val_ticks = self.train_dataset.starts[self.val_dataloader.loader.dataset.tensors[0].to(self.device)]
         harness.epoch_order(self.val_dataloader.loader)     # (the draw of iterating the loader, as test() did)
-        _, val_pred, val_gt = harness.validate_series(best_model, self.train_series, val_ticks,
-                                                      self.train_config["batch"])
+        if train_gaps:
+            _, val_pred, val_gt = harness.validate_series(best_model, fill.series, val_ticks, self.train_config["batch"],
+                                                          valid=fill.valid)
+        else:
+            _, val_pred, val_gt = harness.validate_series(best_model, self.train_series, val_ticks,
+                                                          self.train_config["batch"])
         self.val_result = [val_pred, val_gt, self.train_dataset.labels[val_ticks].view(-1, 1).expand(-1, val_pred.shape[1])]
         info = self.get_score(self.test_result, self.val_result)
         if self.env_config.get("localise"):
@@ -311,7 +332,7 @@ class Main:
 
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
-    -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every."""
+    -train_gaps / -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -332,6 +353,9 @@ def build_parser():
     parser.add_argument("-load_model_path", help="trained model path", type=str, default="")
     parser.add_argument("-data_root", help="directory holding <dataset>/train.csv, test.csv, list.txt", type=str, default="./data")
     parser.add_argument("-no_hip_graph", help="launch every training step eagerly", action="store_true")
+    parser.add_argument("-train_gaps", help="train.csv may hold missing (non-finite) readings after its first slide_win "
+                        "ticks: hold them at the sensor's last real value and leave them out of the training and "
+                        "validation losses (not with -no_hip_graph)", action="store_true")
     parser.add_argument("-localise", help="save the deviating sensors and their attention at the ticks above the "
                         "report's threshold to this .npz", type=str, default="")
     parser.add_argument("-stream", help="after the report, replay the test series through a streaming detector in "
@@ -348,8 +372,17 @@ def build_parser():
     return parser
 
 
+def check_train_gaps(train_gaps: bool, hip_graph: bool) -> None:
+    """-train_gaps trains through harness.train_series (the windows and their validity bytes are cut on the device);
+    the eager loop over the loaders (-no_hip_graph) has no masked loss, so the pair is refused by name."""
+    if train_gaps and not hip_graph:
+        raise ValueError("-train_gaps needs the device-epoch path (harness.train_series): it cannot be combined with "
+                         "-no_hip_graph, whose eager loop over the loaders has no masked loss")
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_train_gaps(args.train_gaps, not args.no_hip_graph)
     random.seed(args.random_seed)                      # main.py:221-228
     np.random.seed(args.random_seed)
     torch.manual_seed(args.random_seed)
@@ -360,7 +393,7 @@ def main(argv=None):
                     "slide_stride": args.slide_stride, "comment": args.comment, "seed": args.random_seed,
                     "out_layer_num": args.out_layer_num, "out_layer_inter_dim": args.out_layer_inter_dim,
                     "decay": args.decay, "val_ratio": args.val_ratio, "topk": args.topk,
-                    "hip_graph": not args.no_hip_graph}
+                    "hip_graph": not args.no_hip_graph, "train_gaps": args.train_gaps}
     env_config = {"save_path": args.save_path_pattern, "dataset": args.dataset, "report": args.report,
                   "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
                   "localise": args.localise, "stream": args.stream,

@@ -584,8 +584,11 @@ def mse_workspace(device) -> torch.Tensor:
     return torch.zeros((_lib.load().gdn_mse_workspace_bytes() // 8,), dtype=torch.float64, device=device)
 
 
-def mse_loss_grad(out, y, workspace, loss=None, d_out=None):
-    """(loss, d_out): F.mse_loss(out, y, reduction='mean') (train.py:20-23) and d loss / d out."""
+def mse_loss_grad(out, y, workspace, loss=None, d_out=None, valid=None, row_valid=None, m_out=None):
+    """(loss, d_out): F.mse_loss(out, y, reduction='mean') (train.py:20-23) and d loss / d out.
+    With `valid` [batch, n] uint8 and `row_valid` [batch] int32 (windows_gather's validity outputs) the mean runs over
+    the observed targets only (gdn_mse_loss_grad_masked): d_out is exactly 0.0 at a masked target, whatever out / y
+    hold there; no observed target: loss 0, d_out zeros.  `m_out`: optional int64 [] that receives their number."""
     out, y = _chk(out, name="out"), _chk(y, name="y")
     if out.shape != y.shape:
         raise ValueError(f"shape mismatch: {tuple(out.shape)} vs {tuple(y.shape)}")
@@ -593,8 +596,25 @@ def mse_loss_grad(out, y, workspace, loss=None, d_out=None):
         loss = torch.empty((), dtype=torch.float32, device=out.device)
     if d_out is None:
         d_out = torch.empty_like(out)
-    _lib.call("gdn_mse_loss_grad", _ptr(out), _ptr(y), out.numel(), _ptr(workspace), _ptr(loss), _ptr(d_out),
-              _stream())
+    if valid is None:
+        if row_valid is not None or m_out is not None:
+            raise ValueError("row_valid / m_out belong to the masked loss: give valid as well")
+        _lib.call("gdn_mse_loss_grad", _ptr(out), _ptr(y), out.numel(), _ptr(workspace), _ptr(loss), _ptr(d_out),
+                  _stream())
+        return loss, d_out
+    if out.dim() != 2:
+        raise ValueError(f"the masked loss takes out / y [batch, n], got {tuple(out.shape)}")
+    batch, n = out.shape
+    valid = _valid_plane(valid, (batch, n), "valid")
+    if row_valid is None:
+        raise ValueError("valid needs row_valid [batch] int32, the per-window counts of the same gather")
+    row_valid = _chk(row_valid, torch.int32, name="row_valid")
+    if row_valid.numel() != batch:
+        raise ValueError(f"row_valid: expected {batch} int32 counts, got {tuple(row_valid.shape)}")
+    if m_out is not None:
+        m_out = _chk(m_out, torch.int64, name="m_out")
+    _lib.call("gdn_mse_loss_grad_masked", _ptr(out), _ptr(y), _ptr(valid), _ptr(row_valid), batch, n, _ptr(workspace),
+              _ptr(loss), _ptr(d_out), _ptr(m_out), _stream())
     return loss, d_out
 
 
@@ -876,11 +896,15 @@ def check_window_table(starts: torch.Tensor, w: int, series_len: int) -> torch.T
     return starts
 
 
-def windows_gather(series, starts, batch: int, w: int, x_out, y_out, first: int = 0, cursor=None, count: int | None = None):
+def windows_gather(series, starts, batch: int, w: int, x_out, y_out, first: int = 0, cursor=None, count: int | None = None,
+                   valid=None, valid_out=None, row_valid=None):
     """x_out[b, i, :] = series[i, t-w : t], y_out[b, i] = series[i, t] with t = starts[first + cursor[0] * batch + b]
     (cursor None: starts[first + b]) for b < batch: datasets/TimeDataset.py's windows of a series [n, T] resident on the
     device.  `starts` int64 on the device (check_window_table), `count` = its valid entries (default: all); entries
-    beyond it give windows of zeros.  x_out / y_out: contiguous fp32 with room for [batch, n, w] / [batch, n]."""
+    beyond it give windows of zeros.  x_out / y_out: contiguous fp32 with room for [batch, n, w] / [batch, n].
+    With `valid` [T - w, n] uint8 (series_fill's plane of the filled `series`) the same launch also writes
+    valid_out[b, :] = valid[t - w, :] (uint8, room for [batch, n]) and row_valid[b] = their sum (int32, room for
+    [batch]); zeros for a window of zeros (gdn_windows_gather_gaps)."""
     series = _chk(series, name="series")
     if series.dim() != 2:
         raise ValueError(f"expected the raw series [n, T], got {tuple(series.shape)}")
@@ -891,8 +915,20 @@ def windows_gather(series, starts, batch: int, w: int, x_out, y_out, first: int 
     for t, need, name in ((x_out, batch * n * w, "x_out"), (y_out, batch * n, "y_out")):
         if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need:
             raise ValueError(f"{name}: a contiguous fp32 device tensor of at least {need} elements is needed")
-    _lib.call("gdn_windows_gather", _ptr(series), n, series_len, _ptr(starts), starts.numel() if count is None else count,
-              _ptr(cursor), first, batch, w, _ptr(x_out), _ptr(y_out), _stream())
+    head = (_ptr(series), n, series_len, _ptr(starts), starts.numel() if count is None else count, _ptr(cursor), first,
+            batch, w, _ptr(x_out), _ptr(y_out))
+    if valid is None:
+        if valid_out is not None or row_valid is not None:
+            raise ValueError("valid_out / row_valid are cut from the validity plane: give valid as well")
+        _lib.call("gdn_windows_gather", *head, _stream())
+        return x_out, y_out
+    valid = _valid_plane(valid, (series_len - w, n), "valid")
+    if valid_out is None or row_valid is None:
+        raise ValueError("valid needs valid_out (uint8, [batch, n]) and row_valid (int32, [batch]) to write into")
+    for t, dtype, need, name in ((valid_out, torch.uint8, batch * n, "valid_out"), (row_valid, torch.int32, batch, "row_valid")):
+        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < need:
+            raise ValueError(f"{name}: a contiguous {dtype} device tensor of at least {need} elements is needed")
+    _lib.call("gdn_windows_gather_gaps", *head, _ptr(valid), _ptr(valid_out), _ptr(row_valid), _stream())
     return x_out, y_out
 
 
@@ -902,19 +938,35 @@ def epoch_advance(loss, cursor, loss_table):
               _ptr(_chk(loss_table, name="loss_table")), loss_table.numel(), _stream())
 
 
-def mse_batch_means(pred, y, batch: int, batch_means=None, mean=None):
+def mse_batch_means(pred, y, batch: int, batch_means=None, mean=None, valid=None, batch_counts=None):
     """(batch_means [ceil(rows / batch)], mean []) float64: F.mse_loss of every logical minibatch of `batch` rows of
-    pred / y [rows, n] (the last one ragged) and test.py's sum(losses) / len(losses).  Bitwise reproducible."""
+    pred / y [rows, n] (the last one ragged) and test.py's sum(losses) / len(losses).  Bitwise reproducible.
+    With `valid` [rows, n] uint8 every minibatch's mean runs over its observed targets (0 when it has none), `mean` over
+    the minibatches that have one (0 when none has), and the return is (batch_means, mean, batch_counts int64)
+    (gdn_mse_batch_means_masked)."""
     pred, y = _chk(pred, name="pred"), _chk(y, name="y")
     if pred.shape != y.shape or pred.dim() != 2:
         raise ValueError(f"expected pred and y of one shape [rows, n], got {tuple(pred.shape)} and {tuple(y.shape)}")
     rows, n = pred.shape
+    batches = (rows + batch - 1) // batch
     if batch_means is None:
-        batch_means = torch.empty(((rows + batch - 1) // batch,), dtype=torch.float64, device=pred.device)
+        batch_means = torch.empty((batches,), dtype=torch.float64, device=pred.device)
     if mean is None:
         mean = torch.empty((), dtype=torch.float64, device=pred.device)
-    _lib.call("gdn_mse_batch_means", _ptr(pred), _ptr(y), rows, n, batch, _ptr(batch_means), _ptr(mean), None, _stream())
-    return batch_means, mean
+    if valid is None:
+        if batch_counts is not None:
+            raise ValueError("batch_counts belongs to the masked means: give valid as well")
+        _lib.call("gdn_mse_batch_means", _ptr(pred), _ptr(y), rows, n, batch, _ptr(batch_means), _ptr(mean), None, _stream())
+        return batch_means, mean
+    valid = _valid_plane(valid, (rows, n), "valid")
+    if batch_counts is None:
+        batch_counts = torch.empty((batches,), dtype=torch.int64, device=pred.device)
+    batch_counts = _chk(batch_counts, torch.int64, name="batch_counts")
+    if batch_counts.numel() < batches or batch_means.numel() < batches:
+        raise ValueError(f"batch_means / batch_counts: room for {batches} minibatches is needed")
+    _lib.call("gdn_mse_batch_means_masked", _ptr(pred), _ptr(y), _ptr(valid), rows, n, batch, _ptr(batch_means),
+              _ptr(batch_counts), _ptr(mean), None, _stream())
+    return batch_means, mean, batch_counts
 
 
 # --------------------------------------------------------------------------- streaming detector

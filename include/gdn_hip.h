@@ -397,6 +397,16 @@ long long gdn_mse_workspace_bytes(void);
 int gdn_mse_loss_grad(const float* out, const float* y, long long count, double* workspace,
                       float* loss, float* d_out, void* stream);
 
+/* gdn_mse_loss_grad_masked: the loss over the observed targets only (training on a series with missing readings).
+ * valid[batch, n] uint8 says which targets are real, row_valid[batch] int32 how many per window (both are
+ * gdn_windows_gather_gaps' outputs); m = sum(row_valid).  loss = sum over valid of (out - y)^2 / m;
+ * d_out = 2 (out - y) / m where valid, EXACTLY 0.0 where not (a select: a non-finite out or y in a masked slot
+ * reaches neither); m = 0: loss 0, d_out all zeros.  One launch: every workgroup adds the `batch` counts itself, then
+ * gdn_mse_loss_grad's grid, chains, finish and scale — with every byte set it writes gdn_mse_loss_grad's bits.  Same
+ * workspace rules.  m_out (int64[1], may be NULL) receives m.  Additive: the ABI version does not move.          */
+int gdn_mse_loss_grad_masked(const float* out, const float* y, const uint8_t* valid, const int* row_valid, int batch,
+                             int n, double* workspace, float* loss, float* d_out, int64_t* m_out, void* stream);
+
 /* ---- fused eval forward (the throughput path) ---------------------------------------
  * Everything from x[batch,n,w] to out[batch,n] in one launch (one workgroup per window,
  * xlin tile and neighbour lists resident in LDS): models/GDN.py:122-187 under
@@ -764,6 +774,22 @@ int gdn_windows_gather(const float* series, int n, long long series_len, const i
 int gdn_epoch_advance(const float* loss, int64_t* cursor, float* loss_table, long long table_len, void* stream);
 int gdn_mse_batch_means(const float* pred, const float* y, long long rows, int n, long long batch,
                         double* batch_means, double* mean, void* workspace, void* stream);
+
+/* The same two with the validity plane of a filled series (gdn_series_fill's `valid` [series_len - w, n] uint8, row
+ * t - w = tick t): training and validating on a series with missing readings.
+ *   gdn_windows_gather_gaps     gdn_windows_gather, and valid_out[b, :] = valid[t - w, :] (n bytes, any alignment, 64-bit
+ *                               offset), row_valid[b] = how many of them are set.  An entry beyond the table or a tick
+ *                               outside [w, series_len): zeros, valid_out = 0, row_valid = 0.  series_len > w.
+ *   gdn_mse_batch_means_masked  gdn_mse_batch_means over the real targets: valid [rows, n] uint8 beside pred / y;
+ *                               batch_means[q] = the masked mean of minibatch q (0 when it has no real target),
+ *                               batch_counts[q] int64 = its real targets; mean[0] = the average of the means of the
+ *                               minibatches that have one, in batch order, 0 when none has.  Same chains and tree.  */
+int gdn_windows_gather_gaps(const float* series, int n, long long series_len, const int64_t* starts, long long count,
+                            const int64_t* cursor, long long first, int batch, int w, float* x_out, float* y_out,
+                            const uint8_t* valid, uint8_t* valid_out, int* row_valid, void* stream);
+int gdn_mse_batch_means_masked(const float* pred, const float* y, const uint8_t* valid, long long rows, int n,
+                               long long batch, double* batch_means, int64_t* batch_counts, double* mean,
+                               void* workspace, void* stream);
 
 /* ---- streaming detector --------------------------------------------------------------------
  * Scoring ticks as they arrive, 1 .. c at a time, against a frozen calibration (median / IQR per sensor and one
