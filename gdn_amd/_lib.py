@@ -123,6 +123,10 @@ SIGNATURES = {
     "gdn_stream_calib_bytes": [_c_int, _c_int],
     "gdn_stream_calib_write": [_p] * 4 + [_c_int] * 5 + [_p] * 3,
     "gdn_stream_calib_write_gaps": [_p] * 5 + [_c_int] * 5 + [_p] * 3,
+    "gdn_score_keys_valid": [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p],
+    "gdn_score_key_counts": [_p, _c_int, _c_int, _c_int, _p, _p],
+    "gdn_score_select_counts": [_p, _c_int, _c_int, _c_int, _p, _c_int, _p, _p, _p, _p],
+    "gdn_stream_calib_write_sensor": [_p] * 5 + [_c_int] * 5 + [_p] * 3,
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

@@ -18,6 +18,64 @@ struct SelectArgs {
   int bracket;       // 1: the one-workgroup flat select first tries the sample brackets (select_onewg_kernel)
 };
 
+// Ranks, interpolation weights and median rule of a sensor with t >= 1 real keys.  ONE function for the host
+// (make_select_args: the same t for every sensor) and the device (gdn_score_select_counts: t = counts[s]): the same
+// float64 operations in the same order, no contraction in this file, hence the same bits.
+__host__ __device__ inline void fill_select_args(SelectArgs& sa, long long t) {
+  // np.median: middle value, or the mean of the two middle values when t is even
+  sa.median_pair = (t % 2 == 0);
+  sa.rank[0] = (int)(sa.median_pair ? t / 2 - 1 : (t - 1) / 2);
+  sa.rank[1] = (int)(sa.median_pair ? t / 2 : (t - 1) / 2);
+  // np.percentile(method='linear'): virtual index n*q + (alpha + q*(1-alpha-beta)) - 1, alpha=beta=1
+  const double qs[2] = {25.0 / 100.0, 75.0 / 100.0};
+  for (int h = 0; h < 2; ++h) {
+    const double vi = (double)t * qs[h] + (1.0 + qs[h] * (1.0 - 1.0 - 1.0)) - 1.0;
+    const double lo = floor(vi);
+    long long ilo = (long long)lo, ihi = ilo + 1;
+    if (ilo < 0) ilo = 0;
+    if (ihi > t - 1) ihi = t - 1;
+    if (ilo > t - 1) ilo = t - 1;
+    sa.rank[2 + 2 * h] = (int)ilo;
+    sa.rank[3 + 2 * h] = (int)ihi;
+    sa.gamma[h] = vi - lo;
+  }
+  sa.total = (int)t;
+}
+
+// gdn_score_select_counts: what the kernels get in SelectArgs' place.  Sensor s has counts[s] real keys; its
+// SelectArgs are formed on the device by select_args_for (one thread, handed to the workgroup through LDS: a
+// workgroup is one sensor, so every test on them stays uniform).  A sensor with fewer than max(min_count, 1) real keys
+// keeps its med_iqr row: total = 0 marks it.
+struct CountArgs {
+  const int* counts;   // [n] on the device
+  int min_count;
+  int bracket;
+};
+
+// The kernels below take their rank arguments as a template type: SelectArgs (the instantiations behind
+// gdn_score_select / _paths / gdn_score_quantiles: the kernel argument itself, nothing added) or CountArgs.
+__device__ __forceinline__ const SelectArgs& select_args_for(const SelectArgs& sa, int) { return sa; }
+template <typename ARGS> constexpr bool kPerSensor = false;
+template <> constexpr bool kPerSensor<CountArgs> = true;
+
+__device__ __forceinline__ const SelectArgs& select_args_for(const CountArgs& ca, int s) {
+  __shared__ SelectArgs sh;
+  if (threadIdx.x == 0) {
+    const int c = ca.counts[s];
+    if (c >= 1 && c >= ca.min_count) {
+      fill_select_args(sh, c);
+    } else {
+      for (int q = 0; q < 6; ++q) sh.rank[q] = 0;
+      sh.gamma[0] = sh.gamma[1] = 0.0;
+      sh.median_pair = 0;
+      sh.total = 0;
+    }
+    sh.bracket = ca.bracket;
+  }
+  __syncthreads();
+  return sh;
+}
+
 // keys[s][tick] = |pred[tick][s] - gt[tick][s]| in float64 (bit pattern = radix key), transposed
 // through LDS so that both the fp32 reads (along sensors) and the fp64 writes (along ticks) are
 // coalesced.  Row pitch >= t; slots t..pitch-1 get the FILLER pattern (all ones: larger than every real
@@ -43,6 +101,52 @@ __global__ __launch_bounds__(256) void score_keys_kernel(const float* __restrict
     if (s < n && tick < pitch)
       keys[(size_t)s * pitch + tick] = tick < t ? tile[lane][r] : __longlong_as_double((long long)FILLER);
   }
+}
+
+// score_keys_kernel with a validity plane (gdn_score_keys_valid): key (s, tick) is the filler wherever
+// valid[tick, s] == 0.  The validity byte is read next to the value and travels through the tile AS the value: a
+// missing reading's tile entry is the filler pattern itself, so the second half is score_keys_kernel's.
+__global__ __launch_bounds__(256) void score_keys_valid_kernel(const float* __restrict__ pred,
+                                                               const float* __restrict__ gt,
+                                                               const unsigned char* __restrict__ valid, int t, int n,
+                                                               int pitch, double* __restrict__ keys) {
+  __shared__ double tile[64][65];
+  const int t0 = blockIdx.x * 64, s0 = blockIdx.y * 64;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int r = wv; r < 64; r += 4) {
+    const int tick = t0 + r, s = s0 + lane;
+    if (tick < t && s < n) {
+      const size_t o = (size_t)tick * n + s;
+      const double e = fabs((double)pred[o] - (double)gt[o]);
+      tile[r][lane] = valid[o] != 0 ? e : __longlong_as_double((long long)FILLER);
+    }
+  }
+  __syncthreads();
+  for (int r = wv; r < 64; r += 4) {
+    const int s = s0 + r, tick = t0 + lane;
+    if (s < n && tick < pitch)
+      keys[(size_t)s * pitch + tick] = tick < t ? tile[lane][r] : __longlong_as_double((long long)FILLER);
+  }
+}
+
+// counts[s] = slots of sensor s that do not hold the filler (gdn_score_key_counts).  A workgroup per sensor walks the
+// sensor's `blocks` rows; register adds, a wave reduction, one integer LDS add per wave, one store.
+__global__ __launch_bounds__(256) void score_key_counts_kernel(const unsigned long long* __restrict__ keys, int blocks,
+                                                               int n, int pitch, int* __restrict__ counts) {
+  __shared__ int total;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) total = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int b = 0; b < blocks; ++b) {
+    const unsigned long long* row = keys + ((size_t)b * n + s) * pitch;
+    for (int i = tid; i < pitch; i += 256) mine += row[i] != FILLER ? 1 : 0;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+  if ((tid & 63) == 0) atomicAdd(&total, mine);
+  __syncthreads();
+  if (tid == 0) counts[s] = total;
 }
 
 // ------------------------------------------------------------------ radix select
@@ -80,8 +184,10 @@ struct KeyLayout {
   int blocks, n, pitch;
 };
 
-__global__ void select_init_kernel(SelState* __restrict__ state, const SelectArgs sa) {
+template <typename ARGS>
+__global__ void select_init_kernel(SelState* __restrict__ state, const ARGS args) {
   SelState& st = state[blockIdx.x];
+  const SelectArgs& sa = select_args_for(args, blockIdx.x);
   for (int i = threadIdx.x; i < NQ * 256; i += blockDim.x) (&st.hist[0][0])[i] = 0u;
   if (threadIdx.x < NQ) {
     st.prefix[threadIdx.x] = 0ull;
@@ -320,9 +426,9 @@ constexpr int FIN_NT = 1024;
 // hand-offs.  Reads the compacted buffer (FROM_B) — normally a handful of keys, <= 2048 stay in
 // registers (<= 4096), more (e.g. thousands of identical values) are re-read per digit — or, for inputs of a
 // single slice, the flat input itself.
-template <bool FROM_B>
+template <bool FROM_B, typename ARGS>
 __global__ __launch_bounds__(FIN_NT) void select_finish_kernel(const KeyLayout kl, SelState* __restrict__ state,
-                                                            int first_pass, const SelectArgs sa,
+                                                            int first_pass, const ARGS args,
                                                             double* __restrict__ med_iqr) {
   __shared__ unsigned int hist[NQ][256];
   __shared__ unsigned long long prefix[NQ];
@@ -330,6 +436,10 @@ __global__ __launch_bounds__(FIN_NT) void select_finish_kernel(const KeyLayout k
   __shared__ int rep[NQ];
   const int s = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const SelectArgs& sa = select_args_for(args, s);
+  if constexpr (kPerSensor<ARGS>) {
+    if (sa.total < 1) return;                // (uniform) too few real keys: the row stays as it is
+  }
   SelState& st = state[s];
   const unsigned int slots = (unsigned int)kl.blocks * (unsigned int)kl.pitch;
   const unsigned int cnt = FROM_B ? st.cnt_b : slots;
@@ -434,8 +544,8 @@ constexpr int BR_S = ONE_NT;      // sample size: one key per thread
 constexpr float BR_C = 2.62f;     // margin in units of sqrt(m) sample positions (see above)
 constexpr unsigned int BR_NONE = 0xffffu;   // bin code of a key outside every interval
 
-template <bool FLAT>
-__global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl, const SelectArgs sa,
+template <bool FLAT, typename ARGS>
+__global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl, const ARGS args,
                                                               double* __restrict__ med_iqr, int* __restrict__ path) {
   __shared__ unsigned int hist[NQ][256];
   __shared__ unsigned int sbuf[2 * BR_S];    // bracket path: the sample (two exchange buffers of the sort)
@@ -450,6 +560,10 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
   __shared__ unsigned int cnt0[2];
   const int s = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const SelectArgs& sa = select_args_for(args, s);
+  if constexpr (kPerSensor<ARGS>) {
+    if (sa.total < 1) return;                // (uniform) too few real keys: the row stays as it is
+  }
   const unsigned int slots = (unsigned int)kl.blocks * (unsigned int)kl.pitch;
 #ifdef GDN_SELECT_TIMING
   const long long tick_start = wall_clock64();
@@ -1166,24 +1280,7 @@ bool bracket_enabled() {
 
 SelectArgs make_select_args(long long t) {
   SelectArgs sa;
-  // np.median: middle value, or the mean of the two middle values when t is even
-  sa.median_pair = (t % 2 == 0);
-  sa.rank[0] = (int)(sa.median_pair ? t / 2 - 1 : (t - 1) / 2);
-  sa.rank[1] = (int)(sa.median_pair ? t / 2 : (t - 1) / 2);
-  // np.percentile(method='linear'): virtual index n*q + (alpha + q*(1-alpha-beta)) - 1, alpha=beta=1
-  const double qs[2] = {25.0 / 100.0, 75.0 / 100.0};
-  for (int h = 0; h < 2; ++h) {
-    const double vi = (double)t * qs[h] + (1.0 + qs[h] * (1.0 - 1.0 - 1.0)) - 1.0;
-    const double lo = floor(vi);
-    long long ilo = (long long)lo, ihi = ilo + 1;
-    if (ilo < 0) ilo = 0;
-    if (ihi > t - 1) ihi = t - 1;
-    if (ilo > t - 1) ilo = t - 1;
-    sa.rank[2 + 2 * h] = (int)ilo;
-    sa.rank[3 + 2 * h] = (int)ihi;
-    sa.gamma[h] = vi - lo;
-  }
-  sa.total = (int)t;
+  fill_select_args(sa, t);
   sa.bracket = bracket_enabled() ? 1 : 0;
   return sa;
 }
@@ -1205,7 +1302,8 @@ __global__ void select_path_fill_kernel(int* __restrict__ path, int n, int value
 
 // path (optional, [n] int32 on the device): 0 where a sensor's ranks were settled by the sample brackets of
 // select_onewg_kernel, 1 where the digit passes ran (every sensor on the other routes)
-int run_select(const double* keys, int blocks, int n, int pitch, long long total, double* workspace,
+template <typename ARGS>
+int run_select(const double* keys, int blocks, int n, int pitch, const ARGS sa, double* workspace,
                double* med_iqr, int* path, hipStream_t st) {
   const long long slots = (long long)blocks * pitch;
   KeyLayout kl;
@@ -1213,25 +1311,24 @@ int run_select(const double* keys, int blocks, int n, int pitch, long long total
   kl.bufb = reinterpret_cast<unsigned long long*>(workspace);
   kl.blocks = blocks; kl.n = n; kl.pitch = pitch;
   SelState* state = reinterpret_cast<SelState*>(kl.bufb + (size_t)slots * n);
-  const SelectArgs sa = make_select_args(total);
   const int slices = (int)((slots + SLICE - 1) / SLICE);
   if (slices > 1 && slots <= (long long)ONE_NT * ONE_FK && !force_multi_block()) {
     // the whole sensor fits one workgroup's registers: one launch, no global state
-    if (kl.blocks == 1) hipLaunchKernelGGL(select_onewg_kernel<true>, dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr, path);
-    else hipLaunchKernelGGL(select_onewg_kernel<false>, dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr, path);
+    if (kl.blocks == 1) hipLaunchKernelGGL((select_onewg_kernel<true, ARGS>), dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr, path);
+    else hipLaunchKernelGGL((select_onewg_kernel<false, ARGS>), dim3(n), dim3(ONE_NT), 0, st, kl, sa, med_iqr, path);
     return gdn_launch_status();
   }
   if (path) hipLaunchKernelGGL(select_path_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, path, n, 1);
-  hipLaunchKernelGGL(select_init_kernel, dim3(n), dim3(256), 0, st, state, sa);
+  hipLaunchKernelGGL(select_init_kernel<ARGS>, dim3(n), dim3(256), 0, st, state, sa);
   if (slices == 1) {   // tiny input: everything in the finisher, straight from the input
-    hipLaunchKernelGGL(select_finish_kernel<false>, dim3(n), dim3(FIN_NT), 0, st, kl, state, 0, sa, med_iqr);
+    hipLaunchKernelGGL((select_finish_kernel<false, ARGS>), dim3(n), dim3(FIN_NT), 0, st, kl, state, 0, sa, med_iqr);
     return gdn_launch_status();
   }
   hipLaunchKernelGGL((select_pass_kernel<false, false>), dim3(slices, n), dim3(256), 0, st, kl, state, 0);
   hipLaunchKernelGGL((select_pass_kernel<false, false>), dim3(slices, n), dim3(256), 0, st, kl, state, 1);
   hipLaunchKernelGGL((select_pass_kernel<false, true>), dim3(slices, n), dim3(256), 0, st, kl, state, 2);
   // digits 3-7 on the survivors (normally a few percent of the keys) in one launch per sensor
-  hipLaunchKernelGGL(select_finish_kernel<true>, dim3(n), dim3(FIN_NT), 0, st, kl, state, 3, sa, med_iqr);
+  hipLaunchKernelGGL((select_finish_kernel<true, ARGS>), dim3(n), dim3(FIN_NT), 0, st, kl, state, 3, sa, med_iqr);
   return gdn_launch_status();
 }
 
@@ -1262,7 +1359,7 @@ extern "C" int gdn_score_select(const double* keys, int blocks, int n, int pitch
   if (!keys || !workspace || !med_iqr || blocks <= 0 || n <= 0 || pitch <= 0 || total <= 0) return GDN_ERR_ARG;
   if (total > (long long)blocks * pitch || (long long)blocks * pitch > 0x7fffffffll) return GDN_ERR_ARG;
   if (blocks > 1 && pitch % SLICE != 0) return GDN_ERR_UNSUPPORTED;   // slices must not straddle blocks
-  return run_select(keys, blocks, n, pitch, total, workspace, med_iqr, nullptr, (hipStream_t)stream);
+  return run_select(keys, blocks, n, pitch, make_select_args(total), workspace, med_iqr, nullptr, (hipStream_t)stream);
 }
 
 // gdn_score_select that also records, per sensor, which path settled its ranks (see run_select)
@@ -1271,7 +1368,40 @@ extern "C" int gdn_score_select_paths(const double* keys, int blocks, int n, int
   if (!keys || !workspace || !med_iqr || !path || blocks <= 0 || n <= 0 || pitch <= 0 || total <= 0) return GDN_ERR_ARG;
   if (total > (long long)blocks * pitch || (long long)blocks * pitch > 0x7fffffffll) return GDN_ERR_ARG;
   if (blocks > 1 && pitch % SLICE != 0) return GDN_ERR_UNSUPPORTED;
-  return run_select(keys, blocks, n, pitch, total, workspace, med_iqr, path, (hipStream_t)stream);
+  return run_select(keys, blocks, n, pitch, make_select_args(total), workspace, med_iqr, path, (hipStream_t)stream);
+}
+
+// Calibration on each sensor's own readings (include/gdn_hip.h): keys with a validity plane, the per-sensor count of
+// real keys, and the select with per-sensor counts.
+extern "C" int gdn_score_keys_valid(const float* pred, const float* gt, const uint8_t* valid, int t, int n, int pitch,
+                                    double* keys, void* stream) {
+  if (!pred || !gt || !valid || !keys || t <= 0 || n <= 0 || pitch < t) return GDN_ERR_ARG;
+  hipLaunchKernelGGL(score_keys_valid_kernel, dim3((pitch + 63) / 64, (n + 63) / 64), dim3(256), 0,
+                     (hipStream_t)stream, pred, gt, valid, t, n, pitch, keys);
+  return gdn_launch_status();
+}
+
+extern "C" int gdn_score_key_counts(const double* keys, int blocks, int n, int pitch, int32_t* counts, void* stream) {
+  if (!keys || !counts || blocks <= 0 || n <= 0 || pitch <= 0) return GDN_ERR_ARG;
+  if ((long long)blocks * pitch > 0x7fffffffll) return GDN_ERR_ARG;
+  hipLaunchKernelGGL(score_key_counts_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const unsigned long long*>(keys), blocks, n, pitch, counts);
+  return gdn_launch_status();
+}
+
+// gdn_score_select where sensor s has counts[s] real keys (device data: no host read); a sensor with fewer than
+// max(min_count, 1) keeps its med_iqr row (and its path entry on the one-workgroup route).  counts[s] must be the
+// number of non-filler slots of sensor s (gdn_score_key_counts computes it).
+extern "C" int gdn_score_select_counts(const double* keys, int blocks, int n, int pitch, const int32_t* counts,
+                                       int min_count, double* workspace, double* med_iqr, int* path, void* stream) {
+  if (!keys || !counts || !workspace || !med_iqr || blocks <= 0 || n <= 0 || pitch <= 0) return GDN_ERR_ARG;
+  if ((long long)blocks * pitch > 0x7fffffffll) return GDN_ERR_ARG;
+  if (blocks > 1 && pitch % SLICE != 0) return GDN_ERR_UNSUPPORTED;
+  CountArgs ca;
+  ca.counts = counts;
+  ca.min_count = min_count;
+  ca.bracket = bracket_enabled() ? 1 : 0;
+  return run_select(keys, blocks, n, pitch, ca, workspace, med_iqr, path, (hipStream_t)stream);
 }
 
 extern "C" int gdn_score_quantiles(const float* pred, const float* gt, int t, int n, double* workspace,
@@ -1280,7 +1410,7 @@ extern "C" int gdn_score_quantiles(const float* pred, const float* gt, int t, in
   double* keys = workspace;
   const int rc = gdn_score_keys(pred, gt, t, n, t, keys, stream);
   if (rc != GDN_OK) return rc;
-  return run_select(keys, 1, n, t, t, workspace + (size_t)t * n, med_iqr, nullptr, (hipStream_t)stream);
+  return run_select(keys, 1, n, t, make_select_args(t), workspace + (size_t)t * n, med_iqr, nullptr, (hipStream_t)stream);
 }
 
 namespace {

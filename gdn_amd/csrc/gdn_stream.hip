@@ -438,6 +438,50 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_ker
   }
 }
 
+// The ring write of per-sensor calibration (gdn_stream_calib_write_sensor; include/gdn_hip.h "Calibration on each
+// sensor's own readings").  Slots and order are those of the kernel above.  A tick excluded by its alarm writes the
+// filler into all n keys and keep = 0; any other tick writes keep = 1 and sensor i's key where valid[b, i] == 1, the
+// filler where it is missing: the validity byte is read next to the value and the tile carries the filler pattern in
+// the key's place.  A kernel of its own, so the two instantiations above stay as they are.
+__global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_sensor_kernel(
+    const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ chunk,
+    const int* __restrict__ alarm, const unsigned char* __restrict__ valid, int count, int n, int R,
+    int exclude_alarms, double* __restrict__ ring_keys, unsigned char* __restrict__ ring_keep) {
+  __shared__ double tile[64][65];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b0 = blockIdx.x * 64;
+  const unsigned base = (unsigned)(reinterpret_cast<const long long*>(state)[0] % (long long)R);   // < R <= 2^20
+  auto slot_of = [&](int b) -> unsigned {                    // b < count <= c <= R: one wrap at the most
+    const unsigned at = base + (unsigned)b;
+    return at >= (unsigned)R ? at - (unsigned)R : at;
+  };
+  if (threadIdx.x < 64) {
+    const int b = b0 + (int)threadIdx.x;
+    if (b < count) ring_keep[slot_of(b)] = (exclude_alarms && alarm[b] != 0) ? 0 : 1;
+  }
+  for (int s0 = 0; s0 < n; s0 += 64) {
+    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
+      const int b = b0 + r, s = s0 + lane;
+      if (b < count && s < n) {
+        const size_t o = (size_t)b * n + s;
+        const bool keep = !(exclude_alarms && alarm[b] != 0) && valid[o] != 0;
+        const double e = fabs((double)pred[o] - (double)chunk[o]);
+        tile[r][lane] = keep ? e : __longlong_as_double((long long)CALIB_FILLER);
+      }
+    }
+    __syncthreads();
+    const int b = b0 + lane;                                 // now the lane runs along the push's rows = ring slots
+    if (b < count) {
+      const unsigned slot = slot_of(b);
+      for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
+        const int s = s0 + r;
+        if (s < n) ring_keys[(size_t)s * R + slot] = tile[lane][r];
+      }
+    }
+    __syncthreads();                                         // the tile is rewritten by the next sensor tile
+  }
+}
+
 bool stream_shape_ok(int n, int w) { return w >= 1 && w <= GDN_LONG_MAX_W && n >= 1 && n <= 4096; }
 
 bool calib_shape_ok(int n, int R) {
@@ -509,6 +553,20 @@ extern "C" int gdn_stream_calib_write_gaps(const void* state, const float* pred,
                                            int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream) {
   return calib_write<true>(state, pred, chunk, alarm, valid, c, count, n, R, exclude_alarms, ring_keys, ring_keep,
                            stream);
+}
+
+extern "C" int gdn_stream_calib_write_sensor(const void* state, const float* pred, const float* chunk,
+                                             const int32_t* alarm, const uint8_t* valid, int c, int count, int n,
+                                             int R, int exclude_alarms, double* ring_keys, uint8_t* ring_keep,
+                                             void* stream) {
+  if (!state || !pred || !chunk || !alarm || !valid || !ring_keys || !ring_keep) return GDN_ERR_ARG;
+  if (count < 1 || count > c) return GDN_ERR_ARG;
+  if (!calib_shape_ok(n, R)) return GDN_ERR_UNSUPPORTED;
+  if (c > R) return GDN_ERR_ARG;                   // two rows of one push would share a slot
+  hipLaunchKernelGGL(gdn_stream_calib_write_sensor_kernel, dim3(((unsigned)count + 63) / 64),
+                     dim3(GDN_STREAM_THREADS), 0, (hipStream_t)stream, state, pred, chunk, alarm, valid, count, n, R,
+                     exclude_alarms, ring_keys, ring_keep);
+  return gdn_launch_status();
 }
 
 extern "C" long long gdn_stream_state_bytes(int n, int w) {

@@ -482,6 +482,14 @@ class ShardedEvaluator:
 
 
 # --------------------------------------------------------------------------- resident-series evaluator
+def too_few_readings(counts, min_kept: int, t: int) -> str:
+    """The refusal of calib="sensor" when a sensor has fewer than `min_kept` real readings: the first 8 such sensors
+    and their counts (`counts` [n] on the host)."""
+    short = torch.nonzero(counts < min_kept).flatten()[:8].tolist()
+    return (f"min_kept = {min_kept}: sensors {short} have only {[int(counts[i]) for i in short]} real readings among "
+            f"the {t} scored ticks; too few for their median / IQR rows")
+
+
 class SeriesEvaluator:
     """Eval forward + anomaly score over a series of T windows resident in HBM.
 
@@ -492,7 +500,8 @@ class SeriesEvaluator:
 
     def __init__(self, model, x_all: torch.Tensor | None, y_all: torch.Tensor | None, batch: int,
                  use_graph: bool = True, want_scores: bool = False, streams: int = 3, coalesce: int = 1,
-                 series: torch.Tensor | None = None, top_m: int = 0, gaps: bool = False, min_kept: int = 64):
+                 series: torch.Tensor | None = None, top_m: int = 0, gaps: bool = False, min_kept: int = 64,
+                 calib: str = "tick"):
         """`batch` = the logical minibatch of the reference's loader; `coalesce` consecutive batches
         (contiguous in the resident series) go out as ONE launch — eval results do not depend on the
         minibatch size, and launches of a few thousand windows amortise the per-workgroup prologue.
@@ -507,9 +516,19 @@ class SeriesEvaluator:
         host read gaps adds) and fewer than `min_kept` of them are refused.  A step is then forward ->
         gdn_score_keys_keep -> gdn_score_select over the kept ticks -> the `_gaps` smooth launch: the table is
         calibrated on complete ticks and a missing reading's normalised error is exactly 0.0.  series[:, :w] must be
-        finite.  On a finite series the step writes the bits of gaps=False; gaps=False issues the launches it did."""
+        finite.  On a finite series the step writes the bits of gaps=False; gaps=False issues the launches it did.
+        `calib="sensor"` (needs gaps=True) calibrates every sensor on ITS OWN real readings instead of
+        on complete ticks: `counts` [n] int32 (t - missing_total, formed once from gdn_series_fill's counters) stays on
+        the device, `kept` is the smallest of them (read with the head check: still ONE host read) and a sensor with
+        fewer than `min_kept` real readings is refused.  A step is forward -> gdn_score_keys_valid ->
+        gdn_score_select_counts -> the `_gaps` smooth launch.  `calib="tick"` (the default) is the path above."""
+        if calib not in ("tick", "sensor"):
+            raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
+        if calib == "sensor" and not gaps:
+            raise ValueError("calib='sensor' calibrates around missing readings: it needs gaps=True")
         self.with_gaps = bool(gaps)
-        self.raw_series = self.valid = self.keep = self._gap_counters = None
+        self.calib = calib
+        self.raw_series = self.valid = self.keep = self._gap_counters = self.counts = None
         self.kept = None
         if self.with_gaps:
             series, y_all = self._fill(model, x_all, y_all, series, int(min_kept))
@@ -576,12 +595,17 @@ class SeriesEvaluator:
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         self.raw_series = ops._chk(series, name="series")
         filled, gt, self.valid, self.keep, self._gap_counters = ops.series_fill(self.raw_series, w)
+        if self.calib == "sensor":          # every sensor's real readings among the scored ticks; stays on the device
+            self.counts = (gt.shape[0] - self._gap_counters[0]).to(torch.int32)
         head_real, kept = torch.stack([torch.isfinite(self.raw_series[:, :w]).all().long(),
-                                       self.keep.sum()]).tolist()            # ONE host read
+                                       self.keep.sum() if self.counts is None else self.counts.min().long()
+                                       ]).tolist()                           # ONE host read
         if not head_real:
             raise ValueError(f"series: its first {w} ticks hold a value that is not finite; with gaps=True every "
                              "missing reading is held at an earlier real one, so the series must begin on real readings")
         self.kept = int(kept)
+        if self.kept < min_kept and self.counts is not None:
+            raise ValueError(too_few_readings(self.counts.cpu(), min_kept, gt.shape[0]))
         if self.kept < min_kept:
             raise ValueError(f"min_kept = {min_kept}: only kept = {self.kept} of the {gt.shape[0]} scored ticks have "
                              "all their readings; too few for a median / IQR table")
@@ -674,6 +698,10 @@ class SeriesEvaluator:
                                     self.t, self.n)
         if have_keys:       # keys [n, t] already sit at the head of the workspace (same layout gdn_score_quantiles uses)
             _lib.call("gdn_score_select", keys, 1, n, t, t, keys + 8 * t * n, med, st)
+        elif self.counts is not None:     # calib="sensor": the counts are device data fixed at construction
+            _lib.call("gdn_score_keys_valid", pred, y, self.valid.data_ptr(), t, n, t, keys, st)
+            _lib.call("gdn_score_select_counts", keys, 1, n, t, self.counts.data_ptr(), 1, keys + 8 * t * n, med, None,
+                      st)
         elif self.with_gaps:
             _lib.call("gdn_score_keys_keep", pred, y, self.keep.data_ptr(), t, n, t, keys, st)
             _lib.call("gdn_score_select", keys, 1, n, t, self.kept, keys + 8 * t * n, med, st)
@@ -1674,11 +1702,24 @@ class StreamDetector:
     (default max(64, R // 4)); `threshold` (IQR-normalised units) and the carry are not touched.  `recal_every=E`:
     `push` calls `recalibrate()` after every sub-push that crosses a multiple of E handed ticks.  `from_calibration`
     seeds the ring with the last min(R, T - w) calibration ticks.  The ring writer only reads the stream: a recal=R
-    detector that never recalibrates writes the bits of a recal=0 one; recal=0 issues exactly the launches it did."""
+    detector that never recalibrates writes the bits of a recal=0 one; recal=0 issues exactly the launches it did.
+
+    `calib="sensor"` (needs gaps=True and recal=R) keeps a tick with missing readings in the ring: the
+    ring write is gdn_stream_calib_write_sensor, which puts the filler into the keys of the missing readings only.
+    `recalibrate()` then counts every sensor's real keys on the device and rewrites the row of every sensor that has
+    at least `recal_min` of them; a dead sensor keeps its row and no longer stops the others.  The default "tick" is
+    the rule above, launch for launch."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, recal: int = 0,
-                 exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None):
+                 exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
+                 calib: str = "tick"):
+        if calib not in ("tick", "sensor"):
+            raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
+        if calib == "sensor" and not (gaps and int(recal) > 0):
+            raise ValueError("calib='sensor' recalibrates every sensor on its own real readings: it needs gaps=True and "
+                             "a calibration ring (recal=R)")
+        self.calib = calib
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -1745,6 +1786,8 @@ class StreamDetector:
         if self.recal:
             self.ring_keys, self.ring_keep = ops.stream_calib_ring(n, self.recal, dev)
             self._recal_ws = ops.score_select_workspace(1, n, self.recal, dev)
+        self._recal_counts = torch.zeros((n,), dtype=torch.int32, device=dev) if calib == "sensor" else None
+        self.recal_counts = None            # calib="sensor": every sensor's real keys at the last recalibrate() (host)
         self.recals = 0                     # tables written by recalibrate()
         self.recal_kept = 0                 # ... and the kept ticks behind the last one
         self._handed = 0                    # ticks handed to push(): recal_every's clock
@@ -1752,6 +1795,7 @@ class StreamDetector:
         self._graph_key = None
         self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
         self.calib_kept = None              # from_calibration(calib_gaps=True): the complete ticks behind the table
+        self.calib_counts = None            # ... calib="sensor": every sensor's real readings behind it (device int32)
 
     @classmethod
     def from_calibration(cls, model, series, chunk: int, batch: int = 8192, calib_gaps: bool = False,
@@ -1764,7 +1808,15 @@ class StreamDetector:
         SeriesEvaluator(gaps=True, min_kept=...), i.e. under the detector's own rules — missing readings held, the
         table from the complete ticks, a missing reading's error neutral — the default history is the FILLED period's
         last w ticks, and the ring is seeded with the period's own keep flags.  `calib_kept` is the number of complete
-        ticks behind the table (None without calib_gaps).  The stream's own counters start at zero."""
+        ticks behind the table (None without calib_gaps).  The stream's own counters start at zero.
+        `calib="sensor"` (needs calib_gaps=True) goes to the evaluator and the detector alike: the table
+        comes from every sensor's own real readings, the ring is seeded through the period's validity plane, and
+        `calib_kept` is the smallest per-sensor count, `calib_counts` [n] int32 (device) all of them.  Without a ring
+        (recal = 0) only the calibration follows it: the detector has nothing to recalibrate."""
+        calib = kw.get("calib", "tick")
+        if calib == "sensor" and not calib_gaps:
+            raise ValueError("calib='sensor' calibrates every sensor on its own real readings: pass calib_gaps=True "
+                             "(and gaps=True) too")
         series = ops._chk(series, name="series")
         if calib_gaps and not kw.get("gaps"):
             raise ValueError("calib_gaps=True calibrates under the rules of a gaps=True detector: pass gaps=True too")
@@ -1776,25 +1828,33 @@ class StreamDetector:
             raise ValueError(f"calibration needs a series [n, T] with T > {w}, got {tuple(series.shape)}")
         if calib_gaps:
             ev = SeriesEvaluator(model, None, None, batch=batch, use_graph=False, series=series, gaps=True,
-                                 min_kept=min_kept)
+                                 min_kept=min_kept, calib=calib)
         else:
             ev = SeriesEvaluator(model, None, series[:, w:].t().contiguous(), batch=batch, use_graph=False, series=series)
         anomaly = ev.step()
         kw.setdefault("history", ev.series[:, -w:])
         history = kw.pop("history")
+        if calib == "sensor" and not int(kw.get("recal", 0)):
+            kw["calib"] = "tick"            # no ring: the detector never calibrates anything itself
         det = cls(model, ev.med_iqr, anomaly.max(), history, chunk, **kw)
         det.calib_kept = ev.kept
+        det.calib_counts = ev.counts
         if det.recal:
-            det._seed(ev.pred, ev.y, ev.keep)
+            det._seed(ev.pred, ev.y, ev.keep, ev.valid if calib == "sensor" else None)
         return det
 
-    def _seed(self, pred, gt, keep=None):
+    def _seed(self, pred, gt, keep=None, valid=None):
         """The keys of the last s = min(R, t) rows of a period normal by declaration, oldest first, into slots R - s ..
         R - 1 with keep = 1 (no alarm is excluded): the stream starts at slot 0, so it overwrites the empty slots first
         and the oldest seeded tick last.  `keep` [t] uint8 (a calibration with missing readings): a tick that is not
-        complete gets the filler and keep = 0, as gdn_stream_calib_write_gaps would have left it."""
+        complete gets the filler and keep = 0, as gdn_stream_calib_write_gaps would have left it.  `valid` [t, n] uint8
+        (calib="sensor") takes keep's place: every tick is kept and the filler sits in the keys of its missing readings,
+        as gdn_stream_calib_write_sensor would have left it."""
         s = min(self.recal, pred.shape[0])
-        keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
+        if valid is not None:
+            keys, keep = ops.score_keys(pred[-s:], gt[-s:], s, valid=valid[-s:]), None
+        else:
+            keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
         if keep is None:
             self.ring_keep[self.recal - s:].fill_(1)
         else:
@@ -1820,7 +1880,8 @@ class StreamDetector:
                          self.top_scores, self.top_sensors, self.alarm, count=count, valid=self.valid)
         if self.recal:
             ops.stream_calib_write(self.state, self.pred, self.chunk_buf, self.alarm, self.ring_keys, self.ring_keep,
-                                   self.exclude_alarms, count=count, valid=self.valid)
+                                   self.exclude_alarms, count=count, valid=self.valid,
+                                   by_sensor=self.calib == "sensor")
         ops.stream_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors, self.w,
                            self.top_m, self.log_ticks, self.log_sensors, count=count, valid=self.valid,
                            gap_chunk=self.gap_chunk, gaps=self.gaps)
@@ -1874,9 +1935,22 @@ class StreamDetector:
         (np.median and numpy's 'linear' 25th / 75th percentiles: gdn_score_quantiles' arithmetic, ONE gdn_score_select
         straight from the ring) and return how many ticks that was; with fewer than `recal_min` kept, write nothing
         and return 0.  Eager, ONE host read (a synchronisation).  `threshold`, the carry and the captured graph stay:
-        the three normalised errors before the switch keep the table they were computed with."""
+        the three normalised errors before the switch keep the table they were computed with.
+        calib="sensor": gdn_score_key_counts over the ring, then gdn_score_select_counts(min_count = recal_min) into
+        `med_iqr` in place: the row of every sensor with at least `recal_min` real keys is rewritten, the others stay.
+        The ONE host read is of the counts: `recal_counts` [n] int64 (host), `recal_kept` = the smallest count among
+        the rewritten sensors (0 if none); returns the NUMBER OF SENSORS whose row was rewritten."""
         if not self.recal:
             raise ValueError("recalibrate(): the detector was built with recal=0 and keeps no calibration ring")
+        if self.calib == "sensor":
+            ops.score_key_counts(self.ring_keys, 1, self.n, self.recal, out=self._recal_counts)
+            ops.score_select_counts(self.ring_keys, 1, self.n, self.recal, self._recal_counts, self.recal_min,
+                                    self._recal_ws, out=self.med_iqr)
+            self.recal_counts = self._recal_counts.cpu().to(torch.int64)
+            done = self.recal_counts[self.recal_counts >= self.recal_min]
+            self.recal_kept = int(done.min()) if done.numel() else 0
+            self.recals += 1 if done.numel() else 0
+            return int(done.numel())
         total = int(self.ring_keep.sum())
         if total < self.recal_min:
             return 0

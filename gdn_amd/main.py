@@ -221,11 +221,12 @@ class Main:
                                     gaps=bool(self.env_config.get("stream_gaps")),
                                     calib_gaps=bool(self.env_config.get("stream_calib_gaps")),
                                     recal=int(self.env_config.get("stream_recal") or 0),
-                                    recal_every=int(self.env_config.get("stream_recal_every") or 0))
+                                    recal_every=int(self.env_config.get("stream_recal_every") or 0),
+                                    by_sensor=bool(self.env_config.get("calib_by_sensor")))
         return info
 
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
-                           recal_every: int = 0, calib_gaps: bool = False):
+                           recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
@@ -237,7 +238,11 @@ class Main:
         of recalibrations and the ticks kept at the last one join the line and `stream_result`.
         -stream_calib_gaps (with -stream_gaps): the validation block may hold missing readings too; it is scored under
         the detector's rules (from_calibration(calib_gaps=True)) and the complete ticks the table was computed from
-        join the line and `stream_result` ("calib_kept")."""
+        join the line and `stream_result` ("calib_kept").
+        -calib_by_sensor (with -stream_gaps -stream_calib_gaps): every sensor's table row comes from its own real
+        readings (calib="sensor"); the smallest and largest per-sensor count join the line and `stream_result`
+        ("calib_count_min", "calib_count_max"), and with -stream_recal the ring recalibrates per sensor as well."""
+        check_calib_by_sensor(by_sensor, bool(chunk), gaps, calib_gaps)
         w = self.train_config["slide_win"]
         lo, hi = int(val_ticks.min()), int(val_ticks.max())
         normal = self.train_series[:, lo - w:hi + 1].contiguous()
@@ -248,6 +253,8 @@ class Main:
             if not gaps:
                 raise ValueError("-stream_calib_gaps needs -stream_gaps (the detector whose rules the calibration follows)")
             rolling["calib_gaps"] = True
+        if by_sensor:
+            rolling["calib"] = "sensor"
         det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
                                                       top_m=min(3, normal.shape[0]), gaps=gaps, **rolling)
         ticks = self.test_series[:, w:].t().contiguous()
@@ -264,7 +271,12 @@ class Main:
             self.stream_result["missing"] = int(missing_total.sum())
             held = (f"; {self.stream_result['missing']} missing readings held on "
                     f"{self.stream_result['gap_sensors']} sensors")
-        if calib_gaps:
+        if by_sensor:
+            lo_c, hi_c = torch.stack([det.calib_counts.min(), det.calib_counts.max()]).tolist()
+            self.stream_result["calib_kept"] = det.calib_kept
+            self.stream_result["calib_count_min"], self.stream_result["calib_count_max"] = int(lo_c), int(hi_c)
+            held += f"; calibrated per sensor on {int(lo_c)} to {int(hi_c)} real validation readings"
+        elif calib_gaps:
             self.stream_result["calib_kept"] = det.calib_kept
             held += f"; calibrated on {det.calib_kept} complete validation ticks"
         if recal:
@@ -272,7 +284,9 @@ class Main:
             self.stream_result["recalibrations"] = det.recals
             self.stream_result["recal_kept"] = det.recal_kept
             held += (f"; {det.recals} recalibrations from a ring of {recal} ticks"
-                     + (f", the last from {det.recal_kept} kept ticks" if det.recals else ""))
+                     + (f", the last from {det.recal_kept} kept ticks" if det.recals and not by_sensor else "")
+                     + (f", the last from at least {det.recal_kept} real readings per sensor"
+                        if det.recal_kept and by_sensor else ""))
         first = ", ".join(str(int(t) + w) for t in self.stream_result["log_ticks"][:show])
         print(f"stream: {scored} ticks in pushes of {chunk}, threshold {self.stream_result['threshold']:.6g} from "
               f"{normal.shape[1] - w} validation ticks: {alarms} alarm ticks" + held
@@ -369,7 +383,18 @@ def build_parser():
                         default=0)
     parser.add_argument("-stream_recal_every", help="with -stream_recal: rewrite the median / IQR table from the ring "
                         "every E replayed ticks (alarm ticks excluded)", type=int, default=0)
+    parser.add_argument("-calib_by_sensor", help="with -stream -stream_gaps -stream_calib_gaps: calibrate (and, with "
+                        "-stream_recal, recalibrate) every sensor on its own real readings, not on complete ticks only",
+                        action="store_true")
     return parser
+
+
+def check_calib_by_sensor(by_sensor: bool, stream: bool, stream_gaps: bool, stream_calib_gaps: bool) -> None:
+    """-calib_by_sensor chooses how the streaming detector's calibration treats missing readings, so it has a meaning
+    only where that calibration sees them: with -stream C -stream_gaps -stream_calib_gaps.  Refused by name otherwise."""
+    if by_sensor and not (stream and stream_gaps and stream_calib_gaps):
+        raise ValueError("-calib_by_sensor needs -stream C -stream_gaps -stream_calib_gaps: it calibrates every sensor "
+                         "on its own real readings of a validation block that has missing ones")
 
 
 def check_train_gaps(train_gaps: bool, hip_graph: bool) -> None:
@@ -383,6 +408,7 @@ def check_train_gaps(train_gaps: bool, hip_graph: bool) -> None:
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_train_gaps(args.train_gaps, not args.no_hip_graph)
+    check_calib_by_sensor(args.calib_by_sensor, bool(args.stream), args.stream_gaps, args.stream_calib_gaps)
     random.seed(args.random_seed)                      # main.py:221-228
     np.random.seed(args.random_seed)
     torch.manual_seed(args.random_seed)
@@ -398,7 +424,7 @@ def main(argv=None):
                   "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
                   "localise": args.localise, "stream": args.stream,
                   "stream_gaps": args.stream_gaps, "stream_calib_gaps": args.stream_calib_gaps, "stream_recal": args.stream_recal,
-                  "stream_recal_every": args.stream_recal_every}
+                  "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor}
     return Main(train_config, env_config, debug=False).run()
 
 

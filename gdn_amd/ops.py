@@ -637,19 +637,26 @@ def score_workspace(t: int, n: int, device) -> torch.Tensor:
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
 
 
-def score_keys(pred, gt, pitch: int, out: torch.Tensor | None = None, keep=None) -> torch.Tensor:
+def score_keys(pred, gt, pitch: int, out: torch.Tensor | None = None, keep=None, valid=None) -> torch.Tensor:
     """keys[n, pitch] float64 = |pred-gt| transposed (radix keys); slots t..pitch-1 = filler.  With `keep` [t] uint8
-    (gdn_score_keys_keep) the filler is also in all n keys of every tick whose flag is 0."""
+    (gdn_score_keys_keep) the filler is also in all n keys of every tick whose flag is 0; with `valid` [t, n] uint8
+    (gdn_score_keys_valid) in the key of every (tick, sensor) whose byte is 0.  One of the two at the most."""
     pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
     t, n = pred.shape
+    if keep is not None and valid is not None:
+        raise ValueError("score_keys: keep (whole ticks) and valid (single readings) exclude each other")
     if keep is not None:
         keep = _chk(keep, torch.uint8, "keep")
         if keep.numel() != t:
             raise ValueError(f"keep: one flag per tick is needed ({t}), got {keep.numel()}")
+    if valid is not None:
+        valid = _valid_plane(valid, pred.shape, "valid")
     keys = out if out is not None else torch.empty((n, pitch), dtype=torch.float64, device=pred.device)
     if keys.shape != (n, pitch) or keys.dtype != torch.float64 or not keys.is_contiguous():
         raise ValueError("keys buffer must be a contiguous float64 [n, pitch] tensor")
-    if keep is None:
+    if valid is not None:
+        _lib.call("gdn_score_keys_valid", _ptr(pred), _ptr(gt), _ptr(valid), t, n, pitch, _ptr(keys), _stream())
+    elif keep is None:
         _lib.call("gdn_score_keys", _ptr(pred), _ptr(gt), t, n, pitch, _ptr(keys), _stream())
     else:
         _lib.call("gdn_score_keys_keep", _ptr(pred), _ptr(gt), _ptr(keep), t, n, pitch, _ptr(keys), _stream())
@@ -683,6 +690,48 @@ def score_select_paths(keys, blocks: int, n: int, pitch: int, total: int):
     path = torch.full((n,), -1, dtype=torch.int32, device=keys.device)
     _lib.call("gdn_score_select_paths", _ptr(keys), blocks, n, pitch, total, _ptr(ws), _ptr(out), _ptr(path), _stream())
     return out, path
+
+
+def score_key_counts(keys, blocks: int, n: int, pitch: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """counts[n] int32: per sensor, the slots of keys[blocks, n, pitch] that do not hold the filler
+    (gdn_score_key_counts).  `out` may be a preallocated int32 [n] buffer."""
+    keys = _chk(keys, torch.float64, "keys")
+    if keys.numel() != blocks * n * pitch:
+        raise ValueError(f"keys: expected {blocks} x {n} x {pitch} slots, got {keys.numel()}")
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=keys.device)
+    out = _chk(out, torch.int32, "counts")
+    if out.numel() != n:
+        raise ValueError(f"counts: one entry per sensor is needed ({n}), got {out.numel()}")
+    _lib.call("gdn_score_key_counts", _ptr(keys), blocks, n, pitch, _ptr(out), _stream())
+    return out
+
+
+def score_select_counts(keys, blocks: int, n: int, pitch: int, counts, min_count: int = 1,
+                        ws: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                        path: torch.Tensor | None = None) -> torch.Tensor:
+    """score_select where sensor s has counts[s] real keys (int32 [n] on the device; gdn_score_select_counts): ranks
+    and interpolation weights are formed per sensor on the device, nothing is read back.  The row of a sensor with
+    fewer than max(min_count, 1) real keys is left as it is: pass `out` to decide what such a row holds (a fresh one
+    is filled with NaN).  `path` (int32 [n]) takes the path per sensor as score_select_paths reports it."""
+    keys = _chk(keys, torch.float64, "keys")
+    counts = _chk(counts, torch.int32, "counts")
+    if counts.numel() != n:
+        raise ValueError(f"counts: one entry per sensor is needed ({n}), got {counts.numel()}")
+    if ws is None:
+        ws = score_select_workspace(blocks, n, pitch, keys.device)
+    if out is None:
+        out = torch.full((n, 2), float("nan"), dtype=torch.float64, device=keys.device)
+    out = _chk(out, torch.float64, "med_iqr")
+    if out.numel() != 2 * n:
+        raise ValueError(f"med_iqr: expected [{n}, 2], got {tuple(out.shape)}")
+    if path is not None:
+        path = _chk(path, torch.int32, "path")
+        if path.numel() != n:
+            raise ValueError(f"path: one entry per sensor is needed ({n}), got {path.numel()}")
+    _lib.call("gdn_score_select_counts", _ptr(keys), blocks, n, pitch, _ptr(counts), int(min_count), _ptr(ws),
+              _ptr(out), _ptr(path), _stream())
+    return out
 
 
 def score_quantiles(pred, gt):
@@ -1110,11 +1159,14 @@ def stream_calib_ring(n: int, R: int, device):
 
 
 def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_alarms: bool = True,
-                       count: int | None = None, valid=None):
+                       count: int | None = None, valid=None, by_sensor: bool = False):
     """Row b < count of the push -> slot (state.ticks + b) mod R of the calibration ring: its keys |pred - chunk| and
     keep = 1, or the filler and keep = 0 when `exclude_alarms` and alarm[b] != 0.  After stream_score, before
     stream_advance.  Writes the ring only.  With `valid` (stream_fill's plane of the filled `chunk`;
-    gdn_stream_calib_write_gaps) a tick with a missing reading in any sensor is not kept either."""
+    gdn_stream_calib_write_gaps) a tick with a missing reading in any sensor is not kept either; with `by_sensor` as
+    well (gdn_stream_calib_write_sensor) such a tick is kept and only the keys of its missing readings are the filler."""
+    if by_sensor and valid is None:
+        raise ValueError("stream_calib_write: by_sensor needs the validity plane `valid`")
     chunk, c, n, count = _stream_dims(state, chunk, count, 1)
     _stream_buf(pred, torch.float32, c * n, "pred")
     _stream_buf(alarm, torch.int32, c, "alarm")
@@ -1128,5 +1180,6 @@ def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_
         _lib.call("gdn_stream_calib_write", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), *tail)
     else:
         _stream_buf(valid, torch.uint8, c * n, "valid")
-        _lib.call("gdn_stream_calib_write_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), *tail)
+        name = "gdn_stream_calib_write_sensor" if by_sensor else "gdn_stream_calib_write_gaps"
+        _lib.call(name, _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), *tail)
     return ring_keys, ring_keep

@@ -895,6 +895,42 @@ int gdn_stream_calib_write_gaps(const void* state, const float* pred, const floa
                                 const uint8_t* valid, int c, int count, int n, int R, int exclude_alarms,
                                 double* ring_keys, uint8_t* ring_keep, void* stream);
 
+/* Calibration on each sensor's own readings (opt-in; additive entry points, the ABI version does not move).  The two
+ * blocks above keep a tick for the median / IQR table only when all n sensors reported, so that every sensor has one
+ * `total`; with many sensors hardly any tick is complete.  Here sensor s's row comes from sensor s's own real readings:
+ * the filler sits in single keys, every sensor has its own count, and the select forms ranks, interpolation weights
+ * and the median rule per sensor on the device.
+ *   gdn_score_keys_valid   gdn_score_keys with valid [t, n] uint8: key (s, tick) is the filler wherever
+ *                          valid[tick, s] == 0, and in slots t .. pitch - 1.  With every reading valid it writes the
+ *                          bits of gdn_score_keys.  valid == NULL: GDN_ERR_ARG.
+ *   gdn_score_key_counts   counts[s] (int32, device) = slots of sensor s in keys[blocks, n, pitch] that do not hold the
+ *                          filler.  One launch, integer adds only, no workgroup waits on another.
+ *   gdn_score_select_counts
+ *                          gdn_score_select where sensor s has counts[s] real keys (device data: nothing is read back).
+ *                          counts[s] must be the number of non-filler slots of sensor s.  The ranks, the two gammas and
+ *                          the median rule are those gdn_score_select forms on the host from `total`, computed with the
+ *                          same float64 operations per sensor, on every route (single slice, one workgroup with its
+ *                          brackets, digit passes; GDN_SELECT_MULTI / GDN_SELECT_BRACKET act as they do there): with
+ *                          every count equal to T it writes the bits of gdn_score_select(total = T).  A sensor with
+ *                          counts[s] < min_count or counts[s] < 1 keeps its med_iqr row as it is.  path may be NULL;
+ *                          where given, a sensor that keeps its row on the one-workgroup route keeps its path entry
+ *                          too.  Workspace: gdn_score_select_workspace_bytes.  Argument rules of gdn_score_select;
+ *                          counts == NULL: GDN_ERR_ARG.
+ *   gdn_stream_calib_write_sensor
+ *                          gdn_stream_calib_write_gaps' slots and order.  A tick excluded by its alarm writes the
+ *                          filler into all n keys and keep = 0; any other tick writes keep = 1, sensor i's key where
+ *                          valid[b, i] == 1 and the filler where it is missing.  One launch, no atomics.
+ * The table of a ring: gdn_score_key_counts(ring_keys, 1, n, R, counts), then
+ * gdn_score_select_counts(ring_keys, 1, n, R, counts, min_count, workspace, med_iqr, NULL).                         */
+int gdn_score_keys_valid(const float* pred, const float* gt, const uint8_t* valid, int t, int n, int pitch,
+                         double* keys, void* stream);
+int gdn_score_key_counts(const double* keys, int blocks, int n, int pitch, int32_t* counts, void* stream);
+int gdn_score_select_counts(const double* keys, int blocks, int n, int pitch, const int32_t* counts, int min_count,
+                            double* workspace, double* med_iqr, int* path, void* stream);
+int gdn_stream_calib_write_sensor(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                                  const uint8_t* valid, int c, int count, int n, int R, int exclude_alarms,
+                                  double* ring_keys, uint8_t* ring_keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
