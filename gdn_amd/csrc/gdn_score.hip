@@ -15,7 +15,8 @@ struct SelectArgs {
   double gamma[2];   // interpolation weights of the 25th / 75th percentile (numpy 'linear')
   int median_pair;   // 1: t even, median = mean of two middle values
   int total;         // real keys per sensor
-  int bracket;       // 1: the one-workgroup flat select first tries the sample brackets (select_onewg_kernel)
+  int bracket;       // the one-workgroup flat select first tries the sample brackets (select_onewg_kernel): 0 no,
+                     // 1 the three-interval tier only, 2 the one-span tier in front of it
 };
 
 // Ranks, interpolation weights and median rule of a sensor with t >= 1 real keys.  ONE function for the host
@@ -256,6 +257,49 @@ __device__ __forceinline__ void locate_bin512(const unsigned int* h, int left0, 
       }
     }
     *code = code0 + (unsigned int)(8 * lane + bin);
+    *nrem = left;
+  }
+}
+
+// the same over the 2048 bins of the one-span tier (32 per lane): the lane that holds position left0 first walks its
+// eight 4-bin groups, then the four bins of the group (one more LDS read); code = the bin, nothing written outside
+__device__ __forceinline__ void locate_bin2048(const unsigned int* h, int left0, int lane, unsigned int* code,
+                                               int* nrem) {
+  int g[8];
+  int mine = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint4 a = *reinterpret_cast<const uint4*>(h + 32 * lane + 4 * j);
+    g[j] = (int)(a.x + a.y + a.z + a.w);
+    mine += g[j];
+  }
+  int incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(incl, d);
+    if (lane >= d) incl += up;
+  }
+  const int excl = incl - mine;
+  if (left0 >= excl && left0 < incl) {
+    int left = left0 - excl, grp = 0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      if (grp == j && left >= g[j]) {
+        left -= g[j];
+        grp = j + 1;
+      }
+    }
+    const uint4 a = *reinterpret_cast<const uint4*>(h + 32 * lane + 4 * grp);
+    const int c[4] = {(int)a.x, (int)a.y, (int)a.z, (int)a.w};
+    int bin = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (bin == j && left >= c[j]) {
+        left -= c[j];
+        bin = j + 1;
+      }
+    }
+    *code = (unsigned int)(32 * lane + 4 * grp + bin);
     *nrem = left;
   }
 }
@@ -543,6 +587,28 @@ constexpr int ONE_CAP2 = 1024;  // 24-bit-prefix survivors finished by counting
 constexpr int BR_S = ONE_NT;      // sample size: one key per thread
 constexpr float BR_C = 2.62f;     // margin in units of sqrt(m) sample positions (see above)
 constexpr unsigned int BR_NONE = 0xffffu;   // bin code of a key outside every interval
+//
+// ONE-SPAN TIER, in front of the three intervals (rows like the bench's: the brackets lie close together): ONE
+// histogram of SPAN_BINS bins over the single hi-word span from the q25 bracket's lower edge to the q75 bracket's upper
+// edge.  Per key one subtract, one unsigned compare, one shift, one LDS atomic and ONE below-counter instead of three
+// interval tests and three counters; the staging pass is three range tests on the hi word instead of a second
+// code_of and six compares.  The tiers run in this order in the same launch, every decision uniform: the one-span
+// tier is chosen from the sorted sample alone (the rule stands where it is evaluated) and falls through to the
+// three-interval tier when the rule rejects it, a rank lies outside the span or more than ONE_CAP2 keys share the
+// ranks' bins; the three-interval tier falls back to the digit passes as before.  SelectArgs::bracket: 0 digit passes
+// only, 1 the three-interval tier only (GDN_SELECT_SPAN=0), 2 both tiers.
+//
+// LDS MAP of select_onewg_kernel (static, no larger than before the one-span tier: its words alias `stage`):
+//   hist[6][256]   digit passes: a 256-bin histogram per rank | bracket path: three intervals x 512 bins
+//   sbuf[2048]     bracket path: the sample, two exchange buffers of its sort; the sorted sample ends in the first
+//   stage[8192]    digit passes: full keys of the 16-bit-prefix survivors (written from pass 1 on) | bracket path,
+//                  as 32-bit words: [0, SPAN_BINS) the one-span histogram, [SPAN_BELOW] keys below the span,
+//                  [SPAN_CODE + q] bin of rank q -- idle there until a fallback, which rewrites it
+//   stage2[1024]   full keys of the candidates of the counting finisher (every path)
+//   sidx[8192]     slot numbers of staged keys; the bracket path keeps the candidates' bins there after the re-read
+constexpr int SPAN_BINS = 2048;
+constexpr int SPAN_BELOW = SPAN_BINS;
+constexpr int SPAN_CODE = SPAN_BINS + 1;
 
 template <bool FLAT, typename ARGS>
 __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl, const ARGS args,
@@ -613,7 +679,8 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
   // survivors (bit u of keep: my key u) first as SLOT NUMBERS in sidx, to be re-read in full by all threads at once
   // (a load inside the per-slot branch would pay one L2 round trip per survivor, serially); one LDS atomic per
   // WAVE: lanes scan their survivor counts, the last lane reserves the range.  Returns the survivors' number.
-  auto stage_slots = [&](unsigned int keep) -> unsigned int {
+  // (Forced inline: with three call sites one instantiation otherwise gets a real call, a stack and scratch.)
+  auto stage_slots = [&](unsigned int keep) __attribute__((always_inline)) -> unsigned int {
     const int mine = __popc(keep);
     int incl = mine;
 #pragma unroll
@@ -664,8 +731,9 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
     __syncthreads();
   };
 #ifdef GDN_SELECT_TIMING
-  long long tick[12], btick[8];
-  int nt = 0, nbt = 0;
+  long long tick[12], btick[6] = {0, 0, 0, 0, 0, 0};   // sort | span pass, span stage | interval pass, stage | finish
+  int nt = 0;
+  int br_tier = 2;           // 0: the one-span tier staged the candidates, 1: it ran and fell through, 2: it did not run
   unsigned int br_n = 0u;
 #endif
   bool bracketed = false;
@@ -673,6 +741,11 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
     if (try_bracket) {
       unsigned int* hflat = &hist[0][0];     // three intervals x 512 bins
       for (int i = tid; i < 3 * 512; i += ONE_NT) hflat[i] = 0u;
+      unsigned int* shist = reinterpret_cast<unsigned int*>(stage);   // the one-span tier's words (see the LDS map)
+      shist[tid] = 0u;
+      shist[tid + ONE_NT] = 0u;
+      if (tid == 0) shist[SPAN_BELOW] = 0u;
+      if (tid < NQ) shist[SPAN_CODE + tid] = ~0u;
       if (tid < 3) br_below[tid] = 0u;
       if (tid < NQ) br_code[tid] = ~0u;
       if (tid == 0) {
@@ -705,7 +778,7 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
       if (v != 0xffffffffu && (tid == BR_S - 1 || sbuf[tid + 1] == 0xffffffffu)) br_m = (unsigned int)(tid + 1);
       __syncthreads();
 #ifdef GDN_SELECT_TIMING
-      btick[nbt++] = wall_clock64();
+      btick[0] = wall_clock64();
 #endif
     }
   }
@@ -750,7 +823,7 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
                            S1 = W1 < 512u ? 0u : 23u - (unsigned int)__clz((int)W1),
                            S2 = W2 < 512u ? 0u : 23u - (unsigned int)__clz((int)W2);
         // interval * 512 + bin of a hi word, BR_NONE outside every interval (the filler and unused intervals included)
-        auto code_of = [&](unsigned int h) -> unsigned int {
+        auto code_of = [&](unsigned int h) __attribute__((always_inline)) -> unsigned int {
           const unsigned int d0 = h - L0, d1 = h - L1, d2 = h - L2;
           unsigned int c = BR_NONE;
           if (d2 <= W2) c = 1024u + (d2 >> S2);
@@ -758,73 +831,156 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
           if (d0 <= W0) c = d0 >> S0;
           return c;
         };
-        unsigned int b01 = 0u, b2 = 0u;        // keys below interval 0 | below interval 1 << 16, below interval 2
-#pragma unroll
-        for (int u = 0; u < ONE_FK; ++u) {
-          const unsigned int h = khi[u];       // the filler (all ones) is below nothing and inside nothing
-          b01 += (h < L0 ? 1u : 0u) + (h < L1 ? 0x10000u : 0u);
-          b2 += h < L2 ? 1u : 0u;
-          const unsigned int c = code_of(h);
-          if (c != BR_NONE) atomicAdd(&hflat[c], 1u);
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {    // <= 2048 per wave and counter: the packed halves do not carry
-          b01 += __shfl_xor(b01, d);
-          b2 += __shfl_xor(b2, d);
-        }
-        if (lane == 0) {
-          atomicAdd(&br_below[0], b01 & 0xffffu);
-          atomicAdd(&br_below[1], b01 >> 16);
-          atomicAdd(&br_below[2], b2);
-        }
-        __syncthreads();
-#ifdef GDN_SELECT_TIMING
-        btick[nbt++] = wall_clock64();
-#endif
-        if (wv < NQ) {                         // wave q: rank q's bin inside its interval
-          const int iv = wv < 2 ? iv_med : (wv < 4 ? 0 : iv_q75);
-          locate_bin512(hflat + 512 * iv, sa.rank[wv] - (int)br_below[iv], 512u * (unsigned int)iv, lane,
-                        &br_code[wv], &rem[wv]);
-        }
-        __syncthreads();
-        unsigned int code[NQ];
-        bool inside = true;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          code[q] = __builtin_amdgcn_readfirstlane(br_code[q]);
-          inside = inside && code[q] != ~0u;   // nothing written: the rank is outside its bracket
-        }
-        if (inside) {
-          unsigned int keep = 0u;
+        // ONE-SPAN TIER.  One monotone histogram of SPAN_BINS bins over [LS, LS + WS]: from the lower edge of the q25
+        // bracket to the upper edge of the q75 bracket.  Chosen from the sorted sample alone: the span's bins must be
+        // at most 4 x as wide as the bins of the finest interval (SS <= min S + 2) -- a bin of the three-interval
+        // tier holds ~15 keys, so six span bins stay far below ONE_CAP2 where the key density between the brackets
+        // is like that inside them; rows whose brackets lie far apart (a level shift, two clusters) fail the rule
+        // and do not pay the pass.  A span of one hi word (WS == 0) cannot separate anything.
+        const int n_iv = iv_q75 + 1;                                     // intervals in use
+        unsigned int Smin = S0;
+        if (n_iv > 1) Smin = min(Smin, S1);
+        if (n_iv > 2) Smin = min(Smin, S2);
+        const unsigned int LS = L0;
+        const unsigned int WS = __builtin_amdgcn_readfirstlane(hi[2] - lo[0]);
+        const unsigned int SS = WS < (unsigned int)SPAN_BINS ? 0u : 21u - (unsigned int)__clz((int)WS);   // WS >> SS < 2048
+        const bool use_span = sa.bracket >= 2 && WS != 0u && SS <= Smin + 2u;   // uniform
+        unsigned int code[NQ];                 // the ranks' bins (of whichever tier staged the candidates)
+        unsigned int n_cand = 0u;
+        bool have = false, by_span = false;    // candidates staged in sidx, at most ONE_CAP2 of them
+        if (use_span) {
+          unsigned int* shist = reinterpret_cast<unsigned int*>(stage);
+          unsigned int below = 0u;
+          unsigned int ssv = SS, one = 1u;     // in vector registers: as scalars they are re-read from a spill lane per key
+          asm volatile("" : "+v"(ssv), "+v"(one));
 #pragma unroll
           for (int u = 0; u < ONE_FK; ++u) {
-            const unsigned int c = code_of(khi[u]);
-            bool any = false;
+            const unsigned int h = khi[u];     // the filler: h - LS >= 0x80000000 > WS
+            const unsigned int d = h - LS;
+            below += h < LS ? 1u : 0u;
+            if (d <= WS) atomicAdd(&shist[d >> ssv], one);
+          }
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) any |= c == code[q];
-            keep |= any ? (1u << u) : 0u;
-          }
-          const unsigned int n_cand = stage_slots(keep);
+          for (int d = 32; d >= 1; d >>= 1) below += __shfl_xor(below, d);
+          if (lane == 0) atomicAdd(&shist[SPAN_BELOW], below);
+          __syncthreads();
 #ifdef GDN_SELECT_TIMING
-          btick[nbt++] = wall_clock64();
-          br_n = n_cand;
+          btick[1] = wall_clock64();
 #endif
-          if (n_cand <= (unsigned int)ONE_CAP2) {
-            if ((unsigned int)tid < n_cand) {
-              const unsigned long long k = key_slot(sidx[tid]);
-              stage2[tid] = k;
-              sidx[tid] = (unsigned short)code_of((unsigned int)(k >> 32));   // the slot number is consumed
-            }
-            __syncthreads();
-            finish_by_counting(stage2, n_cand, [&](unsigned int j) { return (unsigned int)sidx[j]; },
-                               [&](int q) { return code[q]; });
-            bracketed = true;
+          if (wv < NQ) locate_bin2048(shist, sa.rank[wv] - (int)shist[SPAN_BELOW], lane, &shist[SPAN_CODE + wv], &rem[wv]);
+          __syncthreads();
+          bool inside = true;
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) {
+            code[q] = __builtin_amdgcn_readfirstlane(shist[SPAN_CODE + q]);
+            inside = inside && code[q] != ~0u; // nothing written: the rank is outside the span
           }
+          if (inside) {
+            // the six ranks are three adjacent pairs and the bins between a pair's two bins are empty: one range
+            // test per pair, on the hi word itself (bins c_lo..c_hi are the hi words LS + (c_lo << SS) ..
+            // LS + min(((c_hi + 1) << SS) - 1, WS): no key past the span, none was counted)
+            unsigned int r_lo[3], r_w[3];
+            const int first[3] = {2, 0, 4};
+#pragma unroll
+            for (int g = 0; g < 3; ++g) {
+              const unsigned int d_lo = code[first[g]] << SS, d_hi = min(((code[first[g] + 1] + 1u) << SS) - 1u, WS);
+              r_lo[g] = LS + d_lo;
+              r_w[g] = d_hi - d_lo;
+            }
+            unsigned int keep = 0u;
+#pragma unroll
+            for (int u = 0; u < ONE_FK; ++u) {
+              const unsigned int h = khi[u];
+              const bool any = (h - r_lo[0] <= r_w[0]) | (h - r_lo[1] <= r_w[1]) | (h - r_lo[2] <= r_w[2]);
+              keep |= any ? (1u << u) : 0u;
+            }
+            asm volatile("" : "+v"(keep));     // ONE register of bits: 32 compare masks kept as scalar pairs spill
+            n_cand = stage_slots(keep);
+            have = by_span = n_cand <= (unsigned int)ONE_CAP2;
+            if (!have) {                       // (uniform) every thread has read n_stage: start the next tier at 0
+              __syncthreads();
+              if (tid == 0) n_stage = 0u;
+            }
+          }
+#ifdef GDN_SELECT_TIMING
+          btick[2] = wall_clock64();
+          br_tier = have ? 0 : 1;
+#endif
+        }
+        if (!have) {
+          // THREE-INTERVAL TIER
+          unsigned int b01 = 0u, b2 = 0u;      // keys below interval 0 | below interval 1 << 16, below interval 2
+#pragma unroll
+          for (int u = 0; u < ONE_FK; ++u) {
+            const unsigned int h = khi[u];     // the filler (all ones) is below nothing and inside nothing
+            b01 += (h < L0 ? 1u : 0u) + (h < L1 ? 0x10000u : 0u);
+            b2 += h < L2 ? 1u : 0u;
+            const unsigned int c = code_of(h);
+            if (c != BR_NONE) atomicAdd(&hflat[c], 1u);
+          }
+#pragma unroll
+          for (int d = 32; d >= 1; d >>= 1) {  // <= 2048 per wave and counter: the packed halves do not carry
+            b01 += __shfl_xor(b01, d);
+            b2 += __shfl_xor(b2, d);
+          }
+          if (lane == 0) {
+            atomicAdd(&br_below[0], b01 & 0xffffu);
+            atomicAdd(&br_below[1], b01 >> 16);
+            atomicAdd(&br_below[2], b2);
+          }
+          __syncthreads();
+#ifdef GDN_SELECT_TIMING
+          btick[3] = wall_clock64();
+#endif
+          if (wv < NQ) {                       // wave q: rank q's bin inside its interval
+            const int iv = wv < 2 ? iv_med : (wv < 4 ? 0 : iv_q75);
+            locate_bin512(hflat + 512 * iv, sa.rank[wv] - (int)br_below[iv], 512u * (unsigned int)iv, lane,
+                          &br_code[wv], &rem[wv]);
+          }
+          __syncthreads();
+          bool inside = true;
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) {
+            code[q] = __builtin_amdgcn_readfirstlane(br_code[q]);
+            inside = inside && code[q] != ~0u; // nothing written: the rank is outside its bracket
+          }
+          if (inside) {
+            unsigned int keep = 0u;
+#pragma unroll
+            for (int u = 0; u < ONE_FK; ++u) {
+              const unsigned int c = code_of(khi[u]);
+              bool any = false;
+#pragma unroll
+              for (int q = 0; q < NQ; ++q) any |= c == code[q];
+              keep |= any ? (1u << u) : 0u;
+            }
+            n_cand = stage_slots(keep);
+            have = n_cand <= (unsigned int)ONE_CAP2;
+          }
+#ifdef GDN_SELECT_TIMING
+          btick[4] = wall_clock64();
+#endif
+        }
+#ifdef GDN_SELECT_TIMING
+        br_n = n_cand;
+#endif
+        if (have) {
+          // both tiers: the candidates re-read in full, their bin kept beside them, every rank finished by counting
+          if ((unsigned int)tid < n_cand) {
+            const unsigned long long k = key_slot(sidx[tid]);
+            const unsigned int hk = (unsigned int)(k >> 32);
+            stage2[tid] = k;
+            sidx[tid] = (unsigned short)(by_span ? (hk - LS) >> SS : code_of(hk));   // the slot number is consumed
+          }
+          __syncthreads();
+          finish_by_counting(stage2, n_cand, [&](unsigned int j) { return (unsigned int)sidx[j]; },
+                             [&](int q) { return code[q]; });
+          bracketed = true;
         }
       }
       if (!bracketed) __syncthreads();         // the counters read above are reset below
 #ifdef GDN_SELECT_TIMING
-      btick[nbt++] = wall_clock64();
+      btick[5] = wall_clock64();
 #endif
     }
   }
@@ -1010,10 +1166,15 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
 #endif
   }
 #ifdef GDN_SELECT_TIMING
-  if (tid == 0 && s == 1 && bracketed)
+  if (tid == 0 && s == 1 && bracketed && br_tier == 0)
     printf("onewg bracket ticks(10ns): sample sort (under the row load) %lld count+histogram %lld locate+stage %lld "
-           "re-read+finish %lld candidates %u\n",
-           btick[0] - tick_start, btick[1] - btick[0], btick[2] - btick[1], btick[3] - btick[2], br_n);
+           "re-read+finish %lld candidates %u tier one-span\n",
+           btick[0] - tick_start, btick[1] - btick[0], btick[2] - btick[1], btick[5] - btick[2], br_n);
+  else if (tid == 0 && s == 1 && bracketed)
+    printf("onewg bracket ticks(10ns): sample sort (under the row load) %lld count+histogram %lld locate+stage %lld "
+           "re-read+finish %lld candidates %u tier three-interval (one-span before it: %lld)\n",
+           btick[0] - tick_start, btick[3] - (br_tier == 1 ? btick[2] : btick[0]), btick[4] - btick[3],
+           btick[5] - btick[4], br_n, br_tier == 1 ? btick[2] - btick[0] : 0ll);
   else if (tid == 0 && s == 1)
     printf("onewg ticks(10ns): load %lld p0 %lld p1+compact %lld p2+finish %lld (passes run %d) survivors %u / %u\n",
            tick[0] - tick_start, tick[1] - tick[0], tick[2] - tick[1], tick[3] - tick[2], nt - 1, n_keep, n_stage2);
@@ -1268,20 +1429,22 @@ __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
 
 namespace {
 
-// diagnostic knob: GDN_SELECT_BRACKET=0 keeps the one-workgroup select on its digit passes (comparisons)
-bool bracket_enabled() {
+// diagnostic knobs: GDN_SELECT_BRACKET=0 keeps the one-workgroup select on its digit passes, GDN_SELECT_SPAN=0 keeps
+// its bracket path on the three-interval tier (comparisons).  The value of SelectArgs::bracket / CountArgs::bracket.
+int bracket_mode() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("GDN_SELECT_BRACKET");
-    v = (e && e[0] == '0') ? 0 : 1;
+    const char* sp = getenv("GDN_SELECT_SPAN");
+    v = (e && e[0] == '0') ? 0 : ((sp && sp[0] == '0') ? 1 : 2);
   }
-  return v == 1;
+  return v;
 }
 
 SelectArgs make_select_args(long long t) {
   SelectArgs sa;
   fill_select_args(sa, t);
-  sa.bracket = bracket_enabled() ? 1 : 0;
+  sa.bracket = bracket_mode();
   return sa;
 }
 
@@ -1400,7 +1563,7 @@ extern "C" int gdn_score_select_counts(const double* keys, int blocks, int n, in
   CountArgs ca;
   ca.counts = counts;
   ca.min_count = min_count;
-  ca.bracket = bracket_enabled() ? 1 : 0;
+  ca.bracket = bracket_mode();
   return run_select(keys, blocks, n, pitch, ca, workspace, med_iqr, path, (hipStream_t)stream);
 }
 
