@@ -59,6 +59,61 @@ typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// [r18] the three parts of the window loop's VALU trim, each switchable for same-box A/B builds
+// (tools/_diag/build_variant.sh ... -DGDN_TRIM_PACK=0): all on in the product
+#ifndef GDN_TRIM_SPLIT
+#define GDN_TRIM_SPLIT 1    // Fmt<FMT_F16>::split2: three instructions per pair of values
+#endif
+#ifndef GDN_TRIM_RELU
+#define GDN_TRIM_RELU 1     // relu_acc: one instruction on an MFMA result
+#endif
+#ifndef GDN_TRIM_PACK
+#define GDN_TRIM_PACK 1     // Pk2: v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 on register pairs
+#endif
+
+// Elementwise fp32 arithmetic on PAIRS of values: one v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 per pair (a
+// broadcast operand costs nothing: op_sel_hi), written out as vector operations as in axpy_pack of gdn_forward.hip —
+// the vectoriser does not pack these loops by itself.  Each half rounds exactly like the scalar instruction, and the
+// window loop uses them only where no ORDER of additions changes (never for the softmax sum / max, the head's
+// `part`, the butterfly).  PACK = false: the same operations one value at a time (DCfg::PACK).
+template <bool PACK>
+struct Pk2 {
+  static __device__ __forceinline__ f32x2 mul(f32x2 a, f32x2 b) {
+    if constexpr (PACK) return a * b;
+    return f32x2{a[0] * b[0], a[1] * b[1]};
+  }
+  static __device__ __forceinline__ f32x2 mul(f32x2 a, float b) { return mul(a, f32x2{b, b}); }
+  static __device__ __forceinline__ f32x2 add(f32x2 a, f32x2 b) {
+    if constexpr (PACK) return a + b;
+    return f32x2{a[0] + b[0], a[1] + b[1]};
+  }
+  static __device__ __forceinline__ f32x2 add(f32x2 a, float b) { return add(a, f32x2{b, b}); }
+  static __device__ __forceinline__ f32x2 sub(f32x2 a, float b) {
+    if constexpr (PACK) return a - f32x2{b, b};
+    return f32x2{a[0] - b, a[1] - b};
+  }
+  static __device__ __forceinline__ f32x2 fma(f32x2 a, f32x2 b, f32x2 c) {
+    if constexpr (PACK) return __builtin_elementwise_fma(a, b, c);
+    return f32x2{__builtin_fmaf(a[0], b[0], c[0]), __builtin_fmaf(a[1], b[1], c[1])};
+  }
+};
+
+// ReLU of a matrix-core accumulator register.  fmaxf(acc, 0) costs TWO instructions there: IEEE maxnum must quiet a
+// signalling NaN, the compiler cannot prove that an MFMA result is none and puts a canonicalising v_max_f32 v, v, v in
+// front.  IEEE maximum needs no such step: ONE v_maximum3_f32 v, v, 0, 0 on gfx950.  It differs from fmaxf for a NaN
+// accumulator only, which it hands on as NaN where fmaxf returned 0 (and max(-0, +0) is +0 for certain): a window
+// with a NaN input is flagged by the range guard of planned launches and recomputed by the row-gather kernel, and an
+// unguarded launch on such a window now yields NaN outputs for the targets the NaN reaches instead of finite numbers
+// that meant nothing.
+__device__ __forceinline__ float relu_acc(float v) {
+#if GDN_TRIM_RELU
+  return __builtin_elementwise_maximum(v, 0.f);
+#else
+  return fmaxf(v, 0.f);
+#endif
+}
 
 enum { FMT_F16 = 0, FMT_BF16 = 1 };
 #define GDN_LOG2E 1.44269504088896340736f
@@ -89,6 +144,10 @@ struct Fmt<FMT_F16> {
   // different "hi" values, hi + lo missed the value by a whole f16 ulp (2^-11 relative) and the forward was off by
   // 1.2e-6 instead of 3e-8 (4 of the 8192 lin' operand halves of a plan; found in round 3 by comparing plans
   // built by two compilations of the same source, tools/_diag/plan_words_probe.py).
+  // What pk pins is its own by-value COPY of each argument: a caller that goes on using the value (res0 / res1 do)
+  // pays a v_mov per value for it, and a residual routed through pk again is rounded twice (v_fma_mix_f32, then
+  // v_cvt_f16_f32).  Fine for a lone conversion (a store of two values) and for code outside the window loop; a
+  // SPLIT inside it goes through split2 below, which pins in place and leaves the residual un-pinned.
   static __device__ __forceinline__ unsigned pk(float a, float b) {
     asm("" : "+v"(a));
     asm("" : "+v"(b));
@@ -111,6 +170,37 @@ struct Fmt<FMT_F16> {
   static __device__ __forceinline__ float res1(unsigned p, float x) {
     return __builtin_fmaf((float)__builtin_bit_cast(h2, p)[1], neg_one(), x);
   }
+  // Both terms of a pair of values in THREE instructions (v_cvt_pk_f16_f32, v_fma_mixlo_f16, v_fma_mixhi_f16), where
+  // pk(a, b) + pk(res0, res1) above compile to ten for a pair whose values the caller computed itself ([r18]: a v_mov
+  // per value because pk pins a by-value COPY while the residual still needs the value, and the residual rounded
+  // twice, v_fma_mix_f32 + v_cvt_f16_f32).  Same bits.  Four EMPTY asm statements, nothing executes in any of them:
+  //   a, b  pinned IN PLACE, in the caller's variables: the conversion and the residual both read the one materialised
+  //         fp32 value (a product in front of it cannot be contracted into either: the round-3 bug at pk), no copy;
+  //   p     the converted pair as ONE packed register: without the pin the residual re-converts each value on its own
+  //         (two v_cvt_f16_f32 besides the v_cvt_pk_f16_f32) instead of reading the halves of p through op_sel;
+  //   l0    the first lo half: without it the vectoriser pairs the two residuals into v_cvt_f32_f16 x 2 +
+  //         v_pk_fma_f32 + v_cvt_pk_f16_f32.
+  // The RESIDUAL fma(float(hi), -1, a) itself is not pinned and needs none: it is exact in fp32 (hi is a rounded to 11
+  // bits), so converting the exact value once (v_fma_mixlo/hi_f16) or the fp32-rounded value (v_fma_mix_f32, then
+  // v_cvt_f16_f32) is one and the same rounding — there is no second "hi" to disagree with.
+  static __device__ __forceinline__ void split2(float& a, float& b, unsigned& hi, unsigned& lo) {
+#if !GDN_TRIM_SPLIT
+    hi = pk(a, b);
+    lo = pk(res0(hi, a), res1(hi, b));
+    return;
+#endif
+    asm("" : "+v"(a));
+    asm("" : "+v"(b));
+    h2 p = {(_Float16)a, (_Float16)b};
+    asm("" : "+v"(p));
+    const float m1 = neg_one();
+    _Float16 l0 = (_Float16)__builtin_fmaf((float)p[0], m1, a);
+    const _Float16 l1 = (_Float16)__builtin_fmaf((float)p[1], m1, b);
+    asm("" : "+v"(l0));
+    const h2 l = {l0, l1};
+    hi = __builtin_bit_cast(unsigned, p);
+    lo = __builtin_bit_cast(unsigned, l);
+  }
   static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
   }
@@ -126,6 +216,11 @@ struct Fmt<FMT_BF16> {
   }
   static __device__ __forceinline__ float res0(unsigned p, float x) { return x - __uint_as_float(p << 16); }
   static __device__ __forceinline__ float res1(unsigned p, float x) { return x - __uint_as_float(p & 0xffff0000u); }
+  // (the same arithmetic as before [r18]; the pins stay on by-value copies: see DESIGN 3.1 [r18])
+  static __device__ __forceinline__ void split2(float& a, float& b, unsigned& hi, unsigned& lo) {
+    hi = pk(a, b);
+    lo = pk(res0(hi, a), res1(hi, b));
+  }
   static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
   }
@@ -133,11 +228,23 @@ struct Fmt<FMT_BF16> {
 
 // 8 fp32 values -> NTERM operand fragments (element j of the fragment = v[j]); term t+1 holds the
 // rounding residual of terms 0..t
-template <int FMT, int NTERM>
+// (TRIM = false: term by term through pk / res0 / res1 as before [r18]; gdn_dense_project_kernel keeps that form:
+// split2 costs it 2 .. 5 registers, which takes a wave per SIMD from its w <= 16 instantiations)
+template <int FMT, int NTERM, bool TRIM = true>
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&out)[NTERM]) {
   float r[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) r[j] = v[j];
+  if constexpr (NTERM == 2 && TRIM) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned hi, lo;
+      Fmt<FMT>::split2(r[2 * j], r[2 * j + 1], hi, lo);
+      out[0][j] = hi;
+      out[NTERM - 1][j] = lo;
+    }
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < NTERM; ++t)
 #pragma unroll
@@ -212,6 +319,12 @@ struct DCfg {
   // register file (accumulator registers as spill space) at one.
   static constexpr int LDS_UNIT = 1280;
   static constexpr int LDS_ALLOC = (LDS + LDS_UNIT - 1) / LDS_UNIT * LDS_UNIT;
+  // packed fp32 arithmetic in the window loop (Pk2): a v_pk_* operand is an ALIGNED register pair, which costs an
+  // instantiation at its register budget a few registers.  Off for the long-list variants (SL > 16), which take the
+  // whole register file and spill into accumulator registers as it is: with packing they spilled 2 .. 5 more
+  // (DESIGN 3.1 [r18]; no instantiation has scratch either way).  Off for bf16 storage: its kernel sits at its
+  // budget too, gained nothing measurable from packing, and keeps the bits of its softmax split (softmax_split)
+  static constexpr bool PACK = GDN_TRIM_PACK != 0 && SL <= 16 && FMT == FMT_F16;
   static constexpr int WGS = !(DC == 2 && NT >= 3 && SL <= 16 && WK == 1) ? 1
                              : XAGG && 3 * LDS_ALLOC <= 160 * 1024 ? 3 : 2;
 };
@@ -253,10 +366,13 @@ __device__ __forceinline__ u32x4 lds_frag(const char* smem, int byte_off) {
 // Softmax of one target over the 2 x SL list slots of a lane pair (graph_layer.py:106-110 + PyG softmax),
 // in the log2 domain (s_i, s_j carry a factor log2 e; LeakyReLU commutes with a positive scale).  Returns
 // the weights split into two 16-bit terms, packed in slot pairs (and, WANT_ALPHA, the fp32 weights).
-template <int SL, int FMT, bool WANT_ALPHA>
+// The elementwise steps (s_i + s_j, 0.2 v, e - m, e inv) run on slot pairs (Pk2); max, exp2 and the ORDER of the max
+// and sum reductions are what they were.
+template <int SL, int FMT, bool WANT_ALPHA, bool PACK = GDN_TRIM_PACK != 0>
 __device__ __forceinline__ void softmax_split(const char* smem, int si_off, const int (&sjoff)[SL],
                                               unsigned (&ph)[SL / 2], unsigned (&pl)[SL / 2], float (&alpha)[SL]) {
   using F = Fmt<FMT>;
+  using P = Pk2<PACK>;
   const float sti = lds_f32(smem, si_off);
   float e[SL];
 #pragma unroll
@@ -264,25 +380,45 @@ __device__ __forceinline__ void softmax_split(const char* smem, int si_off, cons
   __builtin_amdgcn_sched_barrier(0);
   float m = -3.0e38f;   // keeps pad targets (all slots = sentinel) finite
 #pragma unroll
-  for (int q = 0; q < SL; ++q) {
-    e[q] = leaky(sti + e[q]);
+  for (int q = 0; q < SL; q += 2) {
+    const f32x2 v = P::add(f32x2{e[q], e[q + 1]}, sti);
+    const f32x2 vs = P::mul(v, GDN_NEG_SLOPE);                    // leaky(v) = max(v, 0.2 v)
+    e[q] = fmaxf(v[0], vs[0]);
+    e[q + 1] = fmaxf(v[1], vs[1]);
     m = fmaxf(m, e[q]);
+    m = fmaxf(m, e[q + 1]);
   }
   m = fmaxf(m, dpp_f<GDN_DPP_XOR1>(m));
   float sum = 0.f;
 #pragma unroll
-  for (int q = 0; q < SL; ++q) {
-    e[q] = __builtin_amdgcn_exp2f(e[q] - m);
+  for (int q = 0; q < SL; q += 2) {
+    const f32x2 v = P::sub(f32x2{e[q], e[q + 1]}, m);
+    e[q] = __builtin_amdgcn_exp2f(v[0]);
+    e[q + 1] = __builtin_amdgcn_exp2f(v[1]);
     sum += e[q];
+    sum += e[q + 1];
   }
   sum += dpp_f<GDN_DPP_XOR1>(sum);
   constexpr float ASC = FMT == FMT_F16 ? GDN_F16_ALPHA_SCALE : 1.f;   // inv = ASC / (sum + eps)
   const float inv = __builtin_amdgcn_rcpf(fmaf(sum, 1.f / ASC, GDN_SOFTMAX_EPS / ASC));
 #pragma unroll
   for (int q = 0; q < SL; q += 2) {
-    const float a0 = e[q] * inv, a1 = e[q + 1] * inv;
-    ph[q / 2] = F::pk(a0, a1);
-    pl[q / 2] = F::pk(F::res0(ph[q / 2], a0), F::res1(ph[q / 2], a1));
+    float a0, a1;
+    if constexpr (PACK) {
+      const f32x2 a = P::mul(f32x2{e[q], e[q + 1]}, inv);
+      a0 = a[0];
+      a1 = a[1];
+      F::split2(a0, a1, ph[q / 2], pl[q / 2]);   // (pins a0, a1 where they stand: the products, materialised)
+    } else {
+      // long lists and bf16 storage: this step WORD FOR WORD as before [r18] (DCfg::PACK).  With bf16 terms the
+      // residual a - float(hi) of the un-pinned scalar product is contracted into fma(e, inv, -hi), the residual of
+      // the EXACT product; any other spelling (a product materialised first, a packed product) changes the last
+      // bit of some lo terms and with it the bits of the bf16-storage forward
+      a0 = e[q] * inv;
+      a1 = e[q + 1] * inv;
+      ph[q / 2] = F::pk(a0, a1);
+      pl[q / 2] = F::pk(F::res0(ph[q / 2], a0), F::res1(ph[q / 2], a1));
+    }
     if constexpr (WANT_ALPHA) {
       alpha[q] = a0 * (1.f / ASC);
       alpha[q + 1] = a1 * (1.f / ASC);
@@ -676,6 +812,7 @@ template <int NT, int DC, int WK, int SL, int FMT>
 __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSED_ATTR void gdn_dense_fused_kernel(const DArgs a) {
   using C = DCfg<NT, DC, WK, SL, FMT>;
   using F = Fmt<FMT>;
+  using P = Pk2<C::PACK>;
   extern __shared__ uint4 smem_u4[];
   char* smem = reinterpret_cast<char*>(smem_u4);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -785,7 +922,11 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
       for (int q = 0; q < WK; ++q) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = xv[8 * q + j] * GDN_F16_XT_SCALE;
+        for (int j = 0; j < 8; j += 2) {
+          const f32x2 t = P::mul(f32x2{xv[8 * q + j], xv[8 * q + j + 1]}, GDN_F16_XT_SCALE);
+          v[j] = t[0];
+          v[j + 1] = t[1];
+        }
         u32x4 xf[C::NPX];
         split8<FMT, C::NPX>(v, xf);
 #pragma unroll
@@ -800,9 +941,12 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
       // one (kind, source): 2 XU - 1 exchanges instead of 2 XU x log2(CW).
       float sr[C::XU];
 #pragma unroll
-      for (int u = 0; u < C::XU; ++u) {
-        const float other = WK == 1 ? dpp_f<GDN_DPP_MIRROR>(xv[u]) : __shfl_xor(xv[u], 16);
-        sr[u] = fmaf(other, k.sp, xv[u] * k.sk);
+      for (int u = 0; u < C::XU; u += 2) {
+        const f32x2 other = {WK == 1 ? dpp_f<GDN_DPP_MIRROR>(xv[u]) : __shfl_xor(xv[u], 16),
+                             WK == 1 ? dpp_f<GDN_DPP_MIRROR>(xv[u + 1]) : __shfl_xor(xv[u + 1], 16)};
+        const f32x2 s = P::fma(other, f32x2{k.sp, k.sp}, P::mul(f32x2{xv[u], xv[u + 1]}, k.sk));
+        sr[u] = s[0];
+        sr[u + 1] = s[1];
       }
       if constexpr (WK == 2) halve_sources<8, GDN_DPP_MIRROR>(sr, (xcol & 8) != 0);
       halve_sources<4, GDN_DPP_HALF_MIRROR>(sr, (xcol & 4) != 0);
@@ -888,7 +1032,7 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
     unsigned ph[SL / 2], pl[SL / 2];
     {
       float unused[SL];
-      softmax_split<SL, FMT, false>(smem, si_off, k.sjoff, ph, pl, unused);
+      softmax_split<SL, FMT, false, C::PACK>(smem, si_off, k.sjoff, ph, pl, unused);
     }
     // ------------------------------------------------------------ M
     // The image is wave private and LDS executes one wave's accesses in order: scatter the hi term,
@@ -995,10 +1139,13 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
       for (int wk = 0; wk < WK; ++wk) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < 8; j += 2) {
           // XHALF: row 16 + r of the accumulator is register 8 + j of the same lane: the lo term of X^T (see M)
-          const float z = C::XHALF ? acc2[0][j] + acc2[0][8 + j] : acc2[0][8 * wk + j];
-          v[j] = z * (GDN_F16_Z_SCALE / (GDN_F16_ALPHA_SCALE * GDN_F16_XT_SCALE));
+          f32x2 z = {acc2[0][8 * wk + j], acc2[0][8 * wk + j + 1]};
+          if constexpr (C::XHALF) z = P::add(f32x2{acc2[0][j], acc2[0][j + 1]}, f32x2{acc2[0][8 + j], acc2[0][9 + j]});
+          z = P::mul(z, GDN_F16_Z_SCALE / (GDN_F16_ALPHA_SCALE * GDN_F16_XT_SCALE));
+          v[j] = z[0];
+          v[j + 1] = z[1];
         }
         u32x4 zf[2];
         split8<FMT, 2>(v, zf);
@@ -1035,12 +1182,20 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
           sh1a[0] = t1.x; sh1a[1] = t1.y; sh1a[2] = t1.z; sh1a[3] = t1.w;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float v = acc3[cb][4 * g + i];
-          if constexpr (!FOLD) v = fmaf(v, sc1a[i], sh1a[i]);
-          v = fmaxf(v, 0.f);
-          v = fmaxf(fmaf(v, k.e2[cb][4 * g + i], sh2a[i]), 0.f);
-          part = fmaf(v, woa[i], part);
+        for (int i = 0; i < 4; i += 2) {
+          const int r = 4 * g + i;
+          f32x2 v = {acc3[cb][r], acc3[cb][r + 1]};
+          // first ReLU.  FOLD: straight on the P1 accumulator, one instruction (relu_acc: a NaN stays NaN); bf16
+          // storage has no range guard and its ReLU follows an fma (one v_max_f32 already): fmaxf as before
+          if constexpr (FOLD) {
+            v = f32x2{relu_acc(v[0]), relu_acc(v[1])};
+          } else {
+            v = P::fma(v, f32x2{sc1a[i], sc1a[i + 1]}, f32x2{sh1a[i], sh1a[i + 1]});
+            v = f32x2{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)};
+          }
+          v = P::fma(v, f32x2{k.e2[cb][r], k.e2[cb][r + 1]}, f32x2{sh2a[i], sh2a[i + 1]});
+          part = fmaf(fmaxf(v[0], 0.f), woa[i], part);            // (`part`: one chain, in column order)
+          part = fmaf(fmaxf(v[1], 0.f), woa[i + 1], part);
         }
       }
     part += __shfl_xor(part, 32);
@@ -1187,10 +1342,11 @@ __global__ __launch_bounds__(64 * NT, SL <= 16 ? 2 : 1) void gdn_dense_attn_kern
       if (!tok[u]) continue;        // pad rows stay zero (the loads past row n read the next window)
       char* dst = smem + t_st + u * (C::RSTEP * 128);
       if constexpr (FMT == FMT_F16) {
-        const float v0 = __uint_as_float(pre[u].x), v1 = __uint_as_float(pre[u].y);
-        const float v2 = __uint_as_float(pre[u].z), v3 = __uint_as_float(pre[u].w);
-        const unsigned h0 = F::pk(v0, v1), h1 = F::pk(v2, v3);
-        const unsigned l0 = F::pk(F::res0(h0, v0), F::res1(h0, v1)), l1 = F::pk(F::res0(h1, v2), F::res1(h1, v3));
+        float v0 = __uint_as_float(pre[u].x), v1 = __uint_as_float(pre[u].y);
+        float v2 = __uint_as_float(pre[u].z), v3 = __uint_as_float(pre[u].w);
+        unsigned h0, h1, l0, l1;
+        F::split2(v0, v1, h0, l0);
+        F::split2(v2, v3, h1, l1);
         *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
         *reinterpret_cast<uint2*>(dst + C::TPLANE) = make_uint2(l0, l1);
       } else {
@@ -1209,7 +1365,7 @@ __global__ __launch_bounds__(64 * NT, SL <= 16 ? 2 : 1) void gdn_dense_attn_kern
     unsigned ph[SL / 2], pl[SL / 2];
     {
       float al[SL];
-      softmax_split<SL, FMT, WANT_ALPHA>(smem, si_off, sjoff, ph, pl, al);
+      softmax_split<SL, FMT, WANT_ALPHA, GDN_TRIM_PACK != 0 && SL <= 16 && FMT == FMT_F16>(smem, si_off, sjoff, ph, pl, al);
       if constexpr (WANT_ALPHA) {
         if (ti < n) {
           float4* dst = reinterpret_cast<float4*>(a.alpha + ((size_t)b * n + ti) * a.pitch + half * SL);
@@ -1727,12 +1883,12 @@ __global__ __launch_bounds__(64 * NT) void gdn_dense_project_kernel(const PArgs 
         const int k = wk * 16 + 8 * h + j;
         v[j] = ld_or(a.lin_w, (cb * 32 + l32) * w + k, k < w);
       }
-      split8<FMT, NTL>(v, bl[cb][wk]);
+      split8<FMT, NTL, false>(v, bl[cb][wk]);
     }
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = ld_or(a.node_terms, l32 * GDN_A_PITCH + wk * 16 + 8 * h + j, l32 < 2);
-    split8<FMT, NTL>(v, bs[wk]);
+    split8<FMT, NTL, false>(v, bs[wk]);
   }
   {
     float* ct = reinterpret_cast<float*>(smem + OFF_CS);
@@ -1797,7 +1953,7 @@ __global__ __launch_bounds__(64 * NT) void gdn_dense_project_kernel(const PArgs 
       v[0] = v0.x; v[1] = v0.y; v[2] = v0.z; v[3] = v0.w;
       v[4] = v1.x; v[5] = v1.y; v[6] = v1.z; v[7] = v1.w;
       u32x4 ax[NTXIN];
-      split8<FMT, NTXIN>(v, ax);
+      split8<FMT, NTXIN, false>(v, ax);
 #pragma unroll
       for (int tx = 0; tx < NTXIN; ++tx)
 #pragma unroll
