@@ -27,6 +27,7 @@ SIGNATURES = {
     "gdn_project_fwd_series": [_p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gdn_tile_fits": [_c_int] * 4,
     "gdn_kernel_family": [_c_int] * 6,
+    "gdn_tile_forward_form": [_c_int] * 5,
     "gdn_terms_pitch": [_c_int],
     "gdn_attn_aggregate_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
     "gdn_head_fwd": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p],

@@ -1206,18 +1206,41 @@ int launch_window(const Plan& pl, const Args& a, hipStream_t stream) {
   return gdn_launch_status();
 }
 
+// The PROJ / LST template arguments of gdn_window_kernel for a plan (PROJECT and FUSED: the projection form; ATTN and
+// FUSED: the list form).  The one place that decides them: select_proj / select_maxr below turn the two numbers into
+// template arguments, gdn_tile_forward_form reports them.  proj < 0: no kernel form takes the plan at `threads`.
+struct TileForm { int proj, lst; };
+TileForm tile_form(const Plan& pl, int mode, int threads) {
+  TileForm f = {-1, 0};
+  if (threads == 1024) {           // only the chunked matrix-core projection runs 16-wave workgroups
+    if (mode != MODE_ATTN && pl.mfma == 2) f.proj = 5;
+  } else if (mode == MODE_ATTN) {
+    f.proj = 1;
+  } else if (pl.mfma == 2) {       // chunked: x in registers, the LDS x tile one row chunk at a time (512 / 1024 threads)
+    if (threads == 512) f.proj = 5;
+  } else if (pl.mfma) {
+    f.proj = pl.wpm == 32 ? 4 : pl.n * pl.w <= 8 * threads ? 2 : 3;
+  } else {
+    f.proj = pl.wp == 8 ? 0 : 1;
+  }
+  if (mode != MODE_PROJECT) {
+    if (pl.nbr_lds) f.lst = pl.pitch == 16 ? 1 : pl.pitch == 32 ? 2 : pl.pitch <= 80 ? 5 : 0;
+    else f.lst = pl.pitch <= 80 ? 6 : 0;
+  }
+  return f;
+}
+
 // runtime -> compile-time selection, one level per parameter
 template <int D, int MODE, int NT, int PROJ>
-int select_maxr(const Plan& pl, const Args& a, hipStream_t st) {
+int select_maxr(const Plan& pl, const Args& a, int lst, hipStream_t st) {
   if constexpr (MODE == MODE_PROJECT) {
     return launch_window<D, MODE, NT, PROJ, 0>(pl, a, st);
   } else {
-    if (pl.nbr_lds) {
-      if (pl.pitch == 16) return launch_window<D, MODE, NT, PROJ, 1>(pl, a, st);
-      if (pl.pitch == 32) return launch_window<D, MODE, NT, PROJ, 2>(pl, a, st);
-      if (pl.pitch <= 80) return launch_window<D, MODE, NT, PROJ, 5>(pl, a, st);
-    } else if (pl.pitch <= 80) {
-      return launch_window<D, MODE, NT, PROJ, 6>(pl, a, st);
+    switch (lst) {
+      case 1: return launch_window<D, MODE, NT, PROJ, 1>(pl, a, st);
+      case 2: return launch_window<D, MODE, NT, PROJ, 2>(pl, a, st);
+      case 5: return launch_window<D, MODE, NT, PROJ, 5>(pl, a, st);
+      case 6: return launch_window<D, MODE, NT, PROJ, 6>(pl, a, st);
     }
     return launch_window<D, MODE, NT, PROJ, 0>(pl, a, st);
   }
@@ -1225,27 +1248,26 @@ int select_maxr(const Plan& pl, const Args& a, hipStream_t st) {
 
 template <int D, int MODE, int NT>
 int select_proj(const Plan& pl, const Args& a, int threads, hipStream_t st) {
-  if constexpr (NT == 1024) {      // only the chunked matrix-core projection runs 16-wave workgroups
+  const TileForm f = tile_form(pl, MODE, threads);
+  if constexpr (NT == 1024) {
     if constexpr (MODE != MODE_ATTN && D >= 32) {
-      if (pl.mfma == 2) return select_maxr<D, MODE, NT, 5>(pl, a, st);
+      if (f.proj == 5) return select_maxr<D, MODE, NT, 5>(pl, a, f.lst, st);
     }
     return GDN_ERR_UNSUPPORTED;
   } else if constexpr (MODE == MODE_ATTN) {
-    return select_maxr<D, MODE, NT, 1>(pl, a, st);
+    return select_maxr<D, MODE, NT, 1>(pl, a, f.lst, st);
   } else {
-    if constexpr (D >= 32) {
-      if (pl.mfma == 2) {      // chunked: x in registers, the LDS x tile one row chunk at a time (512 / 1024 threads)
-        if constexpr (NT == 512) return select_maxr<D, MODE, NT, 5>(pl, a, st);
-        else return GDN_ERR_UNSUPPORTED;
+    if constexpr (D >= 32) {       // the matrix-core projections exist at d >= 32 only (make_plan sets mfma there only)
+      if constexpr (NT == 512) {
+        if (f.proj == 5) return select_maxr<D, MODE, NT, 5>(pl, a, f.lst, st);
       }
-      if (pl.mfma) {
-        if (pl.wpm == 32) return select_maxr<D, MODE, NT, 4>(pl, a, st);
-        if (pl.n * pl.w <= 8 * threads) return select_maxr<D, MODE, NT, 2>(pl, a, st);
-        return select_maxr<D, MODE, NT, 3>(pl, a, st);
-      }
+      if (f.proj == 4) return select_maxr<D, MODE, NT, 4>(pl, a, f.lst, st);
+      if (f.proj == 2) return select_maxr<D, MODE, NT, 2>(pl, a, f.lst, st);
+      if (f.proj == 3) return select_maxr<D, MODE, NT, 3>(pl, a, f.lst, st);
     }
-    if (pl.wp == 8) return select_maxr<D, MODE, NT, 0>(pl, a, st);
-    return select_maxr<D, MODE, NT, 1>(pl, a, st);
+    if (f.proj == 0) return select_maxr<D, MODE, NT, 0>(pl, a, f.lst, st);
+    if (f.proj == 1) return select_maxr<D, MODE, NT, 1>(pl, a, f.lst, st);
+    return GDN_ERR_UNSUPPORTED;
   }
 }
 
@@ -1273,6 +1295,20 @@ bool gdn_tile_forward_ok(int stage, int n, int w, int d, int k, bool series) {
   Plan pl; int threads;
   const int mode = stage == GDN_STAGE_PROJECT ? MODE_PROJECT : stage == GDN_STAGE_AGGREGATE ? MODE_ATTN : MODE_FUSED;
   return make_plan(mode, 1, n, w, d, k, &pl, &threads) == GDN_OK && (!series || pl.mfma);
+}
+
+// The kernel form the staged tile forward launches at (n, w, d, k): make_plan and tile_form, the launch's own two steps
+// (layout at the declaration in include/gdn_hip.h).  Host only, no launch.
+extern "C" int gdn_tile_forward_form(int stage, int n, int w, int d, int k) {
+  if (stage != GDN_STAGE_PROJECT && stage != GDN_STAGE_AGGREGATE) return -1;
+  const int mode = stage == GDN_STAGE_PROJECT ? MODE_PROJECT : MODE_ATTN;
+  Plan pl; int threads;
+  if (make_plan(mode, 1, n, mode == MODE_ATTN ? 0 : w, d, mode == MODE_ATTN ? k : 0, &pl, &threads) != GDN_OK) return -1;
+  const TileForm f = tile_form(pl, mode, threads);
+  if (f.proj < 0) return -1;
+  const int chunked = mode != MODE_ATTN && pl.xrows < n;
+  return f.proj | f.lst << 4 | (threads / 256) << 8 | (pl.nslices == 2) << 12 | pl.nbr_lds << 13 | pl.wl_lds << 14 |
+         chunked << 15 | pl.xrows << 16;
 }
 
 // x rows at xb + b*bstride + s*sstride: [B, n, w] windows (n*w, w) or the raw series (1, series_len)

@@ -179,6 +179,25 @@ int gdn_tile_fits(int n, int w, int d, int k);
 #define GDN_BWD_SLICED 2
 int gdn_kernel_family(int stage, int n, int w, int d, int k, int flags);
 
+/* gdn_tile_forward_form: the form of the TILE kernel that the staged forward launches at (n, w, d, k), whatever the
+ * route says (the `_wide` entry points run TILE at dense shapes).  Host only, no launch; the numbers come from the code
+ * that dispatches.  stage = GDN_STAGE_PROJECT (k ignored) or GDN_STAGE_AGGREGATE (w ignored); -1 for any other stage
+ * and for a shape the tile refuses (the fused launch depends on the batch and the CU count and is not reported).
+ *   bits 0-3    PROJ: the projection form — 0 / 1: fp32 VALU, window padded to 8 / to a multiple of 16 ticks;
+ *               2 / 3 / 4: matrix cores, whole window staged (n w <= 8 threads, w <= 16 / above it / w > 16);
+ *               5: matrix cores, x in registers, the LDS x tile one row chunk at a time.  AGGREGATE: 1;
+ *   bits 4-7    LST: the list form — lists in LDS at pitch 16 (1), 32 (2), 48..80 (5); lists read from global at
+ *               pitch <= 80 (6); any longer list (0).  PROJECT: 0;
+ *   bits 8-11   threads / 256 (1 or 2);
+ *   bit 12      two 64-column slices (d = 128 beyond the full tile);
+ *   bit 13      neighbour lists in LDS;
+ *   bit 14      lin weights in LDS (fp32 VALU projections of small tiles);
+ *   bit 15      x tile chunked: it holds fewer rows than the window has sensors;
+ *   bits 16-30  the rows of the x tile (0 for AGGREGATE).
+ * GDN_THREADS and GDN_NO_MFMA act on it as on the launch.  Additive diagnostic entry point: the ABI version does not
+ * move.                                                                                                           */
+int gdn_tile_forward_form(int stage, int n, int w, int d, int k);
+
 /* gdn_attn_aggregate_fwd: models/graph_layer.py:65-74,82-117 + PyG propagate / softmax:
  * LeakyReLU(0.2) logits, softmax over each target's incoming edges (max-subtract, exp,
  * /(sum+1e-16)), alpha-weighted sum of source rows, + bias.

@@ -43,21 +43,28 @@ def aggregate_ref(xlin, s_i, s_j, bias, nbr, d_z):
     padding, d_xlin[b, n, d], d_si[b, n], d_sj[b, n], d_bias[d]), float64.
     The softmax runs over a row's valid slots only, /(sum + 1e-16); the LeakyReLU derivative at exactly 0 is the
     slope (torch's convention, the kernels' `pi > 0.f ? 1 : slope`)."""
-    nbr = nbr.long()
     b, n, d = xlin.shape
     x64 = xlin.detach().to(f64).clone().requires_grad_(True)
     si64 = s_i.detach().to(f64).clone().requires_grad_(True)
     sj64 = s_j.detach().to(f64).clone().requires_grad_(True)
     b64 = bias.detach().to(f64).clone().requires_grad_(True)
+    z, alpha = aggregate_fwd(x64, si64, sj64, b64, nbr)
+    z.backward(d_z.detach().to(f64).view(b, n, d))
+    return z.detach(), alpha.detach(), x64.grad, si64.grad, sj64.grad, b64.grad
+
+
+def aggregate_fwd(xlin, s_i, s_j, bias, nbr):
+    """The forward half of aggregate_ref in the dtype of its arguments (float64 there; float32 is the yardstick of the
+    forward stage tests): (z[b, n, d], alpha[b, n, pitch]), differentiable."""
+    nbr = nbr.long()
+    n = xlin.shape[1]
     valid = nbr < n
     safe = nbr.clamp(max=n - 1)
-    logit = F.leaky_relu(si64.unsqueeze(-1) + sj64[:, safe], NEG_SLOPE)            # [b, n, pitch]
+    logit = F.leaky_relu(s_i.unsqueeze(-1) + s_j[:, safe], NEG_SLOPE)                # [b, n, pitch]
     logit = logit.masked_fill(~valid, float("-inf"))
     e = (logit - logit.max(dim=-1, keepdim=True).values).exp()                       # padding: exp(-inf) = 0
     alpha = e / (e.sum(dim=-1, keepdim=True) + SOFTMAX_EPS)
-    z = (alpha.unsqueeze(-1) * x64[:, safe]).sum(dim=2) + b64
-    z.backward(d_z.detach().to(f64).view(b, n, d))
-    return z.detach(), alpha.detach(), x64.grad, si64.grad, sj64.grad, b64.grad
+    return (alpha.unsqueeze(-1) * xlin[:, safe]).sum(dim=2) + bias, alpha
 
 
 def project_bwd_ref(x, d_xlin, d_si, d_sj):
