@@ -128,6 +128,10 @@ SIGNATURES = {
     "gdn_score_key_counts": [_p, _c_int, _c_int, _c_int, _p, _p],
     "gdn_score_select_counts": [_p, _c_int, _c_int, _c_int, _p, _c_int, _p, _p, _p, _p],
     "gdn_stream_calib_write_sensor": [_p] * 5 + [_c_int] * 5 + [_p] * 3,
+    "gdn_prep_stats_workspace_bytes": [ctypes.c_longlong, _c_int],
+    "gdn_prep_stats": [_p, ctypes.c_longlong, _c_int, _c_int, _p, _p, _p],
+    "gdn_prep_series": [_p, ctypes.c_longlong, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p],
+    "gdn_prep_ticks": [_p, _c_int, _c_int, _p, _c_int, _p, _c_int, _c_int, _p, _p, _c_int, _p],
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

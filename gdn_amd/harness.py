@@ -1665,6 +1665,24 @@ def train_series(model=None, save_path="", config=None, series=None, w: int | No
 _STREAM_MAX_CHUNK = 4096                # ticks per push: validate_series' cap on windows per launch
 
 
+def raw_push_plan(pending: int, r: int, down: int, chunk: int) -> list:
+    """The sub-pushes of `r` raw ticks handed to a prep= detector that holds `pending` < down raw ticks of an open
+    group: a list of (raw_rows, groups, new_pending, replayable).  A sub-push carries at most chunk * down - pending
+    raw ticks, so it completes at most `chunk` model ticks and a long push reaches a group boundary with its first
+    sub-push; groups = (pending + raw_rows) // down model ticks are scored, new_pending raw ticks stay open.
+    replayable: the sub-push starts on a group boundary and carries exactly chunk * down raw ticks (the captured
+    graph's shape).  Pure host arithmetic."""
+    if down < 1 or chunk < 1 or r < 0 or not 0 <= pending < down:
+        raise ValueError(f"raw_push_plan: pending = {pending}, r = {r}, down = {down}, chunk = {chunk}")
+    plan = []
+    while r > 0:
+        rows = min(r, chunk * down - pending)
+        groups, left = divmod(pending + rows, down)
+        plan.append((rows, groups, left, pending == 0 and rows == chunk * down))
+        pending, r = left, r - rows
+    return plan
+
+
 class StreamDetector:
     """Scores ticks as they arrive against a frozen calibration, with nothing but launches per push.
 
@@ -1708,12 +1726,23 @@ class StreamDetector:
     ring write is gdn_stream_calib_write_sensor, which puts the filler into the keys of the missing readings only.
     `recalibrate()` then counts every sensor's real keys on the device and rewrites the row of every sensor that has
     at least `recal_min` of them; a dead sensor keeps its row and no longer stops the others.  The default "tick" is
-    the rule above, launch for launch."""
+    the rule above, launch for launch.
+
+    `prep=Prep` puts the raw-readings front end on the device: `push()` then takes RAW ticks [r, n], fp32
+    or float64, in engineering units at the raw rate, and gdn_prep_ticks leads the launches: it normalises every
+    reading with the Prep's min-max table and writes the median of each completed group of `prep.down` raw ticks as
+    one model tick into `raw_buf` (gaps=True; a group with no finite reading is a missing reading) or `chunk_buf`.
+    The raw ticks of an open group wait in two float64 planes on the device that alternate (`raw_pending` counts
+    them on the host).  `chunk`, `recal_every`, `history`, the counters and the log stay in model ticks; a sub-push
+    carries up to chunk * down raw ticks (`raw_push_plan`); one that completes no group issues that one launch and
+    scores nothing; one that starts on a group boundary with exactly chunk * down raw ticks is ONE copy and ONE replay
+    of a graph captured with the front end in it.  A prep= detector pushed raw ticks writes the bits a plain one
+    writes when pushed prep.series(raw).t(); prep=None issues exactly the launches it always did."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
-                 calib: str = "tick"):
+                 calib: str = "tick", prep=None):
         if calib not in ("tick", "sensor"):
             raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
         if calib == "sensor" and not (gaps and int(recal) > 0):
@@ -1796,6 +1825,18 @@ class StreamDetector:
         self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
         self.calib_kept = None              # from_calibration(calib_gaps=True): the complete ticks behind the table
         self.calib_counts = None            # ... calib="sensor": every sensor's real readings behind it (device int32)
+        self.prep = prep
+        self.raw_pending = 0                # prep=: raw ticks of the open group, held in _pend[_pend_at]
+        if prep is not None:
+            if prep.n != n:
+                raise ValueError(f"prep: fitted on {prep.n} sensors, the model has {n}")
+            if prep.table.device != dev:
+                raise ValueError(f"prep: its table is on {prep.table.device}, the detector on {dev}")
+            rows = max(1, prep.down - 1)
+            self._pend = [torch.zeros((rows, n), dtype=torch.float64, device=dev) for _ in range(2)]
+            self._pend_at = 0
+            self._raw_stage = {}            # raw dtype -> the static staging buffer [chunk * down, n] of its pushes
+            self._prep_graphs = {}          # ... -> the graph captured with the front end reading that buffer
 
     @classmethod
     def from_calibration(cls, model, series, chunk: int, batch: int = 8192, calib_gaps: bool = False,
@@ -1912,12 +1953,67 @@ class StreamDetector:
         with capture(self.graph):
             self._launch(r, guard)
 
+    def _launch_prep(self, stage, rows: int, groups: int, guard: bool):
+        """gdn_prep_ticks over stage[:rows] and the pending plane, then the launches of a push of `groups` ticks."""
+        ops.prep_ticks(stage, self._pend[self._pend_at], self.raw_pending, self._pend[self._pend_at ^ 1],
+                       self.prep.down, self.prep.table, self.raw_buf if self.with_gaps else self.chunk_buf, rows=rows)
+        if groups:
+            self._launch(groups, guard)
+
+    def _push_raw(self, ticks, groups: int, left: int, replayable: bool):
+        rows = ticks.shape[0]
+        stage = self._raw_stage.get(ticks.dtype)
+        if stage is None:
+            stage = self._raw_stage[ticks.dtype] = torch.zeros((self.chunk * self.prep.down, self.n), dtype=ticks.dtype,
+                                                               device=self.state.device)
+        stage[:rows].copy_(ticks)
+        self._last = groups
+        if not (replayable and self.use_graph):
+            self._launch_prep(stage, rows, groups, self._guarded() if groups else False)
+        else:
+            # (a replayable sub-push opens and leaves no group: the graph neither reads nor writes a pending plane)
+            key = self.model._constants().key
+            if key != self._graph_key:      # (_fresh's rule: a parameter changed, the captured pointers are stale)
+                self._prep_graphs.clear()
+                self._graph_key = key
+            graph = self._prep_graphs.get(ticks.dtype)
+            if graph is not None:
+                graph.replay()
+            else:
+                guard = self._guarded()
+                self._launch_prep(stage, rows, groups, guard)           # the warm-up: the state moves once
+                torch.cuda.synchronize()
+                graph = self._prep_graphs[ticks.dtype] = torch.cuda.CUDAGraph()
+                with capture(graph):
+                    self._launch_prep(stage, rows, groups, guard)
+        self._pend_at ^= 1
+        self.raw_pending = left
+
+    def _push_prep(self, ticks):
+        if ticks.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"ticks: expected raw {torch.float32} or {torch.float64}, got {ticks.dtype}")
+        if ticks.shape[0] < 1:
+            raise ValueError("a push needs at least one raw tick")
+        at = 0
+        for rows, groups, left, replayable in raw_push_plan(self.raw_pending, ticks.shape[0], self.prep.down, self.chunk):
+            self._push_raw(ticks[at:at + rows], groups, left, replayable)
+            at += rows
+            before, self._handed = self._handed, self._handed + groups
+            if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
+                self.recalibrate()
+        r = self._last
+        return self.top_scores[:r], self.top_sensors[:r], self.alarm[:r]
+
     def push(self, ticks):
         """Score `ticks` [r, n] fp32 (device or host), oldest first.  Returns views (top_scores [r', m] float64,
         top_sensors [r', m] int32, alarm [r'] int32) of the static buffers, valid until the next push; r' = r when
-        r <= chunk, else the ticks of the last of the pushes it was split into (the counters and the log hold all)."""
+        r <= chunk, else the ticks of the last of the pushes it was split into (the counters and the log hold all).
+        prep=: `ticks` are RAW ticks, fp32 or float64; the views cover the model ticks the last sub-push completed
+        (possibly none)."""
         if ticks.dim() != 2 or ticks.shape[1] != self.n:
             raise ValueError(f"expected ticks of shape [r, {self.n}], got {tuple(ticks.shape)}")
+        if self.prep is not None:
+            return self._push_prep(ticks)
         if ticks.dtype != torch.float32:
             raise TypeError(f"ticks: expected {torch.float32}, got {ticks.dtype}")
         if ticks.shape[0] < 1:
@@ -1965,13 +2061,15 @@ class StreamDetector:
         return self.med_iqr.clone(), self.recal_kept
 
     def status(self):
-        """(ticks, alarms, log_ticks[:logged], log_sensors[:logged]): ONE read of the counters (a synchronisation)."""
+        """(ticks, alarms, log_ticks[:logged], log_sensors[:logged]): ONE read of the counters (a synchronisation).
+        A prep= detector appends `raw_pending`, the raw ticks of the open group (a host value)."""
         ticks, alarms, logged = (int(v) for v in self.state[:3].tolist())
+        tail = () if self.prep is None else (self.raw_pending,)
         if self.log_ticks is None:
             dev = self.state.device
             return (ticks, alarms, torch.empty((0,), dtype=torch.int64, device=dev),
-                    torch.empty((0, self.top_m), dtype=torch.int32, device=dev))
-        return ticks, alarms, self.log_ticks[:logged], self.log_sensors[:logged]
+                    torch.empty((0, self.top_m), dtype=torch.int32, device=dev)) + tail
+        return (ticks, alarms, self.log_ticks[:logged], self.log_sensors[:logged]) + tail
 
     def status_gaps(self):
         """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: the missing readings of every

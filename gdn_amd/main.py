@@ -222,11 +222,14 @@ class Main:
                                     calib_gaps=bool(self.env_config.get("stream_calib_gaps")),
                                     recal=int(self.env_config.get("stream_recal") or 0),
                                     recal_every=int(self.env_config.get("stream_recal_every") or 0),
-                                    by_sensor=bool(self.env_config.get("calib_by_sensor")))
+                                    by_sensor=bool(self.env_config.get("calib_by_sensor")),
+                                    raw_path=self.env_config.get("stream_raw") or "",
+                                    prep_path=self.env_config.get("prep") or "")
         return info
 
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
-                           recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False):
+                           recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False,
+                           raw_path: str = "", prep_path: str = ""):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
@@ -241,8 +244,14 @@ class Main:
         join the line and `stream_result` ("calib_kept").
         -calib_by_sensor (with -stream_gaps -stream_calib_gaps): every sensor's table row comes from its own real
         readings (calib="sensor"); the smallest and largest per-sensor count join the line and `stream_result`
-        ("calib_count_min", "calib_count_max"), and with -stream_recal the ring recalibrates per sensor as well."""
+        ("calib_count_min", "calib_count_max"), and with -stream_recal the ring recalibrates per sensor as well.
+        -stream_raw RAW.csv -prep prep.npz: the replayed ticks are the RAW file's (engineering units at the raw rate,
+        columns as list.txt names them) from raw tick slide_win * down on, pushed C * down at a time through a prep=
+        detector (gdn_amd.prep.Prep: min-max table and median downsample on the device); the calibration and the
+        history are the prepared series' as before.  "raw_ticks" (pushed) and "raw_pending" (left in an open group)
+        join the line and `stream_result`."""
         check_calib_by_sensor(by_sensor, bool(chunk), gaps, calib_gaps)
+        check_stream_raw(bool(raw_path), bool(chunk), bool(prep_path))
         w = self.train_config["slide_win"]
         lo, hi = int(val_ticks.min()), int(val_ticks.max())
         normal = self.train_series[:, lo - w:hi + 1].contiguous()
@@ -255,16 +264,28 @@ class Main:
             rolling["calib_gaps"] = True
         if by_sensor:
             rolling["calib"] = "sensor"
+        step = chunk
+        if raw_path:
+            from .prep import Prep, read_raw_csv
+            rolling["prep"] = Prep.load(prep_path, self.device)
+            step = chunk * rolling["prep"].down
+            raw_np, _labels, _names = read_raw_csv(raw_path, names=self.feature_map)
+            ticks = torch.from_numpy(raw_np[w * rolling["prep"].down:]).to(self.device)
+        else:
+            ticks = self.test_series[:, w:].t().contiguous()
         det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
                                                       top_m=min(3, normal.shape[0]), gaps=gaps, **rolling)
-        ticks = self.test_series[:, w:].t().contiguous()
-        for s in range(0, ticks.shape[0], chunk):
-            det.push(ticks[s:s + chunk])
-        scored, alarms, log_ticks, log_sensors = det.status()
+        for s in range(0, ticks.shape[0], step):
+            det.push(ticks[s:s + step])
+        scored, alarms, log_ticks, log_sensors = det.status()[:4]
         self.stream_result = {"chunk": chunk, "threshold": float(det.threshold.item()), "ticks": scored,
                               "alarms": alarms, "log_ticks": log_ticks.cpu().numpy(),
                               "log_sensors": log_sensors.cpu().numpy()}
         held = ""
+        if raw_path:
+            self.stream_result["raw_ticks"], self.stream_result["raw_pending"] = int(ticks.shape[0]), det.raw_pending
+            held = (f"; from {ticks.shape[0]} raw ticks, {rolling['prep'].down} to a tick, {det.raw_pending} left in an "
+                    "open group")
         if gaps:
             missing_total, _run = det.status_gaps()
             self.stream_result["gap_sensors"] = int((missing_total > 0).sum())
@@ -346,7 +367,8 @@ class Main:
 
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
-    -train_gaps / -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every."""
+    -train_gaps / -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every /
+    -stream_raw / -prep."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -386,7 +408,22 @@ def build_parser():
     parser.add_argument("-calib_by_sensor", help="with -stream -stream_gaps -stream_calib_gaps: calibrate (and, with "
                         "-stream_recal, recalibrate) every sensor on its own real readings, not on complete ticks only",
                         action="store_true")
+    parser.add_argument("-stream_raw", help="with -stream and -prep: replay this RAW csv (engineering units, raw tick "
+                        "rate) through the detector's on-device front end instead of the prepared test series",
+                        type=str, default="")
+    parser.add_argument("-prep", help="the prep.npz `python -m gdn_amd.prep` wrote (min-max table, down, sensor names)",
+                        type=str, default="")
     return parser
+
+
+def check_stream_raw(stream_raw: bool, stream: bool, prep: bool) -> None:
+    """-stream_raw names the raw file a streaming detector replays through its front end: it means something only
+    with -stream C (the detector) and -prep prep.npz (the fitted table).  Refused by name otherwise."""
+    if stream_raw and not stream:
+        raise ValueError("-stream_raw needs -stream C: the raw file is replayed through the streaming detector")
+    if stream_raw and not prep:
+        raise ValueError("-stream_raw needs -prep prep.npz: raw readings are normalised with the table fitted on the "
+                         "training file (python -m gdn_amd.prep)")
 
 
 def check_calib_by_sensor(by_sensor: bool, stream: bool, stream_gaps: bool, stream_calib_gaps: bool) -> None:
@@ -405,10 +442,12 @@ def check_train_gaps(train_gaps: bool, hip_graph: bool) -> None:
                          "-no_hip_graph, whose eager loop over the loaders has no masked loss")
 
 
-def main(argv=None):
+def from_args(argv=None) -> Main:
+    """The Main of a command line: flags checked, seeds set, data read, model built; `.run()` does the rest."""
     args = build_parser().parse_args(argv)
     check_train_gaps(args.train_gaps, not args.no_hip_graph)
     check_calib_by_sensor(args.calib_by_sensor, bool(args.stream), args.stream_gaps, args.stream_calib_gaps)
+    check_stream_raw(bool(args.stream_raw), bool(args.stream), bool(args.prep))
     random.seed(args.random_seed)                      # main.py:221-228
     np.random.seed(args.random_seed)
     torch.manual_seed(args.random_seed)
@@ -424,8 +463,13 @@ def main(argv=None):
                   "device": args.device, "load_model_path": args.load_model_path, "data_root": args.data_root,
                   "localise": args.localise, "stream": args.stream,
                   "stream_gaps": args.stream_gaps, "stream_calib_gaps": args.stream_calib_gaps, "stream_recal": args.stream_recal,
-                  "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor}
-    return Main(train_config, env_config, debug=False).run()
+                  "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor,
+                  "stream_raw": args.stream_raw, "prep": args.prep}
+    return Main(train_config, env_config, debug=False)
+
+
+def main(argv=None):
+    return from_args(argv).run()
 
 
 if __name__ == "__main__":

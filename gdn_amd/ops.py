@@ -1183,3 +1183,100 @@ def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_
         name = "gdn_stream_calib_write_sensor" if by_sensor else "gdn_stream_calib_write_gaps"
         _lib.call(name, _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), *tail)
     return ring_keys, ring_keep
+
+
+# --------------------------------------------------------------------------- raw readings
+_PREP_MAX_DOWN = 64
+
+
+def _prep_raw(raw, name: str = "raw"):
+    """A raw tick-major block [t_raw, n], fp32 or float64, on the device: (tensor, t_raw, n, raw_f64)."""
+    if not raw.is_cuda:
+        raise _lib.GdnHipError(f"{name} is on {raw.device}: gdn_amd ops need a HIP device (no CPU fallback)")
+    if raw.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name}: expected {torch.float32} or {torch.float64}, got {raw.dtype}")
+    if raw.dim() != 2 or raw.shape[0] < 1 or not 1 <= raw.shape[1] <= 4096:
+        raise ValueError(f"expected {name} [t_raw >= 1, 1 <= n <= 4096] (one row per raw tick), got {tuple(raw.shape)}")
+    raw = raw if raw.is_contiguous() else raw.contiguous()
+    return raw, raw.shape[0], raw.shape[1], int(raw.dtype == torch.float64)
+
+
+def _prep_down(down: int) -> int:
+    if not 1 <= int(down) <= _PREP_MAX_DOWN:
+        raise ValueError(f"down = {down}: a prepared tick is the median of 1 to {_PREP_MAX_DOWN} raw ticks")
+    return int(down)
+
+
+def _prep_table(table, n: int):
+    table = _chk(table, torch.float64, name="table")
+    if table.shape != (n, 2):
+        raise ValueError(f"expected table of shape [{n}, 2] (scale, offset), got {tuple(table.shape)}")
+    return table
+
+
+def prep_stats(raw, out: torch.Tensor | None = None) -> torch.Tensor:
+    """stats [n, 4] float64 = (min, max, mean, count) per sensor over the finite readings of `raw` [t_raw, n] (fp32 or
+    float64, tick-major); all four 0 for a sensor with none (gdn_prep_stats: a fixed summation order)."""
+    raw, t_raw, n, f64 = _prep_raw(raw)
+    ws = torch.empty((_lib.load().gdn_prep_stats_workspace_bytes(t_raw, n) // 8,), dtype=torch.float64, device=raw.device)
+    out = torch.empty((n, 4), dtype=torch.float64, device=raw.device) if out is None else out
+    _stream_buf(out, torch.float64, 4 * n, "out")
+    _lib.call("gdn_prep_stats", _ptr(raw), t_raw, n, f64, _ptr(ws), _ptr(out), _stream())
+    return out
+
+
+def prep_series(raw, table, down: int, fill=None, labels=None):
+    """(series [n, T = t_raw // down] fp32, labels [T] float64 or None): every reading of `raw` [t_raw, n] normalised
+    as x * table[i, 0] + table[i, 1] in float64, then the median of each group of `down` raw ticks (gdn_prep_series).
+    `fill` [n] float64 replaces a missing (non-finite) reading before the normalisation; without it a missing reading
+    is left out of its group's median and an empty group is NaN.  `labels` [t_raw] float64: rint(max) per group."""
+    raw, t_raw, n, f64 = _prep_raw(raw)
+    down = _prep_down(down)
+    if t_raw < down:
+        raise ValueError(f"t_raw = {t_raw} raw ticks are fewer than down = {down}: not one prepared tick")
+    table = _prep_table(table, n)
+    if fill is not None:
+        fill = _chk(fill, torch.float64, name="fill")
+        if fill.shape != (n,):
+            raise ValueError(f"expected fill of shape [{n}], got {tuple(fill.shape)}")
+    T = t_raw // down
+    labels_out = None
+    if labels is not None:
+        labels = _chk(labels, torch.float64, name="labels")
+        if labels.shape != (t_raw,):
+            raise ValueError(f"expected labels of shape [{t_raw}], got {tuple(labels.shape)}")
+        labels_out = torch.empty((T,), dtype=torch.float64, device=raw.device)
+    series = torch.empty((n, T), dtype=torch.float32, device=raw.device)
+    _lib.call("gdn_prep_series", _ptr(raw), t_raw, n, f64, _ptr(table), _ptr(fill), down, _ptr(labels), _ptr(series),
+              _ptr(labels_out), _stream())
+    return series, labels_out
+
+
+def prep_ticks(raw, pend_in, pending: int, pend_out, down: int, table, out, rows: int | None = None) -> int:
+    """The stream's front end (gdn_prep_ticks): the raw ticks [pend_in[:pending] | raw[:rows]] -> out[g, :] for g <
+    (pending + rows) // down (tick-major fp32, `out` [c, n]) and the last (pending + rows) % down of them -> pend_out
+    as float64.  pend_in / pend_out: distinct float64 planes of at least max(1, down - 1) rows of n.  `rows` (default:
+    all of raw) lets a static staging buffer carry a shorter push.  Returns the number of completed groups."""
+    raw, t_raw, n, f64 = _prep_raw(raw)
+    down = _prep_down(down)
+    rows = t_raw if rows is None else int(rows)
+    if not 1 <= rows <= t_raw:
+        raise ValueError(f"rows = {rows}: between 1 and the {t_raw} rows of raw")
+    if not 0 <= int(pending) < down:
+        raise ValueError(f"pending = {pending}: the raw ticks of an open group number 0 to down - 1 = {down - 1}")
+    table = _prep_table(table, n)
+    need = max(1, down - 1) * n
+    _stream_buf(pend_in, torch.float64, need, "pend_in")
+    _stream_buf(pend_out, torch.float64, need, "pend_out")
+    if pend_in.data_ptr() == pend_out.data_ptr():
+        raise ValueError("pend_out must not alias pend_in (alternate the two planes)")
+    _stream_buf(out, torch.float32, 1, "out")
+    if out.dim() != 2 or out.shape[1] != n:
+        raise ValueError(f"expected out [c, {n}] (one row per prepared tick), got {tuple(out.shape)}")
+    groups = (int(pending) + rows) // down
+    if groups > out.shape[0]:
+        raise ValueError(f"{pending} pending + {rows} raw ticks complete {groups} groups of {down}: more than the "
+                         f"{out.shape[0]} rows of out")
+    _lib.call("gdn_prep_ticks", _ptr(raw), rows, f64, _ptr(pend_in), int(pending), _ptr(pend_out), n, down, _ptr(table),
+              _ptr(out), out.shape[0], _stream())
+    return groups

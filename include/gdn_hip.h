@@ -950,6 +950,46 @@ int gdn_stream_calib_write_sensor(const void* state, const float* pred, const fl
                                   const uint8_t* valid, int c, int count, int n, int R, int exclude_alarms,
                                   double* ring_keys, uint8_t* ring_keep, void* stream);
 
+/* ---- Raw readings ----------------------------------------------------------------------------
+ * The front of the deployment path (opt-in; additive entry points, the ABI version does not move): raw engineering
+ * units at the raw tick rate in, the prepared series the model was trained on out — min-max normalised with a table
+ * fitted on the training file, then the median of every `down` raw ticks (the reference's scripts/process_*.py:
+ * MinMaxScaler(0, 1) and np.median over groups of 10).
+ * Conventions: raw data is tick-major [t_raw, n] (a CSV read; the stream's chunk), fp32 when raw_f64 == 0, float64
+ * otherwise.  Every computation is float64 with a multiply and the add after it rounded separately, as numpy does.
+ * A reading that is not finite (NaN, +inf, -inf: exponent field all ones) is MISSING, gdn_stream_fill's rule.
+ * table[n, 2] float64 = (scale, offset) per sensor: a reading x is normalised as x * scale + offset; for the min-max
+ * fit scale = 1 / range and offset = 0 - min * scale (range = 1 where max - min < 10 eps: a constant sensor).
+ * No allocation, no synchronisation (capturable), no atomics: results are bitwise reproducible.
+ *   gdn_prep_stats   stats[i] = (min, max, mean, count) of sensor i's readings that are not missing, as float64; all
+ *                    four 0 for a sensor with none.  The sum runs in a fixed order — rows strided over the four waves
+ *                    of a segment, the waves in wave order, the segments in segment order, the number of segments a
+ *                    function of (t_raw, n) alone — so it does not depend on the device or on how the grid is
+ *                    scheduled.  workspace: gdn_prep_stats_workspace_bytes(t_raw, n) bytes (0: unsupported shape).
+ *                    Two launches.
+ *   gdn_prep_series  T = t_raw / down prepared ticks (the tail t_raw % down is dropped).  A missing reading is first
+ *                    replaced by fill[i] when fill != NULL (fill, then normalise: the reference's order), else it
+ *                    stays missing.  series[i, g] (sensor-major [n, T] fp32, the layout of `series` everywhere) = the
+ *                    median of the group's normalised readings that are not missing, rounded to fp32: the middle
+ *                    value of an odd count, (lo + hi) / 2.0 of the middle pair of an even one, a quiet NaN for a group
+ *                    with none (a missing reading to every gaps consumer downstream).  labels_out[g] (float64, may be
+ *                    NULL) = rint(max of labels_in[g down .. g down + down - 1]), labels_in float64 [t_raw].  One
+ *                    launch; raw is read once, coalesced along sensors, and series is written in 256-byte runs.
+ *   gdn_prep_ticks   the stream's front end.  The raw ticks of the launch are [pend_in[:pending] | raw[:r]], pending <
+ *                    down a host value; out[g, :] (tick-major fp32, rows of a [c, n] chunk) for g < (pending + r) / down
+ *                    by gdn_prep_series' arithmetic with fill == NULL; the last (pending + r) % down raw ticks go to
+ *                    pend_out as float64.  pend_in and pend_out are distinct planes of at least down - 1 rows of n
+ *                    float64 (the caller alternates them: a launch never reads what it writes).  One launch.
+ * 1 <= n <= 4096 and 1 <= down <= 64: else GDN_ERR_UNSUPPORTED.  Null required pointers, t_raw < down, r < 1, pending
+ * outside [0, down), pend_in == pend_out, (pending + r) / down > c, labels_out without labels_in: GDN_ERR_ARG.  All
+ * decided before any launch.                                                                                        */
+long long gdn_prep_stats_workspace_bytes(long long t_raw, int n);
+int gdn_prep_stats(const void* raw, long long t_raw, int n, int raw_f64, void* workspace, double* stats, void* stream);
+int gdn_prep_series(const void* raw, long long t_raw, int n, int raw_f64, const double* table, const double* fill,
+                    int down, const double* labels_in, float* series, double* labels_out, void* stream);
+int gdn_prep_ticks(const void* raw, int r, int raw_f64, const double* pend_in, int pending, double* pend_out, int n,
+                   int down, const double* table, float* out, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
