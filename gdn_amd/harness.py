@@ -17,10 +17,12 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import gc
+import hashlib
 import os
 import warnings
 from typing import NamedTuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -1683,6 +1685,172 @@ def raw_push_plan(pending: int, r: int, down: int, chunk: int) -> list:
     return plan
 
 
+# the checkpoint of a running detector: a flat dict of numpy arrays, one .npz, no Python objects
+STREAM_CHECKPOINT_FORMAT = 1
+# 0-d int64: identity, the configuration, the host counters (calib_kept: -1 for None; prep_down: 0 without a prep)
+_CKPT_INTS = ("format", "abi", "state_bytes", "calib_bytes", "n", "w", "chunk", "top_m", "log", "with_gaps", "recal",
+              "exclude_alarms", "recal_every", "recal_min", "wide", "prep", "prep_down", "handed", "recals",
+              "recal_kept", "calib_kept", "raw_pending")
+_CKPT_STRS = ("calib", "model_sha256")
+_CKPT_CONFIG = ("n", "w", "chunk", "top_m", "log", "with_gaps", "recal", "exclude_alarms", "recal_every", "recal_min",
+                "calib", "wide", "prep", "prep_down")
+
+
+def _host_copies(tensors) -> list:
+    """Host copies of `tensors`, issued and not waited for: a device tensor goes into pinned memory with a
+    non-blocking copy on the current stream (the caller synchronises ONCE before reading any), a host tensor is
+    taken as it is."""
+    out = []
+    for t in tensors:
+        t = t.detach()
+        if t.is_cuda:
+            out.append(torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True))
+        else:
+            out.append(t)
+    return out
+
+
+def _fingerprint(names, host) -> str:
+    h = hashlib.sha256()
+    for name, t in zip(names, host):
+        h.update(f"{name}|{t.dtype}|{tuple(t.shape)}|".encode())
+        h.update(t.contiguous().reshape(-1).view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()
+
+
+def model_fingerprint(model) -> str:
+    """SHA-256 (hex) over the model's state_dict: every tensor in key order as its name, dtype, shape and bytes.  Equal
+    for equal weights on any device; one changed bit of a parameter or of a BatchNorm running statistic changes it.
+    Device tensors are read in one batch of copies and ONE synchronisation."""
+    sd = model.state_dict()
+    names = sorted(sd)
+    host = _host_copies([sd[k] for k in names])
+    if any(sd[k].is_cuda for k in names):
+        torch.cuda.current_stream().synchronize()
+    return _fingerprint(names, host)
+
+
+def _ckpt_int(sd, key: str) -> int:
+    if key not in sd:
+        raise ValueError(f"stream checkpoint: key {key!r} is missing (a truncated or foreign file)")
+    a = np.asarray(sd[key])
+    if a.dtype != np.int64 or a.shape != ():
+        raise ValueError(f"stream checkpoint: {key!r} must be one int64, got {a.dtype} {a.shape}")
+    return int(a)
+
+
+def _ckpt_str(sd, key: str) -> str:
+    if key not in sd:
+        raise ValueError(f"stream checkpoint: key {key!r} is missing (a truncated or foreign file)")
+    a = np.asarray(sd[key])
+    if a.dtype.kind != "U" or a.shape != ():
+        raise ValueError(f"stream checkpoint: {key!r} must be one string, got {a.dtype} {a.shape}")
+    return str(a)
+
+
+def _ckpt_format(sd) -> None:
+    fmt = _ckpt_int(sd, "format")
+    if fmt != STREAM_CHECKPOINT_FORMAT:
+        raise ValueError(f"stream checkpoint: format = {fmt} is not known to this version (it reads format "
+                         f"{STREAM_CHECKPOINT_FORMAT})")
+
+
+def stream_checkpoint_config(sd) -> dict:
+    """The configuration a checkpoint was saved under (`_CKPT_CONFIG`) as Python values; a missing or mistyped field
+    is refused by name.  Host data only."""
+    cfg = {k: _ckpt_str(sd, k) if k in _CKPT_STRS else _ckpt_int(sd, k) for k in _CKPT_CONFIG}
+    if cfg["calib"] not in ("tick", "sensor"):
+        raise ValueError(f"stream checkpoint: calib = {cfg['calib']!r}: 'tick' or 'sensor'")
+    return cfg
+
+
+def stream_checkpoint_check(sd, expect) -> None:
+    """Refuse a checkpoint dict `sd` (StreamDetector.state_dict() or a loaded file) that the loader cannot continue,
+    with a ValueError that names the field.  `expect` holds the loader's own facts: "n", "w" (the model's), "abi"
+    (the loaded library's ABI version), "state_bytes" = gdn_stream_state_bytes(n, w) and "calib_bytes" =
+    gdn_stream_calib_bytes(n, R) for the file's R (0 without a ring) as the loaded library reports them, "model" (its
+    model_fingerprint, or None: do not compare), "prep_down" (the caller's Prep.down, or None: no prep) and "prep_n".
+    Host data only: no device work, no library call."""
+    _ckpt_format(sd)
+    ints = {k: _ckpt_int(sd, k) for k in _CKPT_INTS}
+    strs = {k: _ckpt_str(sd, k) for k in _CKPT_STRS}
+    cfg = stream_checkpoint_config(sd)
+    for k in ("n", "w"):                                    # (first: the byte sizes below are those of the model's n, w)
+        if ints[k] != int(expect[k]):
+            raise ValueError(f"stream checkpoint: {k} = {ints[k]}, the model has {k} = {int(expect[k])}")
+    for k in ("abi", "state_bytes", "calib_bytes"):
+        if ints[k] != int(expect[k]):
+            raise ValueError(f"stream checkpoint: {k} = {ints[k]} was saved by another build of the library (this one "
+                             f"has {k} = {int(expect[k])}); the state's layout is not known to agree")
+    down = expect.get("prep_down")
+    if bool(ints["prep"]) != (down is not None):
+        raise ValueError("stream checkpoint: prep: the detector was saved " + ("with" if ints["prep"] else "without")
+                         + " a raw-readings front end and is resumed " + ("without one (pass prep=)" if ints["prep"]
+                                                                          else "with one (pass prep=None)"))
+    if down is not None:
+        if ints["prep_down"] != int(down):
+            raise ValueError(f"stream checkpoint: prep_down = {ints['prep_down']}, the prep given has down = {int(down)}")
+        if int(expect.get("prep_n", ints["n"])) != ints["n"]:
+            raise ValueError(f"stream checkpoint: prep: fitted on {int(expect['prep_n'])} sensors, n = {ints['n']}")
+    elif ints["prep_down"] != 0:
+        raise ValueError(f"stream checkpoint: prep_down = {ints['prep_down']} without a prep")
+    if expect.get("model") is not None and strs["model_sha256"] != expect["model"]:
+        raise ValueError("stream checkpoint: model_sha256 differs from the model given: the scores are the model's, so "
+                         "resuming under other weights changes the alarm rate (check_model=False resumes all the same)")
+    n, R, m, log = ints["n"], ints["recal"], ints["top_m"], ints["log"]
+    pend_rows = ints["raw_pending"]
+    if not 0 <= pend_rows < max(1, ints["prep_down"]):
+        raise ValueError(f"stream checkpoint: raw_pending = {pend_rows} outside an open group of prep_down = "
+                         f"{ints['prep_down']} raw ticks")
+    for k in ("handed", "recals", "recal_kept", "log", "recal", "recal_every", "recal_min"):
+        if ints[k] < 0:
+            raise ValueError(f"stream checkpoint: {k} = {ints[k]} is negative")
+    if ints["calib_kept"] < -1:
+        raise ValueError(f"stream checkpoint: calib_kept = {ints['calib_kept']} (-1: none)")
+    want = {"state": (np.uint8, (ints["state_bytes"],)), "med_iqr": (np.float64, (n, 2)),
+            "threshold": (np.float64, (1,)), "log_ticks": (np.int64, (log,)), "log_sensors": (np.int32, (log, m))}
+    if cfg["with_gaps"]:
+        want["gaps"] = (np.int64, (2, n))
+    if R:
+        want["ring_keys"], want["ring_keep"] = (np.float64, (n, R)), (np.uint8, (R,))
+    if cfg["prep"]:
+        want["pending"] = (np.float64, (pend_rows, n))
+    optional = {"calib_counts": (np.int32, (n,)), "recal_counts": (np.int64, (n,))}
+    for k in sd:
+        if k not in want and k not in optional and k not in _CKPT_INTS and k not in _CKPT_STRS:
+            raise ValueError(f"stream checkpoint: key {k!r} does not belong to this configuration (a foreign file)")
+    for k, (dtype, shape) in list(want.items()) + [(k, v) for k, v in optional.items() if k in sd]:
+        if k not in sd:
+            raise ValueError(f"stream checkpoint: key {k!r} is missing (a truncated or foreign file)")
+        a = np.asarray(sd[k])
+        if a.dtype != dtype or a.shape != shape:
+            raise ValueError(f"stream checkpoint: {k!r} must be {np.dtype(dtype)} {shape} under this configuration, got "
+                             f"{a.dtype} {a.shape}")
+
+
+def write_stream_checkpoint(path: str, sd) -> None:
+    """`sd` as ONE .npz at exactly `path` (numpy.savez; no suffix is appended): written to path + ".tmp" beside it, made
+    durable, then moved over `path` with os.replace, so a process that dies in the middle of a save leaves the
+    previous checkpoint as it was."""
+    tmp = path + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            np.savez(f, **sd)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        with contextlib.suppress(OSError):
+            os.unlink(tmp)
+        raise
+
+
+def read_stream_checkpoint(path: str) -> dict:
+    """The arrays of a checkpoint file (allow_pickle=False: it holds no Python objects)."""
+    with np.load(path, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
 class StreamDetector:
     """Scores ticks as they arrive against a frozen calibration, with nothing but launches per push.
 
@@ -1737,12 +1905,27 @@ class StreamDetector:
     carries up to chunk * down raw ticks (`raw_push_plan`); one that completes no group issues that one launch and
     scores nothing; one that starts on a group boundary with exactly chunk * down raw ticks is ONE copy and ONE replay
     of a graph captured with the front end in it.  A prep= detector pushed raw ticks writes the bits a plain one
-    writes when pushed prep.series(raw).t(); prep=None issues exactly the launches it always did."""
+    writes when pushed prep.series(raw).t(); prep=None issues exactly the launches it always did.
+
+    `save(path)` / `StreamDetector.load(path, model, prep=)` (`state_dict()` / `load_state_dict(sd)` through
+    a dict of numpy arrays) carry a running detector across a process boundary: the state, the table in force, the
+    threshold, the log, the gap counters, the ring, the open group's raw ticks, the host counters and the configuration
+    go into one .npz; the static buffers of a push, the workspaces and the graphs do not.  A stream cut by a save and a
+    load writes the bits of the uninterrupted stream; a push before a save and after a load issues the launches it
+    always did."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
                  calib: str = "tick", prep=None):
+        self._build(model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, recal,
+                    exclude_alarms, recal_every, recal_min, calib, prep)
+
+    def _build(self, model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, recal,
+               exclude_alarms, recal_every, recal_min, calib, prep, device=None):
+        """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — the state is
+        gdn_stream_state_bytes(n, w) of zeros, the table zeros, the threshold inf, all on `device`, `wide` the
+        caller's word — and load_state_dict fills the allocations."""
         if calib not in ("tick", "sensor"):
             raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
         if calib == "sensor" and not (gaps and int(recal) > 0):
@@ -1781,21 +1964,29 @@ class StreamDetector:
             raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
         if model.out_layer_num > 1 and not ops.mlp_fast_tail_supported(model.out_layer, model.embedding.weight.shape[1]):
             raise model._refusal("refuse_outlayer")        # (GDN.mlp_fast_path_supported's answer, from host facts)
-        history = ops._chk(history, name="history")
-        if history.dim() != 2 or history.shape[0] != n:
-            raise ValueError(f"expected a history of shape [{n}, h], got {tuple(history.shape)}")
-        dev = history.device
-        med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr")
-        if med_iqr.shape != (n, 2):
-            raise ValueError(f"expected med_iqr of shape [{n}, 2], got {tuple(med_iqr.shape)}")
-        self.med_iqr = med_iqr.clone()
-        self.threshold = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev).clone()
         self.with_gaps = bool(gaps)
-        if self.with_gaps and history.shape[1] >= w and not bool(torch.isfinite(history[:, -w:]).all()):
-            raise ValueError(f"history: its last {w} ticks hold a value that is not finite; with gaps=True every "
-                             "missing reading is held at an earlier real one, so the stream must begin on real readings")
-        self.state = ops.stream_state(history, w)
-        self.wide = model.wide_for(history[:, -w:]) if wide is None else bool(wide)
+        if history is None:
+            dev = torch.empty((0,), device=device).device           # ("cuda" -> the current device, with its index)
+            self.med_iqr = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+            self.threshold = torch.full((1,), float("inf"), dtype=torch.float64, device=dev)
+            self.state = ops.stream_state_empty(n, w, dev)
+            self.wide = bool(wide)
+        else:
+            history = ops._chk(history, name="history")
+            if history.dim() != 2 or history.shape[0] != n:
+                raise ValueError(f"expected a history of shape [{n}, h], got {tuple(history.shape)}")
+            dev = history.device
+            med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr")
+            if med_iqr.shape != (n, 2):
+                raise ValueError(f"expected med_iqr of shape [{n}, 2], got {tuple(med_iqr.shape)}")
+            self.med_iqr = med_iqr.clone()
+            self.threshold = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev).clone()
+            if self.with_gaps and history.shape[1] >= w and not bool(torch.isfinite(history[:, -w:]).all()):
+                raise ValueError(f"history: its last {w} ticks hold a value that is not finite; with gaps=True every "
+                                 "missing reading is held at an earlier real one, so the stream must begin on real "
+                                 "readings")
+            self.state = ops.stream_state(history, w)
+            self.wide = model.wide_for(history[:, -w:]) if wide is None else bool(wide)
         c, m = self.chunk, self.top_m
         self.chunk_buf = torch.zeros((c, n), dtype=torch.float32, device=dev)
         self.x = torch.zeros((c, n, w), dtype=torch.float32, device=dev)
@@ -2092,3 +2283,141 @@ class StreamDetector:
         first = self.state[0] - r                       # (advance has run: ticks counts the push already)
         return _localisation(self.model, self.x, first + rows, rows, self.top_sensors[rows].long(), self.top_scores[rows],
                              self.pred, self.chunk_buf)
+
+    # save and resume: a stream cut by a save and a load writes the bits of the uninterrupted stream
+    def _config(self) -> dict:
+        return {"n": self.n, "w": self.w, "chunk": self.chunk, "top_m": self.top_m,
+                "log": 0 if self.log_ticks is None else self.log_ticks.numel(), "with_gaps": int(self.with_gaps),
+                "recal": self.recal, "exclude_alarms": int(self.exclude_alarms), "recal_every": self.recal_every,
+                "recal_min": self.recal_min, "calib": self.calib, "wide": int(self.wide),
+                "prep": int(self.prep is not None), "prep_down": 0 if self.prep is None else self.prep.down}
+
+    def _expect(self, check_model: bool = True) -> dict:
+        """stream_checkpoint_check's `expect` for this detector: its model's shape and fingerprint, its prep, and the
+        loaded library's ABI version and byte sizes."""
+        return _checkpoint_expect(self.model, self.prep, self.recal, check_model)
+
+    def state_dict(self) -> dict:
+        """Everything a continuation of this stream depends on, as a flat dict of numpy arrays (no Python objects:
+        numpy.savez writes it, numpy.load(allow_pickle=False) reads it): the device state as raw bytes, the table in
+        force, the threshold, the alarm log, the gap counters, the calibration ring, the raw ticks of the open
+        downsample group; the host counters; the configuration; and the identity of what wrote it (format, ABI version,
+        byte sizes, the model's fingerprint).  The static buffers of a push, the workspaces and the captured graphs are
+        outputs or scratch and stay behind.  Read-only: ONE batch of device-to-host copies on the current stream and
+        ONE synchronisation; the pushes after it write the bits they would have written."""
+        lib = _lib.load()
+        n, m = self.n, self.top_m
+        cfg = self._config()
+        dev = {"state": self.state.view(torch.uint8), "med_iqr": self.med_iqr,
+               "threshold": torch.as_tensor(self.threshold, dtype=torch.float64).reshape(1)}
+        if self.log_ticks is not None:
+            dev["log_ticks"], dev["log_sensors"] = self.log_ticks, self.log_sensors
+        if self.with_gaps:
+            dev["gaps"] = self.gaps
+        if self.recal:
+            dev["ring_keys"], dev["ring_keep"] = self.ring_keys, self.ring_keep
+        if self.prep is not None:
+            dev["pending"] = self._pend[self._pend_at][:self.raw_pending]
+        if self.calib_counts is not None:
+            dev["calib_counts"] = self.calib_counts
+        weights = self.model.state_dict()
+        names = sorted(weights)
+        host = _host_copies(list(dev.values()) + [weights[k] for k in names])
+        torch.cuda.current_stream().synchronize()
+        sd = {k: t.numpy() for k, t in zip(dev, host)}
+        if self.log_ticks is None:
+            sd["log_ticks"], sd["log_sensors"] = np.zeros((0,), np.int64), np.zeros((0, m), np.int32)
+        if self.recal_counts is not None:
+            sd["recal_counts"] = self.recal_counts.to(torch.int64).numpy().copy()
+        ints = {"format": STREAM_CHECKPOINT_FORMAT, "abi": lib.gdn_abi_version(),
+                "state_bytes": lib.gdn_stream_state_bytes(n, self.w),
+                "calib_bytes": lib.gdn_stream_calib_bytes(n, self.recal) if self.recal else 0,
+                "handed": self._handed, "recals": self.recals, "recal_kept": self.recal_kept,
+                "calib_kept": -1 if self.calib_kept is None else int(self.calib_kept), "raw_pending": self.raw_pending}
+        ints.update({k: v for k, v in cfg.items() if k != "calib"})
+        sd.update({k: np.array(int(ints[k]), dtype=np.int64) for k in _CKPT_INTS})
+        sd["calib"] = np.array(self.calib)
+        sd["model_sha256"] = np.array(_fingerprint(names, host[len(dev):]))
+        return sd
+
+    def load_state_dict(self, sd, check_model: bool = True) -> None:
+        """Take the stream of `sd` (state_dict()'s dict, or a file's) up where it was saved.  `sd` is checked first
+        (stream_checkpoint_check, and its configuration against this detector's own, field by field: a ValueError that
+        names the field, before any device work); the captured graphs are dropped; then every array is copied INTO the
+        allocations this detector already has, so the pointers a later capture records are the ones it always had.
+        Afterwards the last push is empty (`valid[:0]`, `localise()` with no rows) and the first full push captures
+        the graph again."""
+        stream_checkpoint_check(sd, self._expect(check_model))
+        cfg = stream_checkpoint_config(sd)
+        for k, mine in self._config().items():
+            if cfg[k] != mine:
+                raise ValueError(f"stream checkpoint: {k} = {cfg[k]!r}, this detector was built with {k} = {mine!r}")
+        self.graph = None                                   # (outside any capture: ADVICE, third finding)
+        self._graph_key = None
+        if self.prep is not None:
+            self._prep_graphs.clear()
+
+        def host(key):
+            return torch.from_numpy(np.array(sd[key]))      # (a copy: numpy.load may hand out read-only arrays)
+        self.state.view(torch.uint8).copy_(host("state"))
+        self.med_iqr.copy_(host("med_iqr"))
+        if not isinstance(self.threshold, torch.Tensor):    # (a caller's plain number: back to the device scalar)
+            self.threshold = torch.zeros((1,), dtype=torch.float64, device=self.state.device)
+        self.threshold.view(-1).copy_(host("threshold"))
+        if self.log_ticks is not None:
+            self.log_ticks.copy_(host("log_ticks"))
+            self.log_sensors.copy_(host("log_sensors"))
+        if self.with_gaps:
+            self.gaps.copy_(host("gaps"))
+        if self.recal:
+            self.ring_keys.copy_(host("ring_keys"))
+            self.ring_keep.copy_(host("ring_keep"))
+        self.raw_pending = _ckpt_int(sd, "raw_pending")
+        if self.prep is not None:
+            self._pend_at = 0
+            self._pend[0][:self.raw_pending].copy_(host("pending"))
+        self.calib_counts = host("calib_counts").to(self.state.device) if "calib_counts" in sd else None
+        self.recal_counts = host("recal_counts") if "recal_counts" in sd else None
+        kept = _ckpt_int(sd, "calib_kept")
+        self.calib_kept = None if kept < 0 else kept
+        self._handed, self.recals = _ckpt_int(sd, "handed"), _ckpt_int(sd, "recals")
+        self.recal_kept = _ckpt_int(sd, "recal_kept")
+        self._last = 0
+
+    def save(self, path: str) -> None:
+        """state_dict() as one .npz at exactly `path` (write_stream_checkpoint: a temporary file beside it, then
+        os.replace — a save that dies half-way leaves the previous checkpoint loadable)."""
+        write_stream_checkpoint(path, self.state_dict())
+
+    @classmethod
+    def load(cls, path: str, model, prep=None, device="cuda", check_model: bool = True, use_graph: bool = True):
+        """A detector that continues the stream saved at `path`: built from the file's configuration, the caller's
+        `model` and — when the file says one was used — `prep` (on `device`), with no history (nothing is seeded),
+        then load_state_dict.  Refused with a ValueError that names the field, before any device work: an unknown
+        format, another ABI version or byte size, another n or w, a prep against the file's word or with another down,
+        other weights (unless check_model=False), a missing key or an array of the wrong shape or dtype."""
+        sd = read_stream_checkpoint(path)
+        _ckpt_format(sd)                                    # (an unknown format first: its other fields may differ)
+        R = _ckpt_int(sd, "recal")
+        if R < 0:
+            raise ValueError(f"stream checkpoint: recal = {R} is negative")
+        stream_checkpoint_check(sd, _checkpoint_expect(model, prep, R, check_model))
+        cfg = stream_checkpoint_config(sd)
+        det = cls.__new__(cls)
+        det._build(model, None, None, None, cfg["chunk"], cfg["top_m"], cfg["log"], use_graph, bool(cfg["wide"]),
+                   bool(cfg["with_gaps"]), cfg["recal"], bool(cfg["exclude_alarms"]), cfg["recal_every"],
+                   cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, device=device)
+        det.load_state_dict(sd, check_model=False)          # (the weights were compared above, once)
+        return det
+
+
+def _checkpoint_expect(model, prep, recal: int, check_model: bool = True) -> dict:
+    """The loader's own facts for stream_checkpoint_check: host arithmetic and host library calls, plus ONE batch read
+    of the model's tensors for its fingerprint when `check_model`."""
+    lib = _lib.load()
+    w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+    n = model.embedding.weight.shape[0]
+    return {"n": n, "w": w, "abi": lib.gdn_abi_version(), "state_bytes": lib.gdn_stream_state_bytes(n, w),
+            "calib_bytes": lib.gdn_stream_calib_bytes(n, recal) if recal else 0,
+            "model": model_fingerprint(model) if check_model else None,
+            "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n}

@@ -224,12 +224,14 @@ class Main:
                                     recal_every=int(self.env_config.get("stream_recal_every") or 0),
                                     by_sensor=bool(self.env_config.get("calib_by_sensor")),
                                     raw_path=self.env_config.get("stream_raw") or "",
-                                    prep_path=self.env_config.get("prep") or "")
+                                    prep_path=self.env_config.get("prep") or "",
+                                    save_path=self.env_config.get("stream_save") or "",
+                                    resume_path=self.env_config.get("stream_resume") or "")
         return info
 
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
                            recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False,
-                           raw_path: str = "", prep_path: str = ""):
+                           raw_path: str = "", prep_path: str = "", save_path: str = "", resume_path: str = ""):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
@@ -249,9 +251,15 @@ class Main:
         columns as list.txt names them) from raw tick slide_win * down on, pushed C * down at a time through a prep=
         detector (gdn_amd.prep.Prep: min-max table and median downsample on the device); the calibration and the
         history are the prepared series' as before.  "raw_ticks" (pushed) and "raw_pending" (left in an open group)
-        join the line and `stream_result`."""
+        join the line and `stream_result`.
+        -stream_save PATH: the detector is saved (StreamDetector.save) when the replay ends.
+        -stream_resume PATH: the detector is StreamDetector.load(PATH) and not a fresh calibration: its configuration
+        (gaps, ring, calibration rule, chunk) is the file's, -stream C only sizes the pushes, and the replay goes on at
+        the tick the file's counters say has been consumed (of a -stream_raw file: model ticks * down + raw_pending);
+        that tick joins the line and `stream_result` ("resumed_from")."""
         check_calib_by_sensor(by_sensor, bool(chunk), gaps, calib_gaps)
         check_stream_raw(bool(raw_path), bool(chunk), bool(prep_path))
+        check_stream_checkpoint(bool(save_path), bool(resume_path), bool(chunk))
         w = self.train_config["slide_win"]
         lo, hi = int(val_ticks.min()), int(val_ticks.max())
         normal = self.train_series[:, lo - w:hi + 1].contiguous()
@@ -273,25 +281,42 @@ class Main:
             ticks = torch.from_numpy(raw_np[w * rolling["prep"].down:]).to(self.device)
         else:
             ticks = self.test_series[:, w:].t().contiguous()
-        det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
-                                                      top_m=min(3, normal.shape[0]), gaps=gaps, **rolling)
+        resumed = None
+        if resume_path:
+            det = harness.StreamDetector.load(resume_path, model, prep=rolling.get("prep"), device=self.device)
+            resumed = det.status()[0]
+            gaps, recal = det.with_gaps, det.recal          # the file's configuration, whatever the other flags say
+            calib_gaps, by_sensor = det.calib_kept is not None, det.calib_counts is not None
+            at = resumed * det.prep.down + det.raw_pending if raw_path else resumed
+            if at > ticks.shape[0]:
+                raise ValueError(f"-stream_resume {resume_path}: the checkpoint has consumed {at} ticks, the replayed "
+                                 f"file holds {ticks.shape[0]}")
+            ticks = ticks[at:]
+        else:
+            det = harness.StreamDetector.from_calibration(model, normal, chunk, history=self.test_series[:, :w],
+                                                          top_m=min(3, normal.shape[0]), gaps=gaps, **rolling)
         for s in range(0, ticks.shape[0], step):
             det.push(ticks[s:s + step])
+        if save_path:
+            det.save(save_path)
         scored, alarms, log_ticks, log_sensors = det.status()[:4]
         self.stream_result = {"chunk": chunk, "threshold": float(det.threshold.item()), "ticks": scored,
                               "alarms": alarms, "log_ticks": log_ticks.cpu().numpy(),
                               "log_sensors": log_sensors.cpu().numpy()}
         held = ""
+        if resumed is not None:
+            self.stream_result["resumed_from"] = resumed
+            held = f"; resumed at tick {resumed} of the stream"
         if raw_path:
             self.stream_result["raw_ticks"], self.stream_result["raw_pending"] = int(ticks.shape[0]), det.raw_pending
-            held = (f"; from {ticks.shape[0]} raw ticks, {rolling['prep'].down} to a tick, {det.raw_pending} left in an "
-                    "open group")
+            held += (f"; from {ticks.shape[0]} raw ticks, {rolling['prep'].down} to a tick, {det.raw_pending} left in "
+                     "an open group")
         if gaps:
             missing_total, _run = det.status_gaps()
             self.stream_result["gap_sensors"] = int((missing_total > 0).sum())
             self.stream_result["missing"] = int(missing_total.sum())
-            held = (f"; {self.stream_result['missing']} missing readings held on "
-                    f"{self.stream_result['gap_sensors']} sensors")
+            held += (f"; {self.stream_result['missing']} missing readings held on "
+                     f"{self.stream_result['gap_sensors']} sensors")
         if by_sensor:
             lo_c, hi_c = torch.stack([det.calib_counts.min(), det.calib_counts.max()]).tolist()
             self.stream_result["calib_kept"] = det.calib_kept
@@ -309,8 +334,9 @@ class Main:
                      + (f", the last from at least {det.recal_kept} real readings per sensor"
                         if det.recal_kept and by_sensor else ""))
         first = ", ".join(str(int(t) + w) for t in self.stream_result["log_ticks"][:show])
-        print(f"stream: {scored} ticks in pushes of {chunk}, threshold {self.stream_result['threshold']:.6g} from "
-              f"{normal.shape[1] - w} validation ticks: {alarms} alarm ticks" + held
+        origin = f"from {normal.shape[1] - w} validation ticks" if resumed is None else f"from {resume_path}"
+        print(f"stream: {scored} ticks in pushes of {chunk}, threshold {self.stream_result['threshold']:.6g} "
+              f"{origin}: {alarms} alarm ticks" + held
               + (f"; first at test ticks {first}" if alarms else "") + "\n")
         return self.stream_result
 
@@ -368,7 +394,7 @@ class Main:
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
     -train_gaps / -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every /
-    -stream_raw / -prep."""
+    -stream_raw / -prep / -stream_save / -stream_resume."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -413,7 +439,20 @@ def build_parser():
                         type=str, default="")
     parser.add_argument("-prep", help="the prep.npz `python -m gdn_amd.prep` wrote (min-max table, down, sensor names)",
                         type=str, default="")
+    parser.add_argument("-stream_save", help="with -stream: save the running detector to this .npz when the replay ends "
+                        "(the file is written exactly here; no suffix is appended)", type=str, default="")
+    parser.add_argument("-stream_resume", help="with -stream: start from this saved detector instead of a calibration on "
+                        "the validation block, and go on at the tick it had consumed", type=str, default="")
     return parser
+
+
+def check_stream_checkpoint(stream_save: bool, stream_resume: bool, stream: bool) -> None:
+    """-stream_save and -stream_resume name the file a streaming detector is saved to or resumed from: they mean
+    something only with -stream C (the detector).  Refused by name otherwise."""
+    if stream_save and not stream:
+        raise ValueError("-stream_save needs -stream C: the file holds the streaming detector the replay leaves behind")
+    if stream_resume and not stream:
+        raise ValueError("-stream_resume needs -stream C: the file holds a streaming detector, which the replay continues")
 
 
 def check_stream_raw(stream_raw: bool, stream: bool, prep: bool) -> None:
@@ -448,6 +487,7 @@ def from_args(argv=None) -> Main:
     check_train_gaps(args.train_gaps, not args.no_hip_graph)
     check_calib_by_sensor(args.calib_by_sensor, bool(args.stream), args.stream_gaps, args.stream_calib_gaps)
     check_stream_raw(bool(args.stream_raw), bool(args.stream), bool(args.prep))
+    check_stream_checkpoint(bool(args.stream_save), bool(args.stream_resume), bool(args.stream))
     random.seed(args.random_seed)                      # main.py:221-228
     np.random.seed(args.random_seed)
     torch.manual_seed(args.random_seed)
@@ -464,7 +504,8 @@ def from_args(argv=None) -> Main:
                   "localise": args.localise, "stream": args.stream,
                   "stream_gaps": args.stream_gaps, "stream_calib_gaps": args.stream_calib_gaps, "stream_recal": args.stream_recal,
                   "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor,
-                  "stream_raw": args.stream_raw, "prep": args.prep}
+                  "stream_raw": args.stream_raw, "prep": args.prep, "stream_save": args.stream_save,
+                  "stream_resume": args.stream_resume}
     return Main(train_config, env_config, debug=False)
 
 

@@ -1044,6 +1044,15 @@ def stream_state(history, w: int) -> torch.Tensor:
     return state
 
 
+def stream_state_empty(n: int, w: int, device) -> torch.Tensor:
+    """A stream state of gdn_stream_state_bytes(n, w) / 8 zero words that no history has seeded: the allocation a saved
+    state is copied into (harness.StreamDetector.load).  No launch."""
+    nbytes = _lib.load().gdn_stream_state_bytes(n, w)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"stream state: no kernel for n = {n}, w = {w} (1 <= n <= 4096, 1 <= w <= 1024)")
+    return torch.zeros((nbytes // 8,), dtype=torch.int64, device=device)
+
+
 def stream_state_views(state, n: int, w: int):
     """(counters int64[3] = ticks, alarms, logged; carry float64 [3, n]; hist fp32 [n, w]): views of a stream state."""
     carry = state[4:4 + 3 * n].view(torch.float64).view(3, n)
