@@ -132,6 +132,13 @@ SIGNATURES = {
     "gdn_prep_stats": [_p, ctypes.c_longlong, _c_int, _c_int, _p, _p, _p],
     "gdn_prep_series": [_p, ctypes.c_longlong, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p],
     "gdn_prep_ticks": [_p, _c_int, _c_int, _p, _c_int, _p, _c_int, _c_int, _p, _p, _c_int, _p],
+    "gdn_episodes_workspace_bytes": [ctypes.c_longlong, ctypes.c_longlong],
+    "gdn_episodes_scan": [_p, _p, ctypes.c_longlong, _c_int, ctypes.c_double, ctypes.c_double, _c_int, _c_int,
+                          ctypes.c_longlong, ctypes.c_longlong] + [_p] * 10,
+    "gdn_episodes_scan_grid": [_p, _p, ctypes.c_longlong, _c_int, ctypes.c_double, ctypes.c_double, _c_int, _c_int,
+                               ctypes.c_longlong, ctypes.c_longlong] + [_p] * 9 + [_c_int, _p],
+    "gdn_stream_events_bytes": [_c_int, ctypes.c_longlong],
+    "gdn_stream_events": [_p] * 5 + [_c_int] * 5 + [ctypes.c_longlong, _p, _p],
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

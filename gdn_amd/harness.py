@@ -812,6 +812,54 @@ def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localis
                          ev.pred, ev.y)
 
 
+# --------------------------------------------------------------------------- alarm episodes
+class Episodes(NamedTuple):
+    """An episode table, device tensors of `cap` rows of which the first min(count, cap) are written:
+    one row per incident — first tick, first tick of the clearing run (exclusive; -1 while the episode is open), the
+    largest score, the first tick that holds it and the top sensors of that tick.  Ticks are global."""
+    start: torch.Tensor          # [cap] int64
+    end: torch.Tensor            # [cap] int64
+    peak: torch.Tensor           # [cap] float64
+    peak_tick: torch.Tensor      # [cap] int64
+    sensors: torch.Tensor        # [cap, m] int32
+    count: torch.Tensor          # [1] int64: episodes raised, beyond cap too
+
+    def numpy(self) -> dict:
+        """The written rows on the host (ONE synchronisation); `count` as a Python int."""
+        count = int(self.count.item())
+        rows = min(count, self.start.shape[0])
+        out = {name: getattr(self, name)[:rows].cpu().numpy() for name in self._fields[:-1]}
+        out["count"] = count
+        return out
+
+
+def episodes(scores, top_sensors=None, hi=None, lo=None, on: int = 1, off: int = 1, cap: int = 4096,
+             first_tick: int = 0) -> Episodes:
+    """The alarm episodes of a scored series: `scores` [T] float64 and `top_sensors` [T, m] int32 on
+    the device, raised after `on` ticks above `hi`, cleared after `off` ticks at or below `lo` (None: hi).  Or
+    `episodes(evaluator, hi, ...)` for a SeriesEvaluator built with top_m= whose step() has run: its top_scores[:, 0] and
+    top_sensors; the peak ticks go straight into `localise(evaluator, ticks)`.  One gdn_episodes_scan (five launches,
+    parallel over T), no synchronisation."""
+    if isinstance(scores, SeriesEvaluator):
+        ev = scores
+        if isinstance(top_sensors, torch.Tensor) and top_sensors.dim() > 0:
+            raise ValueError("episodes(evaluator, hi, ...): the evaluator brings its own top_sensors")
+        if top_sensors is not None:                         # episodes(evaluator, hi[, lo]): the levels move up one place;
+            if hi is not None and lo is not None:           # what follows them goes by keyword
+                raise ValueError("episodes(evaluator, hi, lo, on=, off=, cap=, first_tick=)")
+            top_sensors, hi, lo = None, top_sensors, (hi if lo is None else lo)
+        if not ev.top_m:
+            raise ValueError("episodes needs an evaluator built with top_m >= 1")
+        scores, top_sensors = ev.top_scores[:, 0].contiguous(), ev.top_sensors
+    if hi is None or top_sensors is None:
+        raise ValueError("episodes(scores, top_sensors, hi, ...): the raise level hi and top_sensors are needed")
+    hi, lo, on, off, cap = ops.episodes_check(hi, lo, on, off, cap)
+    if int(first_tick) < 0:
+        raise ValueError(f"first_tick = {first_tick} is negative")
+    start, end, peak_tick, peak, sensors, count = ops.episodes_scan(scores, top_sensors, hi, lo, on, off, cap, first_tick)
+    return Episodes(start, end, peak, peak_tick, sensors, count)
+
+
 # --------------------------------------------------------------------------- graphed train step
 class _CapturedStep:
     """One optimisation step of the reference's train() (train.py:52-79) issued as two halves: `_first` (the caller's
@@ -1815,6 +1863,22 @@ def stream_checkpoint_check(sd, expect) -> None:
         want["ring_keys"], want["ring_keep"] = (np.float64, (n, R)), (np.uint8, (R,))
     if cfg["prep"]:
         want["pending"] = (np.float64, (pend_rows, n))
+    events = stream_checkpoint_events(sd)
+    if "events" in expect:                                  # (load() builds the detector from the file: nothing to compare)
+        mine = expect["events"]
+        if (events is None) != (mine is None):
+            raise ValueError("stream checkpoint: events: the detector was saved " + ("without" if events is None else "with")
+                             + " an episode table and is resumed " + ("with one (pass events=None)" if events is None
+                                                                      else "without one (pass events=)"))
+        for k in _EVENTS_FIELDS if events is not None else ():
+            if events[k] != int(mine[k]):
+                raise ValueError(f"stream checkpoint: events.{k} = {events[k]}, this detector was built with "
+                                 f"events.{k} = {int(mine[k])}")
+    if events is not None:
+        if events["m"] != m:
+            raise ValueError(f"stream checkpoint: events.m = {events['m']}, top_m = {m}")
+        want["events"] = (np.uint8, (events_bytes(m, events["cap"]),))
+        want["events_lo"], want["events_cfg"] = (np.float64, (1,)), (np.int64, (len(_EVENTS_FIELDS),))
     optional = {"calib_counts": (np.int32, (n,)), "recal_counts": (np.int64, (n,))}
     for k in sd:
         if k not in want and k not in optional and k not in _CKPT_INTS and k not in _CKPT_STRS:
@@ -1826,6 +1890,48 @@ def stream_checkpoint_check(sd, expect) -> None:
         if a.dtype != dtype or a.shape != shape:
             raise ValueError(f"stream checkpoint: {k!r} must be {np.dtype(dtype)} {shape} under this configuration, got "
                              f"{a.dtype} {a.shape}")
+
+
+_EVENTS_FIELDS = ("on", "off", "cap", "m")
+
+
+def events_bytes(m: int, cap: int) -> int:
+    """gdn_stream_events_bytes(m, cap) by host arithmetic: the carry, four 8-byte columns and the sensors."""
+    return (160 + 32 * cap + 4 * cap * m + 7) & ~7
+
+
+def events_config(events, m: int) -> dict:
+    """StreamDetector's events=dict(on=, off=, lo=, cap=) checked on the host and completed: {"on", "off", "cap", "m",
+    "lo"} with on = off = 1, cap = 4096 and lo = None (the raise level) by default; an unknown key is refused by name."""
+    unknown = sorted(set(events) - {"on", "off", "lo", "cap"})
+    if unknown:
+        raise ValueError(f"events: unknown key {unknown[0]!r} (on, off, lo, cap)")
+    _, lo, on, off, cap = ops.episodes_check(None, events.get("lo"), events.get("on", 1), events.get("off", 1),
+                                             events.get("cap", 4096))
+    return {"on": on, "off": off, "cap": cap, "m": int(m), "lo": lo}
+
+
+def stream_checkpoint_events(sd):
+    """The events configuration of a checkpoint ({"on", "off", "cap", "m", "lo"}), None for a file saved without an
+    episode table; the three optional keys come together or not at all.  Host data only."""
+    keys = [k for k in ("events", "events_cfg", "events_lo") if k in sd]
+    if not keys:
+        return None
+    if len(keys) != 3:
+        raise ValueError(f"stream checkpoint: key {keys[0]!r} without the rest of events, events_cfg, events_lo (a "
+                         "truncated or foreign file)")
+    cfg, lo = np.asarray(sd["events_cfg"]), np.asarray(sd["events_lo"])
+    if cfg.dtype != np.int64 or cfg.shape != (len(_EVENTS_FIELDS),):
+        raise ValueError(f"stream checkpoint: 'events_cfg' must be int64 ({len(_EVENTS_FIELDS)},), got {cfg.dtype} "
+                         f"{cfg.shape}")
+    if lo.dtype != np.float64 or lo.shape != (1,):
+        raise ValueError(f"stream checkpoint: 'events_lo' must be float64 (1,), got {lo.dtype} {lo.shape}")
+    out = {k: int(v) for k, v in zip(_EVENTS_FIELDS, cfg)}
+    if not (1 <= out["on"] <= 4096 and 1 <= out["off"] <= 4096 and 0 <= out["cap"] <= 1 << 20 and 1 <= out["m"] <= 8):
+        raise ValueError(f"stream checkpoint: events_cfg = {out} outside 1 <= on, off <= 4096, 0 <= cap <= 2^20, "
+                         "1 <= m <= 8")
+    out["lo"] = float(lo[0])
+    return out
 
 
 def write_stream_checkpoint(path: str, sd) -> None:
@@ -1912,17 +2018,26 @@ class StreamDetector:
     threshold, the log, the gap counters, the ring, the open group's raw ticks, the host counters and the configuration
     go into one .npz; the static buffers of a push, the workspaces and the graphs do not.  A stream cut by a save and a
     load writes the bits of the uninterrupted stream; a push before a save and after a load issues the launches it
-    always did."""
+    always did.
+
+    `events=dict(on=, off=, lo=, cap=)` turns the flag per tick into an event list: an episode is raised
+    after `on` ticks above `threshold` (read on the device through the pointer the score launch reads) and cleared after
+    `off` ticks at or below the clear level `lo` (a float64 scalar on the device, `clear`; None: the threshold at
+    construction).  gdn_stream_events sits between the score and the advance launch (captured with them) and writes only
+    its own allocation, `events`: the carried state and a table of `cap` rows (default 4096) that `episodes()` returns;
+    `status()` then ends with (episodes, episode_open).  The table equals harness.episodes on the evaluator's scores of
+    [history[:, -w:] | stream], bit for bit, however the stream is cut into pushes or by save / load.  The default
+    events=None constructs, pushes, saves and loads exactly as it always did."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
-                 calib: str = "tick", prep=None):
+                 calib: str = "tick", prep=None, events=None):
         self._build(model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, recal,
-                    exclude_alarms, recal_every, recal_min, calib, prep)
+                    exclude_alarms, recal_every, recal_min, calib, prep, events=events)
 
     def _build(self, model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, recal,
-               exclude_alarms, recal_every, recal_min, calib, prep, device=None):
+               exclude_alarms, recal_every, recal_min, calib, prep, device=None, events=None):
         """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — the state is
         gdn_stream_state_bytes(n, w) of zeros, the table zeros, the threshold inf, all on `device`, `wide` the
         caller's word — and load_state_dict fills the allocations."""
@@ -1945,6 +2060,7 @@ class StreamDetector:
             raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {n}")
         if int(log) < 0:
             raise ValueError(f"log = {log}: the alarm log holds 0 or more entries")
+        self.events_cfg = None if events is None else events_config(events, self.top_m)     # host facts only
         self.recal, self.exclude_alarms, self.recal_every = int(recal), bool(exclude_alarms), int(recal_every)
         self.recal_min = 0
         if self.recal_every < 0 or (self.recal_every and not self.recal):
@@ -2002,6 +2118,17 @@ class StreamDetector:
             self.valid = torch.zeros((c, n), dtype=torch.uint8, device=dev)
             self.gap_chunk = torch.zeros((2, n), dtype=torch.int32, device=dev)
             self.gaps = torch.zeros((2, n), dtype=torch.int64, device=dev)      # missing_total, missing_run
+        self.events = self.clear = None
+        if self.events_cfg is not None:
+            # the clear level: a float64 scalar on the device (None: the raise level at construction); load() fills it
+            lo = self.events_cfg.pop("lo")
+            if history is not None:
+                hi = float(self.threshold.item())
+                lo = hi if lo is None else lo
+                if lo > hi:
+                    raise ValueError(f"events: lo = {lo} lies above the raise level (threshold = {hi})")
+            self.clear = torch.full((1,), 0.0 if lo is None else lo, dtype=torch.float64, device=dev)
+            self.events = ops.stream_events_alloc(m, self.events_cfg["cap"], dev)
         self.ring_keys = self.ring_keep = self._recal_ws = None
         if self.recal:
             self.ring_keys, self.ring_keep = ops.stream_calib_ring(n, self.recal, dev)
@@ -2110,6 +2237,10 @@ class StreamDetector:
         # valid, gap_chunk and gaps are None on a plain detector: the wrappers then call the plain symbols
         ops.stream_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.top_m,
                          self.top_scores, self.top_sensors, self.alarm, count=count, valid=self.valid)
+        if self.events is not None:
+            ops.stream_events(self.state, self.top_scores, self.top_sensors, self.threshold, self.clear,
+                              self.events_cfg["on"], self.events_cfg["off"], self.events_cfg["cap"], self.events,
+                              count=count)
         if self.recal:
             ops.stream_calib_write(self.state, self.pred, self.chunk_buf, self.alarm, self.ring_keys, self.ring_keep,
                                    self.exclude_alarms, count=count, valid=self.valid,
@@ -2256,6 +2387,9 @@ class StreamDetector:
         A prep= detector appends `raw_pending`, the raw ticks of the open group (a host value)."""
         ticks, alarms, logged = (int(v) for v in self.state[:3].tolist())
         tail = () if self.prep is None else (self.raw_pending,)
+        if self.events is not None:                         # events on: `episodes` raised so far and `episode_open`
+            raised, is_open = self.events[:2].tolist()
+            tail += (int(raised), bool(is_open))
         if self.log_ticks is None:
             dev = self.state.device
             return (ticks, alarms, torch.empty((0,), dtype=torch.int64, device=dev),
@@ -2270,6 +2404,15 @@ class StreamDetector:
             raise ValueError("status_gaps(): the detector was built with gaps=False and counts no missing readings")
         both = self.gaps.cpu()
         return both[0], both[1]
+
+    def episodes(self) -> Episodes:
+        """The stream's episode table (events= only): views of the events allocation, so a later push
+        moves them.  The open episode's row holds its peak so far and end = -1."""
+        if self.events is None:
+            raise ValueError("episodes(): the detector was built with events=None and keeps no episode table")
+        carry, start, end, peak_tick, peak, sensors = ops.stream_events_views(self.events, self.top_m,
+                                                                              self.events_cfg["cap"])
+        return Episodes(start, end, peak, peak_tick, sensors, carry[:1])
 
     def localise(self, rows=None) -> Localisation:
         """harness.localise for the last push: which sensors deviate at its alarm rows (`rows=None`; or the given
@@ -2295,7 +2438,9 @@ class StreamDetector:
     def _expect(self, check_model: bool = True) -> dict:
         """stream_checkpoint_check's `expect` for this detector: its model's shape and fingerprint, its prep, and the
         loaded library's ABI version and byte sizes."""
-        return _checkpoint_expect(self.model, self.prep, self.recal, check_model)
+        expect = _checkpoint_expect(self.model, self.prep, self.recal, check_model)
+        expect["events"] = self.events_cfg
+        return expect
 
     def state_dict(self) -> dict:
         """Everything a continuation of this stream depends on, as a flat dict of numpy arrays (no Python objects:
@@ -2320,6 +2465,8 @@ class StreamDetector:
             dev["pending"] = self._pend[self._pend_at][:self.raw_pending]
         if self.calib_counts is not None:
             dev["calib_counts"] = self.calib_counts
+        if self.events is not None:
+            dev["events"], dev["events_lo"] = self.events.view(torch.uint8), self.clear
         weights = self.model.state_dict()
         names = sorted(weights)
         host = _host_copies(list(dev.values()) + [weights[k] for k in names])
@@ -2329,6 +2476,8 @@ class StreamDetector:
             sd["log_ticks"], sd["log_sensors"] = np.zeros((0,), np.int64), np.zeros((0, m), np.int32)
         if self.recal_counts is not None:
             sd["recal_counts"] = self.recal_counts.to(torch.int64).numpy().copy()
+        if self.events is not None:
+            sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
         ints = {"format": STREAM_CHECKPOINT_FORMAT, "abi": lib.gdn_abi_version(),
                 "state_bytes": lib.gdn_stream_state_bytes(n, self.w),
                 "calib_bytes": lib.gdn_stream_calib_bytes(n, self.recal) if self.recal else 0,
@@ -2372,6 +2521,9 @@ class StreamDetector:
         if self.recal:
             self.ring_keys.copy_(host("ring_keys"))
             self.ring_keep.copy_(host("ring_keep"))
+        if self.events is not None:
+            self.events.view(torch.uint8).copy_(host("events"))
+            self.clear.copy_(host("events_lo"))
         self.raw_pending = _ckpt_int(sd, "raw_pending")
         if self.prep is not None:
             self._pend_at = 0
@@ -2403,10 +2555,14 @@ class StreamDetector:
             raise ValueError(f"stream checkpoint: recal = {R} is negative")
         stream_checkpoint_check(sd, _checkpoint_expect(model, prep, R, check_model))
         cfg = stream_checkpoint_config(sd)
+        events = stream_checkpoint_events(sd)               # (None: the file has no episode table, nor has the detector)
+        if events is not None:
+            events = {k: events[k] for k in ("on", "off", "cap", "lo")}
         det = cls.__new__(cls)
         det._build(model, None, None, None, cfg["chunk"], cfg["top_m"], cfg["log"], use_graph, bool(cfg["wide"]),
                    bool(cfg["with_gaps"]), cfg["recal"], bool(cfg["exclude_alarms"]), cfg["recal_every"],
-                   cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, device=device)
+                   cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, device=device,
+                   events=events)
         det.load_state_dict(sd, check_model=False)          # (the weights were compared above, once)
         return det
 

@@ -226,12 +226,18 @@ class Main:
                                     raw_path=self.env_config.get("stream_raw") or "",
                                     prep_path=self.env_config.get("prep") or "",
                                     save_path=self.env_config.get("stream_save") or "",
-                                    resume_path=self.env_config.get("stream_resume") or "")
+                                    resume_path=self.env_config.get("stream_resume") or "",
+                                    events=stream_events_config(self.env_config.get("stream_on"),
+                                                                self.env_config.get("stream_off"),
+                                                                self.env_config.get("stream_clear"),
+                                                                self.env_config.get("stream_events") or ""),
+                                    events_path=self.env_config.get("stream_events") or "")
         return info
 
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
                            recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False,
-                           raw_path: str = "", prep_path: str = "", save_path: str = "", resume_path: str = ""):
+                           raw_path: str = "", prep_path: str = "", save_path: str = "", resume_path: str = "",
+                           events=None, events_path: str = ""):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
@@ -256,7 +262,11 @@ class Main:
         -stream_resume PATH: the detector is StreamDetector.load(PATH) and not a fresh calibration: its configuration
         (gaps, ring, calibration rule, chunk) is the file's, -stream C only sizes the pushes, and the replay goes on at
         the tick the file's counters say has been consumed (of a -stream_raw file: model ticks * down + raw_pending);
-        that tick joins the line and `stream_result` ("resumed_from")."""
+        that tick joins the line and `stream_result` ("resumed_from").
+        -stream_on A -stream_off B -stream_clear LO -stream_events OUT.npz (any of them): the detector
+        keeps an episode table (events=dict(on=A, off=B, lo=LO)): one line per episode is printed — test ticks of its
+        start and end, its peak and the sensors at the peak — the table joins `stream_result` ("episodes") and, with
+        -stream_events, is saved to OUT.npz.  A resumed detector keeps the file's own events configuration."""
         check_calib_by_sensor(by_sensor, bool(chunk), gaps, calib_gaps)
         check_stream_raw(bool(raw_path), bool(chunk), bool(prep_path))
         check_stream_checkpoint(bool(save_path), bool(resume_path), bool(chunk))
@@ -272,6 +282,8 @@ class Main:
             rolling["calib_gaps"] = True
         if by_sensor:
             rolling["calib"] = "sensor"
+        if events is not None:
+            rolling["events"] = events
         step = chunk
         if raw_path:
             from .prep import Prep, read_raw_csv
@@ -333,11 +345,23 @@ class Main:
                      + (f", the last from {det.recal_kept} kept ticks" if det.recals and not by_sensor else "")
                      + (f", the last from at least {det.recal_kept} real readings per sensor"
                         if det.recal_kept and by_sensor else ""))
+        lines = ""
+        if det.events is not None:
+            table = det.episodes().numpy()
+            self.stream_result["episodes"] = table
+            held += (f"; {table['count']} episodes (on {det.events_cfg['on']}, off {det.events_cfg['off']}, clear "
+                     f"{float(det.clear.item()):.6g})")
+            for j in range(table["start"].shape[0]):
+                ends = "still open" if table["end"][j] < 0 else f"to {int(table['end'][j]) + w}"
+                lines += (f"episode {j}: test ticks {int(table['start'][j]) + w} {ends}, peak {table['peak'][j]:.6g} at "
+                          f"{int(table['peak_tick'][j]) + w}, sensors {table['sensors'][j].tolist()}\n")
+            if events_path:
+                np.savez(events_path, **table)
         first = ", ".join(str(int(t) + w) for t in self.stream_result["log_ticks"][:show])
         origin = f"from {normal.shape[1] - w} validation ticks" if resumed is None else f"from {resume_path}"
         print(f"stream: {scored} ticks in pushes of {chunk}, threshold {self.stream_result['threshold']:.6g} "
               f"{origin}: {alarms} alarm ticks" + held
-              + (f"; first at test ticks {first}" if alarms else "") + "\n")
+              + (f"; first at test ticks {first}" if alarms else "") + "\n" + lines)
         return self.stream_result
 
     def save_localisation(self, model, gt, threshold: float, path: str, m: int = 3):
@@ -394,7 +418,7 @@ class Main:
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
     -train_gaps / -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every /
-    -stream_raw / -prep / -stream_save / -stream_resume."""
+    -stream_raw / -prep / -stream_save / -stream_resume / -stream_on / -stream_off / -stream_clear / -stream_events."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
     parser.add_argument("-epoch", help="train epoch", type=int, default=100)
@@ -443,7 +467,31 @@ def build_parser():
                         "(the file is written exactly here; no suffix is appended)", type=str, default="")
     parser.add_argument("-stream_resume", help="with -stream: start from this saved detector instead of a calibration on "
                         "the validation block, and go on at the tick it had consumed", type=str, default="")
+    parser.add_argument("-stream_on", help="with -stream: raise an episode after this many ticks above the threshold",
+                        type=int, default=None)
+    parser.add_argument("-stream_off", help="with -stream: clear an episode after this many ticks at or below the clear "
+                        "level", type=int, default=None)
+    parser.add_argument("-stream_clear", help="with -stream: the clear level of an episode (default: the threshold)",
+                        type=float, default=None)
+    parser.add_argument("-stream_events", help="with -stream: save the episode table to this .npz", type=str, default="")
     return parser
+
+
+def check_stream_events(stream_on: bool, stream_off: bool, stream_clear: bool, stream_events: bool, stream: bool) -> None:
+    """-stream_on, -stream_off, -stream_clear and -stream_events configure the episode table of a streaming detector:
+    they mean something only with -stream C (the detector).  Refused by name otherwise."""
+    for given, flag in ((stream_on, "-stream_on"), (stream_off, "-stream_off"), (stream_clear, "-stream_clear"),
+                        (stream_events, "-stream_events")):
+        if given and not stream:
+            raise ValueError(f"{flag} needs -stream C: the episode table is the streaming detector's")
+
+
+def stream_events_config(stream_on, stream_off, stream_clear, stream_events: str):
+    """StreamDetector's events= for the four flags: None when none of them is given (no episode table)."""
+    if stream_on is None and stream_off is None and stream_clear is None and not stream_events:
+        return None
+    return {"on": 1 if stream_on is None else int(stream_on), "off": 1 if stream_off is None else int(stream_off),
+            "lo": None if stream_clear is None else float(stream_clear)}
 
 
 def check_stream_checkpoint(stream_save: bool, stream_resume: bool, stream: bool) -> None:
@@ -488,6 +536,8 @@ def from_args(argv=None) -> Main:
     check_calib_by_sensor(args.calib_by_sensor, bool(args.stream), args.stream_gaps, args.stream_calib_gaps)
     check_stream_raw(bool(args.stream_raw), bool(args.stream), bool(args.prep))
     check_stream_checkpoint(bool(args.stream_save), bool(args.stream_resume), bool(args.stream))
+    check_stream_events(args.stream_on is not None, args.stream_off is not None, args.stream_clear is not None,
+                        bool(args.stream_events), bool(args.stream))
     random.seed(args.random_seed)                      # main.py:221-228
     np.random.seed(args.random_seed)
     torch.manual_seed(args.random_seed)
@@ -505,7 +555,8 @@ def from_args(argv=None) -> Main:
                   "stream_gaps": args.stream_gaps, "stream_calib_gaps": args.stream_calib_gaps, "stream_recal": args.stream_recal,
                   "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor,
                   "stream_raw": args.stream_raw, "prep": args.prep, "stream_save": args.stream_save,
-                  "stream_resume": args.stream_resume}
+                  "stream_resume": args.stream_resume, "stream_on": args.stream_on, "stream_off": args.stream_off,
+                  "stream_clear": args.stream_clear, "stream_events": args.stream_events}
     return Main(train_config, env_config, debug=False)
 
 

@@ -1289,3 +1289,114 @@ def prep_ticks(raw, pend_in, pending: int, pend_out, down: int, table, out, rows
     _lib.call("gdn_prep_ticks", _ptr(raw), rows, f64, _ptr(pend_in), int(pending), _ptr(pend_out), n, down, _ptr(table),
               _ptr(out), out.shape[0], _stream())
     return groups
+
+
+# --------------------------------------------------------------------------- alarm episodes
+EPISODES_CARRY_WORDS = 20           # GDN_EPISODES_CARRY_BYTES / 8
+_EPISODES_MAX_T, _EPISODES_MAX_E, _EPISODES_MAX_RUN = 1 << 26, 1 << 20, 4096
+
+
+def episodes_check(hi, lo, on: int, off: int, cap: int) -> tuple:
+    """(hi, lo, on, off, cap) as Python numbers, refused by name on the host: lo > hi or a NaN level, on / off outside
+    1 .. 4096, cap outside 0 .. 2^20.  `lo=None` means hi; `hi=None` (a level that lives on the device) skips the
+    comparison of the two."""
+    on, off, cap = int(on), int(off), int(cap)
+    if not 1 <= on <= _EPISODES_MAX_RUN:
+        raise ValueError(f"on = {on}: an episode is raised after 1 to {_EPISODES_MAX_RUN} ticks above the level")
+    if not 1 <= off <= _EPISODES_MAX_RUN:
+        raise ValueError(f"off = {off}: an episode is cleared after 1 to {_EPISODES_MAX_RUN} ticks below the clear level")
+    if not 0 <= cap <= _EPISODES_MAX_E:
+        raise ValueError(f"cap = {cap}: the episode table keeps 0 to {_EPISODES_MAX_E} rows")
+    if hi is not None:
+        hi = float(hi)
+        lo = hi if lo is None else float(lo)
+        if hi != hi or lo != lo or lo > hi:
+            raise ValueError(f"lo = {lo}, hi = {hi}: the clear level must be a number at or below the raise level")
+    elif lo is not None:
+        lo = float(lo)
+        if lo != lo:
+            raise ValueError(f"lo = {lo}: the clear level must be a number")
+    return hi, lo, on, off, cap
+
+
+def episodes_table(cap: int, m: int, device):
+    """An empty episode table: (start, end, peak_tick int64 [cap], peak float64 [cap], sensors int32 [cap, m], count
+    int64 [1])."""
+    i64 = dict(dtype=torch.int64, device=device)
+    return (torch.zeros((cap,), **i64), torch.full((cap,), -1, **i64), torch.zeros((cap,), **i64),
+            torch.zeros((cap,), dtype=torch.float64, device=device),
+            torch.zeros((cap, m), dtype=torch.int32, device=device), torch.zeros((1,), **i64))
+
+
+def episodes_scan(scores, top_sensors, hi, lo=None, on: int = 1, off: int = 1, cap: int = 4096, first_tick: int = 0,
+                  carry_in=None, carry_out=None, table=None, grid: int = 0):
+    """gdn_episodes_scan: the episodes of `scores` [T] float64 with their sensors from `top_sensors` [T, m] int32, both
+    on the device (include/gdn_hip.h "Alarm episodes").  Returns `table` = (start, end, peak_tick, peak, sensors,
+    count) — a fresh one, or the one given: with `carry_in` (an int64 [20] device tensor a previous call wrote as its
+    `carry_out`) the rows below the carried count stay and the scan goes on in the same table.  `grid` > 0 forces
+    the grid of the tile launches (a diagnostic: the bits do not depend on it)."""
+    scores = _chk(scores, torch.float64, "scores")
+    top_sensors = _chk(top_sensors, torch.int32, "top_sensors")
+    if scores.dim() != 1 or top_sensors.dim() != 2 or top_sensors.shape[0] != scores.shape[0]:
+        raise ValueError(f"expected scores [T] and top_sensors [T, m], got {tuple(scores.shape)} and "
+                         f"{tuple(top_sensors.shape)}")
+    hi, lo, on, off, cap = episodes_check(hi, lo, on, off, cap)
+    T, m = top_sensors.shape
+    nbytes = _lib.load().gdn_episodes_workspace_bytes(T, cap)
+    if nbytes <= 0 or not 1 <= m <= 8:
+        raise _lib.GdnHipError(f"episodes: no kernel for T = {T}, m = {m}, cap = {cap} (1 <= T <= 2^26, 1 <= m <= 8, "
+                               "0 <= cap <= 2^20)")
+    if table is None:
+        table = episodes_table(cap, m, scores.device)
+    start, end, peak_tick, peak, sensors, count = table
+    for t, dtype, need, name in ((start, torch.int64, cap, "start"), (end, torch.int64, cap, "end"),
+                                 (peak_tick, torch.int64, cap, "peak_tick"), (peak, torch.float64, cap, "peak"),
+                                 (sensors, torch.int32, cap * m, "sensors"), (count, torch.int64, 1, "count")):
+        _stream_buf(t, dtype, need, name)
+    for t, name in ((carry_in, "carry_in"), (carry_out, "carry_out")):
+        if t is not None:
+            _stream_buf(t, torch.int64, EPISODES_CARRY_WORDS, name)
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=scores.device)
+    head = (_ptr(scores), _ptr(top_sensors), T, m, hi, lo, on, off, int(first_tick), cap, _ptr(carry_in),
+            _ptr(carry_out), _ptr(start) if cap else None, _ptr(end) if cap else None, _ptr(peak_tick) if cap else None,
+            _ptr(peak) if cap else None, _ptr(sensors) if cap else None, _ptr(count), _ptr(ws))
+    if grid:
+        _lib.call("gdn_episodes_scan_grid", *head, int(grid), _stream())
+    else:
+        _lib.call("gdn_episodes_scan", *head, _stream())
+    return table
+
+
+def stream_events_alloc(m: int, cap: int, device) -> torch.Tensor:
+    """The events allocation of a stream (gdn_stream_events_bytes(m, cap) / 8 int64 words, zero: no tick seen)."""
+    nbytes = _lib.load().gdn_stream_events_bytes(m, cap)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"stream events: no kernel for m = {m}, cap = {cap} (1 <= m <= 8, 0 <= cap <= 2^20)")
+    return torch.zeros((nbytes // 8,), dtype=torch.int64, device=device)
+
+
+def stream_events_views(events, m: int, cap: int):
+    """(carry int64 [20], start, end, peak_tick int64 [cap], peak float64 [cap], sensors int32 [cap, m]): views of an
+    events allocation."""
+    h = EPISODES_CARRY_WORDS
+    body = events[h:]
+    return (events[:h], body[:cap], body[cap:2 * cap], body[2 * cap:3 * cap], body[3 * cap:4 * cap].view(torch.float64),
+            body[4 * cap:].view(torch.int32)[:cap * m].view(cap, m))
+
+
+def stream_events(state, top_scores, top_sensors, threshold, clear, on: int, off: int, cap: int, events,
+                  count: int | None = None):
+    """gdn_stream_events: the episodes of the push's `count` rows of top_scores [c, m] / top_sensors [c, m] folded into
+    `events` (stream_events_alloc), raise level threshold[0], clear level clear[0] (float64 device scalars).  After
+    stream_score, before stream_advance.  Reads the state, writes `events` only."""
+    c, m = top_scores.shape
+    count = c if count is None else int(count)
+    _stream_buf(state, torch.int64, 4, "state")
+    _stream_buf(top_scores, torch.float64, c * m, "top_scores")
+    _stream_buf(top_sensors, torch.int32, c * m, "top_sensors")
+    _stream_buf(threshold, torch.float64, 1, "threshold")
+    _stream_buf(clear, torch.float64, 1, "clear")
+    _stream_buf(events, torch.int64, max(1, _lib.load().gdn_stream_events_bytes(m, cap) // 8), "events")
+    _lib.call("gdn_stream_events", _ptr(state), _ptr(top_scores), _ptr(top_sensors), _ptr(threshold), _ptr(clear), c,
+              count, m, int(on), int(off), int(cap), _ptr(events), _stream())
+    return events

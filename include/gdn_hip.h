@@ -990,6 +990,59 @@ int gdn_prep_series(const void* raw, long long t_raw, int n, int raw_f64, const 
 int gdn_prep_ticks(const void* raw, int r, int raw_f64, const double* pend_in, int pending, double* pend_out, int n,
                    int down, const double* table, float* out, int c, void* stream);
 
+/* ---- Alarm episodes --------------------------------------------------------------------------
+ * The layer between a score per tick and an event list (opt-in; additive entry points, the ABI version does not move):
+ * on-delay, a clear level below the raise level, off-delay, and a table of episodes.  With s_t = top_scores[t, 0],
+ * float64 levels lo <= hi and integers on, off >= 1:
+ *   above_t = s_t > hi (strict; a NaN score is not above), below_t = !(s_t > lo) (a NaN score is below);
+ *   run_hi(t) / run_lo(t) = the length of the run of above / below ticks that ends at t (0: t is not above / below);
+ *   set_t = run_hi(t) >= on, reset_t = run_lo(t) >= off; active_t = the latest set-or-reset at or before t is a set.
+ *   An episode OPENS where active turns true: start = t - on + 1; it CLOSES where active turns false: end = t - off + 1
+ *   (exclusive; end > start); peak = the largest score in [start, end), peak_tick = the first tick that holds it,
+ *   sensors[:m] = top_sensors[peak_tick]; an episode still open at the last tick has end = -1 and its peak so far.
+ * Episodes are numbered in tick order; the table keeps rows 0 .. E - 1 (start, end, peak_tick int64; peak float64;
+ * sensors [E, m] int32) and `count` goes on counting beyond E.  Ticks are global: first_tick + index.  Comparisons and
+ * copies only, no floating-point arithmetic, integer max / min atomics on an order-preserving image of the score: the
+ * result is deterministic, the same for every grid size, and equal bit for bit between the two forms.
+ * Carry: GDN_EPISODES_CARRY_BYTES bytes on the device, 8-byte aligned, all zero for a series that has not begun:
+ *   int64 count, active, run_hi, run_lo (saturated at on / off); the peak so far of an above-run that has not raised
+ *   (float64 peak, int64 tick, int32 sensors[8]); the open episode (int64 start, float64 peak, int64 peak_tick, int32
+ *   sensors[8]); three reserved words.
+ *   gdn_episodes_scan    the archive form, parallel over T: scores [T] float64 and top_sensors [T, m] int32 on the
+ *                        device.  Five launches — per-tile reduce, a scan of the tile aggregates by one workgroup,
+ *                        two apply passes, finish — and no workgroup waits on another.  carry_in (may be NULL: a
+ *                        series that begins here) / carry_out (may be NULL; may be carry_in) let a long archive be
+ *                        scanned in pieces over ONE table: a call keeps the rows below carry_in's count as they are and
+ *                        completes the open one.  count [1] int64.  workspace: gdn_episodes_workspace_bytes(T, E)
+ *                        bytes (0: unsupported), 8-byte aligned, need not be cleared.
+ *   gdn_episodes_scan_grid  the same with the grid of the tile launches given (0: the library's choice): a diagnostic
+ *                        for the claim that the grid does not change a bit.
+ *   gdn_stream_events    the stream form, ONE launch of one workgroup in a push: after gdn_stream_score[_gaps] (it wrote
+ *                        top_scores [c, m] / top_sensors [c, m]) and before gdn_stream_advance[_gaps] (`ticks` in the
+ *                        stream state is still the push's first tick).  hi = threshold[0], the pointer the score launch
+ *                        reads; lo = clear[0], a float64 device scalar (a clear level above hi, or NaN, acts as hi).
+ *                        Reads the stream state; writes only `events`: ONE allocation of
+ *                        gdn_stream_events_bytes(m, E) bytes, zero before the first push = [the carry | start [E] | end
+ *                        [E] | peak_tick [E] | peak [E] | sensors [E, m]].  Rows >= count of a short push are ignored.
+ *                        The open episode's row is rewritten on every push: a reader sees its peak so far.
+ * 1 <= T <= 2^26 (stream: count <= c <= 4096), 1 <= m <= 8, 1 <= on, off <= 4096, 0 <= E <= 2^20: else
+ * GDN_ERR_UNSUPPORTED (byte counts: 0).  lo > hi, a NaN level, first_tick < 0, a null required pointer (the table's
+ * when E > 0), count < 1, count > c: GDN_ERR_ARG.  All decided before any launch.                                    */
+#define GDN_EPISODES_CARRY_BYTES 160
+long long gdn_episodes_workspace_bytes(long long T, long long E);
+int gdn_episodes_scan(const double* scores, const int32_t* top_sensors, long long T, int m, double hi, double lo,
+                      int on, int off, long long first_tick, long long E, const void* carry_in, void* carry_out,
+                      int64_t* start, int64_t* end, int64_t* peak_tick, double* peak, int32_t* sensors, int64_t* count,
+                      void* workspace, void* stream);
+int gdn_episodes_scan_grid(const double* scores, const int32_t* top_sensors, long long T, int m, double hi, double lo,
+                           int on, int off, long long first_tick, long long E, const void* carry_in, void* carry_out,
+                           int64_t* start, int64_t* end, int64_t* peak_tick, double* peak, int32_t* sensors,
+                           int64_t* count, void* workspace, int grid, void* stream);
+long long gdn_stream_events_bytes(int m, long long E);
+int gdn_stream_events(const void* state, const double* top_scores, const int32_t* top_sensors, const double* threshold,
+                      const double* clear, int c, int count, int m, int on, int off, long long E, void* events,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
