@@ -2,11 +2,13 @@
 // evaluate.py:131-139).  numpy evaluates  a + d*t  and  (x - m) / (|r| + eps)  as separate
 // roundings, so FMA contraction is switched off for this file.
 #pragma clang fp contract(off)
-#include "gdn_common.hpp"
+#include "gdn_score_sweep.hpp"
 
 #include <stdlib.h>
 
 namespace {
+
+using namespace gdn_sweep;
 
 constexpr int NQ = 6;  // order statistics per sensor: median lo/hi, q25 lo/hi, q75 lo/hi
 
@@ -79,9 +81,7 @@ __device__ __forceinline__ const SelectArgs& select_args_for(const CountArgs& ca
 
 // keys[s][tick] = |pred[tick][s] - gt[tick][s]| in float64 (bit pattern = radix key), transposed
 // through LDS so that both the fp32 reads (along sensors) and the fp64 writes (along ticks) are
-// coalesced.  Row pitch >= t; slots t..pitch-1 get the FILLER pattern (all ones: larger than every real
-// key, never counted).
-constexpr unsigned long long FILLER = ~0ull;
+// coalesced.  Row pitch >= t; slots t..pitch-1 get the FILLER pattern (gdn_score_sweep.hpp).
 
 __global__ __launch_bounds__(256) void score_keys_kernel(const float* __restrict__ pred,
                                                          const float* __restrict__ gt, int t, int n, int pitch,
@@ -93,14 +93,14 @@ __global__ __launch_bounds__(256) void score_keys_kernel(const float* __restrict
     const int tick = t0 + r, s = s0 + lane;
     if (tick < t && s < n) {
       const size_t o = (size_t)tick * n + s;
-      tile[r][lane] = fabs((double)pred[o] - (double)gt[o]);
+      tile[r][lane] = score_key(pred[o], gt[o]);
     }
   }
   __syncthreads();
   for (int r = wv; r < 64; r += 4) {
     const int s = s0 + r, tick = t0 + lane;
     if (s < n && tick < pitch)
-      keys[(size_t)s * pitch + tick] = tick < t ? tile[lane][r] : __longlong_as_double((long long)FILLER);
+      keys[(size_t)s * pitch + tick] = tick < t ? tile[lane][r] : filler_key();
   }
 }
 
@@ -118,15 +118,15 @@ __global__ __launch_bounds__(256) void score_keys_valid_kernel(const float* __re
     const int tick = t0 + r, s = s0 + lane;
     if (tick < t && s < n) {
       const size_t o = (size_t)tick * n + s;
-      const double e = fabs((double)pred[o] - (double)gt[o]);
-      tile[r][lane] = valid[o] != 0 ? e : __longlong_as_double((long long)FILLER);
+      const double e = score_key(pred[o], gt[o]);
+      tile[r][lane] = valid[o] != 0 ? e : filler_key();
     }
   }
   __syncthreads();
   for (int r = wv; r < 64; r += 4) {
     const int s = s0 + r, tick = t0 + lane;
     if (s < n && tick < pitch)
-      keys[(size_t)s * pitch + tick] = tick < t ? tile[lane][r] : __longlong_as_double((long long)FILLER);
+      keys[(size_t)s * pitch + tick] = tick < t ? tile[lane][r] : filler_key();
   }
 }
 
@@ -1185,17 +1185,38 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
   }
 }
 
-// Normalise, smooth, max.  One wave owns a run of consecutive ticks; lane l owns sensors l, l+64, ...
-// and slides a 4-deep window of normalised errors down the run, so each (tick, sensor) value — and
-// its float64 division — is computed once.  smoothed = mean of the value at the tick and its 3
-// predecessors (0 for the first 3 ticks of the SERIES), anomaly = max over sensors (wave reduction).
-// Rows before this shard's first tick come from the halo [3][n].
-// GAPS (gdn_score_smooth_max_gaps / _topm_gaps; the same switch as gdn_stream_score_kernel's): `valid` [t, n] (1 = a
-// real reading; `halo_valid` [3, n] for the halo rows) travels as one bit per loaded row and the normalised error of a
-// missing reading is 0.0 in its own tick's mean and in the next three.  Without GAPS the two trailing parameters are
-// not read and the kernels are the ones they were (DESIGN §3.5d has the resource table of both instantiations).
-constexpr int RUN = 8;       // ticks per wave (short runs: thousands of waves keep loads in flight)
+// Normalise, smooth, reduce over sensors: the sweep of gdn_score_sweep.hpp (the one full description).  Here: where a
+// resident shard's rows come from, and the two reductions.
 
+// Rows before this shard's first tick come from the halo [3][n] when the series has them (first_tick > 0); otherwise
+// row 0 stands in (its values only feed ticks whose series index is < 3, which are forced to 0).  Rows past the shard
+// are clamped to its last.  The 3 predecessors of t0 are 0.0 where the series has no such tick.
+struct SeriesSource {
+  const float *pred, *gt, *halo_pred, *halo_gt;
+  const unsigned char *valid, *halo_valid;
+  int t, n, first_tick;
+  template <typename T>
+  __device__ __forceinline__ const T* row(const T* body, const T* halo, int tt) const {
+    const bool before = tt < 0;                  // halo row 3 + tt
+    const int r = before ? (first_tick > 0 ? 3 + tt : 0) : min(tt, t - 1);
+    return (before && first_tick > 0 ? halo : body) + (size_t)r * n;
+  }
+  __device__ __forceinline__ const float* pred_row(int tt) const { return row(pred, halo_pred, tt); }
+  __device__ __forceinline__ const float* gt_row(int tt) const { return row(gt, halo_gt, tt); }
+  __device__ __forceinline__ const unsigned char* valid_row(int tt) const { return row(valid, halo_valid, tt); }
+  template <typename FA, typename FB>
+  __device__ __forceinline__ void before(int t0, const Lanes&, double (&a)[3], double (&b)[3], FA&& na,
+                                         FB&& nb) const {
+    const int g0 = first_tick + t0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      a[k] = g0 >= 3 - k ? na(k) : 0.0;
+      b[k] = g0 >= 3 - k ? nb(k) : 0.0;
+    }
+  }
+};
+
+// anomaly = max over sensors (the transposing butterfly); `scores` (optional) gets the [n, t] table.
 template <bool GAPS>
 __global__ __launch_bounds__(256) void score_smooth_max_kernel(
     const float* __restrict__ pred, const float* __restrict__ gt, const double* __restrict__ med_iqr,
@@ -1206,104 +1227,24 @@ __global__ __launch_bounds__(256) void score_smooth_max_kernel(
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int nruns = (t + RUN - 1) / RUN;
+  const SeriesSource src{pred, gt, halo_pred, halo_gt, valid, halo_valid, t, n, first_tick};
   for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb) {
     const int t0 = run * RUN, t1 = min(t, t0 + RUN);
     for (int s0 = 0; s0 < n; s0 += 128) {          // two sensors per lane per sweep
-      const int sa_ = s0 + lane, sb_ = s0 + 64 + lane;
-      const bool la = sa_ < n, lb = sb_ < n;
-      const int ca = la ? sa_ : n - 1, cb = lb ? sb_ : n - 1;
-      // (x - median) / (|iqr| + eps), evaluate.py:60-62: the divisor is one number per sensor, so the wave divides
-      // ONCE per sensor and run and multiplies per tick (a float64 division is ~35 instructions; eleven per sensor
-      // and run were a third of this kernel).  x * (1/d) is within one ulp of x / d: 2e-16 relative, four orders
-      // below the 1e-12 bar of the scoring parity tests.
-      const double meda = med_iqr[2 * ca], dena = 1.0 / (fabs(med_iqr[2 * ca + 1]) + 1e-2);
-      const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
-      // ALL 4 x (3 + RUN) values of the run are fetched before the first is used (clamped row indices: the loads are
-      // unconditional, rows that do not exist are masked afterwards) — fetched inside the tick loop they were a
-      // chain of dependent round trips and the kernel ran at 2.2 TB/s
-      const int g0 = first_tick + t0;
-      float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
-      unsigned oka = 0u, okb = 0u;                 // GAPS: bit u = the reading of row u is real
-#pragma unroll
-      for (int u = 0; u < RUN + 3; ++u) {
-        const int tt = t0 - 3 + u;                 // < 0: halo row 3 + tt (rows before this shard's first tick)
-        const bool halo = tt < 0;
-        const int row = halo ? (first_tick > 0 ? 3 + tt : 0) : min(tt, t - 1);
-        const float* pp = (halo && first_tick > 0 ? halo_pred : pred) + (size_t)row * n;
-        const float* gg = (halo && first_tick > 0 ? halo_gt : gt) + (size_t)row * n;
-        pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
-        if constexpr (GAPS) {
-          const unsigned char* vv = (halo && first_tick > 0 ? halo_valid : valid) + (size_t)row * n;
-          oka |= (vv[ca] ? 1u : 0u) << u;
-          okb |= (vv[cb] ? 1u : 0u) << u;
-        }
-      }
-      auto norm = [&](float pv, float gv, double med, double inv_den, unsigned ok, int u) -> double {
-        const double a = (fabs((double)pv - (double)gv) - med) * inv_den;
-        if constexpr (GAPS) return ((ok >> u) & 1u) ? a : 0.0;
-        return a;
-      };
-      // the 3 predecessors of t0 that exist in the series (a missing one only feeds ticks whose
-      // series index is < 3, which are forced to 0)
-      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena, oka, 0) : 0.0;
-      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena, oka, 1) : 0.0;
-      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena, oka, 2) : 0.0;
-      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb, okb, 0) : 0.0;
-      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb, okb, 1) : 0.0;
-      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb, okb, 2) : 0.0;
+      const Lanes l(s0, lane, n);
       double mt[RUN];                             // this lane's max over its sensors, per tick of the run
 #pragma unroll
-      for (int u = 0; u < RUN; ++u) {
-        const int tick = t0 + u;
-        mt[u] = -INFINITY;
-        if (tick < t1) {                           // (wave uniform)
-          const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena, oka, 3 + u);
-          const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb, okb, 3 + u);
-          double sma = 0.0, smb = 0.0;
-          if (first_tick + tick >= 3) {               // numpy sums the 4 values left to right
-            sma = (((a3 + a2) + a1) + a0) / 4.0;
-            smb = (((b3 + b2) + b1) + b0) / 4.0;
-          }
-          if (scores) {
-            if (la) scores[(size_t)sa_ * t + tick] = sma;
-            if (lb) scores[(size_t)sb_ * t + tick] = smb;
-          }
-          mt[u] = fmax(la ? sma : -INFINITY, lb ? smb : -INFINITY);
-          a3 = a2; a2 = a1; a1 = a0;
-          b3 = b2; b2 = b1; b1 = b0;
+      for (int u = 0; u < RUN; ++u) mt[u] = -INFINITY;
+      score_sweep<GAPS>(src, med_iqr, l, t0, t1, first_tick, [&](int u, int tick, double sma, double smb) {
+        if (scores) {
+          if (l.la) scores[(size_t)l.sa * t + tick] = sma;
+          if (l.lb) scores[(size_t)l.sb * t + tick] = smb;
         }
-      }
-      // max over the 64 lanes for all 8 ticks together: a butterfly that also transposes — each step a lane keeps
-      // half of its ticks and hands the other half to its partner (8 + 4 + 2 exchanges), then three plain steps on
-      // the one tick left: 20 64-bit exchanges instead of 8 x 6 = 48 (max is exact in any order)
-      static_assert(RUN == 8, "the transposing reduction is written for 8 ticks");
-      double k4[4], k2[2], k1;
-      {
-        const bool up = (lane & 32) != 0;
-#pragma unroll
-        for (int i2 = 0; i2 < 4; ++i2) {
-          const double mine = up ? mt[4 + i2] : mt[i2], send = up ? mt[i2] : mt[4 + i2];
-          k4[i2] = fmax(mine, __shfl_xor(send, 32));
-        }
-      }
-      {
-        const bool up = (lane & 16) != 0;
-#pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) {
-          const double mine = up ? k4[2 + i2] : k4[i2], send = up ? k4[i2] : k4[2 + i2];
-          k2[i2] = fmax(mine, __shfl_xor(send, 16));
-        }
-      }
-      {
-        const bool up = (lane & 8) != 0;
-        const double mine = up ? k2[1] : k2[0], send = up ? k2[0] : k2[1];
-        k1 = fmax(mine, __shfl_xor(send, 8));
-      }
-      k1 = fmax(k1, __shfl_xor(k1, 4));
-      k1 = fmax(k1, __shfl_xor(k1, 2));
-      k1 = fmax(k1, __shfl_xor(k1, 1));
-      if ((lane & 7) == 0) {                       // lanes 0, 8, .., 56 hold ticks 0, 1, .., 7 of the run
-        const int u = ((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1);
+        mt[u] = fmax(l.la ? sma : -INFINITY, l.lb ? smb : -INFINITY);
+      });
+      const double k1 = butterfly_max(mt, lane);
+      if ((lane & 7) == 0) {
+        const int u = butterfly_tick(lane);
         best[wv][u] = s0 == 0 ? k1 : fmax(best[wv][u], k1);
       }
     }
@@ -1312,14 +1253,7 @@ __global__ __launch_bounds__(256) void score_smooth_max_kernel(
   }
 }
 
-// Normalise, smooth, top m.  The same sweep as score_smooth_max_kernel (same loads, same float64 operations in the
-// same order), but a tick keeps its m largest smoothed scores WITH their sensors instead of the maximum alone: the
-// lane's two values of the sweep and the list carried over from earlier sweeps (entry r in lane r) are the
-// candidates; m rounds of "wave maximum of (score, sensor), the owner masks it out" leave the new list, again entry
-// r in lane r.  Order: larger score first, equal scores by the lower sensor (sensors are unique among the
-// candidates, so every round has one owner).  The [n, t] table is never written.
-constexpr int TOPM_MAX = 8;
-
+// The m largest scores of every tick with their sensors (topm_merge).  The [n, t] table is never written.
 template <bool GAPS>
 __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
     const float* __restrict__ pred, const float* __restrict__ gt, const double* __restrict__ med_iqr,
@@ -1329,7 +1263,7 @@ __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int nruns = (t + RUN - 1) / RUN;
-  constexpr int NONE = 0x7fffffff;               // sensor of a masked / missing candidate (score -inf)
+  const SeriesSource src{pred, gt, halo_pred, halo_gt, valid, halo_valid, t, n, first_tick};
   for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb) {
     const int t0 = run * RUN, t1 = min(t, t0 + RUN);
     double cs[RUN];                               // the carried list: entry `lane` of every tick of the run
@@ -1340,88 +1274,12 @@ __global__ __launch_bounds__(256) void score_smooth_topm_kernel(
       ci[u] = NONE;
     }
     for (int s0 = 0; s0 < n; s0 += 128) {
-      const int sa_ = s0 + lane, sb_ = s0 + 64 + lane;
-      const bool la = sa_ < n, lb = sb_ < n;
-      const int ca = la ? sa_ : n - 1, cb = lb ? sb_ : n - 1;
-      const double meda = med_iqr[2 * ca], dena = 1.0 / (fabs(med_iqr[2 * ca + 1]) + 1e-2);
-      const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
-      const int g0 = first_tick + t0;
-      float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
-      unsigned oka = 0u, okb = 0u;                 // GAPS: bit u = the reading of row u is real
-#pragma unroll
-      for (int u = 0; u < RUN + 3; ++u) {
-        const int tt = t0 - 3 + u;
-        const bool halo = tt < 0;
-        const int row = halo ? (first_tick > 0 ? 3 + tt : 0) : min(tt, t - 1);
-        const float* pp = (halo && first_tick > 0 ? halo_pred : pred) + (size_t)row * n;
-        const float* gg = (halo && first_tick > 0 ? halo_gt : gt) + (size_t)row * n;
-        pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
-        if constexpr (GAPS) {
-          const unsigned char* vv = (halo && first_tick > 0 ? halo_valid : valid) + (size_t)row * n;
-          oka |= (vv[ca] ? 1u : 0u) << u;
-          okb |= (vv[cb] ? 1u : 0u) << u;
-        }
-      }
-      auto norm = [&](float pv, float gv, double med, double inv_den, unsigned ok, int u) -> double {
-        const double a = (fabs((double)pv - (double)gv) - med) * inv_den;
-        if constexpr (GAPS) return ((ok >> u) & 1u) ? a : 0.0;
-        return a;
-      };
-      double a3 = g0 >= 3 ? norm(pa[0], ga[0], meda, dena, oka, 0) : 0.0;
-      double a2 = g0 >= 2 ? norm(pa[1], ga[1], meda, dena, oka, 1) : 0.0;
-      double a1 = g0 >= 1 ? norm(pa[2], ga[2], meda, dena, oka, 2) : 0.0;
-      double b3 = g0 >= 3 ? norm(pb[0], gb[0], medb, denb, okb, 0) : 0.0;
-      double b2 = g0 >= 2 ? norm(pb[1], gb[1], medb, denb, okb, 1) : 0.0;
-      double b1 = g0 >= 1 ? norm(pb[2], gb[2], medb, denb, okb, 2) : 0.0;
-#pragma unroll
-      for (int u = 0; u < RUN; ++u) {
-        const int tick = t0 + u;
-        if (tick >= t1) continue;                  // (wave uniform)
-        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena, oka, 3 + u);
-        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb, okb, 3 + u);
-        double sma = 0.0, smb = 0.0;
-        if (first_tick + tick >= 3) {
-          sma = (((a3 + a2) + a1) + a0) / 4.0;
-          smb = (((b3 + b2) + b1) + b0) / 4.0;
-        }
-        a3 = a2; a2 = a1; a1 = a0;
-        b3 = b2; b2 = b1; b1 = b0;
-        // this lane's three candidates
-        double v0 = la ? sma : -INFINITY, v1 = lb ? smb : -INFINITY, v2 = cs[u];
-        int i0 = la ? sa_ : NONE, i1 = lb ? sb_ : NONE, i2 = ci[u];
-        double ns = -INFINITY;
-        int ni = NONE;
-        for (int r = 0; r < m; ++r) {              // (m is wave uniform)
-          double bs = v0;
-          int bi = i0;
-          if (v1 > bs || (v1 == bs && i1 < bi)) { bs = v1; bi = i1; }
-          if (v2 > bs || (v2 == bs && i2 < bi)) { bs = v2; bi = i2; }
-#pragma unroll
-          for (int d = 32; d >= 1; d >>= 1) {
-            const double os = __shfl_xor(bs, d);
-            const int oi = __shfl_xor(bi, d);
-            if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
-          }
-          if (bi != NONE) {                        // the owner masks its candidate out
-            if (i0 == bi) { v0 = -INFINITY; i0 = NONE; }
-            if (i1 == bi) { v1 = -INFINITY; i1 = NONE; }
-            if (i2 == bi) { v2 = -INFINITY; i2 = NONE; }
-          }
-          if (lane == r) { ns = bs; ni = bi; }
-        }
-        cs[u] = ns;
-        ci[u] = ni;
-      }
+      const Lanes l(s0, lane, n);
+      score_sweep<GAPS>(src, med_iqr, l, t0, t1, first_tick, [&](int u, int, double sma, double smb) {
+        topm_merge(l, lane, m, sma, smb, cs[u], ci[u]);
+      });
     }
-    if (lane < m) {
-#pragma unroll
-      for (int u = 0; u < RUN; ++u) {
-        if (t0 + u < t1) {
-          top_scores[(size_t)(t0 + u) * m + lane] = cs[u];
-          top_sensors[(size_t)(t0 + u) * m + lane] = ci[u];
-        }
-      }
-    }
+    topm_store(cs, ci, lane, m, t0, t1, top_scores, top_sensors);
   }
 }
 
@@ -1585,9 +1443,7 @@ int smooth_max(const float* pred, const float* gt, const double* med_iqr, int t,
   if (!pred || !gt || !med_iqr || !anomaly || t <= 0 || n <= 0 || first_tick < 0) return GDN_ERR_ARG;
   if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
   if (GAPS && (!valid || (first_tick > 0 && !halo_valid))) return GDN_ERR_ARG;
-  const int runs = (t + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(score_smooth_max_kernel<GAPS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt,
+  hipLaunchKernelGGL(score_smooth_max_kernel<GAPS>, dim3(sweep_grid(t)), dim3(256), 0, (hipStream_t)stream, pred, gt,
                      med_iqr, t, n, first_tick, halo_pred, halo_gt, scores, anomaly, valid, halo_valid);
   return gdn_launch_status();
 }
@@ -1601,9 +1457,7 @@ int smooth_topm(const float* pred, const float* gt, const double* med_iqr, int t
   if (first_tick > 0 && (!halo_pred || !halo_gt)) return GDN_ERR_ARG;
   if (GAPS && (!valid || (first_tick > 0 && !halo_valid))) return GDN_ERR_ARG;
   if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  const int runs = (t + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(score_smooth_topm_kernel<GAPS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, med_iqr,
+  hipLaunchKernelGGL(score_smooth_topm_kernel<GAPS>, dim3(sweep_grid(t)), dim3(256), 0, (hipStream_t)stream, pred, gt, med_iqr,
                      t, n, first_tick, halo_pred, halo_gt, m, top_scores, top_sensors, valid, halo_valid);
   return gdn_launch_status();
 }

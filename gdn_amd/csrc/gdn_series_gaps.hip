@@ -5,9 +5,12 @@
 // gdn_score_select (total = the kept ticks) calibrates on complete ticks only.  Plain C++: no inline assembly, no
 // atomics.  (The scoring launches of a step are the GAPS instantiations of the two sweeps in gdn_score.hip.)
 #pragma clang fp contract(off)
-#include "gdn_common.hpp"
+#include "gdn_score_sweep.hpp"
 
 namespace {
+
+using gdn_sweep::filler_key;
+using gdn_sweep::score_key;
 
 #define GDN_SERIES_BLOCK 64          // ticks per block = lanes of a wave: raw column c sits in block c / 64, lane c % 64
 #define GDN_SERIES_WAVES 4
@@ -149,8 +152,6 @@ __global__ __launch_bounds__(GDN_SERIES_WAVES * 64) void series_fill_kernel(
 }
 
 // score_keys_kernel (gdn_score.hip) with the keep flags: a tick that is not kept gets the filler in all n keys.
-constexpr unsigned long long KEEP_FILLER = ~0ull;                    // gdn_score.hip's FILLER: the select never counts it
-
 __global__ __launch_bounds__(256) void score_keys_keep_kernel(const float* __restrict__ pred,
                                                               const float* __restrict__ gt,
                                                               const unsigned char* __restrict__ keep, int t, int n,
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void score_keys_keep_kernel(const float* __res
     const int tick = t0 + r, s = s0 + lane;
     if (tick < t && s < n) {
       const size_t o = (size_t)tick * n + s;
-      tile[r][lane] = fabs((double)pred[o] - (double)gt[o]);
+      tile[r][lane] = score_key(pred[o], gt[o]);
     }
   }
   __syncthreads();
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(256) void score_keys_keep_kernel(const float* __res
   for (int r = wv; r < 64; r += 4) {
     const int s = s0 + r;
     if (s < n && tick < pitch)
-      keys[(size_t)s * pitch + tick] = real ? tile[lane][r] : __longlong_as_double((long long)KEEP_FILLER);
+      keys[(size_t)s * pitch + tick] = real ? tile[lane][r] : filler_key();
   }
 }
 

@@ -10,13 +10,13 @@
 // Rolling calibration (opt-in, include/gdn_hip.h "Rolling calibration"): gdn_stream_calib_write sits between the score
 // and the advance launch and keeps |pred - gt| of the last R stream ticks in a ring that gdn_score_select reads as it
 // stands; it reads the state and writes the ring only.
-#include "gdn_common.hpp"
+#include "gdn_score_sweep.hpp"
 
-// The float64 scoring here must round where gdn_score.hip's sweep rounds (the stream is compared with it bit for bit):
-// every product and sum is an operation of its own — no contraction of a normalised error's multiply into the 4-tap sum.
-#pragma clang fp contract(off)
+// (float64 scoring: gdn_score_sweep.hpp switches FMA contraction off for this unit)
 
 namespace {
+
+using namespace gdn_sweep;
 
 #define GDN_STREAM_HEADER 4          // int64 words ahead of the carry: ticks, alarms, logged, (reserved)
 #define GDN_STREAM_THREADS 256
@@ -152,16 +152,33 @@ __global__ __launch_bounds__(GDN_FILL_WAVES * 64) void gdn_stream_fill_kernel(
   }
 }
 
-// Normalise, smooth, top m, flag: the sweep of score_smooth_topm_kernel (gdn_score.hip) — the same loads, the same
-// float64 operations in the same order, the same m rounds of "wave maximum of (score, sensor)" — with the series
-// position of the chunk's first tick read from the state and the three normalised errors before the chunk taken from
-// the carry (rows 0, 1, 2 = three, two, one tick before; zeros where the series has no such tick).  One wave owns a run
-// of 8 consecutive ticks of the chunk; only the run at tick 0 reaches back into the carry.
-// GAPS: `valid` [t, n] (1 = a real reading) travels as one bit per loaded row and the normalised error of a missing
-// reading is 0.0 — in its own tick's mean, as a predecessor inside the chunk, and (through gdn_stream_advance's carry)
-// as a predecessor of the next push.  Without GAPS `valid` is not read and the kernel is the one it was.
-constexpr int RUN = 8;
-constexpr int TOPM_MAX = 8;
+// Normalise, smooth, top m, flag: the sweep of gdn_score_sweep.hpp with top-m lists, as score_smooth_topm_kernel
+// (gdn_score.hip) runs it, over a push.  Here: the series position of the chunk's first tick is read from the state,
+// and only the run at tick 0 reaches back: its three predecessors are the carry (rows 0, 1, 2 = three, two, one tick
+// before; zeros where the series has no such tick, GAPS: 0.0 for a missing reading, through gdn_stream_advance).
+
+// Rows before the chunk are never used as values (row 0 stands in for the loads); rows past it are clamped.
+struct StreamSource {
+  const float *pred, *gt;
+  const unsigned char* valid;
+  const double* carry;
+  int t, n;
+  __device__ __forceinline__ size_t at(int tt) const { return (size_t)(tt < 0 ? 0 : min(tt, t - 1)) * n; }
+  __device__ __forceinline__ const float* pred_row(int tt) const { return pred + at(tt); }
+  __device__ __forceinline__ const float* gt_row(int tt) const { return gt + at(tt); }
+  __device__ __forceinline__ const unsigned char* valid_row(int tt) const { return valid + at(tt); }
+  template <typename FA, typename FB>
+  __device__ __forceinline__ void before(int t0, const Lanes& l, double (&a)[3], double (&b)[3], FA&& na,
+                                         FB&& nb) const {
+    if (t0 == 0) {                                 // (wave uniform) all six loads in one block: one round trip
+      a[0] = carry[l.ca]; a[1] = carry[(size_t)n + l.ca]; a[2] = carry[2 * (size_t)n + l.ca];
+      b[0] = carry[l.cb]; b[1] = carry[(size_t)n + l.cb]; b[2] = carry[2 * (size_t)n + l.cb];
+    } else {
+      a[0] = na(0); a[1] = na(1); a[2] = na(2);
+      b[0] = nb(0); b[1] = nb(1); b[2] = nb(2);
+    }
+  }
+};
 
 template <bool GAPS>
 __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
@@ -172,9 +189,8 @@ __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int nruns = (t + RUN - 1) / RUN;
-  constexpr int NONE = 0x7fffffff;               // sensor of a masked / missing candidate (score -inf)
   const long long first_tick = reinterpret_cast<const long long*>(state)[0];
-  const double* __restrict__ carry = stream_carry(state);
+  const StreamSource src{pred, gt, valid, stream_carry(state), t, n};
   const double thr = threshold[0];
   for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb) {
     const int t0 = run * RUN, t1 = min(t, t0 + RUN);
@@ -186,90 +202,16 @@ __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
       ci[u] = NONE;
     }
     for (int s0 = 0; s0 < n; s0 += 128) {
-      const int sa_ = s0 + lane, sb_ = s0 + 64 + lane;
-      const bool la = sa_ < n, lb = sb_ < n;
-      const int ca = la ? sa_ : n - 1, cb = lb ? sb_ : n - 1;
-      const double meda = med_iqr[2 * ca], dena = 1.0 / (fabs(med_iqr[2 * ca + 1]) + 1e-2);
-      const double medb = med_iqr[2 * cb], denb = 1.0 / (fabs(med_iqr[2 * cb + 1]) + 1e-2);
-      float pa[RUN + 3], ga[RUN + 3], pb[RUN + 3], gb[RUN + 3];
-      unsigned oka = 0u, okb = 0u;                 // GAPS: bit u = the reading of row u is real
-#pragma unroll
-      for (int u = 0; u < RUN + 3; ++u) {
-        const int tt = t0 - 3 + u;                 // < 0 (run 0 only): the value comes from the carry, row 0 is a stand-in
-        const int row = tt < 0 ? 0 : min(tt, t - 1);
-        const float* pp = pred + (size_t)row * n;
-        const float* gg = gt + (size_t)row * n;
-        pa[u] = pp[ca]; ga[u] = gg[ca]; pb[u] = pp[cb]; gb[u] = gg[cb];
-        if constexpr (GAPS) {
-          const unsigned char* vv = valid + (size_t)row * n;
-          oka |= (vv[ca] ? 1u : 0u) << u;
-          okb |= (vv[cb] ? 1u : 0u) << u;
-        }
-      }
-      auto norm = [&](float pv, float gv, double med, double inv_den, unsigned ok, int u) -> double {
-        const double a = (fabs((double)pv - (double)gv) - med) * inv_den;
-        if constexpr (GAPS) return ((ok >> u) & 1u) ? a : 0.0;
-        return a;
-      };
-      double a3, a2, a1, b3, b2, b1;
-      if (t0 == 0) {                               // (wave uniform)
-        a3 = carry[ca]; a2 = carry[(size_t)n + ca]; a1 = carry[2 * (size_t)n + ca];
-        b3 = carry[cb]; b2 = carry[(size_t)n + cb]; b1 = carry[2 * (size_t)n + cb];
-      } else {
-        a3 = norm(pa[0], ga[0], meda, dena, oka, 0); a2 = norm(pa[1], ga[1], meda, dena, oka, 1);
-        a1 = norm(pa[2], ga[2], meda, dena, oka, 2);
-        b3 = norm(pb[0], gb[0], medb, denb, okb, 0); b2 = norm(pb[1], gb[1], medb, denb, okb, 1);
-        b1 = norm(pb[2], gb[2], medb, denb, okb, 2);
-      }
-#pragma unroll
-      for (int u = 0; u < RUN; ++u) {
-        const int tick = t0 + u;
-        if (tick >= t1) continue;                  // (wave uniform)
-        const double a0 = norm(pa[3 + u], ga[3 + u], meda, dena, oka, 3 + u);
-        const double b0 = norm(pb[3 + u], gb[3 + u], medb, denb, okb, 3 + u);
-        double sma = 0.0, smb = 0.0;
-        if (first_tick + tick >= 3) {               // numpy sums the 4 values left to right
-          sma = (((a3 + a2) + a1) + a0) / 4.0;
-          smb = (((b3 + b2) + b1) + b0) / 4.0;
-        }
-        a3 = a2; a2 = a1; a1 = a0;
-        b3 = b2; b2 = b1; b1 = b0;
-        // this lane's three candidates
-        double v0 = la ? sma : -INFINITY, v1 = lb ? smb : -INFINITY, v2 = cs[u];
-        int i0 = la ? sa_ : NONE, i1 = lb ? sb_ : NONE, i2 = ci[u];
-        double ns = -INFINITY;
-        int ni = NONE;
-        for (int r = 0; r < m; ++r) {              // (m is wave uniform)
-          double bs = v0;
-          int bi = i0;
-          if (v1 > bs || (v1 == bs && i1 < bi)) { bs = v1; bi = i1; }
-          if (v2 > bs || (v2 == bs && i2 < bi)) { bs = v2; bi = i2; }
-#pragma unroll
-          for (int d = 32; d >= 1; d >>= 1) {
-            const double os = __shfl_xor(bs, d);
-            const int oi = __shfl_xor(bi, d);
-            if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
-          }
-          if (bi != NONE) {                        // the owner masks its candidate out
-            if (i0 == bi) { v0 = -INFINITY; i0 = NONE; }
-            if (i1 == bi) { v1 = -INFINITY; i1 = NONE; }
-            if (i2 == bi) { v2 = -INFINITY; i2 = NONE; }
-          }
-          if (lane == r) { ns = bs; ni = bi; }
-        }
-        cs[u] = ns;
-        ci[u] = ni;
-      }
+      const Lanes l(s0, lane, n);
+      score_sweep<GAPS>(src, med_iqr, l, t0, t1, first_tick, [&](int u, int, double sma, double smb) {
+        topm_merge(l, lane, m, sma, smb, cs[u], ci[u]);
+      });
     }
-    if (lane < m) {
+    topm_store(cs, ci, lane, m, t0, t1, top_scores, top_sensors);
+    if (lane == 0) {
 #pragma unroll
-      for (int u = 0; u < RUN; ++u) {
-        if (t0 + u < t1) {
-          top_scores[(size_t)(t0 + u) * m + lane] = cs[u];
-          top_sensors[(size_t)(t0 + u) * m + lane] = ci[u];
-          if (lane == 0) alarm[t0 + u] = cs[u] > thr ? 1 : 0;      // strict; a NaN score compares false
-        }
-      }
+      for (int u = 0; u < RUN; ++u)
+        if (t0 + u < t1) alarm[t0 + u] = cs[u] > thr ? 1 : 0;      // strict; a NaN score compares false
     }
   }
 }
@@ -315,7 +257,7 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
   double* __restrict__ carry = stream_carry(state);
   // carry: the last three of [carry0, carry1, carry2, a(chunk row 0), .., a(chunk row count - 1)]
   for (int s = tid; s < n; s += GDN_STREAM_THREADS) {
-    const double med = med_iqr[2 * s], inv_den = 1.0 / (fabs(med_iqr[2 * s + 1]) + 1e-2);
+    const Scale sc = sensor_scale(med_iqr, s);
     double next[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -324,10 +266,9 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
         next[j] = carry[(size_t)q * n + s];
       } else {
         const size_t at = (size_t)(q - 3) * n + s;
-        next[j] = (fabs((double)pred[at] - (double)chunk[at]) - med) * inv_den;     // gdn_stream_score's `norm`
-        if constexpr (GAPS) {
-          if (!valid[at]) next[j] = 0.0;
-        }
+        unsigned ok = 0u;
+        if constexpr (GAPS) ok = valid[at] ? 1u : 0u;
+        next[j] = norm<GAPS>(pred[at], chunk[at], sc.med, sc.inv_den, ok, 0);
       }
     }
 #pragma unroll
@@ -372,14 +313,13 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
 
 // The calibration ring (include/gdn_hip.h "Rolling calibration"): row b < count of the push is stream tick
 // ticks + b and owns slot (ticks + b) mod R of ring_keys [n, R] / ring_keep [R].  A kept tick writes its n keys
-// fabs((double)pred - (double)chunk) — score_keys_kernel's expression — and keep = 1; a tick that is not kept (its
+// score_key(pred, chunk) and keep = 1; a tick that is not kept (its
 // alarm flag under exclude_alarms; GAPS: a missing reading in any sensor) writes the filler into all n keys and
 // keep = 0, so no older tick survives in its slot.  Workgroup g: rows [64 g, 64 g + 64) of the push, sensor tiles of
 // 64 transposed through the padded LDS tile of score_keys_kernel: fp32 reads along sensors, fp64 writes along slots.
 // The slot is computed per row: a tile may wrap the ring's end once (c <= R: no two rows of a push share a slot).
 // Runs between the score launch (which wrote `alarm`) and the advance launch (`ticks` is still the push's first
 // tick); reads the state, writes the ring only.  GAPS first walks the tiles once to AND every row's validity bytes.
-constexpr unsigned long long CALIB_FILLER = ~0ull;          // gdn_score.hip's FILLER: the select never counts it
 #define GDN_CALIB_MIN_R 64
 #define GDN_CALIB_MAX_R (1 << 20)
 
@@ -420,7 +360,7 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_ker
       const int b = b0 + r, s = s0 + lane;
       if (b < count && s < n) {
         const size_t o = (size_t)b * n + s;
-        tile[r][lane] = fabs((double)pred[o] - (double)chunk[o]);
+        tile[r][lane] = score_key(pred[o], chunk[o]);
       }
     }
     __syncthreads();
@@ -431,7 +371,7 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_ker
       for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
         const int s = s0 + r;
         if (s < n)
-          ring_keys[(size_t)s * R + slot] = keep ? tile[lane][r] : __longlong_as_double((long long)CALIB_FILLER);
+          ring_keys[(size_t)s * R + slot] = keep ? tile[lane][r] : filler_key();
       }
     }
     __syncthreads();                                         // the tile is rewritten by the next sensor tile
@@ -465,8 +405,8 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_sen
       if (b < count && s < n) {
         const size_t o = (size_t)b * n + s;
         const bool keep = !(exclude_alarms && alarm[b] != 0) && valid[o] != 0;
-        const double e = fabs((double)pred[o] - (double)chunk[o]);
-        tile[r][lane] = keep ? e : __longlong_as_double((long long)CALIB_FILLER);
+        const double e = score_key(pred[o], chunk[o]);
+        tile[r][lane] = keep ? e : filler_key();
       }
     }
     __syncthreads();
@@ -510,9 +450,7 @@ int stream_score(const void* state, const float* pred, const float* chunk, const
       count < 1 || count > c) return GDN_ERR_ARG;
   if (n < 1 || n > 4096) return GDN_ERR_UNSUPPORTED;
   if (m < 1 || m > TOPM_MAX || m > n) return GDN_ERR_UNSUPPORTED;
-  const int runs = (count + RUN - 1) / RUN;
-  const int grid = min((runs + 3) / 4, gdn_cu_count() * 8);
-  hipLaunchKernelGGL(gdn_stream_score_kernel<GAPS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
+  hipLaunchKernelGGL(gdn_stream_score_kernel<GAPS>, dim3(sweep_grid(count)), dim3(256), 0, (hipStream_t)stream, state, pred, chunk,
                      med_iqr, threshold, count, n, m, top_scores, top_sensors, alarm, valid);
   return gdn_launch_status();
 }

@@ -122,6 +122,73 @@ def test_sharded_smoothing_with_halo_equals_whole_series(t, n, cuts, gpu_device)
     assert torch.equal(torch.cat(parts), whole)
 
 
+@pytest.mark.parametrize("gaps", [False, True])
+def test_the_three_sweep_kernels_write_each_others_bits(gaps, gpu_device):
+    """score_smooth_max, score_smooth_topm and stream_score run one sweep (csrc/gdn_score_sweep.hpp): tied to each
+    other directly, bit for bit.  n = 130: two sweeps, the second with 2 live lanes in its first half and none in its
+    second; t = 41: six runs, the last with one tick; pushes of 7 are ragged against the run of 8."""
+    from gdn_amd import ops
+    dev = gpu_device
+    t, n, w, cut, chunk = 41, 130, 4, 19, 7
+    g = torch.Generator().manual_seed(41)
+    pred = torch.rand((t, n), generator=g).to(dev)
+    gt = (pred + 0.1 * torch.randn((t, n), generator=g).to(dev)).contiguous()
+    valid = None
+    if gaps:
+        valid = (torch.rand((t, n), generator=g) >= 0.1).to(torch.uint8)
+        valid[10] = 0                                                # one whole tick missing
+        valid[0, 3] = valid[1, 5] = valid[2, 129] = 0                # rows 0, 1, 2
+        valid[t - 1, 7] = 0                                          # the last row
+        valid = valid.to(dev)
+    med_iqr = ops.score_quantiles(pred, gt)
+    sc, an = ops.score_smooth_max(pred, gt, med_iqr, want_scores=True, valid=valid)
+    # 1. top-1 is the maximum
+    ts1, _ = ops.score_smooth_topm(pred, gt, med_iqr, 1, valid=valid)
+    assert torch.equal(ts1[:, 0], an)
+    # 2. every top-3 entry is the table's entry of its sensor
+    ts3, ti3 = ops.score_smooth_topm(pred, gt, med_iqr, 3, valid=valid)
+    ticks = torch.arange(t, device=dev)
+    for r in range(3):
+        assert torch.equal(ts3[:, r], sc[ti3[:, r].long(), ticks]), r
+    # 3. two shards cut at tick 19, the second with the 3-row halo (and the halo's validity rows)
+    halo = dict(first_tick=cut, halo_pred=pred[cut - 3:cut].contiguous(), halo_gt=gt[cut - 3:cut].contiguous())
+    head_v = tail_v = None
+    if gaps:
+        head_v, tail_v = valid[:cut].contiguous(), valid[cut:].contiguous()
+        halo["halo_valid"] = valid[cut - 3:cut].contiguous()
+    head = (pred[:cut].contiguous(), gt[:cut].contiguous(), med_iqr)
+    tail = (pred[cut:].contiguous(), gt[cut:].contiguous(), med_iqr)
+    sc_a, an_a = ops.score_smooth_max(*head, want_scores=True, valid=head_v)
+    sc_b, an_b = ops.score_smooth_max(*tail, want_scores=True, valid=tail_v, **halo)
+    assert torch.equal(torch.cat([an_a, an_b]), an) and torch.equal(torch.cat([sc_a, sc_b], dim=1), sc)
+    ts_a, ti_a = ops.score_smooth_topm(*head, 3, valid=head_v)
+    ts_b, ti_b = ops.score_smooth_topm(*tail, 3, valid=tail_v, **halo)
+    assert torch.equal(torch.cat([ts_a, ts_b]), ts3) and torch.equal(torch.cat([ti_a, ti_b]), ti3)
+    # 4. the stream, pushed in chunks of 7, writes the whole-series top-m launch's lists
+    state = ops.stream_state(torch.rand((n, w), generator=g).to(dev), w)
+    thr = torch.full((1,), float("inf"), dtype=torch.float64, device=dev)
+    p_c = torch.zeros((chunk, n), device=dev)
+    g_c = torch.zeros((chunk, n), device=dev)
+    v_c = torch.zeros((chunk, n), dtype=torch.uint8, device=dev) if gaps else None
+    gap_chunk = torch.zeros((2, n), dtype=torch.int32, device=dev) if gaps else None     # (counters only: not scored)
+    gap_total = torch.zeros((2, n), dtype=torch.int64, device=dev) if gaps else None
+    ts_c = torch.zeros((chunk, 3), dtype=torch.float64, device=dev)
+    ti_c = torch.zeros((chunk, 3), dtype=torch.int32, device=dev)
+    al_c = torch.zeros((chunk,), dtype=torch.int32, device=dev)
+    got_s, got_i = [], []
+    for t0 in range(0, t, chunk):
+        r = min(chunk, t - t0)
+        p_c[:r], g_c[:r] = pred[t0:t0 + r], gt[t0:t0 + r]
+        if gaps:
+            v_c[:r] = valid[t0:t0 + r]
+        ops.stream_score(state, p_c, g_c, med_iqr, thr, 3, ts_c, ti_c, al_c, count=r, valid=v_c)
+        ops.stream_advance(state, g_c, p_c, med_iqr, al_c, ti_c, w, 3, count=r, valid=v_c, gap_chunk=gap_chunk,
+                           gaps=gap_total)
+        got_s.append(ts_c[:r].clone())
+        got_i.append(ti_c[:r].clone())
+    assert torch.equal(torch.cat(got_s), ts3) and torch.equal(torch.cat(got_i), ti3)
+
+
 def test_series_evaluator_from_raw_series_equals_window_tensor(gpu_device):
     """SURVEY §8f-1 through the evaluator: windows built in-kernel from the raw [N, T] series give the
     same predictions and anomaly scores as the host-built [T', N, W] tensor."""
