@@ -139,6 +139,7 @@ SIGNATURES = {
                                ctypes.c_longlong, ctypes.c_longlong] + [_p] * 9 + [_c_int, _p],
     "gdn_stream_events_bytes": [_c_int, ctypes.c_longlong],
     "gdn_stream_events": [_p] * 5 + [_c_int] * 5 + [ctypes.c_longlong, _p, _p],
+    "gdn_alarm_sweep": [_p, _p, ctypes.c_longlong, _p, _p, _p, _p, ctypes.c_longlong, _p, _p],
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

@@ -860,6 +860,188 @@ def episodes(scores, top_sensors=None, hi=None, lo=None, on: int = 1, off: int =
     return Episodes(start, end, peak, peak_tick, sensors, count)
 
 
+# --------------------------------------------------------------------------- alarm tuning
+class AlarmSweep(NamedTuple):
+    """The counters of P alarm settings against labelled incidents, device tensors.  Row p of `counts`
+    holds ops.ALARM_SWEEP_COUNTERS for (hi[p], lo[p], on[p], off[p]); -1 in all eight marks a row that is not a
+    setting (lo > hi, a NaN level, on / off outside 1 .. 4096)."""
+    hi: torch.Tensor             # [P] float64
+    lo: torch.Tensor             # [P] float64: the level used (hi * lo_frac already multiplied out)
+    on: torch.Tensor             # [P] int32
+    off: torch.Tensor            # [P] int32
+    counts: torch.Tensor         # [P, 8] int64
+    incidents: torch.Tensor      # [1] int64: I, the maximal runs of labelled ticks
+    label_ticks: torch.Tensor    # [1] int64
+    ticks: torch.Tensor          # [1] int64: T
+
+    def numpy(self) -> dict:
+        """Everything on the host (ONE synchronisation: one packed copy); the three totals as Python ints."""
+        P = self.hi.shape[0]
+        flat = torch.cat([self.hi.view(torch.int64), self.lo.view(torch.int64), self.on.long(), self.off.long(),
+                          self.counts.reshape(-1), self.incidents, self.label_ticks, self.ticks]).cpu().numpy()
+        out = {"hi": flat[:P].view(np.float64), "lo": flat[P:2 * P].view(np.float64),
+               "on": flat[2 * P:3 * P].astype(np.int32), "off": flat[3 * P:4 * P].astype(np.int32),
+               "counts": flat[4 * P:12 * P].reshape(P, 8)}
+        out["incidents"], out["label_ticks"], out["ticks"] = (int(v) for v in flat[12 * P:])
+        return out
+
+    def f1(self) -> torch.Tensor:
+        """[P] float64: the event F1 of every row, 2 * true_episodes * incidents_hit / (true_episodes * I + incidents_hit
+        * episodes); 0 where that denominator is 0 and in rows that are not settings."""
+        ep, te, ih = (self.counts[:, j].double() for j in range(3))
+        den = te * self.incidents.double() + ih * ep
+        return torch.where((den > 0) & (self.counts[:, 0] >= 0), 2.0 * te * ih / den.clamp(min=1.0), torch.zeros_like(den))
+
+    def best(self, min_recall: float = 0.0, max_delay=None) -> dict:
+        """The setting to deploy, chosen on the device: among the valid rows with incidents_hit / I >= min_recall (and a
+        mean delay delay_sum / incidents_hit <= max_delay) the largest event F1; ties go to the smaller delay_sum, then
+        the smaller alarm_ticks, then the lower row.  Returns dict(hi=, lo=, on=, off=) plus the row's counters, `row`
+        and `f1`: `StreamDetector(threshold=hi, events=dict(on=, off=, lo=))`.  No row qualifies: ValueError."""
+        c = self.counts
+        P = c.shape[0]
+        ih = c[:, 2].double()
+        ok = (c[:, 0] >= 0) & (ih >= float(min_recall) * self.incidents.double())
+        if max_delay is not None:
+            ok = ok & (c[:, 3].double() <= float(max_delay) * ih)
+        f1 = self.f1()
+        big = torch.iinfo(torch.int64).max
+        ok = ok & (f1 == torch.where(ok, f1, torch.full_like(f1, -1.0)).max())
+        for j in (3, 5):
+            ok = ok & (c[:, j] == torch.where(ok, c[:, j], torch.full_like(c[:, j], big)).min())
+        rows = torch.arange(P, device=c.device)
+        row = torch.where(ok, rows, torch.full_like(rows, P)).min()
+        at = row.clamp(max=P - 1)
+        packed = torch.cat([row.reshape(1), self.hi[at].view(torch.int64).reshape(1), self.lo[at].view(torch.int64).reshape(1),
+                            self.on[at].long().reshape(1), self.off[at].long().reshape(1), c[at],
+                            f1[at].view(torch.int64).reshape(1)]).cpu().numpy()
+        if int(packed[0]) >= P:
+            raise ValueError(f"alarm sweep: none of the {P} settings is valid and reaches min_recall = {min_recall}"
+                             + ("" if max_delay is None else f" within max_delay = {max_delay}"))
+        out = {"hi": float(packed[1:2].view(np.float64)[0]), "lo": float(packed[2:3].view(np.float64)[0]),
+               "on": int(packed[3]), "off": int(packed[4])}
+        out.update({name: int(v) for name, v in zip(ops.ALARM_SWEEP_COUNTERS, packed[5:13])})
+        out["row"], out["f1"] = int(packed[0]), float(packed[13:14].view(np.float64)[0])
+        return out
+
+
+def alarm_sweep_table(hi, lo=None, on=1, off=1, product: bool = True, lo_frac=None) -> tuple:
+    """The settings of a sweep as host tensors (hi, lo float64 [P]; on, off int32 [P]).  `product=True`: the grid of the
+    four sequences, hi slowest and off fastest; `product=False`: P explicit rows (scalars are broadcast).  The clear
+    level is `lo` (None: hi) or, through `lo_frac`, hi * lo_frac — a float64 multiply in torch whose product is the
+    level used.  Explicit rows are checked whole (ops.alarm_sweep_check); in a grid every value is, and a row of it
+    whose lo lies above its hi is left to the device, which marks it with -1."""
+    if lo is not None and lo_frac is not None:
+        raise ValueError("lo and lo_frac: give the clear level one way")
+
+    def seq(value, dtype):                                  # (Python floats are float64, a tensor keeps its values)
+        exact = isinstance(value, (torch.Tensor, np.ndarray))
+        return (torch.as_tensor(value) if exact else torch.as_tensor(value, dtype=dtype)).detach().cpu().to(dtype).reshape(-1)
+    if not product:
+        if lo_frac is not None:
+            h, f = seq(hi, torch.float64), seq(lo_frac, torch.float64)
+            if f.numel() not in (1, h.numel()) and h.numel() != 1:
+                raise ValueError(f"lo_frac: {f.numel()} values, hi has {h.numel()}")
+            lo = h * f
+        return ops.alarm_sweep_check(hi, hi if lo is None else lo, on, off)
+    # every sequence checked on its own (the row in a message is the place in that sequence), then the grid
+    h = ops.alarm_sweep_check(hi, hi, 1, 1)[0]
+    n_on, n_off = ops.alarm_sweep_check(0.0, 0.0, on, 1)[2], ops.alarm_sweep_check(0.0, 0.0, 1, off)[3]
+    second = seq(1.0 if (lo is None and lo_frac is None) else (lo if lo_frac is None else lo_frac), torch.float64)
+    if bool((second != second).any()):
+        raise ValueError(f"{'lo' if lo_frac is None else 'lo_frac'}[{int(torch.nonzero(second != second)[0])}] = nan: "
+                         "the level must be a number")
+    i, j, k, m = (g.reshape(-1) for g in torch.meshgrid(*(torch.arange(c.numel()) for c in (h, second, n_on, n_off)),
+                                                       indexing="ij"))
+    glo = second[j] if lo is not None else h[i] * second[j]
+    return ops.alarm_sweep_check(h[i], glo, n_on[k].long(), n_off[m].long(), ordered=False)
+
+
+def _labels_u8(labels, device) -> torch.Tensor:
+    labels = torch.as_tensor(labels).to(device)
+    if labels.dim() != 1:
+        raise ValueError(f"labels: expected [T], got {tuple(labels.shape)}")
+    return (labels > 0).to(torch.uint8)
+
+
+def _incident_edges(lab: torch.Tensor) -> tuple:
+    """(first tick, end (exclusive)) of every maximal run of labelled ticks of lab [T] uint8, int64 on lab's device."""
+    pad = torch.zeros((1,), dtype=lab.dtype, device=lab.device)
+    step = torch.diff(torch.cat([pad, lab, pad]).to(torch.int8))
+    return torch.nonzero(step == 1)[:, 0], torch.nonzero(step == -1)[:, 0]
+
+
+def alarm_sweep(scores, labels, hi, lo=None, on=1, off=1, product: bool = True, lo_frac=None) -> AlarmSweep:
+    """Sweep alarm settings against labelled incidents: `scores` [T] float64 on the device — or a
+    SeriesEvaluator built with top_m >= 1 whose step() has run: its top_scores[:, 0] — and `labels` [T] of any numeric
+    or bool dtype (> 0: the tick lies inside an incident).  The settings: alarm_sweep_table(hi, lo, on, off, product,
+    lo_frac).  One gdn_alarm_sweep launch for the counters; I and the labelled ticks by torch ops; no synchronisation."""
+    if isinstance(scores, SeriesEvaluator):
+        if not scores.top_m:
+            raise ValueError("alarm_sweep needs an evaluator built with top_m >= 1")
+        scores = scores.top_scores[:, 0].contiguous()
+    t_hi, t_lo, t_on, t_off = alarm_sweep_table(hi, lo, on, off, product, lo_frac)
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise _lib.GdnHipError("scores: a float64 tensor on a HIP device is needed (no CPU fallback)")
+    dev = scores.device
+    lab = _labels_u8(labels, dev)
+    if lab.shape != scores.shape:
+        raise ValueError(f"labels: {tuple(lab.shape)}, scores {tuple(scores.shape)}")
+    t_hi, t_lo, t_on, t_off = (t.to(dev) for t in (t_hi, t_lo, t_on, t_off))
+    counts = ops.alarm_sweep(scores, lab, t_hi, t_lo, t_on, t_off)
+    step = torch.diff(lab.to(torch.int8), prepend=torch.zeros((1,), dtype=torch.int8, device=dev))
+    return AlarmSweep(t_hi, t_lo, t_on, t_off, counts, (step == 1).sum().reshape(1), lab.sum(dtype=torch.int64).reshape(1),
+                      torch.full((1,), scores.shape[0], dtype=torch.int64, device=dev))
+
+
+class EpisodeReport(NamedTuple):
+    """One setting's episodes against the labelled incidents, row by row (device tensors).  Per incident: `begin`, `end`
+    (exclusive), `hit`, `episode` (the row of the first episode that overlaps it, -1: none), `delay` = max(0, that
+    episode's raise tick - begin), 0 where not hit.  Per episode: `label_ticks` inside its span, `true` = it holds one;
+    `spans` [rows, 2]: (start, end) with an open episode ending at T."""
+    begin: torch.Tensor
+    end: torch.Tensor
+    hit: torch.Tensor
+    episode: torch.Tensor
+    delay: torch.Tensor
+    label_ticks: torch.Tensor
+    true: torch.Tensor
+    spans: torch.Tensor
+    open: torch.Tensor           # [1] int64
+
+    def counters(self) -> torch.Tensor:
+        """[8] int64: the aggregates in the order of ops.ALARM_SWEEP_COUNTERS — by construction the sweep's row."""
+        z = torch.zeros((1,), dtype=torch.int64, device=self.begin.device)
+        delay = torch.cat([self.delay, z])
+        return torch.stack([z[0] + self.spans.shape[0], self.true.sum(), self.hit.sum(), delay.sum(), delay.max(),
+                            (self.spans[:, 1] - self.spans[:, 0]).sum(), self.label_ticks.sum(), self.open[0]])
+
+
+def episode_report(episodes: Episodes, labels, on: int) -> EpisodeReport:
+    """Per-incident and per-episode tables for ONE setting: `episodes` from `harness.episodes(...)` (first_tick 0) with
+    on-delay `on`, `labels` [T] as in alarm_sweep.  Torch ops on the device (searchsorted over the episodes' ends, a
+    prefix sum of the labels) and one host read of the count: this is reporting.  A table that holds fewer rows than
+    were raised (count > cap) is refused."""
+    on = ops.episodes_check(None, None, on, 1, 0)[2]
+    cap, count = episodes.start.shape[0], int(episodes.count.item())
+    if count > cap:
+        raise ValueError(f"episode_report: {count} episodes were raised, the table keeps cap = {cap}: scan with a larger cap")
+    dev = episodes.start.device
+    lab = _labels_u8(labels, dev)
+    T = lab.shape[0]
+    start = episodes.start[:count]
+    end = torch.where(episodes.end[:count] < 0, torch.full_like(start, T), episodes.end[:count])
+    upto = torch.cat([torch.zeros((1,), dtype=torch.int64, device=dev), torch.cumsum(lab, 0, dtype=torch.int64)])
+    label_ticks = upto[end] - upto[start.clamp(min=0)]
+    begin, stop = _incident_edges(lab)
+    k = torch.searchsorted(end, begin, right=True)          # the first episode that ends after the incident begins
+    far = torch.full((1,), T + 1, dtype=torch.int64, device=dev)
+    hit = torch.cat([start, far])[k] < stop
+    delay = torch.where(hit, (torch.cat([start, far])[k] + (on - 1) - begin).clamp(min=0), torch.zeros_like(begin))
+    is_open = (episodes.end[count - 1:count] < 0).long() if count else torch.zeros((1,), dtype=torch.int64, device=dev)
+    return EpisodeReport(begin, stop, hit, torch.where(hit, k, torch.full_like(k, -1)), delay, label_ticks,
+                         label_ticks > 0, torch.stack([start, end], dim=1), is_open)
+
+
 # --------------------------------------------------------------------------- graphed train step
 class _CapturedStep:
     """One optimisation step of the reference's train() (train.py:52-79) issued as two halves: `_first` (the caller's

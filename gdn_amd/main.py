@@ -121,6 +121,8 @@ class Main:
         self.device = torch.device("cuda", 0)                               # util/env.py: `cuda` + CUDA_VISIBLE_DEVICES
         feature_map = get_feature_map(dataset, root)
         fc_struc = get_fc_graph_struc(dataset, root)
+        if env_config.get("tune_alarm"):
+            check_attack_column(os.path.join(root, dataset, "test.csv"))
         train_np, _ = read_series(os.path.join(root, dataset, "train.csv"), feature_map, want_labels=False)
         test_np, test_labels = read_series(os.path.join(root, dataset, "test.csv"), feature_map, want_labels=True)
         self.feature_map = feature_map
@@ -232,7 +234,34 @@ class Main:
                                                                 self.env_config.get("stream_clear"),
                                                                 self.env_config.get("stream_events") or ""),
                                     events_path=self.env_config.get("stream_events") or "")
+        if self.env_config.get("tune_alarm"):
+            self.tune_alarm(best_model, gt, labels, self.env_config["tune_alarm"],
+                            hi_steps=int(self.env_config.get("tune_hi_steps") or 32),
+                            on=self.env_config.get("tune_on") or TUNE_ON, off=self.env_config.get("tune_off") or TUNE_OFF)
         return info
+
+    def tune_alarm(self, model, gt, labels, path: str, hi_steps: int = 32, on="1,2,3,5,10", off="1,5,10,30"):
+        """-tune_alarm OUT.npz: which (threshold, clear level, on-delay, off-delay) to deploy.  The test
+        ticks are scored once (s_t = the evaluator's top_scores[:, 0]), a grid of settings — `hi_steps` raise levels
+        taken evenly from the thresholds of the report's 400-step sweep, clear levels hi * TUNE_LO_FRAC, the on / off
+        delays of -tune_on / -tune_off — is swept against the labelled incidents in one launch, the best row by event
+        F1 is printed, and the whole sweep plus the choice is saved (numpy appends the suffix when OUT lacks it)."""
+        ev = harness.SeriesEvaluator(model, None, gt, batch=8192, use_graph=False, series=self.test_series, top_m=1)
+        ev.step()
+        scores = ev.top_scores[:, 0].contiguous()
+        _f, ths, _o = evaluate._sweep(scores, labels.reshape(-1) > 0, evaluate.TH_STEPS)
+        hi, ticks_on, ticks_off = tune_alarm_grid(ths, hi_steps, on, off)
+        sweep = harness.alarm_sweep(scores, labels, hi, lo_frac=TUNE_LO_FRAC, on=ticks_on, off=ticks_off)
+        best = sweep.best()
+        self.tune_result = dict(sweep.numpy(), **{"best_" + k: v for k, v in best.items()})
+        np.savez(path, **self.tune_result)
+        print(f"tune_alarm: {sweep.hi.shape[0]} settings over {self.tune_result['ticks']} ticks with "
+              f"{self.tune_result['incidents']} labelled incidents; best event F1 {best['f1']:.4f}: threshold "
+              f"{best['hi']:.6g}, clear {best['lo']:.6g}, on {best['on']}, off {best['off']} -> {best['episodes']} episodes "
+              f"({best['true_episodes']} true), {best['incidents_hit']} incidents hit, mean delay "
+              f"{best['delay_sum'] / max(1, best['incidents_hit']):.1f} ticks (max {best['delay_max']}), "
+              f"{best['alarm_ticks']} alarm ticks")
+        return self.tune_result
 
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
                            recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False,
@@ -474,7 +503,57 @@ def build_parser():
     parser.add_argument("-stream_clear", help="with -stream: the clear level of an episode (default: the threshold)",
                         type=float, default=None)
     parser.add_argument("-stream_events", help="with -stream: save the episode table to this .npz", type=str, default="")
+    parser.add_argument("-tune_alarm", help="after the report, sweep alarm settings (threshold, clear level, on / off "
+                        "delay) against the labelled incidents of the test series, print the best one and save the "
+                        "sweep to this .npz (test.csv needs an `attack` column)", type=str, default="")
+    parser.add_argument("-tune_hi_steps", help="with -tune_alarm: raise levels, taken evenly from the report's "
+                        "400-step threshold sweep", type=int, default=None)
+    parser.add_argument("-tune_on", help="with -tune_alarm: on-delays in ticks, comma separated", type=str, default=None)
+    parser.add_argument("-tune_off", help="with -tune_alarm: off-delays in ticks, comma separated", type=str, default=None)
     return parser
+
+
+TUNE_ON, TUNE_OFF, TUNE_LO_FRAC = "1,2,3,5,10", "1,5,10,30", (1.0, 0.9, 0.75, 0.5)
+
+
+def check_tune_alarm(tune_alarm: bool, hi_steps, on, off) -> None:
+    """-tune_hi_steps, -tune_on and -tune_off shape the grid of -tune_alarm OUT.npz: refused by name without it, and
+    when they do not hold what a grid needs."""
+    for given, flag in ((hi_steps is not None, "-tune_hi_steps"), (on is not None, "-tune_on"), (off is not None, "-tune_off")):
+        if given and not tune_alarm:
+            raise ValueError(f"{flag} needs -tune_alarm OUT.npz: it shapes the grid of the alarm sweep")
+    if hi_steps is not None and not 1 <= int(hi_steps) <= evaluate.TH_STEPS:
+        raise ValueError(f"-tune_hi_steps {hi_steps}: 1 to {evaluate.TH_STEPS} raise levels")
+    for text, flag in ((on, "-tune_on"), (off, "-tune_off")):
+        if text is not None:
+            tune_ticks(text, flag)
+
+
+def tune_ticks(text: str, flag: str) -> list:
+    """'1,2,3,5,10' -> [1, 2, 3, 5, 10]; anything but whole numbers from 1 to 4096 is refused by the flag's name."""
+    try:
+        ticks = [int(part) for part in str(text).split(",")]
+    except ValueError:
+        raise ValueError(f"{flag} {text!r}: whole numbers of ticks, comma separated") from None
+    if not ticks or any(not 1 <= v <= 4096 for v in ticks):
+        raise ValueError(f"{flag} {text!r}: every delay is 1 to 4096 ticks")
+    return ticks
+
+
+def tune_alarm_grid(thresholds, hi_steps: int, on: str, off: str) -> tuple:
+    """(hi, on, off) of -tune_alarm's grid: `hi_steps` of the sweep's thresholds at evenly spaced places, duplicates
+    dropped (a float64 tensor on the thresholds' device), and the two lists of delays."""
+    thresholds = torch.as_tensor(thresholds, dtype=torch.float64).reshape(-1)
+    at = torch.linspace(0, thresholds.numel() - 1, int(hi_steps), dtype=torch.float64).round().long()
+    return torch.unique(thresholds[at.to(thresholds.device)]), tune_ticks(on, "-tune_on"), tune_ticks(off, "-tune_off")
+
+
+def check_attack_column(path: str) -> None:
+    """-tune_alarm matches episodes against labelled incidents: a test file without an `attack` column is refused by
+    name (the report itself reads such a file as all normal)."""
+    import pandas as pd
+    if "attack" not in pd.read_csv(path, sep=",", index_col=0, nrows=0).columns:
+        raise ValueError(f"-tune_alarm needs labels: {path} has no `attack` column")
 
 
 def check_stream_events(stream_on: bool, stream_off: bool, stream_clear: bool, stream_events: bool, stream: bool) -> None:
@@ -538,6 +617,7 @@ def from_args(argv=None) -> Main:
     check_stream_checkpoint(bool(args.stream_save), bool(args.stream_resume), bool(args.stream))
     check_stream_events(args.stream_on is not None, args.stream_off is not None, args.stream_clear is not None,
                         bool(args.stream_events), bool(args.stream))
+    check_tune_alarm(bool(args.tune_alarm), args.tune_hi_steps, args.tune_on, args.tune_off)
     random.seed(args.random_seed)                      # main.py:221-228
     np.random.seed(args.random_seed)
     torch.manual_seed(args.random_seed)
@@ -556,7 +636,9 @@ def from_args(argv=None) -> Main:
                   "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor,
                   "stream_raw": args.stream_raw, "prep": args.prep, "stream_save": args.stream_save,
                   "stream_resume": args.stream_resume, "stream_on": args.stream_on, "stream_off": args.stream_off,
-                  "stream_clear": args.stream_clear, "stream_events": args.stream_events}
+                  "stream_clear": args.stream_clear, "stream_events": args.stream_events,
+                  "tune_alarm": args.tune_alarm, "tune_hi_steps": args.tune_hi_steps, "tune_on": args.tune_on,
+                  "tune_off": args.tune_off}
     return Main(train_config, env_config, debug=False)
 
 

@@ -1400,3 +1400,78 @@ def stream_events(state, top_scores, top_sensors, threshold, clear, on: int, off
     _lib.call("gdn_stream_events", _ptr(state), _ptr(top_scores), _ptr(top_sensors), _ptr(threshold), _ptr(clear), c,
               count, m, int(on), int(off), int(cap), _ptr(events), _stream())
     return events
+
+
+# --------------------------------------------------------------------------- alarm tuning
+ALARM_SWEEP_COUNTERS = ("episodes", "true_episodes", "incidents_hit", "delay_sum", "delay_max", "alarm_ticks",
+                        "alarm_label_ticks", "open")
+_ALARM_SWEEP_MAX_T, _ALARM_SWEEP_MAX_P = 1 << 26, 1 << 20
+
+
+def alarm_sweep_check(hi, lo, on, off, ordered: bool = True) -> tuple:
+    """(hi, lo float64 [P]; on, off int32 [P]) as host tensors: scalars and one-element sequences are broadcast to the
+    longest of the four.  Refused by the field's name and the row: a NaN level, lo > hi, on / off outside 1 .. 4096,
+    lengths that do not agree, no row or more than 2^20.  (The device marks such rows with -1 instead: the kernel does
+    not validate.)  `ordered=False` lets lo > hi through: the rows of a grid of levels that the device is to mark."""
+    cols = {}
+    for name, value, dtype in (("hi", hi, torch.float64), ("lo", lo, torch.float64), ("on", on, torch.int64),
+                               ("off", off, torch.int64)):
+        exact = hasattr(value, "dtype") or dtype is torch.int64     # (a tensor or an array keeps its values; Python floats are float64)
+        t = (torch.as_tensor(value) if exact else torch.as_tensor(value, dtype=torch.float64)).detach().cpu()
+        if dtype is torch.int64 and (t.is_floating_point() or t.dtype is torch.bool):
+            raise TypeError(f"{name}: whole numbers of ticks are needed, got {t.dtype}")
+        if t.dim() > 1:
+            raise ValueError(f"{name}: a scalar or a sequence is needed, got shape {tuple(t.shape)}")
+        cols[name] = t.to(dtype).reshape(-1)
+    P = max(c.numel() for c in cols.values())
+    for name, c in cols.items():
+        if c.numel() not in (1, P):
+            raise ValueError(f"{name}: {c.numel()} values, the longest of hi, lo, on, off has {P}")
+        cols[name] = c.expand(P).contiguous()
+    if not 1 <= P <= _ALARM_SWEEP_MAX_P:
+        raise ValueError(f"{P} settings: a sweep takes 1 to {_ALARM_SWEEP_MAX_P} rows")
+
+    def first(mask):
+        return int(torch.nonzero(mask)[0])
+    for name in ("hi", "lo"):
+        bad = cols[name] != cols[name]
+        if bool(bad.any()):
+            raise ValueError(f"{name}[{first(bad)}] = nan: the level must be a number")
+    bad = cols["lo"] > cols["hi"]
+    if ordered and bool(bad.any()):
+        r = first(bad)
+        raise ValueError(f"lo[{r}] = {float(cols['lo'][r])} lies above hi[{r}] = {float(cols['hi'][r])}: the clear level "
+                         "must be at or below the raise level")
+    for name in ("on", "off"):
+        bad = (cols[name] < 1) | (cols[name] > _EPISODES_MAX_RUN)
+        if bool(bad.any()):
+            r = first(bad)
+            raise ValueError(f"{name}[{r}] = {int(cols[name][r])}: 1 to {_EPISODES_MAX_RUN} ticks")
+    return cols["hi"], cols["lo"], cols["on"].to(torch.int32), cols["off"].to(torch.int32)
+
+
+def alarm_sweep(scores, labels, hi, lo, on, off, out=None):
+    """gdn_alarm_sweep (include/gdn_hip.h "Alarm tuning"): scores [T] float64, labels [T] uint8, hi / lo [P] float64 and
+    on / off [P] int32, all on the device -> counts [P, 8] int64 (ALARM_SWEEP_COUNTERS; -1 in a row that is not a
+    setting).  ONE launch, no synchronisation.  `out`: a contiguous int64 device tensor of P * 8 elements to write."""
+    scores = _chk(scores, torch.float64, "scores")
+    labels = _chk(labels, torch.uint8, "labels")
+    hi, lo = _chk(hi, torch.float64, "hi"), _chk(lo, torch.float64, "lo")
+    on, off = _chk(on, torch.int32, "on"), _chk(off, torch.int32, "off")
+    if scores.dim() != 1 or labels.shape != scores.shape:
+        raise ValueError(f"expected scores [T] and labels [T], got {tuple(scores.shape)} and {tuple(labels.shape)}")
+    if hi.dim() != 1:
+        raise ValueError(f"expected hi [P], got {tuple(hi.shape)}")
+    for t, name in ((lo, "lo"), (on, "on"), (off, "off")):
+        if t.shape != hi.shape:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, hi has {tuple(hi.shape)}")
+    T, P = scores.shape[0], hi.shape[0]
+    if not 1 <= T <= _ALARM_SWEEP_MAX_T or not 1 <= P <= _ALARM_SWEEP_MAX_P:
+        raise _lib.GdnHipError(f"alarm sweep: no kernel for T = {T}, P = {P} (1 <= T <= 2^26, 1 <= P <= 2^20)")
+    if out is None:
+        out = torch.empty((P, 8), dtype=torch.int64, device=scores.device)
+    else:
+        _stream_buf(out, torch.int64, P * 8, "out")
+    _lib.call("gdn_alarm_sweep", _ptr(scores), _ptr(labels), T, _ptr(hi), _ptr(lo), _ptr(on), _ptr(off), P, _ptr(out),
+              _stream())
+    return out

@@ -1043,6 +1043,29 @@ int gdn_stream_events(const void* state, const double* top_scores, const int32_t
                       const double* clear, int c, int count, int m, int on, int off, long long E, void* events,
                       void* stream);
 
+/* ---- Alarm tuning ----------------------------------------------------------------------------
+ * Which (hi, lo, on, off) to deploy (additive, the ABI version does not move): the episodes of P settings
+ * over one scored series, matched against labelled incidents.  scores [T] float64 (s_t, as above), labels [T] uint8
+ * (non-zero: the tick lies inside a labelled incident), hi [P], lo [P] float64, on [P], off [P] int32, all on the
+ * device.  Incident i = the i-th maximal run of labelled ticks, [a_i, b_i); I of them.  The episodes of setting p are
+ * those of "Alarm episodes" with first_tick = 0 and no cap; episode k spans [start_k, end_k), end_k = T while it is
+ * open at the last tick, and raise_k = start_k + on - 1 is the tick at which it is first seen.  counts [P, 8] int64:
+ *   0 episodes           episodes raised
+ *   1 true_episodes      episodes whose span holds a labelled tick
+ *   2 incidents_hit      incidents overlapped by at least one span (distinct)
+ *   3 delay_sum          sum over the hit incidents of max(0, raise_k(i) - a_i), k(i) = the first episode that overlaps i
+ *   4 delay_max          the largest of those delays (0: none hit)
+ *   5 alarm_ticks        sum of end_k - start_k
+ *   6 alarm_label_ticks  labelled ticks inside spans
+ *   7 open               1: the last episode is open at T
+ * A row with lo > hi, a NaN level, or on / off outside 1 .. 4096 gets -1 in all eight (decided on the device: no host
+ * read).  ONE launch: a lane is a setting, a workgroup one wave that walks the ticks in order (ceil(P / 64)
+ * workgroups), no atomics, no workspace; integer counts and comparisons only, so the result is exact.  The time is set
+ * by T; below 64 * (number of CUs) settings part of the device idles.
+ * 1 <= T <= 2^26, 1 <= P <= 2^20: else GDN_ERR_UNSUPPORTED; a null pointer: GDN_ERR_ARG; decided before the launch.   */
+int gdn_alarm_sweep(const double* scores, const uint8_t* labels, long long T, const double* hi, const double* lo,
+                    const int32_t* on, const int32_t* off, long long P, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
