@@ -50,6 +50,57 @@ def capture(graph, pool=None):
         if was_enabled:
             gc.enable()
 
+
+class _Replay:
+    """One launch sequence, captured once in a HIP graph and replayed from then on: the ONE copy of that rule.
+
+    `launch(*args())` issues it with static arguments only; `args` is asked once per capture, outside it, for the eager
+    run and the captured one alike.  `key()` names what the captured pointers depend on (`model._constants().key`:
+    asking builds the constants outside the capture); every holder remembers its own.  `on_stale()` runs when the key
+    CHANGED since the last capture, never at the first.  `graph`: the `CUDAGraph`, None while nothing is captured.
+
+    A call without `use_graph` (and with nothing captured) launches eagerly and touches no `torch.cuda`.  A live graph
+    under a fresh key is replayed.  Otherwise the old graph is released FIRST (outside any capture; the holder has the
+    only reference), the sequence is launched eagerly AND THAT LAUNCH IS THE RUN (a detector's state may move only
+    once; it is also the warm-up: occupancy queries, lazy buffers), then synchronize and capture the same call, which
+    executes nothing.  A call returns what `launch` returned: a replay, the value recorded at the capture."""
+
+    def __init__(self, launch, use_graph: bool = True, key=lambda: None, on_stale=None, args=tuple):
+        self.launch, self.use_graph, self.key, self.on_stale, self.args = launch, bool(use_graph), key, on_stale, args
+        self.graph = self._key = self._value = None
+
+    def drop(self):
+        """Release the graph (outside any capture); the next call captures again."""
+        self.graph = self._value = None
+
+    def capture(self, args=None):
+        """Capture now, with no eager run: for a caller whose eager run has happened and who knows that nothing else (a
+        collective above all) is in flight.  Calls replay from here on, whatever `use_graph` says."""
+        self.drop()
+        args = self.args() if args is None else args
+        graph = torch.cuda.CUDAGraph()
+        with capture(graph):
+            self._value = self.launch(*args)
+        self.graph = graph
+
+    def __call__(self):
+        if self.graph is None and not self.use_graph:
+            return self.launch(*self.args())
+        key = self.key()
+        if self.graph is not None and key == self._key:
+            self.graph.replay()
+            return self._value
+        self.drop()
+        if self.on_stale is not None and self._key not in (None, key):
+            self.on_stale()
+        self._key = key
+        args = self.args()
+        value = self.launch(*args)
+        torch.cuda.synchronize()
+        self.capture(args)
+        return value
+
+
 def test(model, dataloader, device=None, as_tensors: bool = False):
     """Mirror of the reference test() (test.py:21-79).  Returns (avg_loss, [predictions, ground
     truth, labels]) with the three results as python lists, exactly like the reference; per-batch
@@ -336,7 +387,7 @@ class ShardedEvaluator:
     def __init__(self, model, x_local, y_local: torch.Tensor, total_ticks: int, chunk: int = 4096,
                  backend=HipScoreBackend, forward=None, group=None, use_graph: bool = False):
         self.rank, self.size = world()
-        self.use_graph, self._graphs, self._warm, self._result = bool(use_graph), None, False, None
+        self.use_graph, self._warm = bool(use_graph), False
         self.group, self.backend, self.model = group, backend, model
         self.x, self.y, self.total = x_local, y_local, total_ticks
         self.t, self.n = y_local.shape
@@ -393,6 +444,12 @@ class ShardedEvaluator:
         self._med_iqr = torch.empty((n, 2), dtype=torch.float64, device=dev)
         self._halo64 = torch.empty((2, 3, n), dtype=torch.float64, device=dev)
         self._halo = torch.empty((2, 3, n), dtype=torch.float32, device=dev)
+        # the compute segments of a step (below): eager until _capture_segments() has captured them
+        self._segs = [_Replay(self._seg_forward, False, args=lambda c=c: (c,)) for c in range(self.nchunks)]
+        self._segs += [_Replay(self._seg_select, False), _Replay(self._seg_finish, False)]
+
+    _graphs = property(lambda self: [seg.graph for seg in self._segs] if self._segs[0].graph is not None else None,
+                       doc="the segments' graphs; None unless they are captured")
 
     def _hip_forward(self, start, stop):
         if self._wide is None:      # range of the resident shard, looked at once
@@ -441,46 +498,30 @@ class ShardedEvaluator:
         False (and stays eager) when anything about the capture fails."""
         try:
             torch.cuda.synchronize()
-            graphs = []
-            for fn, args in [(self._seg_forward, (c,)) for c in range(self.nchunks)] + [(self._seg_select, ()),
-                                                                                         (self._seg_finish, ())]:
-                g = torch.cuda.CUDAGraph()
-                with capture(g):
-                    out = fn(*args)
-                graphs.append(g)
-            self._graphs, self._result = graphs, out
+            for seg in self._segs:
+                seg.capture()
             return True
         except Exception as exc:     # noqa: BLE001 — a capture that fails must not take the evaluator down with it
             warnings.warn(f"ShardedEvaluator: HIP-graph capture of the compute segments failed ({exc!r}); running eagerly")
-            self._graphs = None
+            for seg in self._segs:
+                seg.drop()
             torch.cuda.synchronize()
             return False
 
     def step(self):
-        graphs = self._graphs
-        if self.use_graph and graphs is None and self._warm:
-            self.use_graph = self._capture_segments()
-            graphs = self._graphs
+        if self.use_graph and self._graphs is None and self._warm:      # at the start of the second step: no
+            self.use_graph = self._capture_segments()                   # collective is in flight here
         works = []
         for c in range(self.nchunks):
-            if graphs is not None:
-                graphs[c].replay()
-            else:
-                self._seg_forward(c)
+            self._segs[c]()
             works.append(dist.all_to_all_single(self.recv[c].reshape(-1), self.send[c].reshape(-1),
                                                 self.out_sizes, self.in_sizes, group=self.group, async_op=True))
         for w in works:
             w.wait()
-        if graphs is not None:
-            graphs[self.nchunks].replay()
-        else:
-            self._seg_select()
+        self._segs[self.nchunks]()
         dist.all_gather_into_tensor(self.gathered, self.pub, group=self.group)
         self._warm = True
-        if graphs is not None:
-            graphs[self.nchunks + 1].replay()
-            return self._result
-        return self._seg_finish()
+        return self._segs[self.nchunks + 1]()
 
 
 # --------------------------------------------------------------------------- resident-series evaluator
@@ -490,6 +531,24 @@ def too_few_readings(counts, min_kept: int, t: int) -> str:
     short = torch.nonzero(counts < min_kept).flatten()[:8].tolist()
     return (f"min_kept = {min_kept}: sensors {short} have only {[int(counts[i]) for i in short]} real readings among "
             f"the {t} scored ticks; too few for their median / IQR rows")
+
+
+# the checks and the read that SeriesEvaluator and StreamDetector (status_gaps: SeriesTrainer too) have in common
+def _check_calib(calib):
+    if calib not in ("tick", "sensor"):
+        raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
+
+
+def _check_top_m(top_m, n: int):
+    if not 1 <= int(top_m) <= min(8, n):
+        raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {n}")
+
+
+def _status_gaps(counters, with_gaps: bool, who: str):
+    if not with_gaps:
+        raise ValueError(f"status_gaps(): the {who} was built with gaps=False and counts no missing readings")
+    both = counters.cpu()
+    return both[0], both[1]
 
 
 class SeriesEvaluator:
@@ -524,8 +583,7 @@ class SeriesEvaluator:
         the device, `kept` is the smallest of them (read with the head check: still ONE host read) and a sensor with
         fewer than `min_kept` real readings is refused.  A step is forward -> gdn_score_keys_valid ->
         gdn_score_select_counts -> the `_gaps` smooth launch.  `calib="tick"` (the default) is the path above."""
-        if calib not in ("tick", "sensor"):
-            raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
+        _check_calib(calib)
         if calib == "sensor" and not gaps:
             raise ValueError("calib='sensor' calibrates around missing readings: it needs gaps=True")
         self.with_gaps = bool(gaps)
@@ -561,14 +619,16 @@ class SeriesEvaluator:
         if self.top_m:
             if want_scores:
                 raise ValueError("top_m replaces the [N, T] score table: ask for one of want_scores and top_m")
-            if not 1 <= self.top_m <= min(8, self.n):
-                raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {self.n}")
+            _check_top_m(top_m, self.n)
             self.top_scores = torch.empty((self.t, self.top_m), dtype=torch.float64, device=dev)
             self.top_sensors = torch.empty((self.t, self.top_m), dtype=torch.int32, device=dev)
             self.anomaly = self.top_scores[:, 0]
-        self.graph = None
-        self.fgraph = None
         self.use_graph = use_graph
+        def look_again():                   # a parameter changed under a captured graph: the x limit follows it
+            self.wide = model.wide_for(self.src)
+        # captured graphs bake in the pointers of the model's folded constants: that is their key
+        self._step, self._forward = (_Replay(fn, use_graph, lambda: model._constants().key, look_again)
+                                     for fn in (self._launch_all, self._launch_forward))
         # GDN_FUSE_KEYS=1: the forward's epilogue writes the scoring keys itself (gdn_forward_fused_plan_keys) and
         # the gdn_score_keys launch disappears.  Measured SLOWER and therefore off by default: the 127 scattered
         # 8-byte stores per window (row pitch 256 KB) cost the forward ~40 us per 32768 windows, the transposing
@@ -647,10 +707,7 @@ class SeriesEvaluator:
         """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: every sensor's missing readings
         among the scored ticks and the run of them that ends at the last tick (StreamDetector.status_gaps' counters
         after the same ticks).  ONE read (a synchronisation)."""
-        if not self.with_gaps:
-            raise ValueError("status_gaps(): the evaluator was built with gaps=False and counts no missing readings")
-        both = self._gap_counters.cpu()
-        return both[0], both[1]
+        return _status_gaps(self._gap_counters, self.with_gaps, "evaluator")
 
     def _launch_forward(self, with_keys: bool = False):
         m = self.model
@@ -722,44 +779,16 @@ class SeriesEvaluator:
         self._launch_forward(with_keys=fuse)
         self._launch_score(have_keys=fuse)
 
-    def _fresh(self):
-        """Captured graphs bake in the pointers of the model's folded constants: drop them when a
-        parameter changed since the capture."""
-        key = self.model._constants().key
-        if key != getattr(self, "_graph_key", None):
-            self.graph = self.fgraph = None
-            if getattr(self, "_graph_key", None) is not None:      # the x limit follows the parameters: look again
-                self.wide = self.model.wide_for(self.src)
-            self._graph_key = key
-
-    def _capture(self, fn):
-        self.model._constants()                      # build graph/constants outside the capture
-        fn()                                         # warm-up (occupancy queries, attributes)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with capture(g):
-            fn()
-        return g
+    graph = property(lambda self: self._step.graph, doc="the captured step, None before its first graphed call")
+    fgraph = property(lambda self: self._forward.graph, doc="... of forward_only()")
 
     def forward_only(self):
         """Forward launches only (multi-GPU: scoring then goes through distributed_anomaly)."""
-        if not self.use_graph:
-            self._launch_forward()
-            return self.pred
-        self._fresh()
-        if self.fgraph is None:
-            self.fgraph = self._capture(self._launch_forward)
-        self.fgraph.replay()
+        self._forward()
         return self.pred
 
     def step(self):
-        if not self.use_graph:
-            self._launch_all()
-            return self.anomaly
-        self._fresh()
-        if self.graph is None:
-            self.graph = self._capture(self._launch_all)
-        self.graph.replay()
+        self._step()
         return self.anomaly
 
 
@@ -1771,10 +1800,7 @@ class SeriesTrainer:
     def status_gaps(self):
         """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: every sensor's missing readings
         among ticks w .. T - 1 of the series and the run of them that ends at the last tick.  ONE read."""
-        if not self.gaps:
-            raise ValueError("status_gaps(): the trainer was built with gaps=False and counts no missing readings")
-        both = self._gap_counters.cpu()
-        return both[0], both[1]
+        return _status_gaps(self._gap_counters, self.gaps, "trainer")
 
     def _masked_tail_step(self, x, y, valid, row_valid):
         """The ragged last batch under gaps=True: `_eager_step` with the masked launch in F.mse_loss's place — autograd
@@ -2223,8 +2249,7 @@ class StreamDetector:
         """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — the state is
         gdn_stream_state_bytes(n, w) of zeros, the table zeros, the threshold inf, all on `device`, `wide` the
         caller's word — and load_state_dict fills the allocations."""
-        if calib not in ("tick", "sensor"):
-            raise ValueError(f"calib = {calib!r}: 'tick' (complete ticks) or 'sensor' (each sensor's own readings)")
+        _check_calib(calib)
         if calib == "sensor" and not (gaps and int(recal) > 0):
             raise ValueError("calib='sensor' recalibrates every sensor on its own real readings: it needs gaps=True and "
                              "a calibration ring (recal=R)")
@@ -2238,8 +2263,7 @@ class StreamDetector:
         if self.chunk * n * w * 4 > _VALIDATE_CHUNK_BYTES:
             raise ValueError(f"chunk = {chunk}: the window buffer [{chunk}, {n}, {w}] fp32 exceeds "
                              f"{_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
-        if not 1 <= self.top_m <= min(8, n):
-            raise ValueError(f"top_m = {top_m}: the score launch keeps 1 to 8 sensors per tick, at most all {n}")
+        _check_top_m(top_m, n)
         if int(log) < 0:
             raise ValueError(f"log = {log}: the alarm log holds 0 or more entries")
         self.events_cfg = None if events is None else events_config(events, self.top_m)     # host facts only
@@ -2320,8 +2344,10 @@ class StreamDetector:
         self.recals = 0                     # tables written by recalibrate()
         self.recal_kept = 0                 # ... and the kept ticks behind the last one
         self._handed = 0                    # ticks handed to push(): recal_every's clock
-        self.graph = None
-        self._graph_key = None
+        # the full push (its key: the graph bakes in the folded constants' pointers); `_guarded()` is asked once a capture
+        self._full = _Replay(lambda *a: self._launch(*a), use_graph, lambda: model._constants().key,    # (looked up late)
+                             args=lambda: (self.chunk, self._guarded()))
+        self._prep_full = {}                # prep=: raw dtype -> the full raw push, the front end reading `_raw_stage`'s
         self._last = 0                      # ticks of the last (sub-)push: what the static buffers hold
         self.calib_kept = None              # from_calibration(calib_gaps=True): the complete ticks behind the table
         self.calib_counts = None            # ... calib="sensor": every sensor's real readings behind it (device int32)
@@ -2336,7 +2362,6 @@ class StreamDetector:
             self._pend = [torch.zeros((rows, n), dtype=torch.float64, device=dev) for _ in range(2)]
             self._pend_at = 0
             self._raw_stage = {}            # raw dtype -> the static staging buffer [chunk * down, n] of its pushes
-            self._prep_graphs = {}          # ... -> the graph captured with the front end reading that buffer
 
     @classmethod
     def from_calibration(cls, model, series, chunk: int, batch: int = 8192, calib_gaps: bool = False,
@@ -2431,31 +2456,18 @@ class StreamDetector:
                            self.top_m, self.log_ticks, self.log_sensors, count=count, valid=self.valid,
                            gap_chunk=self.gap_chunk, gaps=self.gaps)
 
-    def _fresh(self):
-        """A captured graph bakes in the pointers of the model's folded constants: drop it when a parameter changed."""
-        key = self.model._constants().key
-        if key != self._graph_key:
-            self.graph = None
-            self._graph_key = key
+    graph = property(lambda self: self._full.graph, doc="the captured full push, None before the first one")
+    _prep_graphs = property(lambda self: {dt: full.graph for dt, full in self._prep_full.items() if full.graph is not None},
+                            doc="raw dtype -> the graph captured with the front end reading that dtype's staging buffer")
 
     def _push(self, ticks):
         r = ticks.shape[0]
         (self.raw_buf if self.with_gaps else self.chunk_buf)[:r].copy_(ticks)
         self._last = r
-        if r != self.chunk or not self.use_graph:
-            return self._launch(r, self._guarded())
-        self._fresh()
-        if self.graph is not None:
-            return self.graph.replay()
-        # the first full push (or the first after a parameter change) goes out eagerly and is the warm-up of the
-        # capture (occupancy queries, the staged route's buffers, the range guard); a capture launches nothing, so the
-        # state moves once
-        guard = self._guarded()
-        self._launch(r, guard)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with capture(self.graph):
-            self._launch(r, guard)
+        if r == self.chunk:
+            self._full()
+        else:
+            self._launch(r, self._guarded())
 
     def _launch_prep(self, stage, rows: int, groups: int, guard: bool):
         """gdn_prep_ticks over stage[:rows] and the pending plane, then the launches of a push of `groups` ticks."""
@@ -2470,28 +2482,24 @@ class StreamDetector:
         if stage is None:
             stage = self._raw_stage[ticks.dtype] = torch.zeros((self.chunk * self.prep.down, self.n), dtype=ticks.dtype,
                                                                device=self.state.device)
+            # (a replayable sub-push opens and leaves no group: the graph neither reads nor writes a pending plane)
+            self._prep_full[ticks.dtype] = _Replay(
+                self._launch_prep, self.use_graph, self._full.key,
+                args=lambda: (stage, self.chunk * self.prep.down, self.chunk, self._guarded()))
         stage[:rows].copy_(ticks)
         self._last = groups
-        if not (replayable and self.use_graph):
-            self._launch_prep(stage, rows, groups, self._guarded() if groups else False)
+        if replayable:
+            self._prep_full[ticks.dtype]()
         else:
-            # (a replayable sub-push opens and leaves no group: the graph neither reads nor writes a pending plane)
-            key = self.model._constants().key
-            if key != self._graph_key:      # (_fresh's rule: a parameter changed, the captured pointers are stale)
-                self._prep_graphs.clear()
-                self._graph_key = key
-            graph = self._prep_graphs.get(ticks.dtype)
-            if graph is not None:
-                graph.replay()
-            else:
-                guard = self._guarded()
-                self._launch_prep(stage, rows, groups, guard)           # the warm-up: the state moves once
-                torch.cuda.synchronize()
-                graph = self._prep_graphs[ticks.dtype] = torch.cuda.CUDAGraph()
-                with capture(graph):
-                    self._launch_prep(stage, rows, groups, guard)
+            self._launch_prep(stage, rows, groups, self._guarded() if groups else False)
         self._pend_at ^= 1
         self.raw_pending = left
+
+    def _hand(self, ticks: int):
+        """recal_every's clock: `ticks` more model ticks were handed over; recalibrate when they cross a multiple of it."""
+        before, self._handed = self._handed, self._handed + ticks
+        if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
+            self.recalibrate()
 
     def _push_prep(self, ticks):
         if ticks.dtype not in (torch.float32, torch.float64):
@@ -2502,9 +2510,7 @@ class StreamDetector:
         for rows, groups, left, replayable in raw_push_plan(self.raw_pending, ticks.shape[0], self.prep.down, self.chunk):
             self._push_raw(ticks[at:at + rows], groups, left, replayable)
             at += rows
-            before, self._handed = self._handed, self._handed + groups
-            if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
-                self.recalibrate()
+            self._hand(groups)
         r = self._last
         return self.top_scores[:r], self.top_sensors[:r], self.alarm[:r]
 
@@ -2524,9 +2530,7 @@ class StreamDetector:
             raise ValueError("a push needs at least one tick")
         for s in range(0, ticks.shape[0], self.chunk):
             self._push(ticks[s:s + self.chunk])
-            before, self._handed = self._handed, self._handed + self._last
-            if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
-                self.recalibrate()
+            self._hand(self._last)
         r = self._last
         return self.top_scores[:r], self.top_sensors[:r], self.alarm[:r]
 
@@ -2582,10 +2586,7 @@ class StreamDetector:
         """(missing_total [n] int64, missing_run [n] int64) on the host, gaps=True only: the missing readings of every
         sensor since the stream began, and the run of missing readings that ends at the last scored tick (0 after a
         real reading; >= w: the sensor's whole window is held values).  ONE read (a synchronisation)."""
-        if not self.with_gaps:
-            raise ValueError("status_gaps(): the detector was built with gaps=False and counts no missing readings")
-        both = self.gaps.cpu()
-        return both[0], both[1]
+        return _status_gaps(self.gaps, self.with_gaps, "detector")
 
     def episodes(self) -> Episodes:
         """The stream's episode table (events= only): views of the events allocation, so a later push
@@ -2683,10 +2684,8 @@ class StreamDetector:
         for k, mine in self._config().items():
             if cfg[k] != mine:
                 raise ValueError(f"stream checkpoint: {k} = {cfg[k]!r}, this detector was built with {k} = {mine!r}")
-        self.graph = None                                   # (outside any capture: ADVICE, third finding)
-        self._graph_key = None
-        if self.prep is not None:
-            self._prep_graphs.clear()
+        for full in (self._full, *self._prep_full.values()):
+            full.drop()
 
         def host(key):
             return torch.from_numpy(np.array(sd[key]))      # (a copy: numpy.load may hand out read-only arrays)

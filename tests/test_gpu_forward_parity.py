@@ -467,6 +467,7 @@ def test_range_guard_inside_a_user_captured_graph(gpu_device):
     """A caller that captures `model(x)` in a HIP graph of their own (static input buffer) gets the guarded pair of
     launches captured with it: replays on in-range and on raw-unit contents of the buffer both equal float64 — the
     flag is raised and consumed on the device, nothing was decided at capture time."""
+    from gdn_amd import harness
     n, w, k, d, b = 127, 15, 30, 64, 16
     model = random_params(n, w, k, d, seed=41)
     p = {key: v.detach().clone() for key, v in model.state_dict().items()}
@@ -478,7 +479,7 @@ def test_range_guard_inside_a_user_captured_graph(gpu_device):
         model._plan(model._constants(), False)           # constants and plan exist before the capture
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with harness.capture(graph):                     # (what INTEGRATION.md tells such a caller to use)
             static_out = model(static_x, None)
     graph_nbr = model.learned_graph.cpu()
     for scale in (1.0, 2.0e5, 1.0, 7.0e6):

@@ -309,6 +309,37 @@ def test_detector_graph_replay_of_aligned_raw_pushes_equals_eager(gpu_device):
     _assert_same_detector(det, plain, n, w)
 
 
+def test_a_parameter_change_drops_the_graph_of_the_raw_push(gpu_device):
+    """tests/test_gpu_stream.py's test of the same name on a prep= detector pushed whole groups of float64 raw ticks:
+    the graph held under that dtype is captured again, and the detector goes on bit for bit like a fresh one that was
+    put at the same point of the stream."""
+    dev = gpu_device
+    n, w = TINY[:2]
+    model = _model(dev, *TINY)
+    prep, hist, raw, prepared = _stream_case(dev)
+    s = torch.cat([hist, prepared.t()], dim=1).cpu()
+    det = _detector(model, s, w, 4, dev, prep=prep, top_m=3)
+    det.push(raw[:40])
+    det.push(raw[40:80])
+    before = det._prep_graphs[torch.float64]
+    assert list(det._prep_graphs) == [torch.float64] and det.graph is None and det.raw_pending == 0
+    with torch.no_grad():
+        model.out_layer.mlp[0].bias.data.add_(0.5)
+        model.embedding.weight.data[3].mul_(1.5)
+    model.invalidate_constants()
+    fresh = _detector(model, s, w, 4, dev, prep=prep, top_m=3)
+    fresh.state.copy_(det.state)                                     # the same point of the same stream
+    for t0 in (80, 120):                                             # the re-capturing push, then a replay
+        a, b = det.push(raw[t0:t0 + 40]), fresh.push(raw[t0:t0 + 40])
+        assert all(torch.equal(u, v) for u, v in zip(a, b)) and torch.equal(det.pred, fresh.pred)
+        assert torch.equal(det.state, fresh.state)
+    assert list(det._prep_graphs) == [torch.float64] and det._prep_graphs[torch.float64] is not before
+    _assert_same_detector(det, fresh, n, w)
+    out = torch.empty((4, n), device=dev)
+    model.forward_into(det.x, out, wide=det.wide)
+    assert torch.equal(det.pred, out)
+
+
 def test_detector_with_gaps_takes_a_missing_raw_group_as_a_missing_reading(gpu_device):
     dev = gpu_device
     n, w = TINY[:2]

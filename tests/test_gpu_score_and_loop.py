@@ -95,6 +95,49 @@ def test_series_evaluator_equals_per_batch_loop(use_graph, gpu_device):
     assert torch.equal(anomaly, a1)
 
 
+def test_the_first_graphed_call_is_the_run_and_a_parameter_change_captures_both_graphs_again(gpu_device):
+    """harness._Replay under SeriesEvaluator: the first graphed step() / forward_only() is the eager launch that warms
+    the capture up (nothing is replayed in that call), the second is a replay that recomputes, and after a parameter
+    change both holders capture again — every result torch.equal to an eager evaluator's.  37 ticks in launches of 16
+    (ragged last launch, three side streams inside the capture)."""
+    from gdn_amd import harness
+    from test_gpu_forward_parity import random_params
+    model = random_params(127, 15, 30, 64, seed=5).to(gpu_device).eval()
+    g = torch.Generator().manual_seed(2)
+    t = 37
+    x = torch.rand((t, 127, 15), generator=g).to(gpu_device)
+    y = torch.rand((t, 127), generator=g).to(gpu_device)
+
+    def eager():
+        ev = harness.SeriesEvaluator(model, x, y, batch=16, use_graph=False)
+        return ev.step().clone(), ev.pred.clone()
+    want_anomaly, want_pred = eager()
+    ev = harness.SeriesEvaluator(model, x, y, batch=16, use_graph=True)
+    assert ev.graph is None and ev.fgraph is None
+    for call in ("first", "replay"):
+        ev.pred.zero_()
+        ev.anomaly.zero_()
+        assert torch.equal(ev.step(), want_anomaly) and torch.equal(ev.pred, want_pred), call
+    for call in ("first", "replay"):
+        ev.pred.zero_()
+        assert torch.equal(ev.forward_only(), want_pred), call
+    graph, fgraph = ev.graph, ev.fgraph
+    assert graph is not None and fgraph is not None and graph is not fgraph
+    with torch.no_grad():
+        model.out_layer.mlp[0].bias.data.add_(0.5)
+        model.embedding.weight.data[3].mul_(1.5)
+    model.invalidate_constants()
+    new_anomaly, new_pred = eager()                      # a freshly built evaluator
+    assert not torch.equal(new_pred, want_pred)
+    for call in ("first", "replay"):
+        ev.pred.zero_()
+        ev.anomaly.zero_()
+        assert torch.equal(ev.step(), new_anomaly) and torch.equal(ev.pred, new_pred), call
+        ev.pred.zero_()
+        assert torch.equal(ev.forward_only(), new_pred), call
+    assert ev.graph is not None and ev.graph is not graph and ev.fgraph is not None and ev.fgraph is not fgraph
+
+
 @pytest.mark.parametrize("t,n,cuts", [(1000, 27, (333, 700)), (40, 5, (1, 2, 3, 5, 38)), (4100, 130, (2049,))])
 def test_sharded_smoothing_with_halo_equals_whole_series(t, n, cuts, gpu_device):
     """The per-rank half of harness.distributed_anomaly on the GPU (first_tick > 0, 3-row halo that can

@@ -24,7 +24,7 @@ for coalesce, streams in ((8, 4), (64, 1)):
     f = timed(ev.forward_only); s = timed(ev.step)
     g = torch.cuda.CUDAGraph()
     ev._launch_score(); torch.cuda.synchronize()
-    with torch.cuda.graph(g):
+    with harness.capture(g):
         ev._launch_score()
     sc = timed(g.replay)
     print(f"coalesce {coalesce} streams {streams}: forward graph {f:.3f} ms, forward+score graph {s:.3f} ms, score-only graph {sc:.3f} ms")
