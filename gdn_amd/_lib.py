@@ -140,6 +140,11 @@ SIGNATURES = {
     "gdn_stream_events_bytes": [_c_int, ctypes.c_longlong],
     "gdn_stream_events": [_p] * 5 + [_c_int] * 5 + [ctypes.c_longlong, _p, _p],
     "gdn_alarm_sweep": [_p, _p, ctypes.c_longlong, _p, _p, _p, _p, ctypes.c_longlong, _p, _p],
+    "gdn_fleet_state_bytes": [_c_int] * 3,
+    "gdn_fleet_init": [_p, _p, ctypes.c_longlong, _c_int, _c_int, _c_int, _p],
+    "gdn_fleet_windows": [_p] * 3 + [_c_int] * 4 + [_p, _p],
+    "gdn_fleet_score": [_p] * 6 + [_c_int] * 5 + [_p] * 4,
+    "gdn_fleet_advance": [_p] * 7 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p],
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

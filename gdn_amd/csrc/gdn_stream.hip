@@ -10,71 +10,27 @@
 // Rolling calibration (opt-in, include/gdn_hip.h "Rolling calibration"): gdn_stream_calib_write sits between the score
 // and the advance launch and keeps |pred - gt| of the last R stream ticks in a ring that gdn_score_select reads as it
 // stands; it reads the state and writes the ring only.
-#include "gdn_score_sweep.hpp"
+#include "gdn_stream_steps.hpp"
 
 // (float64 scoring: gdn_score_sweep.hpp switches FMA contraction off for this unit)
+// The window cut, the score of a run, the hist roll and the carry / log / counters are the __device__ steps of
+// gdn_stream_steps.hpp, which the fleet kernels (gdn_fleet.hip) call too; the kernels here keep their launch shapes.
 
 namespace {
 
-using namespace gdn_sweep;
-
-#define GDN_STREAM_HEADER 4          // int64 words ahead of the carry: ticks, alarms, logged, (reserved)
-#define GDN_STREAM_THREADS 256
-#define GDN_STREAM_PER_THREAD 4      // flat elements per thread, GDN_STREAM_THREADS apart (gdn_windows_gather's shape)
-#define GDN_STREAM_SPAN (GDN_STREAM_THREADS * GDN_STREAM_PER_THREAD)
-
-__host__ __device__ inline const double* stream_carry(const void* state) {
-  return reinterpret_cast<const double*>(state) + GDN_STREAM_HEADER;
-}
-__host__ __device__ inline double* stream_carry(void* state) {
-  return reinterpret_cast<double*>(state) + GDN_STREAM_HEADER;
-}
-__host__ __device__ inline const float* stream_hist(const void* state, int n) {
-  return reinterpret_cast<const float*>(stream_carry(state) + 3 * (size_t)n);
-}
-__host__ __device__ inline float* stream_hist(void* state, int n) {
-  return reinterpret_cast<float*>(stream_carry(state) + 3 * (size_t)n);
-}
+using namespace gdn_stream_steps;
 
 // hist = the last w columns of history[n, h]; counters and carry zero.  Lanes along the flat [i, w] index.
 __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_init_kernel(
     void* __restrict__ state, const float* __restrict__ history, long long h, int n, int w) {
-  const unsigned nw = (unsigned)n * (unsigned)w;
-  const unsigned f0 = blockIdx.x * GDN_STREAM_SPAN + threadIdx.x;
-  float* __restrict__ hist = stream_hist(state, n);
-#pragma unroll
-  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
-    const unsigned f = f0 + j * GDN_STREAM_THREADS;
-    if (f >= nw) break;
-    const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
-    hist[f] = history[(long long)i * h + (h - w) + c];
-  }
-  if (blockIdx.x == 0) {
-    long long* __restrict__ head = reinterpret_cast<long long*>(state);
-    double* __restrict__ carry = stream_carry(state);
-    if (threadIdx.x < GDN_STREAM_HEADER) head[threadIdx.x] = 0;
-    for (int f = threadIdx.x; f < 3 * n; f += GDN_STREAM_THREADS) carry[f] = 0.0;
-  }
+  stream_seed_span(state, history, h, n, w, blockIdx.x, threadIdx.x);
 }
 
-// Workgroup (b, span): elements [span * SPAN, (span + 1) * SPAN) of window b's flat [i, c] index: the w values of
-// sensor i before tick b of the chunk.  Position b - w + c of the stream relative to the chunk's first tick: negative
-// = column w + (b - w + c) = b + c of hist, else that row of the (time-major) chunk.
+// Workgroup (b, span): elements [span * SPAN, (span + 1) * SPAN) of window b's flat [i, c] index.
 __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_windows_kernel(
     const void* __restrict__ state, const float* __restrict__ chunk, int n, int w, float* __restrict__ x_out) {
   const int b = blockIdx.x;
-  const unsigned nw = (unsigned)n * (unsigned)w;     // <= 4096 * 1024
-  const float* __restrict__ hist = stream_hist(state, n);
-  float* __restrict__ xb = x_out + (size_t)b * nw;
-  const unsigned f0 = blockIdx.y * GDN_STREAM_SPAN + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
-    const unsigned f = f0 + j * GDN_STREAM_THREADS;
-    if (f >= nw) break;
-    const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
-    const int pos = b - w + (int)c;
-    xb[f] = pos < 0 ? hist[(size_t)i * w + (unsigned)(b + (int)c)] : chunk[(size_t)pos * n + i];
-  }
+  stream_window_span(state, chunk, n, w, b, blockIdx.y, threadIdx.x, x_out + (size_t)b * ((unsigned)n * (unsigned)w));
 }
 
 // Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it
@@ -152,34 +108,7 @@ __global__ __launch_bounds__(GDN_FILL_WAVES * 64) void gdn_stream_fill_kernel(
   }
 }
 
-// Normalise, smooth, top m, flag: the sweep of gdn_score_sweep.hpp with top-m lists, as score_smooth_topm_kernel
-// (gdn_score.hip) runs it, over a push.  Here: the series position of the chunk's first tick is read from the state,
-// and only the run at tick 0 reaches back: its three predecessors are the carry (rows 0, 1, 2 = three, two, one tick
-// before; zeros where the series has no such tick, GAPS: 0.0 for a missing reading, through gdn_stream_advance).
-
-// Rows before the chunk are never used as values (row 0 stands in for the loads); rows past it are clamped.
-struct StreamSource {
-  const float *pred, *gt;
-  const unsigned char* valid;
-  const double* carry;
-  int t, n;
-  __device__ __forceinline__ size_t at(int tt) const { return (size_t)(tt < 0 ? 0 : min(tt, t - 1)) * n; }
-  __device__ __forceinline__ const float* pred_row(int tt) const { return pred + at(tt); }
-  __device__ __forceinline__ const float* gt_row(int tt) const { return gt + at(tt); }
-  __device__ __forceinline__ const unsigned char* valid_row(int tt) const { return valid + at(tt); }
-  template <typename FA, typename FB>
-  __device__ __forceinline__ void before(int t0, const Lanes& l, double (&a)[3], double (&b)[3], FA&& na,
-                                         FB&& nb) const {
-    if (t0 == 0) {                                 // (wave uniform) all six loads in one block: one round trip
-      a[0] = carry[l.ca]; a[1] = carry[(size_t)n + l.ca]; a[2] = carry[2 * (size_t)n + l.ca];
-      b[0] = carry[l.cb]; b[1] = carry[(size_t)n + l.cb]; b[2] = carry[2 * (size_t)n + l.cb];
-    } else {
-      a[0] = na(0); a[1] = na(1); a[2] = na(2);
-      b[0] = nb(0); b[1] = nb(1); b[2] = nb(2);
-    }
-  }
-};
-
+// Normalise, smooth, top m, flag (stream_score_run): a wave per run of RUN ticks, grid-stride over the runs.
 template <bool GAPS>
 __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
     const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ gt,
@@ -192,123 +121,27 @@ __global__ __launch_bounds__(256) void gdn_stream_score_kernel(
   const long long first_tick = reinterpret_cast<const long long*>(state)[0];
   const StreamSource src{pred, gt, valid, stream_carry(state), t, n};
   const double thr = threshold[0];
-  for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb) {
-    const int t0 = run * RUN, t1 = min(t, t0 + RUN);
-    double cs[RUN];                               // the carried list: entry `lane` of every tick of the run
-    int ci[RUN];
-#pragma unroll
-    for (int u = 0; u < RUN; ++u) {
-      cs[u] = -INFINITY;
-      ci[u] = NONE;
-    }
-    for (int s0 = 0; s0 < n; s0 += 128) {
-      const Lanes l(s0, lane, n);
-      score_sweep<GAPS>(src, med_iqr, l, t0, t1, first_tick, [&](int u, int, double sma, double smb) {
-        topm_merge(l, lane, m, sma, smb, cs[u], ci[u]);
-      });
-    }
-    topm_store(cs, ci, lane, m, t0, t1, top_scores, top_sensors);
-    if (lane == 0) {
-#pragma unroll
-      for (int u = 0; u < RUN; ++u)
-        if (t0 + u < t1) alarm[t0 + u] = cs[u] > thr ? 1 : 0;      // strict; a NaN score compares false
-    }
-  }
+  for (int run = blockIdx.x * wpb + wv; run < nruns; run += gridDim.x * wpb)
+    stream_score_run<GAPS>(src, med_iqr, thr, first_tick, run, lane, m, top_scores, top_sensors, alarm);
 }
 
-// The one launch that writes the state.  Workgroup i < n rolls row i of hist: every thread loads its (up to 4)
-// columns of the NEW row — from the old row where the column survives, else from the chunk — then a barrier, then the
-// stores: no column is read after it has been overwritten, whatever count is.  Workgroup n: the carry (one thread per
-// sensor: its three old entries are read before any is written), the alarm log (an ordered compaction: ballot and
-// popcount inside a wave, four wave totals through LDS, 256 flags a round in tick order) and, last, the counters.
+// The one launch that writes the state.  Workgroup i < n rolls row i of hist (stream_roll_row); workgroup n: the
+// carry, the alarm log and, last, the counters (stream_carry_log).
 // GAPS: `chunk` is the filled chunk; a carry entry taken from the chunk is 0.0 where valid says the reading was
-// missing, and the carry thread of sensor s folds the push's gap_chunk [2, n] into gaps [2, n] (missing_total,
-// missing_run): this launch is the only writer of both.  Without GAPS the three trailing parameters are not read.
+// missing, and the push's gap_chunk [2, n] is folded into gaps [2, n] (missing_total, missing_run): this launch is the
+// only writer of both.  Without GAPS the three trailing parameters are not read.
 template <bool GAPS>
 __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
     void* __restrict__ state, const float* __restrict__ chunk, const float* __restrict__ pred,
     const double* __restrict__ med_iqr, const int* __restrict__ alarm, const int* __restrict__ top_sensors, int count,
     int n, int w, int m, long long* __restrict__ log_ticks, int* __restrict__ log_sensors, long long log_len,
     const unsigned char* __restrict__ valid, const int* __restrict__ gap_chunk, long long* __restrict__ gaps) {
-  const int tid = threadIdx.x;
   if ((int)blockIdx.x < n) {
-    const int i = blockIdx.x;
-    float* __restrict__ row = stream_hist(state, n) + (size_t)i * w;
-    float v[GDN_STREAM_PER_THREAD];
-#pragma unroll
-    for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
-      const int c = tid + j * GDN_STREAM_THREADS;             // w <= 1024 = PER_THREAD * THREADS
-      v[j] = 0.f;
-      if (c < w) {
-        const long long src = (long long)c + count;           // column of [hist | chunk^T]
-        v[j] = src < w ? row[src] : chunk[(size_t)(src - w) * n + i];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
-      const int c = tid + j * GDN_STREAM_THREADS;
-      if (c < w) row[c] = v[j];
-    }
+    stream_roll_row(state, chunk, count, n, w, blockIdx.x, threadIdx.x);
     return;
   }
-  __shared__ int wave_total[GDN_STREAM_THREADS / 64];
-  long long* __restrict__ head = reinterpret_cast<long long*>(state);
-  double* __restrict__ carry = stream_carry(state);
-  // carry: the last three of [carry0, carry1, carry2, a(chunk row 0), .., a(chunk row count - 1)]
-  for (int s = tid; s < n; s += GDN_STREAM_THREADS) {
-    const Scale sc = sensor_scale(med_iqr, s);
-    double next[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int q = count + j;                                 // position in the 3 + count values above
-      if (q < 3) {
-        next[j] = carry[(size_t)q * n + s];
-      } else {
-        const size_t at = (size_t)(q - 3) * n + s;
-        unsigned ok = 0u;
-        if constexpr (GAPS) ok = valid[at] ? 1u : 0u;
-        next[j] = norm<GAPS>(pred[at], chunk[at], sc.med, sc.inv_den, ok, 0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) carry[(size_t)j * n + s] = next[j];
-    if constexpr (GAPS) {
-      const int trail = gap_chunk[n + s];
-      gaps[s] += gap_chunk[s];
-      gaps[(size_t)n + s] = trail == count ? gaps[(size_t)n + s] + count : trail;
-    }
-  }
-  // alarm log
-  const long long ticks = head[0], logged = head[2];
-  const int lane = tid & 63, wv = tid >> 6;
-  long long raised = 0;                                        // flags in the rounds before this one
-  for (int base = 0; base < count; base += GDN_STREAM_THREADS) {
-    const int b = base + tid;
-    const bool flag = b < count && alarm[b] != 0;
-    const unsigned long long mask = __ballot(flag);
-    if (lane == 0) wave_total[wv] = __popcll(mask);
-    __syncthreads();
-    int before = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-    for (int v = 0; v < GDN_STREAM_THREADS / 64; ++v) {
-      if (v < wv) before += wave_total[v];
-      total += wave_total[v];
-    }
-    __syncthreads();                                           // wave_total is rewritten next round
-    const long long slot = logged + raised + before;
-    if (flag && slot < log_len) {
-      log_ticks[slot] = ticks + b;
-      for (int r = 0; r < m; ++r) log_sensors[slot * m + r] = top_sensors[(size_t)b * m + r];
-    }
-    raised += total;
-  }
-  if (tid == 0) {
-    head[0] = ticks + count;
-    head[1] += raised;
-    const long long want = logged + raised, room = log_len > logged ? log_len : logged;
-    head[2] = want < room ? want : room;                       // a full log drops entries; `alarms` keeps counting
-  }
+  stream_carry_log<GAPS>(state, chunk, pred, med_iqr, alarm, top_sensors, count, n, m, log_ticks, log_sensors, log_len,
+                         threadIdx.x, valid, gap_chunk, gaps);
 }
 
 // The calibration ring (include/gdn_hip.h "Rolling calibration"): row b < count of the push is stream tick
@@ -422,8 +255,6 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_sen
   }
 }
 
-bool stream_shape_ok(int n, int w) { return w >= 1 && w <= GDN_LONG_MAX_W && n >= 1 && n <= 4096; }
-
 bool calib_shape_ok(int n, int R) {
   return n >= 1 && n <= 4096 && R >= GDN_CALIB_MIN_R && R <= GDN_CALIB_MAX_R && 8ll * n * R <= (2ll << 30);
 }
@@ -509,8 +340,7 @@ extern "C" int gdn_stream_calib_write_sensor(const void* state, const float* pre
 
 extern "C" long long gdn_stream_state_bytes(int n, int w) {
   if (!stream_shape_ok(n, w)) return 0;
-  const long long bytes = 8ll * GDN_STREAM_HEADER + 8ll * 3 * n + 4ll * n * w;
-  return (bytes + 7) & ~7ll;
+  return stream_state_size(n, w);
 }
 
 extern "C" int gdn_stream_init(void* state, const float* history, long long h, int n, int w, void* stream) {

@@ -1,0 +1,236 @@
+// The steps of a stream push as __device__ functions, ONE source for the single-stream kernels (gdn_stream.hip) and
+// the fleet kernels (gdn_fleet.hip): the layout of a stream state, the seeding of hist, the window cut, the score of a
+// run of ticks with the carried smoothing state, the hist roll, and the carry / ordered log compaction / counters.
+// A kernel decides which state, which rows and which count a workgroup works on and calls the step; a fleet is a
+// stream per unit, so a unit's state block is written bit for bit as the single stream writes it.
+// The float64 scoring arithmetic is gdn_score_sweep.hpp's (no FMA contraction in a unit that includes this header).
+#pragma once
+#include "gdn_score_sweep.hpp"
+
+namespace gdn_stream_steps {
+
+using namespace gdn_sweep;
+
+#define GDN_STREAM_HEADER 4          // int64 words ahead of the carry: ticks, alarms, logged, (reserved)
+#define GDN_STREAM_THREADS 256
+#define GDN_STREAM_PER_THREAD 4      // flat elements per thread, GDN_STREAM_THREADS apart (gdn_windows_gather's shape)
+#define GDN_STREAM_SPAN (GDN_STREAM_THREADS * GDN_STREAM_PER_THREAD)
+
+__host__ __device__ inline bool stream_shape_ok(int n, int w) {
+  return w >= 1 && w <= GDN_LONG_MAX_W && n >= 1 && n <= 4096;
+}
+// bytes of one stream state (header, carry[3, n] float64, hist[n, w] fp32; rounded up to 8): a supported shape only
+__host__ __device__ inline long long stream_state_size(int n, int w) {
+  const long long bytes = 8ll * GDN_STREAM_HEADER + 8ll * 3 * n + 4ll * n * w;
+  return (bytes + 7) & ~7ll;
+}
+
+__host__ __device__ inline const double* stream_carry(const void* state) {
+  return reinterpret_cast<const double*>(state) + GDN_STREAM_HEADER;
+}
+__host__ __device__ inline double* stream_carry(void* state) {
+  return reinterpret_cast<double*>(state) + GDN_STREAM_HEADER;
+}
+__host__ __device__ inline const float* stream_hist(const void* state, int n) {
+  return reinterpret_cast<const float*>(stream_carry(state) + 3 * (size_t)n);
+}
+__host__ __device__ inline float* stream_hist(void* state, int n) {
+  return reinterpret_cast<float*>(stream_carry(state) + 3 * (size_t)n);
+}
+
+// Span `span` of the flat [i, w] index: hist = the last w columns of history[n, h]; span 0 also zeroes the counters
+// and the carry.
+__device__ __forceinline__ void stream_seed_span(void* __restrict__ state, const float* __restrict__ history,
+                                                 long long h, int n, int w, unsigned span, int tid) {
+  const unsigned nw = (unsigned)n * (unsigned)w;
+  const unsigned f0 = span * GDN_STREAM_SPAN + tid;
+  float* __restrict__ hist = stream_hist(state, n);
+#pragma unroll
+  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+    const unsigned f = f0 + j * GDN_STREAM_THREADS;
+    if (f >= nw) break;
+    const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
+    hist[f] = history[(long long)i * h + (h - w) + c];
+  }
+  if (span == 0) {
+    long long* __restrict__ head = reinterpret_cast<long long*>(state);
+    double* __restrict__ carry = stream_carry(state);
+    if (tid < GDN_STREAM_HEADER) head[tid] = 0;
+    for (int f = tid; f < 3 * n; f += GDN_STREAM_THREADS) carry[f] = 0.0;
+  }
+}
+
+// Elements [span * SPAN, (span + 1) * SPAN) of window b's flat [i, c] index, into xb = x_out[b]: the w values of
+// sensor i before tick b of the chunk.  Position b - w + c of the stream relative to the chunk's first tick: negative
+// = column w + (b - w + c) = b + c of hist, else that row of the (time-major) chunk.
+__device__ __forceinline__ void stream_window_span(const void* __restrict__ state, const float* __restrict__ chunk,
+                                                   int n, int w, int b, unsigned span, int tid,
+                                                   float* __restrict__ xb) {
+  const unsigned nw = (unsigned)n * (unsigned)w;     // <= 4096 * 1024
+  const float* __restrict__ hist = stream_hist(state, n);
+  const unsigned f0 = span * GDN_STREAM_SPAN + tid;
+#pragma unroll
+  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+    const unsigned f = f0 + j * GDN_STREAM_THREADS;
+    if (f >= nw) break;
+    const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
+    const int pos = b - w + (int)c;
+    xb[f] = pos < 0 ? hist[(size_t)i * w + (unsigned)(b + (int)c)] : chunk[(size_t)pos * n + i];
+  }
+}
+
+// Normalise, smooth, top m, flag: the sweep of gdn_score_sweep.hpp with top-m lists, as score_smooth_topm_kernel
+// (gdn_score.hip) runs it, over a push.  Here: the series position of the chunk's first tick is read from the state,
+// and only the run at tick 0 reaches back: its three predecessors are the carry (rows 0, 1, 2 = three, two, one tick
+// before; zeros where the series has no such tick, GAPS: 0.0 for a missing reading, through the advance step).
+
+// Rows before the chunk are never used as values (row 0 stands in for the loads); rows past it are clamped.
+struct StreamSource {
+  const float *pred, *gt;
+  const unsigned char* valid;
+  const double* carry;
+  int t, n;
+  __device__ __forceinline__ size_t at(int tt) const { return (size_t)(tt < 0 ? 0 : min(tt, t - 1)) * n; }
+  __device__ __forceinline__ const float* pred_row(int tt) const { return pred + at(tt); }
+  __device__ __forceinline__ const float* gt_row(int tt) const { return gt + at(tt); }
+  __device__ __forceinline__ const unsigned char* valid_row(int tt) const { return valid + at(tt); }
+  template <typename FA, typename FB>
+  __device__ __forceinline__ void before(int t0, const Lanes& l, double (&a)[3], double (&b)[3], FA&& na,
+                                         FB&& nb) const {
+    if (t0 == 0) {                                 // (wave uniform) all six loads in one block: one round trip
+      a[0] = carry[l.ca]; a[1] = carry[(size_t)n + l.ca]; a[2] = carry[2 * (size_t)n + l.ca];
+      b[0] = carry[l.cb]; b[1] = carry[(size_t)n + l.cb]; b[2] = carry[2 * (size_t)n + l.cb];
+    } else {
+      a[0] = na(0); a[1] = na(1); a[2] = na(2);
+      b[0] = nb(0); b[1] = nb(1); b[2] = nb(2);
+    }
+  }
+};
+
+// One wave, one run: ticks [run * RUN, min(t, run * RUN + RUN)) of a push of t rows; lists and flags of those rows.
+template <bool GAPS>
+__device__ __forceinline__ void stream_score_run(const StreamSource& src, const double* __restrict__ med_iqr,
+                                                 double thr, long long first_tick, int run, int lane, int m,
+                                                 double* __restrict__ top_scores, int* __restrict__ top_sensors,
+                                                 int* __restrict__ alarm) {
+  const int t = src.t, n = src.n;
+  const int t0 = run * RUN, t1 = min(t, t0 + RUN);
+  double cs[RUN];                               // the carried list: entry `lane` of every tick of the run
+  int ci[RUN];
+#pragma unroll
+  for (int u = 0; u < RUN; ++u) {
+    cs[u] = -INFINITY;
+    ci[u] = NONE;
+  }
+  for (int s0 = 0; s0 < n; s0 += 128) {
+    const Lanes l(s0, lane, n);
+    score_sweep<GAPS>(src, med_iqr, l, t0, t1, first_tick, [&](int u, int, double sma, double smb) {
+      topm_merge(l, lane, m, sma, smb, cs[u], ci[u]);
+    });
+  }
+  topm_store(cs, ci, lane, m, t0, t1, top_scores, top_sensors);
+  if (lane == 0) {
+#pragma unroll
+    for (int u = 0; u < RUN; ++u)
+      if (t0 + u < t1) alarm[t0 + u] = cs[u] > thr ? 1 : 0;      // strict; a NaN score compares false
+  }
+}
+
+// A whole workgroup rolls row i of hist by `count` ticks: every thread loads its (up to 4) columns of the NEW row —
+// from the old row where the column survives, else from the chunk — then a barrier, then the stores: no column is
+// read after it has been overwritten, whatever count is.
+__device__ __forceinline__ void stream_roll_row(void* __restrict__ state, const float* __restrict__ chunk, int count,
+                                                int n, int w, int i, int tid) {
+  float* __restrict__ row = stream_hist(state, n) + (size_t)i * w;
+  float v[GDN_STREAM_PER_THREAD];
+#pragma unroll
+  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+    const int c = tid + j * GDN_STREAM_THREADS;             // w <= 1024 = PER_THREAD * THREADS
+    v[j] = 0.f;
+    if (c < w) {
+      const long long src = (long long)c + count;           // column of [hist | chunk^T]
+      v[j] = src < w ? row[src] : chunk[(size_t)(src - w) * n + i];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < GDN_STREAM_PER_THREAD; ++j) {
+    const int c = tid + j * GDN_STREAM_THREADS;
+    if (c < w) row[c] = v[j];
+  }
+}
+
+// One workgroup per stream: the carry (one thread per sensor: its three old entries are read before any is written),
+// the alarm log (an ordered compaction: ballot and popcount inside a wave, four wave totals through LDS, 256 flags a
+// round in tick order) and, last, the counters.
+// GAPS: `chunk` is the filled chunk; a carry entry taken from the chunk is 0.0 where valid says the reading was
+// missing, and the carry thread of sensor s folds the push's gap_chunk [2, n] into gaps [2, n] (missing_total,
+// missing_run).  Without GAPS the three trailing parameters are not read.
+template <bool GAPS>
+__device__ __forceinline__ void stream_carry_log(void* __restrict__ state, const float* __restrict__ chunk,
+                                                 const float* __restrict__ pred, const double* __restrict__ med_iqr,
+                                                 const int* __restrict__ alarm, const int* __restrict__ top_sensors,
+                                                 int count, int n, int m, long long* __restrict__ log_ticks,
+                                                 int* __restrict__ log_sensors, long long log_len, int tid,
+                                                 const unsigned char* __restrict__ valid,
+                                                 const int* __restrict__ gap_chunk, long long* __restrict__ gaps) {
+  __shared__ int wave_total[GDN_STREAM_THREADS / 64];
+  long long* __restrict__ head = reinterpret_cast<long long*>(state);
+  double* __restrict__ carry = stream_carry(state);
+  // carry: the last three of [carry0, carry1, carry2, a(chunk row 0), .., a(chunk row count - 1)]
+  for (int s = tid; s < n; s += GDN_STREAM_THREADS) {
+    const Scale sc = sensor_scale(med_iqr, s);
+    double next[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int q = count + j;                                 // position in the 3 + count values above
+      if (q < 3) {
+        next[j] = carry[(size_t)q * n + s];
+      } else {
+        const size_t at = (size_t)(q - 3) * n + s;
+        unsigned ok = 0u;
+        if constexpr (GAPS) ok = valid[at] ? 1u : 0u;
+        next[j] = norm<GAPS>(pred[at], chunk[at], sc.med, sc.inv_den, ok, 0);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) carry[(size_t)j * n + s] = next[j];
+    if constexpr (GAPS) {
+      const int trail = gap_chunk[n + s];
+      gaps[s] += gap_chunk[s];
+      gaps[(size_t)n + s] = trail == count ? gaps[(size_t)n + s] + count : trail;
+    }
+  }
+  // alarm log
+  const long long ticks = head[0], logged = head[2];
+  const int lane = tid & 63, wv = tid >> 6;
+  long long raised = 0;                                        // flags in the rounds before this one
+  for (int base = 0; base < count; base += GDN_STREAM_THREADS) {
+    const int b = base + tid;
+    const bool flag = b < count && alarm[b] != 0;
+    const unsigned long long mask = __ballot(flag);
+    if (lane == 0) wave_total[wv] = __popcll(mask);
+    __syncthreads();
+    int before = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+    for (int v = 0; v < GDN_STREAM_THREADS / 64; ++v) {
+      if (v < wv) before += wave_total[v];
+      total += wave_total[v];
+    }
+    __syncthreads();                                           // wave_total is rewritten next round
+    const long long slot = logged + raised + before;
+    if (flag && slot < log_len) {
+      log_ticks[slot] = ticks + b;
+      for (int r = 0; r < m; ++r) log_sensors[slot * m + r] = top_sensors[(size_t)b * m + r];
+    }
+    raised += total;
+  }
+  if (tid == 0) {
+    head[0] = ticks + count;
+    head[1] += raised;
+    const long long want = logged + raised, room = log_len > logged ? log_len : logged;
+    head[2] = want < room ? want : room;                       // a full log drops entries; `alarms` keeps counting
+  }
+}
+
+}  // namespace gdn_stream_steps

@@ -2165,6 +2165,12 @@ def read_stream_checkpoint(path: str) -> dict:
         return {k: z[k] for k in z.files}
 
 
+def _check_stream_head(model):
+    """The refusal StreamDetector and StreamFleet share: an OutLayer that forward_into has no kernel for."""
+    if model.out_layer_num > 1 and not ops.mlp_fast_tail_supported(model.out_layer, model.embedding.weight.shape[1]):
+        raise model._refusal("refuse_outlayer")            # (GDN.mlp_fast_path_supported's answer, from host facts)
+
+
 class StreamDetector:
     """Scores ticks as they arrive against a frozen calibration, with nothing but launches per push.
 
@@ -2284,8 +2290,7 @@ class StreamDetector:
                 raise ValueError(f"recal_min = {recal_min}: between 1 and recal = {self.recal} kept ticks")
         elif recal_min is not None:
             raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
-        if model.out_layer_num > 1 and not ops.mlp_fast_tail_supported(model.out_layer, model.embedding.weight.shape[1]):
-            raise model._refusal("refuse_outlayer")        # (GDN.mlp_fast_path_supported's answer, from host facts)
+        _check_stream_head(model)
         self.with_gaps = bool(gaps)
         if history is None:
             dev = torch.empty((0,), device=device).device           # ("cuda" -> the current device, with its index)
@@ -2758,3 +2763,186 @@ def _checkpoint_expect(model, prep, recal: int, check_model: bool = True) -> dic
             "calib_bytes": lib.gdn_stream_calib_bytes(n, recal) if recal else 0,
             "model": model_fingerprint(model) if check_model else None,
             "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n}
+
+
+# --------------------------------------------------------------------------- streaming fleet
+def fleet_check_shape(units: int, chunk: int, n: int, w: int) -> None:
+    """The host facts a fleet's buffers depend on, refused by name before any device work: 1 <= units, 1 <= chunk,
+    units * chunk <= 4096 windows per launch, and a window buffer [units, chunk, n, w] fp32 within the evaluators' cap."""
+    if int(units) < 1:
+        raise ValueError(f"units = {units}: a fleet has at least one unit")
+    if int(chunk) < 1 or int(units) * int(chunk) > _STREAM_MAX_CHUNK:
+        raise ValueError(f"units * chunk = {units} * {chunk}: a push scores 1 to {_STREAM_MAX_CHUNK} windows in one "
+                         "launch (longer pushes are split in time; more units: more fleets)")
+    if int(units) * int(chunk) * n * w * 4 > _VALIDATE_CHUNK_BYTES:
+        raise ValueError(f"units * chunk = {units} * {chunk}: the window buffer [{units}, {chunk}, {n}, {w}] fp32 exceeds "
+                         f"{_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
+
+
+def fleet_check_push(ticks, counts, units: int, n: int):
+    """The host checks of StreamFleet.push, before any device work: `ticks` [units, r >= 1, n] fp32; `counts` None, a
+    host sequence / tensor of `units` integers in 0 .. r (returned as a host int64 tensor), or a device int32 tensor
+    [units] (returned as it is: the kernels clamp it)."""
+    if ticks.dim() != 3 or ticks.shape[0] != units or ticks.shape[2] != n:
+        raise ValueError(f"expected ticks of shape [{units}, r, {n}], got {tuple(ticks.shape)}")
+    if ticks.dtype != torch.float32:
+        raise TypeError(f"ticks: expected {torch.float32}, got {ticks.dtype}")
+    r = ticks.shape[1]
+    if r < 1:
+        raise ValueError("a push needs at least one tick")
+    if counts is None:
+        return None
+    if isinstance(counts, torch.Tensor) and counts.is_cuda:
+        if counts.dtype != torch.int32 or counts.shape != (units,):
+            raise ValueError(f"counts: a device tensor must be {torch.int32} of shape [{units}], got {counts.dtype} "
+                             f"{tuple(counts.shape)}")
+        return counts
+    host = torch.as_tensor(counts)
+    if host.dim() != 1 or host.shape[0] != units or host.dtype.is_floating_point or host.dtype == torch.bool:
+        raise ValueError(f"counts: expected {units} integers (one per unit), got {host.dtype} {tuple(host.shape)}")
+    host = host.to(torch.int64)
+    if bool(((host < 0) | (host > r)).any()):
+        raise ValueError(f"counts = {host.tolist()}: every unit contributes 0 to r = {r} of the pushed ticks")
+    return host
+
+
+class StreamFleet:
+    """Scores the ticks of U units of ONE model with one push: a rack of identical servers, a line of identical pumps —
+    the same sensor list and the same trained model, but a median / IQR table, a threshold, a history, counters and an
+    alarm log per unit (include/gdn_hip.h "streaming fleet").
+
+    A push issues ONE copy of `ticks` into the static [U, chunk, n] buffer, ONE small write of the static counts buffer
+    and ONE replay of a graph captured at the first push: fleet_windows -> model.forward_into on the [U * chunk, n, w]
+    view -> fleet_score -> fleet_advance (the only writer of the states).  How many rows a unit contributes is DATA on
+    the device, not a launch argument: the same graph serves a full push, a short one and one in which some units are
+    silent, so there is no eager variant for short pushes.  A push of r > chunk ticks is split in time.
+
+    `med_iqr` [U, n, 2] float64, `threshold` a number or [U], `history` [U, n, h >= w] fp32 on the device; `chunk` ticks
+    per unit and push with U * chunk <= 4096; `top_m`, `log` (entries per unit; 0: no log) and `use_graph` as
+    StreamDetector's.
+
+    The contract: for every unit u the fleet writes the bits of StreamDetector(model, med_iqr[u], threshold[u],
+    history[u], chunk, top_m, log, wide=<the same word>) pushed that unit's real rows in the same cuts, a push with
+    counts[u] == 0 skipped: top_scores, top_sensors and alarm on the real rows, the whole state block (`unit_state(u)`,
+    the layout ops.stream_state_views reads), the log and the counters.  A window's forward does not depend on what else
+    is in its batch.  What IS per launch is the route: `wide=None` asks model.wide_for over ALL units' histories once,
+    and under operand_range == "auto" a guarded forward that meets ONE out-of-range reading redoes the push of all
+    units in fp32; each route is still the evaluator's on that route.  Rows of a push that are not real are cut as zero
+    windows, so a route decision never outlives the push that caused it.
+
+    Out of scope here (the per-unit state layout is a single stream's precisely so that they can follow without a format
+    change): gaps=, recal=, calib="sensor", prep=, events=, save / load, a command-line flag, more than one process."""
+
+    def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
+                 use_graph: bool = True, wide: bool | None = None):
+        self.model = model.eval()
+        w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+        n = model.embedding.weight.shape[0]
+        if not isinstance(history, torch.Tensor) or history.dim() != 3 or history.shape[1] != n:
+            raise ValueError(f"expected a history of shape [U, {n}, h], got "
+                             f"{tuple(history.shape) if isinstance(history, torch.Tensor) else type(history)}")
+        units = history.shape[0]
+        fleet_check_shape(units, chunk, n, w)
+        self.units, self.n, self.w, self.chunk, self.top_m = units, n, w, int(chunk), int(top_m)
+        self.use_graph = bool(use_graph)
+        _check_top_m(top_m, n)
+        if int(log) < 0:
+            raise ValueError(f"log = {log}: the alarm log holds 0 or more entries per unit")
+        if not isinstance(med_iqr, torch.Tensor) or med_iqr.shape != (units, n, 2):
+            raise ValueError(f"expected med_iqr of shape [{units}, {n}, 2], got "
+                             f"{tuple(med_iqr.shape) if isinstance(med_iqr, torch.Tensor) else type(med_iqr)}")
+        threshold = torch.as_tensor(threshold, dtype=torch.float64)
+        if threshold.numel() not in (1, units) or threshold.dim() > 1:
+            raise ValueError(f"threshold: one number or [{units}] of them, got {tuple(threshold.shape)}")
+        _check_stream_head(model)
+        history = ops._chk(history, name="history")
+        dev = history.device
+        self.med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr").clone()
+        self.threshold = threshold.reshape(-1).expand(units).to(dev).clone()
+        self.state = ops.fleet_state(history, w)
+        self.wide = model.wide_for(history[:, :, -w:]) if wide is None else bool(wide)
+        c, m = self.chunk, self.top_m
+        self.chunk_buf = torch.zeros((units, c, n), dtype=torch.float32, device=dev)
+        self.counts = torch.zeros((units,), dtype=torch.int32, device=dev)
+        self.x = torch.zeros((units, c, n, w), dtype=torch.float32, device=dev)
+        self.pred = torch.zeros((units, c, n), dtype=torch.float32, device=dev)
+        self.top_scores = torch.zeros((units, c, m), dtype=torch.float64, device=dev)
+        self.top_sensors = torch.zeros((units, c, m), dtype=torch.int32, device=dev)
+        self.alarm = torch.zeros((units, c), dtype=torch.int32, device=dev)
+        self.log_ticks = torch.zeros((units, int(log)), dtype=torch.int64, device=dev) if log else None
+        self.log_sensors = torch.zeros((units, int(log), m), dtype=torch.int32, device=dev) if log else None
+        self._full = _Replay(lambda *a: self._launch(*a), use_graph, lambda: model._constants().key,
+                             args=lambda: (self._guarded(),))
+        self._last = 0                      # ticks per unit of the last (sub-)push: what the static buffers hold
+
+    @classmethod
+    def from_calibration(cls, model, series, chunk: int, batch: int = 8192, **kw):
+        """A fleet calibrated on `series` [U, n, T] fp32 on the device, each unit's own period known to be normal: ONE
+        SeriesEvaluator step per unit at construction (not a hot path) under the rules of
+        StreamDetector.from_calibration — the table is that step's med_iqr, the threshold the largest anomaly score of
+        the unit's period, the history its last w ticks."""
+        series = ops._chk(series, name="series")
+        w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+        if series.dim() != 3 or series.shape[2] <= w:
+            raise ValueError(f"calibration needs a series [U, n, T] with T > {w}, got {tuple(series.shape)}")
+        fleet_check_shape(series.shape[0], chunk, series.shape[1], w)
+        tables, thresholds = [], []
+        for unit in series:
+            ev = SeriesEvaluator(model, None, unit[:, w:].t().contiguous(), batch=batch, use_graph=False, series=unit)
+            thresholds.append(ev.step().max())
+            tables.append(ev.med_iqr.clone())
+        return cls(model, torch.stack(tables), torch.stack(thresholds), series[:, :, -w:].contiguous(), chunk, **kw)
+
+    # the launches of a push: static arguments only (they are captured)
+    def _guarded(self) -> bool:
+        m = self.model
+        if self.wide or m.operand_range != "auto" or m.out_layer_num != 1:
+            return False
+        c = m._constants()
+        return not c.large and m._plan(c, False) is not None
+
+    def _launch(self, guard: bool):
+        rows = self.units * self.chunk
+        ops.fleet_windows(self.state, self.chunk_buf, self.counts, self.w, self.x)
+        self.model.forward_into(self.x.view(rows, self.n, self.w), self.pred.view(rows, self.n), wide=self.wide,
+                                guard=guard)
+        ops.fleet_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.counts, self.w,
+                        self.top_m, self.top_scores, self.top_sensors, self.alarm)
+        ops.fleet_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors,
+                          self.counts, self.w, self.top_m, self.log_ticks, self.log_sensors)
+
+    graph = property(lambda self: self._full.graph, doc="the captured push, None before the first one")
+
+    def push(self, ticks, counts=None):
+        """Score `ticks` [U, r, n] fp32 (device or host), oldest first, r ticks per unit.  `counts`: None — every unit
+        contributes all r ticks; a host sequence or tensor of U integers, checked here to lie in 0 .. r (ValueError
+        before any device work); or a device int32 tensor [U], which the kernels clamp.  A unit's real rows are its
+        FIRST counts[u] rows of `ticks`.  Returns views (top_scores [U, r', m] float64, top_sensors [U, r', m] int32,
+        alarm [U, r'] int32) of the static buffers, valid until the next push; r' = r when r <= chunk, else the ticks of
+        the last of the pushes it was split into.  Rows of the views at or beyond counts[u] are UNSPECIFIED (whatever an
+        earlier push left there)."""
+        counts = fleet_check_push(ticks, counts, self.units, self.n)
+        for s in range(0, ticks.shape[1], self.chunk):
+            part = ticks[:, s:s + self.chunk]
+            r = part.shape[1]
+            self.chunk_buf[:, :r].copy_(part)
+            if counts is None:
+                self.counts.fill_(r)
+            elif counts.is_cuda:
+                torch.clamp(counts - s if s else counts, 0, r, out=self.counts)
+            else:
+                self.counts.copy_((counts - s).clamp_(0, r).to(torch.int32))
+            self._last = r
+            self._full()
+        r = self._last
+        return self.top_scores[:, :r], self.top_sensors[:, :r], self.alarm[:, :r]
+
+    def status(self):
+        """Per unit (ticks [U], alarms [U], logged [U]) as host int64 tensors: ONE read of the counters (a
+        synchronisation).  Unit u's log is log_ticks[u, :logged[u]] / log_sensors[u, :logged[u]]."""
+        head = ops.fleet_state_views(self.state, self.units, self.n, self.w)[0].cpu()
+        return head[:, 0].clone(), head[:, 1].clone(), head[:, 2].clone()
+
+    def unit_state(self, u: int) -> torch.Tensor:
+        """Unit u's slice of the state (a view): a single stream's state, the layout ops.stream_state_views reads."""
+        return self.state[u]

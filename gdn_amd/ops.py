@@ -1194,6 +1194,102 @@ def stream_calib_write(state, pred, chunk, alarm, ring_keys, ring_keep, exclude_
     return ring_keys, ring_keep
 
 
+# --------------------------------------------------------------------------- streaming fleet
+_FLEET_LIMITS = "1 <= units, units * c <= 4096, 1 <= n <= 4096, 1 <= w <= 1024"
+
+
+def _fleet_state_words(units: int, n: int, w: int) -> int:
+    nbytes = _lib.load().gdn_fleet_state_bytes(units, n, w)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"fleet state: no kernel for units = {units}, n = {n}, w = {w} ({_FLEET_LIMITS})")
+    return nbytes // 8
+
+
+def fleet_state(history, w: int) -> torch.Tensor:
+    """The device states of a fleet (include/gdn_hip.h "streaming fleet") whose units start after `history`
+    [U, n, h >= w]: an int64 tensor [U, gdn_stream_state_bytes(n, w) / 8], row u the stream state of unit u (counters and
+    carry zero, hist = history[u, :, -w:]) in the layout stream_state_views reads.  ONE launch."""
+    history = _chk(history, name="history")
+    if history.dim() != 3:
+        raise ValueError(f"expected the history [U, n, h], got {tuple(history.shape)}")
+    units, n, h = history.shape
+    if h < w:
+        raise ValueError(f"a history of {h} ticks is shorter than the window of {w}: buffer {w} ticks before streaming")
+    words = _fleet_state_words(units, n, w)
+    state = torch.zeros((units, words // units), dtype=torch.int64, device=history.device)
+    _lib.call("gdn_fleet_init", _ptr(state), _ptr(history), h, units, n, w, _stream())
+    return state
+
+
+def fleet_state_views(state, units: int, n: int, w: int):
+    """(counters int64 [U, 3] = ticks, alarms, logged; carry float64 [U, 3, n]; hist fp32 [U, n, w]): views of the
+    states of a fleet.  Row u of each is what stream_state_views gives for unit u's slice."""
+    state = state.view(units, -1)
+    carry = state[:, 4:4 + 3 * n].view(torch.float64).view(units, 3, n)
+    hist = state[:, 4 + 3 * n:].view(torch.float32)[:, : n * w].view(units, n, w)
+    return state[:, :3], carry, hist
+
+
+def _fleet_dims(state, chunk, counts, w: int):
+    chunk = _chk(chunk, name="chunk")
+    if chunk.dim() != 3:
+        raise ValueError(f"expected the chunk [U, c, n] (one row per unit and tick), got {tuple(chunk.shape)}")
+    units, c, n = chunk.shape
+    _stream_buf(state, torch.int64, _fleet_state_words(units, n, w), "state")
+    _stream_buf(counts, torch.int32, units, "counts")
+    return chunk, units, c, n
+
+
+def fleet_windows(state, chunk, counts, w: int, x_out):
+    """x_out[u, b, i, :] = the w values of sensor i of unit u before tick b of `chunk` [U, c, n], for b < counts[u]
+    (int32 [U] on the device, clamped to 0 .. c by the kernel): stream_windows per unit.  Rows b >= counts[u] are
+    written as zeros: the forward's input never depends on an earlier push."""
+    chunk, units, c, n = _fleet_dims(state, chunk, counts, w)
+    _stream_buf(x_out, torch.float32, units * c * n * w, "x_out")
+    _lib.call("gdn_fleet_windows", _ptr(state), _ptr(chunk), _ptr(counts), units, c, n, w, _ptr(x_out), _stream())
+    return x_out
+
+
+def fleet_score(state, pred, chunk, med_iqr, threshold, counts, w: int, m: int, top_scores, top_sensors, alarm):
+    """stream_score per unit in one launch: rows b < counts[u] of pred / chunk [U, c, n] at unit u's stream position,
+    against med_iqr [U, n, 2] and threshold [U] (float64, device).  Rows b >= counts[u] of top_scores [U, c, m],
+    top_sensors [U, c, m] and alarm [U, c] are not written.  `w` places the units' state blocks."""
+    chunk, units, c, n = _fleet_dims(state, chunk, counts, w)
+    _stream_buf(pred, torch.float32, units * c * n, "pred")
+    _stream_buf(med_iqr, torch.float64, units * 2 * n, "med_iqr")
+    _stream_buf(threshold, torch.float64, units, "threshold")
+    _stream_buf(top_scores, torch.float64, units * c * m, "top_scores")
+    _stream_buf(top_sensors, torch.int32, units * c * m, "top_sensors")
+    _stream_buf(alarm, torch.int32, units * c, "alarm")
+    _lib.call("gdn_fleet_score", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(med_iqr), _ptr(threshold), _ptr(counts),
+              units, c, n, w, m, _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
+    return top_scores, top_sensors, alarm
+
+
+def fleet_advance(state, chunk, pred, med_iqr, alarm, top_sensors, counts, w: int, m: int, log_ticks=None,
+                  log_sensors=None):
+    """The one launch that writes the states of a fleet: stream_advance per unit with count = counts[u]; every alarm of
+    unit u is appended to log_ticks [U, L] int64 / log_sensors [U, L, m] int32 in tick order (both None: no log).  A
+    unit with counts[u] == 0 is left as it is, state and log."""
+    chunk, units, c, n = _fleet_dims(state, chunk, counts, w)
+    _stream_buf(pred, torch.float32, units * c * n, "pred")
+    _stream_buf(med_iqr, torch.float64, units * 2 * n, "med_iqr")
+    _stream_buf(alarm, torch.int32, units * c, "alarm")
+    _stream_buf(top_sensors, torch.int32, units * c * m, "top_sensors")
+    if (log_ticks is None) != (log_sensors is None):
+        raise ValueError("give both log_ticks and log_sensors, or neither")
+    log_len = 0
+    if log_ticks is not None:
+        if log_ticks.dim() != 2 or log_ticks.shape[0] != units:
+            raise ValueError(f"log_ticks: expected [{units}, L], got {tuple(log_ticks.shape)}")
+        log_len = log_ticks.shape[1]
+        _stream_buf(log_ticks, torch.int64, units * log_len, "log_ticks")
+        _stream_buf(log_sensors, torch.int32, units * log_len * m, "log_sensors")
+    _lib.call("gdn_fleet_advance", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors),
+              _ptr(counts), units, c, n, w, m, _ptr(log_ticks) if log_len else None,
+              _ptr(log_sensors) if log_len else None, log_len, _stream())
+
+
 # --------------------------------------------------------------------------- raw readings
 _PREP_MAX_DOWN = 64
 

@@ -1066,6 +1066,47 @@ int gdn_stream_events(const void* state, const double* top_scores, const int32_t
 int gdn_alarm_sweep(const double* scores, const uint8_t* labels, long long T, const double* hi, const double* lo,
                     const int32_t* on, const int32_t* off, long long P, int64_t* counts, void* stream);
 
+/* ---- streaming fleet --------------------------------------------------------------------------
+ * U units of ONE model — a rack of servers, a line of pumps: the same sensor list, the same trained model, but a
+ * median / IQR table, a threshold, a history and an alarm log per unit — scored with one run of launches per push, so
+ * that the model's forward sees units x c windows (additive, the ABI version does not move).
+ * State: ONE allocation of gdn_fleet_state_bytes(units, n, w) = units * gdn_stream_state_bytes(n, w) bytes; unit u's
+ * block, at state + u * gdn_stream_state_bytes(n, w), has exactly the layout of "streaming detector" above.
+ * Every tensor of a push gains a leading unit axis:
+ *   chunk [U, c, n] fp32    x_out [U, c, n, w] fp32    pred [U, c, n] fp32    med_iqr [U, n, 2] float64
+ *   threshold [U] float64   top_scores [U, c, m] float64   top_sensors [U, c, m] int32   alarm [U, c] int32
+ *   log_ticks [U, L] int64  log_sensors [U, L, m] int32    counts [U] int32
+ * counts[u] = the rows of unit u that are real in this push, ON THE DEVICE: every kernel reads it there and clamps it
+ * to 0 .. c.  It is never a launch argument, so one captured graph serves a full push, a short one and one in which
+ * some units are silent.  A push is, in stream order: gdn_fleet_windows, the model's forward on x_out viewed as
+ * [U * c, n, w], gdn_fleet_score, gdn_fleet_advance.  Per unit every launch does the single-stream launch's work through
+ * the same device functions, so a unit's outputs on its real rows, its state block and its log are, bit for bit, those
+ * of a single stream pushed that unit's real rows in the same cuts (a push with counts[u] == 0 skipped).
+ *   gdn_fleet_init     gdn_stream_init per unit from history [U, n, h]: one launch, grid (spans, U).
+ *   gdn_fleet_windows  grid (row b, span, unit).  b < counts[u]: the row gdn_stream_windows writes for that unit.
+ *                      b >= counts[u]: zeros, so the forward's input is a function of the states and this push only,
+ *                      never of an earlier push (a stale out-of-range row could otherwise hold a guarded forward on
+ *                      the fp32 route).
+ *   gdn_fleet_score    one wave per (unit, run of 8 ticks): gdn_stream_score's sweep with the unit's first tick and
+ *                      carry, its table rows and its threshold.  Writes rows b < counts[u] only.  `w` only places the
+ *                      unit's state block.
+ *   gdn_fleet_advance  grid (n + 1, unit): gdn_stream_advance per unit with count = counts[u]; the only writer of the
+ *                      states and the logs.  counts[u] == 0 leaves every byte of unit u's state and log untouched.
+ *                      log_len (L, per unit) may be 0 with NULL log pointers.
+ * 1 <= units, units * c <= 4096, 1 <= n <= 4096, 1 <= w <= 1024, 1 <= m <= min(8, n): else GDN_ERR_UNSUPPORTED
+ * (gdn_fleet_state_bytes: 0).  A null required pointer, h < w, log_len < 0, log_len > 0 with a NULL log pointer:
+ * GDN_ERR_ARG.  All decided before any launch.                                                                        */
+long long gdn_fleet_state_bytes(int units, int n, int w);
+int gdn_fleet_init(void* state, const float* history, long long h, int units, int n, int w, void* stream);
+int gdn_fleet_windows(const void* state, const float* chunk, const int32_t* counts, int units, int c, int n, int w,
+                      float* x_out, void* stream);
+int gdn_fleet_score(const void* state, const float* pred, const float* chunk, const double* med_iqr,
+                    const double* threshold, const int32_t* counts, int units, int c, int n, int w, int m,
+                    double* top_scores, int32_t* top_sensors, int32_t* alarm, void* stream);
+int gdn_fleet_advance(void* state, const float* chunk, const float* pred, const double* med_iqr, const int32_t* alarm,
+                      const int32_t* top_sensors, const int32_t* counts, int units, int c, int n, int w, int m,
+                      int64_t* log_ticks, int32_t* log_sensors, long long log_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
