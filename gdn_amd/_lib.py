@@ -145,6 +145,11 @@ SIGNATURES = {
     "gdn_fleet_windows": [_p] * 3 + [_c_int] * 4 + [_p, _p],
     "gdn_fleet_score": [_p] * 6 + [_c_int] * 5 + [_p] * 4,
     "gdn_fleet_advance": [_p] * 7 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p],
+    "gdn_fleet_fill": [_p] * 3 + [_c_int] * 4 + [_p] * 4,
+    "gdn_fleet_score_gaps": [_p] * 7 + [_c_int] * 5 + [_p] * 4,
+    "gdn_fleet_advance_gaps": [_p] * 9 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p, _p],
+    "gdn_fleet_events_bytes": [_c_int, _c_int, ctypes.c_longlong],
+    "gdn_fleet_events": [_p] * 6 + [_c_int] * 7 + [ctypes.c_longlong, _p, _p],
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

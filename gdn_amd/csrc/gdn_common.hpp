@@ -12,6 +12,11 @@
 #define GDN_A_PITCH 64          // a_i / a_j are stored zero padded to 64 floats (w > 64: gdn_terms_pitch(w))
 #define GDN_LONG_MAX_W 1024     // longest window: gdn_long_window.hip
 
+#define GDN_FLEET_MAX_ROWS 4096 // units * c: the cap on windows per launch of a streaming fleet (gdn_fleet.hip, gdn_events.hip)
+static inline bool gdn_fleet_rows_ok(int units, int c) {
+  return units >= 1 && c >= 1 && (long long)units * c <= GDN_FLEET_MAX_ROWS;
+}
+
 static inline int gdn_launch_status() {
   return hipGetLastError() == hipSuccess ? GDN_OK : GDN_ERR_LAUNCH;
 }

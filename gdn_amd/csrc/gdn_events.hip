@@ -1,6 +1,6 @@
 // Alarm episodes (include/gdn_hip.h "Alarm episodes"): on-delay, hysteresis, off-delay and an episode
 // table, as an archive scan that is parallel over T (gdn_episodes_scan) and as one launch of a stream push
-// (gdn_stream_events).  Comparisons and copies only: no floating-point arithmetic, so both forms and the sequential
+// (gdn_stream_events; gdn_fleet_events: the same per unit of a fleet).  Comparisons and copies only: no floating-point arithmetic, so both forms and the sequential
 // definition agree bit for bit.
 //
 // Both forms run the same tile code (EvTile): a workgroup of 256 threads owns a tile of 256 * TPT consecutive ticks,
@@ -33,7 +33,6 @@ constexpr int EV_TPT = 8;                                  // archive: ticks per
 constexpr int EV_TILE = EV_THREADS * EV_TPT;               // 2048 ticks per tile
 constexpr int EV_STREAM_TPT = 16;                          // stream: ONE tile of 4096 ticks
 constexpr int EV_STREAM_MAX = EV_THREADS * EV_STREAM_TPT;
-constexpr int EV_STREAM_SLOTS = EV_STREAM_MAX / 2 + 2;     // the carried episode, <= 2048 opens, the candidate run
 constexpr int EV_MAX_RUN = 4096;
 constexpr long long EV_MAX_T = 1ll << 26;
 constexpr long long EV_MAX_E = 1ll << 20;
@@ -546,20 +545,25 @@ __global__ __launch_bounds__(EV_THREADS) void gdn_episodes_finish_kernel(
 }
 
 // ---- stream form ----------------------------------------------------------------------------------------------------
-// One workgroup, one tile of up to 4096 ticks.  events = [EvCarry | start[E] | end[E] | peak_tick[E] | peak[E] |
-// sensors[E, m]]; the carry is read whole before any of it is written.  Local slot j: the episode that is the j-th open
-// of the push (0: the one open before it); EV_STREAM_SLOTS - 1: the candidate run.
-__global__ __launch_bounds__(EV_THREADS) void gdn_stream_events_kernel(
-    const void* __restrict__ state, const double* __restrict__ top_scores, const int* __restrict__ top_sensors,
-    const double* __restrict__ threshold, const double* __restrict__ clear, int count, int m, int on, int off,
-    long long E, long long* __restrict__ events) {
-  __shared__ unsigned long long key[EV_STREAM_SLOTS], ptick[EV_STREAM_SLOTS];
-  __shared__ long long lstart[EV_STREAM_SLOTS];
+// One workgroup, one tile of up to 256 * TPT ticks (ev_stream_push).  events = [EvCarry | start[E] | end[E] |
+// peak_tick[E] | peak[E] | sensors[E, m]]; the carry is read whole before any of it is written.  Local slot j: the
+// episode that is the j-th open of the push (0: the one open before it); SLOTS - 1: the candidate run.  SLOTS = the
+// carried episode, at most 256 * TPT / 2 opens, the candidate.  The single stream runs TPT = 16 (4096 ticks, about
+// 49 KB of slots); a fleet, whose c is small, instantiates smaller tiles as well (gdn_fleet_events_kernel).
+// Comparisons and copies only, so every TPT that covers `count` writes the same bits.  first_tick: state[0].
+template <int TPT>
+__device__ __forceinline__ void ev_stream_push(const void* __restrict__ state, const double* __restrict__ top_scores,
+                                               const int* __restrict__ top_sensors, const double* __restrict__ threshold,
+                                               const double* __restrict__ clear, int count, int m, int on, int off,
+                                               long long E, long long* __restrict__ events) {
+  constexpr int SLOTS = EV_THREADS * TPT / 2 + 2;
+  __shared__ unsigned long long key[SLOTS], ptick[SLOTS];
+  __shared__ long long lstart[SLOTS];
   __shared__ long long carry_words[EV_CARRY_WORDS];
   __shared__ int sc[EV_THREADS / 64];
   const int tid = threadIdx.x;
   if (tid < EV_CARRY_WORDS) carry_words[tid] = events[tid];
-  for (int j = tid; j < EV_STREAM_SLOTS; j += EV_THREADS) {
+  for (int j = tid; j < SLOTS; j += EV_THREADS) {
     key[j] = 0ull;
     ptick[j] = EV_NO_TICK;
     lstart[j] = 0;
@@ -584,17 +588,17 @@ __global__ __launch_bounds__(EV_THREADS) void gdn_stream_events_kernel(
   P.off = off;
   P.m = m;
   const bool active0 = c.active != 0, cand0 = !active0 && c.run_hi > 0;
-  EvTile<EV_STREAM_TPT> t;
-  ev_tile_events<EV_STREAM_TPT, false>(t, P, 0, (int)c.run_hi, (int)c.run_lo, active0 ? 1 : 0, sc);
-  int rel[EV_STREAM_TPT];
-  ev_tile_targets<EV_STREAM_TPT>(t, P, 0, 0, sc, rel);
+  EvTile<TPT> t;
+  ev_tile_events<TPT, false>(t, P, 0, (int)c.run_hi, (int)c.run_lo, active0 ? 1 : 0, sc);
+  int rel[TPT];
+  ev_tile_targets<TPT>(t, P, 0, 0, sc, rel);
   const long long row0 = c.count - 1;
-  const int p0 = tid * EV_STREAM_TPT;
+  const int p0 = tid * TPT;
   const bool active_out = t.last_code < 0 ? active0 : (t.last_code & 3) == 2;
   if (tid == 0 && active0) lstart[0] = c.open_start;
   __syncthreads();
 #pragma unroll
-  for (int u = 0; u < EV_STREAM_TPT; ++u) {
+  for (int u = 0; u < TPT; ++u) {
     const long long tick = P.first_tick + p0 + u;
     const int j = t.opens_excl + __popc(t.openm & ((2u << u) - 1u));
     if ((t.openm >> u) & 1u) {
@@ -604,16 +608,16 @@ __global__ __launch_bounds__(EV_THREADS) void gdn_stream_events_kernel(
         t_end[row0 + j] = -1;
       }
     }
-    if (rel[u] != -1) atomicMax(&key[rel[u] == -2 ? EV_STREAM_SLOTS - 1 : rel[u]], ev_image(t.s[u]));
+    if (rel[u] != -1) atomicMax(&key[rel[u] == -2 ? SLOTS - 1 : rel[u]], ev_image(t.s[u]));
   }
   __syncthreads();
 #pragma unroll
-  for (int u = 0; u < EV_STREAM_TPT; ++u) {
+  for (int u = 0; u < TPT; ++u) {
     const long long tick = P.first_tick + p0 + u;
     const int j = t.opens_excl + __popc(t.openm & ((2u << u) - 1u));
     if (((t.closem >> u) & 1u) && row0 + j < E) t_end[row0 + j] = tick - off + 1;      // (after its open's end = -1)
     if (rel[u] != -1) {
-      const int slot = rel[u] == -2 ? EV_STREAM_SLOTS - 1 : rel[u];
+      const int slot = rel[u] == -2 ? SLOTS - 1 : rel[u];
       if (ev_image(t.s[u]) == key[slot]) atomicMin(&ptick[slot], (unsigned long long)tick);
     }
   }
@@ -646,7 +650,7 @@ __global__ __launch_bounds__(EV_THREADS) void gdn_stream_events_kernel(
     out->run_lo = rlo_out;
     EvPeak r = {};
     if (!active_out && rhi_out > 0)
-      r = ev_peak_of(P, top_sensors, ptick[EV_STREAM_SLOTS - 1], c, false, cand0 && t.Lh_tot == EV_NONE);
+      r = ev_peak_of(P, top_sensors, ptick[SLOTS - 1], c, false, cand0 && t.Lh_tot == EV_NONE);
     out->cand_peak = r.peak;
     out->cand_tick = r.tick;
     for (int q = 0; q < 8; ++q) out->cand_sensors[q] = r.sensors[q];
@@ -659,9 +663,44 @@ __global__ __launch_bounds__(EV_THREADS) void gdn_stream_events_kernel(
   }
 }
 
+__global__ __launch_bounds__(EV_THREADS) void gdn_stream_events_kernel(
+    const void* __restrict__ state, const double* __restrict__ top_scores, const int* __restrict__ top_sensors,
+    const double* __restrict__ threshold, const double* __restrict__ clear, int count, int m, int on, int off,
+    long long E, long long* __restrict__ events) {
+  ev_stream_push<EV_STREAM_TPT>(state, top_scores, top_sensors, threshold, clear, count, m, on, off, E, events);
+}
+
+// Workgroup u: gdn_stream_events on unit u of a fleet (include/gdn_hip.h "streaming fleet"): its rows of top_scores /
+// top_sensors [U, c, m], its threshold and clear level, first_tick from its state block, count = counts[u] clamped to
+// 0 .. c (0: the unit's events block is not touched), its block at events + u * ev_words.  TPT: the smallest tile of
+// the instantiated ones that covers c, chosen on the host from c alone.
+template <int TPT>
+__global__ __launch_bounds__(EV_THREADS) void gdn_fleet_events_kernel(
+    const void* __restrict__ state, long long state_bytes, const double* __restrict__ top_scores,
+    const int* __restrict__ top_sensors, const double* __restrict__ threshold, const double* __restrict__ clear,
+    const int* __restrict__ counts, int c, int m, int on, int off, long long E, long long* __restrict__ events,
+    long long ev_words) {
+  const int u = blockIdx.x;
+  const int count = min(max(counts[u], 0), c);
+  if (count == 0) return;                                  // (workgroup uniform, ahead of every barrier)
+  const size_t row0 = (size_t)u * c * m;
+  ev_stream_push<TPT>(reinterpret_cast<const char*>(state) + (size_t)u * (size_t)state_bytes, top_scores + row0,
+                      top_sensors + row0, threshold + u, clear + u, count, m, on, off, E, events + (size_t)u * ev_words);
+}
+
 bool ev_shape_ok(long long T, int m, int on, int off, long long E) {
   return T >= 1 && T <= EV_MAX_T && m >= 1 && m <= 8 && on >= 1 && on <= EV_MAX_RUN && off >= 1 && off <= EV_MAX_RUN &&
          E >= 0 && E <= EV_MAX_E;
+}
+
+template <int TPT>
+void fleet_events_launch(const void* state, long long state_bytes, const double* top_scores, const int32_t* top_sensors,
+                         const double* threshold, const double* clear, const int32_t* counts, int units, int c, int m,
+                         int on, int off, long long E, void* events, long long ev_words, hipStream_t stream) {
+  static_assert(TPT <= EV_STREAM_TPT, "no tile beyond the stream's");
+  hipLaunchKernelGGL(gdn_fleet_events_kernel<TPT>, dim3((unsigned)units), dim3(EV_THREADS), 0, stream, state, state_bytes,
+                     top_scores, top_sensors, threshold, clear, counts, c, m, on, off, E,
+                     reinterpret_cast<long long*>(events), ev_words);
 }
 
 int episodes_scan(const double* scores, const int32_t* top_sensors, long long T, int m, double hi, double lo, int on,
@@ -741,5 +780,32 @@ extern "C" int gdn_stream_events(const void* state, const double* top_scores, co
   if (c > EV_STREAM_MAX || !ev_shape_ok(count, m, on, off, E)) return GDN_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(gdn_stream_events_kernel, dim3(1), dim3(EV_THREADS), 0, (hipStream_t)stream, state, top_scores,
                      top_sensors, threshold, clear, count, m, on, off, E, reinterpret_cast<long long*>(events));
+  return gdn_launch_status();
+}
+
+extern "C" long long gdn_fleet_events_bytes(int units, int m, long long E) {
+  if (units < 1 || units > GDN_FLEET_MAX_ROWS) return 0;
+  return (long long)units * gdn_stream_events_bytes(m, E);
+}
+
+// The tile follows c alone (known on the host, captured): 256, 1024 or the stream's 4096 ticks.
+extern "C" int gdn_fleet_events(const void* state, const double* top_scores, const int32_t* top_sensors,
+                                const double* threshold, const double* clear, const int32_t* counts, int units, int c,
+                                int n, int w, int m, int on, int off, long long E, void* events, void* stream) {
+  if (!state || !top_scores || !top_sensors || !threshold || !clear || !counts || !events) return GDN_ERR_ARG;
+  const long long state_bytes = gdn_stream_state_bytes(n, w);                    // 0: no such stream shape
+  if (!gdn_fleet_rows_ok(units, c) || state_bytes <= 0) return GDN_ERR_UNSUPPORTED;
+  if (!ev_shape_ok(c, m, on, off, E)) return GDN_ERR_UNSUPPORTED;
+  const long long ev_words = gdn_stream_events_bytes(m, E) / 8;
+  const hipStream_t s = (hipStream_t)stream;
+  if (c <= EV_THREADS)
+    fleet_events_launch<1>(state, state_bytes, top_scores, top_sensors, threshold, clear, counts, units, c, m, on, off,
+                           E, events, ev_words, s);
+  else if (c <= EV_THREADS * 4)
+    fleet_events_launch<4>(state, state_bytes, top_scores, top_sensors, threshold, clear, counts, units, c, m, on, off,
+                           E, events, ev_words, s);
+  else
+    fleet_events_launch<EV_STREAM_TPT>(state, state_bytes, top_scores, top_sensors, threshold, clear, counts, units, c,
+                                       m, on, off, E, events, ev_words, s);
   return gdn_launch_status();
 }

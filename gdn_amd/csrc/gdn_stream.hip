@@ -33,79 +33,13 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_windows_kernel(
   stream_window_span(state, chunk, n, w, b, blockIdx.y, threadIdx.x, x_out + (size_t)b * ((unsigned)n * (unsigned)w));
 }
 
-// Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it
-// does not depend on how floating-point comparisons with NaN are compiled.
-#define GDN_FILL_WAVES 16            // waves of a workgroup: each owns a contiguous segment of the chunk's rows
-#define GDN_FILL_DEPTH 8             // row loads in flight per lane
-__device__ inline bool stream_missing(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-// Workgroup g: sensors [64 g, 64 g + 64), one per lane (a row of the time-major chunk is contiguous along sensors:
-// coalesced).  Wave v walks rows [v * seg, (v + 1) * seg) ^ [0, count), DEPTH loads at a time, and reduces them to
-// (latest real reading, found one, missing readings, missing readings after the latest real one = the whole segment
-// when there is none).  "The right-most real reading wins" is associative: the segments meet in LDS, every wave takes
-// the latest real reading before its segment (hist[i, w - 1] when no earlier segment has one) and walks its rows a
-// second time, writing.  Wave 0 folds the counts.  Reads the state, writes none of it; no workgroup waits on another.
+// Hold missing readings (stream_fill_group, gdn_stream_steps.hpp): workgroup g of GDN_FILL_WAVES waves owns sensors
+// [64 g, 64 g + 64), each wave a contiguous segment of the chunk's rows.  Reads the state, writes none of it; no
+// workgroup waits on another.
 __global__ __launch_bounds__(GDN_FILL_WAVES * 64) void gdn_stream_fill_kernel(
     const void* __restrict__ state, const float* __restrict__ raw, int count, int n, int w,
     float* __restrict__ filled, unsigned char* __restrict__ valid, int* __restrict__ gap_chunk) {
-  __shared__ float seg_last[GDN_FILL_WAVES][64];
-  __shared__ int seg_found[GDN_FILL_WAVES][64];
-  __shared__ int seg_missing[GDN_FILL_WAVES][64];
-  __shared__ int seg_trail[GDN_FILL_WAVES][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + lane;
-  const bool live = i < n;
-  const int ic = live ? i : n - 1;                                   // a dead lane reads sensor n - 1, writes nothing
-  const int seg = (count + GDN_FILL_WAVES - 1) / GDN_FILL_WAVES;
-  const int r0 = min(count, wv * seg), r1 = min(count, r0 + seg);
-  float last = 0.f;
-  int found = 0, missing = 0, trail = 0;
-  for (int b = r0; b < r1; b += GDN_FILL_DEPTH) {
-    float v[GDN_FILL_DEPTH];
-#pragma unroll
-    for (int u = 0; u < GDN_FILL_DEPTH; ++u) v[u] = raw[(size_t)min(b + u, r1 - 1) * n + ic];
-#pragma unroll
-    for (int u = 0; u < GDN_FILL_DEPTH; ++u) {
-      if (b + u < r1) {                                              // (wave uniform)
-        if (stream_missing(v[u])) { ++missing; ++trail; }
-        else { last = v[u]; found = 1; trail = 0; }
-      }
-    }
-  }
-  seg_last[wv][lane] = last;
-  seg_found[wv][lane] = found;
-  seg_missing[wv][lane] = missing;
-  seg_trail[wv][lane] = trail;
-  __syncthreads();
-  float hold = stream_hist(state, n)[(size_t)ic * w + (w - 1)];
-  for (int v = 0; v < wv; ++v)
-    if (seg_found[v][lane]) hold = seg_last[v][lane];
-  for (int b = r0; b < r1; b += GDN_FILL_DEPTH) {
-    float v[GDN_FILL_DEPTH];
-#pragma unroll
-    for (int u = 0; u < GDN_FILL_DEPTH; ++u) v[u] = raw[(size_t)min(b + u, r1 - 1) * n + ic];
-#pragma unroll
-    for (int u = 0; u < GDN_FILL_DEPTH; ++u) {
-      if (b + u < r1) {
-        const bool gone = stream_missing(v[u]);
-        if (!gone) hold = v[u];
-        if (live) {
-          filled[(size_t)(b + u) * n + i] = hold;
-          valid[(size_t)(b + u) * n + i] = gone ? 0 : 1;
-        }
-      }
-    }
-  }
-  if (wv == 0 && live) {
-    int total = 0, run = 0;
-    for (int v = 0; v < GDN_FILL_WAVES; ++v) total += seg_missing[v][lane];
-    for (int v = GDN_FILL_WAVES - 1; v >= 0; --v) {                  // from the last row back to the latest real reading
-      run += seg_trail[v][lane];
-      if (seg_found[v][lane]) break;
-    }
-    gap_chunk[i] = total;
-    gap_chunk[n + i] = run;
-  }
+  stream_fill_group<GDN_FILL_WAVES>(state, raw, count, n, w, filled, valid, gap_chunk, blockIdx.x, threadIdx.x);
 }
 
 // Normalise, smooth, top m, flag (stream_score_run): a wave per run of RUN ticks, grid-stride over the runs.

@@ -2,7 +2,8 @@
 // the fleet kernels (gdn_fleet.hip): the layout of a stream state, the seeding of hist, the window cut, the score of a
 // run of ticks with the carried smoothing state, the hist roll, and the carry / ordered log compaction / counters.
 // A kernel decides which state, which rows and which count a workgroup works on and calls the step; a fleet is a
-// stream per unit, so a unit's state block is written bit for bit as the single stream writes it.
+// stream per unit, so a unit's state block is written bit for bit as the single stream writes it.  The hold of
+// missing readings (stream_fill_group) is a step like the others.
 // The float64 scoring arithmetic is gdn_score_sweep.hpp's (no FMA contraction in a unit that includes this header).
 #pragma once
 #include "gdn_score_sweep.hpp"
@@ -76,6 +77,85 @@ __device__ __forceinline__ void stream_window_span(const void* __restrict__ stat
     const unsigned i = f / (unsigned)w, c = f - i * (unsigned)w;
     const int pos = b - w + (int)c;
     xb[f] = pos < 0 ? hist[(size_t)i * w + (unsigned)(b + (int)c)] : chunk[(size_t)pos * n + i];
+  }
+}
+
+// Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it
+// does not depend on how floating-point comparisons with NaN are compiled.
+#define GDN_FILL_WAVES 16            // waves of the single stream's workgroup (a fleet picks 1, 4 or 16 from c)
+#define GDN_FILL_DEPTH 8             // row loads in flight per lane
+__device__ inline bool stream_missing(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// A workgroup of WAVES waves, sensor group g: sensors [64 g, 64 g + 64), one per lane (a row of the time-major chunk is
+// contiguous along sensors: coalesced).  Wave v walks rows [v * seg, (v + 1) * seg) ^ [0, count), DEPTH loads at a
+// time, and reduces them to (latest real reading, found one, missing readings, missing readings after the latest real
+// one = the whole segment when there is none).  "The right-most real reading wins" is associative: the segments meet in
+// LDS, every wave takes the latest real reading before its segment (hist[i, w - 1] when no earlier segment has one) and
+// walks its rows a second time, writing.  Wave 0 folds the counts.  Integer counts and copies only, so every WAVES
+// gives the same bits.  Reads the state, writes none of it; rows at or beyond `count` are neither read nor written.
+// Every thread of the workgroup must call it (a barrier inside); count >= 1.
+template <int WAVES>
+__device__ __forceinline__ void stream_fill_group(const void* __restrict__ state, const float* __restrict__ raw,
+                                                  int count, int n, int w, float* __restrict__ filled,
+                                                  unsigned char* __restrict__ valid, int* __restrict__ gap_chunk,
+                                                  int g, int tid) {
+  __shared__ float seg_last[WAVES][64];
+  __shared__ int seg_found[WAVES][64];
+  __shared__ int seg_missing[WAVES][64];
+  __shared__ int seg_trail[WAVES][64];
+  const int lane = tid & 63, wv = tid >> 6;
+  const int i = g * 64 + lane;
+  const bool live = i < n;
+  const int ic = live ? i : n - 1;                                   // a dead lane reads sensor n - 1, writes nothing
+  const int seg = (count + WAVES - 1) / WAVES;
+  const int r0 = min(count, wv * seg), r1 = min(count, r0 + seg);
+  float last = 0.f;
+  int found = 0, missing = 0, trail = 0;
+  for (int b = r0; b < r1; b += GDN_FILL_DEPTH) {
+    float v[GDN_FILL_DEPTH];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) v[u] = raw[(size_t)min(b + u, r1 - 1) * n + ic];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) {
+      if (b + u < r1) {                                              // (wave uniform)
+        if (stream_missing(v[u])) { ++missing; ++trail; }
+        else { last = v[u]; found = 1; trail = 0; }
+      }
+    }
+  }
+  seg_last[wv][lane] = last;
+  seg_found[wv][lane] = found;
+  seg_missing[wv][lane] = missing;
+  seg_trail[wv][lane] = trail;
+  __syncthreads();
+  float hold = stream_hist(state, n)[(size_t)ic * w + (w - 1)];
+  for (int v = 0; v < wv; ++v)
+    if (seg_found[v][lane]) hold = seg_last[v][lane];
+  for (int b = r0; b < r1; b += GDN_FILL_DEPTH) {
+    float v[GDN_FILL_DEPTH];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) v[u] = raw[(size_t)min(b + u, r1 - 1) * n + ic];
+#pragma unroll
+    for (int u = 0; u < GDN_FILL_DEPTH; ++u) {
+      if (b + u < r1) {
+        const bool gone = stream_missing(v[u]);
+        if (!gone) hold = v[u];
+        if (live) {
+          filled[(size_t)(b + u) * n + i] = hold;
+          valid[(size_t)(b + u) * n + i] = gone ? 0 : 1;
+        }
+      }
+    }
+  }
+  if (wv == 0 && live) {
+    int total = 0, run = 0;
+    for (int v = 0; v < WAVES; ++v) total += seg_missing[v][lane];
+    for (int v = WAVES - 1; v >= 0; --v) {                           // from the last row back to the latest real reading
+      run += seg_trail[v][lane];
+      if (seg_found[v][lane]) break;
+    }
+    gap_chunk[i] = total;
+    gap_chunk[n + i] = run;
   }
 }
 

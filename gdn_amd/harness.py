@@ -2806,6 +2806,27 @@ def fleet_check_push(ticks, counts, units: int, n: int):
     return host
 
 
+def fleet_clear_levels(lo, threshold, units: int) -> torch.Tensor:
+    """The clear levels of a fleet's events= as a host float64 tensor [units]: `lo` None (each unit's raise level), one
+    number or `units` of them, against `threshold` (one number or [units]).  Refused by name: another shape, a NaN
+    level, a lo[u] above threshold[u]."""
+    hi = torch.as_tensor(threshold, dtype=torch.float64).detach().cpu().reshape(-1).expand(units)
+    if lo is None:
+        return hi.clone()
+    lo = torch.as_tensor(lo, dtype=torch.float64).detach().cpu()
+    if lo.dim() > 1 or lo.numel() not in (1, units):
+        raise ValueError(f"events: lo is one number, None or [{units}] of them, got {tuple(lo.shape)}")
+    lo = lo.reshape(-1).expand(units).clone()
+    if bool(torch.isnan(lo).any()):
+        raise ValueError("events: lo holds a NaN; the clear level must be a number")
+    bad = torch.nonzero(lo > hi).flatten()
+    if bad.numel():
+        u = int(bad[0])
+        raise ValueError(f"events: lo[{u}] = {float(lo[u])} lies above the raise level of unit {u} (threshold[{u}] = "
+                         f"{float(hi[u])})")
+    return lo
+
+
 class StreamFleet:
     """Scores the ticks of U units of ONE model with one push: a rack of identical servers, a line of identical pumps —
     the same sensor list and the same trained model, but a median / IQR table, a threshold, a history, counters and an
@@ -2830,11 +2851,28 @@ class StreamFleet:
     units in fp32; each route is still the evaluator's on that route.  Rows of a push that are not real are cut as zero
     windows, so a route decision never outlives the push that caused it.
 
+    `gaps=True` is StreamDetector's gaps=True per unit: a pushed value that is not finite is a missing
+    reading.  The push lands in `raw_buf` [U, chunk, n] and fleet_fill leads the launches; `chunk_buf` is then the FILLED
+    chunk, `valid` [U, chunk, n] uint8 the last push's plane (rows at or beyond counts[u] unspecified), and the score and
+    advance launches are their gaps forms.  `status_gaps()` reads the per-unit, per-sensor counters.  Only a unit's real
+    rows are looked at: a non-finite value in a row at or beyond counts[u] is not a missing reading.  The last w ticks
+    of every unit's history must be finite.
+
+    `events=dict(on=, off=, lo=, cap=)` is StreamDetector's events= per unit: fleet_events sits between the score and
+    the advance launch and folds every unit's real rows into that unit's block of `events` [U, words] (a single
+    stream's events allocation per row); `clear` [U] float64 on the device holds the clear levels (`lo`: one number,
+    None = each unit's threshold at construction, or [U]); `episodes(u)` returns unit u's table.  A silent unit's block
+    is not touched, whatever episode is open in it.
+
+    Both are off by default, and then a push issues exactly the launches it always did.  With them the contract above
+    reads StreamDetector(..., gaps=True / events=...) for every unit, `status_gaps()` and `episodes()` included; it is
+    still ONE copy of the ticks, one counts write and ONE replay per push, one graph for full, short and silent units.
+
     Out of scope here (the per-unit state layout is a single stream's precisely so that they can follow without a format
-    change): gaps=, recal=, calib="sensor", prep=, events=, save / load, a command-line flag, more than one process."""
+    change): recal=, calib="sensor", calib_gaps, prep=, save / load, a command-line flag, more than one process."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
-                 use_graph: bool = True, wide: bool | None = None):
+                 use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None):
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -2854,6 +2892,14 @@ class StreamFleet:
         threshold = torch.as_tensor(threshold, dtype=torch.float64)
         if threshold.numel() not in (1, units) or threshold.dim() > 1:
             raise ValueError(f"threshold: one number or [{units}] of them, got {tuple(threshold.shape)}")
+        # the two options: host facts only, before any device work
+        self.with_gaps = bool(gaps)
+        self.events_cfg = None if events is None else events_config({**events, "lo": None}, self.top_m)
+        clear = None if events is None else fleet_clear_levels(events.get("lo"), threshold, units)
+        if self.with_gaps and history.shape[2] >= w and not bool(torch.isfinite(history[:, :, -w:]).all()):
+            raise ValueError(f"history: the last {w} ticks of a unit hold a value that is not finite; with gaps=True "
+                             "every missing reading is held at an earlier real one, so every unit's stream must begin "
+                             "on real readings")
         _check_stream_head(model)
         history = ops._chk(history, name="history")
         dev = history.device
@@ -2871,6 +2917,17 @@ class StreamFleet:
         self.alarm = torch.zeros((units, c), dtype=torch.int32, device=dev)
         self.log_ticks = torch.zeros((units, int(log)), dtype=torch.int64, device=dev) if log else None
         self.log_sensors = torch.zeros((units, int(log), m), dtype=torch.int32, device=dev) if log else None
+        self.raw_buf = self.valid = self.gap_chunk = self.gaps = None
+        if self.with_gaps:
+            self.raw_buf = torch.zeros((units, c, n), dtype=torch.float32, device=dev)
+            self.valid = torch.zeros((units, c, n), dtype=torch.uint8, device=dev)
+            self.gap_chunk = torch.zeros((units, 2, n), dtype=torch.int32, device=dev)
+            self.gaps = torch.zeros((units, 2, n), dtype=torch.int64, device=dev)    # missing_total, missing_run
+        self.events = self.clear = None
+        if self.events_cfg is not None:
+            self.events_cfg.pop("lo")
+            self.clear = clear.to(dev)
+            self.events = ops.fleet_events_alloc(units, m, self.events_cfg["cap"], dev)
         self._full = _Replay(lambda *a: self._launch(*a), use_graph, lambda: model._constants().key,
                              args=lambda: (self._guarded(),))
         self._last = 0                      # ticks per unit of the last (sub-)push: what the static buffers hold
@@ -2880,7 +2937,12 @@ class StreamFleet:
         """A fleet calibrated on `series` [U, n, T] fp32 on the device, each unit's own period known to be normal: ONE
         SeriesEvaluator step per unit at construction (not a hot path) under the rules of
         StreamDetector.from_calibration — the table is that step's med_iqr, the threshold the largest anomaly score of
-        the unit's period, the history its last w ticks."""
+        the unit's period, the history its last w ticks.  `gaps=` and `events=` pass through; the calibration itself
+        knows no missing reading (there is no calib_gaps here), so with gaps=True a series that is not finite is
+        refused."""
+        if kw.get("gaps") and isinstance(series, torch.Tensor) and not bool(torch.isfinite(series).all()):
+            raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
+                             "stream, not the calibration (fill or cut the period first)")
         series = ops._chk(series, name="series")
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         if series.dim() != 3 or series.shape[2] <= w:
@@ -2903,13 +2965,21 @@ class StreamFleet:
 
     def _launch(self, guard: bool):
         rows = self.units * self.chunk
+        if self.with_gaps:
+            ops.fleet_fill(self.state, self.raw_buf, self.counts, self.w, self.chunk_buf, self.valid, self.gap_chunk)
         ops.fleet_windows(self.state, self.chunk_buf, self.counts, self.w, self.x)
         self.model.forward_into(self.x.view(rows, self.n, self.w), self.pred.view(rows, self.n), wide=self.wide,
                                 guard=guard)
+        # valid, gap_chunk and gaps are None on a plain fleet: the wrappers then call the plain symbols
         ops.fleet_score(self.state, self.pred, self.chunk_buf, self.med_iqr, self.threshold, self.counts, self.w,
-                        self.top_m, self.top_scores, self.top_sensors, self.alarm)
+                        self.top_m, self.top_scores, self.top_sensors, self.alarm, valid=self.valid)
+        if self.events is not None:
+            ops.fleet_events(self.state, self.top_scores, self.top_sensors, self.threshold, self.clear, self.counts,
+                             self.n, self.w, self.events_cfg["on"], self.events_cfg["off"], self.events_cfg["cap"],
+                             self.events)
         ops.fleet_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors,
-                          self.counts, self.w, self.top_m, self.log_ticks, self.log_sensors)
+                          self.counts, self.w, self.top_m, self.log_ticks, self.log_sensors, valid=self.valid,
+                          gap_chunk=self.gap_chunk, gaps=self.gaps)
 
     graph = property(lambda self: self._full.graph, doc="the captured push, None before the first one")
 
@@ -2925,7 +2995,7 @@ class StreamFleet:
         for s in range(0, ticks.shape[1], self.chunk):
             part = ticks[:, s:s + self.chunk]
             r = part.shape[1]
-            self.chunk_buf[:, :r].copy_(part)
+            (self.raw_buf if self.with_gaps else self.chunk_buf)[:, :r].copy_(part)
             if counts is None:
                 self.counts.fill_(r)
             elif counts.is_cuda:
@@ -2946,3 +3016,22 @@ class StreamFleet:
     def unit_state(self, u: int) -> torch.Tensor:
         """Unit u's slice of the state (a view): a single stream's state, the layout ops.stream_state_views reads."""
         return self.state[u]
+
+    def status_gaps(self):
+        """(missing_total [U, n] int64, missing_run [U, n] int64) on the host, gaps=True only: per unit what
+        StreamDetector.status_gaps() returns.  ONE read (a synchronisation)."""
+        if not self.with_gaps:
+            raise ValueError("status_gaps(): the fleet was built with gaps=False and counts no missing readings")
+        both = self.gaps.cpu()
+        return both[:, 0], both[:, 1]
+
+    def episodes(self, u: int) -> Episodes:
+        """Unit u's episode table (events= only): views of the unit's block of the events allocation, read exactly as
+        StreamDetector.episodes() reads a single stream's; a later push moves them."""
+        if self.events is None:
+            raise ValueError("episodes(): the fleet was built with events=None and keeps no episode tables")
+        if not 0 <= int(u) < self.units:
+            raise ValueError(f"episodes({u}): the fleet has units 0 .. {self.units - 1}")
+        carry, start, end, peak_tick, peak, sensors = ops.stream_events_views(self.events[int(u)], self.top_m,
+                                                                              self.events_cfg["cap"])
+        return Episodes(start, end, peak, peak_tick, sensors, carry[:1])

@@ -1250,29 +1250,62 @@ def fleet_windows(state, chunk, counts, w: int, x_out):
     return x_out
 
 
-def fleet_score(state, pred, chunk, med_iqr, threshold, counts, w: int, m: int, top_scores, top_sensors, alarm):
+def fleet_fill(state, raw_chunk, counts, w: int, filled_chunk, valid, gap_chunk):
+    """stream_fill per unit in one launch (gdn_fleet_fill): the missing readings (not finite) of rows b < counts[u] of
+    `raw_chunk` [U, c, n] held at the unit's latest real reading — an earlier row of its chunk, else its own
+    hist[:, w - 1] — into `filled_chunk` [U, c, n]; valid [U, c, n] uint8; gap_chunk [U, 2, n] int32.  Rows at or beyond
+    counts[u] are neither read nor written; a unit with counts[u] == 0 writes nothing, gap_chunk included."""
+    raw_chunk, units, c, n = _fleet_dims(state, raw_chunk, counts, w)
+    _stream_buf(filled_chunk, torch.float32, units * c * n, "filled_chunk")
+    _stream_buf(valid, torch.uint8, units * c * n, "valid")
+    _stream_buf(gap_chunk, torch.int32, units * 2 * n, "gap_chunk")
+    if filled_chunk.data_ptr() == raw_chunk.data_ptr():
+        raise ValueError("filled_chunk must not alias raw_chunk")
+    _lib.call("gdn_fleet_fill", _ptr(state), _ptr(raw_chunk), _ptr(counts), units, c, n, w, _ptr(filled_chunk),
+              _ptr(valid), _ptr(gap_chunk), _stream())
+    return filled_chunk, valid, gap_chunk
+
+
+def fleet_score(state, pred, chunk, med_iqr, threshold, counts, w: int, m: int, top_scores, top_sensors, alarm,
+                valid=None):
     """stream_score per unit in one launch: rows b < counts[u] of pred / chunk [U, c, n] at unit u's stream position,
     against med_iqr [U, n, 2] and threshold [U] (float64, device).  Rows b >= counts[u] of top_scores [U, c, m],
-    top_sensors [U, c, m] and alarm [U, c] are not written.  `w` places the units' state blocks."""
+    top_sensors [U, c, m] and alarm [U, c] are not written.  `w` places the units' state blocks.  With `valid`
+    (fleet_fill's plane of the filled `chunk`; gdn_fleet_score_gaps) the normalised error of a missing reading is 0.0."""
     chunk, units, c, n = _fleet_dims(state, chunk, counts, w)
     _stream_buf(pred, torch.float32, units * c * n, "pred")
+    if valid is not None:
+        _stream_buf(valid, torch.uint8, units * c * n, "valid")
     _stream_buf(med_iqr, torch.float64, units * 2 * n, "med_iqr")
     _stream_buf(threshold, torch.float64, units, "threshold")
     _stream_buf(top_scores, torch.float64, units * c * m, "top_scores")
     _stream_buf(top_sensors, torch.int32, units * c * m, "top_sensors")
     _stream_buf(alarm, torch.int32, units * c, "alarm")
-    _lib.call("gdn_fleet_score", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(med_iqr), _ptr(threshold), _ptr(counts),
-              units, c, n, w, m, _ptr(top_scores), _ptr(top_sensors), _ptr(alarm), _stream())
+    tail = (_ptr(med_iqr), _ptr(threshold), _ptr(counts), units, c, n, w, m, _ptr(top_scores), _ptr(top_sensors),
+            _ptr(alarm), _stream())
+    if valid is None:
+        _lib.call("gdn_fleet_score", _ptr(state), _ptr(pred), _ptr(chunk), *tail)
+    else:
+        _lib.call("gdn_fleet_score_gaps", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(valid), *tail)
     return top_scores, top_sensors, alarm
 
 
 def fleet_advance(state, chunk, pred, med_iqr, alarm, top_sensors, counts, w: int, m: int, log_ticks=None,
-                  log_sensors=None):
+                  log_sensors=None, valid=None, gap_chunk=None, gaps=None):
     """The one launch that writes the states of a fleet: stream_advance per unit with count = counts[u]; every alarm of
     unit u is appended to log_ticks [U, L] int64 / log_sensors [U, L, m] int32 in tick order (both None: no log).  A
-    unit with counts[u] == 0 is left as it is, state and log."""
+    unit with counts[u] == 0 is left as it is, state and log.  With `valid`, `gap_chunk` (fleet_fill's, of the filled
+    `chunk`) and `gaps` [U, 2, n] int64, all three or none (gdn_fleet_advance_gaps): stream_advance's gaps form per
+    unit; a silent unit's gaps rows stay too."""
+    with_gaps = valid is not None
+    if (gap_chunk is not None) != with_gaps or (gaps is not None) != with_gaps:
+        raise ValueError("give all of valid, gap_chunk and gaps, or none of them")
     chunk, units, c, n = _fleet_dims(state, chunk, counts, w)
     _stream_buf(pred, torch.float32, units * c * n, "pred")
+    if with_gaps:
+        _stream_buf(valid, torch.uint8, units * c * n, "valid")
+        _stream_buf(gap_chunk, torch.int32, units * 2 * n, "gap_chunk")
+        _stream_buf(gaps, torch.int64, units * 2 * n, "gaps")
     _stream_buf(med_iqr, torch.float64, units * 2 * n, "med_iqr")
     _stream_buf(alarm, torch.int32, units * c, "alarm")
     _stream_buf(top_sensors, torch.int32, units * c * m, "top_sensors")
@@ -1285,9 +1318,44 @@ def fleet_advance(state, chunk, pred, med_iqr, alarm, top_sensors, counts, w: in
         log_len = log_ticks.shape[1]
         _stream_buf(log_ticks, torch.int64, units * log_len, "log_ticks")
         _stream_buf(log_sensors, torch.int32, units * log_len * m, "log_sensors")
-    _lib.call("gdn_fleet_advance", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(med_iqr), _ptr(alarm), _ptr(top_sensors),
-              _ptr(counts), units, c, n, w, m, _ptr(log_ticks) if log_len else None,
-              _ptr(log_sensors) if log_len else None, log_len, _stream())
+    tail = (_ptr(med_iqr), _ptr(alarm), _ptr(top_sensors), _ptr(counts), units, c, n, w, m,
+            _ptr(log_ticks) if log_len else None, _ptr(log_sensors) if log_len else None, log_len)
+    if with_gaps:
+        _lib.call("gdn_fleet_advance_gaps", _ptr(state), _ptr(chunk), _ptr(pred), _ptr(valid), _ptr(gap_chunk), *tail,
+                  _ptr(gaps), _stream())
+    else:
+        _lib.call("gdn_fleet_advance", _ptr(state), _ptr(chunk), _ptr(pred), *tail, _stream())
+
+
+def fleet_events_alloc(units: int, m: int, cap: int, device) -> torch.Tensor:
+    """The events allocation of a fleet: int64 [U, gdn_stream_events_bytes(m, cap) / 8], zero (no tick seen); row u is
+    what stream_events_alloc gives a single stream and stream_events_views reads."""
+    nbytes = _lib.load().gdn_fleet_events_bytes(units, m, cap)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"fleet events: no kernel for units = {units}, m = {m}, cap = {cap} (1 <= units <= 4096, "
+                               "1 <= m <= 8, 0 <= cap <= 2^20)")
+    return torch.zeros((units, nbytes // 8 // units), dtype=torch.int64, device=device)
+
+
+def fleet_events(state, top_scores, top_sensors, threshold, clear, counts, n: int, w: int, on: int, off: int, cap: int,
+                 events):
+    """stream_events per unit in one launch (gdn_fleet_events): the episodes of rows b < counts[u] of top_scores /
+    top_sensors [U, c, m] folded into unit u's row of `events` (fleet_events_alloc), raise level threshold[u], clear
+    level clear[u] (float64 [U], device).  After fleet_score, before fleet_advance.  Reads the states (`n`, `w` place the
+    units' blocks), writes `events` only; a unit with counts[u] == 0 keeps its row byte for byte."""
+    if top_scores.dim() != 3:
+        raise ValueError(f"expected top_scores [U, c, m], got {tuple(top_scores.shape)}")
+    units, c, m = top_scores.shape
+    _stream_buf(state, torch.int64, _fleet_state_words(units, n, w), "state")
+    _stream_buf(counts, torch.int32, units, "counts")
+    _stream_buf(top_scores, torch.float64, units * c * m, "top_scores")
+    _stream_buf(top_sensors, torch.int32, units * c * m, "top_sensors")
+    _stream_buf(threshold, torch.float64, units, "threshold")
+    _stream_buf(clear, torch.float64, units, "clear")
+    _stream_buf(events, torch.int64, max(1, _lib.load().gdn_fleet_events_bytes(units, m, cap) // 8), "events")
+    _lib.call("gdn_fleet_events", _ptr(state), _ptr(top_scores), _ptr(top_sensors), _ptr(threshold), _ptr(clear),
+              _ptr(counts), units, c, n, w, m, int(on), int(off), int(cap), _ptr(events), _stream())
+    return events
 
 
 # --------------------------------------------------------------------------- raw readings

@@ -1106,6 +1106,47 @@ int gdn_fleet_score(const void* state, const float* pred, const float* chunk, co
 int gdn_fleet_advance(void* state, const float* chunk, const float* pred, const double* med_iqr, const int32_t* alarm,
                       const int32_t* top_sensors, const int32_t* counts, int units, int c, int n, int w, int m,
                       int64_t* log_ticks, int32_t* log_sensors, long long log_len, void* stream);
+/* Missing readings and alarm episodes per unit (opt-in; additive entry points, the ABI version does not
+ * move).  Both are the single stream's options ("Missing readings", "Alarm episodes" above) per unit, with counts [U] on
+ * the device in the place of `count`, so the one captured graph still serves full, short and silent units.  New tensors:
+ *   raw_chunk, filled_chunk [U, c, n] fp32   valid [U, c, n] uint8   gap_chunk [U, 2, n] int32   gaps [U, 2, n] int64
+ *   clear [U] float64   events: gdn_fleet_events_bytes(units, m, E) = units * gdn_stream_events_bytes(m, E) bytes, unit
+ *   u's block (a single stream's events allocation, zero before the first push) at u * gdn_stream_events_bytes(m, E).
+ * A push is, in stream order: gdn_fleet_fill, gdn_fleet_windows on the filled chunk, the forward, gdn_fleet_score_gaps,
+ * [gdn_fleet_events,] gdn_fleet_advance_gaps; gdn_fleet_events also sits between the plain score and advance launches.
+ *   gdn_fleet_fill          grid (sensor group of 64, unit): gdn_stream_fill on unit u's rows with count = counts[u]
+ *                           clamped to 0 .. c; the hold value before the unit's first real reading is its own
+ *                           hist[i, w - 1].  Rows at or beyond counts[u] are neither read nor written (a non-finite
+ *                           value there is not a missing reading); a unit with count 0 writes nothing, gap_chunk
+ *                           included.  The workgroup has 1, 4 or 16 waves by c alone (c <= 8, c <= 32, else), never by
+ *                           counts; integer counts and "the right-most real reading wins", so every shape writes the
+ *                           same bits.  Reads the states, writes none.  filled_chunk must not alias raw_chunk.
+ *   gdn_fleet_score_gaps    gdn_fleet_score with `chunk` = the filled chunk and its validity plane: per unit
+ *                           gdn_stream_score_gaps.
+ *   gdn_fleet_advance_gaps  gdn_fleet_advance with `chunk` = the filled chunk: per unit gdn_stream_advance_gaps on the
+ *                           unit's slices of valid, gap_chunk and gaps.  The only writer of the states, the logs and
+ *                           `gaps`; counts[u] == 0 leaves unit u's state, log and gaps rows untouched.
+ *   gdn_fleet_events        workgroup u: gdn_stream_events on unit u's rows of top_scores / top_sensors [U, c, m] with
+ *                           hi = threshold[u], lo = clear[u], first_tick from unit u's state block and count =
+ *                           counts[u] clamped; counts[u] == 0 leaves the unit's events block byte for byte.  After the
+ *                           score launch, before the advance launch (it reads the units' tick counters).  The tile is
+ *                           256, 1024 or 4096 ticks by c alone; comparisons and copies only, so every tile writes the
+ *                           same bits.  Reads the states; writes only `events`.
+ * Refusals, all before any launch: a null pointer: GDN_ERR_ARG; the limits of the fleet entry points above (units * c,
+ * n, w, m) and of gdn_stream_events (on, off, E): GDN_ERR_UNSUPPORTED (gdn_fleet_events_bytes: 0; units <= 4096).      */
+int gdn_fleet_fill(const void* state, const float* raw_chunk, const int32_t* counts, int units, int c, int n, int w,
+                   float* filled_chunk, uint8_t* valid, int32_t* gap_chunk, void* stream);
+int gdn_fleet_score_gaps(const void* state, const float* pred, const float* chunk, const uint8_t* valid,
+                         const double* med_iqr, const double* threshold, const int32_t* counts, int units, int c, int n,
+                         int w, int m, double* top_scores, int32_t* top_sensors, int32_t* alarm, void* stream);
+int gdn_fleet_advance_gaps(void* state, const float* chunk, const float* pred, const uint8_t* valid,
+                           const int32_t* gap_chunk, const double* med_iqr, const int32_t* alarm,
+                           const int32_t* top_sensors, const int32_t* counts, int units, int c, int n, int w, int m,
+                           int64_t* log_ticks, int32_t* log_sensors, long long log_len, int64_t* gaps, void* stream);
+long long gdn_fleet_events_bytes(int units, int m, long long E);
+int gdn_fleet_events(const void* state, const double* top_scores, const int32_t* top_sensors, const double* threshold,
+                     const double* clear, const int32_t* counts, int units, int c, int n, int w, int m, int on, int off,
+                     long long E, void* events, void* stream);
 
 #ifdef __cplusplus
 }
