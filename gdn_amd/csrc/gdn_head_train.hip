@@ -588,7 +588,12 @@ __global__ __launch_bounds__(256) void gdn_head_train_kernel(const HeadArgs a) {
 
 // gdn_head_train_kernel's passes at a run-time width (ANY: d = dd_arg, 1..256, gdn_any_width.hip's widths) on the
 // padded width D: global rows, the accumulator blocks and the LDS column tables are laid out at dd, lane groups at D.
-// The four tile widths keep gdn_head_train_kernel above, source and all (its code and bits stay as they were).
+// The four tile widths keep gdn_head_train_kernel above, source and all.  Running them on this body with ANY = false
+// was tried: same LDS, scratch and occupancy, level speed, but not the same bits.  In the kernel above
+// the vectorizer packs only half of H_BWD1's fourth unrolled window, which leaves its dy2 - m2a - x2h * m2b as a
+// multiply and two subtractions; inlined from here all four windows contract to fused multiply-adds.  d_bn1_*, d_emb
+// and d_z then move in the last bits and tests/test_gpu_z_consistency.py's graph-against-eager epochs drift past
+// their bound.  A fix made to one copy has to be made to the other until that expression is pinned in the source.
 template <int D, int MODE, bool ANY>
 __device__ __forceinline__ void head_train_body(const HeadArgs& a, int dd_arg) {
   using G = HG<D>;
@@ -1019,46 +1024,50 @@ int head_parts(int batch, int chunks, int mode) {
   return parts < 1 ? 1 : parts;
 }
 
-template <int D, int MODE>
-void launch_pass(HeadArgs a, hipStream_t st) {
-  a.chunks = (a.n + HG<D>::SLOTS - 1) / HG<D>::SLOTS;
-  a.parts = head_parts(a.batch, a.chunks, MODE);
-  hipLaunchKernelGGL((gdn_head_train_kernel<D, MODE>), dim3(a.chunks * a.parts), dim3(256), 0, st, a);
+// sensor chunks of a pass on the (padded) width dp: HG<dp>::SLOTS sensors each
+int head_chunks(int n, int dp) {
+  const int slots = 256 / (dp / 4);
+  return (n + slots - 1) / slots;
 }
 
-template <int DP, int MODE>
-void launch_pass_any(HeadArgs a, int d, hipStream_t st) {
-  a.chunks = (a.n + HG<DP>::SLOTS - 1) / HG<DP>::SLOTS;
+template <int DP, bool ANY, int MODE>
+void launch_pass(HeadArgs a, int d, hipStream_t st) {
+  a.chunks = head_chunks(a.n, DP);
   a.parts = head_parts(a.batch, a.chunks, MODE);
-  hipLaunchKernelGGL((gdn_any_head_train_kernel<DP, MODE>), dim3(a.chunks * a.parts), dim3(256), 0, st, a, d);
+  if constexpr (ANY)
+    hipLaunchKernelGGL((gdn_any_head_train_kernel<DP, MODE>), dim3(a.chunks * a.parts), dim3(256), 0, st, a, d);
+  else
+    hipLaunchKernelGGL((gdn_head_train_kernel<DP, MODE>), dim3(a.chunks * a.parts), dim3(256), 0, st, a);
 }
 
-// the three forward (FWD) or backward passes at a gdn_any_width.hip width; returns the chunk count of the passes
-template <bool FWD>
-int head_passes_any(const HeadArgs& a, int d, hipStream_t st) {
-  const int dp = d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : d <= 128 ? 128 : 256;
-#define GDN_HEAD_ANY(DP)                                                                        \
-  case DP:                                                                                      \
-    if (FWD) {                                                                                  \
-      launch_pass_any<DP, H_STAT1>(a, d, st);                                                   \
-      launch_pass_any<DP, H_STAT2>(a, d, st);                                                   \
-      launch_pass_any<DP, H_OUT>(a, d, st);                                                     \
-    } else {                                                                                    \
-      launch_pass_any<DP, H_BWD2>(a, d, st);                                                    \
-      launch_pass_any<DP, H_BWD1>(a, d, st);                                                    \
-      launch_pass_any<DP, H_DZ>(a, d, st);                                                      \
-    }                                                                                           \
-    return (a.n + HG<DP>::SLOTS - 1) / HG<DP>::SLOTS;
-  switch (dp) {
-    GDN_HEAD_ANY(16)
-    GDN_HEAD_ANY(32)
-    GDN_HEAD_ANY(64)
-    GDN_HEAD_ANY(128)
-    GDN_HEAD_ANY(256)
+template <int DP, bool ANY>
+int launch_passes(const HeadArgs& a, int d, bool fwd, hipStream_t st) {
+  if (fwd) {
+    launch_pass<DP, ANY, H_STAT1>(a, d, st);
+    launch_pass<DP, ANY, H_STAT2>(a, d, st);
+    launch_pass<DP, ANY, H_OUT>(a, d, st);
+  } else {
+    launch_pass<DP, ANY, H_BWD2>(a, d, st);
+    launch_pass<DP, ANY, H_BWD1>(a, d, st);
+    launch_pass<DP, ANY, H_DZ>(a, d, st);
   }
-#undef GDN_HEAD_ANY
-  return 0;
+  return head_chunks(a.n, DP);
 }
+
+// The three forward (fwd) or backward passes at width d: a tile width runs gdn_head_train_kernel<d>, any other
+// width of 1..256 gdn_any_head_train_kernel on the padded width.  Returns the chunk count of the passes (the finish
+// launch derives the parts of the embedding-gradient pass from it), 0 for a width outside both.
+int head_passes(const HeadArgs& a, int d, bool fwd, hipStream_t st) {
+  const bool any = gdn_any_width(d);
+  switch (d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : d <= 128 ? 128 : 256) {
+    case 16: return any ? launch_passes<16, true>(a, d, fwd, st) : d == 16 ? launch_passes<16, false>(a, d, fwd, st) : 0;
+    case 32: return any ? launch_passes<32, true>(a, d, fwd, st) : launch_passes<32, false>(a, d, fwd, st);
+    case 64: return any ? launch_passes<64, true>(a, d, fwd, st) : launch_passes<64, false>(a, d, fwd, st);
+    case 128: return any ? launch_passes<128, true>(a, d, fwd, st) : launch_passes<128, false>(a, d, fwd, st);
+    default: return any ? launch_passes<256, true>(a, d, fwd, st) : 0;
+  }
+}
+
 
 // loss = mean((out - y)^2) and its gradient d_out = 2 (out - y) / count in one launch (train.py:20-23
 // `F.mse_loss(..., reduction='mean')` + the first step of loss.backward()).  Per-workgroup fp64 partial
@@ -1251,8 +1260,7 @@ static int head_train_fwd_impl(const float* z, const float* emb, const float* bn
   if (!z || !emb || !bn1_w || !bn1_b || !bn2_w || !bn2_b || !stats) return GDN_ERR_ARG;
   if (act ? (lin_w || lin_b || out) : (!lin_w || !lin_b || !out)) return GDN_ERR_ARG;
   if (!head_shape_ok(batch, n, d)) return GDN_ERR_ARG;   // torch: "Expected more than 1 value per channel"
-  const bool any = gdn_any_width(d);                      // other widths: run-time d (head_train_body<.., true>)
-  if (!any && d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
+  if (!gdn_any_width(d) && d != 16 && d != 32 && d != 64 && d != 128) return GDN_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   HeadArgs a = {};
   a.z = z; a.emb = emb; a.g1 = bn1_w; a.b1 = bn1_b; a.g2 = bn2_w; a.b2 = bn2_b; a.w = lin_w; a.bo = lin_b;
@@ -1266,23 +1274,7 @@ static int head_train_fwd_impl(const float* z, const float* emb, const float* bn
   a.run = {running_mean1, running_var1, running_mean2, running_var2, batches1, batches2, momentum1, momentum2};
   if (!zeroed && hipMemsetAsync(stats, 0, fx_block_words(4, d) * sizeof(double), st) != hipSuccess)
     return GDN_ERR_LAUNCH;
-  if (any) {
-    head_passes_any<true>(a, d, st);
-    return gdn_launch_status();
-  }
-#define GDN_HEAD_F(DD)                 \
-  case DD:                             \
-    launch_pass<DD, H_STAT1>(a, st);   \
-    launch_pass<DD, H_STAT2>(a, st);   \
-    launch_pass<DD, H_OUT>(a, st);     \
-    break;
-  switch (d) {
-    GDN_HEAD_F(16)
-    GDN_HEAD_F(32)
-    GDN_HEAD_F(64)
-    GDN_HEAD_F(128)
-  }
-#undef GDN_HEAD_F
+  head_passes(a, d, true, st);
   return gdn_launch_status();
 }
 
@@ -1341,34 +1333,12 @@ static int head_train_bwd_impl(const float* d_out, const float* z, const float* 
   const size_t sums_bytes = fx_block_words(6, d) * sizeof(double);
   a.demb_part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + sums_bytes);
   if (!zeroed && hipMemsetAsync(workspace, 0, sums_bytes, st) != hipSuccess) return GDN_ERR_LAUNCH;
-  if (any) {
-    const int chunks = head_passes_any<false>(a, d, st);
-    if (defer_finish) return gdn_launch_status();
-    const int total = n * d > d ? n * d : d;
-    hipLaunchKernelGGL(gdn_any_head_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, st, workspace,
-                       a.demb_part, head_parts(batch, chunks, H_BWD1), n, d, d_bn1_w, d_bn1_b, d_bn2_w, d_bn2_b,
-                       d_lin_w, d_lin_b, d_emb, zeroed ? const_cast<double*>(stats) : nullptr);
-    return gdn_launch_status();
-  }
-#define GDN_HEAD_B(DD)                \
-  case DD:                            \
-    launch_pass<DD, H_BWD2>(a, st);   \
-    launch_pass<DD, H_BWD1>(a, st);   \
-    launch_pass<DD, H_DZ>(a, st);     \
-    break;
-  switch (d) {
-    GDN_HEAD_B(16)
-    GDN_HEAD_B(32)
-    GDN_HEAD_B(64)
-    GDN_HEAD_B(128)
-  }
-#undef GDN_HEAD_B
+  const int chunks = head_passes(a, d, false, st);
   if (defer_finish) return gdn_launch_status();     // the caller runs gdn_train_finish after its project backward
   const int total = n * d > d ? n * d : d;
-  const int chunks = (n + 256 / (d / 4) - 1) / (256 / (d / 4));
-  hipLaunchKernelGGL(gdn_head_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, st, workspace,
-                     a.demb_part, head_parts(batch, chunks, H_BWD1), n, d, d_bn1_w, d_bn1_b, d_bn2_w, d_bn2_b, d_lin_w, d_lin_b, d_emb,
-                     zeroed ? const_cast<double*>(stats) : nullptr);
+  hipLaunchKernelGGL(any ? gdn_any_head_finish_kernel : gdn_head_finish_kernel, dim3((total + 255) / 256), dim3(256),
+                     0, st, workspace, a.demb_part, head_parts(batch, chunks, H_BWD1), n, d, d_bn1_w, d_bn1_b, d_bn2_w,
+                     d_bn2_b, d_lin_w, d_lin_b, d_emb, zeroed ? const_cast<double*>(stats) : nullptr);
   return gdn_launch_status();
 }
 
@@ -1464,7 +1434,7 @@ extern "C" int gdn_train_finish(double* head_workspace, double* stats, int head_
   if (w > GDN_MAX_W) return GDN_ERR_UNSUPPORTED;   // (long windows' partial blocks: gdn_project_bwd reduces them)
   TailArgs t = {};
   const size_t sums_bytes = fx_block_words(6, d) * sizeof(double);
-  const int chunks = (n + 256 / (d / 4) - 1) / (256 / (d / 4));
+  const int chunks = head_chunks(n, d);
   const int total = n * d > d ? n * d : d;
   t.head_ws = head_workspace;
   t.demb_part = reinterpret_cast<const float*>(reinterpret_cast<const char*>(head_workspace) + sums_bytes);
