@@ -41,7 +41,8 @@
 //      IS the B operand of the projection in k order "element j of half h = w 16wk + 8(j>>2) + 4h + (j&3)";
 //      w <= 16 (DCfg::XHALF): 2 passes (ahi, alo) x 8 k-steps = 16 products instead of 24, 4 ds_read_b128 less per
 //      pass pair and k-step: product rows 16 .. 31, which no window column fills, carry the lo term of X^T and are
-//      added to rows 0 .. 15 (accumulator registers 8 + j to j) in front of P1;
+//      added to rows 0 .. 15 (accumulator registers 8 + j to j) in front of P1; the two passes multiply the SAME
+//      X^T fragment, which DCfg::XKEEP k-steps keep in registers from the first to the second;
 //   P1 out^T[c, target] = lin' . Zx + C (C-in from the table block), the layout E consumes.
 // With bf16 storage the projected tile must be rounded to bf16 as the staged path stores it: that order stays.
 #include "gdn_common.hpp"
@@ -114,6 +115,14 @@ __device__ __forceinline__ float relu_acc(float v) {
   return fmaxf(v, 0.f);
 #endif
 }
+
+// [r27] DCfg::XKEEP / DCfg::BLDS: -1 = the table in DCfg, otherwise forced for every instantiation of the family
+#ifndef GDN_XKEEP
+#define GDN_XKEEP -1
+#endif
+#ifndef GDN_BL_LDS
+#define GDN_BL_LDS -1
+#endif
 
 enum { FMT_F16 = 0, FMT_BF16 = 1 };
 #define GDN_LOG2E 1.44269504088896340736f
@@ -303,7 +312,21 @@ struct DCfg {
   static constexpr int OFF_EC = OFF_SJ + ROWS * 4;     // epilogue column constants: 4 tables of 32 DC floats
   static constexpr int OFF_CS = OFF_EC + 4 * 32 * DC * 4;   // C-in of the scalar tile: [c_i | c_j | zeros][ROWS]
   static constexpr int CS_WORDS = XAGG ? 0 : 3 * ROWS;      // (XAGG: no scalar tile, c_i / c_j are LaneConsts::sadd)
-  static constexpr int LDS = OFF_CS + CS_WORDS * 4;
+  // [r27] M of the w <= 16 kernel (XHALF) reads the SAME X^T fragment in its ahi and in its alo pass.  XKEEP k-steps
+  // keep theirs in registers from the first pass to the second: 4 registers and one ds_read_b128 less per wave and
+  // window each.  BLDS pays for them where they do not fit: lin', the A operand of P1 (LaneConsts::bl, 4 DC NTL
+  // registers, the same for every wave and every window), waits in LDS behind the table block and is read in front
+  // of P1 (DC NTL reads), when the kept fragments are dead.  Only the family built for three workgroups per CU and
+  // its NT = 1, 2 siblings (DC = 2, SL <= 16), chosen by compiling (profiles/r27_xkeep_kernel_resources.txt: the
+  // fewest reads with no scratch and three waves per SIMD): short lists keep every fragment; SL = 16 keeps all 8 at
+  // NT = 4 with lin' in LDS (-8 + 4 reads) and 2 below (lin' in LDS would return what 4 or 6 kept fragments save).
+  // GDN_XKEEP / GDN_BL_LDS override both for A/B builds (tools/_diag/build_variant.sh).  DESIGN 3.1 [r27]
+  static constexpr bool XKFAM = XHALF && DC == 2 && SL <= 16;
+  static constexpr int XKEEP_TABLE = SL <= 8 || NT == 4 ? KS : 2;
+  static constexpr int XKEEP = !XKFAM ? 0 : GDN_XKEEP < 0 ? XKEEP_TABLE : GDN_XKEEP < KS ? GDN_XKEEP : KS;
+  static constexpr bool BLDS = XKFAM && (GDN_BL_LDS < 0 ? SL > 8 && NT == 4 : GDN_BL_LDS != 0);
+  static constexpr int OFF_BL = OFF_CS + CS_WORDS * 4;  // BLDS: [DC][WK][NTL] fragments of 64 lanes x 16 B
+  static constexpr int LDS = OFF_BL + (BLDS ? DC * WK * NTL * 1024 : 0);
   // x staging (see the kernel): a thread owns column tid % CW of XU rows.  XAGG: its values 8q .. 8q+7 are one
   // operand slot of X^T, slot tid / CW + q RS = 2 (k-step) + (lane half), in the k order of pos_of_source
   static constexpr int CW = 16 * WK, RS = THREADS / CW;
@@ -841,6 +864,17 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
     compute_lane_consts(a, k);     // (no plan, no x limit: the range guard is a feature of planned launches)
     compute_tables<NT, DC, FMT>(a, reinterpret_cast<float*>(smem + C::OFF_EC));
   }
+  if constexpr (C::BLDS) {   // lin' to LDS (wave 0: the operand does not depend on the wave); visible after the barrier below
+    if (wv == 0) {
+#pragma unroll
+      for (int cb = 0; cb < DC; ++cb)
+#pragma unroll
+        for (int wk = 0; wk < WK; ++wk)
+#pragma unroll
+          for (int t = 0; t < C::NTL; ++t)
+            *reinterpret_cast<u32x4*>(smem + C::OFF_BL + (((cb * WK + wk) * C::NTL + t) << 10) + lane * 16) = k.bl[cb][wk][t];
+    }
+  }
   // out-of-range lanes, as a wave-uniform mask in scalar registers (the bf16-storage and long-window variants sit
   // AT their 256-VGPR budget: a per-lane flag cost 20 more spilled registers and 9 % of the launch)
   unsigned long long out_of_range = 0ull;
@@ -1039,7 +1073,17 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
     // read it as operands, scatter the lo term over the same positions, read again — no barrier.
     // Operand reads run one k-step ahead of the products (two named fragment sets).
     float ygt = 0.f;                                  // issued here, consumed after the products
-    if (a.keys && h == 0 && tgt < n) ygt = a.key_gt[(size_t)b * n + tgt];
+    // [r27] XKEEP: the three per-lane global addresses of a target (ground truth, out, keys) are rebuilt per window
+    // from its index, which an EMPTY asm hides from the loop-invariant hoisting, instead of living in three register
+    // pairs across the whole loop, and ygt waits as the float it was loaded as (its float64 form was computed ahead
+    // of M): five registers for the kept fragments.  Same values, same stores.
+    unsigned tg = (unsigned)tgt;
+    if constexpr (C::XKEEP > 0) {
+      asm("" : "+v"(tg));
+      if (a.keys && h == 0 && tgt < n) ygt = (a.key_gt + (size_t)b * n)[tg];
+    } else {
+      if (a.keys && h == 0 && tgt < n) ygt = a.key_gt[(size_t)b * n + tgt];
+    }
     constexpr int MCB = C::MCB;                         // XAGG: one block, Zx^T[w, target]
     f32x16 acc2[MCB];
 #pragma unroll
@@ -1058,22 +1102,25 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
       // neighbour's hi fragment (which would put a second Xhi.alo into the rows that are folded) or a fold between
       // the passes (VALU work inside the accumulator chain): no register, no instruction, and Xlo.alo is the fourth
       // term of (Xhi + Xlo)(ahi + alo), 2^-22 of the product, which the three-product form left out.
-      u32x4 fa[2], fx[2];
-      auto fetch = [&](int ks, int buf) {
+      // [r27] the fragment of k-step ks < XKEEP is read in the first pass only and stays in fk[ks] for the second
+      // (the scatter between the passes writes the alpha image, never the fragment area)
+      u32x4 fa[2], fx[2], fk[C::XKEEP > 0 ? C::XKEEP : 1];
+      auto fetch = [&](int ks, int buf, int pass) {
         fa[buf] = lds_frag(smem, arow_off + ks * 32);
-        fx[buf] = lds_frag(smem, xf_half + ks * XF_KS);
+        if (ks >= C::XKEEP) fx[buf] = lds_frag(smem, xf_half + ks * XF_KS);
+        else if (pass == 0) fk[ks] = lds_frag(smem, xf_half + ks * XF_KS);
       };
 #pragma unroll
       for (int pass = 0; pass < 2; ++pass) {
         scatter_terms<SL>(smem, k.scoff, pass == 0 ? ph : pl);
         __builtin_amdgcn_sched_barrier(0);
-        fetch(0, 0);
+        fetch(0, 0, pass);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
-          if (ks + 1 < C::KS) fetch(ks + 1, (ks + 1) & 1);
+          if (ks + 1 < C::KS) fetch(ks + 1, (ks + 1) & 1, pass);
           __builtin_amdgcn_sched_barrier(0);
-          acc2[0] = F::mfma(fx[ks & 1], fa[ks & 1], acc2[0]);
+          acc2[0] = F::mfma(ks < C::XKEEP ? fk[ks < C::XKEEP ? ks : 0] : fx[ks & 1], fa[ks & 1], acc2[0]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -1128,6 +1175,21 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
     f32x16 acc3[DC];
     if constexpr (C::XAGG) {
       __builtin_amdgcn_s_setprio(GDN_PRIO_P1);
+      // BLDS: lin' from LDS (contiguous ds_read_b128, conflict free), under the tail of M's accumulator chain
+      u32x4 blr[C::BLDS ? DC : 1][WK][C::NTL];
+      if constexpr (C::BLDS) {
+#pragma unroll
+        for (int cb = 0; cb < DC; ++cb)
+#pragma unroll
+          for (int wk = 0; wk < WK; ++wk)
+#pragma unroll
+            for (int t = 0; t < C::NTL; ++t)
+              blr[cb][wk][t] = lds_frag(smem, C::OFF_BL + (((cb * WK + wk) * C::NTL + t) << 10) + lane * 16);
+      }
+      auto lin = [&](int cb, int wk, int t) -> const u32x4& {
+        if constexpr (C::BLDS) return blr[cb][wk][t];
+        else return k.bl[cb][wk][t];
+      };
 #pragma unroll
       for (int cb = 0; cb < DC; ++cb)
 #pragma unroll
@@ -1155,7 +1217,7 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
           for (int tl = 0; tl < C::NTL; ++tl)
             if (tz + tl < 2) {
 #pragma unroll
-              for (int cb = 0; cb < DC; ++cb) acc3[cb] = F::mfma(k.bl[cb][wk][tl], zf[tz], acc3[cb]);
+              for (int cb = 0; cb < DC; ++cb) acc3[cb] = F::mfma(lin(cb, wk, tl), zf[tz], acc3[cb]);
             }
       }
     } else {
@@ -1201,8 +1263,14 @@ __global__ __launch_bounds__(64 * NT, (DCfg<NT, DC, WK, SL, FMT>::WGS)) GDN_FUSE
     part += __shfl_xor(part, 32);
     if (h == 0 && tgt < n) {
       const float o = part + k.out_b;
-      a.out[(size_t)b * n + tgt] = o;
-      if (a.keys) a.keys[(size_t)tgt * a.key_pitch + b] = fabs((double)o - (double)ygt);
+      if constexpr (C::XKEEP > 0) {
+        asm("" : "+v"(ygt));
+        (a.out + (size_t)b * n)[tg] = o;
+        if (a.keys) (a.keys + b)[(size_t)tg * (unsigned)a.key_pitch] = fabs((double)o - (double)ygt);
+      } else {
+        a.out[(size_t)b * n + tgt] = o;
+        if (a.keys) a.keys[(size_t)tgt * a.key_pitch + b] = fabs((double)o - (double)ygt);
+      }
     }
     if (b == (int)blockIdx.x) { GDN_STAMP(10) }
   }
