@@ -150,6 +150,11 @@ SIGNATURES = {
     "gdn_fleet_advance_gaps": [_p] * 9 + [_c_int] * 5 + [_p, _p, ctypes.c_longlong, _p, _p],
     "gdn_fleet_events_bytes": [_c_int, _c_int, ctypes.c_longlong],
     "gdn_fleet_events": [_p] * 6 + [_c_int] * 7 + [ctypes.c_longlong, _p, _p],
+    "gdn_fleet_calib_bytes": [_c_int] * 3,
+    "gdn_fleet_calib_write": [_p] * 5 + [_c_int] * 6 + [_p] * 3,
+    "gdn_fleet_calib_write_gaps": [_p] * 6 + [_c_int] * 6 + [_p] * 3,
+    "gdn_fleet_calib_write_sensor": [_p] * 6 + [_c_int] * 6 + [_p] * 3,
+    "gdn_fleet_ring_counts": [_p, _p, _c_int, _c_int, _c_int, _p, _p, _p],
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

@@ -9,6 +9,9 @@
 // Missing readings (opt-in): gdn_fleet_fill leads the push and the score / advance kernels have a GAPS
 // instantiation each, per unit the single stream's; the plain instantiations never read the trailing parameters.  (The
 // episodes launch of a fleet, gdn_fleet_events, lives with the tile code in gdn_events.hip.)
+// Rolling calibration (opt-in): gdn_fleet_calib_write* sits between the score and the advance launch and
+// writes a single stream's calibration ring per unit; gdn_fleet_ring_counts turns the keep flags into the per-row
+// counts of gdn_score_select_counts, so a fleet recalibrates with no host read.
 // Plain copy, sweep and scan kernels: no inline assembly, no floating-point atomics, no workgroup waits on another.
 #include "gdn_stream_steps.hpp"
 
@@ -124,6 +127,181 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_fleet_advance_kernel(
   stream_carry_log<GAPS>(st, chunk + row0 * n, pred + row0 * n, med_iqr + (size_t)u * 2 * n, alarm + row0,
                          top_sensors + row0 * m, count, n, m, log_ticks + (size_t)u * log_len,
                          log_sensors + (size_t)u * log_len * m, log_len, threadIdx.x, vu, gu, au);
+}
+
+// The calibration rings of a fleet (include/gdn_hip.h "Rolling calibration of a fleet"): ring_keys [U, n, R] float64,
+// ring_keep [U, R] uint8, unit u's slices a single stream's ring.  Row b < counts[u] of unit u is that unit's stream
+// tick ticks_u + b and owns slot (ticks_u + b) mod R of the unit's ring; the keep rules and the key arithmetic are
+// those of gdn_stream_calib_write / _gaps / _sensor (gdn_stream.hip), which the three MODEs restate per unit:
+//   PLAIN   a tick is kept unless it alarmed under exclude_alarms; a tick not kept writes the filler and keep = 0;
+//   GAPS    ... or unless a reading of it was missing (valid);
+//   SENSOR  keep = the alarm rule alone; the key of a missing reading is the filler, the tick's others are real.
+// Reads the states, writes the rings only; a unit with counts[u] == 0 has no byte of its ring touched.
+enum { CALIB_PLAIN = 0, CALIB_GAPS = 1, CALIB_SENSOR = 2 };
+#define GDN_FLEET_CALIB_TILE_C 64    // from this many rows per unit on, the transposing tile form
+
+struct FleetRing {
+  const float *pred, *chunk;
+  const int* alarm;
+  const unsigned char* valid;
+  double* keys;
+  unsigned char* keep;
+  unsigned base;
+};
+__device__ __forceinline__ FleetRing fleet_ring(const void* state, const float* pred, const float* chunk,
+                                                const int* alarm, const unsigned char* valid, int u, int c, int n,
+                                                int w, int R, double* ring_keys, unsigned char* ring_keep) {
+  const size_t row0 = (size_t)u * c;
+  const long long ticks = reinterpret_cast<const long long*>(fleet_state(state, u, n, w))[0];
+  return FleetRing{pred + row0 * n, chunk + row0 * n, alarm + row0, valid ? valid + row0 * n : nullptr,
+                   ring_keys + (size_t)u * n * R, ring_keep + (size_t)u * R, (unsigned)(ticks % (long long)R)};
+}
+// does tick b of the unit count?  All 64 lanes of a wave call it (GAPS: an __all over the row's validity bytes).
+template <int MODE>
+__device__ __forceinline__ bool fleet_ring_keep(const FleetRing& fr, int b, int n, int exclude_alarms, int lane) {
+  bool keep = !(exclude_alarms && fr.alarm[b] != 0);
+  if constexpr (MODE == CALIB_GAPS) {
+    bool real = true;
+    for (int s0 = 0; s0 < n; s0 += 64) {
+      const int s = s0 + lane;
+      real = real && (s >= n || fr.valid[(size_t)b * n + s] != 0);
+    }
+    keep = keep && __all(real);
+  }
+  return keep;
+}
+template <int MODE>
+__device__ __forceinline__ double fleet_ring_key(const FleetRing& fr, size_t o, bool keep) {
+  if constexpr (MODE == CALIB_SENSOR) keep = keep && fr.valid[o] != 0;
+  const double e = score_key(fr.pred[o], fr.chunk[o]);
+  return keep ? e : filler_key();
+}
+
+// The direct form (small c): one wave per (unit, row), lanes along the sensors, every lane stores its key at
+// ring_keys[u][s][slot].  8-byte stores at stride 8 R: as uncoalesced as the tile form's at c of 1 to a few rows (one
+// slot per sensor row either way), but every lane of the wave carries one, and there is no LDS and no barrier.
+template <int MODE>
+__global__ __launch_bounds__(256) void gdn_fleet_calib_direct_kernel(
+    const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ chunk,
+    const int* __restrict__ alarm, const unsigned char* __restrict__ valid, const int* __restrict__ counts, int units,
+    int c, int n, int w, int R, int exclude_alarms, double* __restrict__ ring_keys,
+    unsigned char* __restrict__ ring_keep) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int at = blockIdx.x * (blockDim.x >> 6) + wv;        // (wave uniform) <= 4096 + 3
+  const int u = at / c, b = at - u * c;
+  if (u >= units || b >= fleet_count(counts, u, c)) return;
+  const FleetRing fr = fleet_ring(state, pred, chunk, alarm, valid, u, c, n, w, R, ring_keys, ring_keep);
+  const unsigned slot = calib_slot(fr.base, b, R);
+  const bool keep = fleet_ring_keep<MODE>(fr, b, n, exclude_alarms, lane);
+  if (lane == 0) fr.keep[slot] = keep ? 1 : 0;
+  for (int s = lane; s < n; s += 64)
+    fr.keys[(size_t)s * R + slot] = fleet_ring_key<MODE>(fr, (size_t)b * n + s, keep);
+}
+
+// The tile form, workgroup (row tile g, unit): the single stream's workgroup g on unit u's rows with count = counts[u]
+// — 64 rows x 64 sensors transposed through the padded LDS tile, fp32 reads along sensors, fp64 writes along slots.
+template <int MODE>
+__global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_fleet_calib_tile_kernel(
+    const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ chunk,
+    const int* __restrict__ alarm, const unsigned char* __restrict__ valid, const int* __restrict__ counts, int c,
+    int n, int w, int R, int exclude_alarms, double* __restrict__ ring_keys, unsigned char* __restrict__ ring_keep) {
+  __shared__ double tile[64][65];
+  __shared__ int keep_row[64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int u = blockIdx.y, b0 = blockIdx.x * 64;
+  const int count = fleet_count(counts, u, c);
+  if (b0 >= count) return;                                   // (workgroup uniform, ahead of every barrier)
+  const FleetRing fr = fleet_ring(state, pred, chunk, alarm, valid, u, c, n, w, R, ring_keys, ring_keep);
+  for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {   // wave wv owns rows wv, wv + 4, ..: (wave uniform)
+    const int b = b0 + r;
+    if (b >= count) break;
+    const bool keep = fleet_ring_keep<MODE>(fr, b, n, exclude_alarms, lane);
+    if (lane == 0) {
+      keep_row[r] = keep ? 1 : 0;
+      fr.keep[calib_slot(fr.base, b, R)] = keep ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  for (int s0 = 0; s0 < n; s0 += 64) {
+    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
+      const int b = b0 + r, s = s0 + lane;
+      if (b < count && s < n) tile[r][lane] = fleet_ring_key<MODE>(fr, (size_t)b * n + s, keep_row[r] != 0);
+    }
+    __syncthreads();
+    const int b = b0 + lane;                                 // now the lane runs along the push's rows = ring slots
+    if (b < count) {
+      const unsigned slot = calib_slot(fr.base, b, R);
+      for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
+        const int s = s0 + r;
+        if (s < n) fr.keys[(size_t)s * R + slot] = tile[lane][r];
+      }
+    }
+    __syncthreads();                                         // the tile is rewritten by the next sensor tile
+  }
+}
+
+// Workgroup u, tick mode: kept[u] = the sum of unit u's keep flags (integer adds: any order gives the same number),
+// broadcast into counts[u n .. u n + n).  A unit with select[u] == 0 gets counts 0 and keeps kept[u].
+__global__ __launch_bounds__(256) void gdn_fleet_ring_counts_kernel(
+    const unsigned char* __restrict__ ring_keep, const unsigned char* __restrict__ select, int n, int R,
+    int* __restrict__ counts, int* __restrict__ kept) {
+  __shared__ int wave_sum[4];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  int* __restrict__ cu = counts + (size_t)u * n;
+  if (select && select[u] == 0) {                            // (workgroup uniform, ahead of the barrier)
+    for (int s = tid; s < n; s += 256) cu[s] = 0;
+    return;
+  }
+  const unsigned char* __restrict__ ku = ring_keep + (size_t)u * R;
+  int sum = 0;
+  for (int i = tid; i < R; i += 256) sum += ku[i] != 0 ? 1 : 0;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+  if ((tid & 63) == 0) wave_sum[tid >> 6] = sum;
+  __syncthreads();
+  const int total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+  for (int s = tid; s < n; s += 256) cu[s] = total;
+  if (tid == 0) kept[u] = total;
+}
+
+// Sensor mode: counts [U n] is gdn_score_key_counts' over the rings; the rows of a unit with select[u] == 0 become 0.
+__global__ __launch_bounds__(256) void gdn_fleet_counts_mask_kernel(const unsigned char* __restrict__ select, int n,
+                                                                    long long rows, int* __restrict__ counts) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < rows && select[i / n] == 0) counts[i] = 0;
+}
+
+// diagnostic knob: GDN_FLEET_CALIB_TILE=1 keeps the ring write on the tile form at every c (comparisons)
+bool force_calib_tile() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("GDN_FLEET_CALIB_TILE");
+    v = (e && e[0] == '1') ? 1 : 0;
+  }
+  return v == 1;
+}
+
+// The form follows c alone (known on the host, captured), never counts; both forms write the same bytes.
+template <int MODE>
+int fleet_calib_write(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                      const uint8_t* valid, const int32_t* counts, int units, int c, int n, int w, int R,
+                      int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream) {
+  if (!state || !pred || !chunk || !alarm || !counts || !ring_keys || !ring_keep || (MODE != CALIB_PLAIN && !valid))
+    return GDN_ERR_ARG;
+  if (!gdn_fleet_rows_ok(units, c) || !stream_shape_ok(n, w)) return GDN_ERR_UNSUPPORTED;
+  if (gdn_fleet_calib_bytes(units, n, R) <= 0) return GDN_ERR_UNSUPPORTED;
+  if (c > R) return GDN_ERR_ARG;                   // two rows of one push would share a slot
+  const hipStream_t s = (hipStream_t)stream;
+  if (c < GDN_FLEET_CALIB_TILE_C && !force_calib_tile()) {
+    const unsigned waves = (unsigned)units * (unsigned)c;                            // <= 4096
+    hipLaunchKernelGGL(gdn_fleet_calib_direct_kernel<MODE>, dim3((waves + 3) / 4), dim3(256), 0, s, state, pred, chunk,
+                       alarm, valid, counts, units, c, n, w, R, exclude_alarms, ring_keys, ring_keep);
+  } else {
+    hipLaunchKernelGGL(gdn_fleet_calib_tile_kernel<MODE>, dim3(((unsigned)c + 63) / 64, (unsigned)units),
+                       dim3(GDN_STREAM_THREADS), 0, s, state, pred, chunk, alarm, valid, counts, c, n, w, R,
+                       exclude_alarms, ring_keys, ring_keep);
+  }
+  return gdn_launch_status();
 }
 
 template <int WAVES>
@@ -242,4 +420,53 @@ extern "C" int gdn_fleet_advance_gaps(void* state, const float* chunk, const flo
                                       int64_t* gaps, void* stream) {
   return fleet_advance<true>(state, chunk, pred, valid, gap_chunk, med_iqr, alarm, top_sensors, counts, units, c, n, w,
                              m, log_ticks, log_sensors, log_len, gaps, stream);
+}
+
+// units x the single stream's ring, keys of all units first ([U, n, R] float64), then the keep flags ([U, R] uint8).
+extern "C" long long gdn_fleet_calib_bytes(int units, int n, int R) {
+  const long long one = gdn_stream_calib_bytes(n, R);        // 0: outside the single stream's limits
+  if (one <= 0 || units < 1 || units > GDN_FLEET_MAX_ROWS || 8ll * units * n * R > (2ll << 30)) return 0;
+  return (long long)units * one;
+}
+
+extern "C" int gdn_fleet_calib_write(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                                     const int32_t* counts, int units, int c, int n, int w, int R, int exclude_alarms,
+                                     double* ring_keys, uint8_t* ring_keep, void* stream) {
+  return fleet_calib_write<CALIB_PLAIN>(state, pred, chunk, alarm, nullptr, counts, units, c, n, w, R, exclude_alarms,
+                                        ring_keys, ring_keep, stream);
+}
+
+extern "C" int gdn_fleet_calib_write_gaps(const void* state, const float* pred, const float* chunk,
+                                          const int32_t* alarm, const uint8_t* valid, const int32_t* counts, int units,
+                                          int c, int n, int w, int R, int exclude_alarms, double* ring_keys,
+                                          uint8_t* ring_keep, void* stream) {
+  return fleet_calib_write<CALIB_GAPS>(state, pred, chunk, alarm, valid, counts, units, c, n, w, R, exclude_alarms,
+                                       ring_keys, ring_keep, stream);
+}
+
+extern "C" int gdn_fleet_calib_write_sensor(const void* state, const float* pred, const float* chunk,
+                                            const int32_t* alarm, const uint8_t* valid, const int32_t* counts,
+                                            int units, int c, int n, int w, int R, int exclude_alarms,
+                                            double* ring_keys, uint8_t* ring_keep, void* stream) {
+  return fleet_calib_write<CALIB_SENSOR>(state, pred, chunk, alarm, valid, counts, units, c, n, w, R, exclude_alarms,
+                                         ring_keys, ring_keep, stream);
+}
+
+// ring_keep != NULL (tick mode): the keep sums into kept [U] and counts [U n].  ring_keep == NULL (sensor mode): counts
+// holds gdn_score_key_counts' numbers and only the mask is applied (select == NULL: nothing to do, no launch).
+extern "C" int gdn_fleet_ring_counts(const uint8_t* ring_keep, const uint8_t* select, int units, int n, int R,
+                                     int32_t* counts, int32_t* kept, void* stream) {
+  if (!counts || (ring_keep && !kept)) return GDN_ERR_ARG;
+  if (gdn_fleet_calib_bytes(units, n, R) <= 0) return GDN_ERR_UNSUPPORTED;
+  if (ring_keep) {
+    hipLaunchKernelGGL(gdn_fleet_ring_counts_kernel, dim3((unsigned)units), dim3(256), 0, (hipStream_t)stream,
+                       ring_keep, select, n, R, counts, kept);
+  } else if (select) {
+    const long long rows = (long long)units * n;             // <= 2^24
+    hipLaunchKernelGGL(gdn_fleet_counts_mask_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, select, n, rows, counts);
+  } else {
+    return GDN_OK;
+  }
+  return gdn_launch_status();
 }

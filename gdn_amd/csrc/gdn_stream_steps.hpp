@@ -80,6 +80,13 @@ __device__ __forceinline__ void stream_window_span(const void* __restrict__ stat
   }
 }
 
+// The slot rule of a calibration ring (include/gdn_hip.h "Rolling calibration"): row b of a push whose first tick sits
+// in slot base = ticks mod R owns slot (base + b) mod R.  b < c <= R, so one wrap at the most.
+__device__ __forceinline__ unsigned calib_slot(unsigned base, int b, int R) {
+  const unsigned at = base + (unsigned)b;
+  return at >= (unsigned)R ? at - (unsigned)R : at;
+}
+
 // Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it
 // does not depend on how floating-point comparisons with NaN are compiled.
 #define GDN_FILL_WAVES 16            // waves of the single stream's workgroup (a fleet picks 1, 4 or 16 from c)

@@ -2868,11 +2868,33 @@ class StreamFleet:
     reads StreamDetector(..., gaps=True / events=...) for every unit, `status_gaps()` and `episodes()` included; it is
     still ONE copy of the ticks, one counts write and ONE replay per push, one graph for full, short and silent units.
 
+    `recal=R` is StreamDetector's recal=R per unit: `ring_keys` [U, n, R] float64 and `ring_keep` [U, R]
+    uint8 in one allocation, unit u's slices a single stream's ring.  fleet_calib_write sits between the score (events)
+    and the advance launch, captured with them: ONE more launch in the same replay, and a silent unit's ring is not
+    touched.  `exclude_alarms`, `recal_min` (default max(64, R // 4)) and `calib="sensor"` (needs gaps=True) mean what
+    they mean to a detector.  `recalibrate(units=None)` rewrites `med_iqr` IN PLACE for every unit (or those named) with
+    at least `recal_min` kept ticks — per sensor under calib="sensor" — in a fixed number of launches with NO host read:
+    the keep sums (or the per-sensor key counts) become per-row counts on the device and gdn_score_select_counts reads
+    the rings as U * n sensors.  `recal_kept` [U] / `recal_counts` [U, n] int32 stay on the device; `calibration()`
+    reads them.  The graph reads the table through the same pointer and stays; thresholds, carries, logs and episode
+    tables are not touched.  `recal_every=E`: `push` calls `recalibrate()` after every sub-push in which the ticks
+    handed per unit (r, the time axis of `ticks`, whatever `counts` says) cross a multiple of E.  When every unit
+    contributes every tick that equals U detectors with recal_every=E; otherwise all units are recalibrated on the
+    fleet's clock, each from whatever its own ring holds.  The contract above then reads StreamDetector(recal=R, ...)
+    for every unit: ring, keep flags and the table after recalibrate().  recal=0 issues exactly the launches it did.
+
     Out of scope here (the per-unit state layout is a single stream's precisely so that they can follow without a format
-    change): recal=, calib="sensor", calib_gaps, prep=, save / load, a command-line flag, more than one process."""
+    change): prep=, save / load, a command-line flag, more than one process."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
-                 use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None):
+                 use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None, recal: int = 0,
+                 exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
+                 calib: str = "tick"):
+        _check_calib(calib)
+        if calib == "sensor" and not (gaps and int(recal) > 0):
+            raise ValueError("calib='sensor' recalibrates every sensor on its own real readings: it needs gaps=True and "
+                             "a calibration ring (recal=R)")
+        self.calib = calib
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -2892,7 +2914,24 @@ class StreamFleet:
         threshold = torch.as_tensor(threshold, dtype=torch.float64)
         if threshold.numel() not in (1, units) or threshold.dim() > 1:
             raise ValueError(f"threshold: one number or [{units}] of them, got {tuple(threshold.shape)}")
-        # the two options: host facts only, before any device work
+        # the options: host facts only, before any device work
+        self.recal, self.exclude_alarms, self.recal_every = int(recal), bool(exclude_alarms), int(recal_every)
+        self.recal_min = 0
+        if self.recal_every < 0 or (self.recal_every and not self.recal):
+            raise ValueError(f"recal_every = {recal_every}: recalibrating every so many ticks needs a calibration ring "
+                             "(recal=R) and a positive number of ticks")
+        if self.recal:
+            if self.recal < self.chunk:
+                raise ValueError(f"recal = {recal}: the calibration ring must hold at least one push of chunk = "
+                                 f"{self.chunk} ticks (no two rows of a push may share a slot)")
+            if _lib.load().gdn_fleet_calib_bytes(units, n, self.recal) <= 0:
+                raise ValueError(f"recal = {recal}: no calibration rings for units = {units}, n = {n}, R = {recal} "
+                                 "(1 <= units <= 4096, 1 <= n <= 4096, 64 <= R <= 2^20, 8 units n R <= 2 GiB)")
+            self.recal_min = max(64, self.recal // 4) if recal_min is None else int(recal_min)
+            if not 1 <= self.recal_min <= self.recal:
+                raise ValueError(f"recal_min = {recal_min}: between 1 and recal = {self.recal} kept ticks")
+        elif recal_min is not None:
+            raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
         self.with_gaps = bool(gaps)
         self.events_cfg = None if events is None else events_config({**events, "lo": None}, self.top_m)
         clear = None if events is None else fleet_clear_levels(events.get("lo"), threshold, units)
@@ -2928,19 +2967,45 @@ class StreamFleet:
             self.events_cfg.pop("lo")
             self.clear = clear.to(dev)
             self.events = ops.fleet_events_alloc(units, m, self.events_cfg["cap"], dev)
+        self.ring_keys = self.ring_keep = self._recal_ws = self.recal_kept = self.recal_counts = None
+        if self.recal:
+            self.ring_keys, self.ring_keep = ops.fleet_calib_ring(units, n, self.recal, dev)
+            self._recal_ws = ops.fleet_select_workspace(units, n, self.recal, dev)
+            # what the last recalibrate() counted, on the device: the kept ticks per unit (tick calibration) and the
+            # count handed to the select per (unit, sensor); a unit left out through `units=` shows counts 0
+            self.recal_kept = torch.zeros((units,), dtype=torch.int32, device=dev) if calib == "tick" else None
+            self.recal_counts = torch.zeros((units, n), dtype=torch.int32, device=dev)
+        self.recals = 0                     # calls of recalibrate()
+        self._handed = 0                    # ticks per unit handed to push(): recal_every's clock
+        self.calib_kept = None              # from_calibration(calib_gaps=True): per unit, the ticks behind the table
+        self.calib_counts = None            # ... calib="sensor": every sensor's real readings behind it [U, n]
         self._full = _Replay(lambda *a: self._launch(*a), use_graph, lambda: model._constants().key,
                              args=lambda: (self._guarded(),))
         self._last = 0                      # ticks per unit of the last (sub-)push: what the static buffers hold
 
     @classmethod
-    def from_calibration(cls, model, series, chunk: int, batch: int = 8192, **kw):
+    def from_calibration(cls, model, series, chunk: int, batch: int = 8192, calib_gaps: bool = False,
+                         min_kept: int = 64, **kw):
         """A fleet calibrated on `series` [U, n, T] fp32 on the device, each unit's own period known to be normal: ONE
         SeriesEvaluator step per unit at construction (not a hot path) under the rules of
         StreamDetector.from_calibration — the table is that step's med_iqr, the threshold the largest anomaly score of
-        the unit's period, the history its last w ticks.  `gaps=` and `events=` pass through; the calibration itself
-        knows no missing reading (there is no calib_gaps here), so with gaps=True a series that is not finite is
-        refused."""
-        if kw.get("gaps") and isinstance(series, torch.Tensor) and not bool(torch.isfinite(series).all()):
+        the unit's period, the history its last w ticks.  `gaps=` and `events=` pass through; without `calib_gaps` the
+        calibration itself knows no missing reading, so with gaps=True a series that is not finite is refused.
+        `calib_gaps=True` (needs gaps=True), `min_kept=`, `calib="sensor"` (needs calib_gaps=True) and `recal=R` mean
+        per unit what they mean to StreamDetector.from_calibration: the period is scored under the detector's own rules,
+        the default history is the FILLED period's last w ticks, and unit u's ring is seeded as StreamDetector._seed
+        seeds a detector's — with the period's keep flags under calib_gaps, through its validity plane under
+        calib="sensor".  `calib_kept` [U] int64 (host; None without calib_gaps) and `calib_counts` [U, n] int32 (device;
+        calib="sensor") are the detectors' per unit."""
+        calib = kw.get("calib", "tick")
+        _check_calib(calib)
+        if calib == "sensor" and not calib_gaps:
+            raise ValueError("calib='sensor' calibrates every sensor on its own real readings: pass calib_gaps=True "
+                             "(and gaps=True) too")
+        if calib_gaps and not kw.get("gaps"):
+            raise ValueError("calib_gaps=True calibrates under the rules of a gaps=True fleet: pass gaps=True too")
+        if (kw.get("gaps") and not calib_gaps and isinstance(series, torch.Tensor)
+                and not bool(torch.isfinite(series).all())):
             raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
                              "stream, not the calibration (fill or cut the period first)")
         series = ops._chk(series, name="series")
@@ -2948,12 +3013,49 @@ class StreamFleet:
         if series.dim() != 3 or series.shape[2] <= w:
             raise ValueError(f"calibration needs a series [U, n, T] with T > {w}, got {tuple(series.shape)}")
         fleet_check_shape(series.shape[0], chunk, series.shape[1], w)
-        tables, thresholds = [], []
+        R = int(kw.get("recal", 0))
+        if calib == "sensor" and not R:
+            kw["calib"] = "tick"            # no ring: the fleet never calibrates anything itself
+        tables, thresholds, histories, seeds, kept, counts = [], [], [], [], [], []
         for unit in series:
-            ev = SeriesEvaluator(model, None, unit[:, w:].t().contiguous(), batch=batch, use_graph=False, series=unit)
+            if calib_gaps:
+                ev = SeriesEvaluator(model, None, None, batch=batch, use_graph=False, series=unit, gaps=True,
+                                     min_kept=min_kept, calib=calib)
+            else:
+                ev = SeriesEvaluator(model, None, unit[:, w:].t().contiguous(), batch=batch, use_graph=False,
+                                     series=unit)
             thresholds.append(ev.step().max())
             tables.append(ev.med_iqr.clone())
-        return cls(model, torch.stack(tables), torch.stack(thresholds), series[:, :, -w:].contiguous(), chunk, **kw)
+            histories.append(ev.series[:, -w:].clone())
+            kept.append(ev.kept)
+            counts.append(ev.counts)
+            if R:                            # the rows _seed would read: the period's last min(R, T - w)
+                s = min(R, ev.pred.shape[0])
+                seeds.append(tuple(None if t is None else t[-s:].clone()
+                                   for t in (ev.pred, ev.y, ev.keep, ev.valid if calib == "sensor" else None)))
+        history = kw.pop("history", None)
+        fleet = cls(model, torch.stack(tables), torch.stack(thresholds),
+                    torch.stack(histories) if history is None else history, chunk, **kw)
+        if calib_gaps:
+            fleet.calib_kept = torch.as_tensor([int(k) for k in kept], dtype=torch.int64)
+        if calib == "sensor":
+            fleet.calib_counts = torch.stack(counts)
+        for u, (pred, gt, keep, valid) in enumerate(seeds):
+            fleet._seed(u, pred, gt, keep, valid)
+        return fleet
+
+    def _seed(self, u: int, pred, gt, keep=None, valid=None):
+        """StreamDetector._seed on unit u's slices of the rings."""
+        s = min(self.recal, pred.shape[0])
+        if valid is not None:
+            keys, keep = ops.score_keys(pred[-s:], gt[-s:], s, valid=valid[-s:]), None
+        else:
+            keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
+        if keep is None:
+            self.ring_keep[u, self.recal - s:].fill_(1)
+        else:
+            self.ring_keep[u, self.recal - s:].copy_(keep[-s:])
+        self.ring_keys[u, :, self.recal - s:].copy_(keys)
 
     # the launches of a push: static arguments only (they are captured)
     def _guarded(self) -> bool:
@@ -2977,6 +3079,10 @@ class StreamFleet:
             ops.fleet_events(self.state, self.top_scores, self.top_sensors, self.threshold, self.clear, self.counts,
                              self.n, self.w, self.events_cfg["on"], self.events_cfg["off"], self.events_cfg["cap"],
                              self.events)
+        if self.recal:
+            ops.fleet_calib_write(self.state, self.pred, self.chunk_buf, self.alarm, self.counts, self.w,
+                                  self.ring_keys, self.ring_keep, self.exclude_alarms, valid=self.valid,
+                                  by_sensor=self.calib == "sensor")
         ops.fleet_advance(self.state, self.chunk_buf, self.pred, self.med_iqr, self.alarm, self.top_sensors,
                           self.counts, self.w, self.top_m, self.log_ticks, self.log_sensors, valid=self.valid,
                           gap_chunk=self.gap_chunk, gaps=self.gaps)
@@ -3004,8 +3110,54 @@ class StreamFleet:
                 self.counts.copy_((counts - s).clamp_(0, r).to(torch.int32))
             self._last = r
             self._full()
+            before, self._handed = self._handed, self._handed + r
+            if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
+                self.recalibrate()
         r = self._last
         return self.top_scores[:, :r], self.top_sensors[:, :r], self.alarm[:, :r]
+
+    def _unit_mask(self, units):
+        """recalibrate()'s `units`: None, a device uint8 / bool [U] mask (taken as it is) or a host sequence of unit
+        indices (one small copy to the device)."""
+        if units is None:
+            return None
+        if isinstance(units, torch.Tensor) and units.is_cuda:
+            if units.dtype not in (torch.uint8, torch.bool) or units.shape != (self.units,):
+                raise ValueError(f"units: a device mask must be uint8 or bool of shape [{self.units}], got {units.dtype} "
+                                 f"{tuple(units.shape)}")
+            return units.contiguous()
+        idx = torch.as_tensor(units, dtype=torch.int64).reshape(-1)
+        if idx.numel() and bool(((idx < 0) | (idx >= self.units)).any()):
+            raise ValueError(f"units = {idx.tolist()}: the fleet has units 0 .. {self.units - 1}")
+        mask = torch.zeros((self.units,), dtype=torch.uint8)
+        mask[idx] = 1
+        return mask.to(self.state.device)
+
+    def recalibrate(self, units=None) -> None:
+        """Overwrite `med_iqr` [U, n, 2] in place from the calibration rings, per unit what
+        StreamDetector.recalibrate() writes: tick calibration rewrites the table of every unit whose ring holds at
+        least `recal_min` kept ticks, calib="sensor" the row of every (unit, sensor) with that many real keys; the other
+        rows stay bit for bit.  `units`: None (all), a host sequence of unit indices or a device uint8 / bool [U] mask;
+        a unit left out keeps its table.  A fixed number of launches and NO host read: gdn_fleet_ring_counts (sensor:
+        gdn_score_key_counts, then the mask), then gdn_score_select_counts(min_count = recal_min) straight from the
+        rings, one call per 65535 rows.  The counts stay on the device: `recal_kept` [U] int32 (tick calibration; a
+        unit left out keeps its entry) and `recal_counts` [U, n] int32 (what the select was handed: 0 for a unit left
+        out); `calibration()` reads them.  Thresholds, carries, logs, episode tables and the captured graph stay."""
+        if not self.recal:
+            raise ValueError("recalibrate(): the fleet was built with recal=0 and keeps no calibration rings")
+        select = self._unit_mask(units)
+        ops.fleet_ring_counts(self.ring_keys, self.ring_keep, self.recal_counts, self.recal_kept, select,
+                              by_sensor=self.calib == "sensor")
+        ops.fleet_select_counts(self.ring_keys, self.recal_counts, self.recal_min, self._recal_ws, self.med_iqr)
+        self.recals += 1
+
+    def calibration(self):
+        """(a copy of the tables in force [U, n, 2] float64 on the device, the counts of the last recalibrate() on the
+        host: `recal_kept` [U] under tick calibration, `recal_counts` [U, n] under calib="sensor"; zeros before the
+        first one).  ONE read (a synchronisation)."""
+        if not self.recal:
+            raise ValueError("calibration(): the fleet was built with recal=0 and keeps no calibration rings")
+        return self.med_iqr.clone(), (self.recal_kept if self.calib == "tick" else self.recal_counts).cpu()
 
     def status(self):
         """Per unit (ticks [U], alarms [U], logged [U]) as host int64 tensors: ONE read of the counters (a

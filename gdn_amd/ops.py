@@ -1358,6 +1358,111 @@ def fleet_events(state, top_scores, top_sensors, threshold, clear, counts, n: in
     return events
 
 
+_FLEET_RING_LIMITS = "1 <= units <= 4096, 1 <= n <= 4096, 64 <= R <= 2^20, 8 units n R <= 2 GiB"
+FLEET_SELECT_ROWS = 65535           # rows one select call takes: its multi-pass route launches a grid (slices, rows)
+
+
+def fleet_calib_ring(units: int, n: int, R: int, device):
+    """The EMPTY calibration rings of a fleet (include/gdn_hip.h "Rolling calibration of a fleet") in one allocation of
+    gdn_fleet_calib_bytes(units, n, R): (ring_keys [U, n, R] float64, every key the filler pattern; ring_keep [U, R]
+    uint8, zero).  Unit u's slices are what stream_calib_ring gives a single stream."""
+    nbytes = _lib.load().gdn_fleet_calib_bytes(units, n, R)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"fleet calibration ring: no kernel for units = {units}, n = {n}, R = {R} "
+                               f"({_FLEET_RING_LIMITS})")
+    ring = torch.full((nbytes // 8,), -1, dtype=torch.int64, device=device)            # all ones: the filler
+    ring_keys = ring[: units * n * R].view(torch.float64).view(units, n, R)
+    ring_keep = ring[units * n * R:].view(torch.uint8)[: units * R].view(units, R)
+    ring_keep.zero_()
+    return ring_keys, ring_keep
+
+
+def _fleet_ring_dims(ring_keys, ring_keep, units: int, n: int):
+    if ring_keys.dim() != 3 or ring_keys.shape[:2] != (units, n):
+        raise ValueError(f"ring_keys: expected [{units}, {n}, R], got {tuple(ring_keys.shape)}")
+    R = ring_keys.shape[2]
+    _stream_buf(ring_keys, torch.float64, units * n * R, "ring_keys")
+    if ring_keep is not None:
+        _stream_buf(ring_keep, torch.uint8, units * R, "ring_keep")
+    return R
+
+
+def fleet_calib_write(state, pred, chunk, alarm, counts, w: int, ring_keys, ring_keep, exclude_alarms: bool = True,
+                      valid=None, by_sensor: bool = False):
+    """stream_calib_write per unit in one launch (gdn_fleet_calib_write): row b < counts[u] of unit u -> slot
+    (ticks_u + b) mod R of that unit's slices of ring_keys [U, n, R] / ring_keep [U, R].  After fleet_score (and
+    fleet_events), before fleet_advance.  Writes the rings only; a unit with counts[u] == 0 has no byte of its ring
+    touched.  `valid` (fleet_fill's plane of the filled `chunk`) and `by_sensor` pick gdn_fleet_calib_write_gaps /
+    _sensor as stream_calib_write picks the single stream's."""
+    if by_sensor and valid is None:
+        raise ValueError("fleet_calib_write: by_sensor needs the validity plane `valid`")
+    chunk, units, c, n = _fleet_dims(state, chunk, counts, w)
+    _stream_buf(pred, torch.float32, units * c * n, "pred")
+    _stream_buf(alarm, torch.int32, units * c, "alarm")
+    R = _fleet_ring_dims(ring_keys, ring_keep, units, n)
+    tail = (_ptr(counts), units, c, n, w, R, int(bool(exclude_alarms)), _ptr(ring_keys), _ptr(ring_keep), _stream())
+    if valid is None:
+        _lib.call("gdn_fleet_calib_write", _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), *tail)
+    else:
+        _stream_buf(valid, torch.uint8, units * c * n, "valid")
+        name = "gdn_fleet_calib_write_sensor" if by_sensor else "gdn_fleet_calib_write_gaps"
+        _lib.call(name, _ptr(state), _ptr(pred), _ptr(chunk), _ptr(alarm), _ptr(valid), *tail)
+    return ring_keys, ring_keep
+
+
+def fleet_ring_counts(ring_keys, ring_keep, counts, kept=None, select=None, by_sensor: bool = False):
+    """The per-row counts score_select_counts takes over ring_keys [U, n, R] viewed as U * n sensors, into `counts`
+    [U, n] int32 on the device (gdn_fleet_ring_counts); nothing is read back.  Tick calibration: kept [U] int32 = the sum
+    of each unit's keep flags, broadcast over the unit's rows.  `by_sensor`: score_key_counts over the rings (every row's
+    own real keys; `ring_keep` and `kept` are not used).  `select` [U] uint8 / bool on the device (None: every unit): a
+    unit with select[u] == 0 gets counts 0 — the select then keeps its rows — and keeps kept[u]."""
+    if ring_keys.dim() != 3:
+        raise ValueError(f"ring_keys: expected [U, n, R], got {tuple(ring_keys.shape)}")
+    units, n = ring_keys.shape[:2]
+    R = _fleet_ring_dims(ring_keys, None if by_sensor else ring_keep, units, n)
+    _stream_buf(counts, torch.int32, units * n, "counts")
+    if select is not None:
+        if select.dtype == torch.bool:
+            select = select.view(torch.uint8)
+        _stream_buf(select, torch.uint8, units, "select")
+    if by_sensor:
+        score_key_counts(ring_keys, 1, units * n, R, out=counts.view(-1)[: units * n])
+        _lib.call("gdn_fleet_ring_counts", None, _ptr(select), units, n, R, _ptr(counts), None, _stream())
+        return counts, None
+    if kept is None:
+        raise ValueError("fleet_ring_counts: tick calibration needs `kept` [U] int32")
+    _stream_buf(kept, torch.int32, units, "kept")
+    _lib.call("gdn_fleet_ring_counts", _ptr(ring_keep), _ptr(select), units, n, R, _ptr(counts), _ptr(kept), _stream())
+    return counts, kept
+
+
+def fleet_select_spans(units: int, n: int, limit: int = FLEET_SELECT_ROWS) -> list:
+    """Cut the U * n rows of a fleet's rings into spans [(first unit, units)] of whole units with at most `limit` rows
+    each (n <= limit): what one select call takes.  Host arithmetic only."""
+    if units < 1 or n < 1 or n > limit:
+        raise ValueError(f"units = {units}, n = {n}: at least one unit, and 1 <= n <= {limit} rows per unit")
+    per = limit // n
+    return [(u0, min(per, units - u0)) for u0 in range(0, units, per)]
+
+
+def fleet_select_workspace(units: int, n: int, R: int, device) -> torch.Tensor:
+    """One select workspace sized for the largest span of fleet_select_spans(units, n)."""
+    most = max(k for _, k in fleet_select_spans(units, n))
+    return score_select_workspace(1, most * n, R, device)
+
+
+def fleet_select_counts(ring_keys, counts, min_count: int, ws, med_iqr):
+    """med_iqr [U, n, 2] rewritten in place from ring_keys [U, n, R] with the per-row counts [U, n]: ONE
+    score_select_counts per span of fleet_select_spans (one call up to 65535 rows), straight from the rings."""
+    units, n, R = ring_keys.shape
+    _stream_buf(med_iqr, torch.float64, units * n * 2, "med_iqr")
+    _stream_buf(counts, torch.int32, units * n, "counts")
+    for u0, k in fleet_select_spans(units, n):
+        score_select_counts(ring_keys[u0:u0 + k], 1, k * n, R, counts[u0:u0 + k], min_count, ws,
+                            out=med_iqr[u0:u0 + k])
+    return med_iqr
+
+
 # --------------------------------------------------------------------------- raw readings
 _PREP_MAX_DOWN = 64
 

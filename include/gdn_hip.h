@@ -1147,6 +1147,47 @@ long long gdn_fleet_events_bytes(int units, int m, long long E);
 int gdn_fleet_events(const void* state, const double* top_scores, const int32_t* top_sensors, const double* threshold,
                      const double* clear, const int32_t* counts, int units, int c, int n, int w, int m, int on, int off,
                      long long E, void* events, void* stream);
+/* Rolling calibration of a fleet (opt-in; additive entry points, the ABI version does not move): the
+ * single stream's calibration ring ("Rolling calibration", "Calibration on each sensor's own readings" above) per unit.
+ * Rings: ONE allocation of gdn_fleet_calib_bytes(units, n, R) = units * gdn_stream_calib_bytes(n, R) bytes, the keys of
+ * all units first and then the keep flags:
+ *   ring_keys [U, n, R] float64   unit u's block, a single stream's ring_keys [n, R], at u * n * R;
+ *   ring_keep [U, R] uint8        at byte 8 U n R.
+ * An empty ring holds the filler in every key and 0 in every keep flag.  Limits (gdn_fleet_calib_bytes: 0 outside):
+ * the single stream's per unit (1 <= n <= 4096, 64 <= R <= 2^20), 1 <= units <= 4096, 8 units n R <= 2 GiB.
+ *   gdn_fleet_calib_write         gdn_stream_calib_write per unit with count = counts[u] clamped to 0 .. c, read on the
+ *                                 device: row b < count of unit u is that unit's stream tick ticks_u + b (ticks_u from
+ *                                 the unit's state block) and owns slot (ticks_u + b) mod R of the unit's ring.  Keep
+ *                                 rules and key arithmetic are the single stream's.  A unit with count 0 has no byte of
+ *                                 its ring touched.  In stream order after gdn_fleet_score (and gdn_fleet_events),
+ *                                 before gdn_fleet_advance.  Reads the states, pred, the (filled) chunk, alarm [U, c]
+ *                                 and valid; writes the rings only.  ONE launch whose form follows c alone: c < 64 a
+ *                                 wave per (unit, row) with its lanes along the sensors, no LDS and no barrier; from 64
+ *                                 on the single stream's transposing tile per (row tile, unit).  Both write the same
+ *                                 bytes.  No atomics; no workgroup waits on another.
+ *   gdn_fleet_calib_write_gaps    the same with gdn_stream_calib_write_gaps' rule: valid [U, c, n] of gdn_fleet_fill.
+ *   gdn_fleet_calib_write_sensor  the same with gdn_stream_calib_write_sensor's rule.
+ *   gdn_fleet_ring_counts         the per-row counts gdn_score_select_counts(keys = ring_keys, blocks = 1, n = U n
+ *                                 rows, pitch = R) takes.  ring_keep != NULL (tick calibration): kept [U] int32 = the sum
+ *                                 of each unit's keep flags, counts [U n] int32 = kept[u] for every row of unit u.
+ *                                 ring_keep == NULL (per-sensor calibration): counts already holds gdn_score_key_counts
+ *                                 over the U n rows and `kept` is not used.  select [U] uint8 on the device may be NULL;
+ *                                 a unit with select[u] == 0 gets counts 0 (the select then keeps its rows) and keeps
+ *                                 kept[u].  One launch (none when ring_keep and select are both NULL).
+ * Refusals, all before any launch: a null required pointer, c > R: GDN_ERR_ARG; units * c, n, w and the ring limits:
+ * GDN_ERR_UNSUPPORTED.                                                                                               */
+long long gdn_fleet_calib_bytes(int units, int n, int R);
+int gdn_fleet_calib_write(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                          const int32_t* counts, int units, int c, int n, int w, int R, int exclude_alarms,
+                          double* ring_keys, uint8_t* ring_keep, void* stream);
+int gdn_fleet_calib_write_gaps(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                               const uint8_t* valid, const int32_t* counts, int units, int c, int n, int w, int R,
+                               int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream);
+int gdn_fleet_calib_write_sensor(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
+                                 const uint8_t* valid, const int32_t* counts, int units, int c, int n, int w, int R,
+                                 int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream);
+int gdn_fleet_ring_counts(const uint8_t* ring_keep, const uint8_t* select, int units, int n, int R, int32_t* counts,
+                          int32_t* kept, void* stream);
 
 #ifdef __cplusplus
 }
