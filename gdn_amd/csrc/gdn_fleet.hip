@@ -131,50 +131,19 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_fleet_advance_kernel(
 
 // The calibration rings of a fleet (include/gdn_hip.h "Rolling calibration of a fleet"): ring_keys [U, n, R] float64,
 // ring_keep [U, R] uint8, unit u's slices a single stream's ring.  Row b < counts[u] of unit u is that unit's stream
-// tick ticks_u + b and owns slot (ticks_u + b) mod R of the unit's ring; the keep rules and the key arithmetic are
-// those of gdn_stream_calib_write / _gaps / _sensor (gdn_stream.hip), which the three MODEs restate per unit:
-//   PLAIN   a tick is kept unless it alarmed under exclude_alarms; a tick not kept writes the filler and keep = 0;
-//   GAPS    ... or unless a reading of it was missing (valid);
-//   SENSOR  keep = the alarm rule alone; the key of a missing reading is the filler, the tick's others are real.
+// tick ticks_u + b and owns slot (ticks_u + b) mod R of the unit's ring.  The keep rule and the key of each MODE
+// (CALIB_PLAIN / _GAPS / _SENSOR) and the tile step are gdn_stream_steps.hpp's, the ones gdn_stream_calib_write /
+// _gaps / _sensor run: a kernel here only says which unit's rows, ring and count.
 // Reads the states, writes the rings only; a unit with counts[u] == 0 has no byte of its ring touched.
-enum { CALIB_PLAIN = 0, CALIB_GAPS = 1, CALIB_SENSOR = 2 };
 #define GDN_FLEET_CALIB_TILE_C 64    // from this many rows per unit on, the transposing tile form
 
-struct FleetRing {
-  const float *pred, *chunk;
-  const int* alarm;
-  const unsigned char* valid;
-  double* keys;
-  unsigned char* keep;
-  unsigned base;
-};
-__device__ __forceinline__ FleetRing fleet_ring(const void* state, const float* pred, const float* chunk,
-                                                const int* alarm, const unsigned char* valid, int u, int c, int n,
-                                                int w, int R, double* ring_keys, unsigned char* ring_keep) {
+__device__ __forceinline__ RingSource fleet_ring(const void* state, const float* pred, const float* chunk,
+                                                 const int* alarm, const unsigned char* valid, int u, int c, int n,
+                                                 int w, int R, double* ring_keys, unsigned char* ring_keep) {
   const size_t row0 = (size_t)u * c;
-  const long long ticks = reinterpret_cast<const long long*>(fleet_state(state, u, n, w))[0];
-  return FleetRing{pred + row0 * n, chunk + row0 * n, alarm + row0, valid ? valid + row0 * n : nullptr,
-                   ring_keys + (size_t)u * n * R, ring_keep + (size_t)u * R, (unsigned)(ticks % (long long)R)};
-}
-// does tick b of the unit count?  All 64 lanes of a wave call it (GAPS: an __all over the row's validity bytes).
-template <int MODE>
-__device__ __forceinline__ bool fleet_ring_keep(const FleetRing& fr, int b, int n, int exclude_alarms, int lane) {
-  bool keep = !(exclude_alarms && fr.alarm[b] != 0);
-  if constexpr (MODE == CALIB_GAPS) {
-    bool real = true;
-    for (int s0 = 0; s0 < n; s0 += 64) {
-      const int s = s0 + lane;
-      real = real && (s >= n || fr.valid[(size_t)b * n + s] != 0);
-    }
-    keep = keep && __all(real);
-  }
-  return keep;
-}
-template <int MODE>
-__device__ __forceinline__ double fleet_ring_key(const FleetRing& fr, size_t o, bool keep) {
-  if constexpr (MODE == CALIB_SENSOR) keep = keep && fr.valid[o] != 0;
-  const double e = score_key(fr.pred[o], fr.chunk[o]);
-  return keep ? e : filler_key();
+  return RingSource{pred + row0 * n, chunk + row0 * n, alarm + row0, valid ? valid + row0 * n : nullptr,
+                    ring_keys + (size_t)u * n * R, ring_keep + (size_t)u * R,
+                    ring_base(fleet_state(state, u, n, w), R)};
 }
 
 // The direct form (small c): one wave per (unit, row), lanes along the sensors, every lane stores its key at
@@ -190,54 +159,26 @@ __global__ __launch_bounds__(256) void gdn_fleet_calib_direct_kernel(
   const int at = blockIdx.x * (blockDim.x >> 6) + wv;        // (wave uniform) <= 4096 + 3
   const int u = at / c, b = at - u * c;
   if (u >= units || b >= fleet_count(counts, u, c)) return;
-  const FleetRing fr = fleet_ring(state, pred, chunk, alarm, valid, u, c, n, w, R, ring_keys, ring_keep);
-  const unsigned slot = calib_slot(fr.base, b, R);
-  const bool keep = fleet_ring_keep<MODE>(fr, b, n, exclude_alarms, lane);
-  if (lane == 0) fr.keep[slot] = keep ? 1 : 0;
+  const RingSource rs = fleet_ring(state, pred, chunk, alarm, valid, u, c, n, w, R, ring_keys, ring_keep);
+  const unsigned slot = calib_slot(rs.base, b, R);
+  const bool keep = ring_keep_row<MODE>(rs, b, n, exclude_alarms, lane);
+  if (lane == 0) rs.keep[slot] = keep ? 1 : 0;
   for (int s = lane; s < n; s += 64)
-    fr.keys[(size_t)s * R + slot] = fleet_ring_key<MODE>(fr, (size_t)b * n + s, keep);
+    rs.keys[(size_t)s * R + slot] = ring_key<MODE>(rs, (size_t)b * n + s, keep);
 }
 
 // The tile form, workgroup (row tile g, unit): the single stream's workgroup g on unit u's rows with count = counts[u]
-// — 64 rows x 64 sensors transposed through the padded LDS tile, fp32 reads along sensors, fp64 writes along slots.
+// (ring_write_tile, the step that workgroup runs).
 template <int MODE>
 __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_fleet_calib_tile_kernel(
     const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ chunk,
     const int* __restrict__ alarm, const unsigned char* __restrict__ valid, const int* __restrict__ counts, int c,
     int n, int w, int R, int exclude_alarms, double* __restrict__ ring_keys, unsigned char* __restrict__ ring_keep) {
-  __shared__ double tile[64][65];
-  __shared__ int keep_row[64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int u = blockIdx.y, b0 = blockIdx.x * 64;
   const int count = fleet_count(counts, u, c);
   if (b0 >= count) return;                                   // (workgroup uniform, ahead of every barrier)
-  const FleetRing fr = fleet_ring(state, pred, chunk, alarm, valid, u, c, n, w, R, ring_keys, ring_keep);
-  for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {   // wave wv owns rows wv, wv + 4, ..: (wave uniform)
-    const int b = b0 + r;
-    if (b >= count) break;
-    const bool keep = fleet_ring_keep<MODE>(fr, b, n, exclude_alarms, lane);
-    if (lane == 0) {
-      keep_row[r] = keep ? 1 : 0;
-      fr.keep[calib_slot(fr.base, b, R)] = keep ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  for (int s0 = 0; s0 < n; s0 += 64) {
-    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
-      const int b = b0 + r, s = s0 + lane;
-      if (b < count && s < n) tile[r][lane] = fleet_ring_key<MODE>(fr, (size_t)b * n + s, keep_row[r] != 0);
-    }
-    __syncthreads();
-    const int b = b0 + lane;                                 // now the lane runs along the push's rows = ring slots
-    if (b < count) {
-      const unsigned slot = calib_slot(fr.base, b, R);
-      for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
-        const int s = s0 + r;
-        if (s < n) fr.keys[(size_t)s * R + slot] = tile[lane][r];
-      }
-    }
-    __syncthreads();                                         // the tile is rewritten by the next sensor tile
-  }
+  const RingSource rs = fleet_ring(state, pred, chunk, alarm, valid, u, c, n, w, R, ring_keys, ring_keep);
+  ring_write_tile<MODE>(rs, b0, count, n, R, exclude_alarms, threadIdx.x);
 }
 
 // Workgroup u, tick mode: kept[u] = the sum of unit u's keep flags (integer adds: any order gives the same number),

@@ -79,129 +79,37 @@ __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_advance_kernel(
 }
 
 // The calibration ring (include/gdn_hip.h "Rolling calibration"): row b < count of the push is stream tick
-// ticks + b and owns slot (ticks + b) mod R of ring_keys [n, R] / ring_keep [R].  A kept tick writes its n keys
-// score_key(pred, chunk) and keep = 1; a tick that is not kept (its
-// alarm flag under exclude_alarms; GAPS: a missing reading in any sensor) writes the filler into all n keys and
-// keep = 0, so no older tick survives in its slot.  Workgroup g: rows [64 g, 64 g + 64) of the push, sensor tiles of
-// 64 transposed through the padded LDS tile of score_keys_kernel: fp32 reads along sensors, fp64 writes along slots.
-// The slot is computed per row: a tile may wrap the ring's end once (c <= R: no two rows of a push share a slot).
+// ticks + b and owns slot (ticks + b) mod R of ring_keys [n, R] / ring_keep [R] (c <= R: no two rows of a push share
+// a slot).  Workgroup g: rows [64 g, 64 g + 64) of the push through ring_write_tile (gdn_stream_steps.hpp), which
+// states the keep rule and the key of each MODE (plain, gaps, per-sensor calibration) once, for a fleet's units too.
 // Runs between the score launch (which wrote `alarm`) and the advance launch (`ticks` is still the push's first
-// tick); reads the state, writes the ring only.  GAPS first walks the tiles once to AND every row's validity bytes.
+// tick); reads the state, writes the ring only.
 #define GDN_CALIB_MIN_R 64
 #define GDN_CALIB_MAX_R (1 << 20)
 
-template <bool GAPS>
+template <int MODE>
 __global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_kernel(
     const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ chunk,
     const int* __restrict__ alarm, const unsigned char* __restrict__ valid, int count, int n, int R,
     int exclude_alarms, double* __restrict__ ring_keys, unsigned char* __restrict__ ring_keep) {
-  __shared__ double tile[64][65];
-  __shared__ int keep_row[64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b0 = blockIdx.x * 64;
-  const unsigned base = (unsigned)(reinterpret_cast<const long long*>(state)[0] % (long long)R);   // < R <= 2^20
-  auto slot_of = [&](int b) -> unsigned {                    // b < count <= c <= R: one wrap at the most
-    const unsigned at = base + (unsigned)b;
-    return at >= (unsigned)R ? at - (unsigned)R : at;
-  };
-  for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {   // wave wv owns rows wv, wv + 4, ..: (wave uniform)
-    const int b = b0 + r;
-    if (b >= count) break;
-    bool keep = !(exclude_alarms && alarm[b] != 0);
-    if constexpr (GAPS) {
-      bool real = true;
-      for (int s0 = 0; s0 < n; s0 += 64) {
-        const int s = s0 + lane;
-        real = real && (s >= n || valid[(size_t)b * n + s] != 0);
-      }
-      keep = keep && __all(real);
-    }
-    if (lane == 0) {
-      keep_row[r] = keep ? 1 : 0;
-      ring_keep[slot_of(b)] = keep ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  for (int s0 = 0; s0 < n; s0 += 64) {
-    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
-      const int b = b0 + r, s = s0 + lane;
-      if (b < count && s < n) {
-        const size_t o = (size_t)b * n + s;
-        tile[r][lane] = score_key(pred[o], chunk[o]);
-      }
-    }
-    __syncthreads();
-    const int b = b0 + lane;                                 // now the lane runs along the push's rows = ring slots
-    if (b < count) {
-      const unsigned slot = slot_of(b);
-      const bool keep = keep_row[lane] != 0;
-      for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
-        const int s = s0 + r;
-        if (s < n)
-          ring_keys[(size_t)s * R + slot] = keep ? tile[lane][r] : filler_key();
-      }
-    }
-    __syncthreads();                                         // the tile is rewritten by the next sensor tile
-  }
-}
-
-// The ring write of per-sensor calibration (gdn_stream_calib_write_sensor; include/gdn_hip.h "Calibration on each
-// sensor's own readings").  Slots and order are those of the kernel above.  A tick excluded by its alarm writes the
-// filler into all n keys and keep = 0; any other tick writes keep = 1 and sensor i's key where valid[b, i] == 1, the
-// filler where it is missing: the validity byte is read next to the value and the tile carries the filler pattern in
-// the key's place.  A kernel of its own, so the two instantiations above stay as they are.
-__global__ __launch_bounds__(GDN_STREAM_THREADS) void gdn_stream_calib_write_sensor_kernel(
-    const void* __restrict__ state, const float* __restrict__ pred, const float* __restrict__ chunk,
-    const int* __restrict__ alarm, const unsigned char* __restrict__ valid, int count, int n, int R,
-    int exclude_alarms, double* __restrict__ ring_keys, unsigned char* __restrict__ ring_keep) {
-  __shared__ double tile[64][65];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b0 = blockIdx.x * 64;
-  const unsigned base = (unsigned)(reinterpret_cast<const long long*>(state)[0] % (long long)R);   // < R <= 2^20
-  auto slot_of = [&](int b) -> unsigned {                    // b < count <= c <= R: one wrap at the most
-    const unsigned at = base + (unsigned)b;
-    return at >= (unsigned)R ? at - (unsigned)R : at;
-  };
-  if (threadIdx.x < 64) {
-    const int b = b0 + (int)threadIdx.x;
-    if (b < count) ring_keep[slot_of(b)] = (exclude_alarms && alarm[b] != 0) ? 0 : 1;
-  }
-  for (int s0 = 0; s0 < n; s0 += 64) {
-    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
-      const int b = b0 + r, s = s0 + lane;
-      if (b < count && s < n) {
-        const size_t o = (size_t)b * n + s;
-        const bool keep = !(exclude_alarms && alarm[b] != 0) && valid[o] != 0;
-        const double e = score_key(pred[o], chunk[o]);
-        tile[r][lane] = keep ? e : filler_key();
-      }
-    }
-    __syncthreads();
-    const int b = b0 + lane;                                 // now the lane runs along the push's rows = ring slots
-    if (b < count) {
-      const unsigned slot = slot_of(b);
-      for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
-        const int s = s0 + r;
-        if (s < n) ring_keys[(size_t)s * R + slot] = tile[lane][r];
-      }
-    }
-    __syncthreads();                                         // the tile is rewritten by the next sensor tile
-  }
+  const RingSource rs{pred, chunk, alarm, valid, ring_keys, ring_keep, ring_base(state, R)};
+  ring_write_tile<MODE>(rs, blockIdx.x * 64, count, n, R, exclude_alarms, threadIdx.x);
 }
 
 bool calib_shape_ok(int n, int R) {
   return n >= 1 && n <= 4096 && R >= GDN_CALIB_MIN_R && R <= GDN_CALIB_MAX_R && 8ll * n * R <= (2ll << 30);
 }
 
-template <bool GAPS>
+template <int MODE>
 int calib_write(const void* state, const float* pred, const float* chunk, const int32_t* alarm, const uint8_t* valid,
                 int c, int count, int n, int R, int exclude_alarms, double* ring_keys, uint8_t* ring_keep,
                 void* stream) {
-  if (!state || !pred || !chunk || !alarm || !ring_keys || !ring_keep || (GAPS && !valid)) return GDN_ERR_ARG;
+  if (!state || !pred || !chunk || !alarm || !ring_keys || !ring_keep || (MODE != CALIB_PLAIN && !valid))
+    return GDN_ERR_ARG;
   if (count < 1 || count > c) return GDN_ERR_ARG;
   if (!calib_shape_ok(n, R)) return GDN_ERR_UNSUPPORTED;
   if (c > R) return GDN_ERR_ARG;                   // two rows of one push would share a slot
-  hipLaunchKernelGGL(gdn_stream_calib_write_kernel<GAPS>, dim3(((unsigned)count + 63) / 64), dim3(GDN_STREAM_THREADS),
+  hipLaunchKernelGGL(gdn_stream_calib_write_kernel<MODE>, dim3(((unsigned)count + 63) / 64), dim3(GDN_STREAM_THREADS),
                      0, (hipStream_t)stream, state, pred, chunk, alarm, valid, count, n, R, exclude_alarms, ring_keys,
                      ring_keep);
   return gdn_launch_status();
@@ -247,29 +155,23 @@ extern "C" long long gdn_stream_calib_bytes(int n, int R) {
 extern "C" int gdn_stream_calib_write(const void* state, const float* pred, const float* chunk, const int32_t* alarm,
                                       int c, int count, int n, int R, int exclude_alarms, double* ring_keys,
                                       uint8_t* ring_keep, void* stream) {
-  return calib_write<false>(state, pred, chunk, alarm, nullptr, c, count, n, R, exclude_alarms, ring_keys, ring_keep,
-                            stream);
+  return calib_write<CALIB_PLAIN>(state, pred, chunk, alarm, nullptr, c, count, n, R, exclude_alarms, ring_keys,
+                                  ring_keep, stream);
 }
 
 extern "C" int gdn_stream_calib_write_gaps(const void* state, const float* pred, const float* chunk,
                                            const int32_t* alarm, const uint8_t* valid, int c, int count, int n, int R,
                                            int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream) {
-  return calib_write<true>(state, pred, chunk, alarm, valid, c, count, n, R, exclude_alarms, ring_keys, ring_keep,
-                           stream);
+  return calib_write<CALIB_GAPS>(state, pred, chunk, alarm, valid, c, count, n, R, exclude_alarms, ring_keys,
+                                 ring_keep, stream);
 }
 
 extern "C" int gdn_stream_calib_write_sensor(const void* state, const float* pred, const float* chunk,
                                              const int32_t* alarm, const uint8_t* valid, int c, int count, int n,
                                              int R, int exclude_alarms, double* ring_keys, uint8_t* ring_keep,
                                              void* stream) {
-  if (!state || !pred || !chunk || !alarm || !valid || !ring_keys || !ring_keep) return GDN_ERR_ARG;
-  if (count < 1 || count > c) return GDN_ERR_ARG;
-  if (!calib_shape_ok(n, R)) return GDN_ERR_UNSUPPORTED;
-  if (c > R) return GDN_ERR_ARG;                   // two rows of one push would share a slot
-  hipLaunchKernelGGL(gdn_stream_calib_write_sensor_kernel, dim3(((unsigned)count + 63) / 64),
-                     dim3(GDN_STREAM_THREADS), 0, (hipStream_t)stream, state, pred, chunk, alarm, valid, count, n, R,
-                     exclude_alarms, ring_keys, ring_keep);
-  return gdn_launch_status();
+  return calib_write<CALIB_SENSOR>(state, pred, chunk, alarm, valid, c, count, n, R, exclude_alarms, ring_keys,
+                                   ring_keep, stream);
 }
 
 extern "C" long long gdn_stream_state_bytes(int n, int w) {

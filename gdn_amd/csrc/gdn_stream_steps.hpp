@@ -3,7 +3,7 @@
 // run of ticks with the carried smoothing state, the hist roll, and the carry / ordered log compaction / counters.
 // A kernel decides which state, which rows and which count a workgroup works on and calls the step; a fleet is a
 // stream per unit, so a unit's state block is written bit for bit as the single stream writes it.  The hold of
-// missing readings (stream_fill_group) is a step like the others.
+// missing readings (stream_fill_group) and the write of the calibration ring (ring_write_tile) are steps like the others.
 // The float64 scoring arithmetic is gdn_score_sweep.hpp's (no FMA contraction in a unit that includes this header).
 #pragma once
 #include "gdn_score_sweep.hpp"
@@ -85,6 +85,99 @@ __device__ __forceinline__ void stream_window_span(const void* __restrict__ stat
 __device__ __forceinline__ unsigned calib_slot(unsigned base, int b, int R) {
   const unsigned at = base + (unsigned)b;
   return at >= (unsigned)R ? at - (unsigned)R : at;
+}
+
+// The ring write of a push (include/gdn_hip.h "Rolling calibration"), ONE source for a stream and for a unit of a
+// fleet.  Row b is stream tick ticks + b; which of its keys are real follows the MODE:
+//   PLAIN   a tick is kept unless it alarmed under exclude_alarms; a tick not kept writes the filler and keep = 0;
+//   GAPS    ... or unless a reading of it was missing (valid);
+//   SENSOR  keep = the alarm rule alone; the key of a missing reading is the filler, the tick's others are real.
+// A kept tick writes score_key(pred, chunk) per sensor and keep = 1; a tick not kept leaves no older tick in its slot.
+enum { CALIB_PLAIN = 0, CALIB_GAPS = 1, CALIB_SENSOR = 2 };
+
+// What one stream's (one unit's) ring write reads and writes: the push's rows, the ring, and base = ticks mod R.
+struct RingSource {
+  const float *pred, *chunk;
+  const int* alarm;
+  const unsigned char* valid;        // PLAIN: not read
+  double* keys;                      // [n, R]
+  unsigned char* keep;               // [R]
+  unsigned base;
+};
+__device__ __forceinline__ unsigned ring_base(const void* state, int R) {
+  return (unsigned)(reinterpret_cast<const long long*>(state)[0] % (long long)R);       // < R <= 2^20
+}
+// does tick b count?  All 64 lanes of a wave call it (GAPS: an __all over the row's validity bytes).
+template <int MODE>
+__device__ __forceinline__ bool ring_keep_row(const RingSource& rs, int b, int n, int exclude_alarms, int lane) {
+  bool keep = !(exclude_alarms && rs.alarm[b] != 0);
+  if constexpr (MODE == CALIB_GAPS) {
+    bool real = true;
+    for (int s0 = 0; s0 < n; s0 += 64) {
+      const int s = s0 + lane;
+      real = real && (s >= n || rs.valid[(size_t)b * n + s] != 0);
+    }
+    keep = keep && __all(real);
+  }
+  return keep;
+}
+// the key of reading o = b * n + s of a tick whose keep flag is `keep`
+template <int MODE>
+__device__ __forceinline__ double ring_key(const RingSource& rs, size_t o, bool keep) {
+  if constexpr (MODE == CALIB_SENSOR) keep = keep && rs.valid[o] != 0;
+  const double e = score_key(rs.pred[o], rs.chunk[o]);
+  return keep ? e : filler_key();
+}
+
+// A workgroup of GDN_STREAM_THREADS threads, rows [b0, min(b0 + 64, count)) of the push: the keep flags (wave wv owns
+// rows wv, wv + 4, ..), then sensor tiles of 64 transposed through the padded LDS tile of score_keys_kernel: fp32 reads
+// along sensors, fp64 writes along slots.  The slot is computed per row: a tile may wrap the ring's end once.  Every
+// thread of the workgroup must call it (barriers inside); b0 < count.
+template <int MODE>
+__device__ __forceinline__ void ring_write_tile(const RingSource& rs, int b0, int count, int n, int R,
+                                                int exclude_alarms, int tid) {
+  __shared__ double tile[64][65];
+  __shared__ int keep_row[64];
+  const int lane = tid & 63, wv = tid >> 6;
+  // PLAIN, GAPS: a tick is kept or not as a whole; the flag travels through LDS to the store phase, where the lane
+  // runs along the rows, and the tile carries every key.  SENSOR: the flag is the alarm rule alone, a thread per row
+  // writes it, and the tile carries the filler in the place of a key (no keep_row, one barrier fewer: measured).
+  constexpr bool BY_ROW = MODE != CALIB_SENSOR;
+  if constexpr (BY_ROW) {
+    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) { // (wave uniform)
+      const int b = b0 + r;
+      if (b >= count) break;
+      const bool keep = ring_keep_row<MODE>(rs, b, n, exclude_alarms, lane);
+      if (lane == 0) {
+        keep_row[r] = keep ? 1 : 0;
+        rs.keep[calib_slot(rs.base, b, R)] = keep ? 1 : 0;
+      }
+    }
+    __syncthreads();
+  } else {
+    const int b = b0 + tid;
+    if (tid < 64 && b < count)
+      rs.keep[calib_slot(rs.base, b, R)] = ring_keep_row<MODE>(rs, b, n, exclude_alarms, lane) ? 1 : 0;
+  }
+  for (int s0 = 0; s0 < n; s0 += 64) {
+    for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
+      const int b = b0 + r, s = s0 + lane;
+      if (b < count && s < n)
+        tile[r][lane] = ring_key<MODE>(rs, (size_t)b * n + s,
+                                       BY_ROW || ring_keep_row<MODE>(rs, b, n, exclude_alarms, lane));
+    }
+    __syncthreads();
+    const int b = b0 + lane;                                 // now the lane runs along the push's rows = ring slots
+    if (b < count) {
+      const unsigned slot = calib_slot(rs.base, b, R);
+      const bool keep = !BY_ROW || keep_row[lane] != 0;
+      for (int r = wv; r < 64; r += GDN_STREAM_THREADS / 64) {
+        const int s = s0 + r;
+        if (s < n) rs.keys[(size_t)s * R + slot] = keep ? tile[lane][r] : filler_key();
+      }
+    }
+    __syncthreads();                                         // the tile is rewritten by the next sensor tile
+  }
 }
 
 // Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it

@@ -2171,7 +2171,137 @@ def _check_stream_head(model):
         raise model._refusal("refuse_outlayer")            # (GDN.mlp_fast_path_supported's answer, from host facts)
 
 
-class StreamDetector:
+def _seed_ring(ring_keys, ring_keep, pred, gt, keep=None, valid=None):
+    """Seed the ring (ring_keys [n, R], ring_keep [R]) of a stream or of one unit of a fleet: the keys of the last
+    s = min(R, t) rows of a period normal by declaration, oldest first, into slots R - s .. R - 1 with keep = 1 (no
+    alarm is excluded): the stream starts at slot 0, so it overwrites the empty slots first and the oldest seeded tick
+    last.  `keep` [t] uint8 (a calibration with missing readings): a tick that is not complete gets the filler and
+    keep = 0, as gdn_stream_calib_write_gaps would have left it.  `valid` [t, n] uint8 (calib="sensor") takes keep's
+    place: every tick is kept and the filler sits in the keys of its missing readings, as
+    gdn_stream_calib_write_sensor would have left it."""
+    R = ring_keep.shape[0]
+    s = min(R, pred.shape[0])
+    if valid is not None:
+        keys, keep = ops.score_keys(pred[-s:], gt[-s:], s, valid=valid[-s:]), None
+    else:
+        keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
+    if keep is None:
+        ring_keep[R - s:].fill_(1)
+    else:
+        ring_keep[R - s:].copy_(keep[-s:])
+    ring_keys[:, R - s:].copy_(keys)
+
+
+def _episodes(events, m: int, cap: int) -> Episodes:
+    """The episode table of one events allocation (a stream's, or one unit's block of a fleet's), as views."""
+    carry, start, end, peak_tick, peak, sensors = ops.stream_events_views(events, m, cap)
+    return Episodes(start, end, peak, peak_tick, sensors, carry[:1])
+
+
+def _check_calib_gaps(calib, calib_gaps):
+    if calib == "sensor" and not calib_gaps:
+        raise ValueError("calib='sensor' calibrates every sensor on its own real readings: pass calib_gaps=True "
+                         "(and gaps=True) too")
+
+
+def _check_calib_period(series, calib_gaps, gaps, who: str):
+    """What the two from_calibration refuse about gaps= / calib_gaps= and the period, by name (`who`: what is built)."""
+    if calib_gaps and not gaps:
+        raise ValueError(f"calib_gaps=True calibrates under the rules of a gaps=True {who}: pass gaps=True too")
+    if gaps and not calib_gaps and isinstance(series, torch.Tensor) and not bool(torch.isfinite(series).all()):
+        raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
+                         "stream, not the calibration (fill or cut the period first)")
+
+
+def _calibrate_period(model, series, w: int, batch: int, calib_gaps: bool, min_kept: int, calib: str, seed: bool):
+    """ONE SeriesEvaluator step over a period `series` [n, T > w] known to be normal: (med_iqr, threshold = the period's
+    largest anomaly score, the period's — with calib_gaps: the FILLED period's — last w ticks, kept, counts, and with
+    `seed` the rows a ring is seeded from: (pred, y, keep, valid under calib="sensor"), else None).  Views of the
+    evaluator's tensors."""
+    if calib_gaps:
+        ev = SeriesEvaluator(model, None, None, batch=batch, use_graph=False, series=series, gaps=True,
+                             min_kept=min_kept, calib=calib)
+    else:
+        ev = SeriesEvaluator(model, None, series[:, w:].t().contiguous(), batch=batch, use_graph=False, series=series)
+    threshold = ev.step().max()
+    rows = (ev.pred, ev.y, ev.keep, ev.valid if calib == "sensor" else None) if seed else None
+    return ev.med_iqr, threshold, ev.series[:, -w:], ev.kept, ev.counts, rows
+
+
+class _StreamCore:
+    """What StreamDetector and StreamFleet state once on the host: the rules of the options they share, the static
+    buffers of a push under a leading shape (() for a stream, (units,) for a fleet), the question whether the forward
+    is the guarded launch, and recal_every's clock.  The wording that differs between the two comes from the caller."""
+
+    def _set_calib(self, calib, gaps, recal):
+        _check_calib(calib)
+        if calib == "sensor" and not (gaps and int(recal) > 0):
+            raise ValueError("calib='sensor' recalibrates every sensor on its own real readings: it needs gaps=True and "
+                             "a calibration ring (recal=R)")
+        self.calib = calib
+
+    def _check_lists(self, top_m, log, entries: str):
+        _check_top_m(top_m, self.n)
+        if int(log) < 0:
+            raise ValueError(f"log = {log}: the alarm log holds 0 or more {entries}")
+
+    def _set_recal(self, recal, exclude_alarms, recal_every, recal_min, ring_bytes, no_ring: str):
+        """recal, exclude_alarms, recal_every and recal_min (default max(64, R // 4)): host facts only.  `ring_bytes()`
+        asks the library for the size of the ring(s), 0: none for this shape, refused with `no_ring`."""
+        self.recal, self.exclude_alarms, self.recal_every = int(recal), bool(exclude_alarms), int(recal_every)
+        self.recal_min = 0
+        if self.recal_every < 0 or (self.recal_every and not self.recal):
+            raise ValueError(f"recal_every = {recal_every}: recalibrating every so many ticks needs a calibration ring "
+                             "(recal=R) and a positive number of ticks")
+        if self.recal:
+            if self.recal < self.chunk:
+                raise ValueError(f"recal = {recal}: the calibration ring must hold at least one push of chunk = "
+                                 f"{self.chunk} ticks (no two rows of a push may share a slot)")
+            if ring_bytes() <= 0:
+                raise ValueError(f"recal = {recal}: {no_ring}")
+            self.recal_min = max(64, self.recal // 4) if recal_min is None else int(recal_min)
+            if not 1 <= self.recal_min <= self.recal:
+                raise ValueError(f"recal_min = {recal_min}: between 1 and recal = {self.recal} kept ticks")
+        elif recal_min is not None:
+            raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
+
+    def _alloc_push(self, lead: tuple, log, dev):
+        """The static buffers of a push, zeros: per stream under `lead` = (), per unit under (units,)."""
+        c, n, w, m = self.chunk, self.n, self.w, self.top_m
+
+        def zeros(shape, dtype):
+            return torch.zeros(lead + shape, dtype=dtype, device=dev)
+        self.chunk_buf = zeros((c, n), torch.float32)
+        self.x = zeros((c, n, w), torch.float32)
+        self.pred = zeros((c, n), torch.float32)
+        self.top_scores = zeros((c, m), torch.float64)
+        self.top_sensors = zeros((c, m), torch.int32)
+        self.alarm = zeros((c,), torch.int32)
+        self.log_ticks = zeros((int(log),), torch.int64) if log else None
+        self.log_sensors = zeros((int(log), m), torch.int32) if log else None
+        self.raw_buf = self.valid = self.gap_chunk = self.gaps = None
+        if self.with_gaps:
+            self.raw_buf = zeros((c, n), torch.float32)
+            self.valid = zeros((c, n), torch.uint8)
+            self.gap_chunk = zeros((2, n), torch.int32)
+            self.gaps = zeros((2, n), torch.int64)                   # missing_total, missing_run
+
+    # the launches of a push take static arguments only (they are captured)
+    def _guarded(self) -> bool:
+        m = self.model
+        if self.wide or m.operand_range != "auto" or m.out_layer_num != 1:
+            return False
+        c = m._constants()
+        return not c.large and m._plan(c, False) is not None
+
+    def _hand(self, ticks: int):
+        """recal_every's clock: `ticks` more model ticks were handed over; recalibrate when they cross a multiple of it."""
+        before, self._handed = self._handed, self._handed + ticks
+        if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
+            self.recalibrate()
+
+
+class StreamDetector(_StreamCore):
     """Scores ticks as they arrive against a frozen calibration, with nothing but launches per push.
 
     The stream's state lives on the device (include/gdn_hip.h "streaming detector"): the last w ticks of every sensor,
@@ -2255,11 +2385,7 @@ class StreamDetector:
         """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — the state is
         gdn_stream_state_bytes(n, w) of zeros, the table zeros, the threshold inf, all on `device`, `wide` the
         caller's word — and load_state_dict fills the allocations."""
-        _check_calib(calib)
-        if calib == "sensor" and not (gaps and int(recal) > 0):
-            raise ValueError("calib='sensor' recalibrates every sensor on its own real readings: it needs gaps=True and "
-                             "a calibration ring (recal=R)")
-        self.calib = calib
+        self._set_calib(calib, gaps, recal)
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -2269,27 +2395,12 @@ class StreamDetector:
         if self.chunk * n * w * 4 > _VALIDATE_CHUNK_BYTES:
             raise ValueError(f"chunk = {chunk}: the window buffer [{chunk}, {n}, {w}] fp32 exceeds "
                              f"{_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
-        _check_top_m(top_m, n)
-        if int(log) < 0:
-            raise ValueError(f"log = {log}: the alarm log holds 0 or more entries")
+        self._check_lists(top_m, log, "entries")
         self.events_cfg = None if events is None else events_config(events, self.top_m)     # host facts only
-        self.recal, self.exclude_alarms, self.recal_every = int(recal), bool(exclude_alarms), int(recal_every)
-        self.recal_min = 0
-        if self.recal_every < 0 or (self.recal_every and not self.recal):
-            raise ValueError(f"recal_every = {recal_every}: recalibrating every so many ticks needs a calibration ring "
-                             "(recal=R) and a positive number of ticks")
-        if self.recal:                                     # host facts only: before any device work
-            if self.recal < self.chunk:
-                raise ValueError(f"recal = {recal}: the calibration ring must hold at least one push of chunk = "
-                                 f"{self.chunk} ticks (no two rows of a push may share a slot)")
-            if _lib.load().gdn_stream_calib_bytes(n, self.recal) <= 0:
-                raise ValueError(f"recal = {recal}: no calibration ring for n = {n}, R = {recal} (1 <= n <= 4096, "
-                                 "64 <= R <= 2^20, 8 n R <= 2 GiB)")
-            self.recal_min = max(64, self.recal // 4) if recal_min is None else int(recal_min)
-            if not 1 <= self.recal_min <= self.recal:
-                raise ValueError(f"recal_min = {recal_min}: between 1 and recal = {self.recal} kept ticks")
-        elif recal_min is not None:
-            raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
+        self._set_recal(recal, exclude_alarms, recal_every, recal_min,                      # ... before any device work
+                        lambda: _lib.load().gdn_stream_calib_bytes(n, self.recal),
+                        f"no calibration ring for n = {n}, R = {recal} (1 <= n <= 4096, 64 <= R <= 2^20, "
+                        "8 n R <= 2 GiB)")
         _check_stream_head(model)
         self.with_gaps = bool(gaps)
         if history is None:
@@ -2314,21 +2425,8 @@ class StreamDetector:
                                  "readings")
             self.state = ops.stream_state(history, w)
             self.wide = model.wide_for(history[:, -w:]) if wide is None else bool(wide)
-        c, m = self.chunk, self.top_m
-        self.chunk_buf = torch.zeros((c, n), dtype=torch.float32, device=dev)
-        self.x = torch.zeros((c, n, w), dtype=torch.float32, device=dev)
-        self.pred = torch.zeros((c, n), dtype=torch.float32, device=dev)
-        self.top_scores = torch.zeros((c, m), dtype=torch.float64, device=dev)
-        self.top_sensors = torch.zeros((c, m), dtype=torch.int32, device=dev)
-        self.alarm = torch.zeros((c,), dtype=torch.int32, device=dev)
-        self.log_ticks = torch.zeros((int(log),), dtype=torch.int64, device=dev) if log else None
-        self.log_sensors = torch.zeros((int(log), m), dtype=torch.int32, device=dev) if log else None
-        self.raw_buf = self.valid = self.gap_chunk = self.gaps = None
-        if self.with_gaps:
-            self.raw_buf = torch.zeros((c, n), dtype=torch.float32, device=dev)
-            self.valid = torch.zeros((c, n), dtype=torch.uint8, device=dev)
-            self.gap_chunk = torch.zeros((2, n), dtype=torch.int32, device=dev)
-            self.gaps = torch.zeros((2, n), dtype=torch.int64, device=dev)      # missing_total, missing_run
+        m = self.top_m
+        self._alloc_push((), log, dev)
         self.events = self.clear = None
         if self.events_cfg is not None:
             # the clear level: a float64 scalar on the device (None: the raise level at construction); load() fills it
@@ -2385,60 +2483,24 @@ class StreamDetector:
         `calib_kept` is the smallest per-sensor count, `calib_counts` [n] int32 (device) all of them.  Without a ring
         (recal = 0) only the calibration follows it: the detector has nothing to recalibrate."""
         calib = kw.get("calib", "tick")
-        if calib == "sensor" and not calib_gaps:
-            raise ValueError("calib='sensor' calibrates every sensor on its own real readings: pass calib_gaps=True "
-                             "(and gaps=True) too")
+        _check_calib_gaps(calib, calib_gaps)
         series = ops._chk(series, name="series")
-        if calib_gaps and not kw.get("gaps"):
-            raise ValueError("calib_gaps=True calibrates under the rules of a gaps=True detector: pass gaps=True too")
-        if kw.get("gaps") and not calib_gaps and not bool(torch.isfinite(series).all()):
-            raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
-                             "stream, not the calibration (fill or cut the period first)")
+        _check_calib_period(series, calib_gaps, kw.get("gaps"), "detector")
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         if series.dim() != 2 or series.shape[1] <= w:
             raise ValueError(f"calibration needs a series [n, T] with T > {w}, got {tuple(series.shape)}")
-        if calib_gaps:
-            ev = SeriesEvaluator(model, None, None, batch=batch, use_graph=False, series=series, gaps=True,
-                                 min_kept=min_kept, calib=calib)
-        else:
-            ev = SeriesEvaluator(model, None, series[:, w:].t().contiguous(), batch=batch, use_graph=False, series=series)
-        anomaly = ev.step()
-        kw.setdefault("history", ev.series[:, -w:])
-        history = kw.pop("history")
-        if calib == "sensor" and not int(kw.get("recal", 0)):
+        R = int(kw.get("recal", 0))
+        table, threshold, tail, kept, counts, rows = _calibrate_period(model, series, w, batch, calib_gaps, min_kept,
+                                                                       calib, bool(R))
+        history = kw.pop("history", tail)
+        if calib == "sensor" and not R:
             kw["calib"] = "tick"            # no ring: the detector never calibrates anything itself
-        det = cls(model, ev.med_iqr, anomaly.max(), history, chunk, **kw)
-        det.calib_kept = ev.kept
-        det.calib_counts = ev.counts
+        det = cls(model, table, threshold, history, chunk, **kw)
+        det.calib_kept = kept
+        det.calib_counts = counts
         if det.recal:
-            det._seed(ev.pred, ev.y, ev.keep, ev.valid if calib == "sensor" else None)
+            _seed_ring(det.ring_keys, det.ring_keep, *rows)
         return det
-
-    def _seed(self, pred, gt, keep=None, valid=None):
-        """The keys of the last s = min(R, t) rows of a period normal by declaration, oldest first, into slots R - s ..
-        R - 1 with keep = 1 (no alarm is excluded): the stream starts at slot 0, so it overwrites the empty slots first
-        and the oldest seeded tick last.  `keep` [t] uint8 (a calibration with missing readings): a tick that is not
-        complete gets the filler and keep = 0, as gdn_stream_calib_write_gaps would have left it.  `valid` [t, n] uint8
-        (calib="sensor") takes keep's place: every tick is kept and the filler sits in the keys of its missing readings,
-        as gdn_stream_calib_write_sensor would have left it."""
-        s = min(self.recal, pred.shape[0])
-        if valid is not None:
-            keys, keep = ops.score_keys(pred[-s:], gt[-s:], s, valid=valid[-s:]), None
-        else:
-            keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
-        if keep is None:
-            self.ring_keep[self.recal - s:].fill_(1)
-        else:
-            self.ring_keep[self.recal - s:].copy_(keep[-s:])
-        self.ring_keys[:, self.recal - s:].copy_(keys)
-
-    # the launches of a push: static arguments only (they are captured)
-    def _guarded(self) -> bool:
-        m = self.model
-        if self.wide or m.operand_range != "auto" or m.out_layer_num != 1:
-            return False
-        c = m._constants()
-        return not c.large and m._plan(c, False) is not None
 
     def _launch(self, count: int, guard: bool):
         if self.with_gaps:
@@ -2499,12 +2561,6 @@ class StreamDetector:
             self._launch_prep(stage, rows, groups, self._guarded() if groups else False)
         self._pend_at ^= 1
         self.raw_pending = left
-
-    def _hand(self, ticks: int):
-        """recal_every's clock: `ticks` more model ticks were handed over; recalibrate when they cross a multiple of it."""
-        before, self._handed = self._handed, self._handed + ticks
-        if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
-            self.recalibrate()
 
     def _push_prep(self, ticks):
         if ticks.dtype not in (torch.float32, torch.float64):
@@ -2598,9 +2654,7 @@ class StreamDetector:
         moves them.  The open episode's row holds its peak so far and end = -1."""
         if self.events is None:
             raise ValueError("episodes(): the detector was built with events=None and keeps no episode table")
-        carry, start, end, peak_tick, peak, sensors = ops.stream_events_views(self.events, self.top_m,
-                                                                              self.events_cfg["cap"])
-        return Episodes(start, end, peak, peak_tick, sensors, carry[:1])
+        return _episodes(self.events, self.top_m, self.events_cfg["cap"])
 
     def localise(self, rows=None) -> Localisation:
         """harness.localise for the last push: which sensors deviate at its alarm rows (`rows=None`; or the given
@@ -2827,7 +2881,7 @@ def fleet_clear_levels(lo, threshold, units: int) -> torch.Tensor:
     return lo
 
 
-class StreamFleet:
+class StreamFleet(_StreamCore):
     """Scores the ticks of U units of ONE model with one push: a rack of identical servers, a line of identical pumps —
     the same sensor list and the same trained model, but a median / IQR table, a threshold, a history, counters and an
     alarm log per unit (include/gdn_hip.h "streaming fleet").
@@ -2890,11 +2944,7 @@ class StreamFleet:
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
                  calib: str = "tick"):
-        _check_calib(calib)
-        if calib == "sensor" and not (gaps and int(recal) > 0):
-            raise ValueError("calib='sensor' recalibrates every sensor on its own real readings: it needs gaps=True and "
-                             "a calibration ring (recal=R)")
-        self.calib = calib
+        self._set_calib(calib, gaps, recal)
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
@@ -2905,9 +2955,7 @@ class StreamFleet:
         fleet_check_shape(units, chunk, n, w)
         self.units, self.n, self.w, self.chunk, self.top_m = units, n, w, int(chunk), int(top_m)
         self.use_graph = bool(use_graph)
-        _check_top_m(top_m, n)
-        if int(log) < 0:
-            raise ValueError(f"log = {log}: the alarm log holds 0 or more entries per unit")
+        self._check_lists(top_m, log, "entries per unit")
         if not isinstance(med_iqr, torch.Tensor) or med_iqr.shape != (units, n, 2):
             raise ValueError(f"expected med_iqr of shape [{units}, {n}, 2], got "
                              f"{tuple(med_iqr.shape) if isinstance(med_iqr, torch.Tensor) else type(med_iqr)}")
@@ -2915,23 +2963,10 @@ class StreamFleet:
         if threshold.numel() not in (1, units) or threshold.dim() > 1:
             raise ValueError(f"threshold: one number or [{units}] of them, got {tuple(threshold.shape)}")
         # the options: host facts only, before any device work
-        self.recal, self.exclude_alarms, self.recal_every = int(recal), bool(exclude_alarms), int(recal_every)
-        self.recal_min = 0
-        if self.recal_every < 0 or (self.recal_every and not self.recal):
-            raise ValueError(f"recal_every = {recal_every}: recalibrating every so many ticks needs a calibration ring "
-                             "(recal=R) and a positive number of ticks")
-        if self.recal:
-            if self.recal < self.chunk:
-                raise ValueError(f"recal = {recal}: the calibration ring must hold at least one push of chunk = "
-                                 f"{self.chunk} ticks (no two rows of a push may share a slot)")
-            if _lib.load().gdn_fleet_calib_bytes(units, n, self.recal) <= 0:
-                raise ValueError(f"recal = {recal}: no calibration rings for units = {units}, n = {n}, R = {recal} "
-                                 "(1 <= units <= 4096, 1 <= n <= 4096, 64 <= R <= 2^20, 8 units n R <= 2 GiB)")
-            self.recal_min = max(64, self.recal // 4) if recal_min is None else int(recal_min)
-            if not 1 <= self.recal_min <= self.recal:
-                raise ValueError(f"recal_min = {recal_min}: between 1 and recal = {self.recal} kept ticks")
-        elif recal_min is not None:
-            raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
+        self._set_recal(recal, exclude_alarms, recal_every, recal_min,
+                        lambda: _lib.load().gdn_fleet_calib_bytes(units, n, self.recal),
+                        f"no calibration rings for units = {units}, n = {n}, R = {recal} (1 <= units <= 4096, "
+                        "1 <= n <= 4096, 64 <= R <= 2^20, 8 units n R <= 2 GiB)")
         self.with_gaps = bool(gaps)
         self.events_cfg = None if events is None else events_config({**events, "lo": None}, self.top_m)
         clear = None if events is None else fleet_clear_levels(events.get("lo"), threshold, units)
@@ -2946,22 +2981,9 @@ class StreamFleet:
         self.threshold = threshold.reshape(-1).expand(units).to(dev).clone()
         self.state = ops.fleet_state(history, w)
         self.wide = model.wide_for(history[:, :, -w:]) if wide is None else bool(wide)
-        c, m = self.chunk, self.top_m
-        self.chunk_buf = torch.zeros((units, c, n), dtype=torch.float32, device=dev)
+        m = self.top_m
         self.counts = torch.zeros((units,), dtype=torch.int32, device=dev)
-        self.x = torch.zeros((units, c, n, w), dtype=torch.float32, device=dev)
-        self.pred = torch.zeros((units, c, n), dtype=torch.float32, device=dev)
-        self.top_scores = torch.zeros((units, c, m), dtype=torch.float64, device=dev)
-        self.top_sensors = torch.zeros((units, c, m), dtype=torch.int32, device=dev)
-        self.alarm = torch.zeros((units, c), dtype=torch.int32, device=dev)
-        self.log_ticks = torch.zeros((units, int(log)), dtype=torch.int64, device=dev) if log else None
-        self.log_sensors = torch.zeros((units, int(log), m), dtype=torch.int32, device=dev) if log else None
-        self.raw_buf = self.valid = self.gap_chunk = self.gaps = None
-        if self.with_gaps:
-            self.raw_buf = torch.zeros((units, c, n), dtype=torch.float32, device=dev)
-            self.valid = torch.zeros((units, c, n), dtype=torch.uint8, device=dev)
-            self.gap_chunk = torch.zeros((units, 2, n), dtype=torch.int32, device=dev)
-            self.gaps = torch.zeros((units, 2, n), dtype=torch.int64, device=dev)    # missing_total, missing_run
+        self._alloc_push((units,), log, dev)
         self.events = self.clear = None
         if self.events_cfg is not None:
             self.events_cfg.pop("lo")
@@ -2993,21 +3015,14 @@ class StreamFleet:
         calibration itself knows no missing reading, so with gaps=True a series that is not finite is refused.
         `calib_gaps=True` (needs gaps=True), `min_kept=`, `calib="sensor"` (needs calib_gaps=True) and `recal=R` mean
         per unit what they mean to StreamDetector.from_calibration: the period is scored under the detector's own rules,
-        the default history is the FILLED period's last w ticks, and unit u's ring is seeded as StreamDetector._seed
-        seeds a detector's — with the period's keep flags under calib_gaps, through its validity plane under
+        the default history is the FILLED period's last w ticks, and unit u's ring is seeded as a detector's
+        is (_seed_ring) — with the period's keep flags under calib_gaps, through its validity plane under
         calib="sensor".  `calib_kept` [U] int64 (host; None without calib_gaps) and `calib_counts` [U, n] int32 (device;
         calib="sensor") are the detectors' per unit."""
         calib = kw.get("calib", "tick")
         _check_calib(calib)
-        if calib == "sensor" and not calib_gaps:
-            raise ValueError("calib='sensor' calibrates every sensor on its own real readings: pass calib_gaps=True "
-                             "(and gaps=True) too")
-        if calib_gaps and not kw.get("gaps"):
-            raise ValueError("calib_gaps=True calibrates under the rules of a gaps=True fleet: pass gaps=True too")
-        if (kw.get("gaps") and not calib_gaps and isinstance(series, torch.Tensor)
-                and not bool(torch.isfinite(series).all())):
-            raise ValueError("series: the calibration period holds a value that is not finite; gaps=True fills the "
-                             "stream, not the calibration (fill or cut the period first)")
+        _check_calib_gaps(calib, calib_gaps)
+        _check_calib_period(series, calib_gaps, kw.get("gaps"), "fleet")
         series = ops._chk(series, name="series")
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         if series.dim() != 3 or series.shape[2] <= w:
@@ -3018,21 +3033,16 @@ class StreamFleet:
             kw["calib"] = "tick"            # no ring: the fleet never calibrates anything itself
         tables, thresholds, histories, seeds, kept, counts = [], [], [], [], [], []
         for unit in series:
-            if calib_gaps:
-                ev = SeriesEvaluator(model, None, None, batch=batch, use_graph=False, series=unit, gaps=True,
-                                     min_kept=min_kept, calib=calib)
-            else:
-                ev = SeriesEvaluator(model, None, unit[:, w:].t().contiguous(), batch=batch, use_graph=False,
-                                     series=unit)
-            thresholds.append(ev.step().max())
-            tables.append(ev.med_iqr.clone())
-            histories.append(ev.series[:, -w:].clone())
-            kept.append(ev.kept)
-            counts.append(ev.counts)
-            if R:                            # the rows _seed would read: the period's last min(R, T - w)
-                s = min(R, ev.pred.shape[0])
-                seeds.append(tuple(None if t is None else t[-s:].clone()
-                                   for t in (ev.pred, ev.y, ev.keep, ev.valid if calib == "sensor" else None)))
+            table, threshold, tail, k, cnt, rows = _calibrate_period(model, unit, w, batch, calib_gaps, min_kept, calib,
+                                                                     bool(R))
+            thresholds.append(threshold)
+            tables.append(table.clone())
+            histories.append(tail.clone())
+            kept.append(k)
+            counts.append(cnt)
+            if R:                            # the rows _seed_ring would read: the period's last min(R, T - w)
+                s = min(R, rows[0].shape[0])
+                seeds.append(tuple(None if t is None else t[-s:].clone() for t in rows))
         history = kw.pop("history", None)
         fleet = cls(model, torch.stack(tables), torch.stack(thresholds),
                     torch.stack(histories) if history is None else history, chunk, **kw)
@@ -3040,30 +3050,9 @@ class StreamFleet:
             fleet.calib_kept = torch.as_tensor([int(k) for k in kept], dtype=torch.int64)
         if calib == "sensor":
             fleet.calib_counts = torch.stack(counts)
-        for u, (pred, gt, keep, valid) in enumerate(seeds):
-            fleet._seed(u, pred, gt, keep, valid)
+        for u, rows in enumerate(seeds):
+            _seed_ring(fleet.ring_keys[u], fleet.ring_keep[u], *rows)
         return fleet
-
-    def _seed(self, u: int, pred, gt, keep=None, valid=None):
-        """StreamDetector._seed on unit u's slices of the rings."""
-        s = min(self.recal, pred.shape[0])
-        if valid is not None:
-            keys, keep = ops.score_keys(pred[-s:], gt[-s:], s, valid=valid[-s:]), None
-        else:
-            keys = ops.score_keys(pred[-s:], gt[-s:], s, keep=None if keep is None else keep[-s:])
-        if keep is None:
-            self.ring_keep[u, self.recal - s:].fill_(1)
-        else:
-            self.ring_keep[u, self.recal - s:].copy_(keep[-s:])
-        self.ring_keys[u, :, self.recal - s:].copy_(keys)
-
-    # the launches of a push: static arguments only (they are captured)
-    def _guarded(self) -> bool:
-        m = self.model
-        if self.wide or m.operand_range != "auto" or m.out_layer_num != 1:
-            return False
-        c = m._constants()
-        return not c.large and m._plan(c, False) is not None
 
     def _launch(self, guard: bool):
         rows = self.units * self.chunk
@@ -3110,9 +3099,7 @@ class StreamFleet:
                 self.counts.copy_((counts - s).clamp_(0, r).to(torch.int32))
             self._last = r
             self._full()
-            before, self._handed = self._handed, self._handed + r
-            if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
-                self.recalibrate()
+            self._hand(r)
         r = self._last
         return self.top_scores[:, :r], self.top_sensors[:, :r], self.alarm[:, :r]
 
@@ -3184,6 +3171,4 @@ class StreamFleet:
             raise ValueError("episodes(): the fleet was built with events=None and keeps no episode tables")
         if not 0 <= int(u) < self.units:
             raise ValueError(f"episodes({u}): the fleet has units 0 .. {self.units - 1}")
-        carry, start, end, peak_tick, peak, sensors = ops.stream_events_views(self.events[int(u)], self.top_m,
-                                                                              self.events_cfg["cap"])
-        return Episodes(start, end, peak, peak_tick, sensors, carry[:1])
+        return _episodes(self.events[int(u)], self.top_m, self.events_cfg["cap"])

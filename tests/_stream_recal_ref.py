@@ -103,6 +103,52 @@ def brute_force(pred, gt, alarm, R, exclude_alarms=True, valid=None):
     return keys, keep
 
 
+# The stage test of the ring write alone (test_gpu_stream_recal.py): ONE launch on a ring full of a sentinel, from a
+# staged tick counter.  The shapes are the smallest at which the 64 x 64 tile can go wrong: one sensor, a full tile, one
+# past it, two tiles and one; one row, one short of a tile, a full tile, one past it (a second workgroup).
+SENTINEL_KEY, SENTINEL_KEEP = 123.0, 9
+STAGE_N = (1, 64, 65, 129)
+STAGE_COUNT_R = [(count, R) for R in (64, 130) for count in (1, 63, 64, 65) if count <= R]
+
+
+def stage_ticks(count, R):
+    """The staged tick counters: the ring's first slot, its last, and a second lap placed so that the push straddles
+    the ring's end (slot R - (count + 1) // 2: a 64-row tile wraps inside)."""
+    return (0, R - 1, 2 * R - (count + 1) // 2)
+
+
+def stage_inputs(n, count, seed=0):
+    """(pred, chunk [count, n] fp32, alarm [count] int32, valid [count, n] uint8) of one launch.  About one tick in
+    four alarms and about one in three has a missing reading; then, by construction: the first row alarms and — from
+    two rows on — has a missing reading (a broken tick), the last row does neither (a complete tick, no alarm)."""
+    rng = np.random.default_rng(100003 * seed + 131 * n + count)
+    pred, chunk = rng.random((count, n), dtype=np.float32), rng.random((count, n), dtype=np.float32)
+    alarm = (rng.random(count) < 0.25).astype(np.int32)
+    valid = (rng.random((count, n)) >= 1.0 - (2.0 / 3.0) ** (1.0 / n)).astype(np.uint8)
+    alarm[0], valid[0, n // 2] = 1, 0
+    alarm[count - 1], valid[count - 1] = 0, 1
+    return pred, chunk, alarm, valid
+
+
+def stage_ring(mode, n, R, ticks, exclude_alarms, pred, chunk, alarm, valid):
+    """The ring after ONE push at stream tick `ticks` onto a ring full of the sentinel, `mode` "plain", "gaps" or
+    "sensor" (tests/_sensor_calib_ref.py's ring): (keys [n, R] as uint64 bit patterns, keep [R] uint8)."""
+    if mode == "sensor":
+        import _sensor_calib_ref
+        ring = _sensor_calib_ref.SensorRing(n, R, exclude_alarms)
+        ring.keys[...] = bits(np.full((n, R), SENTINEL_KEY))
+    else:
+        ring = CalibRing(n, R, exclude_alarms=exclude_alarms)
+        ring.keys[...] = SENTINEL_KEY
+    ring.keep[...] = SENTINEL_KEEP
+    ring.ticks = ticks
+    if mode == "plain":
+        ring.push(pred, chunk, alarm)
+    else:
+        ring.push(pred, chunk, alarm, valid.astype(bool))
+    return bits(ring.keys.view(np.float64)), ring.keep
+
+
 class SwitchedStreamRef(_stream_ref.StreamRef):
     """StreamRef whose table can be replaced between pushes: the carry keeps the normalised errors it holds (they were
     computed with the table in force at their tick), everything from the next push on uses the new table."""

@@ -250,3 +250,35 @@ def test_the_command_line_knows_the_two_flags():
     assert (args.stream, args.stream_recal, args.stream_recal_every) == (16, 4096, 500)
     args = cli.build_parser().parse_args([])
     assert (args.stream_recal, args.stream_recal_every) == (0, 0)
+
+
+# ------------------------------------------------------------------------------------------- the staged ring write
+@pytest.mark.parametrize("n", rref.STAGE_N)
+@pytest.mark.parametrize("mode", ["plain", "gaps", "sensor"])
+def test_the_staged_ring_write_cases_meet_a_kept_tick_a_filler_and_the_rings_end(mode, n):
+    """The reference alone, on the inputs of the GPU stage test (test_gpu_stream_recal.py): every (mode, n) meets a
+    kept tick and a filler, the inputs hold a complete and a broken tick, an alarm on the first row and none on the
+    last, exactly `count` slots leave the sentinel, and the third staged counter wraps the ring's end inside a push."""
+    met_kept = met_filler = wrapped = False
+    sentinel = rref.bits(np.array(rref.SENTINEL_KEY))
+    for count, R in rref.STAGE_COUNT_R:
+        pred, chunk, alarm, valid = rref.stage_inputs(n, count)
+        assert alarm[-1] == 0 and valid[-1].all()
+        assert count == 1 or (alarm[0] != 0 and not valid[0].all())
+        assert rref.stage_ticks(count, R)[:2] == (0, R - 1)
+        for ticks in rref.stage_ticks(count, R):
+            for exclude in (True, False):
+                keys, keep = rref.stage_ring(mode, n, R, ticks, exclude, pred, chunk, alarm, valid)
+                written = keep != rref.SENTINEL_KEEP
+                assert int(written.sum()) == count and set(keep[written]) <= {0, 1}
+                assert ((keys != sentinel).all(axis=0) == written).all()
+                slots = (ticks + np.arange(count)) % R
+                assert written[slots].all()
+                wrapped |= count > 1 and slots[0] > slots[-1]
+                # a slot that is not kept holds the filler in every sensor
+                assert (keys[:, keep == 0] == rref.FILLER_BITS).all()
+                if mode != "sensor":
+                    assert not (keys[:, keep == 1] == rref.FILLER_BITS).any()
+                met_kept |= bool((keep == 1).any())
+                met_filler |= bool((keys == rref.FILLER_BITS).any())
+    assert met_kept and met_filler and wrapped

@@ -159,6 +159,46 @@ def test_the_ring_writer_only_reads_the_stream(shape, use_graph, gpu_device):
         plain.recalibrate()
 
 
+# ------------------------------------------------------------------------------------------------ the ring write alone
+@pytest.mark.parametrize("n", rref.STAGE_N)
+@pytest.mark.parametrize("mode", ["plain", "gaps", "sensor"])
+def test_one_ring_write_launch_equals_numpy_from_a_staged_tick_counter(mode, n, gpu_device):
+    """ops.stream_calib_write alone, against numpy (tests/_stream_recal_ref.py, tests/_sensor_calib_ref.py's ring) and
+    no device code: the one body a stream and a fleet's units share has no other anchor outside itself.  One launch
+    per (count = c, R, staged tick counter, exclude_alarms) onto a ring full of a sentinel: keys as bit patterns, keep
+    flags, exactly `count` keep bytes changed, the state as it was.  (tests/test_cpu_stream_recal.py shows on the
+    reference alone that every (mode, n) here meets a kept tick and a filler.)"""
+    from gdn_amd import ops
+    dev = gpu_device
+    met_kept = met_filler = False
+    for count, R in rref.STAGE_COUNT_R:
+        pred, chunk, alarm, valid = rref.stage_inputs(n, count)
+        assert alarm[0] != 0 or count == 1
+        assert alarm[-1] == 0 and valid[-1].all() and (count == 1 or not valid[0].all())
+        on_dev = [torch.from_numpy(a).to(dev) for a in (pred, chunk, alarm, valid)]
+        for ticks in rref.stage_ticks(count, R):
+            for exclude in (True, False):
+                what = (mode, n, count, R, ticks, exclude)
+                want_keys, want_keep = rref.stage_ring(mode, n, R, ticks, exclude, pred, chunk, alarm, valid)
+                state = ops.stream_state_empty(n, 1, dev)
+                state[0] = ticks
+                before = state.clone()
+                ring_keys, ring_keep = ops.stream_calib_ring(n, R, dev)
+                ring_keys.fill_(rref.SENTINEL_KEY)
+                ring_keep.fill_(rref.SENTINEL_KEEP)
+                ops.stream_calib_write(state, on_dev[0], on_dev[1], on_dev[2], ring_keys, ring_keep, exclude,
+                                       count=count, valid=None if mode == "plain" else on_dev[3],
+                                       by_sensor=mode == "sensor")
+                got_keys, got_keep = _bits(ring_keys).cpu().numpy(), ring_keep.cpu().numpy()
+                np.testing.assert_array_equal(got_keys, want_keys.view(np.int64), err_msg=str(what))
+                np.testing.assert_array_equal(got_keep, want_keep, err_msg=str(what))
+                assert int((got_keep != rref.SENTINEL_KEEP).sum()) == count, what
+                assert torch.equal(state, before), what
+                met_kept |= bool((want_keep == 1).any())
+                met_filler |= bool((want_keys == rref.FILLER_BITS).any())
+    assert met_kept and met_filler, (mode, n)
+
+
 # ------------------------------------------------------------------------------------------------ recalibrate
 def _device_order_switch(delta, tables, sizes, m, threshold):
     """_stream_recal_ref.run_switched with the normalised error as the kernels round it, (delta - med) * (1 / den)
