@@ -155,6 +155,8 @@ SIGNATURES = {
     "gdn_fleet_calib_write_gaps": [_p] * 6 + [_c_int] * 6 + [_p] * 3,
     "gdn_fleet_calib_write_sensor": [_p] * 6 + [_c_int] * 6 + [_p] * 3,
     "gdn_fleet_ring_counts": [_p, _p, _c_int, _c_int, _c_int, _p, _p, _p],
+    "gdn_fleet_prep_bytes": [_c_int] * 3,
+    "gdn_fleet_prep_ticks": [_p, _c_int, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4,
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

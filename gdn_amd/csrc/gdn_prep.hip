@@ -3,6 +3,8 @@
 // gdn_prep_stats (min / max / mean / count per sensor over its finite readings: what a min-max fit and a mean fill
 // need), gdn_prep_series (a resident raw file -> the prepared sensor-major series) and gdn_prep_ticks (the stream's
 // front end: raw ticks and the pending tail of the push before -> tick-major model ticks and the new tail).
+// gdn_fleet_prep_ticks ("Raw readings of a fleet") is that front end per unit of a streaming fleet in one launch, the
+// open groups and their lengths on the device.
 // Raw data is tick-major [t_raw, n], fp32 or float64 (one template parameter); lanes run along sensors, so every
 // row read is coalesced.  All arithmetic is float64, every product and sum an operation of its own.  Plain loads,
 // compares and stores: no inline assembly, no atomics, no allocation, no synchronisation.
@@ -231,6 +233,57 @@ __global__ __launch_bounds__(GDN_PREP_THREADS) void gdn_prep_ticks_kernel(
   if (i < n) out[(size_t)g * n + i] = med;
 }
 
+// The fleet's front end (include/gdn_hip.h "Raw readings of a fleet"): gdn_prep_ticks per unit, with the unit's open
+// group and its count kept ON THE DEVICE.  Workgroup (tile, u): sensors [64 tile, 64 tile + 64) of unit u, lane = sensor.
+// k = raw_counts[u] clamped to 0 .. rows, p = this tile's own count word; the raw ticks of the unit are
+// [pend_ticks[u, :p] | raw[u, :k]].  Wave v takes groups v, v + waves, .. < groups = (p + k) / down and writes
+// out[u, g, i] (coalesced).  After ONE barrier (every read of the pending rows lies before it) the workgroup writes
+// the new tail into ITS OWN 64 columns of pend_ticks[u], then its own count word; tile 0 also writes counts[u].  A
+// workgroup reads nothing that another workgroup of the launch writes (a dead lane reads column n - 1: its own tile's),
+// so the state is updated in place with no second plane, no host parity and no atomic.  k == 0: counts[u] = 0 and
+// nothing else.  A count word outside 0 .. down - 1 (never written by this kernel) is clamped: no index leaves a buffer.
+template <typename RAW>
+__global__ __launch_bounds__(GDN_PREP_THREADS) void gdn_fleet_prep_ticks_kernel(
+    const RAW* __restrict__ raw, int rows, const int* __restrict__ raw_counts, double* __restrict__ pend_ticks,
+    int* __restrict__ pend_counts, int c, int n, int down, const double* __restrict__ table, float* __restrict__ out,
+    int* __restrict__ counts) {
+  __shared__ double cols[GDN_PREP_COL_DOUBLES];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const int tile = blockIdx.x, u = blockIdx.y;
+  const int k = min(max(raw_counts[u], 0), rows);
+  if (k == 0) {                                                      // (workgroup uniform, ahead of the barrier)
+    if (tile == 0 && threadIdx.x == 0) counts[u] = 0;
+    return;
+  }
+  int* __restrict__ word = pend_counts + (size_t)u * gridDim.x + tile;
+  const int p = min(max(*word, 0), down - 1);
+  const int groups = (p + k) / down;                                 // <= c: p < down, k <= rows <= c down
+  const int i = tile * 64 + lane;
+  const int ic = i < n ? i : n - 1;
+  const RAW* __restrict__ ru = raw + (size_t)u * rows * n;
+  double* __restrict__ pu = pend_ticks + (size_t)u * down * n;
+  auto tick = [&](int q) -> double { return q < p ? pu[(size_t)q * n + ic] : (double)ru[(size_t)(q - p) * n + ic]; };
+  const double scale = table[2 * ic], offset = table[2 * ic + 1];
+  double* __restrict__ col = cols + (size_t)wv * down * 64;
+  float* __restrict__ ou = out + (size_t)u * c * n;
+  for (int g = wv; g < groups; g += waves) {
+    const float med = prep_group_median([&](int j) { return tick(g * down + j); }, down, scale, offset, false, 0.0,
+                                        col, lane);
+    if (i < n) ou[(size_t)g * n + i] = med;
+  }
+  __syncthreads();
+  // groups >= 1: the tail lies in raw alone (groups * down >= down > p); else the k new rows go behind the p that stay
+  const int first = groups ? groups * down - p : 0, at = groups ? 0 : p, tail = groups ? p + k - groups * down : k;
+  for (int j = wv; j < tail; j += waves) {
+    const double v = (double)ru[(size_t)(first + j) * n + ic];
+    if (i < n) pu[(size_t)(at + j) * n + i] = v;
+  }
+  if (threadIdx.x == 0) {
+    *word = at + tail;
+    if (tile == 0) counts[u] = groups;
+  }
+}
+
 template <typename RAW>
 int prep_stats(const void* raw, long long t_raw, int n, double* workspace, double* stats, hipStream_t stream) {
   const int segments = prep_segments(t_raw, n);
@@ -258,6 +311,18 @@ int prep_ticks(const void* raw, int r, const double* pend_in, int pending, doubl
   hipLaunchKernelGGL(gdn_prep_ticks_kernel<RAW>, dim3(((unsigned)n + 63) / 64, (unsigned)gy + 1), dim3(64 * waves), 0,
                      stream, static_cast<const RAW*>(raw), r, pend_in, pending, pend_out, n, down, table, out, groups,
                      gy);
+  return gdn_launch_status();
+}
+
+template <typename RAW>
+int fleet_prep_ticks(const void* raw, int rows, const int32_t* raw_counts, void* pend, int units, int c, int n, int down,
+                     const double* table, float* out, int32_t* counts, hipStream_t stream) {
+  const unsigned tiles = ((unsigned)n + 63) / 64;
+  double* ticks = static_cast<double*>(pend);
+  int* words = reinterpret_cast<int*>(ticks + (size_t)units * down * n);
+  hipLaunchKernelGGL(gdn_fleet_prep_ticks_kernel<RAW>, dim3(tiles, (unsigned)units), dim3(64 * prep_waves(down)), 0,
+                     stream, static_cast<const RAW*>(raw), rows, raw_counts, ticks, words, c, n, down, table, out,
+                     counts);
   return gdn_launch_status();
 }
 
@@ -299,4 +364,23 @@ extern "C" int gdn_prep_ticks(const void* raw, int r, int raw_f64, const double*
                                       (hipStream_t)stream)
                  : prep_ticks<float>(raw, r, pend_in, pending, pend_out, n, down, table, out, (int)groups,
                                      (hipStream_t)stream);
+}
+
+// pend: the pending ticks of all units first ([U, down, n] float64), then one int32 count per (unit, tile of 64 sensors)
+// ([U, tiles]), rounded up to 8 bytes.
+extern "C" long long gdn_fleet_prep_bytes(int units, int n, int down) {
+  if (units < 1 || units > GDN_FLEET_MAX_ROWS || !prep_shape_ok(n, down)) return 0;
+  return 8ll * units * down * n + ((4ll * units * ((n + 63) / 64) + 7) & ~7ll);
+}
+
+extern "C" int gdn_fleet_prep_ticks(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend,
+                                    int units, int c, int n, int down, const double* table, float* out,
+                                    int32_t* counts, void* stream) {
+  if (!raw || !raw_counts || !pend || !table || !out || !counts) return GDN_ERR_ARG;
+  if (!gdn_fleet_rows_ok(units, c) || !prep_shape_ok(n, down)) return GDN_ERR_UNSUPPORTED;
+  if (rows < 1 || rows > c * down) return GDN_ERR_ARG;
+  return raw_f64 ? fleet_prep_ticks<double>(raw, rows, raw_counts, pend, units, c, n, down, table, out, counts,
+                                            (hipStream_t)stream)
+                 : fleet_prep_ticks<float>(raw, rows, raw_counts, pend, units, c, n, down, table, out, counts,
+                                           (hipStream_t)stream);
 }

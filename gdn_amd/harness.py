@@ -1986,21 +1986,21 @@ def model_fingerprint(model) -> str:
     return _fingerprint(names, host)
 
 
-def _ckpt_int(sd, key: str) -> int:
+def _ckpt_int(sd, key: str, who: str = "stream checkpoint") -> int:
     if key not in sd:
-        raise ValueError(f"stream checkpoint: key {key!r} is missing (a truncated or foreign file)")
+        raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
     a = np.asarray(sd[key])
     if a.dtype != np.int64 or a.shape != ():
-        raise ValueError(f"stream checkpoint: {key!r} must be one int64, got {a.dtype} {a.shape}")
+        raise ValueError(f"{who}: {key!r} must be one int64, got {a.dtype} {a.shape}")
     return int(a)
 
 
-def _ckpt_str(sd, key: str) -> str:
+def _ckpt_str(sd, key: str, who: str = "stream checkpoint") -> str:
     if key not in sd:
-        raise ValueError(f"stream checkpoint: key {key!r} is missing (a truncated or foreign file)")
+        raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
     a = np.asarray(sd[key])
     if a.dtype.kind != "U" or a.shape != ():
-        raise ValueError(f"stream checkpoint: {key!r} must be one string, got {a.dtype} {a.shape}")
+        raise ValueError(f"{who}: {key!r} must be one string, got {a.dtype} {a.shape}")
     return str(a)
 
 
@@ -2833,13 +2833,15 @@ def fleet_check_shape(units: int, chunk: int, n: int, w: int) -> None:
                          f"{_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
 
 
-def fleet_check_push(ticks, counts, units: int, n: int):
-    """The host checks of StreamFleet.push, before any device work: `ticks` [units, r >= 1, n] fp32; `counts` None, a
-    host sequence / tensor of `units` integers in 0 .. r (returned as a host int64 tensor), or a device int32 tensor
-    [units] (returned as it is: the kernels clamp it)."""
+def fleet_check_push(ticks, counts, units: int, n: int, raw: bool = False):
+    """The host checks of StreamFleet.push, before any device work: `ticks` [units, r >= 1, n] fp32 (`raw`: the raw
+    ticks of a prep= fleet, fp32 or float64); `counts` None, a host sequence / tensor of `units` integers in 0 .. r
+    (returned as a host int64 tensor), or a device int32 tensor [units] (returned as it is: the kernels clamp it)."""
     if ticks.dim() != 3 or ticks.shape[0] != units or ticks.shape[2] != n:
         raise ValueError(f"expected ticks of shape [{units}, r, {n}], got {tuple(ticks.shape)}")
-    if ticks.dtype != torch.float32:
+    if raw and ticks.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"ticks: expected raw {torch.float32} or {torch.float64}, got {ticks.dtype}")
+    if not raw and ticks.dtype != torch.float32:
         raise TypeError(f"ticks: expected {torch.float32}, got {ticks.dtype}")
     r = ticks.shape[1]
     if r < 1:
@@ -2879,6 +2881,191 @@ def fleet_clear_levels(lo, threshold, units: int) -> torch.Tensor:
         raise ValueError(f"events: lo[{u}] = {float(lo[u])} lies above the raise level of unit {u} (threshold[{u}] = "
                          f"{float(hi[u])})")
     return lo
+
+
+def fleet_check_prep(prep, units: int, chunk: int, n: int, itemsize: int = 4) -> None:
+    """The host facts of a fleet's prep=, refused by name before any device work: a Prep fitted on another sensor count,
+    and a staging buffer [units, chunk * down, n] of `itemsize` bytes per reading beyond the evaluators' cap."""
+    if prep.n != n:
+        raise ValueError(f"prep: fitted on {prep.n} sensors, the model has {n}")
+    if int(units) * int(chunk) * prep.down * n * int(itemsize) > _VALIDATE_CHUNK_BYTES:
+        raise ValueError(f"prep: the raw staging buffer [{units}, {chunk} * {prep.down}, {n}] of {itemsize}-byte readings "
+                         f"exceeds {_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
+
+
+def fleet_raw_cuts(r: int, down: int, chunk: int) -> list:
+    """The sub-pushes of `r` raw ticks of the time axis handed to a prep= fleet: a list of (first raw row, raw rows,
+    rows of the returned views).  A sub-push carries at most chunk * down raw rows, whatever any unit holds: with
+    p < down pending raw ticks it completes (p + rows) // down <= chunk model ticks, so no plan depends on the pending
+    state (unlike raw_push_plan).  The views cover min(chunk, (down - 1 + rows) // down) rows: the most model ticks a
+    unit can have completed.  Pure host arithmetic."""
+    if down < 1 or chunk < 1 or r < 0:
+        raise ValueError(f"fleet_raw_cuts: r = {r}, down = {down}, chunk = {chunk}")
+    span = chunk * down
+    return [(s, min(span, r - s), min(chunk, (down - 1 + min(span, r - s)) // down)) for s in range(0, r, span)]
+
+
+def fleet_raw_hand(raw_handed: int, rows: int, down: int) -> int:
+    """recal_every's clock of a prep= fleet: the model ticks that `rows` more raw rows of the time axis hand over when
+    `raw_handed` were handed before — model ticks handed = raw rows handed // down.  Pure host arithmetic."""
+    return (raw_handed + rows) // down - raw_handed // down
+
+
+# the checkpoint of a running fleet (DESIGN §3.8k): the detector's rules (§3.8e) with a leading unit axis and a format
+# number of its own; a detector's file has no "units", a fleet's file holds keys a detector's checker calls foreign
+FLEET_CHECKPOINT_FORMAT = 1
+_FLEET_CKPT = "fleet checkpoint"
+_FLEET_CKPT_INTS = ("format", "units", "abi", "state_bytes", "calib_bytes", "n", "w", "chunk", "top_m", "log",
+                    "with_gaps", "recal", "exclude_alarms", "recal_every", "recal_min", "wide", "prep", "prep_down",
+                    "handed", "raw_handed", "recals")
+_FLEET_CKPT_STRS = ("calib", "model_sha256")
+_FLEET_CKPT_CONFIG = ("units", "n", "w", "chunk", "top_m", "log", "with_gaps", "recal", "exclude_alarms", "recal_every",
+                      "recal_min", "calib", "wide", "prep", "prep_down")
+
+
+def _fleet_ckpt_format(sd) -> None:
+    fmt = _ckpt_int(sd, "format", _FLEET_CKPT)
+    if fmt != FLEET_CHECKPOINT_FORMAT:
+        raise ValueError(f"{_FLEET_CKPT}: format = {fmt} is not known to this version (it reads format "
+                         f"{FLEET_CHECKPOINT_FORMAT})")
+    if "units" not in sd:
+        raise ValueError(f"{_FLEET_CKPT}: key 'units' is missing: this is a single detector's checkpoint "
+                         "(StreamDetector.load reads it)")
+
+
+def fleet_checkpoint_config(sd) -> dict:
+    """The configuration a fleet checkpoint was saved under (`_FLEET_CKPT_CONFIG`) as Python values; a missing or
+    mistyped field is refused by name.  Host data only."""
+    cfg = {k: _ckpt_str(sd, k, _FLEET_CKPT) if k in _FLEET_CKPT_STRS else _ckpt_int(sd, k, _FLEET_CKPT)
+           for k in _FLEET_CKPT_CONFIG}
+    if cfg["calib"] not in ("tick", "sensor"):
+        raise ValueError(f"{_FLEET_CKPT}: calib = {cfg['calib']!r}: 'tick' or 'sensor'")
+    return cfg
+
+
+def fleet_checkpoint_events(sd):
+    """The events configuration of a fleet checkpoint ({"on", "off", "cap", "m"}), None for a file saved without episode
+    tables; `events`, `events_cfg` and `clear` come together or not at all.  Host data only."""
+    keys = [k for k in ("events", "events_cfg", "clear") if k in sd]
+    if not keys:
+        return None
+    if len(keys) != 3:
+        raise ValueError(f"{_FLEET_CKPT}: key {keys[0]!r} without the rest of events, events_cfg, clear (a truncated or "
+                         "foreign file)")
+    cfg = np.asarray(sd["events_cfg"])
+    if cfg.dtype != np.int64 or cfg.shape != (len(_EVENTS_FIELDS),):
+        raise ValueError(f"{_FLEET_CKPT}: 'events_cfg' must be int64 ({len(_EVENTS_FIELDS)},), got {cfg.dtype} {cfg.shape}")
+    out = {k: int(v) for k, v in zip(_EVENTS_FIELDS, cfg)}
+    if not (1 <= out["on"] <= 4096 and 1 <= out["off"] <= 4096 and 0 <= out["cap"] <= 1 << 20 and 1 <= out["m"] <= 8):
+        raise ValueError(f"{_FLEET_CKPT}: events_cfg = {out} outside 1 <= on, off <= 4096, 0 <= cap <= 2^20, 1 <= m <= 8")
+    return out
+
+
+def fleet_checkpoint_check(sd, expect) -> None:
+    """Refuse a fleet checkpoint dict `sd` (StreamFleet.state_dict() or a loaded file) that the loader cannot continue,
+    with a ValueError that names the field.  `expect` holds the loader's own facts: "n", "w" (the model's), "abi",
+    "state_bytes" = gdn_stream_state_bytes(n, w) PER UNIT and "calib_bytes" = gdn_fleet_calib_bytes(units, n, R) for the
+    file's units and R (0 without rings) as the loaded library reports them, "model" (its model_fingerprint, or None: do
+    not compare), "prep_down" (the caller's Prep.down, or None: no prep), "prep_n", and — a fleet that exists already —
+    "units" and "events" (its events configuration or None).  Host data only: no device work, no library call."""
+    who = _FLEET_CKPT
+    _fleet_ckpt_format(sd)
+    ints = {k: _ckpt_int(sd, k, who) for k in _FLEET_CKPT_INTS}
+    strs = {k: _ckpt_str(sd, k, who) for k in _FLEET_CKPT_STRS}
+    cfg = fleet_checkpoint_config(sd)
+    U = ints["units"]
+    if U < 1:
+        raise ValueError(f"{who}: units = {U}: a fleet has at least one unit")
+    if expect.get("units") is not None and U != int(expect["units"]):
+        raise ValueError(f"{who}: units = {U}, this fleet has units = {int(expect['units'])}")
+    for k in ("n", "w"):
+        if ints[k] != int(expect[k]):
+            raise ValueError(f"{who}: {k} = {ints[k]}, the model has {k} = {int(expect[k])}")
+    for k in ("abi", "state_bytes", "calib_bytes"):
+        if ints[k] != int(expect[k]):
+            raise ValueError(f"{who}: {k} = {ints[k]} was saved by another build of the library (this one has {k} = "
+                             f"{int(expect[k])}); the state's layout is not known to agree")
+    down = expect.get("prep_down")
+    if bool(ints["prep"]) != (down is not None):
+        raise ValueError(f"{who}: prep: the fleet was saved " + ("with" if ints["prep"] else "without")
+                         + " a raw-readings front end and is resumed " + ("without one (pass prep=)" if ints["prep"]
+                                                                          else "with one (pass prep=None)"))
+    if down is not None:
+        if ints["prep_down"] != int(down):
+            raise ValueError(f"{who}: prep_down = {ints['prep_down']}, the prep given has down = {int(down)}")
+        if int(expect.get("prep_n", ints["n"])) != ints["n"]:
+            raise ValueError(f"{who}: prep: fitted on {int(expect['prep_n'])} sensors, n = {ints['n']}")
+    elif ints["prep_down"] != 0:
+        raise ValueError(f"{who}: prep_down = {ints['prep_down']} without a prep")
+    if expect.get("model") is not None and strs["model_sha256"] != expect["model"]:
+        raise ValueError(f"{who}: model_sha256 differs from the model given: the scores are the model's, so resuming "
+                         "under other weights changes the alarm rate (check_model=False resumes all the same)")
+    for k in ("handed", "raw_handed", "recals", "log", "recal", "recal_every", "recal_min", "chunk", "top_m"):
+        if ints[k] < 0:
+            raise ValueError(f"{who}: {k} = {ints[k]} is negative")
+    n, R, m, log = ints["n"], ints["recal"], ints["top_m"], ints["log"]
+    want = {"state": (np.uint8, (U, ints["state_bytes"])), "med_iqr": (np.float64, (U, n, 2)),
+            "threshold": (np.float64, (U,)), "log_ticks": (np.int64, (U, log)), "log_sensors": (np.int32, (U, log, m))}
+    optional = {"calib_kept": (np.int64, (U,)), "calib_counts": (np.int32, (U, n))}
+    if cfg["with_gaps"]:
+        want["gaps"] = (np.int64, (U, 2, n))
+    if R:
+        want["ring_keys"], want["ring_keep"] = (np.float64, (U, n, R)), (np.uint8, (U, R))
+        want["recal_counts"] = (np.int32, (U, n))
+        if cfg["calib"] == "tick":
+            want["recal_kept"] = (np.int32, (U,))
+    if cfg["prep"]:
+        want["pending_ticks"] = (np.float64, (U, ints["prep_down"], n))
+        want["pending"] = (np.int32, (U,))
+    elif ints["raw_handed"] != 0:
+        raise ValueError(f"{who}: raw_handed = {ints['raw_handed']} without a prep")
+    events = fleet_checkpoint_events(sd)
+    if "events" in expect:                                  # (load() builds the fleet from the file: nothing to compare)
+        mine = expect["events"]
+        if (events is None) != (mine is None):
+            raise ValueError(f"{who}: events: the fleet was saved " + ("without" if events is None else "with")
+                             + " episode tables and is resumed " + ("with them (pass events=None)" if events is None
+                                                                    else "without them (pass events=)"))
+        for k in _EVENTS_FIELDS if events is not None else ():
+            if events[k] != int(mine[k]):
+                raise ValueError(f"{who}: events.{k} = {events[k]}, this fleet was built with events.{k} = {int(mine[k])}")
+    if events is not None:
+        if events["m"] != m:
+            raise ValueError(f"{who}: events.m = {events['m']}, top_m = {m}")
+        want["events"] = (np.int64, (U, events_bytes(m, events["cap"]) // 8))
+        want["clear"], want["events_cfg"] = (np.float64, (U,)), (np.int64, (len(_EVENTS_FIELDS),))
+    for k in sd:
+        if k not in want and k not in optional and k not in _FLEET_CKPT_INTS and k not in _FLEET_CKPT_STRS:
+            raise ValueError(f"{who}: key {k!r} does not belong to this configuration (a foreign file)")
+    for k, (dtype, shape) in list(want.items()) + [(k, v) for k, v in optional.items() if k in sd]:
+        if k not in sd:
+            raise ValueError(f"{who}: key {k!r} is missing (a truncated or foreign file)")
+        a = np.asarray(sd[k])
+        if a.dtype != dtype or a.shape != shape:
+            raise ValueError(f"{who}: {k!r} must be {np.dtype(dtype)} {shape} under this configuration, got {a.dtype} "
+                             f"{a.shape}")
+    if cfg["prep"]:
+        pending = np.asarray(sd["pending"])
+        if ((pending < 0) | (pending >= ints["prep_down"])).any():
+            raise ValueError(f"{who}: pending = {pending.tolist()} outside an open group of prep_down = "
+                             f"{ints['prep_down']} raw ticks (0 .. {ints['prep_down'] - 1})")
+    for k in ("recal_kept", "recal_counts", "calib_counts"):
+        if k in sd and (np.asarray(sd[k]) < 0).any():
+            raise ValueError(f"{who}: {k} holds a negative count")
+    if "calib_kept" in sd and (np.asarray(sd["calib_kept"]) < 0).any():
+        raise ValueError(f"{who}: calib_kept holds a negative count")
+
+
+def _fleet_checkpoint_expect(model, prep, units: int, recal: int, check_model: bool = True) -> dict:
+    """The loader's own facts for fleet_checkpoint_check: host arithmetic and host library calls, plus ONE batch read of
+    the model's tensors for its fingerprint when `check_model`."""
+    lib = _lib.load()
+    w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+    n = model.embedding.weight.shape[0]
+    return {"n": n, "w": w, "abi": lib.gdn_abi_version(), "state_bytes": lib.gdn_stream_state_bytes(n, w),
+            "calib_bytes": lib.gdn_fleet_calib_bytes(units, n, recal) if recal else 0,
+            "model": model_fingerprint(model) if check_model else None,
+            "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n}
 
 
 class StreamFleet(_StreamCore):
@@ -2937,31 +3124,64 @@ class StreamFleet(_StreamCore):
     fleet's clock, each from whatever its own ring holds.  The contract above then reads StreamDetector(recal=R, ...)
     for every unit: ring, keep flags and the table after recalibrate().  recal=0 issues exactly the launches it did.
 
-    Out of scope here (the per-unit state layout is a single stream's precisely so that they can follow without a format
-    change): prep=, save / load, a command-line flag, more than one process."""
+    `prep=Prep` is StreamDetector's prep= per unit with ONE table for all units: `push()` then takes RAW
+    ticks [U, r, n], fp32 or float64, and `counts` are RAW counts.  gdn_fleet_prep_ticks leads the captured launches (in
+    front of fleet_fill under gaps=True): per unit it completes the groups of `prep.down` raw ticks its open group and
+    its real raw rows make up, writes their medians as model ticks into `raw_buf` (gaps=True) or `chunk_buf`, writes
+    `counts` [U] — on the device, the model ticks each unit completed in the last sub-push — and keeps the open group in
+    `pend` (ops.fleet_prep_views), in place.  Pending counts are data on the device like everything else: one graph per
+    raw dtype serves every mix of open groups, counts and silent units.  A sub-push carries up to chunk * down raw rows
+    of the time axis: ONE copy into the static staging buffer of that dtype, one write of `raw_counts`, ONE replay.
+    `chunk`, `recal`, `log` and `history` stay in model ticks; recal_every's clock counts raw rows of the time axis
+    handed // down.  A prep= fleet pushed raw ticks writes, for every unit, the bits of this fleet without prep pushed
+    that unit's completed medians with counts = groups, hence those of StreamDetector(prep=prep, ...) pushed that unit's
+    real raw rows; a silent unit keeps its open group byte for byte.  prep=None issues exactly the launches it did.
+
+    `save(path)` / `StreamFleet.load(path, model, prep=)` (`state_dict()` / `load_state_dict(sd)`) carry a
+    running fleet across a process boundary under StreamDetector's rules (§3.8e): states, tables in force, thresholds,
+    logs, gap counters, rings, episode tables and clear levels, open groups, the counters and the configuration go into
+    one .npz with a format number of its own; the static buffers of a push, the workspaces and the graphs do not.  A
+    fleet stream cut by a save and a load writes the bits of the uninterrupted one.
+
+    Out of scope: a command-line flag, per-unit prep tables, more than one process, moving a unit between a fleet file
+    and a detector file."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
-                 calib: str = "tick"):
+                 calib: str = "tick", prep=None):
+        self._build(model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, events, recal,
+                    exclude_alarms, recal_every, recal_min, calib, prep)
+
+    def _build(self, model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, events, recal,
+               exclude_alarms, recal_every, recal_min, calib, prep, units=None, device=None):
+        """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — `units` states of
+        zeros, the tables zeros, the thresholds inf and the clear levels 0, all on `device`, `wide` the caller's word —
+        and load_state_dict fills the allocations."""
         self._set_calib(calib, gaps, recal)
         self.model = model.eval()
         w = model.gnn_layers[0].gnn.lin.weight.shape[1]
         n = model.embedding.weight.shape[0]
-        if not isinstance(history, torch.Tensor) or history.dim() != 3 or history.shape[1] != n:
-            raise ValueError(f"expected a history of shape [U, {n}, h], got "
-                             f"{tuple(history.shape) if isinstance(history, torch.Tensor) else type(history)}")
-        units = history.shape[0]
+        seeded = history is not None
+        if seeded:
+            if not isinstance(history, torch.Tensor) or history.dim() != 3 or history.shape[1] != n:
+                raise ValueError(f"expected a history of shape [U, {n}, h], got "
+                                 f"{tuple(history.shape) if isinstance(history, torch.Tensor) else type(history)}")
+            units = history.shape[0]
+        units = int(units)
         fleet_check_shape(units, chunk, n, w)
         self.units, self.n, self.w, self.chunk, self.top_m = units, n, w, int(chunk), int(top_m)
         self.use_graph = bool(use_graph)
         self._check_lists(top_m, log, "entries per unit")
-        if not isinstance(med_iqr, torch.Tensor) or med_iqr.shape != (units, n, 2):
-            raise ValueError(f"expected med_iqr of shape [{units}, {n}, 2], got "
-                             f"{tuple(med_iqr.shape) if isinstance(med_iqr, torch.Tensor) else type(med_iqr)}")
-        threshold = torch.as_tensor(threshold, dtype=torch.float64)
-        if threshold.numel() not in (1, units) or threshold.dim() > 1:
-            raise ValueError(f"threshold: one number or [{units}] of them, got {tuple(threshold.shape)}")
+        if prep is not None:
+            fleet_check_prep(prep, units, self.chunk, n)
+        if seeded:
+            if not isinstance(med_iqr, torch.Tensor) or med_iqr.shape != (units, n, 2):
+                raise ValueError(f"expected med_iqr of shape [{units}, {n}, 2], got "
+                                 f"{tuple(med_iqr.shape) if isinstance(med_iqr, torch.Tensor) else type(med_iqr)}")
+            threshold = torch.as_tensor(threshold, dtype=torch.float64)
+            if threshold.numel() not in (1, units) or threshold.dim() > 1:
+                raise ValueError(f"threshold: one number or [{units}] of them, got {tuple(threshold.shape)}")
         # the options: host facts only, before any device work
         self._set_recal(recal, exclude_alarms, recal_every, recal_min,
                         lambda: _lib.load().gdn_fleet_calib_bytes(units, n, self.recal),
@@ -2969,18 +3189,27 @@ class StreamFleet(_StreamCore):
                         "1 <= n <= 4096, 64 <= R <= 2^20, 8 units n R <= 2 GiB)")
         self.with_gaps = bool(gaps)
         self.events_cfg = None if events is None else events_config({**events, "lo": None}, self.top_m)
-        clear = None if events is None else fleet_clear_levels(events.get("lo"), threshold, units)
-        if self.with_gaps and history.shape[2] >= w and not bool(torch.isfinite(history[:, :, -w:]).all()):
-            raise ValueError(f"history: the last {w} ticks of a unit hold a value that is not finite; with gaps=True "
-                             "every missing reading is held at an earlier real one, so every unit's stream must begin "
-                             "on real readings")
+        if seeded:
+            clear = None if events is None else fleet_clear_levels(events.get("lo"), threshold, units)
+            if self.with_gaps and history.shape[2] >= w and not bool(torch.isfinite(history[:, :, -w:]).all()):
+                raise ValueError(f"history: the last {w} ticks of a unit hold a value that is not finite; with "
+                                 "gaps=True every missing reading is held at an earlier real one, so every unit's "
+                                 "stream must begin on real readings")
         _check_stream_head(model)
-        history = ops._chk(history, name="history")
-        dev = history.device
-        self.med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr").clone()
-        self.threshold = threshold.reshape(-1).expand(units).to(dev).clone()
-        self.state = ops.fleet_state(history, w)
-        self.wide = model.wide_for(history[:, :, -w:]) if wide is None else bool(wide)
+        if seeded:
+            history = ops._chk(history, name="history")
+            dev = history.device
+            self.med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr").clone()
+            self.threshold = threshold.reshape(-1).expand(units).to(dev).clone()
+            self.state = ops.fleet_state(history, w)
+            self.wide = model.wide_for(history[:, :, -w:]) if wide is None else bool(wide)
+        else:
+            dev = torch.empty((0,), device=device).device           # ("cuda" -> the current device, with its index)
+            clear = torch.zeros((units,), dtype=torch.float64)
+            self.med_iqr = torch.zeros((units, n, 2), dtype=torch.float64, device=dev)
+            self.threshold = torch.full((units,), float("inf"), dtype=torch.float64, device=dev)
+            self.state = ops.fleet_state_empty(units, n, w, dev)
+            self.wide = bool(wide)
         m = self.top_m
         self.counts = torch.zeros((units,), dtype=torch.int32, device=dev)
         self._alloc_push((units,), log, dev)
@@ -3004,6 +3233,15 @@ class StreamFleet(_StreamCore):
         self._full = _Replay(lambda *a: self._launch(*a), use_graph, lambda: model._constants().key,
                              args=lambda: (self._guarded(),))
         self._last = 0                      # ticks per unit of the last (sub-)push: what the static buffers hold
+        self.prep = prep
+        self._raw_handed = 0                # prep=: raw rows of the time axis handed to push()
+        self._prep_full = {}                # prep=: raw dtype -> the push with the front end reading `_raw_stage`'s
+        if prep is not None:
+            if prep.table.device != dev:
+                raise ValueError(f"prep: its table is on {prep.table.device}, the fleet on {dev}")
+            self.pend = ops.fleet_prep_state(units, n, prep.down, dev)       # open groups and their lengths, per unit
+            self.raw_counts = torch.zeros((units,), dtype=torch.int32, device=dev)
+            self._raw_stage = {}            # raw dtype -> the static staging buffer [U, chunk * down, n] of its pushes
 
     @classmethod
     def from_calibration(cls, model, series, chunk: int, batch: int = 8192, calib_gaps: bool = False,
@@ -3077,6 +3315,46 @@ class StreamFleet(_StreamCore):
                           gap_chunk=self.gap_chunk, gaps=self.gaps)
 
     graph = property(lambda self: self._full.graph, doc="the captured push, None before the first one")
+    _prep_graphs = property(lambda self: {dt: full.graph for dt, full in self._prep_full.items() if full.graph is not None},
+                            doc="raw dtype -> the graph captured with the front end reading that dtype's staging buffer")
+
+    def _launch_prep(self, stage, guard: bool):
+        """gdn_fleet_prep_ticks over the staging buffer and the pending state (it writes `counts`), then the push."""
+        ops.fleet_prep_ticks(stage, self.raw_counts, self.pend, self.prep.down, self.prep.table,
+                             self.raw_buf if self.with_gaps else self.chunk_buf, self.counts)
+        self._launch(guard)
+
+    def _prep_stage(self, dtype):
+        stage = self._raw_stage.get(dtype)
+        if stage is None:
+            fleet_check_prep(self.prep, self.units, self.chunk, self.n, torch.empty((), dtype=dtype).element_size())
+            stage = self._raw_stage[dtype] = torch.zeros((self.units, self.chunk * self.prep.down, self.n), dtype=dtype,
+                                                         device=self.state.device)
+            self._prep_full[dtype] = _Replay(self._launch_prep, self.use_graph, self._full.key,
+                                             args=lambda: (stage, self._guarded()))
+        return stage, self._prep_full[dtype]
+
+    def _write_counts(self, into, counts, s: int, r: int):
+        """Sub-push from row `s` of the time axis, `r` rows long: every unit's clamp(counts[u] - s, 0, r) into `into`."""
+        if counts is None:
+            into.fill_(r)
+        elif counts.is_cuda:
+            torch.clamp(counts - s if s else counts, 0, r, out=into)
+        else:
+            into.copy_((counts - s).clamp_(0, r).to(torch.int32))
+
+    def _push_prep(self, ticks, counts):
+        down = self.prep.down
+        stage, full = self._prep_stage(ticks.dtype)
+        for s, rows, views in fleet_raw_cuts(ticks.shape[1], down, self.chunk):
+            stage[:, :rows].copy_(ticks[:, s:s + rows])
+            self._write_counts(self.raw_counts, counts, s, rows)
+            self._last = views
+            full()
+            self._hand(fleet_raw_hand(self._raw_handed, rows, down))
+            self._raw_handed += rows
+        r = self._last
+        return self.top_scores[:, :r], self.top_sensors[:, :r], self.alarm[:, :r]
 
     def push(self, ticks, counts=None):
         """Score `ticks` [U, r, n] fp32 (device or host), oldest first, r ticks per unit.  `counts`: None — every unit
@@ -3085,18 +3363,19 @@ class StreamFleet(_StreamCore):
         FIRST counts[u] rows of `ticks`.  Returns views (top_scores [U, r', m] float64, top_sensors [U, r', m] int32,
         alarm [U, r'] int32) of the static buffers, valid until the next push; r' = r when r <= chunk, else the ticks of
         the last of the pushes it was split into.  Rows of the views at or beyond counts[u] are UNSPECIFIED (whatever an
-        earlier push left there)."""
-        counts = fleet_check_push(ticks, counts, self.units, self.n)
+        earlier push left there).
+        prep=: `ticks` are RAW ticks, fp32 or float64, and `counts` RAW counts under the same three forms; a sub-push
+        carries up to chunk * down raw rows and gives unit u clamp(counts[u] - its first row, 0, its rows).  `counts`
+        (the fleet's buffer, on the device) then holds the model ticks each unit completed in the last sub-push, and the
+        views cover min(chunk, (down - 1 + rows) // down) rows of it; rows at or beyond counts[u] are UNSPECIFIED."""
+        counts = fleet_check_push(ticks, counts, self.units, self.n, raw=self.prep is not None)
+        if self.prep is not None:
+            return self._push_prep(ticks, counts)
         for s in range(0, ticks.shape[1], self.chunk):
             part = ticks[:, s:s + self.chunk]
             r = part.shape[1]
             (self.raw_buf if self.with_gaps else self.chunk_buf)[:, :r].copy_(part)
-            if counts is None:
-                self.counts.fill_(r)
-            elif counts.is_cuda:
-                torch.clamp(counts - s if s else counts, 0, r, out=self.counts)
-            else:
-                self.counts.copy_((counts - s).clamp_(0, r).to(torch.int32))
+            self._write_counts(self.counts, counts, s, r)
             self._last = r
             self._full()
             self._hand(r)
@@ -3172,3 +3451,142 @@ class StreamFleet(_StreamCore):
         if not 0 <= int(u) < self.units:
             raise ValueError(f"episodes({u}): the fleet has units 0 .. {self.units - 1}")
         return _episodes(self.events[int(u)], self.top_m, self.events_cfg["cap"])
+
+    # save and resume: a fleet stream cut by a save and a load writes the bits of the uninterrupted one
+    def _config(self) -> dict:
+        return {"units": self.units, "n": self.n, "w": self.w, "chunk": self.chunk, "top_m": self.top_m,
+                "log": 0 if self.log_ticks is None else self.log_ticks.shape[1], "with_gaps": int(self.with_gaps),
+                "recal": self.recal, "exclude_alarms": int(self.exclude_alarms), "recal_every": self.recal_every,
+                "recal_min": self.recal_min, "calib": self.calib, "wide": int(self.wide),
+                "prep": int(self.prep is not None), "prep_down": 0 if self.prep is None else self.prep.down}
+
+    def _expect(self, check_model: bool = True) -> dict:
+        """fleet_checkpoint_check's `expect` for this fleet: its model's shape and fingerprint, its units, prep and
+        events, and the loaded library's ABI version and byte sizes."""
+        expect = _fleet_checkpoint_expect(self.model, self.prep, self.units, self.recal, check_model)
+        expect["units"], expect["events"] = self.units, self.events_cfg
+        return expect
+
+    def state_dict(self) -> dict:
+        """Everything a continuation of this fleet depends on, as a flat dict of numpy arrays (numpy.savez writes it,
+        numpy.load(allow_pickle=False) reads it), StreamDetector.state_dict's keys with a leading unit axis: `state`
+        uint8 [U, state_bytes], `med_iqr`, `threshold`, the logs, `gaps`, the rings with `recal_kept` / `recal_counts`,
+        `events` / `clear` / `events_cfg`, `calib_kept` / `calib_counts` where present, with prep= the open groups
+        (`pending_ticks` [U, down, n] float64, `pending` [U] int32: tile 0's count, all tiles of a unit agree) and the
+        raw rows handed; the host counters, the configuration, and the identity of what wrote it.  The staging, chunk,
+        window, prediction and output buffers, gap_chunk, counts, the workspaces and the graphs stay behind.
+        Read-only: ONE batch of device-to-host copies on the current stream and ONE synchronisation."""
+        lib = _lib.load()
+        U, n, m = self.units, self.n, self.top_m
+        cfg = self._config()
+        dev = {"state": self.state.view(torch.uint8).view(U, -1), "med_iqr": self.med_iqr, "threshold": self.threshold}
+        if self.log_ticks is not None:
+            dev["log_ticks"], dev["log_sensors"] = self.log_ticks, self.log_sensors
+        if self.with_gaps:
+            dev["gaps"] = self.gaps
+        if self.recal:
+            dev["ring_keys"], dev["ring_keep"], dev["recal_counts"] = self.ring_keys, self.ring_keep, self.recal_counts
+            if self.recal_kept is not None:
+                dev["recal_kept"] = self.recal_kept
+        if self.events is not None:
+            dev["events"], dev["clear"] = self.events, self.clear
+        if self.calib_counts is not None:
+            dev["calib_counts"] = self.calib_counts
+        if self.prep is not None:
+            dev["pending_ticks"], dev["pending"] = ops.fleet_prep_views(self.pend, U, n, self.prep.down)
+        weights = self.model.state_dict()
+        names = sorted(weights)
+        host = _host_copies(list(dev.values()) + [weights[k] for k in names])
+        torch.cuda.current_stream().synchronize()
+        sd = {k: t.numpy() for k, t in zip(dev, host)}
+        if self.log_ticks is None:
+            sd["log_ticks"], sd["log_sensors"] = np.zeros((U, 0), np.int64), np.zeros((U, 0, m), np.int32)
+        if self.events is not None:
+            sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
+        if self.calib_kept is not None:
+            sd["calib_kept"] = torch.as_tensor(self.calib_kept, dtype=torch.int64).reshape(U).numpy().copy()
+        if self.prep is not None:
+            tiles = sd["pending"]
+            assert (tiles == tiles[:, :1]).all(), "the pending counts of a unit's sensor tiles disagree"
+            sd["pending"] = np.ascontiguousarray(tiles[:, 0])
+        ints = {"format": FLEET_CHECKPOINT_FORMAT, "abi": lib.gdn_abi_version(),
+                "state_bytes": lib.gdn_stream_state_bytes(n, self.w),
+                "calib_bytes": lib.gdn_fleet_calib_bytes(U, n, self.recal) if self.recal else 0,
+                "handed": self._handed, "raw_handed": self._raw_handed, "recals": self.recals}
+        ints.update({k: v for k, v in cfg.items() if k != "calib"})
+        sd.update({k: np.array(int(ints[k]), dtype=np.int64) for k in _FLEET_CKPT_INTS})
+        sd["calib"] = np.array(self.calib)
+        sd["model_sha256"] = np.array(_fingerprint(names, host[len(dev):]))
+        return sd
+
+    def load_state_dict(self, sd, check_model: bool = True) -> None:
+        """Take the fleet stream of `sd` (state_dict()'s dict, or a file's) up where it was saved.  `sd` is checked first
+        (fleet_checkpoint_check, and its configuration against this fleet's own, field by field: a ValueError that names
+        the field, before any device work); the captured graphs are dropped; then every array is copied INTO the
+        allocations this fleet already has, so the pointers a later capture records are the ones it always had.  A
+        unit's pending count goes to every sensor tile's word.  Afterwards the last push is empty."""
+        fleet_checkpoint_check(sd, self._expect(check_model))
+        cfg = fleet_checkpoint_config(sd)
+        for k, mine in self._config().items():
+            if cfg[k] != mine:
+                raise ValueError(f"{_FLEET_CKPT}: {k} = {cfg[k]!r}, this fleet was built with {k} = {mine!r}")
+        for full in (self._full, *self._prep_full.values()):
+            full.drop()
+
+        def host(key):
+            return torch.from_numpy(np.array(sd[key]))      # (a copy: numpy.load may hand out read-only arrays)
+        self.state.view(torch.uint8).view(self.units, -1).copy_(host("state"))
+        self.med_iqr.copy_(host("med_iqr"))
+        self.threshold.copy_(host("threshold"))
+        if self.log_ticks is not None:
+            self.log_ticks.copy_(host("log_ticks"))
+            self.log_sensors.copy_(host("log_sensors"))
+        if self.with_gaps:
+            self.gaps.copy_(host("gaps"))
+        if self.recal:
+            self.ring_keys.copy_(host("ring_keys"))
+            self.ring_keep.copy_(host("ring_keep"))
+            self.recal_counts.copy_(host("recal_counts"))
+            if self.recal_kept is not None:
+                self.recal_kept.copy_(host("recal_kept"))
+        if self.events is not None:
+            self.events.copy_(host("events"))
+            self.clear.copy_(host("clear"))
+        if self.prep is not None:
+            ticks, pending = ops.fleet_prep_views(self.pend, self.units, self.n, self.prep.down)
+            ticks.copy_(host("pending_ticks"))
+            pending.copy_(host("pending").view(-1, 1).expand(-1, pending.shape[1]))
+        self.calib_counts = host("calib_counts").to(self.state.device) if "calib_counts" in sd else None
+        self.calib_kept = host("calib_kept") if "calib_kept" in sd else None
+        self._handed, self.recals = _ckpt_int(sd, "handed", _FLEET_CKPT), _ckpt_int(sd, "recals", _FLEET_CKPT)
+        self._raw_handed = _ckpt_int(sd, "raw_handed", _FLEET_CKPT)
+        self._last = 0
+
+    def save(self, path: str) -> None:
+        """state_dict() as one .npz at exactly `path` (write_stream_checkpoint: a temporary file beside it, then
+        os.replace — a save that dies half-way leaves the previous checkpoint loadable)."""
+        write_stream_checkpoint(path, self.state_dict())
+
+    @classmethod
+    def load(cls, path: str, model, prep=None, device="cuda", check_model: bool = True, use_graph: bool = True):
+        """A fleet that continues the streams saved at `path`: built from the file's configuration, the caller's `model`
+        and — when the file says one was used — `prep` (on `device`), with no history (nothing is seeded), then
+        load_state_dict.  Refused with a ValueError that names the field, before any device work: an unknown format, a
+        single detector's file, another ABI version or byte size, another n or w, a prep against the file's word or with
+        another down, other weights (unless check_model=False), a missing key or an array of the wrong shape or dtype."""
+        sd = read_stream_checkpoint(path)
+        _fleet_ckpt_format(sd)                              # (an unknown format first: its other fields may differ)
+        units, R = _ckpt_int(sd, "units", _FLEET_CKPT), _ckpt_int(sd, "recal", _FLEET_CKPT)
+        if units < 1 or R < 0:
+            raise ValueError(f"{_FLEET_CKPT}: units = {units}, recal = {R}: at least one unit, no negative ring")
+        fleet_checkpoint_check(sd, _fleet_checkpoint_expect(model, prep, units, R, check_model))
+        cfg = fleet_checkpoint_config(sd)
+        events = fleet_checkpoint_events(sd)                # (None: the file has no episode tables, nor has the fleet)
+        if events is not None:
+            events = {k: events[k] for k in ("on", "off", "cap")}
+        fleet = cls.__new__(cls)
+        fleet._build(model, None, None, None, cfg["chunk"], cfg["top_m"], cfg["log"], use_graph, bool(cfg["wide"]),
+                     bool(cfg["with_gaps"]), events, cfg["recal"], bool(cfg["exclude_alarms"]), cfg["recal_every"],
+                     cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, units=units, device=device)
+        fleet.load_state_dict(sd, check_model=False)        # (the weights were compared above, once)
+        return fleet

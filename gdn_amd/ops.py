@@ -1221,6 +1221,13 @@ def fleet_state(history, w: int) -> torch.Tensor:
     return state
 
 
+def fleet_state_empty(units: int, n: int, w: int, device) -> torch.Tensor:
+    """Fleet states [U, gdn_stream_state_bytes(n, w) / 8] of zero words that no history has seeded: the allocation saved
+    states are copied into (harness.StreamFleet.load).  No launch."""
+    words = _fleet_state_words(units, n, w)
+    return torch.zeros((units, words // units), dtype=torch.int64, device=device)
+
+
 def fleet_state_views(state, units: int, n: int, w: int):
     """(counters int64 [U, 3] = ticks, alarms, logged; carry float64 [U, 3, n]; hist fp32 [U, n, w]): views of the
     states of a fleet.  Row u of each is what stream_state_views gives for unit u's slice."""
@@ -1558,6 +1565,63 @@ def prep_ticks(raw, pend_in, pending: int, pend_out, down: int, table, out, rows
     _lib.call("gdn_prep_ticks", _ptr(raw), rows, f64, _ptr(pend_in), int(pending), _ptr(pend_out), n, down, _ptr(table),
               _ptr(out), out.shape[0], _stream())
     return groups
+
+
+_FLEET_PREP_LIMITS = "1 <= units <= 4096, 1 <= n <= 4096, 1 <= down <= 64"
+
+
+def _fleet_prep_bytes(units: int, n: int, down: int) -> int:
+    nbytes = _lib.load().gdn_fleet_prep_bytes(int(units), int(n), int(down))
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"fleet prep state: no kernel for units = {units}, n = {n}, down = {down} "
+                               f"({_FLEET_PREP_LIMITS})")
+    return nbytes
+
+
+def fleet_prep_state(units: int, n: int, down: int, device) -> torch.Tensor:
+    """The pending state of a fleet's raw-readings front end (include/gdn_hip.h "Raw readings of a fleet"): ONE zeroed
+    allocation of gdn_fleet_prep_bytes(units, n, down) as int64 words — no unit holds a raw tick.  No launch."""
+    return torch.zeros((_fleet_prep_bytes(units, n, down) // 8,), dtype=torch.int64, device=device)
+
+
+def fleet_prep_views(pend, units: int, n: int, down: int):
+    """(ticks [U, down, n] float64, pending [U, tiles] int32, tiles = ceil(n / 64)): views of a fleet's pending state.
+    Unit u's open group is ticks[u, :pending[u, 0]]; all tiles of a unit hold the same count."""
+    tiles = (n + 63) // 64
+    words = units * down * n
+    ticks = pend[:words].view(torch.float64).view(units, down, n)
+    pending = pend[words:].view(torch.int32)[: units * tiles].view(units, tiles)
+    return ticks, pending
+
+
+def fleet_prep_ticks(raw, raw_counts, pend, down: int, table, out, counts):
+    """gdn_prep_ticks per unit in ONE launch (gdn_fleet_prep_ticks): unit u's raw ticks [its open group | raw[u,
+    :raw_counts[u]]] (`raw` [U, rows, n] fp32 or float64; raw_counts [U] int32 on the device, clamped to 0 .. rows by
+    the kernel) -> out[u, g, :] for g < groups = (pending_u + raw_counts[u]) // down (`out` [U, c, n] fp32, rows
+    <= c * down), counts[u] = groups, and the rest becomes the unit's open group in `pend` (fleet_prep_state), in
+    place.  Rows of out at or beyond groups are not written; a unit with raw_counts[u] == 0 keeps its pending state."""
+    if not raw.is_cuda:
+        raise _lib.GdnHipError(f"raw is on {raw.device}: gdn_amd ops need a HIP device (no CPU fallback)")
+    if raw.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"raw: expected {torch.float32} or {torch.float64}, got {raw.dtype}")
+    if raw.dim() != 3 or not raw.is_contiguous():
+        raise ValueError(f"expected a contiguous raw [U, rows, n] (one row per unit and raw tick), got "
+                         f"{tuple(raw.shape)}")
+    units, rows, n = raw.shape
+    down = _prep_down(down)
+    table = _prep_table(table, n)
+    _stream_buf(out, torch.float32, 1, "out")
+    if out.dim() != 3 or out.shape[0] != units or out.shape[2] != n:
+        raise ValueError(f"expected out [{units}, c, {n}] (one row per unit and prepared tick), got {tuple(out.shape)}")
+    c = out.shape[1]
+    if not 1 <= rows <= c * down:
+        raise ValueError(f"rows = {rows}: a launch carries 1 to c * down = {c * down} raw ticks per unit")
+    _stream_buf(raw_counts, torch.int32, units, "raw_counts")
+    _stream_buf(counts, torch.int32, units, "counts")
+    _stream_buf(pend, torch.int64, _fleet_prep_bytes(units, n, down) // 8, "pend")
+    _lib.call("gdn_fleet_prep_ticks", _ptr(raw), rows, int(raw.dtype == torch.float64), _ptr(raw_counts), _ptr(pend),
+              units, c, n, down, _ptr(table), _ptr(out), _ptr(counts), _stream())
+    return out
 
 
 # --------------------------------------------------------------------------- alarm episodes

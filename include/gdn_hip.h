@@ -1188,6 +1188,31 @@ int gdn_fleet_calib_write_sensor(const void* state, const float* pred, const flo
                                  int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream);
 int gdn_fleet_ring_counts(const uint8_t* ring_keep, const uint8_t* select, int units, int n, int R, int32_t* counts,
                           int32_t* kept, void* stream);
+/* Raw readings of a fleet (opt-in; additive entry points, the ABI version does not move): gdn_prep_ticks
+ * ("Raw readings" above) per unit in ONE launch, with every unit's open downsample group and its length on the device,
+ * so that how many raw ticks a unit hands over — and how many it holds — is data, never a launch argument.
+ * Pending state: ONE allocation of gdn_fleet_prep_bytes(units, n, down) bytes (zeroed: no unit holds a raw tick):
+ *   ticks   [U, down, n] float64   at byte 0: unit u's open group, raw tick q < pending of sensor i at (u down + q) n + i
+ *                                  (the bits of a float64 reading are kept);
+ *   pending [U, tiles] int32       at byte 8 U down n, tiles = ceil(n / 64): the length of unit u's open group, one
+ *                                  word per tile of 64 sensors, all tiles of a unit equal; padded to 8 bytes.
+ *   gdn_fleet_prep_ticks  raw [U, rows, n] fp32 (raw_f64 = 0) or float64, rows <= c down; raw_counts [U] int32 on the
+ *                         device, clamped to 0 .. rows: unit u's real raw rows are its first k = raw_counts[u].  With p
+ *                         the unit's pending count, groups = (p + k) / down <= c.  out[u, g, :] (out [U, c, n] fp32) =
+ *                         the median of raw ticks g down .. g down + down - 1 of [ticks[u, :p] | raw[u, :k]] for g <
+ *                         groups, computed as gdn_prep_ticks computes it (table [n, 2] shared by all units; a group with
+ *                         no finite reading: the quiet NaN); rows of out at or beyond groups are not written.
+ *                         counts[u] = groups (the buffer every later fleet launch reads).  The new open group is the
+ *                         last (p + k) mod down of those ticks.  Grid (tile, unit), 64 prep_waves(down) threads: a
+ *                         workgroup reads its own count word and its own 64 columns of ticks[u], and after one barrier
+ *                         writes them; tile 0 also writes counts[u].  No workgroup reads what another writes: in place,
+ *                         no second plane, no atomic.  raw_counts[u] == 0: counts[u] = 0, the unit's pending state
+ *                         stays byte for byte.
+ * Refusals, all before any launch: a null pointer, rows < 1, rows > c down: GDN_ERR_ARG; units * c > 4096, units, c < 1,
+ * n outside 1 .. 4096, down outside 1 .. 64: GDN_ERR_UNSUPPORTED (gdn_fleet_prep_bytes: 0; units <= 4096).             */
+long long gdn_fleet_prep_bytes(int units, int n, int down);
+int gdn_fleet_prep_ticks(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend, int units,
+                         int c, int n, int down, const double* table, float* out, int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }
