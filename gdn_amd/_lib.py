@@ -155,6 +155,8 @@ SIGNATURES = {
     "gdn_fleet_calib_write_gaps": [_p] * 6 + [_c_int] * 6 + [_p] * 3,
     "gdn_fleet_calib_write_sensor": [_p] * 6 + [_c_int] * 6 + [_p] * 3,
     "gdn_fleet_ring_counts": [_p, _p, _c_int, _c_int, _c_int, _p, _p, _p],
+    "gdn_fleet_ring_threshold_bytes": [_c_int, _c_int],
+    "gdn_fleet_ring_threshold": [_p] * 5 + [_c_int] * 5 + [ctypes.c_double, _c_int] + [_p] * 8,
     "gdn_fleet_prep_bytes": [_c_int] * 3,
     "gdn_fleet_prep_ticks": [_p, _c_int, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4,
 }

@@ -11,7 +11,9 @@
 // episodes launch of a fleet, gdn_fleet_events, lives with the tile code in gdn_events.hip.)
 // Rolling calibration (opt-in): gdn_fleet_calib_write* sits between the score and the advance launch and
 // writes a single stream's calibration ring per unit; gdn_fleet_ring_counts turns the keep flags into the per-row
-// counts of gdn_score_select_counts, so a fleet recalibrates with no host read.
+// counts of gdn_score_select_counts, so a fleet recalibrates with no host read.  gdn_fleet_ring_threshold (opt-in,
+// DESIGN §3.8l) re-derives every unit's threshold from its ring under the table just written; a single stream calls it
+// with units = 1.
 // Plain copy, sweep and scan kernels: no inline assembly, no floating-point atomics, no workgroup waits on another.
 #include "gdn_stream_steps.hpp"
 
@@ -212,6 +214,69 @@ __global__ __launch_bounds__(256) void gdn_fleet_counts_mask_kernel(const unsign
   if (i < rows && select[i / n] == 0) counts[i] = 0;
 }
 
+// The threshold from the rings (include/gdn_hip.h "Threshold from the ring").  Two launches, no atomics,
+// no workgroup waits on another: the tile kernel leaves one RingPeak per (unit, tile of 61 slots) in the workspace
+// [U, ring_tiles(R)], the finisher folds a unit's row and applies the rule.  A single stream is the fleet of one unit.
+// Wave (unit u, tile t): ring_peak_tile, the step of gdn_stream_steps.hpp, on unit u's ring, table and base.
+template <int MODE>
+__global__ __launch_bounds__(256) void gdn_fleet_ring_peak_kernel(
+    const void* __restrict__ state, const double* __restrict__ ring_keys, const unsigned char* __restrict__ ring_keep,
+    const double* __restrict__ med_iqr, int n, int w, int R, RingPeak* __restrict__ partials) {
+  const int lane = threadIdx.x & 63, u = blockIdx.y, tiles = ring_tiles(R);
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);         // (wave uniform)
+  if (t >= tiles) return;
+  const RingPeak p = ring_peak_tile<MODE>(ring_keys + (size_t)u * n * R, ring_keep + (size_t)u * R,
+                                          med_iqr + (size_t)u * n * 2, ring_base(fleet_state(state, u, n, w), R), n, R,
+                                          t, lane);
+  if (lane == 0) partials[(size_t)u * tiles + t] = p;
+}
+
+// Workgroup u: the maximum (ties by slot) and the eligible sum of the unit's partials, then the rule: the threshold is
+// rewritten as peak * margin (ONE multiply) iff the unit is selected, eligible >= min_eligible and peak is finite and
+// > 0; with episodes, clear = the new threshold * clear_frac in the same step.  peak, eligible and peak_slot (-1: no
+// eligible slot) are written either way.
+__global__ __launch_bounds__(256) void gdn_fleet_ring_threshold_kernel(
+    const RingPeak* __restrict__ partials, const unsigned char* __restrict__ select, int tiles, double margin,
+    int min_eligible, double* __restrict__ threshold, const double* __restrict__ clear_frac,
+    double* __restrict__ clear, double* __restrict__ peak, int* __restrict__ eligible, int* __restrict__ peak_slot) {
+  __shared__ RingPeak wave_part[4];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const RingPeak* __restrict__ row = partials + (size_t)u * tiles;
+  RingPeak acc{-INFINITY, NONE, 0};
+  for (int t = tid; t < tiles; t += 256) {
+    const RingPeak p = row[t];
+    ring_peak_merge(acc.peak, acc.slot, p.peak, p.slot);
+    acc.eligible += p.eligible;
+  }
+  ring_peak_wave(acc.peak, acc.slot);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc.eligible += __shfl_xor(acc.eligible, d);
+  if ((tid & 63) == 0) wave_part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int v = 1; v < 4; ++v) {
+    ring_peak_merge(acc.peak, acc.slot, wave_part[v].peak, wave_part[v].slot);
+    acc.eligible += wave_part[v].eligible;
+  }
+  peak[u] = acc.peak;
+  eligible[u] = acc.eligible;
+  peak_slot[u] = acc.slot == NONE ? -1 : acc.slot;
+  const bool selected = !select || select[u] != 0;
+  if (selected && acc.eligible >= min_eligible && acc.peak > 0.0 && acc.peak < INFINITY) {
+    const double thr = acc.peak * margin;
+    threshold[u] = thr;
+    if (clear) clear[u] = thr * clear_frac[u];
+  }
+}
+
+template <int MODE>
+void fleet_ring_peak_launch(const void* state, const double* ring_keys, const uint8_t* ring_keep,
+                            const double* med_iqr, int units, int n, int w, int R, RingPeak* partials, hipStream_t s) {
+  const unsigned tiles = (unsigned)ring_tiles(R);            // <= 17190
+  hipLaunchKernelGGL(gdn_fleet_ring_peak_kernel<MODE>, dim3((tiles + 3) / 4, (unsigned)units), dim3(256), 0, s, state,
+                     ring_keys, ring_keep, med_iqr, n, w, R, partials);
+}
+
 // diagnostic knob: GDN_FLEET_CALIB_TILE=1 keeps the ring write on the tile form at every c (comparisons)
 bool force_calib_tile() {
   static int v = -1;
@@ -409,5 +474,34 @@ extern "C" int gdn_fleet_ring_counts(const uint8_t* ring_keep, const uint8_t* se
   } else {
     return GDN_OK;
   }
+  return gdn_launch_status();
+}
+
+// One RingPeak (16 bytes) per unit and tile of 61 slots.
+extern "C" long long gdn_fleet_ring_threshold_bytes(int units, int R) {
+  if (gdn_fleet_calib_bytes(units, 1, R) <= 0) return 0;
+  return (long long)sizeof(RingPeak) * units * ring_tiles(R);
+}
+
+// mode: the CALIB_* of the ring's writer (PLAIN and GAPS are tick calibration: no filler test; SENSOR has it).
+extern "C" int gdn_fleet_ring_threshold(const void* state, const double* ring_keys, const uint8_t* ring_keep,
+                                        const double* med_iqr, const uint8_t* select, int units, int n, int w, int R,
+                                        int mode, double margin, int min_eligible, void* workspace, double* threshold,
+                                        const double* clear_frac, double* clear, double* peak, int32_t* eligible,
+                                        int32_t* peak_slot, void* stream) {
+  if (!state || !ring_keys || !ring_keep || !med_iqr || !workspace || !threshold || !peak || !eligible || !peak_slot ||
+      (clear_frac == nullptr) != (clear == nullptr))
+    return GDN_ERR_ARG;
+  if (!(margin > 0.0 && margin < INFINITY) || min_eligible < 1) return GDN_ERR_ARG;       // (a NaN margin compares false)
+  if (mode != CALIB_PLAIN && mode != CALIB_GAPS && mode != CALIB_SENSOR) return GDN_ERR_ARG;
+  if (!stream_shape_ok(n, w) || gdn_fleet_calib_bytes(units, n, R) <= 0) return GDN_ERR_UNSUPPORTED;
+  const hipStream_t s = (hipStream_t)stream;
+  RingPeak* partials = reinterpret_cast<RingPeak*>(workspace);
+  if (mode == CALIB_SENSOR)
+    fleet_ring_peak_launch<CALIB_SENSOR>(state, ring_keys, ring_keep, med_iqr, units, n, w, R, partials, s);
+  else
+    fleet_ring_peak_launch<CALIB_PLAIN>(state, ring_keys, ring_keep, med_iqr, units, n, w, R, partials, s);
+  hipLaunchKernelGGL(gdn_fleet_ring_threshold_kernel, dim3((unsigned)units), dim3(256), 0, s, partials, select,
+                     ring_tiles(R), margin, min_eligible, threshold, clear_frac, clear, peak, eligible, peak_slot);
   return gdn_launch_status();
 }

@@ -3,7 +3,8 @@
 // run of ticks with the carried smoothing state, the hist roll, and the carry / ordered log compaction / counters.
 // A kernel decides which state, which rows and which count a workgroup works on and calls the step; a fleet is a
 // stream per unit, so a unit's state block is written bit for bit as the single stream writes it.  The hold of
-// missing readings (stream_fill_group) and the write of the calibration ring (ring_write_tile) are steps like the others.
+// missing readings (stream_fill_group), the write of the calibration ring (ring_write_tile) and the threshold a ring
+// supports (ring_peak_tile) are steps like the others.
 // The float64 scoring arithmetic is gdn_score_sweep.hpp's (no FMA contraction in a unit that includes this header).
 #pragma once
 #include "gdn_score_sweep.hpp"
@@ -178,6 +179,92 @@ __device__ __forceinline__ void ring_write_tile(const RingSource& rs, int b0, in
     }
     __syncthreads();                                         // the tile is rewritten by the next sensor tile
   }
+}
+
+// The threshold a ring supports (include/gdn_hip.h "Threshold from the ring"), ONE source for a stream
+// and for a unit of a fleet: the largest smoothed score, under the table in force, among the slots whose four-tick
+// window the ring holds whole.  The rule per slot stands here once:
+//   ring_norm      the normalised error of one key: norm's expression on a key that is already |pred - gt|; SENSOR:
+//                  the filler is a missing reading, error exactly 0.0 (tick modes never read a filler in an eligible
+//                  window: a tick not kept holds the filler in every key and makes its window ineligible);
+//   ring_smooth    the scorer's left-to-right 4-term mean;
+//   ring_eligible  keep at q, q - 1, q - 2, q - 3 (mod R) and (q - base) mod R >= 3: the window neither holds a tick
+//                  that was left out nor straddles the seam between the newest tick (base - 1) and the oldest (base).
+template <int MODE>
+__device__ __forceinline__ double ring_norm(double key, double med, double inv_den) {
+  const double a = (key - med) * inv_den;
+  if constexpr (MODE == CALIB_SENSOR) return (unsigned long long)__double_as_longlong(key) == FILLER ? 0.0 : a;
+  return a;
+}
+__device__ __forceinline__ double ring_smooth(double e3, double e2, double e1, double e0) {
+  return (((e3 + e2) + e1) + e0) / 4.0;
+}
+__device__ __forceinline__ bool ring_eligible(bool k3, bool k2, bool k1, bool k0, unsigned q, unsigned base, int R) {
+  const unsigned age = q >= base ? q - base : q + (unsigned)R - base;        // 0: the oldest tick of a full ring
+  return k3 && k2 && k1 && k0 && age >= 3u;
+}
+
+// What a run of slots, a unit's ring or a fleet's workspace row reduces to.  slot == NONE: no eligible slot (peak is
+// then -inf).  Larger peak first, equal peaks by the lower slot: exact in any order, so no tiling changes a bit.
+struct RingPeak {
+  double peak;
+  int slot, eligible;
+};
+__device__ __forceinline__ void ring_peak_merge(double& peak, int& slot, double op, int os) {
+  if (op > peak || (op == peak && os < slot)) { peak = op; slot = os; }
+}
+__device__ __forceinline__ void ring_peak_wave(double& peak, int& slot) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const double op = __shfl_xor(peak, d);
+    const int os = __shfl_xor(slot, d);
+    ring_peak_merge(peak, slot, op, os);
+  }
+}
+
+#define GDN_RING_TILE 61             // slots a wave owns: its 64 lanes hold them and the 3 slots before (mod R)
+__host__ __device__ inline int ring_tiles(int R) { return (R + GDN_RING_TILE - 1) / GDN_RING_TILE; }
+
+// One wave, tile t < ring_tiles(R) of one ring (keys [n, R], keep [R], the table med_iqr [n, 2] in force): lane l holds
+// slot (61 t - 3 + l) mod R — lanes 0, 1, 2 the halo, taken mod R and never clamped, lanes 3 .. 63 the slots the wave
+// owns (those below R).  The lanes run along the slots (R is contiguous: one coalesced 8-byte load per lane and
+// sensor); the three predecessors of a slot come from the lanes below (__shfl_up), never from memory again.  The wave
+// walks the sensors, four loads in flight, and keeps the running maximum per slot in a register (fmax: a NaN error
+// never wins, as in the scorer).  sensor_scale runs once per sensor and wave — 64 sensors at a time, a lane each, then
+// broadcast — so the float64 division is off the per-slot path.  Returns, in every lane, the wave's masked maximum
+// with its slot and its eligible count.  All 64 lanes call it; no LDS, no barrier.
+template <int MODE>
+__device__ __forceinline__ RingPeak ring_peak_tile(const double* __restrict__ keys,
+                                                   const unsigned char* __restrict__ keep,
+                                                   const double* __restrict__ med_iqr, unsigned base, int n, int R,
+                                                   int t, int lane) {
+  const int at = t * GDN_RING_TILE - 3 + lane;               // < R + 64 <= 2 R
+  const unsigned q = (unsigned)(at < 0 ? at + R : (at >= R ? at - R : at));
+  const bool owned = lane >= 3 && at < R;
+  const int k0 = keep[q] != 0 ? 1 : 0;
+  const int k1 = __shfl_up(k0, 1), k2 = __shfl_up(k0, 2), k3 = __shfl_up(k0, 3);
+  const bool ok = owned && ring_eligible(k3 != 0, k2 != 0, k1 != 0, k0 != 0, q, base, R);
+  double best = -INFINITY;
+  for (int s0 = 0; s0 < n; s0 += 64) {
+    const Scale mine = sensor_scale(med_iqr, min(s0 + lane, n - 1));
+    const int cnt = min(64, n - s0);                         // (wave uniform)
+    for (int j0 = 0; j0 < cnt; j0 += 4) {
+      double key[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)                            // past the last sensor: the last one again (max is idempotent)
+        key[i] = keys[(size_t)(s0 + min(j0 + i, cnt - 1)) * R + q];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = min(j0 + i, cnt - 1);
+        const double e0 = ring_norm<MODE>(key[i], __shfl(mine.med, j), __shfl(mine.inv_den, j));
+        const double e1 = __shfl_up(e0, 1), e2 = __shfl_up(e0, 2), e3 = __shfl_up(e0, 3);
+        best = fmax(best, ring_smooth(e3, e2, e1, e0));
+      }
+    }
+  }
+  RingPeak out{ok ? best : -INFINITY, ok ? (int)q : NONE, (int)__popcll(__ballot(ok))};
+  ring_peak_wave(out.peak, out.slot);
+  return out;
 }
 
 // Hold missing readings.  "Missing" is decided on the bit pattern (exponent field all ones: NaN, +inf, -inf), so it

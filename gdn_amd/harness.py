@@ -2004,6 +2004,33 @@ def _ckpt_str(sd, key: str, who: str = "stream checkpoint") -> str:
     return str(a)
 
 
+def checkpoint_recal_threshold(sd, who: str = "stream checkpoint"):
+    """The margin a checkpoint (a detector's or a fleet's) was saved with under recal_threshold=, None
+    for a file saved without it — every file written before the option existed.  Host data only."""
+    if "recal_threshold" not in sd:
+        return None
+    a = np.asarray(sd["recal_threshold"])
+    if a.dtype != np.float64 or a.shape != () or not (np.isfinite(a) and a > 0):
+        raise ValueError(f"{who}: 'recal_threshold' must be one finite float64 > 0, got {a.dtype} {a.shape} {a!r}")
+    return float(a)
+
+
+def _check_recal_threshold(sd, expect, recal: int, events, who: str):
+    """What the two checkpoint checkers refuse about the optional keys of recal_threshold=: `recal_threshold` without a
+    ring, `clear_frac` without it or without episode tables, and — against a detector or fleet that exists already — a
+    margin on one side only, or another one.  The shapes are checked with the other optional keys."""
+    margin = checkpoint_recal_threshold(sd, who)
+    if margin is not None and not recal:
+        raise ValueError(f"{who}: recal_threshold = {margin} without a calibration ring (recal = 0)")
+    if "clear_frac" in sd and (margin is None or events is None):
+        raise ValueError(f"{who}: key 'clear_frac' without recal_threshold and events (a truncated or foreign file)")
+    if "recal_threshold" in expect:                         # (load() builds from the file: nothing to compare)
+        mine = expect["recal_threshold"]
+        if margin != mine:
+            raise ValueError(f"{who}: recal_threshold = {margin}, this one was built with recal_threshold = {mine} "
+                             "(the threshold in the file was, or was not, re-derived from the ring)")
+
+
 def _ckpt_format(sd) -> None:
     fmt = _ckpt_int(sd, "format")
     if fmt != STREAM_CHECKPOINT_FORMAT:
@@ -2087,7 +2114,9 @@ def stream_checkpoint_check(sd, expect) -> None:
             raise ValueError(f"stream checkpoint: events.m = {events['m']}, top_m = {m}")
         want["events"] = (np.uint8, (events_bytes(m, events["cap"]),))
         want["events_lo"], want["events_cfg"] = (np.float64, (1,)), (np.int64, (len(_EVENTS_FIELDS),))
-    optional = {"calib_counts": (np.int32, (n,)), "recal_counts": (np.int64, (n,))}
+    _check_recal_threshold(sd, expect, R, events, "stream checkpoint")
+    optional = {"calib_counts": (np.int32, (n,)), "recal_counts": (np.int64, (n,)),
+                "recal_threshold": (np.float64, ()), "clear_frac": (np.float64, (1,))}
     for k in sd:
         if k not in want and k not in optional and k not in _CKPT_INTS and k not in _CKPT_STRS:
             raise ValueError(f"stream checkpoint: key {k!r} does not belong to this configuration (a foreign file)")
@@ -2265,6 +2294,55 @@ class _StreamCore:
         elif recal_min is not None:
             raise ValueError(f"recal_min = {recal_min}: there is no calibration ring (recal = 0)")
 
+    def _set_recal_threshold(self, recal_threshold):
+        """recal_threshold (None: off, else the margin on the ring's largest score): host facts only."""
+        self.recal_threshold = None
+        self.ring_peak = self.ring_eligible = self.ring_peak_slot = self.clear_frac = self._thr_ws = None
+        if recal_threshold is not None:
+            if not self.recal:
+                raise ValueError(f"recal_threshold = {recal_threshold!r}: re-deriving the threshold needs a calibration "
+                                 "ring (recal=R)")
+            self.recal_threshold = ops.check_ring_margin(recal_threshold, "recal_threshold")
+
+    def _margin(self, threshold):
+        """recalibrate()'s `threshold` as a margin or None (the table only): None is the constructor's setting, False
+        the table only, a number a one-off margin (refused by name when it is not finite or <= 0)."""
+        if threshold is None:
+            return getattr(self, "recal_threshold", None)   # (an object put together without the constructor: off)
+        if threshold is False:
+            return None
+        return ops.check_ring_margin(threshold, "threshold")
+
+    def _ring_buffers(self):
+        """The outputs and the workspace of the threshold step, allocated at its first use (a detector that never asks
+        for it allocates and launches nothing): `ring_peak`, `ring_eligible`, `ring_peak_slot` per unit, and with
+        episodes `clear_frac` = lo / threshold as they stand (1 where that is not a number or exceeds 1, so that the
+        clear level never rises above the threshold)."""
+        units, dev = getattr(self, "units", 1), self.state.device
+        if self.ring_peak is None:
+            self.ring_peak = torch.full((units,), float("-inf"), dtype=torch.float64, device=dev)
+            self.ring_eligible = torch.zeros((units,), dtype=torch.int32, device=dev)
+            self.ring_peak_slot = torch.full((units,), -1, dtype=torch.int32, device=dev)
+            self._thr_ws = ops.fleet_ring_threshold_workspace(units, self.recal, dev)
+        if self.clear_frac is None and self.events is not None:
+            frac = self.clear.view(-1) / self.threshold.view(-1)
+            self.clear_frac = torch.where(torch.isfinite(frac) & (frac <= 1.0), frac, torch.ones_like(frac))
+
+    def _ring_threshold(self, margin: float, select=None):
+        """The threshold step after a table rewrite: two launches, no host read (ops.fleet_ring_threshold); a single
+        stream is the fleet of one unit.  min_eligible is recal_min."""
+        if not isinstance(self.threshold, torch.Tensor):
+            raise ValueError("threshold: the device scalar the captured graph reads was replaced by a plain number; "
+                             "write into it (det.threshold[0] = value) and it can be re-derived in place")
+        self._ring_buffers()
+        n, R = self.n, self.recal
+        ops.fleet_ring_threshold(self.state, self.ring_keys.view(-1, n, R), self.ring_keep.view(-1, R),
+                                 self.med_iqr.view(-1, n, 2), self.w, margin, self.recal_min, self._thr_ws,
+                                 self.threshold.view(-1), self.ring_peak, self.ring_eligible, self.ring_peak_slot,
+                                 select=select, clear_frac=self.clear_frac,
+                                 clear=None if self.clear_frac is None else self.clear.view(-1),
+                                 by_sensor=self.calib == "sensor")
+
     def _alloc_push(self, lead: tuple, log, dev):
         """The static buffers of a push, zeros: per stream under `lead` = (), per unit under (units,)."""
         c, n, w, m = self.chunk, self.n, self.w, self.top_m
@@ -2346,6 +2424,14 @@ class StreamDetector(_StreamCore):
     at least `recal_min` of them; a dead sensor keeps its row and no longer stops the others.  The default "tick" is
     the rule above, launch for launch.
 
+    `recal_threshold=margin` (needs recal=R; None: off) makes a recalibration whole: whenever
+    `recalibrate()` has rewritten the table it also rewrites `threshold` IN PLACE — a number in units of that table —
+    as margin times the largest smoothed score the ring supports under the new table (the rule of `from_calibration`,
+    over the ticks whose four-tick window the ring holds whole, if at least `recal_min` are), and with events= the
+    clear level as the new threshold times `clear_frac` (lo / threshold at construction).  Two more launches, no
+    host read, no recapture.  `recalibrate(threshold=...)` overrides it once.  With exclude_alarms=True the ring holds
+    no tick that alarmed, so only a change of table or a margin above 1 raises the threshold.
+
     `prep=Prep` puts the raw-readings front end on the device: `push()` then takes RAW ticks [r, n], fp32
     or float64, in engineering units at the raw rate, and gdn_prep_ticks leads the launches: it normalises every
     reading with the Prep's min-max table and writes the median of each completed group of `prep.down` raw ticks as
@@ -2376,12 +2462,12 @@ class StreamDetector(_StreamCore):
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
-                 calib: str = "tick", prep=None, events=None):
+                 calib: str = "tick", prep=None, events=None, recal_threshold=None):
         self._build(model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, recal,
-                    exclude_alarms, recal_every, recal_min, calib, prep, events=events)
+                    exclude_alarms, recal_every, recal_min, calib, prep, events=events, recal_threshold=recal_threshold)
 
     def _build(self, model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, recal,
-               exclude_alarms, recal_every, recal_min, calib, prep, device=None, events=None):
+               exclude_alarms, recal_every, recal_min, calib, prep, device=None, events=None, recal_threshold=None):
         """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — the state is
         gdn_stream_state_bytes(n, w) of zeros, the table zeros, the threshold inf, all on `device`, `wide` the
         caller's word — and load_state_dict fills the allocations."""
@@ -2401,6 +2487,7 @@ class StreamDetector(_StreamCore):
                         lambda: _lib.load().gdn_stream_calib_bytes(n, self.recal),
                         f"no calibration ring for n = {n}, R = {recal} (1 <= n <= 4096, 64 <= R <= 2^20, "
                         "8 n R <= 2 GiB)")
+        self._set_recal_threshold(recal_threshold)
         _check_stream_head(model)
         self.with_gaps = bool(gaps)
         if history is None:
@@ -2442,6 +2529,8 @@ class StreamDetector(_StreamCore):
         if self.recal:
             self.ring_keys, self.ring_keep = ops.stream_calib_ring(n, self.recal, dev)
             self._recal_ws = ops.score_select_workspace(1, n, self.recal, dev)
+        if self.recal_threshold is not None:
+            self._ring_buffers()
         self._recal_counts = torch.zeros((n,), dtype=torch.int32, device=dev) if calib == "sensor" else None
         self.recal_counts = None            # calib="sensor": every sensor's real keys at the last recalibrate() (host)
         self.recals = 0                     # tables written by recalibrate()
@@ -2595,8 +2684,13 @@ class StreamDetector(_StreamCore):
         r = self._last
         return self.top_scores[:r], self.top_sensors[:r], self.alarm[:r]
 
-    def recalibrate(self) -> int:
-        """Overwrite `med_iqr` in place with the median / IQR per sensor of the kept ticks in the calibration ring
+    def recalibrate(self, threshold=None) -> int:
+        """`threshold`: None — the constructor's `recal_threshold`; a number — a one-off margin; False —
+        the table only.  With a margin, and only when the table was rewritten, two more launches re-derive `threshold`
+        (and with events= the clear level) in place from the ring under the new table: margin times the largest
+        smoothed score among the ring's eligible ticks, if at least `recal_min` are eligible; `ring_peak`,
+        `ring_eligible` and `ring_peak_slot` (device tensors of one element) say what was found.  No further host read.
+        Overwrite `med_iqr` in place with the median / IQR per sensor of the kept ticks in the calibration ring
         (np.median and numpy's 'linear' 25th / 75th percentiles: gdn_score_quantiles' arithmetic, ONE gdn_score_select
         straight from the ring) and return how many ticks that was; with fewer than `recal_min` kept, write nothing
         and return 0.  Eager, ONE host read (a synchronisation).  `threshold`, the carry and the captured graph stay:
@@ -2607,6 +2701,7 @@ class StreamDetector(_StreamCore):
         the rewritten sensors (0 if none); returns the NUMBER OF SENSORS whose row was rewritten."""
         if not self.recal:
             raise ValueError("recalibrate(): the detector was built with recal=0 and keeps no calibration ring")
+        margin = self._margin(threshold)
         if self.calib == "sensor":
             ops.score_key_counts(self.ring_keys, 1, self.n, self.recal, out=self._recal_counts)
             ops.score_select_counts(self.ring_keys, 1, self.n, self.recal, self._recal_counts, self.recal_min,
@@ -2615,11 +2710,15 @@ class StreamDetector(_StreamCore):
             done = self.recal_counts[self.recal_counts >= self.recal_min]
             self.recal_kept = int(done.min()) if done.numel() else 0
             self.recals += 1 if done.numel() else 0
+            if margin is not None and done.numel():
+                self._ring_threshold(margin)
             return int(done.numel())
         total = int(self.ring_keep.sum())
         if total < self.recal_min:
             return 0
         ops.score_select(self.ring_keys, 1, self.n, self.recal, total, self._recal_ws, out=self.med_iqr)
+        if margin is not None:
+            self._ring_threshold(margin)
         self.recals += 1
         self.recal_kept = total
         return total
@@ -2681,7 +2780,7 @@ class StreamDetector(_StreamCore):
         """stream_checkpoint_check's `expect` for this detector: its model's shape and fingerprint, its prep, and the
         loaded library's ABI version and byte sizes."""
         expect = _checkpoint_expect(self.model, self.prep, self.recal, check_model)
-        expect["events"] = self.events_cfg
+        expect["events"], expect["recal_threshold"] = self.events_cfg, self.recal_threshold
         return expect
 
     def state_dict(self) -> dict:
@@ -2709,11 +2808,15 @@ class StreamDetector(_StreamCore):
             dev["calib_counts"] = self.calib_counts
         if self.events is not None:
             dev["events"], dev["events_lo"] = self.events.view(torch.uint8), self.clear
+        if self.recal_threshold is not None and self.clear_frac is not None:
+            dev["clear_frac"] = self.clear_frac
         weights = self.model.state_dict()
         names = sorted(weights)
         host = _host_copies(list(dev.values()) + [weights[k] for k in names])
         torch.cuda.current_stream().synchronize()
         sd = {k: t.numpy() for k, t in zip(dev, host)}
+        if self.recal_threshold is not None:
+            sd["recal_threshold"] = np.array(self.recal_threshold, dtype=np.float64)
         if self.log_ticks is None:
             sd["log_ticks"], sd["log_sensors"] = np.zeros((0,), np.int64), np.zeros((0, m), np.int32)
         if self.recal_counts is not None:
@@ -2764,6 +2867,8 @@ class StreamDetector(_StreamCore):
         if self.events is not None:
             self.events.view(torch.uint8).copy_(host("events"))
             self.clear.copy_(host("events_lo"))
+        # the fraction behind the clear level: the file's, else (at its next use) that of the levels just loaded
+        self.clear_frac = host("clear_frac").to(self.state.device) if "clear_frac" in sd else None
         self.raw_pending = _ckpt_int(sd, "raw_pending")
         if self.prep is not None:
             self._pend_at = 0
@@ -2802,7 +2907,7 @@ class StreamDetector(_StreamCore):
         det._build(model, None, None, None, cfg["chunk"], cfg["top_m"], cfg["log"], use_graph, bool(cfg["wide"]),
                    bool(cfg["with_gaps"]), cfg["recal"], bool(cfg["exclude_alarms"]), cfg["recal_every"],
                    cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, device=device,
-                   events=events)
+                   events=events, recal_threshold=checkpoint_recal_threshold(sd))
         det.load_state_dict(sd, check_model=False)          # (the weights were compared above, once)
         return det
 
@@ -3034,6 +3139,8 @@ def fleet_checkpoint_check(sd, expect) -> None:
             raise ValueError(f"{who}: events.m = {events['m']}, top_m = {m}")
         want["events"] = (np.int64, (U, events_bytes(m, events["cap"]) // 8))
         want["clear"], want["events_cfg"] = (np.float64, (U,)), (np.int64, (len(_EVENTS_FIELDS),))
+    _check_recal_threshold(sd, expect, R, events, who)
+    optional["recal_threshold"], optional["clear_frac"] = (np.float64, ()), (np.float64, (U,))
     for k in sd:
         if k not in want and k not in optional and k not in _FLEET_CKPT_INTS and k not in _FLEET_CKPT_STRS:
             raise ValueError(f"{who}: key {k!r} does not belong to this configuration (a foreign file)")
@@ -3123,6 +3230,9 @@ class StreamFleet(_StreamCore):
     contributes every tick that equals U detectors with recal_every=E; otherwise all units are recalibrated on the
     fleet's clock, each from whatever its own ring holds.  The contract above then reads StreamDetector(recal=R, ...)
     for every unit: ring, keep flags and the table after recalibrate().  recal=0 issues exactly the launches it did.
+    `recal_threshold=margin` is StreamDetector's per unit: `recalibrate()` then re-derives `threshold` [U]
+    (and `clear` [U] under events=) in place from the rings under the tables just written, two more launches after the
+    select and still no host read; a unit left out, silent or with fewer than `recal_min` eligible ticks keeps its own.
 
     `prep=Prep` is StreamDetector's prep= per unit with ONE table for all units: `push()` then takes RAW
     ticks [U, r, n], fp32 or float64, and `counts` are RAW counts.  gdn_fleet_prep_ticks leads the captured launches (in
@@ -3149,12 +3259,12 @@ class StreamFleet(_StreamCore):
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None, recal: int = 0,
                  exclude_alarms: bool = True, recal_every: int = 0, recal_min: int | None = None,
-                 calib: str = "tick", prep=None):
+                 calib: str = "tick", prep=None, recal_threshold=None):
         self._build(model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, events, recal,
-                    exclude_alarms, recal_every, recal_min, calib, prep)
+                    exclude_alarms, recal_every, recal_min, calib, prep, recal_threshold=recal_threshold)
 
     def _build(self, model, med_iqr, threshold, history, chunk, top_m, log, use_graph, wide, gaps, events, recal,
-               exclude_alarms, recal_every, recal_min, calib, prep, units=None, device=None):
+               exclude_alarms, recal_every, recal_min, calib, prep, units=None, device=None, recal_threshold=None):
         """The constructor's body.  `history=None` is load()'s private path: nothing is seeded — `units` states of
         zeros, the tables zeros, the thresholds inf and the clear levels 0, all on `device`, `wide` the caller's word —
         and load_state_dict fills the allocations."""
@@ -3187,6 +3297,7 @@ class StreamFleet(_StreamCore):
                         lambda: _lib.load().gdn_fleet_calib_bytes(units, n, self.recal),
                         f"no calibration rings for units = {units}, n = {n}, R = {recal} (1 <= units <= 4096, "
                         "1 <= n <= 4096, 64 <= R <= 2^20, 8 units n R <= 2 GiB)")
+        self._set_recal_threshold(recal_threshold)
         self.with_gaps = bool(gaps)
         self.events_cfg = None if events is None else events_config({**events, "lo": None}, self.top_m)
         if seeded:
@@ -3226,6 +3337,8 @@ class StreamFleet(_StreamCore):
             # count handed to the select per (unit, sensor); a unit left out through `units=` shows counts 0
             self.recal_kept = torch.zeros((units,), dtype=torch.int32, device=dev) if calib == "tick" else None
             self.recal_counts = torch.zeros((units, n), dtype=torch.int32, device=dev)
+        if self.recal_threshold is not None:
+            self._ring_buffers()
         self.recals = 0                     # calls of recalibrate()
         self._handed = 0                    # ticks per unit handed to push(): recal_every's clock
         self.calib_kept = None              # from_calibration(calib_gaps=True): per unit, the ticks behind the table
@@ -3399,8 +3512,13 @@ class StreamFleet(_StreamCore):
         mask[idx] = 1
         return mask.to(self.state.device)
 
-    def recalibrate(self, units=None) -> None:
-        """Overwrite `med_iqr` [U, n, 2] in place from the calibration rings, per unit what
+    def recalibrate(self, units=None, threshold=None) -> None:
+        """`threshold`: None — the constructor's `recal_threshold`; a number — a one-off margin; False —
+        the tables only.  With a margin, two more launches after the select and still no host read: every unit that is
+        selected and whose ring holds at least `recal_min` eligible ticks gets threshold[u] = margin times the largest
+        smoothed score among them under its table in force (and with events= clear[u] = threshold[u] * clear_frac[u]);
+        the others keep theirs.  `ring_peak`, `ring_eligible`, `ring_peak_slot` [U] on the device say what was found.
+        Overwrite `med_iqr` [U, n, 2] in place from the calibration rings, per unit what
         StreamDetector.recalibrate() writes: tick calibration rewrites the table of every unit whose ring holds at
         least `recal_min` kept ticks, calib="sensor" the row of every (unit, sensor) with that many real keys; the other
         rows stay bit for bit.  `units`: None (all), a host sequence of unit indices or a device uint8 / bool [U] mask;
@@ -3411,10 +3529,13 @@ class StreamFleet(_StreamCore):
         out); `calibration()` reads them.  Thresholds, carries, logs, episode tables and the captured graph stay."""
         if not self.recal:
             raise ValueError("recalibrate(): the fleet was built with recal=0 and keeps no calibration rings")
+        margin = self._margin(threshold)
         select = self._unit_mask(units)
         ops.fleet_ring_counts(self.ring_keys, self.ring_keep, self.recal_counts, self.recal_kept, select,
                               by_sensor=self.calib == "sensor")
         ops.fleet_select_counts(self.ring_keys, self.recal_counts, self.recal_min, self._recal_ws, self.med_iqr)
+        if margin is not None:
+            self._ring_threshold(margin, select)
         self.recals += 1
 
     def calibration(self):
@@ -3465,6 +3586,7 @@ class StreamFleet(_StreamCore):
         events, and the loaded library's ABI version and byte sizes."""
         expect = _fleet_checkpoint_expect(self.model, self.prep, self.units, self.recal, check_model)
         expect["units"], expect["events"] = self.units, self.events_cfg
+        expect["recal_threshold"] = self.recal_threshold
         return expect
 
     def state_dict(self) -> dict:
@@ -3490,6 +3612,8 @@ class StreamFleet(_StreamCore):
                 dev["recal_kept"] = self.recal_kept
         if self.events is not None:
             dev["events"], dev["clear"] = self.events, self.clear
+        if self.recal_threshold is not None and self.clear_frac is not None:
+            dev["clear_frac"] = self.clear_frac
         if self.calib_counts is not None:
             dev["calib_counts"] = self.calib_counts
         if self.prep is not None:
@@ -3499,6 +3623,8 @@ class StreamFleet(_StreamCore):
         host = _host_copies(list(dev.values()) + [weights[k] for k in names])
         torch.cuda.current_stream().synchronize()
         sd = {k: t.numpy() for k, t in zip(dev, host)}
+        if self.recal_threshold is not None:
+            sd["recal_threshold"] = np.array(self.recal_threshold, dtype=np.float64)
         if self.log_ticks is None:
             sd["log_ticks"], sd["log_sensors"] = np.zeros((U, 0), np.int64), np.zeros((U, 0, m), np.int32)
         if self.events is not None:
@@ -3552,6 +3678,8 @@ class StreamFleet(_StreamCore):
         if self.events is not None:
             self.events.copy_(host("events"))
             self.clear.copy_(host("clear"))
+        # the fractions behind the clear levels: the file's, else (at their next use) those of the levels just loaded
+        self.clear_frac = host("clear_frac").to(self.state.device) if "clear_frac" in sd else None
         if self.prep is not None:
             ticks, pending = ops.fleet_prep_views(self.pend, self.units, self.n, self.prep.down)
             ticks.copy_(host("pending_ticks"))
@@ -3587,6 +3715,7 @@ class StreamFleet(_StreamCore):
         fleet = cls.__new__(cls)
         fleet._build(model, None, None, None, cfg["chunk"], cfg["top_m"], cfg["log"], use_graph, bool(cfg["wide"]),
                      bool(cfg["with_gaps"]), events, cfg["recal"], bool(cfg["exclude_alarms"]), cfg["recal_every"],
-                     cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, units=units, device=device)
+                     cfg["recal_min"] if cfg["recal"] else None, cfg["calib"], prep, units=units, device=device,
+                     recal_threshold=checkpoint_recal_threshold(sd, _FLEET_CKPT))
         fleet.load_state_dict(sd, check_model=False)        # (the weights were compared above, once)
         return fleet

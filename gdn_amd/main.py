@@ -224,6 +224,7 @@ class Main:
                                     calib_gaps=bool(self.env_config.get("stream_calib_gaps")),
                                     recal=int(self.env_config.get("stream_recal") or 0),
                                     recal_every=int(self.env_config.get("stream_recal_every") or 0),
+                                    recal_threshold=self.env_config.get("stream_recal_threshold"),
                                     by_sensor=bool(self.env_config.get("calib_by_sensor")),
                                     raw_path=self.env_config.get("stream_raw") or "",
                                     prep_path=self.env_config.get("prep") or "",
@@ -266,7 +267,7 @@ class Main:
     def stream_test_series(self, model, val_ticks, chunk: int, show: int = 10, gaps: bool = False, recal: int = 0,
                            recal_every: int = 0, calib_gaps: bool = False, by_sensor: bool = False,
                            raw_path: str = "", prep_path: str = "", save_path: str = "", resume_path: str = "",
-                           events=None, events_path: str = ""):
+                           events=None, events_path: str = "", recal_threshold=None):
         """-stream C: the deployment form of the run.  A harness.StreamDetector is calibrated on the validation block
         of the training series (median / IQR per sensor and the largest anomaly score of that block: `-report val`'s
         threshold rule), then the test series after its first window is replayed through it in pushes of C ticks; the
@@ -276,6 +277,10 @@ class Main:
         -stream_recal R: the detector keeps a calibration ring of the last R ticks (seeded from the validation block)
         and, with -stream_recal_every E, rewrites its median / IQR table from it every E replayed ticks; the number
         of recalibrations and the ticks kept at the last one join the line and `stream_result`.
+        -stream_recal_threshold MARGIN (with -stream_recal): every recalibration also re-derives the
+        threshold from the ring under the new table, as MARGIN times the ring's largest smoothed score; the threshold
+        in force is the line's, and the eligible ticks behind the last one join it and `stream_result`
+        ("recal_threshold", "recal_eligible").
         -stream_calib_gaps (with -stream_gaps): the validation block may hold missing readings too; it is scored under
         the detector's rules (from_calibration(calib_gaps=True)) and the complete ticks the table was computed from
         join the line and `stream_result` ("calib_kept").
@@ -304,7 +309,11 @@ class Main:
         normal = self.train_series[:, lo - w:hi + 1].contiguous()
         if recal_every and not recal:
             raise ValueError("-stream_recal_every needs -stream_recal R (the calibration ring it recalibrates from)")
+        if recal_threshold is not None and not recal:
+            raise ValueError("-stream_recal_threshold needs -stream_recal R (the ring the threshold is re-derived from)")
         rolling = {"recal": recal, "recal_every": recal_every} if recal else {}
+        if recal_threshold is not None:
+            rolling["recal_threshold"] = float(recal_threshold)
         if calib_gaps:
             if not gaps:
                 raise ValueError("-stream_calib_gaps needs -stream_gaps (the detector whose rules the calibration follows)")
@@ -374,6 +383,12 @@ class Main:
                      + (f", the last from {det.recal_kept} kept ticks" if det.recals and not by_sensor else "")
                      + (f", the last from at least {det.recal_kept} real readings per sensor"
                         if det.recal_kept and by_sensor else ""))
+            if det.recal_threshold is not None:
+                eligible = int(det.ring_eligible.item()) if det.recals else 0
+                self.stream_result["recal_threshold"] = det.recal_threshold
+                self.stream_result["recal_eligible"] = eligible
+                held += (f", the threshold re-derived with margin {det.recal_threshold:g} from {eligible} eligible ticks "
+                         "at the last one")
         lines = ""
         if det.events is not None:
             table = det.episodes().numpy()
@@ -447,6 +462,7 @@ class Main:
 def build_parser():
     """main.py:199-217 (single-dash long flags and defaults as in the reference) + -data_root / -no_hip_graph /
     -train_gaps / -localise / -stream / -stream_gaps / -stream_calib_gaps / -stream_recal / -stream_recal_every /
+    -stream_recal_threshold /
     -stream_raw / -prep / -stream_save / -stream_resume / -stream_on / -stream_off / -stream_clear / -stream_events."""
     parser = argparse.ArgumentParser()
     parser.add_argument("-batch", help="batch size", type=int, default=128)
@@ -484,6 +500,9 @@ def build_parser():
                         default=0)
     parser.add_argument("-stream_recal_every", help="with -stream_recal: rewrite the median / IQR table from the ring "
                         "every E replayed ticks (alarm ticks excluded)", type=int, default=0)
+    parser.add_argument("-stream_recal_threshold", help="with -stream_recal: every recalibration also re-derives the "
+                        "threshold from the ring under the new table, as MARGIN times the ring's largest smoothed score",
+                        type=float, default=None, metavar="MARGIN")
     parser.add_argument("-calib_by_sensor", help="with -stream -stream_gaps -stream_calib_gaps: calibrate (and, with "
                         "-stream_recal, recalibrate) every sensor on its own real readings, not on complete ticks only",
                         action="store_true")
@@ -634,6 +653,7 @@ def from_args(argv=None) -> Main:
                   "localise": args.localise, "stream": args.stream,
                   "stream_gaps": args.stream_gaps, "stream_calib_gaps": args.stream_calib_gaps, "stream_recal": args.stream_recal,
                   "stream_recal_every": args.stream_recal_every, "calib_by_sensor": args.calib_by_sensor,
+                  "stream_recal_threshold": args.stream_recal_threshold,
                   "stream_raw": args.stream_raw, "prep": args.prep, "stream_save": args.stream_save,
                   "stream_resume": args.stream_resume, "stream_on": args.stream_on, "stream_off": args.stream_off,
                   "stream_clear": args.stream_clear, "stream_events": args.stream_events,

@@ -6,6 +6,7 @@ device — there is no CPU path.
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -1441,6 +1442,64 @@ def fleet_ring_counts(ring_keys, ring_keep, counts, kept=None, select=None, by_s
     _stream_buf(kept, torch.int32, units, "kept")
     _lib.call("gdn_fleet_ring_counts", _ptr(ring_keep), _ptr(select), units, n, R, _ptr(counts), _ptr(kept), _stream())
     return counts, kept
+
+
+def check_ring_margin(margin, name: str = "margin") -> float:
+    """A threshold margin as a float: finite and > 0, else a ValueError that names `name`.  Host arithmetic only."""
+    try:
+        value = float(margin)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} = {margin!r}: a finite number > 0 (the factor on the ring's largest score)") from None
+    if not (math.isfinite(value) and value > 0.0):
+        raise ValueError(f"{name} = {margin!r}: a finite number > 0 (the factor on the ring's largest score)")
+    return value
+
+
+def fleet_ring_threshold_workspace(units: int, R: int, device) -> torch.Tensor:
+    """The workspace of fleet_ring_threshold for `units` rings of R slots (gdn_fleet_ring_threshold_bytes)."""
+    nbytes = _lib.load().gdn_fleet_ring_threshold_bytes(units, R)
+    if nbytes <= 0:
+        raise _lib.GdnHipError(f"ring threshold: no kernel for units = {units}, R = {R} ({_FLEET_RING_LIMITS})")
+    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+
+
+def fleet_ring_threshold(state, ring_keys, ring_keep, med_iqr, w: int, margin: float, min_eligible: int, ws, threshold,
+                         peak, eligible, peak_slot, select=None, clear_frac=None, clear=None, by_sensor: bool = False):
+    """Re-derive the thresholds from the rings under the tables in force (gdn_fleet_ring_threshold, include/gdn_hip.h
+    "Threshold from the ring"): per unit the largest smoothed score among the eligible slots of ring_keys [U, n, R] /
+    ring_keep [U, R] into `peak` [U] float64, their number into `eligible` [U] int32, the smallest slot of the peak into
+    `peak_slot` [U] int32; threshold[u] = peak * margin in place for every unit with select[u] != 0 (None: all),
+    eligible >= min_eligible and a finite peak > 0, and with `clear_frac` / `clear` [U] float64 (both or neither)
+    clear[u] = threshold[u] * clear_frac[u] in the same step.  A single stream passes its tensors with a leading axis of
+    one.  `by_sensor`: the rings were written by calib="sensor" (the filler in a key is a missing reading, error 0.0).
+    Two launches, nothing is read back."""
+    if ring_keys.dim() != 3:
+        raise ValueError(f"ring_keys: expected [U, n, R], got {tuple(ring_keys.shape)}")
+    margin = check_ring_margin(margin)
+    if int(min_eligible) < 1:
+        raise ValueError(f"min_eligible = {min_eligible}: at least one eligible slot")
+    if (clear_frac is None) != (clear is None):
+        raise ValueError("clear_frac and clear: both or neither")
+    units, n = ring_keys.shape[:2]
+    R = _fleet_ring_dims(ring_keys, ring_keep, units, n)
+    _stream_buf(state, torch.int64, _fleet_state_words(units, n, w), "state")
+    _stream_buf(med_iqr, torch.float64, units * n * 2, "med_iqr")
+    _stream_buf(ws, torch.int64, max(1, _lib.load().gdn_fleet_ring_threshold_bytes(units, R) // 8), "ws")
+    _stream_buf(threshold, torch.float64, units, "threshold")
+    _stream_buf(peak, torch.float64, units, "peak")
+    _stream_buf(eligible, torch.int32, units, "eligible")
+    _stream_buf(peak_slot, torch.int32, units, "peak_slot")
+    if select is not None:
+        if select.dtype == torch.bool:
+            select = select.view(torch.uint8)
+        _stream_buf(select, torch.uint8, units, "select")
+    if clear is not None:
+        _stream_buf(clear_frac, torch.float64, units, "clear_frac")
+        _stream_buf(clear, torch.float64, units, "clear")
+    _lib.call("gdn_fleet_ring_threshold", _ptr(state), _ptr(ring_keys), _ptr(ring_keep), _ptr(med_iqr), _ptr(select),
+              units, n, w, R, 2 if by_sensor else 0, margin, int(min_eligible), _ptr(ws), _ptr(threshold),
+              _ptr(clear_frac), _ptr(clear), _ptr(peak), _ptr(eligible), _ptr(peak_slot), _stream())
+    return threshold
 
 
 def fleet_select_spans(units: int, n: int, limit: int = FLEET_SELECT_ROWS) -> list:

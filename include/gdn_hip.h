@@ -1188,6 +1188,37 @@ int gdn_fleet_calib_write_sensor(const void* state, const float* pred, const flo
                                  int exclude_alarms, double* ring_keys, uint8_t* ring_keep, void* stream);
 int gdn_fleet_ring_counts(const uint8_t* ring_keep, const uint8_t* select, int units, int n, int R, int32_t* counts,
                           int32_t* kept, void* stream);
+/* Threshold from the ring (opt-in; additive entry points, the ABI version does not move): after a
+ * recalibration has rewritten a table, the alarm threshold — a number in units of that table — is re-derived from the
+ * same ring by the rule of the first calibration: the largest smoothed anomaly score of the period.  A single stream is
+ * the fleet of one unit (its state is one state block, its ring one unit's slices): ONE symbol serves both.
+ * Per unit, with base = ticks mod R (from the unit's state block: the slot the next tick takes, the oldest of a full
+ * ring) and the table med_iqr [n, 2] as it stands when the launch runs (in stream order after the select):
+ *   error(s, q)  = (ring_keys[s, q] - median_s) * (1 / (|iqr_s| + 1e-2)), the scorer's expression and reciprocal;
+ *                  mode 2 (per-sensor rings): a key that is the filler bit pattern is a missing reading, error 0.0;
+ *   score(q)     = max over s of (((error(s, q-3) + error(s, q-2)) + error(s, q-1)) + error(s, q)) / 4.0, slots mod R,
+ *                  no FMA contraction; a NaN never wins the maximum;
+ *   eligible(q)  = ring_keep is 1 at q, q-1, q-2, q-3 (mod R) and (q - base) mod R >= 3: the ring holds the whole
+ *                  window the live scorer would smooth over, and the window does not straddle the seam between the
+ *                  newest and the oldest tick;
+ *   peak [U] float64 = the largest score of an eligible slot (-inf when there is none), peak_slot [U] int32 the
+ *   smallest slot that attains it (-1 when none does), eligible [U] int32 the number of eligible slots: always written.
+ *   threshold[u] = peak * margin (one float64 multiply) iff select[u] != 0 (select [U] uint8 may be NULL: every unit),
+ *   eligible >= min_eligible and peak is finite and > 0; otherwise it keeps its bits.  clear_frac / clear [U] float64
+ *   (both NULL, or both given): clear[u] = the new threshold * clear_frac[u], written with it and only then.
+ * mode: 0 or 1 — tick calibration (gdn_*_calib_write / _gaps rings: no filler test), 2 — gdn_*_calib_write_sensor rings.
+ * workspace: gdn_fleet_ring_threshold_bytes(units, R) bytes (16 per unit and tile of 61 slots; 0 outside the limits of
+ * gdn_fleet_calib_bytes), written and read by the call, nothing carried.  Two launches: a wave per (unit, tile) whose
+ * lanes run along the slots, three halo slots taken mod R, the sensors walked with the running maximum in a register;
+ * then a workgroup per unit that folds the partials (maximum, ties by the lower slot; integer sums) and applies the
+ * rule.  The maximum is exact in any order: no tiling changes a bit.  No atomics; no workgroup waits on another.
+ * Refusals, all before any launch: a null required pointer, one of clear_frac / clear without the other, a margin that
+ * is not finite or <= 0, min_eligible < 1, another mode: GDN_ERR_ARG; n, w and the ring limits: GDN_ERR_UNSUPPORTED.   */
+long long gdn_fleet_ring_threshold_bytes(int units, int R);
+int gdn_fleet_ring_threshold(const void* state, const double* ring_keys, const uint8_t* ring_keep, const double* med_iqr,
+                             const uint8_t* select, int units, int n, int w, int R, int mode, double margin,
+                             int min_eligible, void* workspace, double* threshold, const double* clear_frac,
+                             double* clear, double* peak, int32_t* eligible, int32_t* peak_slot, void* stream);
 /* Raw readings of a fleet (opt-in; additive entry points, the ABI version does not move): gdn_prep_ticks
  * ("Raw readings" above) per unit in ONE launch, with every unit's open downsample group and its length on the device,
  * so that how many raw ticks a unit hands over — and how many it holds — is data, never a launch argument.
