@@ -2,7 +2,7 @@
 the reference's `GDN(nn.Module).forward(data, org_edge_index)` API (models/GDN.py:82-187)."""
 from .model import GDN, GNNLayer, GraphLayer, OutLayer  # noqa: F401
 
-__all__ = ["GDN", "GNNLayer", "GraphLayer", "OutLayer", "Prep"]
+__all__ = ["GDN", "GNNLayer", "GraphLayer", "OutLayer", "Prep", "PrepUnits"]
 
 
 def __getattr__(name):
@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "Prep":
         from .prep import Prep
         return Prep
+    if name == "PrepUnits":
+        from .prep import PrepUnits
+        return PrepUnits
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -159,6 +159,7 @@ SIGNATURES = {
     "gdn_fleet_ring_threshold": [_p] * 5 + [_c_int] * 5 + [ctypes.c_double, _c_int] + [_p] * 8,
     "gdn_fleet_prep_bytes": [_c_int] * 3,
     "gdn_fleet_prep_ticks": [_p, _c_int, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4,
+    "gdn_fleet_prep_ticks_units": [_p, _c_int, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4,
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

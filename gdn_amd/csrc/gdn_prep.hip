@@ -4,7 +4,7 @@
 // need), gdn_prep_series (a resident raw file -> the prepared sensor-major series) and gdn_prep_ticks (the stream's
 // front end: raw ticks and the pending tail of the push before -> tick-major model ticks and the new tail).
 // gdn_fleet_prep_ticks ("Raw readings of a fleet") is that front end per unit of a streaming fleet in one launch, the
-// open groups and their lengths on the device.
+// open groups and their lengths on the device; gdn_fleet_prep_ticks_units is the same launch with a table per unit.
 // Raw data is tick-major [t_raw, n], fp32 or float64 (one template parameter); lanes run along sensors, so every
 // row read is coalesced.  All arithmetic is float64, every product and sum an operation of its own.  Plain loads,
 // compares and stores: no inline assembly, no atomics, no allocation, no synchronisation.
@@ -242,11 +242,13 @@ __global__ __launch_bounds__(GDN_PREP_THREADS) void gdn_prep_ticks_kernel(
 // workgroup reads nothing that another workgroup of the launch writes (a dead lane reads column n - 1: its own tile's),
 // so the state is updated in place with no second plane, no host parity and no atomic.  k == 0: counts[u] = 0 and
 // nothing else.  A count word outside 0 .. down - 1 (never written by this kernel) is clamped: no index leaves a buffer.
+// table_stride: doubles between two units' tables: 0 (gdn_fleet_prep_ticks: one table [n, 2] for all units) or 2 n
+// (gdn_fleet_prep_ticks_units: tables [U, n, 2]); the workgroup reads its own 64 rows of unit u's table either way.
 template <typename RAW>
 __global__ __launch_bounds__(GDN_PREP_THREADS) void gdn_fleet_prep_ticks_kernel(
     const RAW* __restrict__ raw, int rows, const int* __restrict__ raw_counts, double* __restrict__ pend_ticks,
-    int* __restrict__ pend_counts, int c, int n, int down, const double* __restrict__ table, float* __restrict__ out,
-    int* __restrict__ counts) {
+    int* __restrict__ pend_counts, int c, int n, int down, const double* __restrict__ table, size_t table_stride,
+    float* __restrict__ out, int* __restrict__ counts) {
   __shared__ double cols[GDN_PREP_COL_DOUBLES];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = blockDim.x >> 6;
   const int tile = blockIdx.x, u = blockIdx.y;
@@ -263,7 +265,8 @@ __global__ __launch_bounds__(GDN_PREP_THREADS) void gdn_fleet_prep_ticks_kernel(
   const RAW* __restrict__ ru = raw + (size_t)u * rows * n;
   double* __restrict__ pu = pend_ticks + (size_t)u * down * n;
   auto tick = [&](int q) -> double { return q < p ? pu[(size_t)q * n + ic] : (double)ru[(size_t)(q - p) * n + ic]; };
-  const double scale = table[2 * ic], offset = table[2 * ic + 1];
+  const double* __restrict__ tu = table + (size_t)u * table_stride;
+  const double scale = tu[2 * ic], offset = tu[2 * ic + 1];
   double* __restrict__ col = cols + (size_t)wv * down * 64;
   float* __restrict__ ou = out + (size_t)u * c * n;
   for (int g = wv; g < groups; g += waves) {
@@ -316,13 +319,13 @@ int prep_ticks(const void* raw, int r, const double* pend_in, int pending, doubl
 
 template <typename RAW>
 int fleet_prep_ticks(const void* raw, int rows, const int32_t* raw_counts, void* pend, int units, int c, int n, int down,
-                     const double* table, float* out, int32_t* counts, hipStream_t stream) {
+                     const double* table, size_t table_stride, float* out, int32_t* counts, hipStream_t stream) {
   const unsigned tiles = ((unsigned)n + 63) / 64;
   double* ticks = static_cast<double*>(pend);
   int* words = reinterpret_cast<int*>(ticks + (size_t)units * down * n);
   hipLaunchKernelGGL(gdn_fleet_prep_ticks_kernel<RAW>, dim3(tiles, (unsigned)units), dim3(64 * prep_waves(down)), 0,
-                     stream, static_cast<const RAW*>(raw), rows, raw_counts, ticks, words, c, n, down, table, out,
-                     counts);
+                     stream, static_cast<const RAW*>(raw), rows, raw_counts, ticks, words, c, n, down, table,
+                     table_stride, out, counts);
   return gdn_launch_status();
 }
 
@@ -373,14 +376,28 @@ extern "C" long long gdn_fleet_prep_bytes(int units, int n, int down) {
   return 8ll * units * down * n + ((4ll * units * ((n + 63) / 64) + 7) & ~7ll);
 }
 
-extern "C" int gdn_fleet_prep_ticks(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend,
-                                    int units, int c, int n, int down, const double* table, float* out,
-                                    int32_t* counts, void* stream) {
+// the two entry points of the fleet's front end: one body, the table stride apart
+static int fleet_prep_ticks_any(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend, int units,
+                                int c, int n, int down, const double* table, size_t table_stride, float* out,
+                                int32_t* counts, void* stream) {
   if (!raw || !raw_counts || !pend || !table || !out || !counts) return GDN_ERR_ARG;
   if (!gdn_fleet_rows_ok(units, c) || !prep_shape_ok(n, down)) return GDN_ERR_UNSUPPORTED;
   if (rows < 1 || rows > c * down) return GDN_ERR_ARG;
-  return raw_f64 ? fleet_prep_ticks<double>(raw, rows, raw_counts, pend, units, c, n, down, table, out, counts,
-                                            (hipStream_t)stream)
-                 : fleet_prep_ticks<float>(raw, rows, raw_counts, pend, units, c, n, down, table, out, counts,
-                                           (hipStream_t)stream);
+  return raw_f64 ? fleet_prep_ticks<double>(raw, rows, raw_counts, pend, units, c, n, down, table, table_stride, out,
+                                            counts, (hipStream_t)stream)
+                 : fleet_prep_ticks<float>(raw, rows, raw_counts, pend, units, c, n, down, table, table_stride, out,
+                                           counts, (hipStream_t)stream);
+}
+
+extern "C" int gdn_fleet_prep_ticks(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend,
+                                    int units, int c, int n, int down, const double* table, float* out,
+                                    int32_t* counts, void* stream) {
+  return fleet_prep_ticks_any(raw, rows, raw_f64, raw_counts, pend, units, c, n, down, table, 0, out, counts, stream);
+}
+
+extern "C" int gdn_fleet_prep_ticks_units(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend,
+                                          int units, int c, int n, int down, const double* tables, float* out,
+                                          int32_t* counts, void* stream) {
+  return fleet_prep_ticks_any(raw, rows, raw_f64, raw_counts, pend, units, c, n, down, tables, n > 0 ? 2 * (size_t)n : 0,
+                              out, counts, stream);
 }

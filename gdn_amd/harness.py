@@ -2990,12 +2990,21 @@ def fleet_clear_levels(lo, threshold, units: int) -> torch.Tensor:
 
 def fleet_check_prep(prep, units: int, chunk: int, n: int, itemsize: int = 4) -> None:
     """The host facts of a fleet's prep=, refused by name before any device work: a Prep fitted on another sensor count,
-    and a staging buffer [units, chunk * down, n] of `itemsize` bytes per reading beyond the evaluators' cap."""
+    a PrepUnits (per-unit tables) of another number of units, and a staging buffer [units, chunk * down,
+    n] of `itemsize` bytes per reading beyond the evaluators' cap."""
     if prep.n != n:
         raise ValueError(f"prep: fitted on {prep.n} sensors, the model has {n}")
+    if getattr(prep, "tables", None) is not None and prep.units != int(units):
+        raise ValueError(f"prep: per-unit tables of {prep.units} units, the fleet has units = {int(units)}")
     if int(units) * int(chunk) * prep.down * n * int(itemsize) > _VALIDATE_CHUNK_BYTES:
         raise ValueError(f"prep: the raw staging buffer [{units}, {chunk} * {prep.down}, {n}] of {itemsize}-byte readings "
                          f"exceeds {_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
+
+
+def prep_units(prep):
+    """The fingerprint of a per-unit prep's tables (PrepUnits.fingerprint), None for a shared Prep or no prep at all:
+    what tells the two forms apart on the host."""
+    return prep.fingerprint() if getattr(prep, "tables", None) is not None else None
 
 
 def fleet_raw_cuts(r: int, down: int, chunk: int) -> list:
@@ -3072,7 +3081,9 @@ def fleet_checkpoint_check(sd, expect) -> None:
     "state_bytes" = gdn_stream_state_bytes(n, w) PER UNIT and "calib_bytes" = gdn_fleet_calib_bytes(units, n, R) for the
     file's units and R (0 without rings) as the loaded library reports them, "model" (its model_fingerprint, or None: do
     not compare), "prep_down" (the caller's Prep.down, or None: no prep), "prep_n", and — a fleet that exists already —
-    "units" and "events" (its events configuration or None).  Host data only: no device work, no library call."""
+    "units" and "events" (its events configuration or None).  "prep_units": PrepUnits.fingerprint() of the caller's
+    per-unit tables, None (or absent) for a shared Prep; the file's optional `prep_units_sha256` must say the same.
+    Host data only: no device work, no library call."""
     who = _FLEET_CKPT
     _fleet_ckpt_format(sd)
     ints = {k: _ckpt_int(sd, k, who) for k in _FLEET_CKPT_INTS}
@@ -3102,6 +3113,16 @@ def fleet_checkpoint_check(sd, expect) -> None:
             raise ValueError(f"{who}: prep: fitted on {int(expect['prep_n'])} sensors, n = {ints['n']}")
     elif ints["prep_down"] != 0:
         raise ValueError(f"{who}: prep_down = {ints['prep_down']} without a prep")
+    tables = _ckpt_str(sd, "prep_units_sha256", who) if "prep_units_sha256" in sd else None
+    if tables is not None and not ints["prep"]:
+        raise ValueError(f"{who}: key 'prep_units_sha256' without a prep (a truncated or foreign file)")
+    if down is not None and tables != expect.get("prep_units"):
+        if tables is None or expect.get("prep_units") is None:
+            raise ValueError(f"{who}: prep_units_sha256: the fleet was saved with " + (
+                "one shared prep table and is resumed with per-unit tables (pass the Prep)" if tables is None else
+                "per-unit prep tables and is resumed with one shared Prep (pass the PrepUnits)"))
+        raise ValueError(f"{who}: prep_units_sha256 differs from the per-unit tables given: the open groups and the "
+                         "scores behind the state were normalised with other tables")
     if expect.get("model") is not None and strs["model_sha256"] != expect["model"]:
         raise ValueError(f"{who}: model_sha256 differs from the model given: the scores are the model's, so resuming "
                          "under other weights changes the alarm rate (check_model=False resumes all the same)")
@@ -3142,6 +3163,8 @@ def fleet_checkpoint_check(sd, expect) -> None:
     _check_recal_threshold(sd, expect, R, events, who)
     optional["recal_threshold"], optional["clear_frac"] = (np.float64, ()), (np.float64, (U,))
     for k in sd:
+        if k == "prep_units_sha256":                        # (an optional string, checked with the prep above)
+            continue
         if k not in want and k not in optional and k not in _FLEET_CKPT_INTS and k not in _FLEET_CKPT_STRS:
             raise ValueError(f"{who}: key {k!r} does not belong to this configuration (a foreign file)")
     for k, (dtype, shape) in list(want.items()) + [(k, v) for k, v in optional.items() if k in sd]:
@@ -3169,10 +3192,144 @@ def _fleet_checkpoint_expect(model, prep, units: int, recal: int, check_model: b
     lib = _lib.load()
     w = model.gnn_layers[0].gnn.lin.weight.shape[1]
     n = model.embedding.weight.shape[0]
+    if prep is not None and getattr(prep, "tables", None) is not None and prep.units != int(units):
+        raise ValueError(f"{_FLEET_CKPT}: prep: per-unit tables of {prep.units} units, units = {int(units)}")
     return {"n": n, "w": w, "abi": lib.gdn_abi_version(), "state_bytes": lib.gdn_stream_state_bytes(n, w),
             "calib_bytes": lib.gdn_fleet_calib_bytes(units, n, recal) if recal else 0,
             "model": model_fingerprint(model) if check_model else None,
-            "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n}
+            "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n,
+            "prep_units": prep_units(prep)}
+
+
+# unit hand-over: unit u's block of every fleet array is a single stream's byte for byte, so a unit moves
+# between a fleet's dict and a detector's by slicing and renaming; what is left is the configuration, checked by name
+_UNIT_CONFIG = ("n", "w", "top_m", "log", "with_gaps", "recal", "exclude_alarms", "recal_min", "calib", "wide", "prep",
+                "prep_down")
+
+
+def stream_calib_bytes(n: int, R: int) -> int:
+    """gdn_stream_calib_bytes(n, R) by host arithmetic (0 without a ring): the keys, the keep flags, 8-byte padding."""
+    return (8 * n * R + R + 7) & ~7 if R else 0
+
+
+def fleet_unit_to_stream(sd_fleet, u: int) -> dict:
+    """Unit `u` of a fleet's state dict as the state dict of a single detector (StreamDetector.load_state_dict's input):
+    the unit's slice of every per-unit array under the detector's key, the open group cut to its length, the fleet's
+    configuration, chunk and clocks (`handed`: recal_every goes on from the fleet's clock; `recals`: the fleet's calls).
+    `recal_counts` travels under every calibration (the fleet keeps it under both); under calib="sensor" `recal_kept` is
+    the smallest count that reached recal_min, as a detector states it.  The fingerprint of per-unit prep tables stays
+    behind: the detector takes prep.unit(u).  Host data only."""
+    who = _FLEET_CKPT
+    _fleet_ckpt_format(sd_fleet)
+    cfg = fleet_checkpoint_config(sd_fleet)
+    ints = {k: _ckpt_int(sd_fleet, k, who) for k in _FLEET_CKPT_INTS}
+    U, n, R = cfg["units"], cfg["n"], cfg["recal"]
+    u = int(u)
+    if not 0 <= u < U:
+        raise ValueError(f"{who}: unit {u}: the file holds units 0 .. {U - 1}")
+
+    def unit(key):
+        if key not in sd_fleet:
+            raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
+        return np.array(np.asarray(sd_fleet[key])[u])       # (a contiguous copy; one number stays 0-d)
+    sd = {"state": unit("state"), "med_iqr": unit("med_iqr"), "threshold": unit("threshold").reshape(1),
+          "log_ticks": unit("log_ticks"), "log_sensors": unit("log_sensors")}
+    if cfg["with_gaps"]:
+        sd["gaps"] = unit("gaps")
+    recal_kept = 0
+    if R:
+        sd["ring_keys"], sd["ring_keep"] = unit("ring_keys"), unit("ring_keep")
+        counts = unit("recal_counts").astype(np.int64)
+        sd["recal_counts"] = counts
+        if cfg["calib"] == "tick":
+            recal_kept = int(unit("recal_kept"))
+        else:
+            done = counts[counts >= cfg["recal_min"]]
+            recal_kept = int(done.min()) if done.size else 0
+    pending = 0
+    if cfg["prep"]:
+        pending = int(unit("pending"))
+        if not 0 <= pending < cfg["prep_down"]:
+            raise ValueError(f"{who}: pending[{u}] = {pending} outside an open group of prep_down = {cfg['prep_down']}")
+        sd["pending"] = np.ascontiguousarray(unit("pending_ticks")[:pending])
+    if fleet_checkpoint_events(sd_fleet) is not None:
+        sd["events"] = unit("events").view(np.uint8)
+        sd["events_lo"], sd["events_cfg"] = unit("clear").reshape(1), np.array(sd_fleet["events_cfg"])
+    if "recal_threshold" in sd_fleet:
+        sd["recal_threshold"] = np.array(sd_fleet["recal_threshold"])
+    if "clear_frac" in sd_fleet:
+        sd["clear_frac"] = unit("clear_frac").reshape(1)
+    if "calib_counts" in sd_fleet:
+        sd["calib_counts"] = unit("calib_counts")
+    out = dict(ints, format=STREAM_CHECKPOINT_FORMAT, calib_bytes=stream_calib_bytes(n, R), recal_kept=recal_kept,
+               calib_kept=int(unit("calib_kept")) if "calib_kept" in sd_fleet else -1, raw_pending=pending)
+    sd.update({k: np.array(int(out[k]), dtype=np.int64) for k in _CKPT_INTS})
+    sd["calib"], sd["model_sha256"] = np.array(cfg["calib"]), np.array(_ckpt_str(sd_fleet, "model_sha256", who))
+    return sd
+
+
+def stream_to_fleet_unit(sd_stream, sd_fleet_config) -> dict:
+    """A detector's state dict as ONE unit of the fleet whose state dict (or any dict that holds its configuration keys,
+    `abi`, `state_bytes`, `model_sha256` and the optional events_cfg / recal_threshold) is `sd_fleet_config`: the unit's
+    block of every per-unit array under the fleet's key, without the unit axis (`pending_ticks`: the rows of the open
+    group only, `pending` their number; `recal_counts` int32, from the detector's or — tick calibration — its
+    `recal_kept` for every sensor).  Refused with a ValueError that names the field: any of n, w, top_m, log, with_gaps,
+    recal, exclude_alarms, recal_min, calib, wide, prep, prep_down, events (and on, off, cap, m), recal_threshold,
+    model_sha256, abi or state_bytes that differs.  chunk, recal_every and the clocks are the fleet's.  Host data only."""
+    who = "unit hand-over"
+    _ckpt_format(sd_stream)
+    mine, theirs = stream_checkpoint_config(sd_stream), fleet_checkpoint_config(sd_fleet_config)
+    for k in _UNIT_CONFIG:
+        if mine[k] != theirs[k]:
+            raise ValueError(f"{who}: {k} = {mine[k]!r}, the fleet was built with {k} = {theirs[k]!r}"
+                             + (" (the route is per launch: all units of a push share it)" if k == "wide" else ""))
+    for k in ("abi", "state_bytes"):
+        a, b = _ckpt_int(sd_stream, k), _ckpt_int(sd_fleet_config, k, _FLEET_CKPT)
+        if a != b:
+            raise ValueError(f"{who}: {k} = {a}, the fleet has {k} = {b} (another build of the library)")
+    if _ckpt_str(sd_stream, "model_sha256") != _ckpt_str(sd_fleet_config, "model_sha256", _FLEET_CKPT):
+        raise ValueError(f"{who}: model_sha256 differs from the fleet's model: a fleet scores all units with one model")
+    ev, fev = stream_checkpoint_events(sd_stream), None
+    if "events_cfg" in sd_fleet_config:                     # (the configuration alone: the tables need not be there)
+        fev = fleet_checkpoint_events({"events": None, "clear": None, "events_cfg": sd_fleet_config["events_cfg"]})
+    if (ev is None) != (fev is None):
+        raise ValueError(f"{who}: events: the detector keeps " + ("no" if ev is None else "an") + " episode table, the "
+                         "fleet " + ("does" if ev is None else "does not"))
+    for k in _EVENTS_FIELDS if ev is not None else ():
+        if ev[k] != fev[k]:
+            raise ValueError(f"{who}: events.{k} = {ev[k]}, the fleet was built with events.{k} = {fev[k]}")
+    margin, theirs_margin = checkpoint_recal_threshold(sd_stream), checkpoint_recal_threshold(sd_fleet_config, _FLEET_CKPT)
+    if margin != theirs_margin:
+        raise ValueError(f"{who}: recal_threshold = {margin}, the fleet was built with recal_threshold = {theirs_margin}")
+    n, R = mine["n"], mine["recal"]
+
+    def arr(key):
+        if key not in sd_stream:
+            raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
+        return np.ascontiguousarray(np.asarray(sd_stream[key]))
+    out = {"state": arr("state"), "med_iqr": arr("med_iqr"), "threshold": arr("threshold").reshape(()),
+           "log_ticks": arr("log_ticks"), "log_sensors": arr("log_sensors")}
+    if mine["with_gaps"]:
+        out["gaps"] = arr("gaps")
+    if R:
+        out["ring_keys"], out["ring_keep"] = arr("ring_keys"), arr("ring_keep")
+        kept = _ckpt_int(sd_stream, "recal_kept")
+        if mine["calib"] == "tick":
+            out["recal_kept"] = np.array(kept, dtype=np.int32)
+        out["recal_counts"] = (arr("recal_counts") if "recal_counts" in sd_stream else
+                               np.full((n,), kept if mine["calib"] == "tick" else 0)).astype(np.int32)
+    if mine["prep"]:
+        out["pending_ticks"] = arr("pending")
+        out["pending"] = np.array(_ckpt_int(sd_stream, "raw_pending"), dtype=np.int32)
+    if ev is not None:
+        out["events"], out["clear"] = arr("events").view(np.int64), arr("events_lo").reshape(())
+    if "clear_frac" in sd_stream:
+        out["clear_frac"] = arr("clear_frac").reshape(())
+    if "calib_counts" in sd_stream:
+        out["calib_counts"] = arr("calib_counts")
+    if _ckpt_int(sd_stream, "calib_kept") >= 0:
+        out["calib_kept"] = np.array(_ckpt_int(sd_stream, "calib_kept"), dtype=np.int64)
+    return out
 
 
 class StreamFleet(_StreamCore):
@@ -3253,8 +3410,20 @@ class StreamFleet(_StreamCore):
     one .npz with a format number of its own; the static buffers of a push, the workspaces and the graphs do not.  A
     fleet stream cut by a save and a load writes the bits of the uninterrupted one.
 
-    Out of scope: a command-line flag, per-unit prep tables, more than one process, moving a unit between a fleet file
-    and a detector file."""
+    `prep=PrepUnits` gives every unit a min-max table of its own — pumps of one model with duty points,
+    hence raw ranges, of their own: the same copy, counts write and replay, the leading launch
+    gdn_fleet_prep_ticks_units (the same kernel body, reading tables[u]).  The contract per unit reads
+    StreamDetector(prep=prep.unit(u), ...).  A checkpoint keeps the tables' fingerprint (`prep_units_sha256`, an optional
+    key) and `load(path, model, prep=)` refuses a shared Prep for such a file, per-unit tables for a shared one, and other
+    tables, by that name.
+
+    Unit hand-over: `unit_state_dict(u)` is the dict StreamDetector.load_state_dict / load accepts (the
+    unit leaves the fleet and goes on alone, bit for bit); `load_unit(u, sd)` takes a detector's state dict into unit u
+    in place, through the pointers the captured graph reads (no recapture; every other unit's memory stays byte for
+    byte); `reset_unit(u, med_iqr, threshold, history)` re-seeds one unit as the constructor seeds it.
+    `localise(u, rows=None)` is StreamDetector.localise for unit u's real rows of the last sub-push.
+
+    Out of scope: a command-line flag, more than one process."""
 
     def __init__(self, model, med_iqr, threshold, history, chunk: int, top_m: int = 1, log: int = 4096,
                  use_graph: bool = True, wide: bool | None = None, gaps: bool = False, events=None, recal: int = 0,
@@ -3597,27 +3766,40 @@ class StreamFleet(_StreamCore):
         (`pending_ticks` [U, down, n] float64, `pending` [U] int32: tile 0's count, all tiles of a unit agree) and the
         raw rows handed; the host counters, the configuration, and the identity of what wrote it.  The staging, chunk,
         window, prediction and output buffers, gap_chunk, counts, the workspaces and the graphs stay behind.
-        Read-only: ONE batch of device-to-host copies on the current stream and ONE synchronisation."""
+        Read-only: ONE batch of device-to-host copies on the current stream and ONE synchronisation.
+        prep=PrepUnits adds the optional `prep_units_sha256` (the tables' fingerprint)."""
+        sd = self._state_dict(slice(None))
+        if prep_units(self.prep) is not None:
+            sd["prep_units_sha256"] = np.array(prep_units(self.prep))
+        return sd
+
+    def _state_dict(self, sel: slice) -> dict:
+        """state_dict() of the units `sel` as a fleet of that many units (all of them: the fleet's own; one: what
+        unit_state_dict converts), the host counters and the configuration the fleet's."""
         lib = _lib.load()
-        U, n, m = self.units, self.n, self.top_m
-        cfg = self._config()
-        dev = {"state": self.state.view(torch.uint8).view(U, -1), "med_iqr": self.med_iqr, "threshold": self.threshold}
+        n, m = self.n, self.top_m
+        U = len(range(*sel.indices(self.units)))
+        cfg = dict(self._config(), units=U)
+        dev = {"state": self.state.view(torch.uint8).view(self.units, -1)[sel], "med_iqr": self.med_iqr[sel],
+               "threshold": self.threshold[sel]}
         if self.log_ticks is not None:
-            dev["log_ticks"], dev["log_sensors"] = self.log_ticks, self.log_sensors
+            dev["log_ticks"], dev["log_sensors"] = self.log_ticks[sel], self.log_sensors[sel]
         if self.with_gaps:
-            dev["gaps"] = self.gaps
+            dev["gaps"] = self.gaps[sel]
         if self.recal:
-            dev["ring_keys"], dev["ring_keep"], dev["recal_counts"] = self.ring_keys, self.ring_keep, self.recal_counts
+            dev["ring_keys"], dev["ring_keep"] = self.ring_keys[sel], self.ring_keep[sel]
+            dev["recal_counts"] = self.recal_counts[sel]
             if self.recal_kept is not None:
-                dev["recal_kept"] = self.recal_kept
+                dev["recal_kept"] = self.recal_kept[sel]
         if self.events is not None:
-            dev["events"], dev["clear"] = self.events, self.clear
+            dev["events"], dev["clear"] = self.events[sel], self.clear[sel]
         if self.recal_threshold is not None and self.clear_frac is not None:
-            dev["clear_frac"] = self.clear_frac
+            dev["clear_frac"] = self.clear_frac[sel]
         if self.calib_counts is not None:
-            dev["calib_counts"] = self.calib_counts
+            dev["calib_counts"] = self.calib_counts[sel]
         if self.prep is not None:
-            dev["pending_ticks"], dev["pending"] = ops.fleet_prep_views(self.pend, U, n, self.prep.down)
+            ticks, pending = ops.fleet_prep_views(self.pend, self.units, n, self.prep.down)
+            dev["pending_ticks"], dev["pending"] = ticks[sel], pending[sel]
         weights = self.model.state_dict()
         names = sorted(weights)
         host = _host_copies(list(dev.values()) + [weights[k] for k in names])
@@ -3630,7 +3812,7 @@ class StreamFleet(_StreamCore):
         if self.events is not None:
             sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
         if self.calib_kept is not None:
-            sd["calib_kept"] = torch.as_tensor(self.calib_kept, dtype=torch.int64).reshape(U).numpy().copy()
+            sd["calib_kept"] = torch.as_tensor(self.calib_kept, dtype=torch.int64).reshape(self.units)[sel].numpy().copy()
         if self.prep is not None:
             tiles = sd["pending"]
             assert (tiles == tiles[:, :1]).all(), "the pending counts of a unit's sensor tiles disagree"
@@ -3719,3 +3901,168 @@ class StreamFleet(_StreamCore):
                      recal_threshold=checkpoint_recal_threshold(sd, _FLEET_CKPT))
         fleet.load_state_dict(sd, check_model=False)        # (the weights were compared above, once)
         return fleet
+
+    # unit hand-over: unit u's block of every allocation is a single stream's byte for byte
+    def _unit(self, u, what: str) -> int:
+        if not 0 <= int(u) < self.units:
+            raise ValueError(f"{what}({u}): the fleet has units 0 .. {self.units - 1}")
+        return int(u)
+
+    def unit_prep(self, u: int):
+        """The prep a detector of unit `u` takes: prep.unit(u) under per-unit tables, else the fleet's own (or None)."""
+        return self.prep.unit(u) if getattr(self.prep, "tables", None) is not None else self.prep
+
+    def unit_state_dict(self, u: int) -> dict:
+        """Unit `u` as the state dict of a single detector (fleet_unit_to_stream of that unit's slice of state_dict()):
+        StreamDetector.load_state_dict / load accept it — with the fleet's model and `unit_prep(u)` — and the detector,
+        pushed the unit's later ticks in the same cuts, writes the bits unit u writes in the fleet that went on; its
+        recal_every clock starts from the fleet's.  Read-only: ONE batch of copies of that unit's blocks alone and ONE
+        synchronisation."""
+        u = self._unit(u, "unit_state_dict")
+        return fleet_unit_to_stream(self._state_dict(slice(u, u + 1)), 0)
+
+    def _config_dict(self, model_sha256: str) -> dict:
+        """What stream_to_fleet_unit reads of a fleet's state dict, from host facts alone (no device read)."""
+        lib = _lib.load()
+        sd = {k: np.array(int(v), dtype=np.int64) for k, v in self._config().items() if k != "calib"}
+        sd.update(format=np.array(FLEET_CHECKPOINT_FORMAT, dtype=np.int64), calib=np.array(self.calib),
+                  abi=np.array(lib.gdn_abi_version(), dtype=np.int64), model_sha256=np.array(model_sha256),
+                  state_bytes=np.array(lib.gdn_stream_state_bytes(self.n, self.w), dtype=np.int64))
+        if self.events is not None:
+            sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
+        if self.recal_threshold is not None:
+            sd["recal_threshold"] = np.array(self.recal_threshold, dtype=np.float64)
+        return sd
+
+    def _clear_frac_unit(self, u: int, frac=None):
+        """clear_frac[u] under recal_threshold= and events=: `frac`, else lo / threshold of the unit's levels as they
+        stand (_ring_buffers' rule); the other units' fractions come into being as they would have at their next use."""
+        if self.recal_threshold is None or self.events is None:
+            return
+        self._ring_buffers()
+        if frac is None:
+            frac = self.clear[u] / self.threshold[u]
+            frac = torch.where(torch.isfinite(frac) & (frac <= 1.0), frac, torch.ones_like(frac))
+        self.clear_frac[u].copy_(frac)
+
+    def load_unit(self, u: int, sd, check_model: bool = True) -> None:
+        """Take the stream of a detector's state dict `sd` (StreamDetector.state_dict(), or a file's) into unit `u`, IN
+        PLACE: every array goes into unit u's block of the allocations the captured graph reads, so nothing is
+        recaptured and every other unit's memory stays byte for byte.  Checked first, before any device write
+        (stream_to_fleet_unit, then stream_checkpoint_check against unit_prep(u)): n, w, top_m, log, gaps, recal and its
+        flags, calib, wide (the route is per launch), prep / down, events, recal_threshold, the model's fingerprint
+        (unless check_model=False) and the ABI version must be the fleet's — a ValueError names the field.  chunk and
+        recal_every are the fleet's: unit u goes on as the detector would have alone, on the fleet's clock.  Afterwards
+        unit u has no rows in the static buffers of the last push (counts[u] = 0: localise(u) is empty)."""
+        u = self._unit(u, "load_unit")
+        expect = _checkpoint_expect(self.model, self.unit_prep(u), self.recal, check_model)
+        expect["events"], expect["recal_threshold"] = self.events_cfg, self.recal_threshold
+        sha = expect["model"] if check_model else _ckpt_str(sd, "model_sha256")
+        unit = stream_to_fleet_unit(sd, self._config_dict(sha))
+        stream_checkpoint_check(sd, expect)
+        dev = self.state.device
+
+        def put(dst, key):
+            dst.copy_(torch.from_numpy(np.array(unit[key])))         # (a copy: numpy.load may hand out read-only arrays)
+        put(self.state.view(torch.uint8).view(self.units, -1)[u], "state")
+        put(self.med_iqr[u], "med_iqr")
+        put(self.threshold[u], "threshold")
+        if self.log_ticks is not None:
+            put(self.log_ticks[u], "log_ticks")
+            put(self.log_sensors[u], "log_sensors")
+        if self.with_gaps:
+            put(self.gaps[u], "gaps")
+        if self.recal:
+            put(self.ring_keys[u], "ring_keys")
+            put(self.ring_keep[u], "ring_keep")
+            put(self.recal_counts[u], "recal_counts")
+            if self.recal_kept is not None:
+                put(self.recal_kept[u], "recal_kept")
+        if self.events is not None:
+            put(self.events[u], "events")
+            put(self.clear[u], "clear")
+            self._clear_frac_unit(u, torch.from_numpy(np.array(unit["clear_frac"])).to(dev) if "clear_frac" in unit
+                                  else None)
+        if self.prep is not None:
+            ticks, pending = ops.fleet_prep_views(self.pend, self.units, self.n, self.prep.down)
+            p = int(unit["pending"])
+            put(ticks[u, :p], "pending_ticks")
+            pending[u].fill_(p)
+        if self.calib_counts is not None and "calib_counts" in unit:
+            put(self.calib_counts[u], "calib_counts")
+        if self.calib_kept is not None and "calib_kept" in unit:
+            self.calib_kept[u] = int(unit["calib_kept"])
+        self.counts[u] = 0
+
+    def reset_unit(self, u: int, med_iqr, threshold, history, lo=None, seed=None) -> None:
+        """Re-seed unit `u` as the constructor seeds a unit — a pump repaired or replaced: `med_iqr` [n, 2] float64,
+        `threshold` one number, `history` [n, h >= w] fp32 on the device (the state starts after its last w ticks, counters
+        and carry zero).  The unit's log and gap counters are emptied, its ring is emptied or — `seed` = (pred, gt, keep,
+        valid), the rows from_calibration seeds a ring from (_seed_ring) — seeded, its episode table is emptied with the
+        clear level `lo` (None: the threshold) and no raw group stays open.  Afterwards unit u equals a fresh
+        StreamDetector(model, med_iqr, threshold, history, ...) of the fleet's options; the other units, the fleet's
+        `wide` word, its clocks and the captured graph are untouched.  Refused before any write to the fleet: another
+        shape, gaps=True with a non-finite tail of `history` (as the constructor refuses it), a `lo` above the threshold
+        or without events=, a `seed` without a ring."""
+        u = self._unit(u, "reset_unit")
+        n, w = self.n, self.w
+        history = ops._chk(history, name="history")
+        if history.dim() != 2 or history.shape[0] != n:
+            raise ValueError(f"expected a history of shape [{n}, h], got {tuple(history.shape)}")
+        med_iqr = ops._chk(med_iqr, torch.float64, name="med_iqr")
+        if med_iqr.shape != (n, 2):
+            raise ValueError(f"expected med_iqr of shape [{n}, 2], got {tuple(med_iqr.shape)}")
+        threshold = torch.as_tensor(threshold, dtype=torch.float64)
+        if threshold.numel() != 1:
+            raise ValueError(f"threshold: one number for one unit, got {tuple(threshold.shape)}")
+        if self.events is None and lo is not None:
+            raise ValueError(f"lo = {lo!r}: the fleet was built with events=None and keeps no clear level")
+        if seed is not None and not self.recal:
+            raise ValueError("seed: the fleet was built with recal=0 and keeps no calibration rings")
+        clear = None if self.events is None else fleet_clear_levels(lo, threshold, 1)
+        if self.with_gaps and history.shape[1] >= w and not bool(torch.isfinite(history[:, -w:]).all()):
+            raise ValueError(f"history: its last {w} ticks hold a value that is not finite; with gaps=True every missing "
+                             "reading is held at an earlier real one, so the unit's stream must begin on real readings")
+        state = ops.stream_state(history, w)                          # (a history shorter than w is refused here)
+        self.state[u].copy_(state)
+        self.med_iqr[u].copy_(med_iqr)
+        self.threshold[u].copy_(threshold.reshape(()))
+        if self.log_ticks is not None:
+            self.log_ticks[u].zero_()
+            self.log_sensors[u].zero_()
+        if self.with_gaps:
+            self.gaps[u].zero_()
+        if self.recal:
+            self.ring_keys[u].view(torch.int64).fill_(-1)            # all ones: the filler (ops.stream_calib_ring)
+            self.ring_keep[u].zero_()
+            self.recal_counts[u].zero_()
+            if self.recal_kept is not None:
+                self.recal_kept[u].zero_()
+            if seed is not None:
+                _seed_ring(self.ring_keys[u], self.ring_keep[u], *seed)
+        if self.events is not None:
+            self.events[u].zero_()
+            self.clear[u].copy_(clear[0])
+            self._clear_frac_unit(u)
+        if self.prep is not None:
+            ops.fleet_prep_views(self.pend, self.units, n, self.prep.down)[1][u].zero_()
+        self.counts[u] = 0
+
+    def localise(self, u: int, rows=None) -> Localisation:
+        """StreamDetector.localise for unit `u`'s real rows of the last sub-push: which sensors deviate at its alarm rows
+        (`rows=None`; or the given rows, refused at or beyond counts[u]) and which neighbours they were reading — ONE
+        model.attention_at on the fleet's static window buffer.  The fields are a detector's of that unit (`ticks`: the
+        unit's own stream ticks; under gaps=True `observed` is the FILLED reading).  A silent unit returns an empty
+        result.  ONE read of counts[u] (a synchronisation)."""
+        u = self._unit(u, "localise")
+        r = min(max(int(self.counts[u]), 0), self._last)
+        if rows is None:
+            rows = torch.nonzero(self.alarm[u, :r]).view(-1)
+        rows = _row_indices(rows, self.state.device, r, f"rows outside [0, {r}): unit {u} has counts[{u}] = {r} real "
+                            "rows in the last push")
+        first = self.state[u, 0] - r                        # (advance has run: ticks counts the push already)
+        c, n = self.chunk, self.n
+        flat = self.units * c
+        return _localisation(self.model, self.x.view(flat, n, self.w), first + rows, u * c + rows,
+                             self.top_sensors[u, rows].long(), self.top_scores[u, rows], self.pred.view(flat, n),
+                             self.chunk_buf.view(flat, n))

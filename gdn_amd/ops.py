@@ -1658,7 +1658,9 @@ def fleet_prep_ticks(raw, raw_counts, pend, down: int, table, out, counts):
     :raw_counts[u]]] (`raw` [U, rows, n] fp32 or float64; raw_counts [U] int32 on the device, clamped to 0 .. rows by
     the kernel) -> out[u, g, :] for g < groups = (pending_u + raw_counts[u]) // down (`out` [U, c, n] fp32, rows
     <= c * down), counts[u] = groups, and the rest becomes the unit's open group in `pend` (fleet_prep_state), in
-    place.  Rows of out at or beyond groups are not written; a unit with raw_counts[u] == 0 keeps its pending state."""
+    place.  Rows of out at or beyond groups are not written; a unit with raw_counts[u] == 0 keeps its pending state.
+    `table` [n, 2] float64 serves all units (gdn_fleet_prep_ticks); tables [U, n, 2] give every unit its own
+    (gdn_fleet_prep_ticks_units: the same kernel body with a table stride)."""
     if not raw.is_cuda:
         raise _lib.GdnHipError(f"raw is on {raw.device}: gdn_amd ops need a HIP device (no CPU fallback)")
     if raw.dtype not in (torch.float32, torch.float64):
@@ -1668,7 +1670,14 @@ def fleet_prep_ticks(raw, raw_counts, pend, down: int, table, out, counts):
                          f"{tuple(raw.shape)}")
     units, rows, n = raw.shape
     down = _prep_down(down)
-    table = _prep_table(table, n)
+    per_unit = isinstance(table, torch.Tensor) and table.dim() == 3
+    if per_unit:
+        table = _chk(table, torch.float64, name="tables")
+        if table.shape != (units, n, 2):
+            raise ValueError(f"expected tables of shape [{units}, {n}, 2] (scale, offset per unit), got "
+                             f"{tuple(table.shape)}")
+    else:
+        table = _prep_table(table, n)
     _stream_buf(out, torch.float32, 1, "out")
     if out.dim() != 3 or out.shape[0] != units or out.shape[2] != n:
         raise ValueError(f"expected out [{units}, c, {n}] (one row per unit and prepared tick), got {tuple(out.shape)}")
@@ -1678,8 +1687,9 @@ def fleet_prep_ticks(raw, raw_counts, pend, down: int, table, out, counts):
     _stream_buf(raw_counts, torch.int32, units, "raw_counts")
     _stream_buf(counts, torch.int32, units, "counts")
     _stream_buf(pend, torch.int64, _fleet_prep_bytes(units, n, down) // 8, "pend")
-    _lib.call("gdn_fleet_prep_ticks", _ptr(raw), rows, int(raw.dtype == torch.float64), _ptr(raw_counts), _ptr(pend),
-              units, c, n, down, _ptr(table), _ptr(out), _ptr(counts), _stream())
+    _lib.call("gdn_fleet_prep_ticks_units" if per_unit else "gdn_fleet_prep_ticks", _ptr(raw), rows,
+              int(raw.dtype == torch.float64), _ptr(raw_counts), _ptr(pend), units, c, n, down, _ptr(table), _ptr(out),
+              _ptr(counts), _stream())
     return out
 
 

@@ -95,6 +95,93 @@ class Prep:
                        [str(s) for s in z["names"]])
 
 
+class PrepUnits:
+    """A fitted front end per unit of a fleet: `tables` [U, n, 2] float64 and `stats` [U, n, 4] float64 on
+    one device — unit u's are a Prep's, fitted on that unit's own raw readings — with ONE `down` and ONE list of sensor
+    `names` for all units (one model).  harness.StreamFleet(prep=PrepUnits) normalises unit u with tables[u]
+    (gdn_fleet_prep_ticks_units); `unit(u)` is the plain Prep of that unit, views of the same memory."""
+
+    def __init__(self, tables: torch.Tensor, stats: torch.Tensor, down: int, names=None):
+        self.down = ops._prep_down(down)
+        if tables.dtype != torch.float64 or tables.dim() != 3 or tables.shape[0] < 1 or tables.shape[2] != 2:
+            raise ValueError(f"expected float64 tables [U >= 1, n, 2] (scale, offset per unit), got {tables.dtype} "
+                             f"{tuple(tables.shape)}")
+        units, n = tables.shape[:2]
+        if stats.dtype != torch.float64 or stats.shape != (units, n, 4):
+            raise ValueError(f"expected float64 stats [{units}, {n}, 4] (min, max, mean, count per unit), got "
+                             f"{stats.dtype} {tuple(stats.shape)}")
+        if stats.device != tables.device:
+            raise ValueError(f"tables are on {tables.device}, stats on {stats.device}")
+        self.tables, self.stats, self.units, self.n = tables.contiguous(), stats.contiguous(), units, n
+        self.table = self.tables                                     # (what ops.fleet_prep_ticks is handed, either form)
+        self.names = [str(s) for s in names] if names is not None else [str(i) for i in range(n)]
+        if len(self.names) != n:
+            raise ValueError(f"{len(self.names)} sensor names for {n} sensors")
+        self._sha256 = None
+
+    @classmethod
+    def fit(cls, raw_train: torch.Tensor, down: int = 10, names=None) -> "PrepUnits":
+        """Every unit's min-max table from its own `raw_train[u]` [t_raw, n] (device; fp32 or float64): Prep.fit per
+        unit, U launches of gdn_prep_stats at fit time."""
+        if raw_train.dim() != 3 or raw_train.shape[0] < 1:
+            raise ValueError(f"expected raw_train of shape [U, t_raw, n], got {tuple(raw_train.shape)}")
+        return cls.from_preps([Prep.fit(unit, down, names) for unit in raw_train])
+
+    @classmethod
+    def from_preps(cls, preps) -> "PrepUnits":
+        """The fitted Preps of U units, stacked; `down` and `n` must agree (refused by name), the names are the first's."""
+        preps = list(preps)
+        if not preps:
+            raise ValueError("from_preps: at least one Prep")
+        for u, p in enumerate(preps):
+            if p.down != preps[0].down:
+                raise ValueError(f"down: unit {u} has down = {p.down}, unit 0 has down = {preps[0].down}")
+            if p.n != preps[0].n:
+                raise ValueError(f"n: unit {u} was fitted on {p.n} sensors, unit 0 on {preps[0].n}")
+        return cls(torch.stack([p.table for p in preps]), torch.stack([p.stats for p in preps]), preps[0].down,
+                   preps[0].names)
+
+    def unit(self, u: int) -> Prep:
+        if not 0 <= int(u) < self.units:
+            raise ValueError(f"unit({u}): the tables cover units 0 .. {self.units - 1}")
+        return Prep(self.tables[int(u)], self.stats[int(u)], self.down, self.names)
+
+    def series(self, raw: torch.Tensor, fill: str | None = None, labels: torch.Tensor | None = None, skip: int = 0):
+        """(series [U, n, T - skip] fp32, labels [T - skip] or None) of `raw` [U, t_raw, n]: Prep.series per unit (one
+        gdn_prep_series each); `labels` [t_raw] belong to the time axis all units share."""
+        if raw.dim() != 3 or raw.shape[0] != self.units:
+            raise ValueError(f"expected raw of shape [{self.units}, t_raw, {self.n}], got {tuple(raw.shape)}")
+        done = [self.unit(u).series(raw[u], fill=fill, labels=labels, skip=skip) for u in range(self.units)]
+        return torch.stack([s for s, _ in done]), done[0][1]
+
+    def fingerprint(self) -> str:
+        """SHA-256 (hex) over down, the shape and the bytes of `tables`: what a fleet checkpoint keeps of them.  ONE
+        device read at its first use."""
+        if self._sha256 is None:
+            host = self.tables.detach().cpu().contiguous().numpy()
+            self._sha256 = tables_fingerprint(host, self.down)
+        return self._sha256
+
+    def save(self, path: str) -> None:
+        np.savez(path, tables=self.tables.cpu().numpy(), stats=self.stats.cpu().numpy(), down=np.int64(self.down),
+                 names=np.array(self.names, dtype=str))
+
+    @classmethod
+    def load(cls, path: str, device="cuda") -> "PrepUnits":
+        with np.load(path, allow_pickle=False) as z:
+            return cls(torch.from_numpy(z["tables"]).to(device), torch.from_numpy(z["stats"]).to(device), int(z["down"]),
+                       [str(s) for s in z["names"]])
+
+
+def tables_fingerprint(tables: np.ndarray, down: int) -> str:
+    """PrepUnits.fingerprint's arithmetic on a host array [U, n, 2] float64."""
+    import hashlib
+    tables = np.ascontiguousarray(tables, dtype=np.float64)
+    h = hashlib.sha256(f"prep_units|{int(down)}|{tables.shape}|".encode())
+    h.update(tables.tobytes())
+    return h.hexdigest()
+
+
 # --------------------------------------------------------------------------- command line
 def read_raw_csv(path: str, label: str = "attack", drop_cols: int = 0, names=None):
     """(raw [t_raw, n] float64, labels [t_raw] float64, sensor names) of a raw CSV read as the scripts read it: the

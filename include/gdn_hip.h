@@ -1239,11 +1239,18 @@ int gdn_fleet_ring_threshold(const void* state, const double* ring_keys, const u
  *                         writes them; tile 0 also writes counts[u].  No workgroup reads what another writes: in place,
  *                         no second plane, no atomic.  raw_counts[u] == 0: counts[u] = 0, the unit's pending state
  *                         stays byte for byte.
+ *   gdn_fleet_prep_ticks_units   the same launch with tables [U, n, 2] float64: unit u normalises with
+ *                         tables[u] — pumps of one model with duty points, hence raw ranges, of their own.  ONE kernel
+ *                         body serves both: the per-unit table stride is 2 n doubles here and 0 above; grid, pending
+ *                         rule, arithmetic and refusals are those of gdn_fleet_prep_ticks, and unit u's output equals
+ *                         gdn_prep_ticks with table = tables[u] on that unit's real rows, bit for bit.
  * Refusals, all before any launch: a null pointer, rows < 1, rows > c down: GDN_ERR_ARG; units * c > 4096, units, c < 1,
  * n outside 1 .. 4096, down outside 1 .. 64: GDN_ERR_UNSUPPORTED (gdn_fleet_prep_bytes: 0; units <= 4096).             */
 long long gdn_fleet_prep_bytes(int units, int n, int down);
 int gdn_fleet_prep_ticks(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend, int units,
                          int c, int n, int down, const double* table, float* out, int32_t* counts, void* stream);
+int gdn_fleet_prep_ticks_units(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend, int units,
+                               int c, int n, int down, const double* tables, float* out, int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }
