@@ -160,6 +160,11 @@ SIGNATURES = {
     "gdn_fleet_prep_bytes": [_c_int] * 3,
     "gdn_fleet_prep_ticks": [_p, _c_int, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4,
     "gdn_fleet_prep_ticks_units": [_p, _c_int, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4,
+    "gdn_fleet_series_keys": [_p] * 4 + [_c_int] * 4 + [_p, _p],
+    "gdn_fleet_series_smooth_max": [_p] * 3 + [_c_int] * 3 + [_p] * 3,
+    "gdn_fleet_series_smooth_topm": [_p] * 3 + [_c_int] * 4 + [_p] * 3,
+    "gdn_fleet_series_smooth_max_gaps": [_p] * 3 + [_c_int] * 3 + [_p] * 4,
+    "gdn_fleet_series_smooth_topm_gaps": [_p] * 3 + [_c_int] * 4 + [_p] * 4,
 }
 
 # gdn_kernel_family's enums (include/gdn_hip.h "route table")

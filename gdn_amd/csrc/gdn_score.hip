@@ -1185,36 +1185,8 @@ __global__ __launch_bounds__(ONE_NT) void select_onewg_kernel(const KeyLayout kl
   }
 }
 
-// Normalise, smooth, reduce over sensors: the sweep of gdn_score_sweep.hpp (the one full description).  Here: where a
-// resident shard's rows come from, and the two reductions.
-
-// Rows before this shard's first tick come from the halo [3][n] when the series has them (first_tick > 0); otherwise
-// row 0 stands in (its values only feed ticks whose series index is < 3, which are forced to 0).  Rows past the shard
-// are clamped to its last.  The 3 predecessors of t0 are 0.0 where the series has no such tick.
-struct SeriesSource {
-  const float *pred, *gt, *halo_pred, *halo_gt;
-  const unsigned char *valid, *halo_valid;
-  int t, n, first_tick;
-  template <typename T>
-  __device__ __forceinline__ const T* row(const T* body, const T* halo, int tt) const {
-    const bool before = tt < 0;                  // halo row 3 + tt
-    const int r = before ? (first_tick > 0 ? 3 + tt : 0) : min(tt, t - 1);
-    return (before && first_tick > 0 ? halo : body) + (size_t)r * n;
-  }
-  __device__ __forceinline__ const float* pred_row(int tt) const { return row(pred, halo_pred, tt); }
-  __device__ __forceinline__ const float* gt_row(int tt) const { return row(gt, halo_gt, tt); }
-  __device__ __forceinline__ const unsigned char* valid_row(int tt) const { return row(valid, halo_valid, tt); }
-  template <typename FA, typename FB>
-  __device__ __forceinline__ void before(int t0, const Lanes&, double (&a)[3], double (&b)[3], FA&& na,
-                                         FB&& nb) const {
-    const int g0 = first_tick + t0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      a[k] = g0 >= 3 - k ? na(k) : 0.0;
-      b[k] = g0 >= 3 - k ? nb(k) : 0.0;
-    }
-  }
-};
+// Normalise, smooth, reduce over sensors: the sweep of gdn_score_sweep.hpp (the one full description).  Here: the two
+// reductions over a resident shard (its rows come from gdn_sweep::SeriesSource).
 
 // anomaly = max over sensors (the transposing butterfly); `scores` (optional) gets the [n, t] table.
 template <bool GAPS>

@@ -9,7 +9,7 @@
 // the value at the tick and its 3 predecessors (0 for the first 3 ticks of the SERIES).  What differs between the
 // kernels is handed in:
 //   the source   where pred / gt / valid of row t0 - 3 + u come from, and what the three predecessors of t0 are
-//                (SeriesSource in gdn_score.hip: halo rows, zeros before the series; StreamSource in gdn_stream.hip:
+//                (SeriesSource below: halo rows, zeros before the series; StreamSource in gdn_stream.hip:
 //                the float64 carry).  The two predecessor rules are different rules, not cases of one.
 //   the sink     what a tick does with the two smoothed scores of the lane (maximum, top-m merge, score table).
 // GAPS: `valid` (1 = a real reading) travels as one bit per loaded row and the normalised error of a missing reading is
@@ -113,6 +113,35 @@ __device__ __forceinline__ void score_sweep(const Source& src, const double* __r
     sink(u, tick, sma, smb);
   }
 }
+
+// The source of a resident series (gdn_score.hip; per unit with first_tick = 0 in gdn_fleet_series.hip).
+// Rows before this shard's first tick come from the halo [3][n] when the series has them (first_tick > 0); otherwise
+// row 0 stands in (its values only feed ticks whose series index is < 3, which are forced to 0).  Rows past the shard
+// are clamped to its last.  The 3 predecessors of t0 are 0.0 where the series has no such tick.
+struct SeriesSource {
+  const float *pred, *gt, *halo_pred, *halo_gt;
+  const unsigned char *valid, *halo_valid;
+  int t, n, first_tick;
+  template <typename T>
+  __device__ __forceinline__ const T* row(const T* body, const T* halo, int tt) const {
+    const bool before = tt < 0;                  // halo row 3 + tt
+    const int r = before ? (first_tick > 0 ? 3 + tt : 0) : min(tt, t - 1);
+    return (before && first_tick > 0 ? halo : body) + (size_t)r * n;
+  }
+  __device__ __forceinline__ const float* pred_row(int tt) const { return row(pred, halo_pred, tt); }
+  __device__ __forceinline__ const float* gt_row(int tt) const { return row(gt, halo_gt, tt); }
+  __device__ __forceinline__ const unsigned char* valid_row(int tt) const { return row(valid, halo_valid, tt); }
+  template <typename FA, typename FB>
+  __device__ __forceinline__ void before(int t0, const Lanes&, double (&a)[3], double (&b)[3], FA&& na,
+                                         FB&& nb) const {
+    const int g0 = first_tick + t0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      a[k] = g0 >= 3 - k ? na(k) : 0.0;
+      b[k] = g0 >= 3 - k ? nb(k) : 0.0;
+    }
+  }
+};
 
 // Top m: a tick keeps its m largest smoothed scores WITH their sensors.  The lane's two values of the sweep and the
 // list carried over from earlier sweeps (entry r in lane r: cs / ci) are the candidates; m rounds of "wave maximum of

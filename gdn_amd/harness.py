@@ -792,6 +792,240 @@ class SeriesEvaluator:
         return self.anomaly
 
 
+# --------------------------------------------------------------------------- fleet archive evaluator
+class UnitSeries(NamedTuple):
+    """One unit of a FleetEvaluator as `localise` and `episodes(evaluator, hi, ...)` read an evaluator: views of the
+    fleet's tensors, nothing copied."""
+    model: object
+    src: torch.Tensor            # [n, T_raw]: the unit's (filled) series
+    pred: torch.Tensor           # [t, n]
+    y: torch.Tensor              # [t, n]
+    t: int
+    top_m: int
+    top_scores: torch.Tensor | None      # [t, m] float64
+    top_sensors: torch.Tensor | None     # [t, m] int32
+
+
+class FleetEvaluator:
+    """The archive side of a fleet: eval forward + median / IQR table + smoothed anomaly scores of U
+    units of ONE model, every unit's series resident in HBM, in one captured step.
+
+    `series` [U, n, T_raw] fp32 on the device; unit u contributes t = T_raw - w scored ticks and is scored as
+    SeriesEvaluator(model, None, y, batch, series=series[u], ...) scores it, bit for bit: `pred`, `y` [U, t, n],
+    `med_iqr` [U, n, 2], `anomaly` [U, t], with `top_m` `top_scores` / `top_sensors` [U, t, m] (anomaly is their column
+    0), with `want_scores` `scores` [U, n, t].  A step is U * ceil(t / batch) forward_series launches round-robin over
+    the side streams, ONE keys launch for all units, the select over U * n rows in spans of at most 65535, ONE smooth
+    launch; with `use_graph` one replay.  The route (`wide`) is decided once for the whole block, as a fleet shares its
+    route.  A model whose shape forward_series refuses is refused here (no window-tensor fallback), so is bf16.
+
+    `gaps=True`: SeriesEvaluator's gaps=True per unit.  The constructor runs gdn_series_fill once per unit and holds
+    `raw_series`, `series` (filled), `valid` [U, t, n], `keep` [U, t], `kept` [U] (int64, host) and with
+    `calib="sensor"` `counts` [U, n] int32 (device) after ONE host read for all units; a unit whose first w ticks are
+    not finite or that has fewer than `min_kept` complete ticks (real readings of a sensor) is refused by number.
+
+    `unit(u)` is what `localise` / `episodes` take; `fleet(chunk, ...)` deploys the last step as a StreamFleet."""
+
+    def __init__(self, model, series: torch.Tensor, batch: int, use_graph: bool = True, want_scores: bool = False,
+                 top_m: int = 0, gaps: bool = False, min_kept: int = 64, calib: str = "tick", streams: int = 3):
+        _check_calib(calib)
+        if calib == "sensor" and not gaps:
+            raise ValueError("calib='sensor' calibrates around missing readings: it needs gaps=True")
+        w = model.gnn_layers[0].gnn.lin.weight.shape[1]
+        if not isinstance(series, torch.Tensor) or series.dim() != 3:
+            raise ValueError("FleetEvaluator needs a series [U, n, T_raw], got "
+                             f"{tuple(series.shape) if isinstance(series, torch.Tensor) else type(series)}")
+        units, n, t_raw = series.shape
+        if t_raw <= w:
+            raise ValueError(f"series [U, n, T_raw]: T_raw = {t_raw} leaves no tick to score behind a window of {w}")
+        if series.dtype == torch.bfloat16:
+            raise _lib.GdnHipError("series is bfloat16: FleetEvaluator runs on fp32 storage only (a bf16 series is not "
+                                   "supported by the fleet-series launches)")
+        if series.dtype != torch.float32:
+            raise TypeError(f"series: expected {torch.float32}, got {series.dtype}")
+        if top_m and want_scores:
+            raise ValueError("top_m replaces the [U, n, t] score table: ask for one of want_scores and top_m")
+        if top_m:
+            _check_top_m(top_m, n)
+        if int(batch) < 1 or int(min_kept) < 1:
+            raise ValueError(f"batch = {batch}, min_kept = {min_kept}: both at least 1")
+        t = t_raw - w
+        ops.fleet_series_check(units, t, n)          # (the 2 GiB cap of the key block among the limits)
+        if n != model.embedding.weight.shape[0]:
+            raise ValueError(f"series [U, n, T_raw]: n = {n}, the model has {model.embedding.weight.shape[0]} sensors")
+        series = ops._chk(series, name="series")     # on the device, contiguous
+        dev = series.device
+        self.model, self.batch, self.units, self.n, self.t, self.w = model.eval(), int(batch), units, n, t, w
+        self.with_gaps, self.calib, self.top_m, self.use_graph = bool(gaps), calib, int(top_m), use_graph
+        self.raw_series = self.valid = self.keep = self._gap_counters = self.counts = self.kept = None
+        if self.with_gaps:
+            self._fill(series, int(min_kept))
+        else:
+            self.series = series
+            self.y = series[:, :, w:].transpose(1, 2).contiguous()
+            self._sel_counts = torch.full((units, n), t, dtype=torch.int32, device=dev)
+        self.wide = model.wide_for(self.series)      # ONE route for the whole block
+        try:                                         # every refusal of the library precedes its launch; an accepted
+            model.forward_series(self.series[0], 0, 1, wide=self.wide)       # window is the warm-up that builds the plan
+        except _lib.GdnHipError as exc:
+            raise _lib.GdnHipError(f"FleetEvaluator: forward_series has no kernel for this model's shape ({exc}); the "
+                                   "window-tensor route is SeriesEvaluator's") from exc
+        self.pred = torch.empty((units, t, n), dtype=torch.float32, device=dev)
+        self.keys = torch.empty((units, n, t), dtype=torch.float64, device=dev)
+        self._ws = ops.fleet_select_workspace(units, n, t, dev)
+        self.med_iqr = torch.empty((units, n, 2), dtype=torch.float64, device=dev)
+        self.scores = torch.empty((units, n, t), dtype=torch.float64, device=dev) if want_scores else None
+        self.top_scores = self.top_sensors = None
+        if self.top_m:
+            self.top_scores = torch.empty((units, t, self.top_m), dtype=torch.float64, device=dev)
+            self.top_sensors = torch.empty((units, t, self.top_m), dtype=torch.int32, device=dev)
+            self.anomaly = self.top_scores[:, :, 0]
+        else:
+            self.anomaly = torch.empty((units, t), dtype=torch.float64, device=dev)
+        self.spans = [(u, s, min(t, s + self.batch)) for u in range(units) for s in range(0, t, self.batch)]
+        self.side = [torch.cuda.Stream(device=dev) for _ in range(min(streams, len(self.spans)))] if streams > 1 else []
+
+        def look_again():                   # a parameter changed under a captured graph: the x limit follows it
+            self.wide = model.wide_for(self.series)
+        self._step = _Replay(self._launch_all, use_graph, lambda: model._constants().key, look_again)
+
+    def _fill(self, raw, min_kept: int):
+        """gaps=True: gdn_series_fill per unit into the stacked planes, the counts on the device, ONE host read."""
+        units, n, t, w = self.units, self.n, self.t, self.w
+        dev = raw.device
+        self.raw_series = raw
+        self.series = torch.empty_like(raw)
+        self.y = torch.empty((units, t, n), dtype=torch.float32, device=dev)
+        self.valid = torch.empty((units, t, n), dtype=torch.uint8, device=dev)
+        self.keep = torch.empty((units, t), dtype=torch.uint8, device=dev)
+        self._gap_counters = torch.empty((units, 2, n), dtype=torch.int64, device=dev)
+        ws = torch.empty((_lib.load().gdn_series_fill_workspace_bytes(n, t + w) // 8,), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        for u in range(units):              # construction is not the step: the existing kernel, once per unit
+            _lib.call("gdn_series_fill", raw[u].data_ptr(), n, t + w, w, self.series[u].data_ptr(), self.y[u].data_ptr(),
+                      self.valid[u].data_ptr(), self.keep[u].data_ptr(), self._gap_counters[u].data_ptr(),
+                      ws.data_ptr(), st)
+        if self.calib == "sensor":          # every sensor's real readings among the scored ticks
+            self.counts = (t - self._gap_counters[:, 0]).to(torch.int32)
+            self._sel_counts, least = self.counts, self.counts.amin(dim=1).long()
+        else:                               # the complete ticks of unit u, for every sensor of unit u
+            least = self.keep.sum(dim=1)
+            self._sel_counts = least.to(torch.int32).view(units, 1).expand(units, n).contiguous()
+        head = torch.isfinite(raw[:, :, :w]).all(dim=2).all(dim=1).long()
+        both = torch.stack([head, least]).cpu()                              # ONE host read for all units
+        bad = torch.nonzero(both[0] == 0).flatten()[:8].tolist()
+        if bad:
+            raise ValueError(f"series: the first {w} ticks of units {bad} hold a value that is not finite; with gaps=True "
+                             "every missing reading is held at an earlier real one, so every unit's series must begin "
+                             "on real readings")
+        self.kept = both[1].clone()
+        short = torch.nonzero(self.kept < min_kept).flatten()[:8].tolist()
+        if short:
+            what = "real readings of their scarcest sensor" if self.calib == "sensor" else "complete ticks"
+            raise ValueError(f"min_kept = {min_kept}: units {short} have only {[int(self.kept[u]) for u in short]} {what} "
+                             f"among the {t} scored ticks; too few for their median / IQR tables")
+
+    def status_gaps(self):
+        """(missing_total [U, n] int64, missing_run [U, n] int64) on the host, gaps=True only: SeriesEvaluator.status_gaps
+        per unit.  ONE read (a synchronisation)."""
+        if not self.with_gaps:
+            raise ValueError("status_gaps(): the fleet evaluator was built with gaps=False and counts no missing readings")
+        both = self._gap_counters.cpu()
+        return both[:, 0], both[:, 1]
+
+    def _launch_forward(self):
+        m = self.model
+        # constants and the plan are built (when stale) HERE, on the caller's stream, before the fork: the side streams
+        # would read them unordered otherwise (SeriesEvaluator._launch_forward)
+        if m.out_layer_num == 1 and not self.wide:
+            m._plan(m._constants(), False)
+        elif m.out_layer_num > 1:
+            m._mlp_tail(m._constants())
+
+        def launch(u, s, e):
+            m.forward_series(self.series[u], s, e - s, out=self.pred[u, s:e], wide=self.wide)
+        if len(self.side) < 2:
+            for span in self.spans:
+                launch(*span)
+            return
+        main = torch.cuda.current_stream()
+        fork = torch.cuda.Event()
+        fork.record(main)
+        for st in self.side:
+            st.wait_event(fork)
+        for i, span in enumerate(self.spans):
+            with torch.cuda.stream(self.side[i % len(self.side)]):
+                launch(*span)
+        for st in self.side:
+            join = torch.cuda.Event()
+            join.record(st)
+            main.wait_event(join)
+
+    def _launch_all(self):
+        """forward -> ONE keys launch -> the select spans -> ONE smooth launch."""
+        self._launch_forward()
+        tick = self.with_gaps and self.counts is None
+        ops.fleet_series_keys(self.pred, self.y, self.t, out=self.keys, keep=self.keep if tick else None,
+                              valid=self.valid if self.counts is not None else None)
+        ops.fleet_select_counts(self.keys, self._sel_counts, 1, self._ws, self.med_iqr)
+        if self.top_m:
+            ops.fleet_series_smooth_topm(self.pred, self.y, self.med_iqr, self.top_m, self.top_scores, self.top_sensors,
+                                         valid=self.valid)
+        else:
+            ops.fleet_series_smooth_max(self.pred, self.y, self.med_iqr, want_scores=False, anomaly=self.anomaly,
+                                        scores=self.scores, valid=self.valid)
+
+    graph = property(lambda self: self._step.graph, doc="the captured step, None before its first graphed call")
+
+    def step(self):
+        self._step()
+        return self.anomaly
+
+    def thresholds(self) -> torch.Tensor:
+        """[U] float64 on the device: every unit's largest anomaly score of the last step."""
+        return self.anomaly.amax(dim=1)
+
+    def unit(self, u: int) -> UnitSeries:
+        """Unit u as `localise(evaluator, ticks)` and `episodes(evaluator, hi, ...)` read an evaluator (views)."""
+        if not 0 <= int(u) < self.units:
+            raise ValueError(f"unit {u} outside [0, {self.units})")
+        top = (None, None) if not self.top_m else (self.top_scores[u], self.top_sensors[u])
+        return UnitSeries(self.model, self.series[u], self.pred[u], self.y[u], self.t, self.top_m, *top)
+
+    def fleet(self, chunk: int, **kw):
+        """A StreamFleet from the last step (step() first), as StreamFleet.from_calibration(model, series, chunk,
+        calib_gaps=<gaps>, calib=<calib>, **kw) builds it, without its loop: the tables, `thresholds()`, every unit's
+        last w (filled) ticks as the history, `calib_kept` / `calib_counts`, and with `recal=R` every unit's ring seeded
+        by the rule of `_seed_ring` from ONE keys launch.  `gaps=` and `calib=` default to the evaluator's."""
+        units, n, t, w = self.units, self.n, self.t, self.w
+        kw.setdefault("gaps", self.with_gaps)
+        if kw.setdefault("calib", self.calib) != self.calib:
+            raise ValueError(f"calib = {kw['calib']!r}: the evaluator calibrated with calib = {self.calib!r}")
+        _check_calib_period(self.series, self.with_gaps, kw["gaps"], "fleet")
+        fleet_check_shape(units, chunk, n, w)
+        R = int(kw.get("recal", 0))
+        if self.calib == "sensor" and not R:
+            kw["calib"] = "tick"            # no ring: the fleet never calibrates anything itself
+        history = kw.pop("history", None)
+        fleet = StreamFleet(self.model, self.med_iqr, self.thresholds(),
+                            self.series[:, :, -w:].contiguous() if history is None else history, chunk, **kw)
+        if self.with_gaps:
+            fleet.calib_kept = self.kept.clone()
+        if self.calib == "sensor":
+            fleet.calib_counts = self.counts.clone()
+        if R:                               # _seed_ring per unit: the last s rows, oldest first, into slots R - s .. R - 1
+            s = min(R, t)
+            sensor = self.calib == "sensor"
+            keep = None if sensor or self.keep is None else self.keep[:, -s:].contiguous()
+            keys = ops.fleet_series_keys(self.pred[:, -s:].contiguous(), self.y[:, -s:].contiguous(), s, keep=keep,
+                                         valid=self.valid[:, -s:].contiguous() if sensor else None)
+            fleet.ring_keys[:, :, R - s:].copy_(keys)
+            if keep is None:
+                fleet.ring_keep[:, R - s:].fill_(1)
+            else:
+                fleet.ring_keep[:, R - s:].copy_(keep)
+        return fleet
+
+
 # --------------------------------------------------------------------------- localisation
 class Localisation(NamedTuple):
     """What `localise` returns, one row per tick: the m most deviating sensors, their smoothed scores, predicted
@@ -828,8 +1062,8 @@ def _localisation(model, src, ticks, rows, sensors, top_scores, pred, observed) 
 
 def localise(evaluator: SeriesEvaluator, ticks, m: int | None = None) -> Localisation:
     """Which sensors deviate at `ticks` (rows of the evaluator's prediction table) and which neighbours they were
-    reading: the top-m table of the evaluator's last step (SeriesEvaluator(top_m >= 1), step() first) plus one
-    gdn_attention_at launch on its resident data.  `m` defaults to the evaluator's top_m."""
+    reading: the top-m table of the evaluator's last step (SeriesEvaluator(top_m >= 1) or FleetEvaluator.unit(u),
+    step() first) plus one gdn_attention_at launch on its resident data.  `m` defaults to the evaluator's top_m."""
     ev = evaluator
     if not ev.top_m:
         raise ValueError("localise needs an evaluator built with top_m >= 1")
@@ -866,11 +1100,11 @@ def episodes(scores, top_sensors=None, hi=None, lo=None, on: int = 1, off: int =
              first_tick: int = 0) -> Episodes:
     """The alarm episodes of a scored series: `scores` [T] float64 and `top_sensors` [T, m] int32 on
     the device, raised after `on` ticks above `hi`, cleared after `off` ticks at or below `lo` (None: hi).  Or
-    `episodes(evaluator, hi, ...)` for a SeriesEvaluator built with top_m= whose step() has run: its top_scores[:, 0] and
-    top_sensors; the peak ticks go straight into `localise(evaluator, ticks)`.  One gdn_episodes_scan (five launches,
-    parallel over T), no synchronisation."""
-    if isinstance(scores, SeriesEvaluator):
-        ev = scores
+    `episodes(evaluator, hi, ...)` for a SeriesEvaluator (or a FleetEvaluator.unit(u)) built with top_m= whose step()
+    has run: its top_scores[:, 0] and top_sensors; the peak ticks go straight into `localise(evaluator, ticks)`.  One
+    gdn_episodes_scan (five launches, parallel over T), no synchronisation."""
+    if not isinstance(scores, torch.Tensor) and hasattr(scores, "top_m"):
+        ev = scores                                         # a SeriesEvaluator, or FleetEvaluator.unit(u)
         if isinstance(top_sensors, torch.Tensor) and top_sensors.dim() > 0:
             raise ValueError("episodes(evaluator, hi, ...): the evaluator brings its own top_sensors")
         if top_sensors is not None:                         # episodes(evaluator, hi[, lo]): the levels move up one place;

@@ -1529,6 +1529,105 @@ def fleet_select_counts(ring_keys, counts, min_count: int, ws, med_iqr):
     return med_iqr
 
 
+# --------------------------------------------------------------------------- fleet series
+FLEET_SERIES_LIMITS = "1 <= units <= 4096, 1 <= n <= 4096, t >= 1, 8 units n pitch <= 2 GiB"
+
+
+def fleet_series_check(units: int, t: int, n: int, pitch: int | None = None) -> None:
+    """The limits of the fleet-series launches (include/gdn_hip.h "Fleet series"), host arithmetic only."""
+    pitch = t if pitch is None else pitch
+    if not (1 <= units <= 4096 and 1 <= n <= 4096 and t >= 1 and pitch >= t and 8 * units * n * pitch <= 2 << 30):
+        raise _lib.GdnHipError(f"fleet series: no kernel for units = {units}, t = {t}, n = {n}, pitch = {pitch} "
+                               f"({FLEET_SERIES_LIMITS}, pitch >= t)")
+
+
+def _fleet_planes(pred, gt, valid):
+    """pred, gt [U, t, n] fp32 and the optional validity planes [U, t, n] uint8 of the fleet-series launches, checked."""
+    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    if pred.dim() != 3 or gt.shape != pred.shape:
+        raise ValueError(f"expected pred and gt of one shape [U, t, n], got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if valid is not None:
+        valid = _valid_plane(valid, pred.shape, "valid")
+    return pred, gt, valid
+
+
+def fleet_series_keys(pred, gt, pitch: int, out: torch.Tensor | None = None, keep=None, valid=None) -> torch.Tensor:
+    """keys [U, n, pitch] float64 of pred / gt [U, t, n] in ONE launch (gdn_fleet_series_keys): unit u's block is
+    score_keys(pred[u], gt[u], pitch, keep=keep[u] / valid=valid[u]) bit for bit.  `keep` [U, t] uint8 or `valid`
+    [U, t, n] uint8, one of the two at the most."""
+    pred, gt, valid = _fleet_planes(pred, gt, valid)
+    units, t, n = pred.shape
+    if keep is not None and valid is not None:
+        raise ValueError("fleet_series_keys: keep (whole ticks) and valid (single readings) exclude each other")
+    if keep is not None:
+        keep = _chk(keep, torch.uint8, "keep")
+        if tuple(keep.shape) != (units, t):
+            raise ValueError(f"keep: one flag per unit and tick is needed [{units}, {t}], got {tuple(keep.shape)}")
+    fleet_series_check(units, t, n, pitch)
+    keys = out if out is not None else torch.empty((units, n, pitch), dtype=torch.float64, device=pred.device)
+    if keys.shape != (units, n, pitch) or keys.dtype != torch.float64 or not keys.is_contiguous():
+        raise ValueError("keys buffer must be a contiguous float64 [U, n, pitch] tensor")
+    _lib.call("gdn_fleet_series_keys", _ptr(pred), _ptr(gt), _ptr(keep), _ptr(valid), units, t, n, pitch, _ptr(keys),
+              _stream())
+    return keys
+
+
+def _fleet_table(med_iqr, units: int, n: int):
+    med_iqr = _chk(med_iqr, torch.float64, "med_iqr")
+    if tuple(med_iqr.shape) != (units, n, 2):
+        raise ValueError(f"med_iqr: expected [{units}, {n}, 2], got {tuple(med_iqr.shape)}")
+    return med_iqr
+
+
+def fleet_series_smooth_max(pred, gt, med_iqr, want_scores: bool = True, anomaly: torch.Tensor | None = None,
+                            scores: torch.Tensor | None = None, valid=None):
+    """score_smooth_max per unit in ONE launch (gdn_fleet_series_smooth_max / _gaps): pred, gt [U, t, n], med_iqr
+    [U, n, 2]; every unit is a series of its own (first_tick = 0, nothing crosses a unit seam).  Returns (scores
+    [U, n, t] | None, anomaly [U, t]); both may be preallocated.  `valid` [U, t, n] uint8 as in score_smooth_max."""
+    pred, gt, valid = _fleet_planes(pred, gt, valid)
+    units, t, n = pred.shape
+    med_iqr = _fleet_table(med_iqr, units, n)
+    fleet_series_check(units, t, n)
+    if scores is None and want_scores:
+        scores = torch.empty((units, n, t), dtype=torch.float64, device=pred.device)
+    if anomaly is None:
+        anomaly = torch.empty((units, t), dtype=torch.float64, device=pred.device)
+    if scores is not None:
+        _stream_buf(scores, torch.float64, units * n * t, "scores")
+    _stream_buf(anomaly, torch.float64, units * t, "anomaly")
+    head = (_ptr(pred), _ptr(gt), _ptr(med_iqr), units, t, n, _ptr(scores), _ptr(anomaly))
+    if valid is None:
+        _lib.call("gdn_fleet_series_smooth_max", *head, _stream())
+    else:
+        _lib.call("gdn_fleet_series_smooth_max_gaps", *head, _ptr(valid), _stream())
+    return scores, anomaly
+
+
+def fleet_series_smooth_topm(pred, gt, med_iqr, m: int, top_scores: torch.Tensor | None = None,
+                             top_sensors: torch.Tensor | None = None, valid=None):
+    """score_smooth_topm per unit in ONE launch (gdn_fleet_series_smooth_topm / _gaps): returns (top_scores [U, t, m]
+    float64 descending, top_sensors [U, t, m] int32); both may be preallocated."""
+    pred, gt, valid = _fleet_planes(pred, gt, valid)
+    units, t, n = pred.shape
+    med_iqr = _fleet_table(med_iqr, units, n)
+    fleet_series_check(units, t, n)
+    m = int(m)
+    if top_scores is None:
+        top_scores = torch.empty((units, t, m), dtype=torch.float64, device=pred.device)
+    if top_sensors is None:
+        top_sensors = torch.empty((units, t, m), dtype=torch.int32, device=pred.device)
+    if (top_scores.shape != (units, t, m) or top_scores.dtype != torch.float64 or not top_scores.is_contiguous()
+            or top_sensors.shape != (units, t, m) or top_sensors.dtype != torch.int32
+            or not top_sensors.is_contiguous()):
+        raise ValueError("top_scores / top_sensors must be contiguous [U, t, m] float64 / int32 tensors")
+    head = (_ptr(pred), _ptr(gt), _ptr(med_iqr), units, t, n, m, _ptr(top_scores), _ptr(top_sensors))
+    if valid is None:
+        _lib.call("gdn_fleet_series_smooth_topm", *head, _stream())
+    else:
+        _lib.call("gdn_fleet_series_smooth_topm_gaps", *head, _ptr(valid), _stream())
+    return top_scores, top_sensors
+
+
 # --------------------------------------------------------------------------- raw readings
 _PREP_MAX_DOWN = 64
 

@@ -1251,6 +1251,35 @@ int gdn_fleet_prep_ticks(const void* raw, int rows, int raw_f64, const int32_t* 
                          int c, int n, int down, const double* table, float* out, int32_t* counts, void* stream);
 int gdn_fleet_prep_ticks_units(const void* raw, int rows, int raw_f64, const int32_t* raw_counts, void* pend, int units,
                                int c, int n, int down, const double* tables, float* out, int32_t* counts, void* stream);
+/* Fleet series (opt-in; additive entry points, the ABI version does not move): the archive side of a
+ * fleet — U units of one model, each with a resident series of its own, scored in launches that cover all units.  All
+ * tensors are stacks of contiguous per-unit planes:
+ *   pred, gt [U, t, n] fp32    valid [U, t, n] uint8    keep [U, t] uint8    med_iqr [U, n, 2] float64
+ *   gdn_fleet_series_keys         ONE launch: keys [U, n, pitch] float64, unit u's block what gdn_score_keys (keep ==
+ *                                 valid == NULL), gdn_score_keys_keep (keep) or gdn_score_keys_valid (valid) writes for
+ *                                 that unit's planes, bit for bit, the filler in slots t .. pitch-1 included.  Both keep
+ *                                 and valid: GDN_ERR_ARG.  The block is what gdn_score_select_counts takes as blocks = 1,
+ *                                 U n sensors (in spans of at most 65535 rows), with counts [U n].
+ *   gdn_fleet_series_smooth_max   ONE launch over all units: unit u reads med_iqr[u] and is scored as a series of its own
+ *   gdn_fleet_series_smooth_topm  with first_tick = 0 — its ticks 0 - 2 are exactly 0.0, no run of ticks and no
+ *                                 predecessor row crosses a unit seam, row clamping stays inside the unit.  anomaly
+ *                                 [U, t], scores [U, n, t] (may be NULL), top_scores / top_sensors [U, t, m]: per unit
+ *                                 the bits of gdn_score_smooth_max / gdn_score_smooth_topm on that unit's planes.
+ *   ..._gaps                      the same with the validity planes: per unit gdn_score_smooth_max_gaps / _topm_gaps.
+ * Limits, decided before any launch: 1 <= U <= 4096, 1 <= n <= 4096, 1 <= m <= min(8, n), 8 U n pitch <= 2 GiB (the
+ * smooth launches: pitch = t): GDN_ERR_UNSUPPORTED; a null required pointer, t < 1, pitch < t: GDN_ERR_ARG.
+ * No floating-point atomics; no workgroup waits on another.                                                          */
+int gdn_fleet_series_keys(const float* pred, const float* gt, const uint8_t* keep, const uint8_t* valid, int units,
+                          int t, int n, int pitch, double* keys, void* stream);
+int gdn_fleet_series_smooth_max(const float* pred, const float* gt, const double* med_iqr, int units, int t, int n,
+                                double* scores, double* anomaly, void* stream);
+int gdn_fleet_series_smooth_topm(const float* pred, const float* gt, const double* med_iqr, int units, int t, int n,
+                                 int m, double* top_scores, int32_t* top_sensors, void* stream);
+int gdn_fleet_series_smooth_max_gaps(const float* pred, const float* gt, const double* med_iqr, int units, int t, int n,
+                                     double* scores, double* anomaly, const uint8_t* valid, void* stream);
+int gdn_fleet_series_smooth_topm_gaps(const float* pred, const float* gt, const double* med_iqr, int units, int t,
+                                      int n, int m, double* top_scores, int32_t* top_sensors, const uint8_t* valid,
+                                      void* stream);
 
 #ifdef __cplusplus
 }
