@@ -50,16 +50,21 @@ def neighbours(graph):
     nb = -np.ones((n, k + 1), dtype=np.int64)
     deg = np.zeros(n, dtype=np.int64)
     for i in range(n):
-        srcs = [int(j) for j in g[i] if int(j) != i] + [i]
+        row = g[i].astype(np.int64)
+        srcs = row[row != i]                                  # (numpy, not a Python loop: 4096 x 1023 tables)
         nb[i, :len(srcs)] = srcs
-        deg[i] = len(srcs)
+        nb[i, len(srcs)] = i
+        deg[i] = len(srcs) + 1
     return nb, deg
 
 
-def attention_rows(params, x, graph):
+def attention_rows(params, x, graph, nb=None, targets=None):
     """Attention of every (window, target) from raw windows x[B, n, w], in float64: alpha[B, n, k+1] in the slot order
     of `neighbours` (padding 0).  s = x . (lin^T att) + emb . att_em (the separable form of models/graph_layer.py:
-    91-104), LeakyReLU(0.2), max-subtract, exp, / (sum + 1e-16)."""
+    91-104), LeakyReLU(0.2), max-subtract, exp, / (sum + 1e-16).
+    `nb`: the lists themselves ([n, slots], -1 padding) where they do not come from `neighbours(graph)` (injected
+    tables with repeats: tests/_graph_build_ref.py).  `targets` [B]: one target per window instead of all n: alpha
+    [B, slots] (the rows gdn_attention_at returns)."""
     pre = "gnn_layers.0.gnn."
     lin = params[pre + "lin.weight"].double()
     emb = params["embedding.weight"].double()
@@ -67,12 +72,20 @@ def attention_rows(params, x, graph):
     x = torch.as_tensor(x).double()
     s_i = x @ (lin.T @ params[pre + "att_i"].double().view(d)) + emb @ params[pre + "att_em_i"].double().view(d)
     s_j = x @ (lin.T @ params[pre + "att_j"].double().view(d)) + emb @ params[pre + "att_em_j"].double().view(d)
-    nb, _ = neighbours(graph)
-    nbt = torch.from_numpy(nb)
+    if nb is None:
+        nb, _ = neighbours(graph)
+    nbt = torch.from_numpy(np.asarray(nb, dtype=np.int64))
     pad = nbt < 0
-    logit = s_i.unsqueeze(-1) + s_j[:, nbt.clamp(min=0)]                                       # [B, n, k+1]
+    if targets is None:
+        logit = s_i.unsqueeze(-1) + s_j[:, nbt.clamp(min=0)]                                   # [B, n, k+1]
+        pad = pad.unsqueeze(0)
+    else:
+        tg = torch.as_tensor(targets, dtype=torch.long)
+        rows = torch.arange(x.shape[0])
+        logit = s_i[rows, tg].unsqueeze(-1) + torch.gather(s_j, 1, nbt[tg].clamp(min=0))       # [B, k+1]
+        pad = pad[tg]
     logit = torch.where(logit > 0, logit, logit * NEG_SLOPE)
-    logit = logit.masked_fill(pad.unsqueeze(0), float("-inf"))
+    logit = logit.masked_fill(pad, float("-inf"))
     e = (logit - logit.max(dim=-1, keepdim=True).values).exp()
     return (e / (e.sum(dim=-1, keepdim=True) + SOFTMAX_EPS)).numpy(), nb
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _graph_build_ref import clear_rows
 from oracle import gdn_oracle
 from test_gpu_forward_parity import random_params
 from test_gpu_train_parity import FixedMaskDropout
@@ -33,11 +34,7 @@ def _p64(p):
     return {key: (v.to(F64) if v.is_floating_point() else v) for key, v in p.items()}
 
 
-def _clear_rows(emb, k, gap=1e-5):
-    """float64 cosine ranking: (rows whose k-th / (k+1)-th gap exceeds `gap`, the top-k sets)."""
-    cos = gdn_oracle.cosine_matrix(emb.to(F64))
-    srt = torch.sort(cos, dim=1, descending=True)
-    return (srt.values[:, k - 1] - srt.values[:, k]) > gap, srt.indices[:, :k]
+_clear_rows = clear_rows      # float64 cosine ranking: rows with a clear k-th / (k+1)-th gap, the top-k sets
 
 
 def test_predicate_and_native_step_stay_on_the_tile(gpu_device):

@@ -537,28 +537,33 @@ def test_matrix_core_backward_of_the_aggregate_over_random_shapes(gpu_device):
                                    atol=2e-6 * float(mags.max()) * (b * n) ** 0.5)
 
 
+def check_graph_and_terms_single_launch(n, k, d, w, device):
+    """One shape of the test below (tests/test_gpu_graph_stages.py runs it at the borders of the rank count)."""
+    from gdn_amd import _lib, ops
+    g = torch.Generator().manual_seed(n)
+    emb = torch.randn((n, d), generator=g).to(device)
+    lin_w = torch.randn((d, w), generator=g).to(device)
+    att = [torch.randn((d,), generator=g).to(device) for _ in range(4)]
+    graph = ops.topk_graph(emb, k)
+    terms = ops.node_terms(lin_w, *[t.view(1, 1, d) for t in att], emb)
+    pitch = ops.nbr_pitch(k)
+    topk = torch.empty((n, k), dtype=torch.int64, device=device)
+    nbr = torch.empty((n, pitch), dtype=torch.uint16, device=device)
+    deg = torch.empty((n,), dtype=torch.int32, device=device)
+    terms2 = torch.empty_like(terms)
+    _lib.call("gdn_topk_graph_terms", emb.data_ptr(), n, d, k, topk.data_ptr(), nbr.data_ptr(), deg.data_ptr(),
+              lin_w.data_ptr(), *[t.data_ptr() for t in att], w, terms2.data_ptr(),
+              torch.cuda.current_stream().cuda_stream)
+    assert torch.equal(topk, graph.topk) and torch.equal(deg, graph.deg)
+    assert torch.equal(nbr.view(torch.int16), graph.nbr.view(torch.int16))
+    assert torch.equal(terms2, terms)
+
+
 def test_graph_and_terms_single_launch_equals_the_two_entry_points(gpu_device):
     """gdn_topk_graph_terms (one launch, used by the native training step) against gdn_topk_graph + gdn_node_terms:
     identical graph tables and folded attention terms, bit for bit."""
-    from gdn_amd import _lib, ops
     for n, k, d, w in ((127, 30, 64, 15), (27, 5, 64, 5), (512, 64, 128, 30), (40, 16, 128, 30)):
-        g = torch.Generator().manual_seed(n)
-        emb = torch.randn((n, d), generator=g).to(gpu_device)
-        lin_w = torch.randn((d, w), generator=g).to(gpu_device)
-        att = [torch.randn((d,), generator=g).to(gpu_device) for _ in range(4)]
-        graph = ops.topk_graph(emb, k)
-        terms = ops.node_terms(lin_w, *[t.view(1, 1, d) for t in att], emb)
-        pitch = ops.nbr_pitch(k)
-        topk = torch.empty((n, k), dtype=torch.int64, device=gpu_device)
-        nbr = torch.empty((n, pitch), dtype=torch.uint16, device=gpu_device)
-        deg = torch.empty((n,), dtype=torch.int32, device=gpu_device)
-        terms2 = torch.empty_like(terms)
-        _lib.call("gdn_topk_graph_terms", emb.data_ptr(), n, d, k, topk.data_ptr(), nbr.data_ptr(), deg.data_ptr(),
-                  lin_w.data_ptr(), *[t.data_ptr() for t in att], w, terms2.data_ptr(),
-                  torch.cuda.current_stream().cuda_stream)
-        assert torch.equal(topk, graph.topk) and torch.equal(deg, graph.deg)
-        assert torch.equal(nbr.view(torch.int16), graph.nbr.view(torch.int16))
-        assert torch.equal(terms2, terms)
+        check_graph_and_terms_single_launch(n, k, d, w, gpu_device)
 
 
 def test_training_statistics_accumulator_is_exact(gpu_device):
