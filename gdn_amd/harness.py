@@ -17,7 +17,6 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import gc
-import hashlib
 import os
 import warnings
 from typing import NamedTuple
@@ -29,6 +28,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
+# the checkpoint layer of StreamDetector and StreamFleet, under the names it always had here
+from .checkpoint import (FLEET_CHECKPOINT_FORMAT, STREAM_CHECKPOINT_FORMAT,  # noqa: F401
+                         _CKPT_CONFIG, _CKPT_INTS, _CKPT_STRS, _EVENTS_FIELDS, _FLEET_CKPT, _FLEET_CKPT_CONFIG,
+                         _FLEET_CKPT_INTS, _FLEET_CKPT_STRS, _UNIT_CONFIG, _check_recal_threshold, _checkpoint_expect,
+                         _ckpt_format, _ckpt_int, _ckpt_str, _fingerprint, _fleet_ckpt_format, _host_copies,
+                         checkpoint_recal_threshold, events_bytes, fleet_checkpoint_check, fleet_checkpoint_config,
+                         fleet_checkpoint_events, fleet_unit_to_stream, model_fingerprint, prep_units,
+                         read_stream_checkpoint, stream_calib_bytes, stream_checkpoint_check,
+                         stream_checkpoint_config, stream_checkpoint_events, stream_to_fleet_unit,
+                         write_stream_checkpoint)
 
 
 # --------------------------------------------------------------------------- eval loop
@@ -2175,202 +2184,6 @@ def raw_push_plan(pending: int, r: int, down: int, chunk: int) -> list:
     return plan
 
 
-# the checkpoint of a running detector: a flat dict of numpy arrays, one .npz, no Python objects
-STREAM_CHECKPOINT_FORMAT = 1
-# 0-d int64: identity, the configuration, the host counters (calib_kept: -1 for None; prep_down: 0 without a prep)
-_CKPT_INTS = ("format", "abi", "state_bytes", "calib_bytes", "n", "w", "chunk", "top_m", "log", "with_gaps", "recal",
-              "exclude_alarms", "recal_every", "recal_min", "wide", "prep", "prep_down", "handed", "recals",
-              "recal_kept", "calib_kept", "raw_pending")
-_CKPT_STRS = ("calib", "model_sha256")
-_CKPT_CONFIG = ("n", "w", "chunk", "top_m", "log", "with_gaps", "recal", "exclude_alarms", "recal_every", "recal_min",
-                "calib", "wide", "prep", "prep_down")
-
-
-def _host_copies(tensors) -> list:
-    """Host copies of `tensors`, issued and not waited for: a device tensor goes into pinned memory with a
-    non-blocking copy on the current stream (the caller synchronises ONCE before reading any), a host tensor is
-    taken as it is."""
-    out = []
-    for t in tensors:
-        t = t.detach()
-        if t.is_cuda:
-            out.append(torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True))
-        else:
-            out.append(t)
-    return out
-
-
-def _fingerprint(names, host) -> str:
-    h = hashlib.sha256()
-    for name, t in zip(names, host):
-        h.update(f"{name}|{t.dtype}|{tuple(t.shape)}|".encode())
-        h.update(t.contiguous().reshape(-1).view(torch.uint8).numpy().tobytes())
-    return h.hexdigest()
-
-
-def model_fingerprint(model) -> str:
-    """SHA-256 (hex) over the model's state_dict: every tensor in key order as its name, dtype, shape and bytes.  Equal
-    for equal weights on any device; one changed bit of a parameter or of a BatchNorm running statistic changes it.
-    Device tensors are read in one batch of copies and ONE synchronisation."""
-    sd = model.state_dict()
-    names = sorted(sd)
-    host = _host_copies([sd[k] for k in names])
-    if any(sd[k].is_cuda for k in names):
-        torch.cuda.current_stream().synchronize()
-    return _fingerprint(names, host)
-
-
-def _ckpt_int(sd, key: str, who: str = "stream checkpoint") -> int:
-    if key not in sd:
-        raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
-    a = np.asarray(sd[key])
-    if a.dtype != np.int64 or a.shape != ():
-        raise ValueError(f"{who}: {key!r} must be one int64, got {a.dtype} {a.shape}")
-    return int(a)
-
-
-def _ckpt_str(sd, key: str, who: str = "stream checkpoint") -> str:
-    if key not in sd:
-        raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
-    a = np.asarray(sd[key])
-    if a.dtype.kind != "U" or a.shape != ():
-        raise ValueError(f"{who}: {key!r} must be one string, got {a.dtype} {a.shape}")
-    return str(a)
-
-
-def checkpoint_recal_threshold(sd, who: str = "stream checkpoint"):
-    """The margin a checkpoint (a detector's or a fleet's) was saved with under recal_threshold=, None
-    for a file saved without it — every file written before the option existed.  Host data only."""
-    if "recal_threshold" not in sd:
-        return None
-    a = np.asarray(sd["recal_threshold"])
-    if a.dtype != np.float64 or a.shape != () or not (np.isfinite(a) and a > 0):
-        raise ValueError(f"{who}: 'recal_threshold' must be one finite float64 > 0, got {a.dtype} {a.shape} {a!r}")
-    return float(a)
-
-
-def _check_recal_threshold(sd, expect, recal: int, events, who: str):
-    """What the two checkpoint checkers refuse about the optional keys of recal_threshold=: `recal_threshold` without a
-    ring, `clear_frac` without it or without episode tables, and — against a detector or fleet that exists already — a
-    margin on one side only, or another one.  The shapes are checked with the other optional keys."""
-    margin = checkpoint_recal_threshold(sd, who)
-    if margin is not None and not recal:
-        raise ValueError(f"{who}: recal_threshold = {margin} without a calibration ring (recal = 0)")
-    if "clear_frac" in sd and (margin is None or events is None):
-        raise ValueError(f"{who}: key 'clear_frac' without recal_threshold and events (a truncated or foreign file)")
-    if "recal_threshold" in expect:                         # (load() builds from the file: nothing to compare)
-        mine = expect["recal_threshold"]
-        if margin != mine:
-            raise ValueError(f"{who}: recal_threshold = {margin}, this one was built with recal_threshold = {mine} "
-                             "(the threshold in the file was, or was not, re-derived from the ring)")
-
-
-def _ckpt_format(sd) -> None:
-    fmt = _ckpt_int(sd, "format")
-    if fmt != STREAM_CHECKPOINT_FORMAT:
-        raise ValueError(f"stream checkpoint: format = {fmt} is not known to this version (it reads format "
-                         f"{STREAM_CHECKPOINT_FORMAT})")
-
-
-def stream_checkpoint_config(sd) -> dict:
-    """The configuration a checkpoint was saved under (`_CKPT_CONFIG`) as Python values; a missing or mistyped field
-    is refused by name.  Host data only."""
-    cfg = {k: _ckpt_str(sd, k) if k in _CKPT_STRS else _ckpt_int(sd, k) for k in _CKPT_CONFIG}
-    if cfg["calib"] not in ("tick", "sensor"):
-        raise ValueError(f"stream checkpoint: calib = {cfg['calib']!r}: 'tick' or 'sensor'")
-    return cfg
-
-
-def stream_checkpoint_check(sd, expect) -> None:
-    """Refuse a checkpoint dict `sd` (StreamDetector.state_dict() or a loaded file) that the loader cannot continue,
-    with a ValueError that names the field.  `expect` holds the loader's own facts: "n", "w" (the model's), "abi"
-    (the loaded library's ABI version), "state_bytes" = gdn_stream_state_bytes(n, w) and "calib_bytes" =
-    gdn_stream_calib_bytes(n, R) for the file's R (0 without a ring) as the loaded library reports them, "model" (its
-    model_fingerprint, or None: do not compare), "prep_down" (the caller's Prep.down, or None: no prep) and "prep_n".
-    Host data only: no device work, no library call."""
-    _ckpt_format(sd)
-    ints = {k: _ckpt_int(sd, k) for k in _CKPT_INTS}
-    strs = {k: _ckpt_str(sd, k) for k in _CKPT_STRS}
-    cfg = stream_checkpoint_config(sd)
-    for k in ("n", "w"):                                    # (first: the byte sizes below are those of the model's n, w)
-        if ints[k] != int(expect[k]):
-            raise ValueError(f"stream checkpoint: {k} = {ints[k]}, the model has {k} = {int(expect[k])}")
-    for k in ("abi", "state_bytes", "calib_bytes"):
-        if ints[k] != int(expect[k]):
-            raise ValueError(f"stream checkpoint: {k} = {ints[k]} was saved by another build of the library (this one "
-                             f"has {k} = {int(expect[k])}); the state's layout is not known to agree")
-    down = expect.get("prep_down")
-    if bool(ints["prep"]) != (down is not None):
-        raise ValueError("stream checkpoint: prep: the detector was saved " + ("with" if ints["prep"] else "without")
-                         + " a raw-readings front end and is resumed " + ("without one (pass prep=)" if ints["prep"]
-                                                                          else "with one (pass prep=None)"))
-    if down is not None:
-        if ints["prep_down"] != int(down):
-            raise ValueError(f"stream checkpoint: prep_down = {ints['prep_down']}, the prep given has down = {int(down)}")
-        if int(expect.get("prep_n", ints["n"])) != ints["n"]:
-            raise ValueError(f"stream checkpoint: prep: fitted on {int(expect['prep_n'])} sensors, n = {ints['n']}")
-    elif ints["prep_down"] != 0:
-        raise ValueError(f"stream checkpoint: prep_down = {ints['prep_down']} without a prep")
-    if expect.get("model") is not None and strs["model_sha256"] != expect["model"]:
-        raise ValueError("stream checkpoint: model_sha256 differs from the model given: the scores are the model's, so "
-                         "resuming under other weights changes the alarm rate (check_model=False resumes all the same)")
-    n, R, m, log = ints["n"], ints["recal"], ints["top_m"], ints["log"]
-    pend_rows = ints["raw_pending"]
-    if not 0 <= pend_rows < max(1, ints["prep_down"]):
-        raise ValueError(f"stream checkpoint: raw_pending = {pend_rows} outside an open group of prep_down = "
-                         f"{ints['prep_down']} raw ticks")
-    for k in ("handed", "recals", "recal_kept", "log", "recal", "recal_every", "recal_min"):
-        if ints[k] < 0:
-            raise ValueError(f"stream checkpoint: {k} = {ints[k]} is negative")
-    if ints["calib_kept"] < -1:
-        raise ValueError(f"stream checkpoint: calib_kept = {ints['calib_kept']} (-1: none)")
-    want = {"state": (np.uint8, (ints["state_bytes"],)), "med_iqr": (np.float64, (n, 2)),
-            "threshold": (np.float64, (1,)), "log_ticks": (np.int64, (log,)), "log_sensors": (np.int32, (log, m))}
-    if cfg["with_gaps"]:
-        want["gaps"] = (np.int64, (2, n))
-    if R:
-        want["ring_keys"], want["ring_keep"] = (np.float64, (n, R)), (np.uint8, (R,))
-    if cfg["prep"]:
-        want["pending"] = (np.float64, (pend_rows, n))
-    events = stream_checkpoint_events(sd)
-    if "events" in expect:                                  # (load() builds the detector from the file: nothing to compare)
-        mine = expect["events"]
-        if (events is None) != (mine is None):
-            raise ValueError("stream checkpoint: events: the detector was saved " + ("without" if events is None else "with")
-                             + " an episode table and is resumed " + ("with one (pass events=None)" if events is None
-                                                                      else "without one (pass events=)"))
-        for k in _EVENTS_FIELDS if events is not None else ():
-            if events[k] != int(mine[k]):
-                raise ValueError(f"stream checkpoint: events.{k} = {events[k]}, this detector was built with "
-                                 f"events.{k} = {int(mine[k])}")
-    if events is not None:
-        if events["m"] != m:
-            raise ValueError(f"stream checkpoint: events.m = {events['m']}, top_m = {m}")
-        want["events"] = (np.uint8, (events_bytes(m, events["cap"]),))
-        want["events_lo"], want["events_cfg"] = (np.float64, (1,)), (np.int64, (len(_EVENTS_FIELDS),))
-    _check_recal_threshold(sd, expect, R, events, "stream checkpoint")
-    optional = {"calib_counts": (np.int32, (n,)), "recal_counts": (np.int64, (n,)),
-                "recal_threshold": (np.float64, ()), "clear_frac": (np.float64, (1,))}
-    for k in sd:
-        if k not in want and k not in optional and k not in _CKPT_INTS and k not in _CKPT_STRS:
-            raise ValueError(f"stream checkpoint: key {k!r} does not belong to this configuration (a foreign file)")
-    for k, (dtype, shape) in list(want.items()) + [(k, v) for k, v in optional.items() if k in sd]:
-        if k not in sd:
-            raise ValueError(f"stream checkpoint: key {k!r} is missing (a truncated or foreign file)")
-        a = np.asarray(sd[k])
-        if a.dtype != dtype or a.shape != shape:
-            raise ValueError(f"stream checkpoint: {k!r} must be {np.dtype(dtype)} {shape} under this configuration, got "
-                             f"{a.dtype} {a.shape}")
-
-
-_EVENTS_FIELDS = ("on", "off", "cap", "m")
-
-
-def events_bytes(m: int, cap: int) -> int:
-    """gdn_stream_events_bytes(m, cap) by host arithmetic: the carry, four 8-byte columns and the sensors."""
-    return (160 + 32 * cap + 4 * cap * m + 7) & ~7
-
-
 def events_config(events, m: int) -> dict:
     """StreamDetector's events=dict(on=, off=, lo=, cap=) checked on the host and completed: {"on", "off", "cap", "m",
     "lo"} with on = off = 1, cap = 4096 and lo = None (the raise level) by default; an unknown key is refused by name."""
@@ -2380,52 +2193,6 @@ def events_config(events, m: int) -> dict:
     _, lo, on, off, cap = ops.episodes_check(None, events.get("lo"), events.get("on", 1), events.get("off", 1),
                                              events.get("cap", 4096))
     return {"on": on, "off": off, "cap": cap, "m": int(m), "lo": lo}
-
-
-def stream_checkpoint_events(sd):
-    """The events configuration of a checkpoint ({"on", "off", "cap", "m", "lo"}), None for a file saved without an
-    episode table; the three optional keys come together or not at all.  Host data only."""
-    keys = [k for k in ("events", "events_cfg", "events_lo") if k in sd]
-    if not keys:
-        return None
-    if len(keys) != 3:
-        raise ValueError(f"stream checkpoint: key {keys[0]!r} without the rest of events, events_cfg, events_lo (a "
-                         "truncated or foreign file)")
-    cfg, lo = np.asarray(sd["events_cfg"]), np.asarray(sd["events_lo"])
-    if cfg.dtype != np.int64 or cfg.shape != (len(_EVENTS_FIELDS),):
-        raise ValueError(f"stream checkpoint: 'events_cfg' must be int64 ({len(_EVENTS_FIELDS)},), got {cfg.dtype} "
-                         f"{cfg.shape}")
-    if lo.dtype != np.float64 or lo.shape != (1,):
-        raise ValueError(f"stream checkpoint: 'events_lo' must be float64 (1,), got {lo.dtype} {lo.shape}")
-    out = {k: int(v) for k, v in zip(_EVENTS_FIELDS, cfg)}
-    if not (1 <= out["on"] <= 4096 and 1 <= out["off"] <= 4096 and 0 <= out["cap"] <= 1 << 20 and 1 <= out["m"] <= 8):
-        raise ValueError(f"stream checkpoint: events_cfg = {out} outside 1 <= on, off <= 4096, 0 <= cap <= 2^20, "
-                         "1 <= m <= 8")
-    out["lo"] = float(lo[0])
-    return out
-
-
-def write_stream_checkpoint(path: str, sd) -> None:
-    """`sd` as ONE .npz at exactly `path` (numpy.savez; no suffix is appended): written to path + ".tmp" beside it, made
-    durable, then moved over `path` with os.replace, so a process that dies in the middle of a save leaves the
-    previous checkpoint as it was."""
-    tmp = path + ".tmp"
-    try:
-        with open(tmp, "wb") as f:
-            np.savez(f, **sd)
-            f.flush()
-            os.fsync(f.fileno())
-        os.replace(tmp, path)
-    except BaseException:
-        with contextlib.suppress(OSError):
-            os.unlink(tmp)
-        raise
-
-
-def read_stream_checkpoint(path: str) -> dict:
-    """The arrays of a checkpoint file (allow_pickle=False: it holds no Python objects)."""
-    with np.load(path, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
 
 
 def _check_stream_head(model):
@@ -2611,6 +2378,66 @@ class _StreamCore:
         before, self._handed = self._handed, self._handed + ticks
         if self.recal_every and self._handed // self.recal_every > before // self.recal_every:
             self.recalibrate()
+
+    # save and resume: what the two classes share around their `_ckpt_tensors()` — checkpoint key -> the
+    # device tensor (a view) that holds it, for the options the object was built with
+    def _config(self) -> dict:
+        cfg = {"units": self.units} if hasattr(self, "units") else {}
+        cfg.update({"n": self.n, "w": self.w, "chunk": self.chunk, "top_m": self.top_m,
+                    "log": 0 if self.log_ticks is None else self.log_ticks.shape[-1], "with_gaps": int(self.with_gaps),
+                    "recal": self.recal, "exclude_alarms": int(self.exclude_alarms), "recal_every": self.recal_every,
+                    "recal_min": self.recal_min, "calib": self.calib, "wide": int(self.wide),
+                    "prep": int(self.prep is not None), "prep_down": 0 if self.prep is None else self.prep.down})
+        return cfg
+
+    def _ckpt_read(self, dev: dict) -> tuple:
+        """({key: numpy array} of the device tensors `dev`, the model's fingerprint): ONE batch of non-blocking copies on
+        the current stream, the model's tensors included, and ONE synchronisation."""
+        weights = self.model.state_dict()
+        names = sorted(weights)
+        host = _host_copies(list(dev.values()) + [weights[k] for k in names])
+        torch.cuda.current_stream().synchronize()
+        return {k: t.numpy() for k, t in zip(dev, host)}, _fingerprint(names, host[len(dev):])
+
+    def _ckpt_finish(self, sd: dict, ints: dict, keys: tuple, cfg: dict, fingerprint: str) -> dict:
+        """`sd` completed by what lives on the host: the empty log of log=0, the shared optional keys, the 0-d ints
+        `keys` (from `ints` and the configuration `cfg`) and the two strings."""
+        if self.log_ticks is None:
+            lead = (cfg["units"],) if "units" in cfg else ()
+            sd["log_ticks"] = np.zeros(lead + (0,), np.int64)
+            sd["log_sensors"] = np.zeros(lead + (0, self.top_m), np.int32)
+        if self.recal_threshold is not None:
+            sd["recal_threshold"] = np.array(self.recal_threshold, dtype=np.float64)
+        if self.events is not None:
+            sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
+        ints = dict(ints, **{k: v for k, v in cfg.items() if k != "calib"})
+        sd.update({k: np.array(int(ints[k]), dtype=np.int64) for k in keys})
+        sd["calib"], sd["model_sha256"] = np.array(self.calib), np.array(fingerprint)
+        return sd
+
+    def _ckpt_same_config(self, cfg: dict, who: str, noun: str) -> None:
+        """The file's configuration `cfg` against this object's own, field by field: refused before any device work."""
+        for k, mine in self._config().items():
+            if cfg[k] != mine:
+                raise ValueError(f"{who}: {k} = {cfg[k]!r}, this {noun} was built with {k} = {mine!r}")
+
+    def _ckpt_fill(self, sd):
+        """The body of load_state_dict after the checks: the captured graphs dropped, every array of `_ckpt_tensors()`
+        copied INTO the allocation that holds it.  `clear_frac` and `calib_counts` come into being from the file: the
+        fractions behind the clear levels are the file's, else (at their next use) those of the levels just loaded.
+        Returns the reader of `sd`'s arrays."""
+        for full in (self._full, *self._prep_full.values()):
+            full.drop()
+
+        def host(key):
+            return torch.from_numpy(np.array(sd[key]))      # (a copy: numpy.load may hand out read-only arrays)
+        self.clear_frac = self.calib_counts = None
+        for k, t in self._ckpt_tensors().items():
+            t.copy_(host(k))
+        self.clear_frac = host("clear_frac").to(self.state.device) if "clear_frac" in sd else None
+        self.calib_counts = host("calib_counts").to(self.state.device) if "calib_counts" in sd else None
+        self._last = 0
+        return host
 
 
 class StreamDetector(_StreamCore):
@@ -3003,19 +2830,23 @@ class StreamDetector(_StreamCore):
                              self.pred, self.chunk_buf)
 
     # save and resume: a stream cut by a save and a load writes the bits of the uninterrupted stream
-    def _config(self) -> dict:
-        return {"n": self.n, "w": self.w, "chunk": self.chunk, "top_m": self.top_m,
-                "log": 0 if self.log_ticks is None else self.log_ticks.numel(), "with_gaps": int(self.with_gaps),
-                "recal": self.recal, "exclude_alarms": int(self.exclude_alarms), "recal_every": self.recal_every,
-                "recal_min": self.recal_min, "calib": self.calib, "wide": int(self.wide),
-                "prep": int(self.prep is not None), "prep_down": 0 if self.prep is None else self.prep.down}
-
     def _expect(self, check_model: bool = True) -> dict:
         """stream_checkpoint_check's `expect` for this detector: its model's shape and fingerprint, its prep, and the
         loaded library's ABI version and byte sizes."""
         expect = _checkpoint_expect(self.model, self.prep, self.recal, check_model)
         expect["events"], expect["recal_threshold"] = self.events_cfg, self.recal_threshold
         return expect
+
+    def _ckpt_tensors(self) -> dict:
+        """Checkpoint key -> the device tensor (a view) that holds it; an option that is off has no tensor and no key.
+        The raw ticks of the open group are not in it: they alternate between two planes (state_dict, load_state_dict)."""
+        held = {"state": self.state.view(torch.uint8), "med_iqr": self.med_iqr,
+                "threshold": torch.as_tensor(self.threshold, dtype=torch.float64).reshape(1),
+                "log_ticks": self.log_ticks, "log_sensors": self.log_sensors, "gaps": self.gaps,
+                "ring_keys": self.ring_keys, "ring_keep": self.ring_keep, "calib_counts": self.calib_counts,
+                "events": None if self.events is None else self.events.view(torch.uint8), "events_lo": self.clear,
+                "clear_frac": None if self.recal_threshold is None else self.clear_frac}
+        return {k: t for k, t in held.items() if t is not None}
 
     def state_dict(self) -> dict:
         """Everything a continuation of this stream depends on, as a flat dict of numpy arrays (no Python objects:
@@ -3026,47 +2857,18 @@ class StreamDetector(_StreamCore):
         outputs or scratch and stay behind.  Read-only: ONE batch of device-to-host copies on the current stream and
         ONE synchronisation; the pushes after it write the bits they would have written."""
         lib = _lib.load()
-        n, m = self.n, self.top_m
-        cfg = self._config()
-        dev = {"state": self.state.view(torch.uint8), "med_iqr": self.med_iqr,
-               "threshold": torch.as_tensor(self.threshold, dtype=torch.float64).reshape(1)}
-        if self.log_ticks is not None:
-            dev["log_ticks"], dev["log_sensors"] = self.log_ticks, self.log_sensors
-        if self.with_gaps:
-            dev["gaps"] = self.gaps
-        if self.recal:
-            dev["ring_keys"], dev["ring_keep"] = self.ring_keys, self.ring_keep
+        dev = self._ckpt_tensors()
         if self.prep is not None:
             dev["pending"] = self._pend[self._pend_at][:self.raw_pending]
-        if self.calib_counts is not None:
-            dev["calib_counts"] = self.calib_counts
-        if self.events is not None:
-            dev["events"], dev["events_lo"] = self.events.view(torch.uint8), self.clear
-        if self.recal_threshold is not None and self.clear_frac is not None:
-            dev["clear_frac"] = self.clear_frac
-        weights = self.model.state_dict()
-        names = sorted(weights)
-        host = _host_copies(list(dev.values()) + [weights[k] for k in names])
-        torch.cuda.current_stream().synchronize()
-        sd = {k: t.numpy() for k, t in zip(dev, host)}
-        if self.recal_threshold is not None:
-            sd["recal_threshold"] = np.array(self.recal_threshold, dtype=np.float64)
-        if self.log_ticks is None:
-            sd["log_ticks"], sd["log_sensors"] = np.zeros((0,), np.int64), np.zeros((0, m), np.int32)
+        sd, fingerprint = self._ckpt_read(dev)
         if self.recal_counts is not None:
             sd["recal_counts"] = self.recal_counts.to(torch.int64).numpy().copy()
-        if self.events is not None:
-            sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
         ints = {"format": STREAM_CHECKPOINT_FORMAT, "abi": lib.gdn_abi_version(),
-                "state_bytes": lib.gdn_stream_state_bytes(n, self.w),
-                "calib_bytes": lib.gdn_stream_calib_bytes(n, self.recal) if self.recal else 0,
+                "state_bytes": lib.gdn_stream_state_bytes(self.n, self.w),
+                "calib_bytes": lib.gdn_stream_calib_bytes(self.n, self.recal) if self.recal else 0,
                 "handed": self._handed, "recals": self.recals, "recal_kept": self.recal_kept,
                 "calib_kept": -1 if self.calib_kept is None else int(self.calib_kept), "raw_pending": self.raw_pending}
-        ints.update({k: v for k, v in cfg.items() if k != "calib"})
-        sd.update({k: np.array(int(ints[k]), dtype=np.int64) for k in _CKPT_INTS})
-        sd["calib"] = np.array(self.calib)
-        sd["model_sha256"] = np.array(_fingerprint(names, host[len(dev):]))
-        return sd
+        return self._ckpt_finish(sd, ints, _CKPT_INTS, self._config(), fingerprint)
 
     def load_state_dict(self, sd, check_model: bool = True) -> None:
         """Take the stream of `sd` (state_dict()'s dict, or a file's) up where it was saved.  `sd` is checked first
@@ -3076,44 +2878,19 @@ class StreamDetector(_StreamCore):
         Afterwards the last push is empty (`valid[:0]`, `localise()` with no rows) and the first full push captures
         the graph again."""
         stream_checkpoint_check(sd, self._expect(check_model))
-        cfg = stream_checkpoint_config(sd)
-        for k, mine in self._config().items():
-            if cfg[k] != mine:
-                raise ValueError(f"stream checkpoint: {k} = {cfg[k]!r}, this detector was built with {k} = {mine!r}")
-        for full in (self._full, *self._prep_full.values()):
-            full.drop()
-
-        def host(key):
-            return torch.from_numpy(np.array(sd[key]))      # (a copy: numpy.load may hand out read-only arrays)
-        self.state.view(torch.uint8).copy_(host("state"))
-        self.med_iqr.copy_(host("med_iqr"))
+        self._ckpt_same_config(stream_checkpoint_config(sd), "stream checkpoint", "detector")
         if not isinstance(self.threshold, torch.Tensor):    # (a caller's plain number: back to the device scalar)
             self.threshold = torch.zeros((1,), dtype=torch.float64, device=self.state.device)
-        self.threshold.view(-1).copy_(host("threshold"))
-        if self.log_ticks is not None:
-            self.log_ticks.copy_(host("log_ticks"))
-            self.log_sensors.copy_(host("log_sensors"))
-        if self.with_gaps:
-            self.gaps.copy_(host("gaps"))
-        if self.recal:
-            self.ring_keys.copy_(host("ring_keys"))
-            self.ring_keep.copy_(host("ring_keep"))
-        if self.events is not None:
-            self.events.view(torch.uint8).copy_(host("events"))
-            self.clear.copy_(host("events_lo"))
-        # the fraction behind the clear level: the file's, else (at its next use) that of the levels just loaded
-        self.clear_frac = host("clear_frac").to(self.state.device) if "clear_frac" in sd else None
+        host = self._ckpt_fill(sd)
         self.raw_pending = _ckpt_int(sd, "raw_pending")
         if self.prep is not None:
             self._pend_at = 0
             self._pend[0][:self.raw_pending].copy_(host("pending"))
-        self.calib_counts = host("calib_counts").to(self.state.device) if "calib_counts" in sd else None
         self.recal_counts = host("recal_counts") if "recal_counts" in sd else None
         kept = _ckpt_int(sd, "calib_kept")
         self.calib_kept = None if kept < 0 else kept
         self._handed, self.recals = _ckpt_int(sd, "handed"), _ckpt_int(sd, "recals")
         self.recal_kept = _ckpt_int(sd, "recal_kept")
-        self._last = 0
 
     def save(self, path: str) -> None:
         """state_dict() as one .npz at exactly `path` (write_stream_checkpoint: a temporary file beside it, then
@@ -3144,18 +2921,6 @@ class StreamDetector(_StreamCore):
                    events=events, recal_threshold=checkpoint_recal_threshold(sd))
         det.load_state_dict(sd, check_model=False)          # (the weights were compared above, once)
         return det
-
-
-def _checkpoint_expect(model, prep, recal: int, check_model: bool = True) -> dict:
-    """The loader's own facts for stream_checkpoint_check: host arithmetic and host library calls, plus ONE batch read
-    of the model's tensors for its fingerprint when `check_model`."""
-    lib = _lib.load()
-    w = model.gnn_layers[0].gnn.lin.weight.shape[1]
-    n = model.embedding.weight.shape[0]
-    return {"n": n, "w": w, "abi": lib.gdn_abi_version(), "state_bytes": lib.gdn_stream_state_bytes(n, w),
-            "calib_bytes": lib.gdn_stream_calib_bytes(n, recal) if recal else 0,
-            "model": model_fingerprint(model) if check_model else None,
-            "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n}
 
 
 # --------------------------------------------------------------------------- streaming fleet
@@ -3235,12 +3000,6 @@ def fleet_check_prep(prep, units: int, chunk: int, n: int, itemsize: int = 4) ->
                          f"exceeds {_VALIDATE_CHUNK_BYTES >> 20} MB; use a smaller chunk")
 
 
-def prep_units(prep):
-    """The fingerprint of a per-unit prep's tables (PrepUnits.fingerprint), None for a shared Prep or no prep at all:
-    what tells the two forms apart on the host."""
-    return prep.fingerprint() if getattr(prep, "tables", None) is not None else None
-
-
 def fleet_raw_cuts(r: int, down: int, chunk: int) -> list:
     """The sub-pushes of `r` raw ticks of the time axis handed to a prep= fleet: a list of (first raw row, raw rows,
     rows of the returned views).  A sub-push carries at most chunk * down raw rows, whatever any unit holds: with
@@ -3257,313 +3016,6 @@ def fleet_raw_hand(raw_handed: int, rows: int, down: int) -> int:
     """recal_every's clock of a prep= fleet: the model ticks that `rows` more raw rows of the time axis hand over when
     `raw_handed` were handed before — model ticks handed = raw rows handed // down.  Pure host arithmetic."""
     return (raw_handed + rows) // down - raw_handed // down
-
-
-# the checkpoint of a running fleet (DESIGN §3.8k): the detector's rules (§3.8e) with a leading unit axis and a format
-# number of its own; a detector's file has no "units", a fleet's file holds keys a detector's checker calls foreign
-FLEET_CHECKPOINT_FORMAT = 1
-_FLEET_CKPT = "fleet checkpoint"
-_FLEET_CKPT_INTS = ("format", "units", "abi", "state_bytes", "calib_bytes", "n", "w", "chunk", "top_m", "log",
-                    "with_gaps", "recal", "exclude_alarms", "recal_every", "recal_min", "wide", "prep", "prep_down",
-                    "handed", "raw_handed", "recals")
-_FLEET_CKPT_STRS = ("calib", "model_sha256")
-_FLEET_CKPT_CONFIG = ("units", "n", "w", "chunk", "top_m", "log", "with_gaps", "recal", "exclude_alarms", "recal_every",
-                      "recal_min", "calib", "wide", "prep", "prep_down")
-
-
-def _fleet_ckpt_format(sd) -> None:
-    fmt = _ckpt_int(sd, "format", _FLEET_CKPT)
-    if fmt != FLEET_CHECKPOINT_FORMAT:
-        raise ValueError(f"{_FLEET_CKPT}: format = {fmt} is not known to this version (it reads format "
-                         f"{FLEET_CHECKPOINT_FORMAT})")
-    if "units" not in sd:
-        raise ValueError(f"{_FLEET_CKPT}: key 'units' is missing: this is a single detector's checkpoint "
-                         "(StreamDetector.load reads it)")
-
-
-def fleet_checkpoint_config(sd) -> dict:
-    """The configuration a fleet checkpoint was saved under (`_FLEET_CKPT_CONFIG`) as Python values; a missing or
-    mistyped field is refused by name.  Host data only."""
-    cfg = {k: _ckpt_str(sd, k, _FLEET_CKPT) if k in _FLEET_CKPT_STRS else _ckpt_int(sd, k, _FLEET_CKPT)
-           for k in _FLEET_CKPT_CONFIG}
-    if cfg["calib"] not in ("tick", "sensor"):
-        raise ValueError(f"{_FLEET_CKPT}: calib = {cfg['calib']!r}: 'tick' or 'sensor'")
-    return cfg
-
-
-def fleet_checkpoint_events(sd):
-    """The events configuration of a fleet checkpoint ({"on", "off", "cap", "m"}), None for a file saved without episode
-    tables; `events`, `events_cfg` and `clear` come together or not at all.  Host data only."""
-    keys = [k for k in ("events", "events_cfg", "clear") if k in sd]
-    if not keys:
-        return None
-    if len(keys) != 3:
-        raise ValueError(f"{_FLEET_CKPT}: key {keys[0]!r} without the rest of events, events_cfg, clear (a truncated or "
-                         "foreign file)")
-    cfg = np.asarray(sd["events_cfg"])
-    if cfg.dtype != np.int64 or cfg.shape != (len(_EVENTS_FIELDS),):
-        raise ValueError(f"{_FLEET_CKPT}: 'events_cfg' must be int64 ({len(_EVENTS_FIELDS)},), got {cfg.dtype} {cfg.shape}")
-    out = {k: int(v) for k, v in zip(_EVENTS_FIELDS, cfg)}
-    if not (1 <= out["on"] <= 4096 and 1 <= out["off"] <= 4096 and 0 <= out["cap"] <= 1 << 20 and 1 <= out["m"] <= 8):
-        raise ValueError(f"{_FLEET_CKPT}: events_cfg = {out} outside 1 <= on, off <= 4096, 0 <= cap <= 2^20, 1 <= m <= 8")
-    return out
-
-
-def fleet_checkpoint_check(sd, expect) -> None:
-    """Refuse a fleet checkpoint dict `sd` (StreamFleet.state_dict() or a loaded file) that the loader cannot continue,
-    with a ValueError that names the field.  `expect` holds the loader's own facts: "n", "w" (the model's), "abi",
-    "state_bytes" = gdn_stream_state_bytes(n, w) PER UNIT and "calib_bytes" = gdn_fleet_calib_bytes(units, n, R) for the
-    file's units and R (0 without rings) as the loaded library reports them, "model" (its model_fingerprint, or None: do
-    not compare), "prep_down" (the caller's Prep.down, or None: no prep), "prep_n", and — a fleet that exists already —
-    "units" and "events" (its events configuration or None).  "prep_units": PrepUnits.fingerprint() of the caller's
-    per-unit tables, None (or absent) for a shared Prep; the file's optional `prep_units_sha256` must say the same.
-    Host data only: no device work, no library call."""
-    who = _FLEET_CKPT
-    _fleet_ckpt_format(sd)
-    ints = {k: _ckpt_int(sd, k, who) for k in _FLEET_CKPT_INTS}
-    strs = {k: _ckpt_str(sd, k, who) for k in _FLEET_CKPT_STRS}
-    cfg = fleet_checkpoint_config(sd)
-    U = ints["units"]
-    if U < 1:
-        raise ValueError(f"{who}: units = {U}: a fleet has at least one unit")
-    if expect.get("units") is not None and U != int(expect["units"]):
-        raise ValueError(f"{who}: units = {U}, this fleet has units = {int(expect['units'])}")
-    for k in ("n", "w"):
-        if ints[k] != int(expect[k]):
-            raise ValueError(f"{who}: {k} = {ints[k]}, the model has {k} = {int(expect[k])}")
-    for k in ("abi", "state_bytes", "calib_bytes"):
-        if ints[k] != int(expect[k]):
-            raise ValueError(f"{who}: {k} = {ints[k]} was saved by another build of the library (this one has {k} = "
-                             f"{int(expect[k])}); the state's layout is not known to agree")
-    down = expect.get("prep_down")
-    if bool(ints["prep"]) != (down is not None):
-        raise ValueError(f"{who}: prep: the fleet was saved " + ("with" if ints["prep"] else "without")
-                         + " a raw-readings front end and is resumed " + ("without one (pass prep=)" if ints["prep"]
-                                                                          else "with one (pass prep=None)"))
-    if down is not None:
-        if ints["prep_down"] != int(down):
-            raise ValueError(f"{who}: prep_down = {ints['prep_down']}, the prep given has down = {int(down)}")
-        if int(expect.get("prep_n", ints["n"])) != ints["n"]:
-            raise ValueError(f"{who}: prep: fitted on {int(expect['prep_n'])} sensors, n = {ints['n']}")
-    elif ints["prep_down"] != 0:
-        raise ValueError(f"{who}: prep_down = {ints['prep_down']} without a prep")
-    tables = _ckpt_str(sd, "prep_units_sha256", who) if "prep_units_sha256" in sd else None
-    if tables is not None and not ints["prep"]:
-        raise ValueError(f"{who}: key 'prep_units_sha256' without a prep (a truncated or foreign file)")
-    if down is not None and tables != expect.get("prep_units"):
-        if tables is None or expect.get("prep_units") is None:
-            raise ValueError(f"{who}: prep_units_sha256: the fleet was saved with " + (
-                "one shared prep table and is resumed with per-unit tables (pass the Prep)" if tables is None else
-                "per-unit prep tables and is resumed with one shared Prep (pass the PrepUnits)"))
-        raise ValueError(f"{who}: prep_units_sha256 differs from the per-unit tables given: the open groups and the "
-                         "scores behind the state were normalised with other tables")
-    if expect.get("model") is not None and strs["model_sha256"] != expect["model"]:
-        raise ValueError(f"{who}: model_sha256 differs from the model given: the scores are the model's, so resuming "
-                         "under other weights changes the alarm rate (check_model=False resumes all the same)")
-    for k in ("handed", "raw_handed", "recals", "log", "recal", "recal_every", "recal_min", "chunk", "top_m"):
-        if ints[k] < 0:
-            raise ValueError(f"{who}: {k} = {ints[k]} is negative")
-    n, R, m, log = ints["n"], ints["recal"], ints["top_m"], ints["log"]
-    want = {"state": (np.uint8, (U, ints["state_bytes"])), "med_iqr": (np.float64, (U, n, 2)),
-            "threshold": (np.float64, (U,)), "log_ticks": (np.int64, (U, log)), "log_sensors": (np.int32, (U, log, m))}
-    optional = {"calib_kept": (np.int64, (U,)), "calib_counts": (np.int32, (U, n))}
-    if cfg["with_gaps"]:
-        want["gaps"] = (np.int64, (U, 2, n))
-    if R:
-        want["ring_keys"], want["ring_keep"] = (np.float64, (U, n, R)), (np.uint8, (U, R))
-        want["recal_counts"] = (np.int32, (U, n))
-        if cfg["calib"] == "tick":
-            want["recal_kept"] = (np.int32, (U,))
-    if cfg["prep"]:
-        want["pending_ticks"] = (np.float64, (U, ints["prep_down"], n))
-        want["pending"] = (np.int32, (U,))
-    elif ints["raw_handed"] != 0:
-        raise ValueError(f"{who}: raw_handed = {ints['raw_handed']} without a prep")
-    events = fleet_checkpoint_events(sd)
-    if "events" in expect:                                  # (load() builds the fleet from the file: nothing to compare)
-        mine = expect["events"]
-        if (events is None) != (mine is None):
-            raise ValueError(f"{who}: events: the fleet was saved " + ("without" if events is None else "with")
-                             + " episode tables and is resumed " + ("with them (pass events=None)" if events is None
-                                                                    else "without them (pass events=)"))
-        for k in _EVENTS_FIELDS if events is not None else ():
-            if events[k] != int(mine[k]):
-                raise ValueError(f"{who}: events.{k} = {events[k]}, this fleet was built with events.{k} = {int(mine[k])}")
-    if events is not None:
-        if events["m"] != m:
-            raise ValueError(f"{who}: events.m = {events['m']}, top_m = {m}")
-        want["events"] = (np.int64, (U, events_bytes(m, events["cap"]) // 8))
-        want["clear"], want["events_cfg"] = (np.float64, (U,)), (np.int64, (len(_EVENTS_FIELDS),))
-    _check_recal_threshold(sd, expect, R, events, who)
-    optional["recal_threshold"], optional["clear_frac"] = (np.float64, ()), (np.float64, (U,))
-    for k in sd:
-        if k == "prep_units_sha256":                        # (an optional string, checked with the prep above)
-            continue
-        if k not in want and k not in optional and k not in _FLEET_CKPT_INTS and k not in _FLEET_CKPT_STRS:
-            raise ValueError(f"{who}: key {k!r} does not belong to this configuration (a foreign file)")
-    for k, (dtype, shape) in list(want.items()) + [(k, v) for k, v in optional.items() if k in sd]:
-        if k not in sd:
-            raise ValueError(f"{who}: key {k!r} is missing (a truncated or foreign file)")
-        a = np.asarray(sd[k])
-        if a.dtype != dtype or a.shape != shape:
-            raise ValueError(f"{who}: {k!r} must be {np.dtype(dtype)} {shape} under this configuration, got {a.dtype} "
-                             f"{a.shape}")
-    if cfg["prep"]:
-        pending = np.asarray(sd["pending"])
-        if ((pending < 0) | (pending >= ints["prep_down"])).any():
-            raise ValueError(f"{who}: pending = {pending.tolist()} outside an open group of prep_down = "
-                             f"{ints['prep_down']} raw ticks (0 .. {ints['prep_down'] - 1})")
-    for k in ("recal_kept", "recal_counts", "calib_counts"):
-        if k in sd and (np.asarray(sd[k]) < 0).any():
-            raise ValueError(f"{who}: {k} holds a negative count")
-    if "calib_kept" in sd and (np.asarray(sd["calib_kept"]) < 0).any():
-        raise ValueError(f"{who}: calib_kept holds a negative count")
-
-
-def _fleet_checkpoint_expect(model, prep, units: int, recal: int, check_model: bool = True) -> dict:
-    """The loader's own facts for fleet_checkpoint_check: host arithmetic and host library calls, plus ONE batch read of
-    the model's tensors for its fingerprint when `check_model`."""
-    lib = _lib.load()
-    w = model.gnn_layers[0].gnn.lin.weight.shape[1]
-    n = model.embedding.weight.shape[0]
-    if prep is not None and getattr(prep, "tables", None) is not None and prep.units != int(units):
-        raise ValueError(f"{_FLEET_CKPT}: prep: per-unit tables of {prep.units} units, units = {int(units)}")
-    return {"n": n, "w": w, "abi": lib.gdn_abi_version(), "state_bytes": lib.gdn_stream_state_bytes(n, w),
-            "calib_bytes": lib.gdn_fleet_calib_bytes(units, n, recal) if recal else 0,
-            "model": model_fingerprint(model) if check_model else None,
-            "prep_down": None if prep is None else prep.down, "prep_n": None if prep is None else prep.n,
-            "prep_units": prep_units(prep)}
-
-
-# unit hand-over (DESIGN §3.8m): unit u's block of every fleet array is a single stream's byte for byte, so a unit moves
-# between a fleet's dict and a detector's by slicing and renaming; what is left is the configuration, checked by name
-_UNIT_CONFIG = ("n", "w", "top_m", "log", "with_gaps", "recal", "exclude_alarms", "recal_min", "calib", "wide", "prep",
-                "prep_down")
-
-
-def stream_calib_bytes(n: int, R: int) -> int:
-    """gdn_stream_calib_bytes(n, R) by host arithmetic (0 without a ring): the keys, the keep flags, 8-byte padding."""
-    return (8 * n * R + R + 7) & ~7 if R else 0
-
-
-def fleet_unit_to_stream(sd_fleet, u: int) -> dict:
-    """Unit `u` of a fleet's state dict as the state dict of a single detector (StreamDetector.load_state_dict's input):
-    the unit's slice of every per-unit array under the detector's key, the open group cut to its length, the fleet's
-    configuration, chunk and clocks (`handed`: recal_every goes on from the fleet's clock; `recals`: the fleet's calls).
-    `recal_counts` travels under every calibration (the fleet keeps it under both); under calib="sensor" `recal_kept` is
-    the smallest count that reached recal_min, as a detector states it.  The fingerprint of per-unit prep tables stays
-    behind: the detector takes prep.unit(u).  Host data only."""
-    who = _FLEET_CKPT
-    _fleet_ckpt_format(sd_fleet)
-    cfg = fleet_checkpoint_config(sd_fleet)
-    ints = {k: _ckpt_int(sd_fleet, k, who) for k in _FLEET_CKPT_INTS}
-    U, n, R = cfg["units"], cfg["n"], cfg["recal"]
-    u = int(u)
-    if not 0 <= u < U:
-        raise ValueError(f"{who}: unit {u}: the file holds units 0 .. {U - 1}")
-
-    def unit(key):
-        if key not in sd_fleet:
-            raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
-        return np.array(np.asarray(sd_fleet[key])[u])       # (a contiguous copy; one number stays 0-d)
-    sd = {"state": unit("state"), "med_iqr": unit("med_iqr"), "threshold": unit("threshold").reshape(1),
-          "log_ticks": unit("log_ticks"), "log_sensors": unit("log_sensors")}
-    if cfg["with_gaps"]:
-        sd["gaps"] = unit("gaps")
-    recal_kept = 0
-    if R:
-        sd["ring_keys"], sd["ring_keep"] = unit("ring_keys"), unit("ring_keep")
-        counts = unit("recal_counts").astype(np.int64)
-        sd["recal_counts"] = counts
-        if cfg["calib"] == "tick":
-            recal_kept = int(unit("recal_kept"))
-        else:
-            done = counts[counts >= cfg["recal_min"]]
-            recal_kept = int(done.min()) if done.size else 0
-    pending = 0
-    if cfg["prep"]:
-        pending = int(unit("pending"))
-        if not 0 <= pending < cfg["prep_down"]:
-            raise ValueError(f"{who}: pending[{u}] = {pending} outside an open group of prep_down = {cfg['prep_down']}")
-        sd["pending"] = np.ascontiguousarray(unit("pending_ticks")[:pending])
-    if fleet_checkpoint_events(sd_fleet) is not None:
-        sd["events"] = unit("events").view(np.uint8)
-        sd["events_lo"], sd["events_cfg"] = unit("clear").reshape(1), np.array(sd_fleet["events_cfg"])
-    if "recal_threshold" in sd_fleet:
-        sd["recal_threshold"] = np.array(sd_fleet["recal_threshold"])
-    if "clear_frac" in sd_fleet:
-        sd["clear_frac"] = unit("clear_frac").reshape(1)
-    if "calib_counts" in sd_fleet:
-        sd["calib_counts"] = unit("calib_counts")
-    out = dict(ints, format=STREAM_CHECKPOINT_FORMAT, calib_bytes=stream_calib_bytes(n, R), recal_kept=recal_kept,
-               calib_kept=int(unit("calib_kept")) if "calib_kept" in sd_fleet else -1, raw_pending=pending)
-    sd.update({k: np.array(int(out[k]), dtype=np.int64) for k in _CKPT_INTS})
-    sd["calib"], sd["model_sha256"] = np.array(cfg["calib"]), np.array(_ckpt_str(sd_fleet, "model_sha256", who))
-    return sd
-
-
-def stream_to_fleet_unit(sd_stream, sd_fleet_config) -> dict:
-    """A detector's state dict as ONE unit of the fleet whose state dict (or any dict that holds its configuration keys,
-    `abi`, `state_bytes`, `model_sha256` and the optional events_cfg / recal_threshold) is `sd_fleet_config`: the unit's
-    block of every per-unit array under the fleet's key, without the unit axis (`pending_ticks`: the rows of the open
-    group only, `pending` their number; `recal_counts` int32, from the detector's or — tick calibration — its
-    `recal_kept` for every sensor).  Refused with a ValueError that names the field: any of n, w, top_m, log, with_gaps,
-    recal, exclude_alarms, recal_min, calib, wide, prep, prep_down, events (and on, off, cap, m), recal_threshold,
-    model_sha256, abi or state_bytes that differs.  chunk, recal_every and the clocks are the fleet's.  Host data only."""
-    who = "unit hand-over"
-    _ckpt_format(sd_stream)
-    mine, theirs = stream_checkpoint_config(sd_stream), fleet_checkpoint_config(sd_fleet_config)
-    for k in _UNIT_CONFIG:
-        if mine[k] != theirs[k]:
-            raise ValueError(f"{who}: {k} = {mine[k]!r}, the fleet was built with {k} = {theirs[k]!r}"
-                             + (" (the route is per launch: all units of a push share it)" if k == "wide" else ""))
-    for k in ("abi", "state_bytes"):
-        a, b = _ckpt_int(sd_stream, k), _ckpt_int(sd_fleet_config, k, _FLEET_CKPT)
-        if a != b:
-            raise ValueError(f"{who}: {k} = {a}, the fleet has {k} = {b} (another build of the library)")
-    if _ckpt_str(sd_stream, "model_sha256") != _ckpt_str(sd_fleet_config, "model_sha256", _FLEET_CKPT):
-        raise ValueError(f"{who}: model_sha256 differs from the fleet's model: a fleet scores all units with one model")
-    ev, fev = stream_checkpoint_events(sd_stream), None
-    if "events_cfg" in sd_fleet_config:                     # (the configuration alone: the tables need not be there)
-        fev = fleet_checkpoint_events({"events": None, "clear": None, "events_cfg": sd_fleet_config["events_cfg"]})
-    if (ev is None) != (fev is None):
-        raise ValueError(f"{who}: events: the detector keeps " + ("no" if ev is None else "an") + " episode table, the "
-                         "fleet " + ("does" if ev is None else "does not"))
-    for k in _EVENTS_FIELDS if ev is not None else ():
-        if ev[k] != fev[k]:
-            raise ValueError(f"{who}: events.{k} = {ev[k]}, the fleet was built with events.{k} = {fev[k]}")
-    margin, theirs_margin = checkpoint_recal_threshold(sd_stream), checkpoint_recal_threshold(sd_fleet_config, _FLEET_CKPT)
-    if margin != theirs_margin:
-        raise ValueError(f"{who}: recal_threshold = {margin}, the fleet was built with recal_threshold = {theirs_margin}")
-    n, R = mine["n"], mine["recal"]
-
-    def arr(key):
-        if key not in sd_stream:
-            raise ValueError(f"{who}: key {key!r} is missing (a truncated or foreign file)")
-        return np.ascontiguousarray(np.asarray(sd_stream[key]))
-    out = {"state": arr("state"), "med_iqr": arr("med_iqr"), "threshold": arr("threshold").reshape(()),
-           "log_ticks": arr("log_ticks"), "log_sensors": arr("log_sensors")}
-    if mine["with_gaps"]:
-        out["gaps"] = arr("gaps")
-    if R:
-        out["ring_keys"], out["ring_keep"] = arr("ring_keys"), arr("ring_keep")
-        kept = _ckpt_int(sd_stream, "recal_kept")
-        if mine["calib"] == "tick":
-            out["recal_kept"] = np.array(kept, dtype=np.int32)
-        out["recal_counts"] = (arr("recal_counts") if "recal_counts" in sd_stream else
-                               np.full((n,), kept if mine["calib"] == "tick" else 0)).astype(np.int32)
-    if mine["prep"]:
-        out["pending_ticks"] = arr("pending")
-        out["pending"] = np.array(_ckpt_int(sd_stream, "raw_pending"), dtype=np.int32)
-    if ev is not None:
-        out["events"], out["clear"] = arr("events").view(np.int64), arr("events_lo").reshape(())
-    if "clear_frac" in sd_stream:
-        out["clear_frac"] = arr("clear_frac").reshape(())
-    if "calib_counts" in sd_stream:
-        out["calib_counts"] = arr("calib_counts")
-    if _ckpt_int(sd_stream, "calib_kept") >= 0:
-        out["calib_kept"] = np.array(_ckpt_int(sd_stream, "calib_kept"), dtype=np.int64)
-    return out
 
 
 class StreamFleet(_StreamCore):
@@ -3977,20 +3429,30 @@ class StreamFleet(_StreamCore):
         return _episodes(self.events[int(u)], self.top_m, self.events_cfg["cap"])
 
     # save and resume: a fleet stream cut by a save and a load writes the bits of the uninterrupted one
-    def _config(self) -> dict:
-        return {"units": self.units, "n": self.n, "w": self.w, "chunk": self.chunk, "top_m": self.top_m,
-                "log": 0 if self.log_ticks is None else self.log_ticks.shape[1], "with_gaps": int(self.with_gaps),
-                "recal": self.recal, "exclude_alarms": int(self.exclude_alarms), "recal_every": self.recal_every,
-                "recal_min": self.recal_min, "calib": self.calib, "wide": int(self.wide),
-                "prep": int(self.prep is not None), "prep_down": 0 if self.prep is None else self.prep.down}
-
     def _expect(self, check_model: bool = True) -> dict:
         """fleet_checkpoint_check's `expect` for this fleet: its model's shape and fingerprint, its units, prep and
         events, and the loaded library's ABI version and byte sizes."""
-        expect = _fleet_checkpoint_expect(self.model, self.prep, self.units, self.recal, check_model)
+        expect = _checkpoint_expect(self.model, self.prep, self.recal, check_model, units=self.units)
         expect["units"], expect["events"] = self.units, self.events_cfg
         expect["recal_threshold"] = self.recal_threshold
         return expect
+
+    def _pend_views(self) -> tuple:
+        """(the open groups [U, down, n] float64, their lengths [U, tiles] int32: one word per sensor tile of a unit)."""
+        return ops.fleet_prep_views(self.pend, self.units, self.n, self.prep.down)
+
+    def _ckpt_tensors(self) -> dict:
+        """Checkpoint key -> the device tensor (a view) that holds it, unit axis first; an option that is off has no
+        tensor and no key.  The lengths of the open groups are not in it: a file holds one per unit, the device one per
+        sensor tile (_state_dict, load_state_dict, load_unit)."""
+        held = {"state": self.state.view(torch.uint8).view(self.units, -1), "med_iqr": self.med_iqr,
+                "threshold": self.threshold, "log_ticks": self.log_ticks, "log_sensors": self.log_sensors,
+                "gaps": self.gaps, "ring_keys": self.ring_keys, "ring_keep": self.ring_keep,
+                "recal_counts": self.recal_counts, "recal_kept": self.recal_kept, "events": self.events,
+                "clear": self.clear, "clear_frac": None if self.recal_threshold is None else self.clear_frac,
+                "calib_counts": self.calib_counts,
+                "pending_ticks": None if self.prep is None else self._pend_views()[0]}
+        return {k: t for k, t in held.items() if t is not None}
 
     def state_dict(self) -> dict:
         """Everything a continuation of this fleet depends on, as a flat dict of numpy arrays (numpy.savez writes it,
@@ -4011,40 +3473,11 @@ class StreamFleet(_StreamCore):
         """state_dict() of the units `sel` as a fleet of that many units (all of them: the fleet's own; one: what
         unit_state_dict converts), the host counters and the configuration the fleet's."""
         lib = _lib.load()
-        n, m = self.n, self.top_m
         U = len(range(*sel.indices(self.units)))
-        cfg = dict(self._config(), units=U)
-        dev = {"state": self.state.view(torch.uint8).view(self.units, -1)[sel], "med_iqr": self.med_iqr[sel],
-               "threshold": self.threshold[sel]}
-        if self.log_ticks is not None:
-            dev["log_ticks"], dev["log_sensors"] = self.log_ticks[sel], self.log_sensors[sel]
-        if self.with_gaps:
-            dev["gaps"] = self.gaps[sel]
-        if self.recal:
-            dev["ring_keys"], dev["ring_keep"] = self.ring_keys[sel], self.ring_keep[sel]
-            dev["recal_counts"] = self.recal_counts[sel]
-            if self.recal_kept is not None:
-                dev["recal_kept"] = self.recal_kept[sel]
-        if self.events is not None:
-            dev["events"], dev["clear"] = self.events[sel], self.clear[sel]
-        if self.recal_threshold is not None and self.clear_frac is not None:
-            dev["clear_frac"] = self.clear_frac[sel]
-        if self.calib_counts is not None:
-            dev["calib_counts"] = self.calib_counts[sel]
+        dev = {k: t[sel] for k, t in self._ckpt_tensors().items()}
         if self.prep is not None:
-            ticks, pending = ops.fleet_prep_views(self.pend, self.units, n, self.prep.down)
-            dev["pending_ticks"], dev["pending"] = ticks[sel], pending[sel]
-        weights = self.model.state_dict()
-        names = sorted(weights)
-        host = _host_copies(list(dev.values()) + [weights[k] for k in names])
-        torch.cuda.current_stream().synchronize()
-        sd = {k: t.numpy() for k, t in zip(dev, host)}
-        if self.recal_threshold is not None:
-            sd["recal_threshold"] = np.array(self.recal_threshold, dtype=np.float64)
-        if self.log_ticks is None:
-            sd["log_ticks"], sd["log_sensors"] = np.zeros((U, 0), np.int64), np.zeros((U, 0, m), np.int32)
-        if self.events is not None:
-            sd["events_cfg"] = np.array([self.events_cfg[k] for k in _EVENTS_FIELDS], dtype=np.int64)
+            dev["pending"] = self._pend_views()[1][sel]
+        sd, fingerprint = self._ckpt_read(dev)
         if self.calib_kept is not None:
             sd["calib_kept"] = torch.as_tensor(self.calib_kept, dtype=torch.int64).reshape(self.units)[sel].numpy().copy()
         if self.prep is not None:
@@ -4052,14 +3485,10 @@ class StreamFleet(_StreamCore):
             assert (tiles == tiles[:, :1]).all(), "the pending counts of a unit's sensor tiles disagree"
             sd["pending"] = np.ascontiguousarray(tiles[:, 0])
         ints = {"format": FLEET_CHECKPOINT_FORMAT, "abi": lib.gdn_abi_version(),
-                "state_bytes": lib.gdn_stream_state_bytes(n, self.w),
-                "calib_bytes": lib.gdn_fleet_calib_bytes(U, n, self.recal) if self.recal else 0,
+                "state_bytes": lib.gdn_stream_state_bytes(self.n, self.w),
+                "calib_bytes": lib.gdn_fleet_calib_bytes(U, self.n, self.recal) if self.recal else 0,
                 "handed": self._handed, "raw_handed": self._raw_handed, "recals": self.recals}
-        ints.update({k: v for k, v in cfg.items() if k != "calib"})
-        sd.update({k: np.array(int(ints[k]), dtype=np.int64) for k in _FLEET_CKPT_INTS})
-        sd["calib"] = np.array(self.calib)
-        sd["model_sha256"] = np.array(_fingerprint(names, host[len(dev):]))
-        return sd
+        return self._ckpt_finish(sd, ints, _FLEET_CKPT_INTS, dict(self._config(), units=U), fingerprint)
 
     def load_state_dict(self, sd, check_model: bool = True) -> None:
         """Take the fleet stream of `sd` (state_dict()'s dict, or a file's) up where it was saved.  `sd` is checked first
@@ -4068,43 +3497,14 @@ class StreamFleet(_StreamCore):
         allocations this fleet already has, so the pointers a later capture records are the ones it always had.  A
         unit's pending count goes to every sensor tile's word.  Afterwards the last push is empty."""
         fleet_checkpoint_check(sd, self._expect(check_model))
-        cfg = fleet_checkpoint_config(sd)
-        for k, mine in self._config().items():
-            if cfg[k] != mine:
-                raise ValueError(f"{_FLEET_CKPT}: {k} = {cfg[k]!r}, this fleet was built with {k} = {mine!r}")
-        for full in (self._full, *self._prep_full.values()):
-            full.drop()
-
-        def host(key):
-            return torch.from_numpy(np.array(sd[key]))      # (a copy: numpy.load may hand out read-only arrays)
-        self.state.view(torch.uint8).view(self.units, -1).copy_(host("state"))
-        self.med_iqr.copy_(host("med_iqr"))
-        self.threshold.copy_(host("threshold"))
-        if self.log_ticks is not None:
-            self.log_ticks.copy_(host("log_ticks"))
-            self.log_sensors.copy_(host("log_sensors"))
-        if self.with_gaps:
-            self.gaps.copy_(host("gaps"))
-        if self.recal:
-            self.ring_keys.copy_(host("ring_keys"))
-            self.ring_keep.copy_(host("ring_keep"))
-            self.recal_counts.copy_(host("recal_counts"))
-            if self.recal_kept is not None:
-                self.recal_kept.copy_(host("recal_kept"))
-        if self.events is not None:
-            self.events.copy_(host("events"))
-            self.clear.copy_(host("clear"))
-        # the fractions behind the clear levels: the file's, else (at their next use) those of the levels just loaded
-        self.clear_frac = host("clear_frac").to(self.state.device) if "clear_frac" in sd else None
+        self._ckpt_same_config(fleet_checkpoint_config(sd), _FLEET_CKPT, "fleet")
+        host = self._ckpt_fill(sd)
         if self.prep is not None:
-            ticks, pending = ops.fleet_prep_views(self.pend, self.units, self.n, self.prep.down)
-            ticks.copy_(host("pending_ticks"))
-            pending.copy_(host("pending").view(-1, 1).expand(-1, pending.shape[1]))
-        self.calib_counts = host("calib_counts").to(self.state.device) if "calib_counts" in sd else None
+            words = self._pend_views()[1]
+            words.copy_(host("pending").view(-1, 1).expand(-1, words.shape[1]))
         self.calib_kept = host("calib_kept") if "calib_kept" in sd else None
         self._handed, self.recals = _ckpt_int(sd, "handed", _FLEET_CKPT), _ckpt_int(sd, "recals", _FLEET_CKPT)
         self._raw_handed = _ckpt_int(sd, "raw_handed", _FLEET_CKPT)
-        self._last = 0
 
     def save(self, path: str) -> None:
         """state_dict() as one .npz at exactly `path` (write_stream_checkpoint: a temporary file beside it, then
@@ -4123,7 +3523,7 @@ class StreamFleet(_StreamCore):
         units, R = _ckpt_int(sd, "units", _FLEET_CKPT), _ckpt_int(sd, "recal", _FLEET_CKPT)
         if units < 1 or R < 0:
             raise ValueError(f"{_FLEET_CKPT}: units = {units}, recal = {R}: at least one unit, no negative ring")
-        fleet_checkpoint_check(sd, _fleet_checkpoint_expect(model, prep, units, R, check_model))
+        fleet_checkpoint_check(sd, _checkpoint_expect(model, prep, R, check_model, units=units))
         cfg = fleet_checkpoint_config(sd)
         events = fleet_checkpoint_events(sd)                # (None: the file has no episode tables, nor has the fleet)
         if events is not None:
@@ -4194,36 +3594,19 @@ class StreamFleet(_StreamCore):
         sha = expect["model"] if check_model else _ckpt_str(sd, "model_sha256")
         unit = stream_to_fleet_unit(sd, self._config_dict(sha))
         stream_checkpoint_check(sd, expect)
-        dev = self.state.device
 
-        def put(dst, key):
-            dst.copy_(torch.from_numpy(np.array(unit[key])))         # (a copy: numpy.load may hand out read-only arrays)
-        put(self.state.view(torch.uint8).view(self.units, -1)[u], "state")
-        put(self.med_iqr[u], "med_iqr")
-        put(self.threshold[u], "threshold")
-        if self.log_ticks is not None:
-            put(self.log_ticks[u], "log_ticks")
-            put(self.log_sensors[u], "log_sensors")
-        if self.with_gaps:
-            put(self.gaps[u], "gaps")
-        if self.recal:
-            put(self.ring_keys[u], "ring_keys")
-            put(self.ring_keep[u], "ring_keep")
-            put(self.recal_counts[u], "recal_counts")
-            if self.recal_kept is not None:
-                put(self.recal_kept[u], "recal_kept")
-        if self.events is not None:
-            put(self.events[u], "events")
-            put(self.clear[u], "clear")
-            self._clear_frac_unit(u, torch.from_numpy(np.array(unit["clear_frac"])).to(dev) if "clear_frac" in unit
-                                  else None)
+        def host(key):
+            return torch.from_numpy(np.array(unit[key]))             # (a copy: numpy.load may hand out read-only arrays)
+        held = self._ckpt_tensors()
+        held.pop("clear_frac", None)                                 # (it may not exist yet: _clear_frac_unit below)
         if self.prep is not None:
-            ticks, pending = ops.fleet_prep_views(self.pend, self.units, self.n, self.prep.down)
             p = int(unit["pending"])
-            put(ticks[u, :p], "pending_ticks")
-            pending[u].fill_(p)
-        if self.calib_counts is not None and "calib_counts" in unit:
-            put(self.calib_counts[u], "calib_counts")
+            held.pop("pending_ticks")[u, :p].copy_(host("pending_ticks"))    # the rows of the open group only
+            self._pend_views()[1][u].fill_(p)
+        for k, t in held.items():
+            if k in unit:                                            # (calib_counts: only a detector that has them)
+                t[u].copy_(host(k))
+        self._clear_frac_unit(u, host("clear_frac").to(self.state.device) if "clear_frac" in unit else None)
         if self.calib_kept is not None and "calib_kept" in unit:
             self.calib_kept[u] = int(unit["calib_kept"])
         self.counts[u] = 0
